@@ -13,7 +13,15 @@ i.e. the coarse levels, the transfers, the bottom solve and the norm are all
 inside the time but only fine-grid updates are counted.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--level L] [--dtype f64|f32|mixed]
-                    [--smoother jacobi|rbgs] [--mu1 A --mu2 B] [--no-cpu-baseline]
+                    [--smoother jacobi|rbgs] [--mu1 A --mu2 B] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the line (the headline, `ms_per_step`, the
+roofline and phase split of those same steps).  --full adds everything that takes runs of its own: the
+solve to 1e-8, the first five cycles from a random guess, the profiling-off handle, the single-sweep
+roofline, the reference problem's FMG solve and the CPU baselines.
+--dump-outputs DIR (N = 1): after the timed steps, DIR/residual_history.npy (float64, the history the
+timed solve returned) and DIR/solution_sample.npy (the finest-level iterate after the last step, in its
+own precision: every point when n^2 <= 2^22, else a fixed seeded sample of 2^22 draws, row-major order).
 
 N = 1 : one process, libmgx (C-ABI) through ctypes, HIP events for the roofline.
 N > 1 : one process per GPU (ranks from torch.distributed.run or from this script's own launcher;
@@ -68,9 +76,19 @@ def parse():
     p.add_argument("--arith", choices=["fma", "separate"], default="fma",
                    help="rounding of the Jacobi update (mgx_config.arith): fma = v' = fma(c1, nb, fma(c0, v, c1 b)), "
                         "separate = the reference's five library calls as five roundings (PS:138-142)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beyond the headline (solve to 1e-8, profiling off, single-sweep roofline, "
+                        "reference FMG problem, CPU baselines)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the timed steps computed as DIR/<name>.npy (single GPU)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     p.add_argument("--cpu-level", type=int, default=13, help="grid level of the bounded CPU-baseline sample")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus > 1:
+        p.error("--dump-outputs is implemented for --gpus 1 only")
+    return args
 
 
 DT = {"f32": 0, "f64": 1, "mixed": 2}
@@ -169,20 +187,21 @@ def run_single(args):
     # synthetic input, generated on the device: resident in HBM before any timing
     mg.fill_rhs(1, 0.0)               # b = h^2 8 pi^2 sin(2 pi x) sin(2 pi y)
     mg.fill_guess_random(12345)       # u0 ~ U(-1,1)
-    # ---- the "V-cycles to 1e-8" half of the metric (untimed here) ----
     mg.solve(tol=0.0, max_cycles=1)   # (graph capture, code objects, clocks: not part of a solve's own time)
-    mg.fill_guess_random(12345)
-    st0, hist0 = mg.solve(tol=1e-8, max_cycles=60)
-    cycles_to_tol = st0.cycles if st0.converged else None
-    solve_seconds = st0.seconds
-    # the same cycles on an iterate that is still far from converged: the first five from a fresh random guess
-    # (the K timed steps below mostly run on an iterate already at the rounding floor; same kernels, same bytes)
-    mg.fill_guess_random(54321)
-    mg.synchronize()
-    t0 = time.perf_counter()
-    st5, _ = mg.solve(tol=0.0, max_cycles=5)
-    mg.synchronize()
-    first5_ms = (time.perf_counter() - t0) / 5 * 1e3
+    if args.full:
+        # ---- the "V-cycles to 1e-8" half of the metric (untimed here) ----
+        mg.fill_guess_random(12345)
+        st0, hist0 = mg.solve(tol=1e-8, max_cycles=60)
+        cycles_to_tol = st0.cycles if st0.converged else None
+        solve_seconds = st0.seconds
+        # the same cycles on an iterate that is still far from converged: the first five from a fresh random guess
+        # (the K timed steps below mostly run on an iterate already at the rounding floor; same kernels, same bytes)
+        mg.fill_guess_random(54321)
+        mg.synchronize()
+        t0 = time.perf_counter()
+        st5, _ = mg.solve(tol=0.0, max_cycles=5)
+        mg.synchronize()
+        first5_ms = (time.perf_counter() - t0) / 5 * 1e3
     # ---- warmup + timed steps on a fresh random guess ----
     mg.fill_guess_random(12345)
     if args.warmup > 0:
@@ -252,11 +271,7 @@ def run_single(args):
             "smoother": args.smoother, "arith": args.arith, "step": "one V-cycle + residual norm (mgx_solve loop body)",
             "parallelism": "1 GPU",
         },
-        "vcycles_to_1e-8": cycles_to_tol,
-        "seconds_to_1e-8": solve_seconds,
-        "ms_per_step_first_5_cycles_from_a_random_guess": first5_ms,      # incl. the initial residual norm (one more pass)
         "runtime_libs": pkg.runtime_libs(),
-        "residual_history_to_1e-8": [float(x) for x in hist0],
         "roofline": {
             "bound": "hbm",
             "kernel": kernel,
@@ -286,7 +301,37 @@ def run_single(args):
             "coarse_levels": prof["ms"][4] / args.steps,
         },
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, mg, hist)
     mg.close()
+    if args.full:
+        out.update({
+            "vcycles_to_1e-8": cycles_to_tol,
+            "seconds_to_1e-8": solve_seconds,
+            "ms_per_step_first_5_cycles_from_a_random_guess": first5_ms,  # incl. the initial residual norm (one more pass)
+            "residual_history_to_1e-8": [float(x) for x in hist0],
+        })
+        full_legs(args, pkg, cfg, out, es, n, tname)
+    emit(out)
+
+
+def dump_outputs(path, mg, hist):
+    """What the timed solve hands its caller: the residual history it returned and the finest-level
+    iterate after the last step (all of it up to 2^22 points, else a fixed seeded sample)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "residual_history.npy"), np.asarray(hist, dtype=np.float64))
+    u = mg.get_solution().reshape(-1)
+    cap = 1 << 22
+    if u.size > cap:
+        u = u[np.unique(np.random.default_rng(0).integers(0, u.size, size=cap))]
+    np.save(os.path.join(path, "solution_sample.npy"), np.ascontiguousarray(u))
+
+
+def full_legs(args, pkg, cfg, out, es, n, tname):
+    """--full: the measurements beyond the headline, each on a handle of its own."""
+    L = args.level
     # ---- the same K steps the way mgx_solve runs them when nobody is timing phases (cfg.profile = 0: the whole cycle and its
     # norm replayed from ONE hipGraph, no events, no eager launches).  Informational: `value` above stays the number of the
     # instrumented region the roofline figures come from.
@@ -359,7 +404,6 @@ def run_single(args):
         main, extra = cpu_baseline(args)
         out["cpu_baseline"] = main
         out["cpu_baseline_reference_shaped"] = extra
-    emit(out)
 
 
 def free_port():

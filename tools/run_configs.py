@@ -33,7 +33,7 @@ def main():
           "cycles, s | smoother G upd/s | 1-sweep frac |")
     print("|---|---|---|---|---|---|---|---|---|")
     for name, flags in ROWS:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + flags.split()
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + flags.split()
         if "--steps" not in flags:
             cmd += ["--steps", "10", "--warmup", "2"]
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
