@@ -307,7 +307,9 @@ MGX_API int mgx_slab_rbgs(const mgx_slab* s, void* u, const void* b, void* tmp,
  * and with coarse_e the coarse rows around them.
  * zero_in != 0 : the input iterate is known to be all zero (PS:613: the guess of a coarse-grid correction) and
  *                is NOT read - nobody has to write those zeros first; u is then scratch for the passes' ping-pong.
- *                Not with coarse_e; MGX_ERR_INVALID when the first pass cannot synthesise its input (mu = 1). */
+ *                Not with coarse_e; MGX_ERR_INVALID when the first pass cannot synthesise its input (mu = 1).
+ * smoother: MGX_SMOOTHER_JACOBI or MGX_SMOOTHER_RBGS; restrict_mode: MGX_RESTRICT_CONSISTENT or MGX_RESTRICT_FW16
+ * (the injection modes are single-GPU only) - any other value is MGX_ERR_INVALID. */
 MGX_API int mgx_slab_cycle(const mgx_slab* f, void* u, const void* b, void* tmp,
                            int row_lo, int row_hi, int mu, double omega, int smoother,
                            const mgx_slab* c, const void* coarse_e, void* coarse_b,
@@ -315,7 +317,8 @@ MGX_API int mgx_slab_cycle(const mgx_slab* f, void* u, const void* b, void* tmp,
                            double* scratch, double* sum_dev, int* result_in_tmp, void* stream);
 /* fused residual + restriction (PS:604-611) of fine slab `f` into coarse slab
  * `c`, coarse local rows [crow_lo,crow_hi); zero_u (may be NULL) is the coarse
- * solution slab to zero on the same rows (PS:613). */
+ * solution slab to zero on the same rows (PS:613).  restrict_mode as for
+ * mgx_slab_cycle: CONSISTENT or FW16, anything else is MGX_ERR_INVALID. */
 MGX_API int mgx_slab_restrict(const mgx_slab* f, const void* u, const void* b,
                               const mgx_slab* c, void* cb, void* zero_u,
                               int crow_lo, int crow_hi, int restrict_mode, int fused, void* stream);

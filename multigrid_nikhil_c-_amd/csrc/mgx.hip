@@ -1878,6 +1878,9 @@ int mgx_slab_cycle(const mgx_slab* f, void* u, const void* b, void* tmp, int row
                    int restrict_mode, int zero_in, double* scratch, double* sum_dev, int* result_in_tmp, void* stream)
 {
     if (zero_in && coarse_e) return MGX_ERR_INVALID;
+    // the slab kernels implement Jacobi / red-black GS and the two weights of full weighting (include/mgx.h)
+    if (smoother != MGX_SMOOTHER_JACOBI && smoother != MGX_SMOOTHER_RBGS) return MGX_ERR_INVALID;
+    if (restrict_mode != MGX_RESTRICT_CONSISTENT && restrict_mode != MGX_RESTRICT_FW16) return MGX_ERR_INVALID;
     // the folded restriction wants its range to start on an odd global row (include/mgx.h) - whichever kernel serves the call
     if (coarse_b && !((std::max(row_lo + f->row0, 1)) & 1)) return MGX_ERR_INVALID;
     if (slab_check(f) || !u || !b || !tmp || mu < 1 || mu > 64 || row_hi <= row_lo) return MGX_ERR_INVALID;
@@ -1903,6 +1906,7 @@ int mgx_slab_restrict(const mgx_slab* f, const void* u, const void* b, const mgx
                       int crow_lo, int crow_hi, int restrict_mode, int fused, void* stream)
 {
     if (slab_check(f) || slab_check(c) || !b || !cb || (fused && !u)) return MGX_ERR_INVALID;
+    if (restrict_mode != MGX_RESTRICT_CONSISTENT && restrict_mode != MGX_RESTRICT_FW16) return MGX_ERR_INVALID;
     if (c->level != f->level - 1 || c->dtype != f->dtype) return MGX_ERR_INVALID;
     const int N = 1 << f->level;
     const long pitch = level_pitch(f->level, f->dtype), cpitch = level_pitch(c->level, c->dtype);

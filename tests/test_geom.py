@@ -1,6 +1,7 @@
 """Tile map of the deep folded passes (csrc/mgx_geom.hpp) checked on the CPU: the same two functions the launcher and the
 kernel use (cycle_geom_pick, cycle_tile_at), compiled with g++ into tests/geom_check.cpp."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -27,4 +28,8 @@ def test_every_row_of_every_strip_is_covered_exactly_once(geom_check, env):
 def test_the_bench_grid_runs_in_one_round_of_paired_chunks(geom_check):
     out = subprocess.run([geom_check, "v"], capture_output=True, text=True, check=True).stdout
     line = next(l for l in out.splitlines() if l.startswith("N= 8192 rows     1.. 8192 K=10 POST=1"))
-    assert " tall " in line and "tall  0" not in line and "(1.00 rounds)" in line or "(0.9" in line, line
+    tall = int(re.search(r" tall +(\d+) ", line).group(1))
+    short = int(re.search(r" short +(\d+) ", line).group(1))
+    rounds = float(re.search(r"\(([0-9.]+) rounds\)", line).group(1))
+    # the paired form (tall and short chunks) and at most one round of resident workgroups
+    assert tall > 0 and short > 0 and rounds <= 1.0, line

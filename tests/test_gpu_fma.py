@@ -79,9 +79,14 @@ def test_history_matches_the_oracle_fma_mode_and_the_default_mode(pkg, po, cfg, 
     if cfg.get("dtype", 1) == 1:
         assert hist_close(h, h_sep, HIST_TOL, noise_floor(u_ref)), (h, h_sep)
     else:
-        # mixed precision: the inner cycle is fp32, whose residuals sit on the float rounding floor (D11) - two
-        # roundings of it differ at float, not double, precision; the outer iteration converges alike
+        # mixed precision: the two rounding modes are two different iterations, not one iteration rounded twice.
+        # The oracle's own modes (L10, sine-transform bottom, zero guess, tol 1e-8) differ per cycle by 1.7 % (constant
+        # rhs) and 7.5 % (sine rhs) for FMG V(2,1), by 1.7 % and 0.11 % for V(4,3), with the same cycle counts in
+        # every case: the gap is the algorithm's, not the kernel's, and the 1e-10 check above (FMA oracle) holds the
+        # kernels.  Here: the same cycle count, converged, and a history that really is not the separate mode's
+        # (the float FMA kernels ran)
         assert len(h) == len(h_sep) and h[-1] <= 1e-8 * h[0]
+        assert not np.allclose(h, h_sep, rtol=1e-10, atol=0), (h, h_sep)
 
 
 @pytest.mark.parametrize("dtype", [1, 0])

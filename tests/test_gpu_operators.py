@@ -252,3 +252,45 @@ def test_lds_tile_smoother_is_bit_identical(pkg, po, name, tile_k, monkeypatch):
             v[31, :] = v[32, :] = v[:, 31] = v[:, 32] = -2          # tile seams
             f[0, 0] = f[-1, -1] = 3
             assert exact(mg.jacobirelaxation(10, v, f, 7), orc(v, f, 7))
+
+
+# ---- the stand-alone smoother at the sizes whose passes the launcher sizes itself ---------------------------------
+# 4096^2 and 8192^2: the shallow K <= 4 passes in 48- and 96-row chunks (fuse_rows), the float 10-level passes with
+# launcher-sized chunks (fuse_rows_auto, N >= 2048) and the deep double ones (fuse_rows_deep); nothing above 2048^2
+# was compared with the oracle operator by operator
+BIG_LEVELS = (12, 13)
+
+
+def _big_inputs(level, dt, seed):
+    n = (1 << level) - 1
+    rng = np.random.default_rng(seed)
+    return rng.uniform(-1, 1, (n, n)).astype(dt), rng.uniform(-1, 1, (n, n)).astype(dt)
+
+
+@pytest.mark.parametrize("arith", ["separate", "fma"])
+@pytest.mark.parametrize("name", ["f64", "f32"])
+def test_jacobi_at_4096_and_8192_matches_oracle(pkg, po, name, arith):
+    dt, code, _ = DT[name]
+    ar = po.ARITH_FMA if arith == "fma" else po.ARITH_SEPARATE
+    with pkg.Multigrid(finest_level=13, coarsest_level=12, dtype=code, smoother=0, bottom=pkg.BOTTOM_SMOOTH,
+                       arith=pkg.ARITH_FMA if arith == "fma" else pkg.ARITH_SEPARATE) as mg:
+        for level in BIG_LEVELS:
+            v, f = _big_inputs(level, dt, 1100 + level)
+            ref, done = v, 0
+            for mu in (1, 2, 3, 4, 10):
+                ref = po.jacobi(ref, f, mu - done, arith=ar)        # the oracle's sweeps continue where they stopped
+                done = mu
+                assert exact(mg.jacobirelaxation(level, v, f, mu), ref), (name, arith, level, mu)
+            del v, f, ref
+
+
+@pytest.mark.parametrize("name", ["f64", "f32"])
+def test_rbgs_at_4096_and_8192_matches_oracle(pkg, po, name):
+    dt, code, _ = DT[name]
+    with pkg.Multigrid(finest_level=13, coarsest_level=12, dtype=code, smoother=1, bottom=pkg.BOTTOM_SMOOTH) as mg:
+        for level in BIG_LEVELS:
+            v, f = _big_inputs(level, dt, 1200 + level)
+            ref = po.rbgs(v, f, 1)
+            assert exact(mg.jacobirelaxation(level, v, f, 1), ref), (name, level, 1)
+            assert exact(mg.jacobirelaxation(level, v, f, 2), po.rbgs(ref, f, 1)), (name, level, 2)
+            del v, f, ref

@@ -11,6 +11,8 @@ pytestmark = pytest.mark.gpu
 
 import hipmem as hm      # device buffers on the HIP runtime libmgx is linked against (see hipmem.py)
 
+MGX_ERR_INVALID = 1      # include/mgx.h
+
 
 def grid_from_interior(pkg, a, level, dt):
     """padded device grid (rows 0..N, level pitch) from an interior array"""
@@ -133,6 +135,49 @@ def test_slab_argument_validation(pkg):
     assert L.mgx_slab_rbgs(C.byref(s), t.data_ptr(), t.data_ptr(), t.data_ptr(), 1, 9, 1, 0, C.byref(flag), None) != 0
     assert L.mgx_slab_jacobi(C.byref(s), t.data_ptr(), t.data_ptr(), t.data_ptr(), 1, 9, 1, 0.6, 0, C.byref(flag), None) == 0
     hm.synchronize()
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+def test_slab_entry_points_refuse_other_smoothers_and_restrictions(pkg, dt):
+    """mgx_slab_cycle and mgx_slab_restrict implement Jacobi / red-black GS and the two full-weighting weights only:
+    an injection mode (published in the same enum), an out-of-range mode or smoother is MGX_ERR_INVALID - not a
+    quarter-weight restriction or a Jacobi sweep.  The buffers are whole, correctly sized grids, and the same calls
+    with valid values succeed."""
+    L = pkg.lib()
+    level = 7
+    N, NC = 1 << level, 1 << (level - 1)
+    code = pkg.DTYPE_F64 if dt == np.float64 else pkg.DTYPE_F32
+    rng = np.random.default_rng(13)
+    U = grid_from_interior(pkg, rng.uniform(-1, 1, (N - 1, N - 1)).astype(dt), level, dt)
+    B = grid_from_interior(pkg, rng.uniform(-1, 1, (N - 1, N - 1)).astype(dt), level, dt)
+    E = grid_from_interior(pkg, np.zeros((NC - 1, NC - 1), dt), level - 1, dt)
+    tmp, cb = hm.zeros_like(U), hm.zeros_like(E)
+    fs = pkg.Slab(level=level, dtype=code, rows=N + 1, row0=0)
+    cs = pkg.Slab(level=level - 1, dtype=code, rows=NC + 1, row0=0)
+    flag = C.c_int()
+
+    def cycle(smoother, mode):
+        # 3 sweeps on rows 1..N-1, residual restricted into coarse rows 1..NC-1
+        st = L.mgx_slab_cycle(C.byref(fs), U.data_ptr(), B.data_ptr(), tmp.data_ptr(), 1, N, 3, 2.0 / 3.0, smoother,
+                              C.byref(cs), None, cb.data_ptr(), 1, NC, mode, 0, None, None, C.byref(flag), None)
+        hm.synchronize()
+        return st
+
+    def restrict(mode):
+        st = L.mgx_slab_restrict(C.byref(fs), U.data_ptr(), B.data_ptr(), C.byref(cs), cb.data_ptr(), None, 1, NC, mode, 1, None)
+        hm.synchronize()
+        return st
+
+    bad_modes = (-1, pkg.RESTRICT_INJECT, pkg.RESTRICT_INJECT4, 7)
+    for mode in bad_modes:
+        assert restrict(mode) == MGX_ERR_INVALID, mode
+        assert cycle(pkg.SMOOTHER_JACOBI, mode) == MGX_ERR_INVALID, mode
+    for smoother in (-1, 2):
+        assert cycle(smoother, pkg.RESTRICT_CONSISTENT) == MGX_ERR_INVALID, smoother
+    for mode in (pkg.RESTRICT_CONSISTENT, pkg.RESTRICT_FW16):
+        assert restrict(mode) == 0, mode
+        for smoother in (pkg.SMOOTHER_JACOBI, pkg.SMOOTHER_RBGS):
+            assert cycle(smoother, mode) == 0, (smoother, mode)
 
 
 # path: "tile" = the register-tile kernel (what a range this small gets), "march" = the marching passes
