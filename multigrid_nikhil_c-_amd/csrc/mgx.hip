@@ -271,27 +271,21 @@ int copy_out(mgx_solver* s, Level& l, const void* src_grid, void* dst, size_t co
 // ---- operators on the working hierarchy -----------------------------------------------
 inline bool tile_level(const mgx_solver* s, const Level& l) { return s->fuse.tile_max_n > 0 && l.N <= s->fuse.tile_max_n; }
 
-template <typename T>
 void smooth_t(mgx_solver* s, Level& l, int mu)
 {
-    int parity = 0, launches = 0;
-    if (tile_level(s, l)) {
-        FoldArgs fa;
-        const int rc = s->cfg.smoother == MGX_SMOOTHER_RBGS
-            ? smooth_tiled<T, 1, 0>((T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, mu, s->cfg.omega, s->fuse.tile_k, fa, false, 0, false, s->stream, &launches)
-            : (s->fuse.arith
-               ? smooth_tiled<T, 0, 1>((T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, mu, s->cfg.omega, s->fuse.tile_k, fa, false, 0, false, s->stream, &launches)
-               : smooth_tiled<T, 0, 0>((T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, mu, s->cfg.omega, s->fuse.tile_k, fa, false, 0, false, s->stream, &launches));
-        if (rc >= 0) {
-            s->last_smooth_launches = launches;
-            if (launches & 1) std::swap(l.u, l.tmp);
-            return;
-        }
-    }
-    (void)smooth_block<T>(s->cfg.smoother, (T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, l.rows, 1, l.N, mu,
-                          s->cfg.omega, false, 1, l.N, 0, s->rows_per_chunk, s->fuse, s->stream, &parity, &launches);
-    s->last_smooth_launches = launches;
-    if (parity) std::swap(l.u, l.tmp);
+    with_kernel_set(l.f64, s->cfg.smoother, s->fuse.arith, [&](auto k) {
+        using K = decltype(k);
+        using T = typename K::T;
+        int parity = 0, launches = 0;
+        if (tile_level(s, l) && smooth_tiled<T, K::SM, K::AR>((T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, mu, s->cfg.omega,
+                                                              s->fuse.tile_k, FoldArgs(), false, 0, false, s->stream, &launches) >= 0)
+            parity = launches & 1;
+        else
+            (void)smooth_block<T>(s->cfg.smoother, (T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, l.rows, 1, l.N, mu,
+                                  s->cfg.omega, false, 1, l.N, 0, s->rows_per_chunk, s->fuse, s->stream, &parity, &launches);
+        s->last_smooth_launches = launches;
+        if (parity) std::swap(l.u, l.tmp);
+    });
 }
 
 // ---- general per-level operators (cfg.op = MGX_OPERATOR_STENCIL5; kernels in mgx_var.hpp) ---------------
@@ -376,15 +370,7 @@ void residual_var_t(mgx_solver* s, const Level& l, const void* u, const void* b,
 // (0.56 ms) - a 10-level pass now costs less than two 5-level ones, so V(10,10) is planned as ONE
 // pass per block ([10]: 1.93 ms per cycle against 2.35 as [5,5], 2.28 as [8,2], 2.35 as [6,4]).
 // float (no LDS variants, packed arithmetic): 6: 1.34, 8: 1.53; red-black Gauss-Seidel (levels =
-// 2 x sweeps) 6: 1.1, 8: 1.3, 10: 2.4.  kcap: MGX_FOLD_KMAX / _BIG / _NOPOST / _GS still cap the depth.
-inline int fold_kcap(const FuseCfg& f, int smoother, int N, int post, bool f64)
-{
-    int k = N >= 8192 ? f.fold_kmax_big : f.fold_kmax;
-    if (post == 0) k = std::min(k, f.fold_kmax_nopost);
-    if (smoother == MGX_SMOOTHER_RBGS) k = std::min(k, env_int("MGX_FOLD_KMAX_GS", 10));
-    return k;
-}
-
+// 2 x sweeps) 6: 1.1, 8: 1.3, 10: 2.4.  MGX_FOLD_KMAX / _BIG / _NOPOST / _GS still cap the depth.
 inline double fold_pass_cost(int K, int smoother, int N, int post, bool f64, int arith)
 {
     const bool rbgs = (smoother == MGX_SMOOTHER_RBGS);
@@ -398,12 +384,39 @@ inline double fold_pass_cost(int K, int smoother, int N, int post, bool f64, int
     return 1.46;
 }
 
-// parts[] = sweeps per pass, deepest first (the last pass carries the residual stage, which is
-// what gets expensive with depth; a leading single sweep could not synthesise a zero input)
-inline int plan_folded(const FuseCfg& f, int smoother, int N, int mu, int post, bool f64, int* parts, bool pre = false)
+// The passes of a folded smoothing block of mu sweeps on a grid of N: parts[] = sweeps per pass, returns their
+// count.  pre: the first pass adds the correction; post: the last pass restricts the residual (1) or sums its
+// squares (2).  An explicit plan (FuseCfg::plan_pre / plan_post) wins when it fits; otherwise the DP over the
+// measured rates, deepest pass first (the last pass carries the residual stage, which is what gets expensive with
+// depth; a leading single sweep could not synthesise a zero input), capped at the folded kernels' depth.
+int fold_plan(const FuseCfg& f, int smoother, int N, bool f64, int mu, bool pre, int post, int* parts)
 {
-    const int per = (smoother == MGX_SMOOTHER_RBGS) ? 2 : 1;
-    const int smax = std::max(1, fold_kcap(f, smoother, N, post, f64) / per);
+    const bool rbgs = (smoother == MGX_SMOOTHER_RBGS);
+    const int per = rbgs ? 2 : 1;
+    const int* forced = nullptr;
+    int nf = 0;
+    if (!pre && post == 1) { forced = f.plan_pre; nf = f.n_pre; }
+    else if (pre) { forced = f.plan_post; nf = f.n_post; }
+    if (nf > 0 && N >= f.plan_min_n) {
+        int sum = 0;
+        bool ok = true;
+        for (int i = 0; i < nf; ++i) {
+            sum += forced[i];
+            const int K = per * forced[i];
+            const bool folded = (i == 0 && pre) || (i == nf - 1 && post != 0);
+            const int q = (i == nf - 1) ? post : 0;
+            ok = ok && K <= 10 && (folded ? cycle_k_supported(K, rbgs, f64, q, pre && i == 0, f.arith) : (K != 7 && K != 9 && (!rbgs || K % 2 == 0)));
+        }
+        if (ok && sum == mu) {
+            for (int i = 0; i < nf; ++i) parts[i] = forced[i];
+            return nf;
+        }
+    }
+    int kcap = N >= 8192 ? f.fold_kmax_big : f.fold_kmax;
+    if (post == 0) kcap = std::min(kcap, f.fold_kmax_nopost);
+    if (rbgs) kcap = std::min(kcap, env_int("MGX_FOLD_KMAX_GS", 10));
+    if (pre && post == 1) kcap = std::min(kcap, 8);         // correction and restriction may meet in one pass: at most 8 levels
+    const int smax = std::max(1, kcap / per);
     std::vector<double> best(mu + 1, 1e300);
     std::vector<int> pick(mu + 1, 1);
     best[0] = 0.0;
@@ -412,7 +425,7 @@ inline int plan_folded(const FuseCfg& f, int smoother, int N, int mu, int post, 
             const double c = fold_pass_cost(per * k, smoother, N, post, f64, f.arith);
             if (c < 0.0) continue;
             // a block done in ONE pass carries the correction AND the residual stage: some depths exist for either only
-            if (k == mu && m == mu && !cycle_k_supported(per * k, smoother == MGX_SMOOTHER_RBGS, f64, post, pre, f.arith)) continue;
+            if (k == mu && m == mu && !cycle_k_supported(per * k, rbgs, f64, post, pre, f.arith)) continue;
             const double t = best[m - k] + c + 1e-3;      // equal sums: fewer passes
             if (t < best[m] - 1e-12) { best[m] = t; pick[m] = k; }
         }
@@ -422,94 +435,104 @@ inline int plan_folded(const FuseCfg& f, int smoother, int N, int mu, int post, 
     return n;
 }
 
-// The passes (sweeps per pass) of a folded smoothing block: pre-smoothing = (pre false, post 1),
-// post-smoothing = (pre true, post 0 or 2).  An explicit plan wins when it fits; otherwise the
-// DP over the measured rates, capped at the folded kernels' depth.
-int fold_plan(const mgx_solver* s, const Level& l, int mu, bool pre, int post, int* parts)
-{
-    const bool rbgs = (s->cfg.smoother == MGX_SMOOTHER_RBGS);
-    const FuseCfg& f = s->fuse;
-    const int* forced = nullptr;
-    int nf = 0;
-    if (!pre && post == 1) { forced = f.plan_pre; nf = f.n_pre; }
-    else if (pre) { forced = f.plan_post; nf = f.n_post; }
-    if (nf > 0 && l.N >= f.plan_min_n) {
-        const int per = rbgs ? 2 : 1;
-        int sum = 0;
-        bool ok = true;
-        for (int i = 0; i < nf; ++i) {
-            sum += forced[i];
-            const int K = per * forced[i];
-            const bool folded = (i == 0 && pre) || (i == nf - 1 && post != 0);
-            const int q = (i == nf - 1) ? post : 0;
-            ok = ok && K <= 10 && (folded ? cycle_k_supported(K, rbgs, l.f64, q, pre && i == 0, f.arith) : (K != 7 && K != 9 && (!rbgs || K % 2 == 0)));
-        }
-        if (ok && sum == mu) {
-            for (int i = 0; i < nf; ++i) parts[i] = forced[i];
-            return nf;
-        }
-    }
-    return plan_folded(f, s->cfg.smoother, l.N, mu, post, l.f64, parts, pre);
-}
-
-// mu Jacobi sweeps on a whole level with the prolongation+correction applied while
-// loading (pre_e: coarse correction, may be null) and/or the residual restriction
-// (post = 1) or the residual norm (post = 2) produced by the last pass.
-// Returns false when this level / configuration is not eligible (caller then
-// uses the stand-alone kernels); on success *norm_blocks = partial sums written.
-
+// ---- a folded smoothing block ----------------------------------------------------------------------
+// mu sweeps on the local rows [row_lo, row_hi) of slab f with the cycle's transfers folded into the passes
+// (k_jacobi_cycle / k_tile_smooth on the window of rows the slab holds; a whole level is the slab row0 = 0,
+// rows = N + 1).  coarse_e (slab c, may be null): the first pass adds the prolonged correction while loading.
+// post 1: the last pass restricts the residual into coarse rows [crow_lo, crow_hi) of coarse_b and zeroes them
+// in coarse_zero (may be null); post 2: it writes per-block sums of r^2 to `partial`.  Local row numbers in,
+// global ones to the kernels.  Returns the number of partial sums written (0 unless post 2), < 0 when the block
+// cannot run as asked; *flips = launches made (the result is in tmp when odd).
 template <typename T, int SM, int AR>
-bool smooth_folded_t(mgx_solver* s, Level& l, int mu, const Level* coarse, bool pre, int post, int* launches,
-                     int* norm_blocks, bool zero_in)
+int fold_block(const FuseCfg& fc, long tile_points, const mgx_slab* f, T* u, const T* b, T* tmp, int row_lo, int row_hi,
+               int mu, double omega, const mgx_slab* c, const T* coarse_e, T* coarse_b, T* coarse_zero, int crow_lo,
+               int crow_hi, int restrict_mode, int zero_in, int post, double* partial, hipStream_t st, int* flips)
 {
     constexpr bool rbgs = (SM == 1);
     constexpr int per = rbgs ? 2 : 1;
+    const bool pre = (coarse_e != nullptr);
+    const int N = 1 << f->level;
+    const long pitch = level_pitch(f->level, f->dtype);
+    const int first = 1 - f->row0, last = N - f->row0;        // local unknown rows [first, last)
+    const JacobiCoef<T> jc = jacobi_coef<T>(omega);
     FoldArgs fa;
-    fa.restrict_mode = s->cfg.restrict_mode;
-    fa.partial = s->partial;
-    if (coarse) {
-        fa.cpitch = coarse->pitch; fa.coarse_e = coarse->u; fa.coarse_b = coarse->b;
-        // PS:613: zero the coarse guess here unless its first pre-smoothing pass synthesises it
-        fa.coarse_zero = (post == 1 && s->zero_in_level == coarse->L) ? nullptr : coarse->u;
+    fa.restrict_mode = restrict_mode;
+    fa.partial = partial;
+    fa.win.row_first = std::max(f->row0, 0);
+    fa.win.row_last = std::min(f->row0 + f->rows - 1, N);
+    fa.win.crow_first = 0; fa.win.crow_last = -1; fa.win.emit_lo = 0; fa.win.emit_hi = 0;
+    if (c) {
+        fa.cpitch = level_pitch(c->level, c->dtype);
+        fa.win.crow_first = std::max(c->row0, 0);
+        fa.win.crow_last = std::min(c->row0 + c->rows - 1, N / 2);
+        fa.win.emit_lo = std::max(c->row0 + crow_lo, 1);
+        fa.win.emit_hi = std::min(c->row0 + crow_hi, N / 2);
+        // base pointers moved back so that GLOBAL coarse rows index them (never dereferenced outside the window)
+        const long cback = (long)c->row0 * fa.cpitch;
+        if (coarse_e) fa.coarse_e = coarse_e - cback;
+        if (coarse_b) fa.coarse_b = coarse_b - cback;
+        if (coarse_zero) fa.coarse_zero = coarse_zero - cback;
     }
-    if (tile_level(s, l)) {
-        int flips = 0;
-        const int nb = smooth_tiled<T, SM, AR>((T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, mu, s->cfg.omega,
-                                           s->fuse.tile_k, fa, pre, post, zero_in, s->stream, &flips);
-        if (nb < 0) return false;
-        if (flips & 1) std::swap(l.u, l.tmp);
-        if (post == 2) *norm_blocks = nb;
-        *launches = flips;
-        return true;
+    const long back = (long)f->row0 * pitch;
+    // Register tiles (k_tile_smooth): the whole block in one launch of independent tiles, where a marching pass would be
+    // latency-bound - R + 2K row steps one after the other, however few rows (small levels; 2048^2 slabs of 256 rows at
+    // 8 GPUs, the edge bands of an overlapped exchange).  Same arithmetic in the same order: same bits.  Ranges of at
+    // most tile_points rows x N; a block deeper than one tile launch only on a range that needs no rows beyond it (a
+    // whole grid), since the tile launches do not widen their range for the ones that follow.
+    {
+        const int lo = std::max(std::max(row_lo, first), 1), hi = std::min(std::min(row_hi, last), f->rows - 1);
+        const bool whole = row_lo <= first && row_hi >= last;
+        if (fc.tile_max_n > 0 && hi > lo && (long)(hi - lo) * N <= tile_points && (per * mu <= fc.tile_k || whole)) {
+            fa.row_lo = lo + f->row0; fa.row_hi = hi + f->row0;
+            return smooth_tiled<T, SM, AR>(u - back, b - back, tmp - back, N, pitch, mu, omega, fc.tile_k, fa, pre, post,
+                                           zero_in != 0, st, flips);
+        }
     }
     int parts[64];
-    const int np = fold_plan(s, l, mu, pre, post, parts);
-    const T om = (T)s->cfg.omega;
-    const T c0 = (T)(1.0 - (double)om);
-    const T c1 = (T)((double)om / 4.0);
-    T* src = (T*)l.u; T* dst = (T*)l.tmp;
-    const T* b = (const T*)l.b;
+    const int np = fold_plan(fc, rbgs ? MGX_SMOOTHER_RBGS : MGX_SMOOTHER_JACOBI, N, sizeof(T) == 8, mu, pre, post, parts);
+    const int rpc = env_int("MGX_ROWS", 0);                    // rows per chunk of a single sweep (0: one wave per row)
+    T* src = u; T* dst = tmp;
+    int done = 0, blocks = 0;
     for (int p = 0; p < np; ++p) {
-        const bool first = (p == 0), last = (p == np - 1);
-        const bool P = pre && first;
-        const int Q = last ? post : 0;
-        const int K = per * parts[p];
-        const int R = fuse_rows(s->fuse, l.N, K, sizeof(T) == 8);
-        const int Rc = fuse_rows_auto(s->fuse, l.N, K, sizeof(T) == 8) ? -R : R;      // folded passes: sized by the launcher
-        fa.zero_in = (first && zero_in) ? 1 : 0;
-        int blocks = 0;
-        if (P && Q == 2) blocks = launch_cycle<T, 1, 2, SM, AR>(K, src, b, dst, fa, l.N, l.pitch, c0, c1, Rc, s->stream);
-        else if (P) blocks = launch_cycle<T, 1, 0, SM, AR>(K, src, b, dst, fa, l.N, l.pitch, c0, c1, Rc, s->stream);
-        else if (Q == 1) blocks = launch_cycle<T, 0, 1, SM, AR>(K, src, b, dst, fa, l.N, l.pitch, c0, c1, Rc, s->stream);
-        else if (Q == 2) blocks = launch_cycle<T, 0, 2, SM, AR>(K, src, b, dst, fa, l.N, l.pitch, c0, c1, Rc, s->stream);
-        else if (!rbgs && K == 1) (void)launch_jacobi<T>(src, b, dst, l.N, l.pitch, 1, l.N, s->cfg.omega, s->rows_per_chunk, s->stream, l.rows, AR);
-        else (void)launch_fused<T, SM, AR>(K, src, b, dst, l.N, l.pitch, 1, l.N, c0, c1, 0, l.N, 0, R, s->stream, l.rows, fa.zero_in);
-        if (Q == 2) *norm_blocks = blocks;
+        const int sw = parts[p], K = per * sw;
+        const bool P = pre && p == 0;
+        const int Q = (p == np - 1) ? post : 0;
+        fa.zero_in = (p == 0 && zero_in) ? 1 : 0;              // PS:613: the first pass synthesises the zero guess
+        // rows the later passes still consume; the norm / restriction stage of the last pass also
+        // needs the result one / two rows beyond its range (it recomputes those rows itself, from
+        // this pass's output)
+        const int ext = per * (mu - (done + sw)) + (p != np - 1 ? (post == 2 ? 1 : (post == 1 ? 2 : 0)) : 0);
+        // never beyond the unknown rows, and never the slab's first or last row unless it is a global
+        // boundary's neighbour: a row is updated from the rows above and below it, and the single-sweep
+        // kernel (k_jacobi_rows) reads them without asking whether they exist
+        const int lo = std::max(std::max(row_lo - ext, first), 1), hi = std::min(std::min(row_hi + ext, last), f->rows - 1);
+        if (hi > lo) {
+            const int R = fuse_rows(fc, N, K, sizeof(T) == 8, hi - lo);
+            if (P || Q) {
+                if (!cycle_k_supported(K, rbgs, sizeof(T) == 8, Q, P, AR)) return -1;
+                fa.row_lo = lo + f->row0; fa.row_hi = hi + f->row0;
+                const int Rc = fuse_rows_auto(fc, N, K, sizeof(T) == 8) ? -R : R;      // folded passes: sized by the launcher
+                const int rc = with_stages(P, Q, [&](auto s) {
+                    using S = decltype(s);
+                    if constexpr (S::PRE || S::POST)
+                        return launch_cycle<T, S::PRE, S::POST, SM, AR>(K, src - back, b - back, dst - back, fa, N, pitch, jc.c0, jc.c1, Rc, st);
+                    else
+                        return -1;
+                });
+                if (rc < 0) return -1;
+                if (Q == 2) blocks = rc;
+            } else if (!rbgs && K == 1) {
+                if (fa.zero_in) return -1;                     // a stand-alone single sweep reads its input
+                if (launch_jacobi<T>(src, b, dst, N, pitch, lo, hi, omega, rpc, st, f->rows, AR)) return -1;
+            } else if (!launch_fused<T, SM, AR>(K, src, b, dst, N, pitch, lo, hi, jc.c0, jc.c1, first - 1, last, f->row0 & 1, R, st, f->rows, fa.zero_in)) {
+                return -1;
+            }
+        }
         std::swap(src, dst);
+        done += sw;
     }
-    if (np & 1) std::swap(l.u, l.tmp);
-    *launches = np;
-    return true;
+    *flips = np;
+    return blocks;
 }
 
 // pre-check made before any launch (so a `false` never leaves a half-done block)
@@ -524,10 +547,9 @@ bool fold_eligible(const mgx_solver* s, const Level& l, int mu, bool pre = false
     const int per = rbgs ? 2 : 1;
     if (s->fuse.kmax < per) return false;
     int parts[64];
-    const int np = fold_plan(s, l, mu, pre, post, parts);
+    const int np = fold_plan(s->fuse, s->cfg.smoother, l.N, l.f64, mu, pre, post, parts);
     for (int p = 0; p < np; ++p)
         if (!cycle_k_supported(per * parts[p], rbgs, l.f64, p == np - 1 ? post : 0, pre && p == 0, s->fuse.arith)) return false;
-    // the norm partials of the folded pass must fit the reduction buffer
     return true;
 }
 
@@ -543,38 +565,46 @@ bool zero_in_ok(const mgx_solver* s, int level)
     if (tile_level(s, l)) return true;
     const bool rbgs = (s->cfg.smoother == MGX_SMOOTHER_RBGS);
     int parts[64];
-    const int np = fold_plan(s, l, mu, false, 1, parts);
+    const int np = fold_plan(s->fuse, s->cfg.smoother, l.N, l.f64, mu, false, 1, parts);
     return !(np >= 2 && !rbgs && parts[0] == 1);      // a leading plain single Jacobi sweep reads its input
 }
 
+// mu sweeps on a whole level with the prolongation+correction applied while loading (pre) and/or the
+// residual restriction (post = 1) or the residual norm (post = 2) produced by the last pass.  Returns
+// false when this level / configuration is not eligible (the caller then uses the stand-alone kernels).
 bool smooth_folded(mgx_solver* s, int level, int mu, bool pre, int post, bool zero_in = false)
 {
     Level& l = s->lv[level];
     if (!fold_eligible(s, l, mu, pre, post)) return false;
-    const Level* coarse = (pre || post == 1) ? &s->lv[level - 1] : nullptr;
     const bool fine = (level == s->cfg.finest_level);
     const bool rbgs = (s->cfg.smoother == MGX_SMOOTHER_RBGS);
-    const bool fma = s->fuse.arith != 0;
     // float: the 10-level pass with BOTH the correction stage and the norm stage does not fit its registers (mgx_launch.hpp,
     // cycle_k_supported) and a block of 10 would run as two passes of 5 (8192^2: 223 + 190 us); one 10-level pass without
     // the norm stage and the stand-alone norm kernel are 216 + ~110 us.  (The same for the restriction stage of the
     // separately rounded mode - 10 levels + the stand-alone residual / restriction instead of 8 + 2 - was measured and is
     // worse: mixed cycle 1.54 -> 1.72 ms, the stand-alone transfer alone is 0.15 ms.)
-    static const bool f32_norm_apart = env_int("MGX_F32_NORM_APART", 1) != 0;
-    if (!l.f64 && !rbgs && mu == 10 && l.N > s->fuse.tile_max_n && f32_norm_apart && post == 2 && pre &&
+    if (!l.f64 && !rbgs && mu == 10 && l.N > s->fuse.tile_max_n && post == 2 && pre &&
         cycle_k_supported(mu, false, false, 0, pre, s->fuse.arith) && !cycle_k_supported(mu, false, false, post, pre, s->fuse.arith))
         post = 0;
     {
         Prof p(s, fine ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, mu);
-        int launches = 0, nb = 0;
-        bool ok;
-        if (l.f64) ok = rbgs ? smooth_folded_t<double, 1, 0>(s, l, mu, coarse, pre, post, &launches, &nb, zero_in)
-                             : (fma ? smooth_folded_t<double, 0, 1>(s, l, mu, coarse, pre, post, &launches, &nb, zero_in)
-                                    : smooth_folded_t<double, 0, 0>(s, l, mu, coarse, pre, post, &launches, &nb, zero_in));
-        else ok = rbgs ? smooth_folded_t<float, 1, 0>(s, l, mu, coarse, pre, post, &launches, &nb, zero_in)
-                       : (fma ? smooth_folded_t<float, 0, 1>(s, l, mu, coarse, pre, post, &launches, &nb, zero_in)
-                              : smooth_folded_t<float, 0, 0>(s, l, mu, coarse, pre, post, &launches, &nb, zero_in));
-        if (!ok) return false;
+        // the whole level is the slab of all its rows, the level below it the coarse slab; the restriction stage zeroes
+        // the coarse guess (PS:613) unless that level's first pre-smoothing pass synthesises it
+        const Level& c = s->lv[level - 1];
+        const int dt = l.f64 ? MGX_DTYPE_F64 : MGX_DTYPE_F32;
+        const mgx_slab fs{level, dt, l.rows, 0, s->cfg.arith}, cs{level - 1, dt, c.rows, 0, s->cfg.arith};
+        void* czero = (post == 1 && s->zero_in_level == c.L) ? nullptr : c.u;
+        const long tile_points = (long)(s->fuse.tile_max_n - 1) * s->fuse.tile_max_n;      // whole levels of N <= tile_max_n
+        int launches = 0;
+        const int nb = with_kernel_set(l.f64, s->cfg.smoother, s->fuse.arith, [&](auto k) {
+            using K = decltype(k);
+            using T = typename K::T;
+            return fold_block<T, K::SM, K::AR>(s->fuse, tile_points, &fs, (T*)l.u, (const T*)l.b, (T*)l.tmp, 1, l.N, mu,
+                                               s->cfg.omega, &cs, pre ? (const T*)c.u : nullptr, post == 1 ? (T*)c.b : nullptr,
+                                               (T*)czero, 1, c.N, s->cfg.restrict_mode, zero_in, post, s->partial, s->stream, &launches);
+        });
+        if (nb < 0) return false;
+        if (launches & 1) std::swap(l.u, l.tmp);
         p.set(launches, mu);
         if (post == 2) s->norm_blocks_ready = nb;
     }
@@ -590,7 +620,7 @@ void smooth(mgx_solver* s, int level, int mu)
     const bool fine = (level == s->cfg.finest_level);
     Prof p(s, fine ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, mu);
     if (s->var) { if (l.f64) smooth_var_t<double>(s, l, mu); else smooth_var_t<float>(s, l, mu); }       // MF:75-96
-    else if (l.f64) smooth_t<double>(s, l, mu); else smooth_t<float>(s, l, mu);
+    else smooth_t(s, l, mu);
     p.set(s->last_smooth_launches, mu);
     if (fine) s->fine_updates += (double)mu * (double)(l.N - 1) * (double)(l.N - 1);
 }
@@ -1692,7 +1722,7 @@ int mgx_time_smoother(mgx_handle s, int sweeps, double* ms)
     Level& l = s->lv[s->cfg.finest_level];
     HIPCHK(s, hipEventRecord(a, s->stream));
     if (s->var) { if (l.f64) smooth_var_t<double>(s, l, sweeps); else smooth_var_t<float>(s, l, sweeps); }
-    else if (l.f64) smooth_t<double>(s, l, sweeps); else smooth_t<float>(s, l, sweeps);
+    else smooth_t(s, l, sweeps);
     HIPCHK(s, hipEventRecord(b, s->stream));
     HIPCHK(s, hipEventSynchronize(b));
     float f = 0.f;
@@ -1763,116 +1793,6 @@ int mgx_slab_rbgs(const mgx_slab* s, void* u, const void* b, void* tmp, int row_
     return slab_smooth(MGX_SMOOTHER_RBGS, s, u, b, tmp, row_lo, row_hi, mu, 1.0, shrink, result_in_tmp, stream);
 }
 
-} // extern "C"
-
-namespace {
-// mu sweeps on a slab with the cycle's transfers folded into the passes (k_jacobi_cycle on the
-// window of rows the slab holds).  Local row numbers in, global ones to the kernel.
-template <typename T, int SM, int AR>
-int slab_cycle_t(const mgx_slab* f, T* u, const T* b, T* tmp, int row_lo, int row_hi, int mu, double omega,
-                        const mgx_slab* c, const T* coarse_e, T* coarse_b, int crow_lo, int crow_hi, int restrict_mode, int zero_in,
-                        double* scratch, double* sum_dev, int* result_in_tmp, hipStream_t st)
-{
-    constexpr bool rbgs = (SM == 1);
-    constexpr int per = rbgs ? 2 : 1;
-    const int N = 1 << f->level;
-    const long pitch = level_pitch(f->level, f->dtype);
-    const int first = 1 - f->row0, last = N - f->row0;        // local unknown rows [first, last)
-    FuseCfg fc = fuse_cfg();
-    fc.arith = AR;
-    const int post = coarse_b ? 1 : (sum_dev ? 2 : 0);
-    if (coarse_e && coarse_b) {                  // correction and restriction may meet in one pass: at most 8 levels
-        fc.fold_kmax = std::min(fc.fold_kmax, 8); fc.fold_kmax_big = std::min(fc.fold_kmax_big, 8);
-    }
-    int parts[64];
-    const int np = plan_folded(fc, rbgs ? MGX_SMOOTHER_RBGS : MGX_SMOOTHER_JACOBI, N, mu, post, sizeof(T) == 8, parts, coarse_e != nullptr);
-    const T om = (T)omega;
-    const T c0 = (T)(1.0 - (double)om);
-    const T c1 = (T)((double)om / 4.0);
-    FoldArgs fa;
-    fa.restrict_mode = restrict_mode;
-    fa.partial = scratch;
-    fa.win.row_first = std::max(f->row0, 0);
-    fa.win.row_last = std::min(f->row0 + f->rows - 1, N);
-    fa.win.crow_first = 0; fa.win.crow_last = -1; fa.win.emit_lo = 0; fa.win.emit_hi = 0;
-    if (c) {
-        fa.cpitch = level_pitch(c->level, c->dtype);
-        fa.win.crow_first = std::max(c->row0, 0);
-        fa.win.crow_last = std::min(c->row0 + c->rows - 1, N / 2);
-        fa.win.emit_lo = std::max(c->row0 + crow_lo, 1);
-        fa.win.emit_hi = std::min(c->row0 + crow_hi, N / 2);
-        // base pointers moved back so that GLOBAL coarse rows index them (never dereferenced outside the window)
-        if (coarse_e) fa.coarse_e = coarse_e - (long)c->row0 * fa.cpitch;
-        if (coarse_b) fa.coarse_b = coarse_b - (long)c->row0 * fa.cpitch;
-    }
-    const long back = (long)f->row0 * pitch;
-    // Small slab ranges (2048^2 slabs of 256 rows at 8 GPUs, the edge bands of an overlapped exchange): a marching pass is
-    // latency-bound there - R + 2K row steps one after the other, however few rows - and the register-tile kernel does
-    // the whole block in one launch of independent tiles.  Same arithmetic in the same order: same bits.
-    {
-        const long tile_points = env_int("MGX_SLAB_TILE_POINTS", 1 << 20);          // (read per call: the parity tests switch it)
-        const int lo = std::max(std::max(row_lo, first), 1), hi = std::min(std::min(row_hi, last), f->rows - 1);
-        if (fc.tile_max_n > 0 && per * mu <= fc.tile_k && hi > lo && (long)(hi - lo) * N <= tile_points) {
-            FoldArgs ta = fa;
-            ta.row_lo = lo + f->row0; ta.row_hi = hi + f->row0;
-            int flips = 0;
-            const int nb = smooth_tiled<T, SM, AR>(u - back, b - back, tmp - back, N, pitch, mu, omega, fc.tile_k, ta, coarse_e != nullptr,
-                                                   post, zero_in != 0, st, &flips);
-            if (nb >= 0) {
-                if (post == 2) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, st, scratch, nb, sum_dev);
-                if (result_in_tmp) *result_in_tmp = flips & 1;
-                return hipGetLastError() == hipSuccess ? MGX_OK : MGX_ERR_HIP;
-            }
-        }
-    }
-    T* src = u; T* dst = tmp;
-    int done = 0, blocks = 0;
-    for (int p = 0; p < np; ++p) {
-        const int sw = parts[p], K = per * sw;
-        const bool P = coarse_e && p == 0;
-        const int Q = (p == np - 1) ? post : 0;
-        fa.zero_in = (p == 0 && zero_in) ? 1 : 0;              // PS:613: the first pass synthesises the zero guess
-        if (fa.zero_in && !rbgs && K == 1) return MGX_ERR_INVALID;      // (a stand-alone single sweep reads its input)
-        // rows the later passes still consume; the norm / restriction stage of the last pass also
-        // needs the result one / two rows beyond its range (it recomputes those rows itself, from
-        // this pass's output)
-        const int ext = per * (mu - (done + sw)) + (p != np - 1 ? (post == 2 ? 1 : (post == 1 ? 2 : 0)) : 0);
-        // never beyond the unknown rows, and never the slab's first or last row unless it is a global
-        // boundary's neighbour: a row is updated from the rows above and below it, and the single-sweep
-        // kernel (k_jacobi_rows) reads them without asking whether they exist
-        const int lo = std::max(std::max(row_lo - ext, first), 1), hi = std::min(std::min(row_hi + ext, last), f->rows - 1);
-        if (hi > lo) {
-            const int R = fuse_rows(fc, N, K, sizeof(T) == 8, hi - lo);
-            if (P || Q) {
-                if (!cycle_k_supported(K, rbgs, sizeof(T) == 8, Q, P, AR)) return MGX_ERR_INVALID;
-                fa.row_lo = lo + f->row0; fa.row_hi = hi + f->row0;
-                int rc;
-                const int Rc = fuse_rows_auto(fc, N, K, sizeof(T) == 8) ? -R : R;
-                if (P && Q == 2) rc = launch_cycle<T, 1, 2, SM, AR>(K, src - back, b - back, dst - back, fa, N, pitch, c0, c1, Rc, st);
-                else if (P && Q == 1) rc = launch_cycle<T, 1, 1, SM, AR>(K, src - back, b - back, dst - back, fa, N, pitch, c0, c1, Rc, st);
-                else if (P) rc = launch_cycle<T, 1, 0, SM, AR>(K, src - back, b - back, dst - back, fa, N, pitch, c0, c1, Rc, st);
-                else if (Q == 1) rc = launch_cycle<T, 0, 1, SM, AR>(K, src - back, b - back, dst - back, fa, N, pitch, c0, c1, Rc, st);
-                else rc = launch_cycle<T, 0, 2, SM, AR>(K, src - back, b - back, dst - back, fa, N, pitch, c0, c1, Rc, st);
-                if (rc < 0) return MGX_ERR_INVALID;
-                if (Q == 2) blocks = rc;
-            } else if (!rbgs && K == 1) {
-                if (launch_jacobi<T>(src, b, dst, N, pitch, lo, hi, omega, env_int("MGX_ROWS", 0), st, f->rows, AR)) return MGX_ERR_INVALID;
-            } else if (!launch_fused<T, SM, AR>(K, src, b, dst, N, pitch, lo, hi, c0, c1, first - 1, last, f->row0 & 1, R, st, f->rows, fa.zero_in)) {
-                return MGX_ERR_INVALID;
-            }
-        }
-        std::swap(src, dst);
-        done += sw;
-    }
-    if (post == 2) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, st, scratch, blocks, sum_dev);
-    if (result_in_tmp) *result_in_tmp = np & 1;
-    return hipGetLastError() == hipSuccess ? MGX_OK : MGX_ERR_HIP;
-}
-
-} // namespace
-
-extern "C" {
-
 int mgx_slab_cycle(const mgx_slab* f, void* u, const void* b, void* tmp, int row_lo, int row_hi, int mu, double omega,
                    int smoother, const mgx_slab* c, const void* coarse_e, void* coarse_b, int crow_lo, int crow_hi,
                    int restrict_mode, int zero_in, double* scratch, double* sum_dev, int* result_in_tmp, void* stream)
@@ -1890,16 +1810,23 @@ int mgx_slab_cycle(const mgx_slab* f, void* u, const void* b, void* tmp, int row
     if (coarse_b && (crow_lo < 0 || crow_hi > c->rows || crow_hi < crow_lo)) return MGX_ERR_INVALID;
     const int N = 1 << f->level;
     if (row_lo < 0 || row_hi > f->rows || row_lo + f->row0 < 1 || row_hi + f->row0 > N) return MGX_ERR_INVALID;
+    FuseCfg fc = fuse_cfg();
+    fc.arith = f->arith;
+    const long tile_points = env_int("MGX_SLAB_TILE_POINTS", 1 << 20);      // (read per call: the parity tests switch it)
+    const int post = coarse_b ? 1 : (sum_dev ? 2 : 0);
     hipStream_t st = (hipStream_t)stream;
-    const bool rbgs = (smoother == MGX_SMOOTHER_RBGS);
-#define MGX_SLAB_CYCLE(T, SM, AR)                                                                                       \
-    slab_cycle_t<T, SM, AR>(f, (T*)u, (const T*)b, (T*)tmp, row_lo, row_hi, mu, omega, c, (const T*)coarse_e, (T*)coarse_b, \
-                            crow_lo, crow_hi, restrict_mode, zero_in, scratch, sum_dev, result_in_tmp, st)
-    const bool fma = f->arith == MGX_ARITH_FMA;
-    if (f->dtype == MGX_DTYPE_F64)
-        return rbgs ? MGX_SLAB_CYCLE(double, 1, 0) : (fma ? MGX_SLAB_CYCLE(double, 0, 1) : MGX_SLAB_CYCLE(double, 0, 0));
-    return rbgs ? MGX_SLAB_CYCLE(float, 1, 0) : (fma ? MGX_SLAB_CYCLE(float, 0, 1) : MGX_SLAB_CYCLE(float, 0, 0));
-#undef MGX_SLAB_CYCLE
+    int flips = 0;
+    const int nb = with_kernel_set(f->dtype == MGX_DTYPE_F64, smoother, f->arith, [&](auto k) {
+        using K = decltype(k);
+        using T = typename K::T;
+        return fold_block<T, K::SM, K::AR>(fc, tile_points, f, (T*)u, (const T*)b, (T*)tmp, row_lo, row_hi, mu, omega, c,
+                                           (const T*)coarse_e, (T*)coarse_b, nullptr, crow_lo, crow_hi, restrict_mode, zero_in, post,
+                                           scratch, st, &flips);
+    });
+    if (nb < 0) return MGX_ERR_INVALID;
+    if (post == 2) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, st, scratch, nb, sum_dev);
+    if (result_in_tmp) *result_in_tmp = flips & 1;
+    return hipGetLastError() == hipSuccess ? MGX_OK : MGX_ERR_HIP;
 }
 
 int mgx_slab_restrict(const mgx_slab* f, const void* u, const void* b, const mgx_slab* c, void* cb, void* zero_u,

@@ -469,7 +469,7 @@ int dist_block_launches(const mgx_dist* d, int N, int mu, int post, bool pre = f
     int parts[64];
     FuseCfg fc = fuse_cfg();
     fc.arith = d->cfg.arith;
-    return plan_folded(fc, d->cfg.smoother, N, mu, post, d->f64, parts, pre);
+    return fold_plan(fc, d->cfg.smoother, N, d->f64, mu, pre, post, parts);
 }
 
 // the CYCLE operation of a plan on local rows [row_lo,row_hi) of its range, on `stream` (the whole

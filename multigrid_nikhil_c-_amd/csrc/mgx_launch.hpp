@@ -31,12 +31,34 @@ inline int env_int(const char* name, int dflt)
 struct FuseCfg {
     int kmax; int rows; int min_n; int fold_kmax; int fold_kmax_big; int tile_max_n; int tile_k; int fold_kmax_nopost;
     // explicit pass plans (sweeps per pass) for the pre- / post-smoothing block of grids with
-    // N >= plan_min_n: tuning knobs MGX_PLAN_PRE / MGX_PLAN_POST ("8,2"), MGX_PLAN_MIN_N
+    // N >= plan_min_n: tuning knobs MGX_PLAN_PRE / MGX_PLAN_POST ("8,2"), MGX_PLAN_MIN_N.  They apply to the
+    // folded blocks of whole levels and of slabs alike (fold_plan in mgx.hip)
     int plan_pre[8] = {0}; int n_pre = 0; int plan_post[8] = {0}; int n_post = 0; int plan_min_n = 8192;
     // mgx_config.arith (MGX_ARITH_*): not a tuning knob - it selects which of the two arithmetic modes of the
     // Jacobi update every smoother kernel uses (jac_pt in mgx_kernels.hpp); set by the handle / the slab, never from the environment
     int arith = 0;
 };
+
+// PS:127, 138-140: the Jacobi scalars c0 = 1 - omega, c1 = omega / 4.  The float path evaluates them in double
+// from the float omega and narrows them: the float bits depend on this exact expression.
+template <typename T> struct JacobiCoef { T c0, c1; };
+template <typename T>
+JacobiCoef<T> jacobi_coef(double omega)
+{
+    const T om = (T)omega;
+    return {(T)(1.0 - (double)om), (T)((double)om / 4.0)};
+}
+
+// The smoother kernels come in three sets per element type: Jacobi separately rounded, Jacobi FMA, red-black GS.
+// f(KernelSet<T, SM, AR>{}) for the set of (f64, smoother, arith).
+template <typename T_, int SM_, int AR_> struct KernelSet { using T = T_; static constexpr int SM = SM_, AR = AR_; };
+template <typename F>
+decltype(auto) with_kernel_set(bool f64, int smoother, int arith, F&& f)
+{
+    const bool rbgs = (smoother == MGX_SMOOTHER_RBGS);
+    if (f64) return rbgs ? f(KernelSet<double, 1, 0>{}) : (arith ? f(KernelSet<double, 0, 1>{}) : f(KernelSet<double, 0, 0>{}));
+    return rbgs ? f(KernelSet<float, 1, 0>{}) : (arith ? f(KernelSet<float, 0, 1>{}) : f(KernelSet<float, 0, 0>{}));
+}
 
 // ---- typed operator launches ----------------------------------------------------
 // rows_alloc: rows the arrays hold.  A sweep of rows [row_lo,row_hi) reads rows row_lo-1 .. row_hi:
@@ -48,11 +70,7 @@ int launch_jacobi(const T* vin, const T* b, T* vout, int N, long pitch, int row_
 {
     if (row_hi <= row_lo) return MGX_OK;
     if (row_lo < 1 || row_hi > rows_alloc - 1) return MGX_ERR_INVALID;
-    // PS:127, 138-140: the float path evaluates the scalars in double from the
-    // float omega and narrows them
-    const T om = (T)omega;
-    const T c0 = (T)(1.0 - (double)om);
-    const T c1 = (T)((double)om / 4.0);
+    const auto [c0, c1] = jacobi_coef<T>(omega);
     if (rpc <= 0) {
         // default: one wave per row and strip (see k_jacobi_rows)
         const Launch g = make_launch(N, VecOf<T>::W, row_hi - row_lo, 1);
@@ -152,8 +170,7 @@ inline int fuse_rows_deep(int N, int rows)
 // chunks, 52 row steps for 32 rows)
 inline bool fuse_rows_auto(const FuseCfg& fc, int N, int K, bool f64)
 {
-    static const bool f32_auto = env_int("MGX_F32_AUTO_ROWS", 1) != 0;
-    return fc.rows <= 0 && (f64 ? K >= 8 : (K >= 10 && f32_auto)) && N >= 2048;
+    return fc.rows <= 0 && K >= (f64 ? 8 : 10) && N >= 2048;
 }
 
 inline int shallow_big_n() { static const int n = env_int("MGX_SHALLOW_BIG_N", 8192); return n; }
@@ -275,9 +292,7 @@ int smooth_block(int smoother, T* a, const T* rhs, T* b2, int N, long pitch, int
 {
     const bool rbgs = (smoother == MGX_SMOOTHER_RBGS);
     const int per = rbgs ? 2 : 1;
-    const T om = (T)omega;
-    const T c0 = (T)(1.0 - (double)om);
-    const T c1 = (T)((double)om / 4.0);
+    const auto [c0, c1] = jacobi_coef<T>(omega);
     T* src = a; T* dst = b2;
     int flips = 0;
     int done = 0;
@@ -374,9 +389,8 @@ int launch_cycle_k(const T* vin, const T* b, T* vout, const FoldArgs& fa, int N,
     // an end of the range whose cone (K + 1 rows above, K + 1..2 below: the kernel's `interior`) leaves the unknown rows
     // that exist runs the edge body and gets shorter chunks; the ends of a middle slab, whose halo rows hold the cone, do not
     constexpr int ETOP = POST ? 1 : 0, EBOT = POST == 1 ? 2 : (POST == 2 ? 1 : 0);
-    const bool ends_interior = env_int("MGX_SLAB_ENDS_INTERIOR", 1) != 0;      // 0: shortened chunks at every end of every range (the geometry before round 3's last change)
-    const bool top_edge = !ends_interior || (row_lo - K - ETOP) < std::max(win.row_first, 1) || (PRE && ((row_lo - K - ETOP) >> 1) < win.crow_first);
-    const bool bot_edge = !ends_interior || (row_hi + K + EBOT - 1) > std::min(win.row_last, N - 1) || (PRE && ((row_hi + K + EBOT) >> 1) > win.crow_last);
+    const bool top_edge = (row_lo - K - ETOP) < std::max(win.row_first, 1) || (PRE && ((row_lo - K - ETOP) >> 1) < win.crow_first);
+    const bool bot_edge = (row_hi + K + EBOT - 1) > std::min(win.row_last, N - 1) || (PRE && ((row_hi + K + EBOT) >> 1) > win.crow_last);
     GeomKnobs kn = BL ? geom_knobs() : GeomKnobs();
     // (float passes: a wave covers twice the columns, a grid has half the strips and twice the chunks per strip - the paired
     // form pays from shorter chunks: mixed V(10,10) at 8192^2, float finest-level passes 0.403 -> 0.393-0.395 ms at 100 rows)
@@ -434,6 +448,15 @@ inline bool cycle_k_supported(int K, bool rbgs, bool f64, int post, bool pre, in
     return rbgs ? (K == 2 || K == 4 || K == 6 || K == 8) : (K >= 1 && K <= 8 && K != 7);
 }
 
+// runtime (pre, post) -> the folded stages of k_jacobi_cycle / k_tile_smooth: f(Stages<PRE, POST>{}), all six pairs
+template <int PRE_, int POST_> struct Stages { static constexpr int PRE = PRE_, POST = POST_; };
+template <typename F>
+int with_stages(bool pre, int post, F&& f)
+{
+    if (pre) return post == 2 ? f(Stages<1, 2>{}) : (post == 1 ? f(Stages<1, 1>{}) : f(Stages<1, 0>{}));
+    return post == 2 ? f(Stages<0, 2>{}) : (post == 1 ? f(Stages<0, 1>{}) : f(Stages<0, 0>{}));
+}
+
 // ---- small levels: every sweep of a block in one launch on register tiles (k_tile_smooth) ----
 template <typename T, int SM, int PRE, int POST, int AR>
 int launch_tile(const T* vin, const T* b, T* vout, const FoldArgs& fa, int N, long pitch, T c0, T c1, int levels,
@@ -455,16 +478,15 @@ int launch_tile(const T* vin, const T* b, T* vout, const FoldArgs& fa, int N, lo
     return tiles_y * tiles_x;
 }
 
-// mu sweeps of a whole level, a <-> b2 ping-pong (*flips launches made); pre / post as in
-// smooth_folded_t.  Returns the number of norm partials (post == 2), < 0 on a launch error.
+// mu sweeps on rows [fa.row_lo, fa.row_hi) of the window fa.win (fa.row_hi == 0: a whole level), tile_k levels per
+// launch, a <-> b2 ping-pong (*flips launches made); pre / post as in fold_block (mgx.hip).  Returns the number of norm
+// partials (post == 2), < 0 on a launch error.
 template <typename T, int SM, int AR>
 int smooth_tiled(T* a, const T* rhs, T* b2, int N, long pitch, int mu, double omega, int tile_k, FoldArgs fa,
                  bool pre, int post, bool zero_in, hipStream_t st, int* flips)
 {
     constexpr int per = (SM == 1) ? 2 : 1;
-    const T om = (T)omega;
-    const T c0 = (T)(1.0 - (double)om);
-    const T c1 = (T)((double)om / 4.0);
+    const JacobiCoef<T> jc = jacobi_coef<T>(omega);
     const int smax = std::max(1, tile_k / per);            // sweeps per launch
     const int np = (mu + smax - 1) / smax;
     T* src = a; T* dst = b2;
@@ -474,13 +496,9 @@ int smooth_tiled(T* a, const T* rhs, T* b2, int N, long pitch, int mu, double om
         const bool P = pre && p == 0;
         const int Q = (p == np - 1) ? post : 0;
         fa.zero_in = (p == 0 && zero_in) ? 1 : 0;
-        int rc;
-        if (P && Q == 2) rc = launch_tile<T, SM, 1, 2, AR>(src, rhs, dst, fa, N, pitch, c0, c1, per * sw, st);
-        else if (P && Q == 1) rc = launch_tile<T, SM, 1, 1, AR>(src, rhs, dst, fa, N, pitch, c0, c1, per * sw, st);
-        else if (P) rc = launch_tile<T, SM, 1, 0, AR>(src, rhs, dst, fa, N, pitch, c0, c1, per * sw, st);
-        else if (Q == 1) rc = launch_tile<T, SM, 0, 1, AR>(src, rhs, dst, fa, N, pitch, c0, c1, per * sw, st);
-        else if (Q == 2) rc = launch_tile<T, SM, 0, 2, AR>(src, rhs, dst, fa, N, pitch, c0, c1, per * sw, st);
-        else rc = launch_tile<T, SM, 0, 0, AR>(src, rhs, dst, fa, N, pitch, c0, c1, per * sw, st);
+        const int rc = with_stages(P, Q, [&](auto s) {
+            return launch_tile<T, SM, decltype(s)::PRE, decltype(s)::POST, AR>(src, rhs, dst, fa, N, pitch, jc.c0, jc.c1, per * sw, st);
+        });
         if (rc < 0) return -1;
         if (Q == 2) blocks = rc;
         std::swap(src, dst);
