@@ -231,6 +231,21 @@ typedef struct {
 MGX_API int mgx_solve(mgx_handle h, double tol, int max_cycles, mgx_stats* stats,
                       double* history, int history_cap);
 
+/* Conjugate gradients on the finest level, preconditioned by one V(mu1, mu2) cycle from zero
+ * (mgx_vcycle_zero), run to ||r||_2 <= tol ||r0||_2 or max_iters iterations (absent in the reference).
+ * Starts from the current U; B is not modified.  On return U holds the iterate.  stats / history as for
+ * mgx_solve: history[0] = ||b - A u0||, then the norm of the (recursively updated) residual after each
+ * iteration; stats->cycles = iterations = V-cycles applied.  cfg.schedule is ignored.
+ * Flexible PCG (Polak-Ribiere beta: the V-cycle need not be symmetric, e.g. RB-GS or mu1 != mu2); the
+ * scalars are doubles computed on the device, dots accumulated in double also for F32 handles; results are
+ * deterministic (fixed-order reductions).  A breakdown (p.Ap not a positive finite number) stops the
+ * iteration with stats->converged = 0, MGX_OK and the reason in mgx_last_error.
+ * Single-GPU handles of dtype F64 or F32, op POISSON or STENCIL5; MGX_ERR_STATE on multi-GPU handles and
+ * dtype MIXED (an fp64 CG around the float cycle is a follow-up); MGX_ERR_INVALID for tol < 0 or
+ * max_iters < 0. */
+MGX_API int mgx_solve_pcg(mgx_handle h, double tol, int max_iters, mgx_stats* stats,
+                          double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */

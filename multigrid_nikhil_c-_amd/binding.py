@@ -43,7 +43,7 @@ EXPORTS = [
     "mgx_plan_create", "mgx_plan_destroy", "mgx_plan_last_error", "mgx_plan_cut_level", "mgx_plan_level",
     "mgx_plan_cut_share", "mgx_plan_guess_set", "mgx_plan_vcycle", "mgx_plan_norm", "mgx_plan_fmg", "mgx_rccl_unique_id",
     "mgx_create_rank", "mgx_dist_exchanges", "mgx_dist_overlapped", "mgx_memcpy_d2h", "mgx_memcpy_h2d", "mgx_runtime_libs",
-    "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil",
+    "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg",
 ]
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
@@ -159,6 +159,7 @@ def lib() -> C.CDLL:
         getattr(L, name).argtypes = [vp]
     L.mgx_residual_norm.argtypes = [vp, C.c_int, dp]
     L.mgx_solve.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
+    L.mgx_solve_pcg.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_profile_get.argtypes = [vp, C.POINTER(Profile)]
     L.mgx_time_smoother.argtypes = [vp, C.c_int, dp]
     sp = C.POINTER(Slab)
@@ -498,6 +499,15 @@ class Multigrid:
         hist = np.zeros(max_cycles + 1, dtype=np.float64)
         self._chk(lib().mgx_solve(self._h, tol, max_cycles, C.byref(st), hist.ctypes.data_as(C.POINTER(C.c_double)),
                                   hist.size), "mgx_solve")
+        return st, hist[: st.history_len].copy()
+
+    def solve_pcg(self, tol=1e-8, max_iters=100):
+        """conjugate gradients preconditioned by one V-cycle from zero per iteration, from the current
+        guess; returns (stats, residual history) as solve() does (stats.cycles = iterations)."""
+        st = Stats()
+        hist = np.zeros(max_iters + 1, dtype=np.float64)
+        self._chk(lib().mgx_solve_pcg(self._h, tol, max_iters, C.byref(st), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                      hist.size), "mgx_solve_pcg")
         return st, hist[: st.history_len].copy()
 
     # -- measurement -----------------------------------------------------------------

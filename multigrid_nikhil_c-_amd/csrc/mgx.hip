@@ -8,6 +8,7 @@
 //   Solver::vcycle      PS:575-627 vcyclemultigrid / MF:132-173
 //   Solver::fmg         PS:629-650 fullmultigrid   / MF:175-191
 //   mgx_solve           PS:727 (main's call) / MF:193-197 multigrid_solver
+//   mgx_solve_pcg       (absent in the reference) CG preconditioned by one V-cycle, mgx_krylov.hpp
 // There is no CPU fallback anywhere in this file.
 
 #include "../../include/mgx.h"
@@ -15,6 +16,7 @@
 #include "mgx_kernels.hpp"
 #include "mgx_launch.hpp"
 #include "mgx_var.hpp"
+#include "mgx_krylov.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -103,6 +105,11 @@ struct mgx_solver {
     // general per-level operators: dense inverse of the coarsest one (MF:18 coarsest_level_matrix, MF:63-72)
     double *var_M = nullptr, *var_inv = nullptr, *var_pm = nullptr, *var_pi = nullptr;
     bool var = false;               // cfg.op == MGX_OPERATOR_STENCIL5
+    // mgx_solve_pcg (allocated by its first call): iterate x, directions p / p' (ping-pong), q = A p, the caller's b
+    // while r occupies lv[finest].b, per-block partials of the Krylov passes, the device scalars and their host copy
+    void *pcg_x = nullptr, *pcg_p[2] = {nullptr, nullptr}, *pcg_q = nullptr, *pcg_b = nullptr;
+    double *pcg_part = nullptr, *pcg_sc = nullptr, *pcg_sc_host = nullptr;
+    long pcg_part_cap = 0;
     struct mgx_dist* dist = nullptr; // multi-GPU handle (cfg.n_gpus > 1 / mgx_create_rank): mgx_dist.hpp; no levels of its own
 
     int fail(int code, const std::string& m) { err = m; return code; }
@@ -1020,6 +1027,110 @@ void fold_ring(std::vector<T>& b, const T* ring, size_t n)
         b[i * n + (n - 1)] += rig[i];
     }
 }
+// ---- conjugate gradients preconditioned by one V-cycle (absent in the reference; mgx_krylov.hpp) ----------------
+int pcg_alloc(mgx_solver* s, const Level& l, const Launch& g)
+{
+    for (void** p : {&s->pcg_x, &s->pcg_p[0], &s->pcg_p[1], &s->pcg_q, &s->pcg_b}) {
+        if (*p) continue;
+        if (hipMalloc(p, l.bytes) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the PCG vectors");
+        HIPCHK(s, hipMemsetAsync(*p, 0, l.bytes, s->stream));       // the ring and the padding stay zero from here on
+    }
+    if (!s->pcg_part) {
+        s->pcg_part_cap = 2L * g.blocks + 8;                           // k_pcg_dots writes two partials per workgroup
+        if (hipMalloc(&s->pcg_part, s->pcg_part_cap * sizeof(double)) != hipSuccess)
+            return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the PCG partial sums");
+    }
+    if (!s->pcg_sc && hipMalloc(&s->pcg_sc, kPcgScalars * sizeof(double)) != hipSuccess)
+        return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the PCG scalars");
+    if (!s->pcg_sc_host && hipHostMalloc(&s->pcg_sc_host, kPcgScalars * sizeof(double)) != hipSuccess)
+        return s->fail(MGX_ERR_ALLOC, "hipHostMalloc failed for the PCG scalars");
+    if (2L * g.blocks > s->pcg_part_cap) return s->fail(MGX_ERR_STATE, "PCG partial-sum buffer smaller than its launch");
+    return MGX_OK;
+}
+
+inline void pcg_reduce(mgx_solver* s, int n, int mode)
+{
+    hipLaunchKernelGGL(k_pcg_reduce, dim3(1), dim3(kReduceThreads), 0, s->stream, s->pcg_part, n, mode, s->pcg_sc);
+}
+
+// rho_new = r.z, gamma = z.q (r = B, z = U of the finest level); mode kPcgInit or kPcgBetaMode
+template <typename T>
+void pcg_dots(mgx_solver* s, const Level& l, const Launch& g, int mode)
+{
+    hipLaunchKernelGGL((k_pcg_dots<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.b, (const T*)l.u,
+                       (const T*)s->pcg_q, s->pcg_part, l.N, l.pitch, g.R, g.strips, g.chunks);
+    pcg_reduce(s, g.blocks, mode);
+}
+
+// p' = z + beta p, q = A p', alpha = rho / p'.q; then x += alpha p', r -= alpha q and ||r||^2
+template <typename T>
+void pcg_step(mgx_solver* s, const Level& l, const Launch& g, bool first_it, int& pp)
+{
+    const T* z = (const T*)l.u;
+    const T* p = (const T*)s->pcg_p[pp];
+    T* pn = (T*)s->pcg_p[pp ^ 1];
+    if (s->var)
+        hipLaunchKernelGGL((k_pcg_direction<T, 1>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, p, pn, (T*)s->pcg_q, s->pcg_sc,
+                           first_it ? 1 : 0, s->pcg_part, (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2],
+                           (const T*)l.coef[3], (const T*)l.coef[4], l.N, l.pitch, g.R, g.strips, g.chunks);
+    else
+        hipLaunchKernelGGL((k_pcg_direction<T, 0>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, p, pn, (T*)s->pcg_q, s->pcg_sc,
+                           first_it ? 1 : 0, s->pcg_part, (const T*)nullptr, (const T*)nullptr, (const T*)nullptr,
+                           (const T*)nullptr, (const T*)nullptr, l.N, l.pitch, g.R, g.strips, g.chunks);
+    pcg_reduce(s, g.blocks, kPcgAlphaMode);
+    pp ^= 1;
+    hipLaunchKernelGGL((k_pcg_update<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)s->pcg_x, (const T*)pn, (T*)l.b,
+                       (const T*)s->pcg_q, s->pcg_sc, s->pcg_part, l.N, l.pitch, g.R, g.strips, g.chunks);
+    pcg_reduce(s, g.blocks, kPcgRRMode);
+}
+
+// The iteration proper.  r lives in lv[L].b for the whole solve: it is the V-cycle's right-hand side, and the cached
+// cycle graphs hold that pointer (they are keyed on the u / tmp pointers only).  The caller's b waits in pcg_b.
+template <typename T>
+int pcg_run(mgx_solver* s, double tol, int max_iters, std::vector<double>& hist, int* iters, int* breakdown)
+{
+    Level& l = s->lv[s->cfg.finest_level];
+    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, s->rows_per_chunk);
+    int rc = pcg_alloc(s, l, g);
+    if (rc) return rc;
+    HIPCHK(s, hipMemcpyAsync(s->pcg_x, l.u, l.bytes, hipMemcpyDeviceToDevice, s->stream));
+    HIPCHK(s, hipMemcpyAsync(s->pcg_b, l.b, l.bytes, hipMemcpyDeviceToDevice, s->stream));
+    s->norm_blocks_ready = 0;
+    double h0 = 0.0;
+    if ((rc = residual_norm_grid(s, l, s->pcg_x, s->pcg_b, &h0, MGX_PROF_NORM_FINE))) return rc;
+    hist.push_back(h0);
+    if (h0 <= tol * h0 || max_iters == 0) return MGX_OK;               // (b = 0, u = 0: converged, nothing divided)
+    // r = b - A x, into lv[L].b
+    if (s->var) residual_var_t<T, 0>(s, l, s->pcg_x, s->pcg_b, l.b);
+    else launch_residual<T, 0>((const T*)s->pcg_x, (const T*)s->pcg_b, l.b, l.pitch, nullptr, nullptr, 1.0, l.N, l.pitch, 1, l.N,
+                               s->rows_per_chunk, s->stream, s->partial_cap, l.rows);
+    double unused = 0.0;
+    if ((rc = cycle_body(s, false, true, &unused))) return rc;         // z = M r: one V-cycle from zero, into lv[L].u
+    pcg_dots<T>(s, l, g, kPcgInit);                                    // rho = r.z; p = z (first pcg_step)
+    int pp = 0;
+    for (int k = 0; k < max_iters; ++k) {
+        pcg_step<T>(s, l, g, k == 0, pp);
+        HIPCHK(s, hipGetLastError());
+        HIPCHK(s, hipMemcpyAsync(s->pcg_sc_host, s->pcg_sc, kPcgScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(s, hipStreamSynchronize(s->stream));                    // the one host synchronisation per iteration
+        if (s->pcg_sc_host[kPcgBreak] != 0.0) {
+            *breakdown = 1;
+            char m[160];
+            std::snprintf(m, sizeof m, "PCG breakdown at iteration %d: p.Ap = %.17g is not a positive finite number", k + 1,
+                          s->pcg_sc_host[kPcgDelta]);
+            s->err = m;
+            return MGX_OK;
+        }
+        *iters = k + 1;
+        const double rn = std::sqrt(s->pcg_sc_host[kPcgRR]);
+        hist.push_back(rn);
+        if (rn <= tol * h0 || k + 1 == max_iters) break;
+        if ((rc = cycle_body(s, false, true, &unused))) return rc;     // z = M r
+        pcg_dots<T>(s, l, g, kPcgBetaMode);                            // beta = -alpha z.q / rho, rho = r.z
+    }
+    return MGX_OK;
+}
+
 } // namespace
 
 #include "mgx_dist.hpp"
@@ -1197,6 +1308,8 @@ int mgx_destroy(mgx_handle s)
     if (s->sum_dev) (void)hipFree(s->sum_dev);
     if (s->sum_host) (void)hipHostFree(s->sum_host);
     for (double* p : {s->var_M, s->var_inv, s->var_pm, s->var_pi}) if (p) (void)hipFree(p);
+    for (void* p : {s->pcg_x, s->pcg_p[0], s->pcg_p[1], s->pcg_q, s->pcg_b, (void*)s->pcg_part, (void*)s->pcg_sc}) if (p) (void)hipFree(p);
+    if (s->pcg_sc_host) (void)hipHostFree(s->pcg_sc_host);
     for (auto& g : s->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -1665,6 +1778,46 @@ int mgx_solve(mgx_handle s, double tol, int max_cycles, mgx_stats* stats, double
         stats->initial_residual = hist.front();
         stats->final_residual = hist.back();
         stats->converged = (hist.back() <= tol * hist.front()) ? 1 : 0;
+        stats->seconds = std::chrono::duration<double>(t1 - t0).count();
+        stats->fine_updates = s->fine_updates;
+        stats->history_len = (int)hist.size();
+    }
+    if (history)
+        for (int i = 0; i < (int)hist.size() && i < history_cap; ++i) history[i] = hist[i];
+    return MGX_OK;
+}
+
+int mgx_solve_pcg(mgx_handle s, double tol, int max_iters, mgx_stats* stats, double* history, int history_cap)
+{
+    if (!s) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (s->mixed) return s->fail(MGX_ERR_STATE, "mgx_solve_pcg: dtype MIXED is not supported (F64 or F32 handles)");
+    if (max_iters < 0 || !(tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_solve_pcg: tol >= 0 and max_iters >= 0 required");
+    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
+    Level& l = s->lv[s->cfg.finest_level];
+    std::vector<double> hist;
+    hist.reserve(max_iters + 1);
+    s->fine_updates = 0.0;
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    int iters = 0, breakdown = 0;
+    const int rc = s->work_f64 ? pcg_run<double>(s, tol, max_iters, hist, &iters, &breakdown)
+                               : pcg_run<float>(s, tol, max_iters, hist, &iters, &breakdown);
+    // U = x, B = the caller's b again (also after a failure part way, where they were saved)
+    if (s->pcg_x && !hist.empty()) {
+        (void)hipMemcpyAsync(l.u, s->pcg_x, l.bytes, hipMemcpyDeviceToDevice, s->stream);
+        (void)hipMemcpyAsync(l.b, s->pcg_b, l.bytes, hipMemcpyDeviceToDevice, s->stream);
+    }
+    s->norm_blocks_ready = 0;
+    if (rc) return rc;
+    HIPCHK(s, hipGetLastError());
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (stats) {
+        stats->cycles = iters;
+        stats->initial_residual = hist.front();
+        stats->final_residual = hist.back();
+        stats->converged = (!breakdown && hist.back() <= tol * hist.front()) ? 1 : 0;
         stats->seconds = std::chrono::duration<double>(t1 - t0).count();
         stats->fine_updates = s->fine_updates;
         stats->history_len = (int)hist.size();
