@@ -285,7 +285,8 @@ void smooth_t(mgx_solver* s, Level& l, int mu)
         using T = typename K::T;
         int parity = 0, launches = 0;
         if (tile_level(s, l) && smooth_tiled<T, K::SM, K::AR>((T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, mu, s->cfg.omega,
-                                                              s->fuse.tile_k, FoldArgs(), false, 0, false, s->stream, &launches) >= 0)
+                                                              s->fuse.tile_k, tile_band<T>(s->fuse, l.N), FoldArgs(), false, 0, false,
+                                                              s->stream, &launches) >= 0)
             parity = launches & 1;
         else
             (void)smooth_block<T>(s->cfg.smoother, (T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, l.rows, 1, l.N, mu,
@@ -491,8 +492,8 @@ int fold_block(const FuseCfg& fc, long tile_points, const mgx_slab* f, T* u, con
         const bool whole = row_lo <= first && row_hi >= last;
         if (fc.tile_max_n > 0 && hi > lo && (long)(hi - lo) * N <= tile_points && (per * mu <= fc.tile_k || whole)) {
             fa.row_lo = lo + f->row0; fa.row_hi = hi + f->row0;
-            return smooth_tiled<T, SM, AR>(u - back, b - back, tmp - back, N, pitch, mu, omega, fc.tile_k, fa, pre, post,
-                                           zero_in != 0, st, flips);
+            return smooth_tiled<T, SM, AR>(u - back, b - back, tmp - back, N, pitch, mu, omega, fc.tile_k, tile_band<T>(fc, N), fa,
+                                           pre, post, zero_in != 0, st, flips);
         }
     }
     int parts[64];

@@ -302,4 +302,40 @@ inline CycleGeom cycle_geom_pick(int row_lo, int row_hi, int strips, int extra, 
     return g;
 }
 
+// ---- k_tile_wide (mgx_kernels.hpp): the register tiles of a whole smoothing block on a small level ----------------
+// A workgroup of kTileWideWaves waves holds an array of SY = kTileWideWaves * RW rows (wave w: the band of RW rows
+// [w RW, w RW + RW)) by SX = 64 W columns (lane l: the W columns [W l, W l + W), one 16-B vector).  Level j of the
+// block is valid on the array minus j nodes per side, so the output tile is the array minus a halo of He = levels
+// (+2 for a folded restriction, +1 for a norm) nodes: rows [He, SY - He), and columns [Hx, SX - Hx) with Hx = He
+// rounded up to whole vectors, so that the output columns of a tile - [tx TW, tx TW + TW), global - start on a 16-B
+// boundary and every lane stores its vector whole.  Tile (ty, tx): global rows row_lo + ty TH + [0, TH) of the range
+// [row_lo, row_hi), global columns tx TW + [0, TW) of [1, N) (column 0 is the boundary, never updated).
+constexpr int kTileWideWaves = 8;
+
+struct TileWideGeom {
+    int He, Hx;                 // halo rows, halo columns (He rounded up to a multiple of W)
+    int TH, TW;                 // output tile: rows x columns
+    int tiles_y, tiles_x;
+};
+
+MGX_GEOM_HD TileWideGeom tile_wide_geom(int N, int row_lo, int row_hi, int He, int W, int RW)
+{
+    TileWideGeom g;
+    g.He = He;
+    g.Hx = (He + W - 1) / W * W;
+    g.TH = kTileWideWaves * RW - 2 * He;
+    g.TW = 64 * W - 2 * g.Hx;
+    g.tiles_y = (g.TH > 0 && row_hi > row_lo) ? (row_hi - row_lo + g.TH - 1) / g.TH : 0;
+    g.tiles_x = g.TW > 0 ? (N + g.TW - 1) / g.TW : 0;
+    return g;
+}
+
+// band height (fp64): 10 rows (80 x 128 arrays, 56 x 104 output tiles at He = 12: 57 %) above short_max_n.  The time of
+// these launches is one workgroup's chain of levels (a 1024^2 block is one round of workgroups): bands of 10 against 12
+// rows took 19 + 19 us against 22 + 20 per V(10,10) at 1024^2, in 190 / 180 workgroups against 150 / 140 (MI355X).
+// The small levels have a few dozen tiles at most and take 8-row bands (64-row arrays, more tiles).  fp32 lanes hold four
+// columns (256-column arrays) and always take 8-row bands.  Every choice keeps the tiles at least 32 x 40 nodes for
+// He <= 12 (the norm partials' buffer is sized for that: mgx.hip).
+MGX_GEOM_HD int tile_wide_rw(int N, int short_max_n) { return N <= short_max_n ? 8 : 10; }
+
 } // namespace mgx

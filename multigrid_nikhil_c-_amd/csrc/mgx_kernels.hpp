@@ -1901,6 +1901,250 @@ k_tile_smooth(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restric
     }
 }
 
+// =============================================================================
+// k_tile_wide: k_tile_smooth's contract (every PRE / POST stage, SM 0 / 1, AR, zero_in, row windows) on wider
+// register tiles, for the levels up to 2048^2.
+//
+// k_tile_smooth's 56 x 64 array keeps 32 x 40 of it after a halo of 12 (36 %), and its lanes hold one node, so
+// every point pays two DPP moves per x-neighbour.  Here a lane holds one 16-byte vector of W nodes (2 doubles /
+// 4 floats): the x-neighbours inside the vector are registers and only the two outer ones come by DPP.  The
+// workgroup is kTileWideWaves = 8 waves with bands of RW rows: with RW = 14 the array is 112 x 128 (fp64) and a
+// halo of 12 leaves 88 x 104 (64 %); the launcher uses RW = 10 (80 x 128, 56 x 104: 57 %) and RW = 8.  Geometry:
+// tile_wide_geom (mgx_geom.hpp).
+//
+// Per point the same operations in the same order as k_tile_smooth: the stored values are bit-identical.  Nodes
+// outside level j's valid region (the array minus j nodes per side) are updated as well - only unknowns are, and
+// only valid nodes feed the stored ones - so the level loop has no region test.  The norm partials (POST 2) sum a
+// different set of nodes per workgroup than k_tile_smooth's, so their sum may differ in the last bits.
+// =============================================================================
+__device__ __forceinline__ double vget(const double2& v, int e) { return e == 0 ? v.x : v.y; }
+__device__ __forceinline__ float vget(const float4& v, int e) { return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w)); }
+__device__ __forceinline__ double2 vmake(const double (&a)[2]) { return make_double2(a[0], a[1]); }
+__device__ __forceinline__ float4 vmake(const float (&a)[4]) { return make_float4(a[0], a[1], a[2], a[3]); }
+
+template <typename T, int SM, int PRE, int POST, int AR, int RW>
+__global__ void __launch_bounds__(kTileWideWaves * kWave)
+k_tile_wide(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ vout,
+            const T* __restrict__ coarse_e, T* __restrict__ coarse_b, T* __restrict__ coarse_zero, T wgt,
+            double* __restrict__ partial, int N, long pitch, long cpitch, int levels, T c0, T c1,
+            int tiles_x, int zero_in, int row_lo, int row_hi, CycleWin win)
+{
+    using V = typename VecOf<T>::type;
+    constexpr int W = VecOf<T>::W;
+    constexpr int NW = kTileWideWaves;
+    __shared__ V edge[2][NW][2][kWave];             // [buffer][wave][first / last row][lane]
+    __shared__ double wsum[NW];
+    const TileWideGeom g = tile_wide_geom(N, row_lo, row_hi, levels + tile_extra<POST>(), W, RW);
+    const int He = g.He, TH = g.TH, TW = g.TW;
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int y0 = wv * RW;                         // array row of this wave's register row 0
+    const int gy0 = row_lo + ty * TH - He + y0;     // its global node row
+    const int cx0 = tx * TW;                        // the tile's first output column
+    const int gx0 = cx0 - g.Hx + W * lane;          // global column of this lane's first node (a multiple of W)
+    const bool vld = gx0 >= 0 && gx0 < N;           // the vector exists and holds an unknown (N is a multiple of W)
+    // node e is in a column of unknowns: columns 1 .. N - 1, i.e. the whole vector but column 0 (two lane masks)
+    const bool cu0 = vld && gx0 > 0;
+    bool cu[W];
+#pragma unroll
+    for (int e = 0; e < W; ++e) cu[e] = e == 0 ? cu0 : vld;
+    const int NC = N / 2;
+
+    // ---- load the band (with the correction, PRE) -----------------------------------------------------
+    T u[RW][W], b[RW][W];
+    unsigned rowmask = 0;                           // bit i: register row i is a row of unknowns
+#pragma unroll
+    for (int i = 0; i < RW; ++i) {
+        const int gy = gy0 + i;
+        const bool rowok = gy > 0 && gy < N && gy >= win.row_first && gy <= win.row_last;     // wave-uniform
+        if (rowok) rowmask |= 1u << i;
+        const long at = (long)gy * pitch + gx0;
+        V uv = vzero((V*)nullptr), bv = vzero((V*)nullptr);
+        if (vld && rowok) {
+            bv = *reinterpret_cast<const V*>(rhs + at);
+            if (!zero_in) uv = *reinterpret_cast<const V*>(vin + at);
+        }
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            u[i][e] = cu[e] ? vget(uv, e) : (T)0;
+            b[i][e] = cu[e] ? vget(bv, e) : (T)0;
+        }
+    }
+    if (PRE) {
+        // The band's fine rows gy0 .. gy0 + RW - 1 lie on the RW / 2 + 1 coarse rows kc0 + k (kc0 = gy0 >> 1) and the lane's
+        // nodes on the W / 2 + 1 coarse columns J + m (J = gx0 / 2): each is loaded once, where it exists.  A node then takes
+        // the four coarse values k_tile_smooth takes, under the same conditions (0 where that kernel reads none): same bits.
+        // The fine row parity is wave-uniform but not known at compile time: one body per parity of gy0.
+        constexpr int NCR = RW / 2 + 1, NCC = W / 2 + 1;
+        const int kc0 = gy0 >> 1, J = gx0 >> 1;
+        T cr[NCR][NCC];
+#pragma unroll
+        for (int k = 0; k < NCR; ++k) {
+            const int cy = kc0 + k;
+            const bool ok = vld && cy >= 0 && cy <= NC && cy >= win.crow_first && cy <= win.crow_last;
+            const T* ep = coarse_e + (long)cy * cpitch + J;
+#pragma unroll
+            for (int m = 0; m < NCC; ++m) cr[k][m] = ok ? ep[m] : (T)0;
+        }
+        auto correct = [&](auto parity) {
+            constexpr int par = decltype(parity)::value;              // gy0 & 1
+#pragma unroll
+            for (int i = 0; i < RW; ++i) {
+                const int gy = gy0 + i;
+                const bool rodd = ((par + i) & 1) != 0;
+                const int kr = (par + i) >> 1;                         // coarse row gy >> 1 = kc0 + kr
+                const bool rin = ((rowmask >> i) & 1u) && (gy >> 1) >= win.crow_first && (gy >> 1) + (rodd ? 1 : 0) <= win.crow_last;
+#pragma unroll
+                for (int e = 0; e < W; ++e) {
+                    const bool codd = (e & 1) != 0;                    // gx0 is even
+                    const bool unk = cu[e] && rin;
+                    // the four coarse nodes around (gy, gx); all inside the coarse grid when (gy, gx) is an unknown
+                    const T a00 = unk ? cr[kr][e >> 1] : (T)0;
+                    const T a01 = (unk && codd) ? cr[kr][(e >> 1) + 1] : (T)0;
+                    const T a10 = (unk && rodd) ? cr[kr + (rodd ? 1 : 0)][e >> 1] : (T)0;
+                    const T a11 = (unk && rodd && codd) ? cr[kr + (rodd ? 1 : 0)][(e >> 1) + 1] : (T)0;
+                    const T ev = codd ? (T)0.5 * (a00 + a01) : a00;                          // even row
+                    const T od = codd ? (T)0.25 * (((a00 + a10) + a01) + a11) : (T)0.5 * (a00 + a10);
+                    const T add = rodd ? od : ev;
+                    u[i][e] = unk ? u[i][e] + add : u[i][e];
+                }
+            }
+        };
+        if (gy0 & 1) correct(std::integral_constant<int, 1>{});
+        else correct(std::integral_constant<int, 0>{});
+    }
+
+    // ---- the smoother levels, in lockstep over the workgroup ---------------------------
+    int buf = 0;
+    auto halo_rows = [&](const T (&a)[RW][W], T (&up)[W], T (&dn)[W]) {
+        edge[buf][wv][0][lane] = vmake(a[0]);
+        edge[buf][wv][1][lane] = vmake(a[RW - 1]);
+        __syncthreads();
+        const V uv = wv > 0 ? edge[buf][wv - 1][1][lane] : vzero((V*)nullptr);
+        const V dv = wv < NW - 1 ? edge[buf][wv + 1][0][lane] : vzero((V*)nullptr);
+#pragma unroll
+        for (int e = 0; e < W; ++e) { up[e] = vget(uv, e); dn[e] = vget(dv, e); }
+        buf ^= 1;       // the next exchange writes the other buffer; its barrier orders the re-use of this one
+    };
+    for (int j = 1; j <= levels; ++j) {
+        T up[W], dn[W];
+        halo_rows(u, up, dn);
+        const int colour = (j - 1) & 1;             // SM 1: the colour level j updates
+        // straight-line over the rows: they are independent, so their dependent add chains interleave
+        T prev[W];                                  // old values of the row above
+#pragma unroll
+        for (int e = 0; e < W; ++e) prev[e] = up[e];
+#pragma unroll
+        for (int i = 0; i < RW; ++i) {
+            T cur[W];
+#pragma unroll
+            for (int e = 0; e < W; ++e) cur[e] = u[i][e];
+            const T l = from_left(cur[W - 1]), r = from_right(cur[0]);
+            const bool rowact = (rowmask >> i) & 1u;                            // wave-uniform
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const T below = (i == RW - 1) ? dn[e] : u[i + 1][e];
+                const T we = e == 0 ? l : cur[e - 1], ea = e == W - 1 ? r : cur[e + 1];
+                if (SM == 0) {
+                    const T o = jac_pt<AR>(c0, cur[e], c1 * b[i][e], c1, nbr(prev[e], we, ea, below));
+                    u[i][e] = (cu[e] && rowact) ? o : cur[e];
+                } else {
+                    const T o = (T)0.25 * (b[i][e] + nbr(prev[e], we, ea, below));
+                    u[i][e] = (cu[e] && rowact && ((gy0 + i + e) & 1) == colour) ? o : cur[e];    // gx0 is even
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < W; ++e) prev[e] = cur[e];
+        }
+    }
+    // u is the result on array rows [levels, SY - levels) and columns [levels, SX - levels)
+
+    // ---- store the tile (whole vectors: a lane's vector lies in one tile's output columns) ----------------------
+    const bool colout = gx0 >= cx0 && gx0 < cx0 + TW && gx0 < N;
+#pragma unroll
+    for (int i = 0; i < RW; ++i) {
+        const int y = y0 + i, gy = gy0 + i;
+        if (y >= He && y < He + TH && gy < N && gy >= row_lo && gy < row_hi && colout)
+            *reinterpret_cast<V*>(vout + (long)gy * pitch + gx0) = vmake(u[i]);
+    }
+
+    if (POST != 0) {
+        // residual of the result: r = b - A u on the tile (+- 1 node for the restriction)
+        T up[W], dn[W];
+        halo_rows(u, up, dn);
+        T res[RW][W];
+        double acc = 0.0;
+        T prev[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) prev[e] = up[e];
+#pragma unroll
+        for (int i = 0; i < RW; ++i) {
+            const int y = y0 + i, gy = gy0 + i;
+            const T l = from_left(u[i][W - 1]), r = from_right(u[i][0]);
+            const bool rowunk = gy > 0 && gy < N;
+            const bool rowout = POST == 2 && y >= He && y < He + TH && gy >= row_lo && gy < row_hi && colout;
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const T cur = u[i][e];
+                const T below = (i == RW - 1) ? dn[e] : u[i + 1][e];
+                const T we = e == 0 ? l : u[i][e - 1], ea = e == W - 1 ? r : u[i][e + 1];
+                T rr = (T)0;
+                if (cu[e] && rowunk) rr = b[i][e] - (-nbr(prev[e], we, ea, below) + (T)4 * cur);
+                res[i][e] = rr;
+                if (rowout) acc += (double)rr * (double)rr;
+            }
+#pragma unroll
+            for (int e = 0; e < W; ++e) prev[e] = u[i][e];
+        }
+        if (POST == 2) {
+            for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, kWave);
+            if (lane == 0) wsum[wv] = acc;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                double sum = 0.0;
+                for (int w2 = 0; w2 < NW; ++w2) sum += wsum[w2];
+                partial[blockIdx.x] = sum;
+            }
+        }
+        if (POST == 1) {
+            T rup[W], rdn[W];
+            halo_rows(res, rup, rdn);
+#pragma unroll
+            for (int i = 0; i < RW; ++i) {
+                const int y = y0 + i, gy = gy0 + i;
+                const bool rowst = y >= He && y < He + TH && (gy & 1) == 0 && gy < N && gy >= row_lo && gy < row_hi &&
+                                   (gy >> 1) >= win.emit_lo && (gy >> 1) < win.emit_hi;    // a coarse row of this tile
+                T n[W], s2[W];
+#pragma unroll
+                for (int e = 0; e < W; ++e) {
+                    n[e] = (i == 0) ? rup[e] : res[i - 1][e];
+                    s2[e] = (i == RW - 1) ? rdn[e] : res[i + 1][e];
+                }
+                const T nl = from_left(n[W - 1]), sl = from_left(s2[W - 1]), cl = from_left(res[i][W - 1]);
+#pragma unroll
+                for (int e = 0; e < W; e += 2) {          // the even columns: coarse node J = gx / 2
+                    const T c = res[i][e];
+                    // PS:539-542 order: ((nw+ne)+sw)+se + 2*(((w+e)+n)+s) + 4*c
+                    T corners = (e == 0 ? nl : n[e - 1]) + n[e + 1];
+                    corners = corners + (e == 0 ? sl : s2[e - 1]);
+                    corners = corners + s2[e + 1];
+                    T edges = (e == 0 ? cl : res[i][e - 1]) + res[i][e + 1];
+                    edges = edges + n[e];
+                    edges = edges + s2[e];
+                    const T o = wgt * ((corners + (T)2 * edges) + (T)4 * c);
+                    const int J = (gx0 + e) >> 1;
+                    if (rowst && colout && J >= 1 && J < NC) {
+                        const long at = (long)(gy >> 1) * cpitch + J;
+                        coarse_b[at] = o;
+                        if (coarse_zero) coarse_zero[at] = (T)0;
+                    }
+                }
+            }
+        }
+    }
+}
+
 // mixed precision (config 5): u64 += scale * (double) e32, rows [row_lo,row_hi)
 static __global__ void __launch_bounds__(kBlock)
 k_axpy_f32_to_f64(double* __restrict__ u, const float* __restrict__ e, double scale, int N, long pitch, long epitch,

@@ -30,6 +30,7 @@ inline int env_int(const char* name, int dflt)
 // fused grid, levels per pass for the folded kernels
 struct FuseCfg {
     int kmax; int rows; int min_n; int fold_kmax; int fold_kmax_big; int tile_max_n; int tile_k; int fold_kmax_nopost;
+    int tile_wide; int tile_short_n;    // register tiles: k_tile_wide for fp64 (1) / all levels (2), else k_tile_smooth; 8-row bands up to tile_short_n
     // explicit pass plans (sweeps per pass) for the pre- / post-smoothing block of grids with
     // N >= plan_min_n: tuning knobs MGX_PLAN_PRE / MGX_PLAN_POST ("8,2"), MGX_PLAN_MIN_N.  They apply to the
     // folded blocks of whole levels and of slabs alike (fold_plan in mgx.hip)
@@ -218,7 +219,13 @@ inline FuseCfg fuse_cfg()
     // another (VALU-bound passes follow the clock the chip holds; the HBM-bound [5,5] does not).
     f.fold_kmax_big = std::max(1, std::min(f.kmax, env_int("MGX_FOLD_KMAX_BIG", 10)));
     // Whole levels up to this N (= 2^L) are smoothed by the LDS tile kernel, all sweeps of a
-    // block (up to tile_k levels) per launch; 0 disables it.
+    // block (up to tile_k levels) per launch; 0 disables it.  MGX_TILE_WIDE selects the kernel: k_tile_wide for fp64
+    // levels (1, the default), for fp32 levels too (2), or k_tile_smooth everywhere (0).  In fp32 k_tile_wide measured
+    // slower (bench --dtype f32: 0.918 against 0.902-0.910 ms), so fp32 levels keep k_tile_smooth by default.  At 2048^2 the tiles lose to the marching passes (k_tile_wide 64 + 64 us per V(10,10)
+    // against 47 + 44: 580 workgroups of one per CU are three rounds), so the default stays 1024.  MGX_TILE_SHORT_N:
+    // levels up to this N run k_tile_wide with 8-row bands (tile_wide_rw, mgx_geom.hpp).
+    f.tile_wide = std::max(0, std::min(2, env_int("MGX_TILE_WIDE", 1)));
+    f.tile_short_n = env_int("MGX_TILE_SHORT_N", 512);
     f.tile_max_n = std::max(0, env_int("MGX_TILE_MAX_N", 1024));
     f.tile_k = std::max(2, std::min(10, env_int("MGX_TILE_K", 10)));
     // levels per folded pass for blocks that end WITHOUT a residual stage (post-smoothing below
@@ -457,7 +464,7 @@ int with_stages(bool pre, int post, F&& f)
     return post == 2 ? f(Stages<0, 2>{}) : (post == 1 ? f(Stages<0, 1>{}) : f(Stages<0, 0>{}));
 }
 
-// ---- small levels: every sweep of a block in one launch on register tiles (k_tile_smooth) ----
+// ---- small levels: every sweep of a block in one launch on register tiles (k_tile_smooth / k_tile_wide) ----
 template <typename T, int SM, int PRE, int POST, int AR>
 int launch_tile(const T* vin, const T* b, T* vout, const FoldArgs& fa, int N, long pitch, T c0, T c1, int levels,
                 hipStream_t st)
@@ -478,11 +485,47 @@ int launch_tile(const T* vin, const T* b, T* vout, const FoldArgs& fa, int N, lo
     return tiles_y * tiles_x;
 }
 
+// the same block on k_tile_wide with bands of rw (8 or 10) rows; geometry: tile_wide_geom (mgx_geom.hpp)
+template <typename T, int SM, int PRE, int POST, int AR>
+int launch_tile_wide(const T* vin, const T* b, T* vout, const FoldArgs& fa, int N, long pitch, T c0, T c1, int levels,
+                     int rw, hipStream_t st)
+{
+    // fp32: four columns per lane, 256-column arrays; 12-row bands would not fit the registers
+    if (VecOf<T>::W == 4) rw = 8;
+    const bool whole = (fa.row_hi == 0);
+    const int row_lo = whole ? 1 : fa.row_lo, row_hi = whole ? N : fa.row_hi;
+    const CycleWin win = whole ? CycleWin{0, N, 0, N / 2, 1, N / 2} : fa.win;
+    const TileWideGeom g = tile_wide_geom(N, row_lo, row_hi, levels + tile_extra<POST>(), VecOf<T>::W, rw);
+    if (g.TH < 8 || g.TW < 8) return -1;
+    if (g.tiles_y < 1) return 0;
+    const T w = (fa.restrict_mode == MGX_RESTRICT_FW16) ? (T)0.0625 : (T)0.25;
+    const dim3 grid(g.tiles_y * g.tiles_x), block(kTileWideWaves * kWave);
+    if (rw == 8)
+        hipLaunchKernelGGL((k_tile_wide<T, SM, PRE, POST, AR, 8>), grid, block, 0, st, vin, b, vout, (const T*)fa.coarse_e,
+                           (T*)fa.coarse_b, (T*)fa.coarse_zero, w, fa.partial, N, pitch, fa.cpitch, levels, c0, c1, g.tiles_x,
+                           fa.zero_in, row_lo, row_hi, win);
+    else if constexpr (VecOf<T>::W == 2) {
+        if (rw != 10) return -1;
+        hipLaunchKernelGGL((k_tile_wide<T, SM, PRE, POST, AR, 10>), grid, block, 0, st, vin, b, vout, (const T*)fa.coarse_e,
+                           (T*)fa.coarse_b, (T*)fa.coarse_zero, w, fa.partial, N, pitch, fa.cpitch, levels, c0, c1, g.tiles_x,
+                           fa.zero_in, row_lo, row_hi, win);
+    } else {
+        return -1;
+    }
+    return g.tiles_y * g.tiles_x;
+}
+
+// band height of k_tile_wide for a level of N (= 2^L) of T, 0: k_tile_smooth
+template <typename T> int tile_band(const FuseCfg& fc, int N)
+{
+    return (fc.tile_wide >= (sizeof(T) == 8 ? 1 : 2)) ? tile_wide_rw(N, fc.tile_short_n) : 0;
+}
+
 // mu sweeps on rows [fa.row_lo, fa.row_hi) of the window fa.win (fa.row_hi == 0: a whole level), tile_k levels per
-// launch, a <-> b2 ping-pong (*flips launches made); pre / post as in fold_block (mgx.hip).  Returns the number of norm
-// partials (post == 2), < 0 on a launch error.
+// launch, a <-> b2 ping-pong (*flips launches made); pre / post as in fold_block (mgx.hip).  band: k_tile_wide's band
+// height (tile_band), 0 for k_tile_smooth.  Returns the number of norm partials (post == 2), < 0 on a launch error.
 template <typename T, int SM, int AR>
-int smooth_tiled(T* a, const T* rhs, T* b2, int N, long pitch, int mu, double omega, int tile_k, FoldArgs fa,
+int smooth_tiled(T* a, const T* rhs, T* b2, int N, long pitch, int mu, double omega, int tile_k, int band, FoldArgs fa,
                  bool pre, int post, bool zero_in, hipStream_t st, int* flips)
 {
     constexpr int per = (SM == 1) ? 2 : 1;
@@ -497,7 +540,9 @@ int smooth_tiled(T* a, const T* rhs, T* b2, int N, long pitch, int mu, double om
         const int Q = (p == np - 1) ? post : 0;
         fa.zero_in = (p == 0 && zero_in) ? 1 : 0;
         const int rc = with_stages(P, Q, [&](auto s) {
-            return launch_tile<T, SM, decltype(s)::PRE, decltype(s)::POST, AR>(src, rhs, dst, fa, N, pitch, jc.c0, jc.c1, per * sw, st);
+            using S = decltype(s);
+            return band ? launch_tile_wide<T, SM, S::PRE, S::POST, AR>(src, rhs, dst, fa, N, pitch, jc.c0, jc.c1, per * sw, band, st)
+                        : launch_tile<T, SM, S::PRE, S::POST, AR>(src, rhs, dst, fa, N, pitch, jc.c0, jc.c1, per * sw, st);
         });
         if (rc < 0) return -1;
         if (Q == 2) blocks = rc;
@@ -575,7 +620,7 @@ void launch_residual(const T* v, const T* b, void* out, long pitch_out, double* 
 #define MGX_DECL_FUSED(T, SM, AR) \
     extern template bool launch_fused<T, SM, AR>(int, const T*, const T*, T*, int, long, int, int, T, T, int, int, int, int, hipStream_t, int, int);
 #define MGX_DECL_TILE(T, SM, AR) \
-    extern template int smooth_tiled<T, SM, AR>(T*, const T*, T*, int, long, int, double, int, FoldArgs, bool, int, bool, hipStream_t, int*);
+    extern template int smooth_tiled<T, SM, AR>(T*, const T*, T*, int, long, int, double, int, int, FoldArgs, bool, int, bool, hipStream_t, int*);
 #if !defined(MGX_INST_KIND) && !defined(MGX_SINGLE_TU)
 MGX_FOR_SMAR(MGX_DECL_CYCLE, double) MGX_FOR_SMAR(MGX_DECL_CYCLE, float)
 MGX_FOR_SMAR(MGX_DECL_FUSED, double) MGX_FOR_SMAR(MGX_DECL_FUSED, float)
