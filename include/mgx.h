@@ -300,7 +300,9 @@ MGX_API long mgx_level_pitch(int level, int dtype);
  * u <-> tmp; with shrink = 1 the range shrinks by one row per sweep at each
  * end that is not a global boundary (deep-halo communication avoidance): the
  * first sweep then covers [row_lo - (mu-1), row_hi + (mu-1)) clipped to the
- * unknown rows.  *result_in_tmp is set to 1 when mu is odd. */
+ * unknown rows.  *result_in_tmp is set to 1 when the block made an odd number of
+ * launches: sweeps may be fused, so a block of 10 sweeps run as one pass leaves
+ * the result in tmp. */
 MGX_API int mgx_slab_jacobi(const mgx_slab* s, void* u, const void* b, void* tmp,
                             int row_lo, int row_hi, int mu, double omega, int shrink,
                             int* result_in_tmp, void* stream);

@@ -278,22 +278,14 @@ int copy_out(mgx_solver* s, Level& l, const void* src_grid, void* dst, size_t co
 // ---- operators on the working hierarchy -----------------------------------------------
 inline bool tile_level(const mgx_solver* s, const Level& l) { return s->fuse.tile_max_n > 0 && l.N <= s->fuse.tile_max_n; }
 
-void smooth_t(mgx_solver* s, Level& l, int mu)
+// the plan request of a smoothing block on a whole level: the slab of all its rows, register tiles for levels of
+// N <= tile_max_n
+BlockReq level_req(const mgx_solver* s, const Level& l, int mu, bool pre, int post, bool zero_in, int rpc)
 {
-    with_kernel_set(l.f64, s->cfg.smoother, s->fuse.arith, [&](auto k) {
-        using K = decltype(k);
-        using T = typename K::T;
-        int parity = 0, launches = 0;
-        if (tile_level(s, l) && smooth_tiled<T, K::SM, K::AR>((T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, mu, s->cfg.omega,
-                                                              s->fuse.tile_k, tile_band<T>(s->fuse, l.N), FoldArgs(), false, 0, false,
-                                                              s->stream, &launches) >= 0)
-            parity = launches & 1;
-        else
-            (void)smooth_block<T>(s->cfg.smoother, (T*)l.u, (const T*)l.b, (T*)l.tmp, l.N, l.pitch, l.rows, 1, l.N, mu,
-                                  s->cfg.omega, false, 1, l.N, 0, s->rows_per_chunk, s->fuse, s->stream, &parity, &launches);
-        s->last_smooth_launches = launches;
-        if (parity) std::swap(l.u, l.tmp);
-    });
+    BlockReq q{s->cfg.smoother, l.f64, l.N, 0, l.rows, 1, l.N, mu, pre, post, zero_in};
+    q.tile_points = (long)(s->fuse.tile_max_n - 1) * s->fuse.tile_max_n;
+    q.rpc = rpc;
+    return q;
 }
 
 // ---- general per-level operators (cfg.op = MGX_OPERATOR_STENCIL5; kernels in mgx_var.hpp) ---------------
@@ -370,104 +362,26 @@ void residual_var_t(mgx_solver* s, const Level& l, const void* u, const void* b,
     if (MODE == 1) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, s->partial, g.blocks, s->sum_dev);
 }
 
-// ---- planning the passes of a folded smoothing block ------------------------------------------
-// Pass costs relative to a pass of up to 5 levels (HBM-bound: ~385 us at 8192^2 in double whatever
-// its depth), from bench.py runs with explicit plans (MGX_PLAN_PRE / MGX_PLAN_POST) against each other
-// inside one GPU call.  Round 2, double, after the deep passes got their rhs window in LDS and
-// branch-free interior bodies (rows really in flight): 6 levels 1.05, 8 levels 1.12, 10 levels 1.46
-// (0.56 ms) - a 10-level pass now costs less than two 5-level ones, so V(10,10) is planned as ONE
-// pass per block ([10]: 1.93 ms per cycle against 2.35 as [5,5], 2.28 as [8,2], 2.35 as [6,4]).
-// float (no LDS variants, packed arithmetic): 6: 1.34, 8: 1.53; red-black Gauss-Seidel (levels =
-// 2 x sweeps) 6: 1.1, 8: 1.3, 10: 2.4.  MGX_FOLD_KMAX / _BIG / _NOPOST / _GS still cap the depth.
-inline double fold_pass_cost(int K, int smoother, int N, int post, bool f64, int arith)
-{
-    const bool rbgs = (smoother == MGX_SMOOTHER_RBGS);
-    if (!cycle_k_supported(K, rbgs, f64, post, false, arith)) return -1.0;
-    (void)N;
-    if (rbgs) return K <= 4 ? 1.0 : (K == 6 ? 1.1 : (K == 8 ? 1.3 : 2.4));
-    if (K <= 5) return 1.0;
-    if (!f64) return K == 6 ? 1.34 : (K == 8 ? 1.53 : 1.75);      // (10 levels: rhs window in LDS since round 3)
-    if (K == 6) return 1.05;
-    if (K == 8) return 1.12;
-    return 1.46;
-}
-
-// The passes of a folded smoothing block of mu sweeps on a grid of N: parts[] = sweeps per pass, returns their
-// count.  pre: the first pass adds the correction; post: the last pass restricts the residual (1) or sums its
-// squares (2).  An explicit plan (FuseCfg::plan_pre / plan_post) wins when it fits; otherwise the DP over the
-// measured rates, deepest pass first (the last pass carries the residual stage, which is what gets expensive with
-// depth; a leading single sweep could not synthesise a zero input), capped at the folded kernels' depth.
-int fold_plan(const FuseCfg& f, int smoother, int N, bool f64, int mu, bool pre, int post, int* parts)
-{
-    const bool rbgs = (smoother == MGX_SMOOTHER_RBGS);
-    const int per = rbgs ? 2 : 1;
-    const int* forced = nullptr;
-    int nf = 0;
-    if (!pre && post == 1) { forced = f.plan_pre; nf = f.n_pre; }
-    else if (pre) { forced = f.plan_post; nf = f.n_post; }
-    if (nf > 0 && N >= f.plan_min_n) {
-        int sum = 0;
-        bool ok = true;
-        for (int i = 0; i < nf; ++i) {
-            sum += forced[i];
-            const int K = per * forced[i];
-            const bool folded = (i == 0 && pre) || (i == nf - 1 && post != 0);
-            const int q = (i == nf - 1) ? post : 0;
-            ok = ok && K <= 10 && (folded ? cycle_k_supported(K, rbgs, f64, q, pre && i == 0, f.arith) : (K != 7 && K != 9 && (!rbgs || K % 2 == 0)));
-        }
-        if (ok && sum == mu) {
-            for (int i = 0; i < nf; ++i) parts[i] = forced[i];
-            return nf;
-        }
-    }
-    int kcap = N >= 8192 ? f.fold_kmax_big : f.fold_kmax;
-    if (post == 0) kcap = std::min(kcap, f.fold_kmax_nopost);
-    if (rbgs) kcap = std::min(kcap, env_int("MGX_FOLD_KMAX_GS", 10));
-    if (pre && post == 1) kcap = std::min(kcap, 8);         // correction and restriction may meet in one pass: at most 8 levels
-    const int smax = std::max(1, kcap / per);
-    std::vector<double> best(mu + 1, 1e300);
-    std::vector<int> pick(mu + 1, 1);
-    best[0] = 0.0;
-    for (int m = 1; m <= mu; ++m)
-        for (int k = 1; k <= std::min(m, smax); ++k) {
-            const double c = fold_pass_cost(per * k, smoother, N, post, f64, f.arith);
-            if (c < 0.0) continue;
-            // a block done in ONE pass carries the correction AND the residual stage: some depths exist for either only
-            if (k == mu && m == mu && !cycle_k_supported(per * k, rbgs, f64, post, pre, f.arith)) continue;
-            const double t = best[m - k] + c + 1e-3;      // equal sums: fewer passes
-            if (t < best[m] - 1e-12) { best[m] = t; pick[m] = k; }
-        }
-    int n = 0;
-    for (int m = mu; m > 0; m -= pick[m]) parts[n++] = pick[m];
-    std::sort(parts, parts + n, [](int a, int b) { return a > b; });
-    return n;
-}
-
-// ---- a folded smoothing block ----------------------------------------------------------------------
-// mu sweeps on the local rows [row_lo, row_hi) of slab f with the cycle's transfers folded into the passes
-// (k_jacobi_cycle / k_tile_smooth on the window of rows the slab holds; a whole level is the slab row0 = 0,
-// rows = N + 1).  coarse_e (slab c, may be null): the first pass adds the prolonged correction while loading.
-// post 1: the last pass restricts the residual into coarse rows [crow_lo, crow_hi) of coarse_b and zeroes them
-// in coarse_zero (may be null); post 2: it writes per-block sums of r^2 to `partial`.  Local row numbers in,
-// global ones to the kernels.  Returns the number of partial sums written (0 unless post 2), < 0 when the block
-// cannot run as asked; *flips = launches made (the result is in tmp when odd).
+// ---- the executor of smoothing blocks ----------------------------------------------------------------
+// Runs the plan of q (fold_plan) on u <-> tmp, the arrays of the window q.row0 .. q.row0 + q.rows - 1 (a whole level:
+// row0 = 0, rows = N + 1).  c (may be null): the coarse window; coarse_e: the correction of q.pre; post 1: the residual
+// restricted into coarse rows [crow_lo, crow_hi) of coarse_b, zeroed in coarse_zero (may be null); post 2: per-block sums
+// of r^2 in `partial`.  Returns the number of those sums (0 unless post 2), < 0 when the block cannot run as asked (then
+// before any launch); *flips = launches made (the result is in tmp when odd).
 template <typename T, int SM, int AR>
-int fold_block(const FuseCfg& fc, long tile_points, const mgx_slab* f, T* u, const T* b, T* tmp, int row_lo, int row_hi,
-               int mu, double omega, const mgx_slab* c, const T* coarse_e, T* coarse_b, T* coarse_zero, int crow_lo,
-               int crow_hi, int restrict_mode, int zero_in, int post, double* partial, hipStream_t st, int* flips)
+int fold_block(const FuseCfg& fc, const BlockReq& q, T* u, const T* b, T* tmp, long pitch, double omega, const mgx_slab* c,
+               const T* coarse_e, T* coarse_b, T* coarse_zero, int crow_lo, int crow_hi, int restrict_mode, double* partial,
+               hipStream_t st, int* flips)
 {
-    constexpr bool rbgs = (SM == 1);
-    constexpr int per = rbgs ? 2 : 1;
-    const bool pre = (coarse_e != nullptr);
-    const int N = 1 << f->level;
-    const long pitch = level_pitch(f->level, f->dtype);
-    const int first = 1 - f->row0, last = N - f->row0;        // local unknown rows [first, last)
+    std::vector<Pass> plan;
+    if (!fold_plan(fc, q, &plan)) return -1;
+    const int N = q.N, row0 = q.row0;
     const JacobiCoef<T> jc = jacobi_coef<T>(omega);
     FoldArgs fa;
     fa.restrict_mode = restrict_mode;
     fa.partial = partial;
-    fa.win.row_first = std::max(f->row0, 0);
-    fa.win.row_last = std::min(f->row0 + f->rows - 1, N);
+    fa.win.row_first = std::max(row0, 0);
+    fa.win.row_last = std::min(row0 + q.rows - 1, N);
     fa.win.crow_first = 0; fa.win.crow_last = -1; fa.win.emit_lo = 0; fa.win.emit_hi = 0;
     if (c) {
         fa.cpitch = level_pitch(c->level, c->dtype);
@@ -481,100 +395,61 @@ int fold_block(const FuseCfg& fc, long tile_points, const mgx_slab* f, T* u, con
         if (coarse_b) fa.coarse_b = coarse_b - cback;
         if (coarse_zero) fa.coarse_zero = coarse_zero - cback;
     }
-    const long back = (long)f->row0 * pitch;
-    // Register tiles (k_tile_smooth): the whole block in one launch of independent tiles, where a marching pass would be
-    // latency-bound - R + 2K row steps one after the other, however few rows (small levels; 2048^2 slabs of 256 rows at
-    // 8 GPUs, the edge bands of an overlapped exchange).  Same arithmetic in the same order: same bits.  Ranges of at
-    // most tile_points rows x N; a block deeper than one tile launch only on a range that needs no rows beyond it (a
-    // whole grid), since the tile launches do not widen their range for the ones that follow.
-    {
-        const int lo = std::max(std::max(row_lo, first), 1), hi = std::min(std::min(row_hi, last), f->rows - 1);
-        const bool whole = row_lo <= first && row_hi >= last;
-        if (fc.tile_max_n > 0 && hi > lo && (long)(hi - lo) * N <= tile_points && (per * mu <= fc.tile_k || whole)) {
-            fa.row_lo = lo + f->row0; fa.row_hi = hi + f->row0;
-            return smooth_tiled<T, SM, AR>(u - back, b - back, tmp - back, N, pitch, mu, omega, fc.tile_k, tile_band<T>(fc, N), fa,
-                                           pre, post, zero_in != 0, st, flips);
-        }
-    }
-    int parts[64];
-    const int np = fold_plan(fc, rbgs ? MGX_SMOOTHER_RBGS : MGX_SMOOTHER_JACOBI, N, sizeof(T) == 8, mu, pre, post, parts);
-    const int rpc = env_int("MGX_ROWS", 0);                    // rows per chunk of a single sweep (0: one wave per row)
+    const long back = (long)row0 * pitch;
     T* src = u; T* dst = tmp;
-    int done = 0, blocks = 0;
-    for (int p = 0; p < np; ++p) {
-        const int sw = parts[p], K = per * sw;
-        const bool P = pre && p == 0;
-        const int Q = (p == np - 1) ? post : 0;
-        fa.zero_in = (p == 0 && zero_in) ? 1 : 0;              // PS:613: the first pass synthesises the zero guess
-        // rows the later passes still consume; the norm / restriction stage of the last pass also
-        // needs the result one / two rows beyond its range (it recomputes those rows itself, from
-        // this pass's output)
-        const int ext = per * (mu - (done + sw)) + (p != np - 1 ? (post == 2 ? 1 : (post == 1 ? 2 : 0)) : 0);
-        // never beyond the unknown rows, and never the slab's first or last row unless it is a global
-        // boundary's neighbour: a row is updated from the rows above and below it, and the single-sweep
-        // kernel (k_jacobi_rows) reads them without asking whether they exist
-        const int lo = std::max(std::max(row_lo - ext, first), 1), hi = std::min(std::min(row_hi + ext, last), f->rows - 1);
-        if (hi > lo) {
-            const int R = fuse_rows(fc, N, K, sizeof(T) == 8, hi - lo);
-            if (P || Q) {
-                if (!cycle_k_supported(K, rbgs, sizeof(T) == 8, Q, P, AR)) return -1;
-                fa.row_lo = lo + f->row0; fa.row_hi = hi + f->row0;
-                const int Rc = fuse_rows_auto(fc, N, K, sizeof(T) == 8) ? -R : R;      // folded passes: sized by the launcher
-                const int rc = with_stages(P, Q, [&](auto s) {
+    int blocks = 0;
+    for (const Pass& p : plan) {
+        if (p.hi > p.lo) {
+            const int lo = p.lo - row0, hi = p.hi - row0;             // local rows
+            fa.row_lo = p.lo; fa.row_hi = p.hi;
+            fa.zero_in = p.zero_in ? 1 : 0;                           // PS:613: the first pass synthesises the zero guess
+            int rc = 0;
+            if (p.kind == PASS_JACOBI)
+                rc = launch_jacobi<T>(src, b, dst, N, pitch, lo, hi, omega, p.R, st, q.rows, AR) ? -1 : 0;
+            else if (p.kind == PASS_RBGS)
+                launch_rbgs<T>(src, b, dst, N, pitch, lo, hi, row0 & 1, -row0, N - row0, p.R, st);
+            else if (p.kind == PASS_FUSED)
+                rc = launch_fused<T, SM, AR>(p.K, src, b, dst, N, pitch, lo, hi, jc.c0, jc.c1, -row0, N - row0, row0 & 1, p.R, st,
+                                             q.rows, fa.zero_in) ? 0 : -1;
+            else if (p.kind == PASS_FOLDED)
+                rc = with_stages(p.pre, p.post, [&](auto s) {
                     using S = decltype(s);
                     if constexpr (S::PRE || S::POST)
-                        return launch_cycle<T, S::PRE, S::POST, SM, AR>(K, src - back, b - back, dst - back, fa, N, pitch, jc.c0, jc.c1, Rc, st);
+                        return launch_cycle<T, S::PRE, S::POST, SM, AR>(p.K, src - back, b - back, dst - back, fa, N, pitch, jc.c0, jc.c1, p.R, st);
                     else
                         return -1;
                 });
-                if (rc < 0) return -1;
-                if (Q == 2) blocks = rc;
-            } else if (!rbgs && K == 1) {
-                if (fa.zero_in) return -1;                     // a stand-alone single sweep reads its input
-                if (launch_jacobi<T>(src, b, dst, N, pitch, lo, hi, omega, rpc, st, f->rows, AR)) return -1;
-            } else if (!launch_fused<T, SM, AR>(K, src, b, dst, N, pitch, lo, hi, jc.c0, jc.c1, first - 1, last, f->row0 & 1, R, st, f->rows, fa.zero_in)) {
-                return -1;
-            }
+            else
+                rc = launch_tile_pass<T, SM, AR>(src - back, b - back, dst - back, fa, N, pitch, jc.c0, jc.c1, p.K, p.R, p.pre, p.post, st);
+            if (rc < 0) return -1;                                    // (the plan rules these out)
+            if (p.post == 2) blocks = rc;
         }
         std::swap(src, dst);
-        done += sw;
     }
-    *flips = np;
+    *flips = (int)plan.size();
     return blocks;
 }
 
-// pre-check made before any launch (so a `false` never leaves a half-done block)
-bool fold_eligible(const mgx_solver* s, const Level& l, int mu, bool pre = false, int post = 1)
+// May a whole level run this block with folded stages?  Decided before any launch (a `false` never leaves a half-done
+// block): the handle's settings, then whether a plan exists.
+bool fold_eligible(const mgx_solver* s, const Level& l, int mu, bool pre = false, int post = 1, bool zero_in = false)
 {
     if (!s->fold || mu < 1 || mu > 64) return false;
     // general operators have no fused / folded kernels; the folded restriction is full weighting
     if (s->var || (post == 1 && s->cfg.restrict_mode >= MGX_RESTRICT_INJECT)) return false;
-    if (tile_level(s, l)) return true;
-    if (l.N < s->fuse.min_n) return false;
-    const bool rbgs = (s->cfg.smoother == MGX_SMOOTHER_RBGS);
-    const int per = rbgs ? 2 : 1;
-    if (s->fuse.kmax < per) return false;
-    int parts[64];
-    const int np = fold_plan(s->fuse, s->cfg.smoother, l.N, l.f64, mu, pre, post, parts);
-    for (int p = 0; p < np; ++p)
-        if (!cycle_k_supported(per * parts[p], rbgs, l.f64, p == np - 1 ? post : 0, pre && p == 0, s->fuse.arith)) return false;
-    return true;
+    const int per = (s->cfg.smoother == MGX_SMOOTHER_RBGS) ? 2 : 1;
+    if (!tile_level(s, l) && (l.N < s->fuse.min_n || s->fuse.kmax < per)) return false;
+    std::vector<Pass> plan;
+    return fold_plan(s->fuse, level_req(s, l, mu, pre, post, zero_in, 0), &plan);
 }
 
 // May the pre-smoothing of `level` start from an implicit zero iterate (the producer then
-// skips the zero fill)?  Only when its first pass is a kernel that honours zero_in: a folded
-// or fused pass, not a stand-alone single sweep.
+// skips the zero fill)?  Only when its plan's first pass is a kernel that honours zero_in: a folded,
+// fused or tile pass, not a stand-alone single sweep.
 bool zero_in_ok(const mgx_solver* s, int level)
 {
     if (!s->use_zero_in || level <= s->cfg.coarsest_level) return false;
-    const Level& l = s->lv[level];
-    const int mu = s->cfg.mu1;
-    if (!fold_eligible(s, l, mu)) return false;
-    if (tile_level(s, l)) return true;
-    const bool rbgs = (s->cfg.smoother == MGX_SMOOTHER_RBGS);
-    int parts[64];
-    const int np = fold_plan(s->fuse, s->cfg.smoother, l.N, l.f64, mu, false, 1, parts);
-    return !(np >= 2 && !rbgs && parts[0] == 1);      // a leading plain single Jacobi sweep reads its input
+    return fold_eligible(s, s->lv[level], s->cfg.mu1, false, 1, true);
 }
 
 // mu sweeps on a whole level with the prolongation+correction applied while loading (pre) and/or the
@@ -586,7 +461,7 @@ bool smooth_folded(mgx_solver* s, int level, int mu, bool pre, int post, bool ze
     if (!fold_eligible(s, l, mu, pre, post)) return false;
     const bool fine = (level == s->cfg.finest_level);
     const bool rbgs = (s->cfg.smoother == MGX_SMOOTHER_RBGS);
-    // float: the 10-level pass with BOTH the correction stage and the norm stage does not fit its registers (mgx_launch.hpp,
+    // float: the 10-level pass with BOTH the correction stage and the norm stage does not fit its registers (mgx_pass_plan.hpp,
     // cycle_k_supported) and a block of 10 would run as two passes of 5 (8192^2: 223 + 190 us); one 10-level pass without
     // the norm stage and the stand-alone norm kernel are 216 + ~110 us.  (The same for the restriction stage of the
     // separately rounded mode - 10 levels + the stand-alone residual / restriction instead of 8 + 2 - was measured and is
@@ -596,20 +471,20 @@ bool smooth_folded(mgx_solver* s, int level, int mu, bool pre, int post, bool ze
         post = 0;
     {
         Prof p(s, fine ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, mu);
-        // the whole level is the slab of all its rows, the level below it the coarse slab; the restriction stage zeroes
+        // the level below is the coarse window of the whole level; the restriction stage zeroes
         // the coarse guess (PS:613) unless that level's first pre-smoothing pass synthesises it
         const Level& c = s->lv[level - 1];
         const int dt = l.f64 ? MGX_DTYPE_F64 : MGX_DTYPE_F32;
-        const mgx_slab fs{level, dt, l.rows, 0, s->cfg.arith}, cs{level - 1, dt, c.rows, 0, s->cfg.arith};
+        const mgx_slab cs{level - 1, dt, c.rows, 0, s->cfg.arith};
         void* czero = (post == 1 && s->zero_in_level == c.L) ? nullptr : c.u;
-        const long tile_points = (long)(s->fuse.tile_max_n - 1) * s->fuse.tile_max_n;      // whole levels of N <= tile_max_n
+        const BlockReq q = level_req(s, l, mu, pre, post, zero_in, env_int("MGX_ROWS", 0));
         int launches = 0;
         const int nb = with_kernel_set(l.f64, s->cfg.smoother, s->fuse.arith, [&](auto k) {
             using K = decltype(k);
             using T = typename K::T;
-            return fold_block<T, K::SM, K::AR>(s->fuse, tile_points, &fs, (T*)l.u, (const T*)l.b, (T*)l.tmp, 1, l.N, mu,
-                                               s->cfg.omega, &cs, pre ? (const T*)c.u : nullptr, post == 1 ? (T*)c.b : nullptr,
-                                               (T*)czero, 1, c.N, s->cfg.restrict_mode, zero_in, post, s->partial, s->stream, &launches);
+            return fold_block<T, K::SM, K::AR>(s->fuse, q, (T*)l.u, (const T*)l.b, (T*)l.tmp, l.pitch, s->cfg.omega, &cs,
+                                               pre ? (const T*)c.u : nullptr, post == 1 ? (T*)c.b : nullptr, (T*)czero, 1, c.N,
+                                               s->cfg.restrict_mode, s->partial, s->stream, &launches);
         });
         if (nb < 0) return false;
         if (launches & 1) std::swap(l.u, l.tmp);
@@ -619,6 +494,21 @@ bool smooth_folded(mgx_solver* s, int level, int mu, bool pre, int post, bool ze
     // (the norm stage left out: mgx_solve's residual_norm_grid finds norm_blocks_ready == 0 and runs the norm kernel)
     if (fine) s->fine_updates += (double)mu * (double)(l.N - 1) * (double)(l.N - 1);
     return true;
+}
+
+// mu sweeps on a whole level, no folded stage
+void smooth_t(mgx_solver* s, Level& l, int mu)
+{
+    int launches = 0;
+    with_kernel_set(l.f64, s->cfg.smoother, s->fuse.arith, [&](auto k) {
+        using K = decltype(k);
+        using T = typename K::T;
+        (void)fold_block<T, K::SM, K::AR>(s->fuse, level_req(s, l, mu, false, 0, false, s->rows_per_chunk), (T*)l.u, (const T*)l.b,
+                                          (T*)l.tmp, l.pitch, s->cfg.omega, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
+                                          s->stream, &launches);
+    });
+    s->last_smooth_launches = launches;
+    if (launches & 1) std::swap(l.u, l.tmp);
 }
 
 void smooth(mgx_solver* s, int level, int mu)
@@ -727,7 +617,7 @@ void vcycle(mgx_solver* s, int level)
     // PS:581 pre-smoothing + PS:604-613 residual, restriction, zero coarse guess:
     // one set of passes when the level is eligible for folding
     if (!smooth_folded(s, level, s->cfg.mu1, false, 1, zin_here)) {
-        if (zin_here) (void)zero_u(s, level);                 // cannot happen (zero_in_ok == fold_eligible); stay correct
+        if (zin_here) (void)zero_u(s, level);                 // cannot happen (zero_in_ok planned this block); stay correct
         smooth(s, level, s->cfg.mu1);                         // PS:581
         restrict_level(s, level, true, !zin_next);            // PS:604-613
     }
@@ -1913,25 +1803,34 @@ long mgx_slab_scratch_doubles(const mgx_slab* s)
     return cap + 8;
 }
 
+// the plan request of a block on slab s (mgx_slab_jacobi / _rbgs / _cycle): knobs read per call
+static BlockReq slab_req(const mgx_slab& s, int smoother, int row_lo, int row_hi, int mu, bool pre = false, int post = 0,
+                         bool zero_in = false)
+{
+    BlockReq q{smoother, s.dtype == MGX_DTYPE_F64, 1 << s.level, s.row0, s.rows, row_lo, row_hi, mu, pre, post, zero_in};
+    q.rpc = env_int("MGX_ROWS", 0);
+    return q;
+}
+
 static int slab_smooth(int smoother, const mgx_slab* s, void* u, const void* b, void* tmp, int row_lo, int row_hi,
                        int mu, double omega, int shrink, int* result_in_tmp, void* stream)
 {
     if (slab_check(s) || !u || !b || !tmp || mu < 0) return MGX_ERR_INVALID;
-    const int N = 1 << s->level;
-    const long pitch = level_pitch(s->level, s->dtype);
-    const int first = 1 - s->row0, last = N - s->row0;      // unknown rows are [first, last)
-    const int rpc = env_int("MGX_ROWS", 0);
     FuseCfg fc = fuse_cfg();
     fc.arith = s->arith;
-    int parity = 0, rc;
-    if (s->dtype == MGX_DTYPE_F64)
-        rc = smooth_block<double>(smoother, (double*)u, (const double*)b, (double*)tmp, N, pitch, s->rows, row_lo, row_hi,
-                                  mu, omega, shrink != 0, first, last, s->row0 & 1, rpc, fc, (hipStream_t)stream, &parity);
-    else
-        rc = smooth_block<float>(smoother, (float*)u, (const float*)b, (float*)tmp, N, pitch, s->rows, row_lo, row_hi,
-                                 mu, omega, shrink != 0, first, last, s->row0 & 1, rpc, fc, (hipStream_t)stream, &parity);
-    if (rc) return rc;
-    if (result_in_tmp) *result_in_tmp = parity;
+    BlockReq q = slab_req(*s, smoother, row_lo, row_hi, mu);
+    q.widen = shrink != 0;
+    q.strict = true;
+    const long pitch = level_pitch(s->level, s->dtype);
+    int flips = 0;
+    const int rc = with_kernel_set(q.f64, smoother, s->arith, [&](auto k) {
+        using K = decltype(k);
+        using T = typename K::T;
+        return fold_block<T, K::SM, K::AR>(fc, q, (T*)u, (const T*)b, (T*)tmp, pitch, omega, nullptr, nullptr, nullptr, nullptr,
+                                           0, 0, 0, nullptr, (hipStream_t)stream, &flips);
+    });
+    if (rc < 0) return MGX_ERR_INVALID;
+    if (result_in_tmp) *result_in_tmp = flips & 1;
     return hipGetLastError() == hipSuccess ? MGX_OK : MGX_ERR_HIP;
 }
 
@@ -1966,16 +1865,17 @@ int mgx_slab_cycle(const mgx_slab* f, void* u, const void* b, void* tmp, int row
     if (row_lo < 0 || row_hi > f->rows || row_lo + f->row0 < 1 || row_hi + f->row0 > N) return MGX_ERR_INVALID;
     FuseCfg fc = fuse_cfg();
     fc.arith = f->arith;
-    const long tile_points = env_int("MGX_SLAB_TILE_POINTS", 1 << 20);      // (read per call: the parity tests switch it)
     const int post = coarse_b ? 1 : (sum_dev ? 2 : 0);
+    BlockReq q = slab_req(*f, smoother, row_lo, row_hi, mu, coarse_e != nullptr, post, zero_in != 0);
+    q.tile_points = env_int("MGX_SLAB_TILE_POINTS", 1 << 20);      // (read per call: the parity tests switch it)
+    const long pitch = level_pitch(f->level, f->dtype);
     hipStream_t st = (hipStream_t)stream;
     int flips = 0;
-    const int nb = with_kernel_set(f->dtype == MGX_DTYPE_F64, smoother, f->arith, [&](auto k) {
+    const int nb = with_kernel_set(q.f64, smoother, f->arith, [&](auto k) {
         using K = decltype(k);
         using T = typename K::T;
-        return fold_block<T, K::SM, K::AR>(fc, tile_points, f, (T*)u, (const T*)b, (T*)tmp, row_lo, row_hi, mu, omega, c,
-                                           (const T*)coarse_e, (T*)coarse_b, nullptr, crow_lo, crow_hi, restrict_mode, zero_in, post,
-                                           scratch, st, &flips);
+        return fold_block<T, K::SM, K::AR>(fc, q, (T*)u, (const T*)b, (T*)tmp, pitch, omega, c, (const T*)coarse_e,
+                                           (T*)coarse_b, nullptr, crow_lo, crow_hi, restrict_mode, scratch, st, &flips);
     });
     if (nb < 0) return MGX_ERR_INVALID;
     if (post == 2) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, st, scratch, nb, sum_dev);

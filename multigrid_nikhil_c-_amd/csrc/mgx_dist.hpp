@@ -463,13 +463,13 @@ struct DistProf {
     hipStream_t st = nullptr;
 };
 
-// passes a folded block of mu sweeps is split into (what mgx_slab_cycle will launch)
+// passes a folded block of mu sweeps is split into (what mgx_slab_cycle will launch; -1: it cannot run)
 int dist_block_launches(const mgx_dist* d, int N, int mu, int post, bool pre = false)
 {
-    int parts[64];
     FuseCfg fc = fuse_cfg();
     fc.arith = d->cfg.arith;
-    return fold_plan(fc, d->cfg.smoother, N, d->f64, mu, pre, post, parts);
+    std::vector<Pass> plan;
+    return fold_plan(fc, BlockReq{d->cfg.smoother, d->f64, N, 0, N + 1, 1, N, mu, pre, post}, &plan) ? (int)plan.size() : -1;
 }
 
 // the CYCLE operation of a plan on local rows [row_lo,row_hi) of its range, on `stream` (the whole

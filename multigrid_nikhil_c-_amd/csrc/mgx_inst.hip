@@ -3,7 +3,7 @@
 // builds in parallel (see the end of mgx_launch.hpp and the Makefile):
 //   -DMGX_INST_KIND=1  launch_cycle<T, PRE, POST, SM, AR> for the (PRE, POST) pair number MGX_INST_PP
 //   -DMGX_INST_KIND=2  launch_fused<T, SM, AR>
-//   -DMGX_INST_KIND=3  smooth_tiled<T, SM, AR>  (all six (PRE, POST) pairs of k_tile_smooth and k_tile_wide)
+//   -DMGX_INST_KIND=3  launch_tile_pass<T, SM, AR>  (all six (PRE, POST) pairs of k_tile_smooth and k_tile_wide)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 
@@ -25,7 +25,7 @@ template int launch_cycle<T_, PP_, MGX_INST_SM, MGX_INST_AR>(int, const T_*, con
 #elif MGX_INST_KIND == 2
 template bool launch_fused<T_, MGX_INST_SM, MGX_INST_AR>(int, const T_*, const T_*, T_*, int, long, int, int, T_, T_, int, int, int, int, hipStream_t, int, int);
 #elif MGX_INST_KIND == 3
-template int smooth_tiled<T_, MGX_INST_SM, MGX_INST_AR>(T_*, const T_*, T_*, int, long, int, double, int, int, FoldArgs, bool, int, bool, hipStream_t, int*);
+template int launch_tile_pass<T_, MGX_INST_SM, MGX_INST_AR>(const T_*, const T_*, T_*, const FoldArgs&, int, long, T_, T_, int, int, bool, int, hipStream_t);
 #else
 #error "MGX_INST_KIND must be 1, 2 or 3"
 #endif

@@ -1,15 +1,14 @@
-// mgx_launch.hpp - host side of the kernels of mgx_kernels.hpp: launch geometry, the typed
-// launch wrappers, the pass planner (how mu sweeps are split into fused / folded launches) and
-// the tuning knobs.  No solver state here: the single-GPU handle (mgx.hip) and the slab
-// operators of the multi-GPU driver use the same functions.
+// mgx_launch.hpp - host side of the kernels of mgx_kernels.hpp: launch geometry and the typed launch
+// wrappers.  Which launches make up a smoothing block is decided by the pass planner (mgx_pass_plan.hpp).
+// No solver state here: the single-GPU handle (mgx.hip) and the slab operators of the multi-GPU
+// driver use the same functions.
 #pragma once
 
 #include "../../include/mgx.h"
 #include "mgx_kernels.hpp"
+#include "mgx_pass_plan.hpp"
 
 #include <algorithm>
-#include <cstdlib>
-#include <vector>
 
 namespace mgx {
 
@@ -19,26 +18,6 @@ inline long level_pitch(int level, int dtype)
     const long align = (dtype == MGX_DTYPE_F64) ? 32 : 64;   // 256 bytes
     return (N + 1 + align - 1) / align * align;
 }
-
-inline int env_int(const char* name, int dflt)
-{
-    const char* s = getenv(name);
-    return (s && *s) ? atoi(s) : dflt;
-}
-
-// temporal fusion knobs: levels per pass, chunk height (0 = by grid size), smallest
-// fused grid, levels per pass for the folded kernels
-struct FuseCfg {
-    int kmax; int rows; int min_n; int fold_kmax; int fold_kmax_big; int tile_max_n; int tile_k; int fold_kmax_nopost;
-    int tile_wide; int tile_short_n;    // register tiles: k_tile_wide for fp64 (1) / all levels (2), else k_tile_smooth; 8-row bands up to tile_short_n
-    // explicit pass plans (sweeps per pass) for the pre- / post-smoothing block of grids with
-    // N >= plan_min_n: tuning knobs MGX_PLAN_PRE / MGX_PLAN_POST ("8,2"), MGX_PLAN_MIN_N.  They apply to the
-    // folded blocks of whole levels and of slabs alike (fold_plan in mgx.hip)
-    int plan_pre[8] = {0}; int n_pre = 0; int plan_post[8] = {0}; int n_post = 0; int plan_min_n = 8192;
-    // mgx_config.arith (MGX_ARITH_*): not a tuning knob - it selects which of the two arithmetic modes of the
-    // Jacobi update every smoother kernel uses (jac_pt in mgx_kernels.hpp); set by the handle / the slab, never from the environment
-    int arith = 0;
-};
 
 // PS:127, 138-140: the Jacobi scalars c0 = 1 - omega, c1 = omega / 4.  The float path evaluates them in double
 // from the float omega and narrows them: the float bits depend on this exact expression.
@@ -99,8 +78,6 @@ void launch_rbgs(const T* vin, const T* b, T* vout, int N, long pitch, int row_l
                        row_lo, row_hi, g.R, g.strips, g.chunks, row_parity, bnd_lo, bnd_hi);
 }
 
-// chunk height >= R (in steps of `step`) for which a chunk's step count R + extra is a whole number of
-// loop trips, or one short of it when parity rules the exact fit out
 // K levels in one pass (k_jacobi_fused<T,K,SM>): K Jacobi sweeps (SM = 0) or K/2
 // red-black Gauss-Seidel sweeps (SM = 1)
 template <typename T, int K, int SM, int AR>
@@ -140,206 +117,6 @@ bool launch_fused(int K, const T* vin, const T* b, T* vout, int N, long pitch, i
     return false;
 }
 
-// chunk height of a fused pass: a chunk recomputes 2K halo rows, so the deeper the pass the
-// taller the chunk, against the parallelism short chunks give (all measured, bench.py sweeps
-// of MGX_FUSE_ROWS): K <= 2: 8 rows (flat from 8 to 24); K = 3, 4: 16-24 rows (8192^2 RB-GS
-// V(2,2) 1.52 -> 1.32 ms, Jacobi V(4,3) 1.45 -> 1.27 ms against 8 rows; 4-7 % at 4096^2 and
-// 2048^2); K >= 5: N/128 clamped to [8, 64] in double (flat between 48 and 96 at 8192^2), to
-// [8, 32] in float (a float wave covers twice the columns, so a grid has half the strips:
-// 8192^2 fp32 V(10,10) finest level 0.96 -> 0.90 ms at 32 rows)
-// deep double passes (K >= 8: two workgroups of four waves per CU = 2048 waves per round): whole
-// rounds.  One wave per (chunk, strip of 52-54 vectors): with cpr = 2048 / strips chunk rows per round,
-// `rows` rows in m rounds take R = rows / (m cpr); m = the fewest rounds with R <= 200.  Measured (one
-// pass, us): 4096^2 whole 183 at 36 rows, 154 at 84 (m = 1, 490 workgroups), 167-190 at 48-72 and
-// 90-108; 16384^2 whole 1947 at 72, 1807 at 200; 8192^2 whole 487-498 at 72 and 484-492 at 168 (flat; on
-// a box that clocks down under the f64 load, 540 against 492).  Fewer, taller chunks also recompute
-// fewer halo rows (2K + 3 per chunk).
-inline int fuse_rows_deep(int N, int rows)
-{
-    const int strips = (N / 2 + 51) / 52;
-    const int cpr = std::max(1, 2048 / strips);
-    for (int m = 1; m <= 64; ++m) {
-        const int R = (rows + m * cpr - 1) / (m * cpr);
-        if (R <= 200) return std::max(R, 16);
-    }
-    return 64;
-}
-
-// deep double passes on big grids, height not given by MGX_FUSE_ROWS: launch_cycle_k sizes the chunks itself
-// (edge tiles shorter than interior ones) - it is handed -fuse_rows(...)
-// (float: the 10-level passes, whose rhs window is in LDS like the deep double ones - until round 3 they ran 32-row
-// chunks, 52 row steps for 32 rows)
-inline bool fuse_rows_auto(const FuseCfg& fc, int N, int K, bool f64)
-{
-    return fc.rows <= 0 && K >= (f64 ? 8 : 10) && N >= 2048;
-}
-
-inline int shallow_big_n() { static const int n = env_int("MGX_SHALLOW_BIG_N", 8192); return n; }
-// (4096^2: 48 rows - config 2's V(2,1) cycle 0.416-0.418 -> 0.389-0.395 ms, the 4096^2 level of config 3 -4 %; 96 there: 0.402)
-inline int shallow_mid_rows() { static const int r = env_int("MGX_SHALLOW_ROWS_MID", 48); return r; }
-
-inline int fuse_rows(const FuseCfg& fc, int N, int K, bool f64 = true, int rows = 0)
-{
-    if (fc.rows > 0) return fc.rows;
-    if (K <= 2) {
-        // (8192^2 and up: 96 rows like the K <= 4 passes below - together −2..−3.5 % on the finest-level part of a V(2,1) cycle)
-        static const int big2 = env_int("MGX_SHALLOW2_ROWS_BIG", 96);
-        return N >= shallow_big_n() ? big2 : (N >= 4096 ? shallow_mid_rows() : 8);
-    }
-    if (K <= 4) {
-        // (8192^2 and up: 96 rows - finest-level part of the red-black V(2,1) cycle 0.828-0.833 -> 0.789 ms, Jacobi V(2,1)
-        // 0.811-0.817 -> 0.786-0.794; round 1's 24 rows paid (24 + 2K) / 24 in recomputed rows)
-        static const int big = env_int("MGX_SHALLOW_ROWS_BIG", 96);
-        return N >= shallow_big_n() ? big : (N >= 4096 ? shallow_mid_rows() : 16);
-    }
-    if (f64 && K >= 8 && N >= 2048) return fuse_rows_deep(N, rows > 0 ? rows : N - 1);
-    int R = N / 128;
-    if (R < 8) R = 8;
-    if (R > (f64 ? 64 : 32)) R = f64 ? 64 : 32;
-    return R;
-}
-
-inline FuseCfg fuse_cfg()
-{
-    FuseCfg f;
-    f.kmax = env_int("MGX_FUSE", 10);          // levels per pass; 1 disables temporal fusion
-    if (f.kmax < 1) f.kmax = 1;
-    if (f.kmax > 10) f.kmax = 10;
-    f.rows = env_int("MGX_FUSE_ROWS", 0);      // 0: chosen from the grid size
-    if (f.rows < 0) f.rows = 0;
-    // smallest grid (N = 2^L) on which fused / folded passes replace single sweeps
-    f.min_n = std::max(64, env_int("MGX_FUSE_MIN_N", 256));
-    // Levels per pass for the folded kernels.  They carry one more level window and the
-    // transfer state, so their sweet spot is shallower than the plain fused kernel's and
-    // flat: measured in one process on one MI355X, V(10,10) at 8192^2 fp64 takes 2.63 ms as
-    // [5,5] and 2.62 as [10] (244-256 VGPRs, 2 waves/SIMD); [5,5] is better on smaller grids.
-    f.fold_kmax = std::max(1, std::min(f.kmax, env_int("MGX_FOLD_KMAX", 10)));
-    // The same for grids with N >= 8192 (separate knob): there the deep variant [10] is
-    // device-dependent - 1.55 vs 1.62 ms for the finest level on one MI355X, 1.87 vs 1.50 ms on
-    // another (VALU-bound passes follow the clock the chip holds; the HBM-bound [5,5] does not).
-    f.fold_kmax_big = std::max(1, std::min(f.kmax, env_int("MGX_FOLD_KMAX_BIG", 10)));
-    // Whole levels up to this N (= 2^L) are smoothed by the LDS tile kernel, all sweeps of a
-    // block (up to tile_k levels) per launch; 0 disables it.  MGX_TILE_WIDE selects the kernel: k_tile_wide for fp64
-    // levels (1, the default), for fp32 levels too (2), or k_tile_smooth everywhere (0).  In fp32 k_tile_wide measured
-    // slower (bench --dtype f32: 0.918 against 0.902-0.910 ms), so fp32 levels keep k_tile_smooth by default.  At 2048^2 the tiles lose to the marching passes (k_tile_wide 64 + 64 us per V(10,10)
-    // against 47 + 44: 580 workgroups of one per CU are three rounds), so the default stays 1024.  MGX_TILE_SHORT_N:
-    // levels up to this N run k_tile_wide with 8-row bands (tile_wide_rw, mgx_geom.hpp).
-    f.tile_wide = std::max(0, std::min(2, env_int("MGX_TILE_WIDE", 1)));
-    f.tile_short_n = env_int("MGX_TILE_SHORT_N", 512);
-    f.tile_max_n = std::max(0, env_int("MGX_TILE_MAX_N", 1024));
-    f.tile_k = std::max(2, std::min(10, env_int("MGX_TILE_K", 10)));
-    // levels per folded pass for blocks that end WITHOUT a residual stage (post-smoothing below
-    // the finest level): those passes keep c1 * b in their window and are cheaper per level
-    f.fold_kmax_nopost = std::max(1, std::min(f.kmax, env_int("MGX_FOLD_KMAX_NOPOST", 10)));
-    auto parse = [](const char* name, int* out) {
-        const char* v = std::getenv(name);
-        int n = 0;
-        while (v && *v && n < 8) {
-            char* end = nullptr;
-            const long k = std::strtol(v, &end, 10);
-            if (end == v || k < 1 || k > 10) return 0;
-            out[n++] = (int)k;
-            v = (*end == ',') ? end + 1 : end;
-            if (*end && *end != ',') return 0;
-        }
-        return n;
-    };
-    f.n_pre = parse("MGX_PLAN_PRE", f.plan_pre);
-    f.n_post = parse("MGX_PLAN_POST", f.plan_post);
-    f.plan_min_n = env_int("MGX_PLAN_MIN_N", 8192);
-    return f;
-}
-
-// Per-sweep throughput of a fused launch relative to one stand-alone sweep,
-// measured on MI355X at 8192^2 (tools/microbench, profiles/r01_fused_microbench.md).
-// Index = sweeps per launch; 0 = not instantiated.  Jacobi: K = 5 is poor in
-// float because it needs a second halo lane per side for one extra column.
-// Re-measured after the fused Jacobi passes started keeping c1 * b in their rhs window
-// (K - 1 fewer multiplications per point: fp64 K=8 1138 -> 1349 G upd/s, fp32 K=6 1457 -> 1852,
-// fp32 K=10 1371 -> 2019).
-constexpr double kFuseRate64[11] = {0, 1.00, 1.80, 2.45, 3.16, 3.81, 4.80, 0, 5.60, 0, 5.63};
-// float again after the row operators were written on pairs (all arithmetic packed:
-// v_pk_add_f32 / v_pk_mul_f32): K=5 1508 -> 1743, K=8 1731 -> 2301 G upd/s.
-constexpr double kFuseRate32[11] = {0, 1.00, 1.67, 2.38, 3.10, 3.77, 4.26, 0, 4.98, 0, 4.67};
-// red-black Gauss-Seidel: s sweeps = 2 s levels, s <= 5
-constexpr double kFuseRateGS64[11] = {0, 1.00, 1.81, 2.50, 3.19, 3.12, 0, 0, 0, 0, 0};
-constexpr double kFuseRateGS32[11] = {0, 1.00, 1.79, 2.20, 2.87, 2.69, 0, 0, 0, 0, 0};
-
-// split mu sweeps into fused launches minimising the modelled time; parts[] gets
-// the sweeps of each launch, returns their count.  kmax bounds the LEVELS per pass.
-inline int plan_fusion(int mu, int kmax, bool f64, int* parts, bool rbgs = false)
-{
-    const double* rate = rbgs ? (f64 ? kFuseRateGS64 : kFuseRateGS32) : (f64 ? kFuseRate64 : kFuseRate32);
-    const int per = rbgs ? 2 : 1;
-    const int smax = std::max(1, std::min(kmax, 10) / per);
-    std::vector<double> best(mu + 1, 1e300);
-    std::vector<int> pick(mu + 1, 1);
-    best[0] = 0.0;
-    for (int m = 1; m <= mu; ++m)
-        for (int k = 1; k <= std::min(m, smax); ++k) {
-            if (rate[k] <= 0.0) continue;
-            // + a small per-launch cost so that equal-rate splits prefer fewer launches
-            const double c = best[m - k] + (double)k / rate[k] + 0.02;
-            if (c < best[m]) { best[m] = c; pick[m] = k; }
-        }
-    int n = 0;
-    for (int m = mu; m > 0; m -= pick[m]) parts[n++] = pick[m];
-    return n;
-}
-
-// mu smoother sweeps on rows [row_lo,row_hi) ping-ponging a <-> b2; *parity = 1 when
-// the result ends in `b2`.  Unknown rows are [first, last) (so the global
-// boundary rows are first-1 and last).  shrink: deep-halo mode, the sweeps still
-// to come after a launch widen its range by `per` rows each at every interior
-// edge.  rows_alloc bounds every row that is read (validated, never assumed).
-template <typename T>
-int smooth_block(int smoother, T* a, const T* rhs, T* b2, int N, long pitch, int rows_alloc, int row_lo, int row_hi,
-                 int mu, double omega, bool shrink, int first, int last, int row_parity, int rpc, const FuseCfg& fc,
-                 hipStream_t st, int* parity, int* launches = nullptr)
-{
-    const bool rbgs = (smoother == MGX_SMOOTHER_RBGS);
-    const int per = rbgs ? 2 : 1;
-    const auto [c0, c1] = jacobi_coef<T>(omega);
-    T* src = a; T* dst = b2;
-    int flips = 0;
-    int done = 0;
-    // Fused launches pay (R + 2K)/R redundant rows and need enough chunks to fill
-    // the chip: measured worthwhile from 256^2 up, with R growing with the grid.
-    const bool allow_fuse = fc.kmax > per && N >= fc.min_n && (row_hi - row_lo) >= 64 && mu <= 64;
-    std::vector<int> parts(mu > 0 ? mu : 1, 1);
-    const int nparts = allow_fuse ? plan_fusion(mu, fc.kmax, sizeof(T) == 8, parts.data(), rbgs) : mu;
-    const int bl = first - 1, bh = last;
-    for (int p = 0; p < nparts; ++p) {
-        const int sw = allow_fuse ? parts[p] : 1;               // sweeps in this launch
-        const int K = per * sw;                                  // levels in this launch
-        const int ext = shrink ? per * (mu - (done + sw)) : 0;   // rows the later launches still consume
-        const int lo = std::max(row_lo - ext, first), hi = std::min(row_hi + ext, last);
-        if (hi > lo) {
-            // rows read: [lo-K, hi+K) clipped to the global boundary rows
-            const int rd_lo = std::max(lo - K, bl), rd_hi = std::min(hi + K - 1, bh);
-            if (rd_lo < 0 || rd_hi > rows_alloc - 1) return MGX_ERR_INVALID;
-            if (!rbgs && sw == 1) {
-                const int rc = launch_jacobi<T>(src, rhs, dst, N, pitch, lo, hi, omega, rpc, st, rows_alloc, fc.arith);
-                if (rc) return rc;
-            } else if (rbgs && !allow_fuse) {
-                launch_rbgs<T>(src, rhs, dst, N, pitch, lo, hi, row_parity, bl, bh, rpc, st);
-            } else {
-                const int R = fuse_rows(fc, N, K, sizeof(T) == 8, hi - lo);
-                const bool ok = rbgs ? launch_fused<T, 1, 0>(K, src, rhs, dst, N, pitch, lo, hi, c0, c1, bl, bh, row_parity, R, st, rows_alloc, 0)
-                                : (fc.arith ? launch_fused<T, 0, 1>(K, src, rhs, dst, N, pitch, lo, hi, c0, c1, bl, bh, row_parity, R, st, rows_alloc, 0)
-                                            : launch_fused<T, 0, 0>(K, src, rhs, dst, N, pitch, lo, hi, c0, c1, bl, bh, row_parity, R, st, rows_alloc, 0));
-                if (!ok) return MGX_ERR_INVALID;
-            }
-        }
-        std::swap(src, dst);
-        ++flips;
-        done += sw;
-    }
-    *parity = flips & 1;
-    if (launches) *launches = flips;
-    return MGX_OK;
-}
-
 // ---- smoother passes with the cycle's transfers folded in (k_jacobi_cycle) ----------
 struct FoldArgs {
     const void* coarse_e = nullptr;   // PRE: correction to add while loading
@@ -349,8 +126,7 @@ struct FoldArgs {
     double* partial = nullptr;        // POST 2: per-block sums of r^2
     long cpitch = 0;
     int zero_in = 0;                  // the input iterate is all zero: the pass does not read it
-    // rows to update, GLOBAL numbers, and the window of rows that exist; row_hi == 0: the whole
-    // grid (rows 1..N-1, window 0..N).  Slabs pass base pointers moved back by row0 rows.
+    // rows to update, GLOBAL numbers (base pointers moved back by the window's first row), and the window of rows that exist
     int row_lo = 0, row_hi = 0;
     CycleWin win{0, 0, 0, 0, 0, 0};
 };
@@ -382,9 +158,8 @@ int launch_cycle_k(const T* vin, const T* b, T* vout, const FoldArgs& fa, int N,
     constexpr bool BL = cycle_b_in_lds<T, K, POST, SM>();
     constexpr int E = (POST == 1 ? 3 : (POST == 2 ? 2 : 0)) + (cycle_skew<T, K, PRE, POST, SM, AR>() > 0 ? 1 : 0);   // row steps of a chunk beyond R + 2K
     constexpr int kTripSteps = BL ? kBRing : trip_steps<T>();
-    const bool whole = (fa.row_hi == 0);
-    const int row_lo = whole ? 1 : fa.row_lo, row_hi = whole ? N : fa.row_hi;
-    const CycleWin win = whole ? CycleWin{0, N, 0, N / 2, 1, N / 2} : fa.win;
+    const int row_lo = fa.row_lo, row_hi = fa.row_hi;
+    const CycleWin& win = fa.win;
     if (POST == 1 && !(row_lo & 1)) return -1;         // chunks must start on odd rows (POST = 1)
     const int strips = (N / VecOf<T>::W + OUT - 1) / OUT;
     const bool auto_rows = R < 0;
@@ -447,14 +222,6 @@ int launch_cycle(int K, const T* vin, const T* b, T* vout, const FoldArgs& fa, i
     return -1;
 }
 
-// levels per pass the folded kernels are instantiated for
-inline bool cycle_k_supported(int K, bool rbgs, bool f64, int post, bool pre, int arith)
-{
-    if (K == 10) return !(pre && post == 1) && !(rbgs && post == 1) && !(!f64 && pre && post == 2) && !(!f64 && post == 1 && arith == 0);
-    if (K == 8 && !f64 && !pre && post != 0) return false;
-    return rbgs ? (K == 2 || K == 4 || K == 6 || K == 8) : (K >= 1 && K <= 8 && K != 7);
-}
-
 // runtime (pre, post) -> the folded stages of k_jacobi_cycle / k_tile_smooth: f(Stages<PRE, POST>{}), all six pairs
 template <int PRE_, int POST_> struct Stages { static constexpr int PRE = PRE_, POST = POST_; };
 template <typename F>
@@ -472,10 +239,8 @@ int launch_tile(const T* vin, const T* b, T* vout, const FoldArgs& fa, int N, lo
     const int He = levels + tile_extra<POST>();
     const int TH = kTileSY - 2 * He, TW = kTileSX - 2 * He;
     if (TH < 8 || TW < 8) return -1;
-    // whole grid (fa.row_hi == 0), or rows [row_lo, row_hi) of a slab whose base pointers were moved back by row0 rows
-    const bool whole = (fa.row_hi == 0);
-    const int row_lo = whole ? 1 : fa.row_lo, row_hi = whole ? N : fa.row_hi;
-    const CycleWin win = whole ? CycleWin{0, N, 0, N / 2, 1, N / 2} : fa.win;
+    const int row_lo = fa.row_lo, row_hi = fa.row_hi;
+    const CycleWin& win = fa.win;
     const int tiles_y = (row_hi - row_lo + TH - 1) / TH, tiles_x = (N - 1 + TW - 1) / TW;
     if (tiles_y < 1) return 0;
     const T w = (fa.restrict_mode == MGX_RESTRICT_FW16) ? (T)0.0625 : (T)0.25;
@@ -492,9 +257,8 @@ int launch_tile_wide(const T* vin, const T* b, T* vout, const FoldArgs& fa, int 
 {
     // fp32: four columns per lane, 256-column arrays; 12-row bands would not fit the registers
     if (VecOf<T>::W == 4) rw = 8;
-    const bool whole = (fa.row_hi == 0);
-    const int row_lo = whole ? 1 : fa.row_lo, row_hi = whole ? N : fa.row_hi;
-    const CycleWin win = whole ? CycleWin{0, N, 0, N / 2, 1, N / 2} : fa.win;
+    const int row_lo = fa.row_lo, row_hi = fa.row_hi;
+    const CycleWin& win = fa.win;
     const TileWideGeom g = tile_wide_geom(N, row_lo, row_hi, levels + tile_extra<POST>(), VecOf<T>::W, rw);
     if (g.TH < 8 || g.TW < 8) return -1;
     if (g.tiles_y < 1) return 0;
@@ -515,41 +279,17 @@ int launch_tile_wide(const T* vin, const T* b, T* vout, const FoldArgs& fa, int 
     return g.tiles_y * g.tiles_x;
 }
 
-// band height of k_tile_wide for a level of N (= 2^L) of T, 0: k_tile_smooth
-template <typename T> int tile_band(const FuseCfg& fc, int N)
-{
-    return (fc.tile_wide >= (sizeof(T) == 8 ? 1 : 2)) ? tile_wide_rw(N, fc.tile_short_n) : 0;
-}
-
-// mu sweeps on rows [fa.row_lo, fa.row_hi) of the window fa.win (fa.row_hi == 0: a whole level), tile_k levels per
-// launch, a <-> b2 ping-pong (*flips launches made); pre / post as in fold_block (mgx.hip).  band: k_tile_wide's band
-// height (tile_band), 0 for k_tile_smooth.  Returns the number of norm partials (post == 2), < 0 on a launch error.
+// one register-tile launch of `levels` levels with the stages (pre, post): k_tile_wide with bands of `band` rows
+// (tile_band), k_tile_smooth when band = 0.  Returns the number of tiles, < 0 when the geometry does not fit.
 template <typename T, int SM, int AR>
-int smooth_tiled(T* a, const T* rhs, T* b2, int N, long pitch, int mu, double omega, int tile_k, int band, FoldArgs fa,
-                 bool pre, int post, bool zero_in, hipStream_t st, int* flips)
+int launch_tile_pass(const T* vin, const T* b, T* vout, const FoldArgs& fa, int N, long pitch, T c0, T c1, int levels,
+                     int band, bool pre, int post, hipStream_t st)
 {
-    constexpr int per = (SM == 1) ? 2 : 1;
-    const JacobiCoef<T> jc = jacobi_coef<T>(omega);
-    const int smax = std::max(1, tile_k / per);            // sweeps per launch
-    const int np = (mu + smax - 1) / smax;
-    T* src = a; T* dst = b2;
-    int blocks = 0;
-    for (int p = 0; p < np; ++p) {
-        const int sw = mu / np + (p < mu % np ? 1 : 0);
-        const bool P = pre && p == 0;
-        const int Q = (p == np - 1) ? post : 0;
-        fa.zero_in = (p == 0 && zero_in) ? 1 : 0;
-        const int rc = with_stages(P, Q, [&](auto s) {
-            using S = decltype(s);
-            return band ? launch_tile_wide<T, SM, S::PRE, S::POST, AR>(src, rhs, dst, fa, N, pitch, jc.c0, jc.c1, per * sw, band, st)
-                        : launch_tile<T, SM, S::PRE, S::POST, AR>(src, rhs, dst, fa, N, pitch, jc.c0, jc.c1, per * sw, st);
-        });
-        if (rc < 0) return -1;
-        if (Q == 2) blocks = rc;
-        std::swap(src, dst);
-    }
-    *flips = np;
-    return blocks;
+    return with_stages(pre, post, [&](auto s) {
+        using S = decltype(s);
+        return band ? launch_tile_wide<T, SM, S::PRE, S::POST, AR>(vin, b, vout, fa, N, pitch, c0, c1, levels, band, st)
+                    : launch_tile<T, SM, S::PRE, S::POST, AR>(vin, b, vout, fa, N, pitch, c0, c1, levels, st);
+    });
 }
 
 template <typename T>
@@ -620,7 +360,7 @@ void launch_residual(const T* v, const T* b, void* out, long pitch_out, double* 
 #define MGX_DECL_FUSED(T, SM, AR) \
     extern template bool launch_fused<T, SM, AR>(int, const T*, const T*, T*, int, long, int, int, T, T, int, int, int, int, hipStream_t, int, int);
 #define MGX_DECL_TILE(T, SM, AR) \
-    extern template int smooth_tiled<T, SM, AR>(T*, const T*, T*, int, long, int, double, int, int, FoldArgs, bool, int, bool, hipStream_t, int*);
+    extern template int launch_tile_pass<T, SM, AR>(const T*, const T*, T*, const FoldArgs&, int, long, T, T, int, int, bool, int, hipStream_t);
 #if !defined(MGX_INST_KIND) && !defined(MGX_SINGLE_TU)
 MGX_FOR_SMAR(MGX_DECL_CYCLE, double) MGX_FOR_SMAR(MGX_DECL_CYCLE, float)
 MGX_FOR_SMAR(MGX_DECL_FUSED, double) MGX_FOR_SMAR(MGX_DECL_FUSED, float)

@@ -190,7 +190,8 @@ def test_slab_entry_points_refuse_other_smoothers_and_restrictions(pkg, dt):
 def test_slab_cycle_equals_the_separate_slab_operators(pkg, po, dt, smoother, mu, path, extra, monkeypatch):
     """mgx_slab_cycle on an INTERIOR slab (halo rows on both sides, window narrower than the grid)
     against the oracle's whole-grid operators: correction on load, residual + restriction of
-    the result, and the norm of the result - and its argument checks."""
+    the result, and the norm of the result - and its argument checks; without a stage, against
+    mgx_slab_jacobi / mgx_slab_rbgs with shrink = 1."""
     for k in ("MGX_SLAB_TILE_POINTS", "MGX_PAIR_MIN_ROWS", "MGX_MIN_CHUNK"):
         monkeypatch.delenv(k, raising=False)
     if path != "tile":
@@ -265,3 +266,18 @@ def test_slab_cycle_equals_the_separate_slab_operators(pkg, po, dt, smoother, mu
     assert np.array_equal(cb[own_lo // 2 - clo:own_hi // 2 - clo, 1:NC], rr[own_lo // 2 - 1:own_hi // 2 - 1])
     st, *_ = run(True, 0, own_lo, own_hi, zero_in=1)
     assert st != 0                                   # a correction is added to an iterate that exists
+    # no stage: the block the slab smoother makes with shrink = 1, bit for bit
+    st, got, _, _ = run(False, 0, own_lo, own_hi)
+    assert st == 0
+    u, b, tmp = U[lo:hi].clone(), B[lo:hi].clone(), hm.zeros_like(U[lo:hi])
+    flag = C.c_int()
+    if smoother == "rbgs":
+        st = L.mgx_slab_rbgs(C.byref(fs), u.data_ptr(), b.data_ptr(), tmp.data_ptr(), own_lo - lo, own_hi - lo, mu, 1, C.byref(flag), None)
+    else:
+        st = L.mgx_slab_jacobi(C.byref(fs), u.data_ptr(), b.data_ptr(), tmp.data_ptr(), own_lo - lo, own_hi - lo, mu, 2.0 / 3.0, 1,
+                               C.byref(flag), None)
+    hm.synchronize()
+    assert st == 0
+    sep = (tmp if flag.value else u).cpu().numpy()
+    assert np.array_equal(got[own_lo - lo:own_hi - lo, 1:N], sep[own_lo - lo:own_hi - lo, 1:N])
+    assert np.array_equal(got[own_lo - lo:own_hi - lo, 1:N], sm(v, f, mu)[own_lo - 1:own_hi - 1])
