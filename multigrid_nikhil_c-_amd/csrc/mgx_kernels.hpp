@@ -1092,6 +1092,9 @@ template <typename T, int CW> struct CycleState {
     //   ct = nw + ne, tc = n (top row);  em = ((w + e) + n), mc = c (mid row)
     // four values instead of the six residuals: the folded restriction is register-bound
     T ct[CW], tc[CW], em[CW], mc[CW];
+    // PRE, bodies whose step parity is a compile-time fact: coarse row y>>1 of the current fine row y,
+    // CW+1 columns (loaded once, on the odd fine row that first needs it, and kept for the next two)
+    T ea[CW + 1];
     double acc;                 // POST 2: sum of r^2
 };
 
@@ -1144,6 +1147,27 @@ coarse_loads(PreFetch<T, VecOf<T>::W / 2>& pe, int y, const T* __restrict__ coar
     }
 }
 
+// PRE with a compile-time step parity: ONE coarse row I (CW+1 columns) into e.  Interior bodies: the nearest row that
+// exists (as coarse_loads); edge bodies: 0 where the row does not exist or the lane must not load - which fine rows
+// may use it is decided where it is used (cycle_step masks the correction of the others)
+template <typename T, bool EDGE>
+__device__ __forceinline__ void
+coarse_row(T (&e)[VecOf<T>::W / 2 + 1], int I, bool cld, const CycleWin& win, const FastOut& fo)
+{
+    constexpr int CW = VecOf<T>::W / 2;
+    if constexpr (!EDGE) {
+        const int Ic = min(max(I, win.crow_first), win.crow_last);
+        const unsigned srow = (unsigned)(Ic - fo.crb) * fo.cpitch_bytes;
+#pragma unroll
+        for (int k = 0; k <= CW; ++k) e[k] = bload1_s((T*)nullptr, fo.ce, fo.clane_off + (unsigned)(k * sizeof(T)), srow);
+    } else {
+        const bool ok = cld && I >= win.crow_first && I <= win.crow_last;
+        const unsigned at = (unsigned)(I - fo.crb) * fo.cpitch_bytes + fo.clane_off;
+#pragma unroll
+        for (int k = 0; k <= CW; ++k) e[k] = bload1((T*)nullptr, fo.ce, ok ? at + (unsigned)(k * sizeof(T)) : kOobOffset);
+    }
+}
+
 // loads of one step of k_jacobi_cycle (whole grids: rows 0..N exist)
 template <typename T, bool EDGE, bool ZIN = false>
 __device__ __forceinline__ void
@@ -1182,6 +1206,20 @@ cycle_loads(typename VecOf<T>::type& in, typename VecOf<T>::type& bn, int y,
 constexpr int kBRing = 12;                     // >= K + 1 for K <= 10, multiple of the 3 rotation phases
 // (float: from 10 levels - the 8-level float bodies fit their registers with the window in them and keep 3-step trips)
 template <typename T, int K, int POST, int SM> constexpr bool cycle_b_in_lds() { return (sizeof(T) == 8 && K >= 8) || (sizeof(T) == 4 && K >= 10); }
+// The deep bodies' trips are kBRing (even) steps long, so the parity of every step's fine row is a compile-time fact once
+// the march starts on a row of fixed parity, cycle_par(): that of the first cone row of a chunk that starts on an odd row
+// (whole grids: row_lo = 1 and even chunk heights, mgx_geom.hpp).  A chunk whose cone starts on the other parity starts its
+// march one row earlier (cycle_y0): one more row step before the cone, whose values are never stored.  The prolongation
+// and restriction stages then drop the work and the memory instructions the other parity would need.  -1: the shallow
+// bodies (3-step trips), which keep the run-time parity.
+static_assert(kBRing % 2 == 0, "the deep bodies' step parity needs an even trip");
+template <typename T, int K, int POST, int SM> constexpr int cycle_par() { return cycle_b_in_lds<T, K, POST, SM>() ? ((1 + K + (POST ? 1 : 0)) & 1) : -1; }
+template <typename T, int K, int POST, int SM> __device__ __forceinline__ int cycle_y0(int r0)
+{
+    constexpr int PAR = cycle_par<T, K, POST, SM>();
+    const int y0 = r0 - K - (POST ? 1 : 0);
+    return PAR < 0 ? y0 : y0 - ((y0 - PAR) & 1);
+}
 // Two level chains per step (round 3; built, bit-identical, measured, OFF).  A row step of a K-level pass is a serial
 // chain: level j needs level j-1's row of this very step, ten times over, and a wave's two points per lane are all the
 // independent work there is; the counters (profiles/r03a_sq_summary.md: vector ALU busy 0.64-0.67 with 1.6 waves per
@@ -1272,8 +1310,8 @@ constexpr int kPrefetchMax = MGX_PFD_DEEP > kPrefetch ? MGX_PFD_DEEP : kPrefetch
 template <typename T, bool BL, bool EDGE, int POST> constexpr int cycle_cpfd() { return (BL && !(EDGE && POST == 0)) ? cycle_pfd<BL, POST, EDGE>() : 1; }
 
 // RP: phase of the step inside the kBRing-fold unrolled loop (BL) or inside the 3-fold one (!BL);
-// the window-rotation phase is RP % 3 either way
-template <typename T, int K, int PRE, int POST, int SM, bool EDGE, int RP, bool BL, bool ZIN, int AR>
+// the window-rotation phase is RP % 3 either way; YP: the parity of y (deep bodies, see cycle_par) or -1 (run time)
+template <typename T, int K, int PRE, int POST, int SM, bool EDGE, int RP, bool BL, bool ZIN, int AR, int YP>
 __device__ __forceinline__ void
 cycle_step(typename VecOf<T>::type (&lev)[K + 1][3], typename VecOf<T>::type (&bw)[BL ? 1 : K + 1], lds_vec_ptr<T> ring,
            lds_vec_ptr<T> ring2, typename VecOf<T>::type (&rawq)[cycle_rawq<T, K, PRE, POST, SM, AR>() ? kBRing : 1],
@@ -1305,14 +1343,16 @@ cycle_step(typename VecOf<T>::type (&lev)[K + 1][3], typename VecOf<T>::type (&b
     cycle_loads<T, EDGE, ZIN>(nin[kPfStages - 1], nbn[kPfStages - 1], y + cycle_pfd<BL, POST, EDGE>(), pv, pb, pitch, N, ca.y_end, ld, ca.zero_in, ca.win, fo);
     const ColMask cm = col_mask(col, N);
     if (PRE) {
-        // v + P e on unknown rows, exactly as k_prolong<T,true> (PS:620-624).  The coarse
-        // values of row y were fetched during the previous step (pe.a = coarse row y>>1,
-        // pe.b = the row below it); fetch the next row's before using these.
-        T a[CW + 1], b2[CW + 1], o[W];
+        // v + P e on unknown rows, exactly as k_prolong<T,true> (PS:620-624).
+        T o[W];
+        bool row_zero = false;                        // (edge bodies: a fine row whose correction the run-time form zeroes)
+        if constexpr (YP < 0) {
+            // The coarse values of row y were fetched during the previous step (pe.a = coarse row y>>1,
+            // pe.b = the row below it); fetch the next row's before using these.
+            T a[CW + 1], b2[CW + 1];
 #pragma unroll
-        for (int k = 0; k <= CW; ++k) { a[k] = pe.a[k]; b2[k] = pe.b[k]; }
-        coarse_loads<T, EDGE>(pe, y + cycle_cpfd<T, BL, EDGE, POST>(), coarse_e, ca.cpitch, ccol, N, cld, ca.win, fo);
-        {
+            for (int k = 0; k <= CW; ++k) { a[k] = pe.a[k]; b2[k] = pe.b[k]; }
+            coarse_loads<T, EDGE>(pe, y + cycle_cpfd<T, BL, EDGE, POST>(), coarse_e, ca.cpitch, ccol, N, cld, ca.win, fo);
             // branch-free: both row parities evaluated (same expressions, same order), one selected
             const bool even = (y & 1) == 0;
 #pragma unroll
@@ -1324,11 +1364,44 @@ cycle_step(typename VecOf<T>::type (&lev)[K + 1][3], typename VecOf<T>::type (&b
                 o[2 * k] = even ? a[k] : od0;
                 o[2 * k + 1] = even ? ev1 : od1;
             }
+        } else {
+            // the parity of y is known: coarse row I = y>>1 (cs.ea) serves fine rows 2I and 2I+1; row I+1 - in this
+            // step's slot, fetched CPFD steps ago - only the odd one, after which it is row I of the next two.  One
+            // coarse row fetched per two fine rows, the fetch issued before these values are used.
+            constexpr int CPFD = cycle_cpfd<T, BL, EDGE, POST>();
+            T b2[CW + 1];
+            if constexpr (YP == 1) {
+#pragma unroll
+                for (int k = 0; k <= CW; ++k) b2[k] = pe.b[k];
+            }
+            if constexpr (((YP + CPFD) & 1) == 1) coarse_row<T, EDGE>(pe.b, ((y + CPFD) >> 1) + 1, cld, ca.win, fo);
+#pragma unroll
+            for (int k = 0; k < CW; ++k) {
+                if constexpr (YP == 0) {
+                    o[2 * k] = cs.ea[k];
+                    o[2 * k + 1] = (T)0.5 * (cs.ea[k] + cs.ea[k + 1]);
+                } else {
+                    const T ab = cs.ea[k] + b2[k];
+                    o[2 * k] = (T)0.5 * ab;
+                    o[2 * k + 1] = (T)0.25 * ((ab + cs.ea[k + 1]) + b2[k + 1]);
+                }
+            }
+            if constexpr (YP == 1) {
+#pragma unroll
+                for (int k = 0; k <= CW; ++k) cs.ea[k] = b2[k];
+            }
+            // (the rows coarse_row reads hold 0 where the row does not exist; the run-time form also zeroes the
+            // correction of the boundary rows, of the rows outside the grid and of an odd row whose lower coarse row
+            // does not exist)
+            if constexpr (EDGE) {
+                const int I = y >> 1;
+                row_zero = !(y > 0 && y < N && I >= ca.win.crow_first && I + YP <= ca.win.crow_last);
+            }
         }
         V add;
         if constexpr (W == 2) add = make_double2(o[0], o[1]);
         else add = make_float4(o[0], o[1], o[2], o[3]);
-        if constexpr (EDGE) mask_sel(add, cm, false);
+        if constexpr (EDGE) mask_sel(add, cm, row_zero);
         if constexpr (W == 2) { in.x = in.x + add.x; in.y = in.y + add.y; }
         else { in.x = in.x + add.x; in.y = in.y + add.y; in.z = in.z + add.z; in.w = in.w + add.w; }
     }
@@ -1451,34 +1524,60 @@ cycle_step(typename VecOf<T>::type (&lev)[K + 1][3], typename VecOf<T>::type (&b
             if constexpr (W == 2) { cl[0] = l; cc[0] = res.x; cr[0] = res.y; }
             else { cl[0] = l; cc[0] = res.x; cr[0] = res.y; cl[1] = res.y; cc[1] = res.z; cr[1] = res.w; }
             // rho odd (= 2I+1) closes coarse row I (top = 2I-1, mid = 2I, bot = this row) and
-            // becomes the next top; rho even becomes mid.  Written with selects, not
-            // branches: a branch on the run-time parity made the compiler index the
-            // state as a stack array (scratch).
-            const bool odd = (rho & 1) != 0;
+            // becomes the next top; rho even becomes mid
+            constexpr int RHOP = YP < 0 ? -1 : ((YP + K + 1 + SKD) & 1);     // parity of rho when known
             const int I = (rho - 1) >> 1;
-            const bool emit = odd && (2 * I >= r0) && (2 * I < r1) && I >= ca.win.emit_lo && I < ca.win.emit_hi;
-            T o[CW];
+            // (the run-time form stays spelled out inline: through a lambda the float passes spilled their state)
+            if constexpr (RHOP < 0) {
+                // Written with selects, not branches: a branch on the run-time parity made the compiler
+                // index the state as a stack array (scratch).
+                const bool odd = (rho & 1) != 0;
+                const bool emit = odd && (2 * I >= r0) && (2 * I < r1) && I >= ca.win.emit_lo && I < ca.win.emit_hi;
+                T o[CW];
 #pragma unroll
-            for (int k = 0; k < CW; ++k) {
-                // PS:539-542 order: ((nw+ne)+sw)+se + 2*(((w+e)+n)+s) + 4*c
-                T corners = cs.ct[k] + cl[k]; corners = corners + cr[k];
-                const T edges = cs.em[k] + cc[k];
-                o[k] = wgt * ((corners + (T)2 * edges) + (T)4 * cs.mc[k]);
-                if constexpr (EDGE) o[k] = (ccol + k == 0 || ccol + k >= ca.NC) ? (T)0 : o[k];
-            }
-            {
-                const unsigned at = (st && emit) ? ((unsigned)(I - fo.crb) * fo.cpitch_bytes + fo.clane_off) : kOobOffset;
-                if constexpr (CW == 1) { bstore8(o[0], fo.cb, at); bstore8((T)0, fo.cz, at); }
-                else { bstore8(make_float2((float)o[0], (float)o[1]), fo.cb, at); bstore8(make_float2(0.f, 0.f), fo.cz, at); }
-            }
+                for (int k = 0; k < CW; ++k) {
+                    // PS:539-542 order: ((nw+ne)+sw)+se + 2*(((w+e)+n)+s) + 4*c
+                    T corners = cs.ct[k] + cl[k]; corners = corners + cr[k];
+                    const T edges = cs.em[k] + cc[k];
+                    o[k] = wgt * ((corners + (T)2 * edges) + (T)4 * cs.mc[k]);
+                    if constexpr (EDGE) o[k] = (ccol + k == 0 || ccol + k >= ca.NC) ? (T)0 : o[k];
+                }
+                {
+                    const unsigned at = (st && emit) ? ((unsigned)(I - fo.crb) * fo.cpitch_bytes + fo.clane_off) : kOobOffset;
+                    if constexpr (CW == 1) { bstore8(o[0], fo.cb, at); bstore8((T)0, fo.cz, at); }
+                    else { bstore8(make_float2((float)o[0], (float)o[1]), fo.cb, at); bstore8(make_float2(0.f, 0.f), fo.cz, at); }
+                }
 #pragma unroll
-            for (int k = 0; k < CW; ++k) {
-                const T lr = cl[k] + cr[k];                    // nw + ne of the next coarse row / w + e of this one
-                const T em = lr + cs.tc[k];                    // (w + e) + n   (uses the OLD top centre)
-                cs.em[k] = odd ? cs.em[k] : em;
-                cs.mc[k] = odd ? cs.mc[k] : cc[k];
-                cs.ct[k] = odd ? lr : cs.ct[k];
-                cs.tc[k] = odd ? cc[k] : cs.tc[k];
+                for (int k = 0; k < CW; ++k) {
+                    const T lr = cl[k] + cr[k];                    // nw + ne of the next coarse row / w + e of this one
+                    const T em = lr + cs.tc[k];                    // (w + e) + n   (uses the OLD top centre)
+                    cs.em[k] = odd ? cs.em[k] : em;
+                    cs.mc[k] = odd ? cs.mc[k] : cc[k];
+                    cs.ct[k] = odd ? lr : cs.ct[k];
+                    cs.tc[k] = odd ? cc[k] : cs.tc[k];
+                }
+            } else if constexpr (RHOP == 1) {
+                // (the coarse b and zero-guess stores only on the rows that close a coarse row; as a lambda - spelled
+                // out inline, the separately rounded 10-level pass needed one register more than 256 and spilled)
+                auto close_row = [&](bool emit) {
+                    T o[CW];
+#pragma unroll
+                    for (int k = 0; k < CW; ++k) {
+                        T corners = cs.ct[k] + cl[k]; corners = corners + cr[k];      // PS:539-542 order, as above
+                        const T edges = cs.em[k] + cc[k];
+                        o[k] = wgt * ((corners + (T)2 * edges) + (T)4 * cs.mc[k]);
+                        if constexpr (EDGE) o[k] = (ccol + k == 0 || ccol + k >= ca.NC) ? (T)0 : o[k];
+                    }
+                    const unsigned at = (st && emit) ? ((unsigned)(I - fo.crb) * fo.cpitch_bytes + fo.clane_off) : kOobOffset;
+                    if constexpr (CW == 1) { bstore8(o[0], fo.cb, at); bstore8((T)0, fo.cz, at); }
+                    else { bstore8(make_float2((float)o[0], (float)o[1]), fo.cb, at); bstore8(make_float2(0.f, 0.f), fo.cz, at); }
+                };
+                close_row((2 * I >= r0) && (2 * I < r1) && I >= ca.win.emit_lo && I < ca.win.emit_hi);
+#pragma unroll
+                for (int k = 0; k < CW; ++k) { cs.ct[k] = cl[k] + cr[k]; cs.tc[k] = cc[k]; }
+            } else {
+#pragma unroll
+                for (int k = 0; k < CW; ++k) { cs.em[k] = (cl[k] + cr[k]) + cs.tc[k]; cs.mc[k] = cc[k]; }
             }
         }
     }
@@ -1496,7 +1595,6 @@ cycle_body(const T* __restrict__ pv, const T* __restrict__ pb, T* __restrict__ p
     using V = typename VecOf<T>::type;
     constexpr int W = VecOf<T>::W;
     constexpr int CW = W / 2;
-    constexpr int ETOP = POST ? 1 : 0;
     constexpr int EBOT = POST == 1 ? 2 : (POST == 2 ? 1 : 0);
     const V Z = vzero((V*)nullptr);
     const long ccol = col / 2;
@@ -1522,9 +1620,12 @@ cycle_body(const T* __restrict__ pv, const T* __restrict__ pb, T* __restrict__ p
     cs.acc = 0.0;
 #pragma unroll
     for (int k = 0; k < CW; ++k) cs.ct[k] = cs.tc[k] = cs.em[k] = cs.mc[k] = (T)0;
+#pragma unroll
+    for (int k = 0; k <= CW; ++k) cs.ea[k] = (T)0;
     CycleArgs ca;
     ca.cpitch = cpitch; ca.NC = N / 2; ca.r0 = r0; ca.r1 = r1; ca.zero_in = zero_in; ca.win = win;
-    const int y0 = r0 - K - ETOP;
+    constexpr int PAR = cycle_par<T, K, POST, SM>();          // parity of y0 (deep bodies) or -1
+    const int y0 = cycle_y0<T, K, POST, SM>(r0);              // r0 - K - ETOP, or one row earlier
     ca.y_end = r1 + K + EBOT + (cycle_skew<T, K, PRE, POST, SM, AR>() > 0 ? 1 : 0);      // exclusive end of the steps that matter
     // rounded up to whole rotations; the deep (BL) bodies run whole kBRing-step trips with no exit in
     // between - a branch-free trip is what lets the compiler keep several rows in flight - and the
@@ -1544,10 +1645,18 @@ cycle_body(const T* __restrict__ pv, const T* __restrict__ pb, T* __restrict__ p
     for (int q = 0; q < PFD; ++q)
         cycle_loads<T, EDGE, ZIN>(nin[q][0], nbn[q][0], y0 + q, pv, pb, pitch, N, ca.y_end, ld, ca.zero_in, ca.win, fo);
     if (PRE) {
+        if constexpr (PAR < 0) {
 #pragma unroll
-        for (int q = 0; q < CPFD; ++q) coarse_loads<T, EDGE>(pe[q], y0 + q, coarse_e, cpitch, ccol, N, cld, ca.win, fo);
+            for (int q = 0; q < CPFD; ++q) coarse_loads<T, EDGE>(pe[q], y0 + q, coarse_e, cpitch, ccol, N, cld, ca.win, fo);
+        } else {
+            // coarse row y0>>1, and row I+1 for each odd row 2I+1 among the first CPFD steps (see cycle_step)
+            coarse_row<T, EDGE>(cs.ea, y0 >> 1, cld, ca.win, fo);
+#pragma unroll
+            for (int q = 0; q < CPFD; ++q)
+                if (((PAR + q) & 1) == 1) coarse_row<T, EDGE>(pe[q].b, ((y0 + q) >> 1) + 1, cld, ca.win, fo);
+        }
     }
-#define MGX_CSTEP(RP, Y) cycle_step<T, K, PRE, POST, SM, EDGE, RP, BL, ZIN, AR>(lev, bw, ring, ring2, rawq, nin[(RP) % PFD], nbn[(RP) % PFD], pe[(RP) % CPFD], cs, Y, pv, pb, po, coarse_e, coarse_b, coarse_zero, wgt, pitch, col, ccol, N, ca, ld, cld, st, c0, c1, fo)
+#define MGX_CSTEP(RP, Y) cycle_step<T, K, PRE, POST, SM, EDGE, RP, BL, ZIN, AR, (PAR < 0 ? -1 : ((PAR + (RP)) & 1))>(lev, bw, ring, ring2, rawq, nin[(RP) % PFD], nbn[(RP) % PFD], pe[(RP) % CPFD], cs, Y, pv, pb, po, coarse_e, coarse_b, coarse_zero, wgt, pitch, col, ccol, N, ca, ld, cld, st, c0, c1, fo)
     if constexpr (BL) {
         // kBRing steps per trip so that every ring slot is a compile-time offset
 #define MGX_CTRIP(Y) do { MGX_CSTEP(0, Y); MGX_CSTEP(1, Y + 1); MGX_CSTEP(2, Y + 2); MGX_CSTEP(3, Y + 3); MGX_CSTEP(4, Y + 4); \
@@ -1639,7 +1748,7 @@ k_jacobi_cycle(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restri
         // the matching coarse rows/columns) strictly inside the grid and inside the window
         // (the deep bodies round their step count up to whole kBRing-step trips)
         constexpr int kRound = BL ? kBRing : trip_steps<T>();
-        const int y_first = r0 - K - ETOP - 1;
+        const int y_first = cycle_y0<T, K, POST, SM>(r0) - 1;          // (the rhs row of the first step)
         constexpr int SKD = cycle_skew<T, K, PRE, POST, SM, AR>() > 0 ? 1 : 0;            // the skewed chain's extra step
         const int y_lastp = (r0 - K - ETOP) + ((r1 + K + EBOT + SKD) - (r0 - K - ETOP) + kRound - 1) / kRound * kRound + kPrefetchMax;
         // The unpredicated body is safe when the rows its STORED values depend on - input rows y0 = r0 - K - ETOP ..
@@ -1651,6 +1760,8 @@ k_jacobi_cycle(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restri
         const int y0c = r0 - K - ETOP, y1c = r1 + K + EBOT - 1;
         bool interior = (vx0 >= 1) && ((long)(vx0 + kWave + 1) * W < N) &&
                         (y0c > 0) && (y1c < N) && (y0c >= win.row_first) && (y1c <= win.row_last);
+        // (a march that starts one row before the cone for its parity - cycle_y0 - reads that row unclamped: it must exist)
+        interior = interior && (y_first + 1 >= win.row_first);
         if (PRE) interior = interior && (y0c >> 1) >= win.crow_first && ((y1c + 1) >> 1) <= win.crow_last;
         interior = interior && !(PRE != 0 && zero_in);
         // both bodies store (and the edge body loads) through buffer descriptors that start at the first

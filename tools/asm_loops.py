@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Loops of a kernel in a device assembly file (hipcc -S --offload-device-only): length, vector-ALU
-instructions, scratch accesses inside each.   python tools/asm_loops.py file.s <mangled-name-substring>"""
+"""Loops of a kernel in a device assembly file (hipcc -S --offload-device-only): length, vector-ALU,
+buffer load / store and LDS instructions, scratch accesses inside each.
+python tools/asm_loops.py file.s <mangled-name-substring>"""
 import re
 import sys
 
@@ -25,4 +26,8 @@ for f in re.split(r'\n(?=_Z\w+:)', s):
             n = sum(1 for k in sc if a <= k <= i)
             v = sum(1 for x in lines[a:i] if re.match(r'\s+v_', x))
             dpp = sum(1 for x in lines[a:i] if 'dpp' in x)
-            print('  loop', a, i, 'len', i - a, 'valu', v, 'dpp', dpp, 'scratch in loop', n)
+            bl = sum(1 for x in lines[a:i] if re.match(r'\s+buffer_load', x))
+            bs = sum(1 for x in lines[a:i] if re.match(r'\s+buffer_store', x))
+            ds = sum(1 for x in lines[a:i] if re.match(r'\s+ds_', x))
+            print('  loop', a, i, 'len', i - a, 'valu', v, 'dpp', dpp, 'vmem load', bl, 'vmem store', bs, 'lds', ds,
+                  'scratch in loop', n)
