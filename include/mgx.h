@@ -55,7 +55,14 @@ enum { MGX_RESTRICT_CONSISTENT = 0, MGX_RESTRICT_FW16 = 1,
  * smoothed in MF's form  v <- R_omega v + omega D^-1 b  (MF:86-93), residual b - A v (MF:150-153), direct solve of
  * the coarsest operator (MF:63-72: dense inverse; coarsest_level <= 5).  dtype F64 / F32, Jacobi, one GPU.
  * Algorithmic bytes per point and sweep: 8 sizeof(T) (v, b, D_inv, four R arrays in; v' out). */
-enum { MGX_OPERATOR_POISSON = 0, MGX_OPERATOR_STENCIL5 = 1 };
+enum { MGX_OPERATOR_POISSON = 0, MGX_OPERATOR_STENCIL5 = 1,
+       /* GALERKIN: the variational hierarchy.  The finest level is a general five-point operator given as for STENCIL5;
+        * every coarser level is the NINE-point operator A_{l-1} = R A_l P built on the device by mgx_build_galerkin
+        * (P: the bilinear prolongation, R: the handle's full weighting; csrc/mgx_galerkin.hpp).  Same restrictions as
+        * STENCIL5, and restrict_mode CONSISTENT or FW16 only.  Coarse levels move 12 sizeof(T) per point and sweep
+        * (v, b, D_inv, eight R arrays in; v' out); the finest keeps 8 sizeof(T).
+        * (The value 2 stays an invalid operator: mgx_create has always refused it and the suite pins that.) */
+       MGX_OPERATOR_GALERKIN = 3 };
 enum { MGX_BOTTOM_EXACT = 0, MGX_BOTTOM_SMOOTH = 1 };
 /* Arithmetic of the weighted-Jacobi update  v' = (1-w) v + (w/4) b + (w/4)(N+W+E+S)  (PS:138-142):
  *   SEPARATE: the reference's five library calls as five roundings per point, in its order
@@ -178,6 +185,21 @@ MGX_API int mgx_set_stencil(mgx_handle h, int level, const void* c, const void* 
 MGX_API int mgx_set_coefficient(mgx_handle h, const double* a_nodes, size_t count);
 /* read back: which = 0..4 the operator (c, n, s, w, e), 5..9 its Jacobi splitting (D_inv, R_n, R_s, R_w, R_e) */
 MGX_API int mgx_get_stencil(mgx_handle h, int level, int which, void* dst, size_t count);
+
+/* ---- Galerkin coarse operators: handles with op = MGX_OPERATOR_GALERKIN -------------------------------------
+ * mgx_set_stencil (finest level only; a coarser level: MGX_ERR_STATE) or mgx_set_coefficient (samples the finest
+ * level only) give the finest operator and invalidate the hierarchy; mgx_build_galerkin then builds
+ *     A_{l-1} = R A_l P   for l = finest .. coarsest + 1,
+ * the Jacobi splitting {D_inv, R_omega} of every level and the dense inverse of the coarsest operator.  R is the
+ * handle's restriction: CONSISTENT -> R = P^T (weights 1, 1/2, 1/4), FW16 -> R = P^T / 4; all weights are powers of
+ * two, so the two modes give coarse operators that differ by an exact factor 4 per level, and the same iterates.
+ * Schedules and operators return MGX_ERR_STATE until it has run.  MGX_ERR_STATE when the finest operator has not
+ * been given or the handle's op is not GALERKIN. */
+MGX_API int mgx_build_galerkin(mgx_handle h);
+/* read back (after mgx_build_galerkin): which = 0..8 the level's operator (c, n, s, w, e, nw, ne, sw, se; the corners
+ * are zero on the finest level), 9 = D_inv, 10..17 = the off-diagonals of R_omega in the same order (n .. se).
+ * mgx_get_stencil keeps its meaning on the finest level and returns MGX_ERR_STATE for the nine-point levels. */
+MGX_API int mgx_get_stencil9(mgx_handle h, int level, int which, void* dst, size_t count);
 
 /* ---- grid operators (one call = the reference function named) ------------
  * On a dtype MIXED handle the finest level holds double data for the accessors above and a

@@ -25,6 +25,7 @@ DTYPE_F32, DTYPE_F64, DTYPE_MIXED = 0, 1, 2
 SCHEDULE_V, SCHEDULE_FMG = 0, 1
 RESTRICT_CONSISTENT, RESTRICT_FW16, RESTRICT_INJECT, RESTRICT_INJECT4 = 0, 1, 2, 3
 OPERATOR_POISSON, OPERATOR_STENCIL5 = 0, 1
+OPERATOR_GALERKIN = OP_GALERKIN = 3      # coarse operators R A P (nine-point), built on the device by build_galerkin()
 BOTTOM_EXACT, BOTTOM_SMOOTH = 0, 1
 ARITH_SEPARATE, ARITH_FMA = 0, 1
 VEC_U, VEC_B, VEC_R = 0, 1, 2
@@ -44,6 +45,7 @@ EXPORTS = [
     "mgx_plan_cut_share", "mgx_plan_guess_set", "mgx_plan_vcycle", "mgx_plan_norm", "mgx_plan_fmg", "mgx_rccl_unique_id",
     "mgx_create_rank", "mgx_dist_exchanges", "mgx_dist_overlapped", "mgx_memcpy_d2h", "mgx_memcpy_h2d", "mgx_runtime_libs",
     "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg",
+    "mgx_build_galerkin", "mgx_get_stencil9",
 ]
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
@@ -194,6 +196,8 @@ def lib() -> C.CDLL:
     L.mgx_set_stencil.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_size_t]
     L.mgx_set_coefficient.argtypes = [vp, vp, C.c_size_t]
     L.mgx_get_stencil.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
+    L.mgx_build_galerkin.argtypes = [vp]
+    L.mgx_get_stencil9.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     _lib = L
     return L
 
@@ -407,6 +411,19 @@ class Multigrid:
         n = self.n(level)
         a = np.empty((n, n), dtype=self.level_dtype(level))
         self._chk(lib().mgx_get_stencil(self._h, level, which, a.ctypes.data, a.size), "mgx_get_stencil")
+        return a
+
+    # -- Galerkin coarse operators (op = OPERATOR_GALERKIN) ------------------------------
+    def build_galerkin(self):
+        """A_{l-1} = R A_l P below the finest operator (set_stencil / set_coefficient), every level's Jacobi splitting
+        and the coarsest operator's dense inverse"""
+        self._chk(lib().mgx_build_galerkin(self._h), "mgx_build_galerkin")
+
+    def get_stencil9(self, level, which):
+        """which = 0..8: c, n, s, w, e, nw, ne, sw, se;  9: D_inv;  10..17: the off-diagonals of R_omega (n .. se)"""
+        n = self.n(level)
+        a = np.empty((n, n), dtype=self.level_dtype(level))
+        self._chk(lib().mgx_get_stencil9(self._h, level, which, a.ctypes.data, a.size), "mgx_get_stencil9")
         return a
 
     def fill_rhs(self, kind=0, f=4.0):

@@ -16,6 +16,7 @@
 #include "mgx_kernels.hpp"
 #include "mgx_launch.hpp"
 #include "mgx_var.hpp"
+#include "mgx_galerkin.hpp"
 #include "mgx_krylov.hpp"
 #include "mgx_dist_plan.hpp"
 
@@ -53,6 +54,11 @@ struct Level {
     // splitting (D_inv, R_n, R_s, R_w, R_e)  [A_jacobi_sp_dict, MF:20, 28-32]
     void* coef[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     void* jac[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    // MGX_OPERATOR_GALERKIN (mgx_galerkin.hpp), levels below the finest: the corner grids (nw, ne, sw, se) of the
+    // nine-point operator R A P and of its R_omega
+    void* corner[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* jcorner[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool nine = false;
     bool stencil_set = false;
     size_t esize() const { return f64 ? 8 : 4; }
 };
@@ -104,7 +110,9 @@ struct mgx_solver {
     int mixed_fuse = 1;             // mixed precision: u += s e and the residual in one pass (MGX_MIXED_FUSE)
     // general per-level operators: dense inverse of the coarsest one (MF:18 coarsest_level_matrix, MF:63-72)
     double *var_M = nullptr, *var_inv = nullptr, *var_pm = nullptr, *var_pi = nullptr;
-    bool var = false;               // cfg.op == MGX_OPERATOR_STENCIL5
+    bool var = false;               // cfg.op == MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN
+    bool galerkin = false;          // cfg.op == MGX_OPERATOR_GALERKIN: coarse operators are R A P (mgx_build_galerkin)
+    bool gal_built = false;         // ... and have been built from the current finest operator
     // mgx_solve_pcg (allocated by its first call): iterate x, directions p / p' (ping-pong), q = A p, the caller's b
     // while r occupies lv[finest].b, per-block partials of the Krylov passes, the device scalars and their host copy
     void *pcg_x = nullptr, *pcg_p[2] = {nullptr, nullptr}, *pcg_q = nullptr, *pcg_b = nullptr;
@@ -233,7 +241,8 @@ int alloc_level(mgx_solver* s, Level& l, int level, bool f64)
 void free_level(Level& l)
 {
     for (void** p : {&l.u, &l.b, &l.tmp, &l.r, &l.coef[0], &l.coef[1], &l.coef[2], &l.coef[3], &l.coef[4],
-                     &l.jac[0], &l.jac[1], &l.jac[2], &l.jac[3], &l.jac[4]}) {
+                     &l.jac[0], &l.jac[1], &l.jac[2], &l.jac[3], &l.jac[4], &l.corner[0], &l.corner[1], &l.corner[2], &l.corner[3],
+                     &l.jcorner[0], &l.jcorner[1], &l.jcorner[2], &l.jcorner[3]}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -295,7 +304,27 @@ int var_alloc_level(mgx_solver* s, Level& l)
         if (hipMalloc(p, l.bytes) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the operator's coefficient arrays");
         HIPCHK(s, hipMemsetAsync(*p, 0, l.bytes, s->stream));
     }
+    if (!l.nine) return MGX_OK;
+    for (void** p : {&l.corner[0], &l.corner[1], &l.corner[2], &l.corner[3], &l.jcorner[0], &l.jcorner[1], &l.jcorner[2], &l.jcorner[3]}) {
+        if (hipMalloc(p, l.bytes) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the nine-point operator's corner arrays");
+        HIPCHK(s, hipMemsetAsync(*p, 0, l.bytes, s->stream));
+    }
     return MGX_OK;
+}
+
+// dense inverse of the NN x NN matrix in var_M (k_var_dense_fill / k_var_dense_fill9 wrote it) into var_inv
+void gj_invert(mgx_solver* s, int NN)
+{
+    for (int k = 0; k < NN; ++k) {
+        hipLaunchKernelGGL(k_gj_prow, dim3((NN + 255) / 256), dim3(256), 0, s->stream, s->var_M, s->var_inv, s->var_pm, s->var_pi, NN, k);
+        hipLaunchKernelGGL(k_gj_elim, dim3(NN), dim3(256), 0, s->stream, s->var_M, s->var_inv, s->var_pm, s->var_pi, NN, k);
+    }
+}
+
+void drop_graphs(mgx_solver* s)
+{
+    for (auto& g : s->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    s->graphs.clear();
 }
 
 // the level's operator has been written into l.coef[]: build {D_inv, R_omega} (MF:28-32) and, on the coarsest
@@ -311,24 +340,92 @@ int var_build_t(mgx_solver* s, Level& l)
         const int n = l.N - 1, NN = n * n;
         hipLaunchKernelGGL((k_var_dense_fill<T>), dim3((NN + 255) / 256, NN), dim3(256), 0, s->stream, s->var_M, s->var_inv,
                            (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3], (const T*)l.coef[4], n, l.pitch);
-        for (int k = 0; k < NN; ++k) {
-            hipLaunchKernelGGL(k_gj_prow, dim3((NN + 255) / 256), dim3(256), 0, s->stream, s->var_M, s->var_inv, s->var_pm, s->var_pi, NN, k);
-            hipLaunchKernelGGL(k_gj_elim, dim3(NN), dim3(256), 0, s->stream, s->var_M, s->var_inv, s->var_pm, s->var_pi, NN, k);
-        }
+        gj_invert(s, NN);
     }
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipStreamSynchronize(s->stream));
     l.stencil_set = true;
-    for (auto& g : s->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    s->graphs.clear();       // (the kernels' coefficient pointers are unchanged, but a new operator is a new problem: recapture)
+    drop_graphs(s);          // (the kernels' coefficient pointers are unchanged, but a new operator is a new problem: recapture)
     return MGX_OK;
 }
 int var_build(mgx_solver* s, Level& l) { return l.f64 ? var_build_t<double>(s, l) : var_build_t<float>(s, l); }
+
+// ---- Galerkin hierarchy (cfg.op = MGX_OPERATOR_GALERKIN; kernels in mgx_galerkin.hpp) ---------------------
+template <typename T> Op9<T> op9_of(const Level& l)
+{
+    return Op9<T>{{(const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3], (const T*)l.coef[4],
+                   (const T*)l.corner[0], (const T*)l.corner[1], (const T*)l.corner[2], (const T*)l.corner[3]}};
+}
+template <typename T> Op9<T> jac9_of(const Level& l)      // slot 0 (the diagonal of R_omega) is a scalar: unused
+{
+    return Op9<T>{{nullptr, (const T*)l.jac[1], (const T*)l.jac[2], (const T*)l.jac[3], (const T*)l.jac[4],
+                   (const T*)l.jcorner[0], (const T*)l.jcorner[1], (const T*)l.jcorner[2], (const T*)l.jcorner[3]}};
+}
+template <typename T> Op9Out<T> out9(const Op9<T>& o)
+{
+    Op9Out<T> w;
+    for (int q = 0; q < 9; ++q) w.a[q] = const_cast<T*>(o.a[q]);
+    return w;
+}
+
+// A_{l-1} = R A_l P for l = finest .. coarsest + 1, then {D_inv, R_omega} of every level and the dense inverse of
+// the coarsest operator
+template <typename T>
+int galerkin_build_t(mgx_solver* s)
+{
+    const int lo = s->cfg.coarsest_level, hi = s->cfg.finest_level;
+    const T rscale = (s->cfg.restrict_mode == MGX_RESTRICT_FW16) ? (T)0.25 : (T)1;
+    for (int lv = hi; lv > lo; --lv) {
+        const Level& f = s->lv[lv];
+        const Level& c = s->lv[lv - 1];
+        const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
+        if (f.nine) hipLaunchKernelGGL((k_galerkin_rap<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), out9(op9_of<T>(c)),
+                                       c.N, f.pitch, c.pitch, g.strips, rscale);
+        else hipLaunchKernelGGL((k_galerkin_rap<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), out9(op9_of<T>(c)),
+                                c.N, f.pitch, c.pitch, g.strips, rscale);
+    }
+    for (int lv = lo; lv <= hi; ++lv) {
+        const Level& l = s->lv[lv];
+        const dim3 blk(256), grd((l.N + 1 + 255) / 256, l.N + 1);
+        if (l.nine) hipLaunchKernelGGL((k_var_build_jacobi9<T>), grd, blk, 0, s->stream, op9_of<T>(l), (T*)l.jac[0], out9(jac9_of<T>(l)),
+                                       l.N, l.pitch, (T)s->cfg.omega);
+        else hipLaunchKernelGGL((k_var_build_jacobi<T>), grd, blk, 0, s->stream, (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2],
+                                (const T*)l.coef[3], (const T*)l.coef[4], (T*)l.jac[0], (T*)l.jac[1], (T*)l.jac[2], (T*)l.jac[3], (T*)l.jac[4],
+                                l.N, l.pitch, (T)s->cfg.omega);
+    }
+    if (s->cfg.bottom == MGX_BOTTOM_EXACT) {
+        const Level& l = s->lv[lo];
+        const int n = l.N - 1, NN = n * n;
+        if (l.nine) hipLaunchKernelGGL((k_var_dense_fill9<T>), dim3((NN + 255) / 256, NN), dim3(256), 0, s->stream, s->var_M, s->var_inv,
+                                       op9_of<T>(l), n, l.pitch);
+        else hipLaunchKernelGGL((k_var_dense_fill<T>), dim3((NN + 255) / 256, NN), dim3(256), 0, s->stream, s->var_M, s->var_inv,
+                                (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3], (const T*)l.coef[4], n, l.pitch);
+        gj_invert(s, NN);
+    }
+    HIPCHK(s, hipGetLastError());
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    for (int lv = lo; lv <= hi; ++lv) s->lv[lv].stencil_set = true;
+    s->gal_built = true;
+    drop_graphs(s);          // the buffers have not moved, but a new hierarchy is a new problem: recapture
+    return MGX_OK;
+}
+
+// a new finest operator of a GALERKIN handle: the coarse operators and every splitting are stale
+void galerkin_invalidate(mgx_solver* s)
+{
+    for (int lv = s->cfg.coarsest_level; lv < s->cfg.finest_level; ++lv) s->lv[lv].stencil_set = false;
+    s->lv[s->cfg.finest_level].stencil_set = true;
+    s->gal_built = false;
+    drop_graphs(s);
+}
 
 // every level's operator must have been given before a schedule or operator runs
 int var_ready(mgx_solver* s, int lo, int hi)
 {
     if (!s->var) return MGX_OK;
+    if (s->galerkin && !s->gal_built)
+        return s->fail(MGX_ERR_STATE, s->lv[s->cfg.finest_level].stencil_set ? "Galerkin hierarchy not built (mgx_build_galerkin)"
+                                                                             : "finest operator not set (mgx_set_stencil / mgx_set_coefficient)");
     for (int l = lo; l <= hi; ++l)
         if (!s->lv[l].stencil_set)
             return s->fail(MGX_ERR_STATE, "operator of level " + std::to_string(l) + " not set (mgx_set_stencil / mgx_set_coefficient)");
@@ -343,7 +440,9 @@ void smooth_var_t(mgx_solver* s, Level& l, int mu)
     const T rc = (T)(1.0 - (double)om);
     const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
     for (int i = 0; i < mu; ++i) {
-        hipLaunchKernelGGL((k_jacobi_var<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.u, (const T*)l.b, (T*)l.tmp,
+        if (l.nine) hipLaunchKernelGGL((k_jacobi_var9<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.u, (const T*)l.b, (T*)l.tmp,
+                                       (const T*)l.jac[0], jac9_of<T>(l), l.N, l.pitch, 1, l.N, g.strips, rc, om, l.rows);
+        else hipLaunchKernelGGL((k_jacobi_var<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.u, (const T*)l.b, (T*)l.tmp,
                            (const T*)l.jac[0], (const T*)l.jac[1], (const T*)l.jac[2], (const T*)l.jac[3], (const T*)l.jac[4],
                            l.N, l.pitch, 1, l.N, g.strips, rc, om, l.rows);
         std::swap(l.u, l.tmp);
@@ -356,7 +455,9 @@ template <typename T, int MODE>
 void residual_var_t(mgx_solver* s, const Level& l, const void* u, const void* b, void* out)
 {
     const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
-    hipLaunchKernelGGL((k_residual_var<T, MODE>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)u, (const T*)b, (T*)out,
+    if (l.nine) hipLaunchKernelGGL((k_residual_var9<T, MODE>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)u, (const T*)b, (T*)out,
+                                   s->partial, op9_of<T>(l), l.N, l.pitch, 1, l.N, g.strips, l.rows);
+    else hipLaunchKernelGGL((k_residual_var<T, MODE>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)u, (const T*)b, (T*)out,
                        s->partial, (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3],
                        (const T*)l.coef[4], l.N, l.pitch, 1, l.N, g.strips, l.rows);
     if (MODE == 1) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, s->partial, g.blocks, s->sum_dev);
@@ -1092,18 +1193,24 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
         cfg->mu0 < 0 || cfg->mu1 < 0 || cfg->mu2 < 0 || !(cfg->omega > 0.0 && cfg->omega < 2.0) ||
         cfg->smoother < 0 || cfg->smoother > 1 || cfg->dtype < 0 || cfg->dtype > 2 ||
         cfg->schedule < 0 || cfg->schedule > 1 || cfg->restrict_mode < 0 || cfg->restrict_mode > MGX_RESTRICT_INJECT4 ||
-        cfg->bottom < 0 || cfg->bottom > 1 || cfg->arith < 0 || cfg->arith > 1 || cfg->op < 0 || cfg->op > 1) {
+        cfg->bottom < 0 || cfg->bottom > 1 || cfg->arith < 0 || cfg->arith > 1 || (cfg->op != MGX_OPERATOR_POISSON && cfg->op != MGX_OPERATOR_STENCIL5 && cfg->op != MGX_OPERATOR_GALERKIN)) {
         g_create_error = "invalid configuration";
         return MGX_ERR_INVALID;
     }
-    const bool var = (cfg->op == MGX_OPERATOR_STENCIL5);
+    const bool galerkin = (cfg->op == MGX_OPERATOR_GALERKIN);
+    const bool var = (cfg->op == MGX_OPERATOR_STENCIL5) || galerkin;
     if (cfg->bottom == MGX_BOTTOM_EXACT && cfg->coarsest_level > (var ? 5 : 8)) {
         g_create_error = var ? "exact bottom solve of a general operator (dense inverse) supports coarsest_level <= 5"
                              : "exact bottom solve supports coarsest_level <= 8";
         return MGX_ERR_INVALID;
     }
     if (var && (cfg->dtype == MGX_DTYPE_MIXED || cfg->smoother != MGX_SMOOTHER_JACOBI || cfg->arith != MGX_ARITH_SEPARATE || cfg->n_gpus > 1)) {
-        g_create_error = "MGX_OPERATOR_STENCIL5: dtype F64 or F32, Jacobi (MF:75-96), arith SEPARATE, one GPU";
+        g_create_error = galerkin ? "MGX_OPERATOR_GALERKIN: dtype F64 or F32, Jacobi, arith SEPARATE, one GPU"
+                                  : "MGX_OPERATOR_STENCIL5: dtype F64 or F32, Jacobi (MF:75-96), arith SEPARATE, one GPU";
+        return MGX_ERR_INVALID;
+    }
+    if (galerkin && cfg->restrict_mode >= MGX_RESTRICT_INJECT) {
+        g_create_error = "MGX_OPERATOR_GALERKIN: restrict_mode CONSISTENT or FW16 (R A P needs R = c P^T; injection has no variational meaning)";
         return MGX_ERR_INVALID;
     }
     if (cfg->restrict_mode >= MGX_RESTRICT_INJECT && (cfg->n_gpus > 1 || cfg->dtype == MGX_DTYPE_MIXED)) {
@@ -1124,6 +1231,7 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     s->cfg = *cfg;
     s->mixed = (cfg->dtype == MGX_DTYPE_MIXED);
     s->var = var;
+    s->galerkin = galerkin;
     s->work_f64 = (cfg->dtype == MGX_DTYPE_F64);
     s->rows_per_chunk = env_int("MGX_ROWS", 0);
     s->fuse = fuse_cfg();
@@ -1145,8 +1253,10 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
             if ((rc = ensure_r(s, s->lv[l])) != MGX_OK) return bail(rc);
     }
     if (var) {
-        for (int l = cfg->coarsest_level; l <= cfg->finest_level; ++l)
+        for (int l = cfg->coarsest_level; l <= cfg->finest_level; ++l) {
+            s->lv[l].nine = galerkin && l < cfg->finest_level;
             if ((rc = var_alloc_level(s, s->lv[l])) != MGX_OK) return bail(rc);
+        }
         if (cfg->bottom == MGX_BOTTOM_EXACT) {
             const size_t NN = (size_t)((1 << cfg->coarsest_level) - 1) * ((1 << cfg->coarsest_level) - 1);
             if (hipMalloc(&s->var_M, NN * NN * sizeof(double)) != hipSuccess || hipMalloc(&s->var_inv, NN * NN * sizeof(double)) != hipSuccess ||
@@ -1368,12 +1478,15 @@ int mgx_set_stencil(mgx_handle s, int level, const void* c, const void* n, const
     NO_DIST(s)
     if (!s->var) return s->fail(MGX_ERR_STATE, "handle was created with op = MGX_OPERATOR_POISSON (the constant stencil needs no coefficients)");
     if (!level_ok(s, level)) return s->fail(MGX_ERR_INVALID, "level out of range");
+    if (s->galerkin && level != s->cfg.finest_level)
+        return s->fail(MGX_ERR_STATE, "MGX_OPERATOR_GALERKIN: only the finest operator is the caller's (coarse levels are R A P: mgx_build_galerkin)");
     Level& l = s->lv[level];
     const void* src[5] = {c, n, so, w, e};
     for (int q = 0; q < 5; ++q) {
         int rc = copy_in(s, l, l.coef[q], src[q], count);
         if (rc) return rc;
     }
+    if (s->galerkin) { galerkin_invalidate(s); return MGX_OK; }
     return var_build(s, l);
 }
 
@@ -1388,7 +1501,7 @@ int mgx_set_coefficient(mgx_handle s, const double* a_nodes, size_t count)
     if (hipMalloc(&dev, count * sizeof(double)) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the nodal coefficient");
     int rc = MGX_OK;
     if (hipMemcpyAsync(dev, a_nodes, count * sizeof(double), hipMemcpyHostToDevice, s->stream) != hipSuccess) rc = s->fail(MGX_ERR_HIP, "copy of the nodal coefficient failed");
-    for (int lv = s->cfg.coarsest_level; lv <= Lf && rc == MGX_OK; ++lv) {
+    for (int lv = s->galerkin ? Lf : s->cfg.coarsest_level; lv <= Lf && rc == MGX_OK; ++lv) {
         Level& l = s->lv[lv];
         const dim3 blk(256), grd((l.N + 1 + 255) / 256, l.N + 1);
         const int q = 1 << (Lf - lv);
@@ -1396,10 +1509,11 @@ int mgx_set_coefficient(mgx_handle s, const double* a_nodes, size_t count)
                                       (double*)l.coef[2], (double*)l.coef[3], (double*)l.coef[4], l.N, l.pitch);
         else hipLaunchKernelGGL((k_var_from_nodes<float>), grd, blk, 0, s->stream, dev, Nf, q, (float*)l.coef[0], (float*)l.coef[1],
                                 (float*)l.coef[2], (float*)l.coef[3], (float*)l.coef[4], l.N, l.pitch);
-        rc = var_build(s, l);
+        if (!s->galerkin) rc = var_build(s, l);
     }
-    (void)hipStreamSynchronize(s->stream);
+    if (hipStreamSynchronize(s->stream) != hipSuccess && rc == MGX_OK) rc = s->fail(MGX_ERR_HIP, "sampling the nodal coefficient failed");
     (void)hipFree(dev);
+    if (s->galerkin && rc == MGX_OK) galerkin_invalidate(s);
     return rc;
 }
 
@@ -1410,8 +1524,39 @@ int mgx_get_stencil(mgx_handle s, int level, int which, void* dst, size_t count)
     if (!s->var) return s->fail(MGX_ERR_STATE, "handle was created with op = MGX_OPERATOR_POISSON");
     if (!level_ok(s, level) || which < 0 || which > 9) return s->fail(MGX_ERR_INVALID, "level or array selector out of range");
     Level& l = s->lv[level];
+    if (l.nine) return s->fail(MGX_ERR_STATE, "nine-point operator (coarse level of a GALERKIN handle): use mgx_get_stencil9");
     if (!l.stencil_set) return s->fail(MGX_ERR_STATE, "operator of this level not set");
+    if (s->galerkin && which >= 5 && !s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
     return copy_out(s, l, which < 5 ? l.coef[which] : l.jac[which - 5], dst, count);
+}
+
+int mgx_build_galerkin(mgx_handle s)
+{
+    if (!s) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (!s->galerkin) return s->fail(MGX_ERR_STATE, "handle was not created with op = MGX_OPERATOR_GALERKIN");
+    if (!s->lv[s->cfg.finest_level].stencil_set)
+        return s->fail(MGX_ERR_STATE, "finest operator not set (mgx_set_stencil / mgx_set_coefficient)");
+    return s->work_f64 ? galerkin_build_t<double>(s) : galerkin_build_t<float>(s);
+}
+
+int mgx_get_stencil9(mgx_handle s, int level, int which, void* dst, size_t count)
+{
+    if (!s || !dst) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (!s->galerkin) return s->fail(MGX_ERR_STATE, "handle was not created with op = MGX_OPERATOR_GALERKIN");
+    if (!level_ok(s, level) || which < 0 || which > 17) return s->fail(MGX_ERR_INVALID, "level or array selector out of range");
+    if (!s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
+    Level& l = s->lv[level];
+    // 0..8: c, n, s, w, e, nw, ne, sw, se;  9: D_inv;  10..17: R_n, R_s, R_w, R_e, R_nw, R_ne, R_sw, R_se
+    const void* src = which < 5 ? l.coef[which] : which < 9 ? l.corner[which - 5] : which < 14 ? l.jac[which - 9] : l.jcorner[which - 14];
+    if (!src) {                                               // corners of the five-point finest level
+        const size_t n = (size_t)l.N - 1;
+        if (count != n * n) return s->fail(MGX_ERR_INVALID, "vector length must be n*n with n = 2^level - 1");
+        std::memset(dst, 0, count * l.esize());
+        return MGX_OK;
+    }
+    return copy_out(s, l, src, dst, count);
 }
 
 // ---- operators ------------------------------------------------------------------------

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Measurements of the Galerkin hierarchy (op = MGX_OPERATOR_GALERKIN, csrc/mgx_galerkin.hpp) on one MI355X; prints the
+markdown kept as profiles/galerkin_kernel_trace_summary.md:
+  - k_jacobi_var9 / k_residual_var9 at 4096^2 (level 12 of a 13..5 hierarchy): achieved bytes/s over their
+    12 sizeof(T) per point, next to k_jacobi_var / k_residual_var (8 sizeof(T)) on a STENCIL5 handle at the same grid;
+  - set-up: mgx_build_galerkin at 8192^2 levels 13..5 next to mgx_set_coefficient on a STENCIL5 handle;
+  - time to 1e-8 (sine right-hand side as tools/pcg_bench.py): mgx_solve and mgx_solve_pcg at 2047^2 contrast 10 and
+    511^2 contrast 100.
+Wall times around calls that end in a device synchronise (40 sweeps or 20 residuals per timed call).
+    python tools/galerkin_bench.py [--quick]"""
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import __graft_entry__ as ge  # noqa: E402
+from pcg_ref import contrast_coefficient  # noqa: E402
+
+pkg = ge.load_package()
+QUICK = "--quick" in sys.argv
+LF = 9 if QUICK else 13          # finest level of the kernel / set-up handles; the timed nine-point level is LF - 1
+LK = LF - 1
+
+
+def wall(f, reps=3):
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        f()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(out)
+
+
+def kernels():
+    n = (1 << LK) - 1
+    x = np.linspace(0.0, 1.0, (1 << LF) + 1)
+    a = 1.0 + 0.8 * np.sin(3 * np.pi * x)[None, :] * np.cos(2 * np.pi * x)[:, None]
+    rng = np.random.default_rng(0)
+    u, b = rng.uniform(-1, 1, (n, n)), rng.uniform(-1, 1, (n, n))
+    print(f"| kernel | grid | dtype | ms per pass | bytes per point | achieved GB/s | fraction of the 8 TB/s HBM peak |")
+    print("|---|---|---|---|---|---|---|")
+    rate = {}
+    for dtype, name, es in ((pkg.DTYPE_F64, "f64", 8), (pkg.DTYPE_F32, "f32", 4)):
+        for op, tag, words, finest in ((pkg.OPERATOR_STENCIL5, "var", 8, LK), (pkg.OP_GALERKIN, "var9", 12, LF)):
+            with pkg.Multigrid(finest_level=finest, coarsest_level=5, mu1=2, mu2=2, schedule=pkg.SCHEDULE_V, op=op, dtype=dtype, omega=0.8) as mg:
+                if op == pkg.OP_GALERKIN:
+                    mg.set_coefficient(a)
+                    t0 = time.perf_counter()
+                    mg.build_galerkin()
+                    rate[("build", name)] = (time.perf_counter() - t0) * 1e3
+                else:
+                    mg.set_coefficient(a[::2, ::2])
+                mg.set_level(LK, pkg.VEC_U, u)
+                mg.set_level(LK, pkg.VEC_B, b)
+                mg.smooth(LK, 4)
+                sweeps = 40
+                ms = wall(lambda: mg.smooth(LK, sweeps)) / sweeps
+                gbs = words * es * n * n / (ms * 1e-3) / 1e9
+                rate[(tag, name)] = gbs
+                print(f"| k_jacobi_{tag}<{name}> | {1 << LK}^2 | {name} | {ms:.4f} | {words * es} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
+                mg.residual(LK, u, b)
+                lib, h = pkg.lib(), mg._h
+
+                def res20():
+                    for _ in range(20):
+                        lib.mgx_residual(h, LK)
+                ms = wall(res20) / 20
+                gbs = words * es * n * n / (ms * 1e-3) / 1e9
+                print(f"| k_residual_{tag}<{name}, 0> (one host synchronise per pass) | {1 << LK}^2 | {name} | {ms:.4f} | {words * es} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
+    for name in ("f64", "f32"):
+        print(f"\nk_jacobi_var9 / k_jacobi_var bytes/s, {name}: {rate[('var9', name)] / rate[('var', name)]:.3f} (accepted: >= 0.9)")
+    return rate
+
+
+def setup(rate):
+    N = 1 << LF
+    a = contrast_coefficient(LF, 10.0)
+    print(f"\n| set-up at {N}^2, levels {LF}..5, f64 | ms (wall, one call, after a warm-up call) |\n|---|---|")
+    with pkg.Multigrid(finest_level=LF, coarsest_level=5, schedule=0, op=pkg.OP_GALERKIN) as mg:
+        mg.set_coefficient(a)
+        mg.build_galerkin()
+        print(f"| mgx_build_galerkin (R A P on {LF - 5} levels, all splittings, dense inverse of the 31^2 level) | {wall(mg.build_galerkin):.1f} |")
+        print(f"| mgx_set_coefficient on the GALERKIN handle (finest level only; includes the host-to-device copy of the nodal coefficient) | {wall(lambda: mg.set_coefficient(a)):.1f} |")
+    with pkg.Multigrid(finest_level=LF, coarsest_level=5, schedule=0, op=pkg.OPERATOR_STENCIL5) as mg:
+        mg.set_coefficient(a)
+        print(f"| mgx_set_coefficient on a STENCIL5 handle (re-discretises every level, splittings, dense inverse; includes the same copy) | {wall(lambda: mg.set_coefficient(a)):.1f} |", flush=True)
+
+
+def solves():
+    print("\n| problem, V(2,2), levels L..5, f64, sine right-hand side | GALERKIN mgx_solve | GALERKIN mgx_solve_pcg |\n|---|---|---|")
+    for L, contrast in ((9, 10.0), (9, 100.0)) if QUICK else ((11, 10.0), (9, 100.0)):
+        with pkg.Multigrid(finest_level=L, coarsest_level=5, mu1=2, mu2=2, schedule=0, op=pkg.OP_GALERKIN) as mg:
+            mg.set_coefficient(contrast_coefficient(L, contrast))
+            mg.build_galerkin()
+            mg.fill_rhs(1)
+            cells = []
+            for f in (lambda: mg.solve(tol=1e-8, max_cycles=100), lambda: mg.solve_pcg(tol=1e-8, max_iters=200)):
+                ts = []
+                for rep in range(6):                    # the first run captures the graphs: not timed
+                    mg.set_guess(np.zeros((mg.n(), mg.n())))
+                    st, h = f()
+                    if rep:
+                        ts.append(st.seconds * 1e3)
+                cells.append(f"{st.cycles} {'it' if len(cells) else 'cycles'}, {statistics.median(ts):.2f} ms (min {min(ts):.2f}, max {max(ts):.2f}), converged {st.converged}")
+            print(f"| {(1 << L) - 1}^2 contrast {contrast:g} | {cells[0]} | {cells[1]} |", flush=True)
+
+
+if __name__ == "__main__":
+    r = kernels()
+    setup(r)
+    solves()
