@@ -452,7 +452,8 @@ typedef struct {
  * distributes the bytes */
 MGX_API int mgx_rccl_unique_id(void* out128);
 /* One rank of `world` (one process per GPU).  transport = NULL: built-in RCCL (rccl_id = the 128
- * bytes of mgx_rccl_unique_id from rank 0); otherwise the caller's transport (rccl_id ignored). */
+ * bytes of mgx_rccl_unique_id from rank 0); otherwise the caller's transport (rccl_id ignored).
+ * cfg.op must be MGX_OPERATOR_POISSON (MGX_ERR_INVALID otherwise: the general operators are single-GPU). */
 MGX_API int mgx_create_rank(const mgx_config* cfg, int rank, int world, const void* rccl_id,
                             const mgx_transport* transport, mgx_handle* out);
 /* number of halo exchanges a multi-GPU handle has performed (tests: communication plan) */

@@ -2100,6 +2100,11 @@ int mgx_create_rank(const mgx_config* cfg, int rank, int world, const void* rccl
         g_create_error = "invalid configuration";
         return MGX_ERR_INVALID;
     }
+    // the slab plan runs the constant stencil only: a general operator must not silently become Poisson
+    if (cfg->op != MGX_OPERATOR_POISSON) {
+        g_create_error = "multi-GPU handles: op = MGX_OPERATOR_POISSON only (MGX_OPERATOR_STENCIL5 / MGX_OPERATOR_GALERKIN: one GPU)";
+        return MGX_ERR_INVALID;
+    }
     log_runtime_libs("mgx_create_rank");
     mgx_solver* s = new (std::nothrow) mgx_solver();
     if (!s) { g_create_error = "out of host memory"; return MGX_ERR_ALLOC; }

@@ -1,6 +1,6 @@
 """numpy statement of the Galerkin hierarchy (op = MGX_OPERATOR_GALERKIN, csrc/mgx_galerkin.hpp): the coarse operator
 A_c = R A_f P term by term in the kernel's documented order, the nine-point Jacobi sweep and residual in the kernels'
-summation order, the dense coarsest solve in the device's elimination order, and the V-cycle / solve built from them plus the oracle's transfer operators
+summation order, the dense coarsest solve in the device's elimination order, and the V-cycle / FMG pass / solve built from them plus the oracle's transfer operators
 and five-point finest-level kernels (oracle/pyoracle.py).  numpy's elementwise arithmetic rounds every operation
 separately, which is what the kernels do (-ffp-contract=off), so every step is meant bit for bit.
 
@@ -12,6 +12,8 @@ SLOTS = ("c", "n", "s", "w", "e", "nw", "ne", "sw", "se")
 SLOT = {(0, 0): 0, (-1, 0): 1, (1, 0): 2, (0, -1): 3, (0, 1): 4, (-1, -1): 5, (-1, 1): 6, (1, -1): 7, (1, 1): 8}
 ROW_MAJOR = [(dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1)]       # NW, N, NE, W, C, E, SW, S, SE
 CONSISTENT, FW16 = 0, 1
+EXACT, SMOOTH = 0, 1                   # cfg.bottom
+V, FMG = 0, 1                          # cfg.schedule
 
 
 def nine(st5):
@@ -137,10 +139,15 @@ def dense_apply(Inv, b):
 
 
 class Hierarchy:
-    """finest level: the five-point operator `st5` (oracle kernels); levels below: rap()"""
+    """finest level: the five-point operator `st5` (oracle kernels); levels below: rap().
 
-    def __init__(self, po, st5, finest, coarsest, dtype=np.float64, mode=CONSISTENT, omega=2.0 / 3.0, mu1=2, mu2=2):
+    bottom = SMOOTH (vcycle() of mgx.hip at the coarsest level, the oracle's orc_vcycle): no dense solve; the coarsest
+    level runs mu1 sweeps and then mu2 sweeps, mu1 + mu2 in all, of its own smoother, starting from the guess it is
+    handed: zero inside a V-cycle (the restriction zeroes the coarse guess, PS:613) and in fmg() (PS:630)."""
+
+    def __init__(self, po, st5, finest, coarsest, dtype=np.float64, mode=CONSISTENT, omega=2.0 / 3.0, mu1=2, mu2=2, mu0=0, bottom=EXACT):
         self.po, self.L, self.Lc, self.dt, self.mode, self.omega, self.mu1, self.mu2 = po, finest, coarsest, dtype, mode, omega, mu1, mu2
+        self.mu0, self.bottom_mode = mu0, bottom
         self.st = {finest: nine([np.asarray(x, dtype=dtype) for x in st5])}
         for lv in range(finest, coarsest, -1):
             self.st[lv - 1] = rap(self.st[lv], 1 << lv, mode)
@@ -167,21 +174,44 @@ class Hierarchy:
 
     def vcycle(self, lv, v, b):
         if lv == self.Lc:
-            return self.bottom(b)
+            if self.bottom_mode == EXACT:
+                return self.bottom(b)
+            return self.smooth(lv, self.smooth(lv, v, b, self.mu1), b, self.mu2)
         v = self.smooth(lv, v, b, self.mu1)
         rc = self.po.restrict(self.residual(lv, v, b), self.mode)
         e = self.vcycle(lv - 1, np.zeros_like(rc), rc)
         v = self.po.prolong_add(v, e)
         return self.smooth(lv, v, b, self.mu2)
 
-    def solve(self, b, u0=None, tol=1e-8, max_cycles=50):
-        """(u, history of ||b - A u||) as the oracle's and the device's solve report it"""
+    def fmg(self, b):
+        """fmg() of mgx.hip / the oracle's orc_fmg: b restricted with the handle's mode down to the coarsest level
+        (PS:641); there the dense solve (EXACT) or mu0 + 1 coarsest "V-cycles" from zero (SMOOTH, PS:630-635); then per
+        level up to the finest: prolong (PS:645, not added: the level's previous iterate is discarded) and mu0 + 1
+        V-cycles with that level's restricted right-hand side (PS:646-648)"""
+        rhs = {self.L: np.ascontiguousarray(b, dtype=self.dt)}
+        for lv in range(self.L, self.Lc, -1):
+            rhs[lv - 1] = self.po.restrict(rhs[lv], self.mode)
+        if self.bottom_mode == EXACT:
+            v = self.bottom(rhs[self.Lc])
+        else:
+            v = np.zeros_like(rhs[self.Lc])
+            for _ in range(self.mu0 + 1):
+                v = self.vcycle(self.Lc, v, rhs[self.Lc])
+        for lv in range(self.Lc + 1, self.L + 1):
+            v = self.po.prolong(v)
+            for _ in range(self.mu0 + 1):
+                v = self.vcycle(lv, v, rhs[lv])
+        return v
+
+    def solve(self, b, u0=None, tol=1e-8, max_cycles=50, schedule=V):
+        """(u, history of ||b - A u||) as the oracle's and the device's solve report it.  schedule = FMG: the first
+        cycle is fmg(b), which discards the guess (the history still starts at the guess's residual); V-cycles after"""
         b = np.ascontiguousarray(b, dtype=self.dt)
         u = np.zeros_like(b) if u0 is None else np.array(u0, dtype=self.dt, order="C")
         hist = [self.po.norm2(self.residual(self.L, u, b))]
-        for _ in range(max_cycles):
+        for k in range(max_cycles):
             if hist[-1] <= tol * hist[0]:
                 break
-            u = self.vcycle(self.L, u, b)
+            u = self.fmg(b) if (k == 0 and schedule == FMG) else self.vcycle(self.L, u, b)
             hist.append(self.po.norm2(self.residual(self.L, u, b)))
         return u, np.array(hist)

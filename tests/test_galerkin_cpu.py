@@ -24,6 +24,27 @@ def coefficient(L, kind):
     return contrast_coefficient(L, 100.0)
 
 
+def random_stencil5(L, seed, c_lo=3.0, c_hi=5.0):
+    """a seeded non-symmetric five-point operator (c, n, s, w, e): c in [c_lo, c_hi], every off-diagonal drawn on its
+    own in [-1, -0.5], so A(i, i+d) != A(i+d, i) and the four directions differ"""
+    n = (1 << L) - 1
+    rng = np.random.default_rng(seed)
+    return [rng.uniform(c_lo, c_hi, (n, n))] + [-rng.uniform(0.5, 1.0, (n, n)) for _ in range(4)]
+
+
+def with_ring_values(st5, seed, big=1e30):
+    """the same operator with the coefficients that point at the Dirichlet ring (n on row 1, s on row n, w on column 1,
+    e on column n) overwritten by finite values of mixed sign and magnitudes from 1 to `big` (float32 holds 1e30)"""
+    rng = np.random.default_rng(seed)
+    out = [np.array(x, copy=True) for x in st5]
+    n = out[0].shape[0]
+
+    def junk():
+        return rng.choice([-1.0, 1.0], n) * 10.0 ** rng.uniform(0.0, np.log10(big), n)
+    out[1][0, :], out[2][-1, :], out[3][:, 0], out[4][:, -1] = junk(), junk(), junk(), junk()
+    return out
+
+
 def sparse_of(st9):
     n = st9[0].shape[0]
     idx = np.arange(n * n).reshape(n, n)
@@ -63,6 +84,80 @@ def test_rap_is_scipy_s_triple_product(po, L, kind, mode):
         M = gr.dense(got)
         assert np.max(np.abs(M - M.T)) <= 1e-12 * scale
         st = got
+
+
+@pytest.mark.parametrize("L", [5, 6])
+@pytest.mark.parametrize("mode", [gr.CONSISTENT, gr.FW16])
+def test_rap_of_a_non_symmetric_operator_is_scipy_s_triple_product(L, mode):
+    """R A P, not a formula that leans on A = A^T: c in [4, 5] against off-diagonals in [-1, -0.5] is diagonally
+    dominant, and A(i, i+d) != A(i+d, i) in all four directions"""
+    st5 = random_stencil5(L, 40 + L, c_lo=4.0)
+    assert np.all(st5[0] >= -(st5[1] + st5[2] + st5[3] + st5[4]))
+    A = sparse_of(gr.nine(st5)).toarray()
+    assert np.max(np.abs(A - A.T)) > 0.1
+    st = gr.nine(st5)
+    for lv in (L, L - 1):
+        got = gr.rap(st, 1 << lv, mode)
+        P = prolongation(lv)
+        want = (P.T @ sparse_of(st) @ P).toarray() * (0.25 if mode == gr.FW16 else 1.0)
+        scale = np.max(np.abs(want))
+        assert np.max(np.abs(gr.dense(got) - want)) <= 1e-12 * scale
+        M = gr.dense(got)
+        assert np.max(np.abs(M - M.T)) > 1e-3 * scale           # the coarse operator is not symmetric either
+        st = got
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+@pytest.mark.parametrize("mode", [gr.CONSISTENT, gr.FW16])
+def test_rap_ignores_what_the_ring_pointing_coefficients_hold(dt, mode):
+    """mgx.h: coefficients that point at the eliminated Dirichlet ring are ignored.  They only ever enter coarse
+    coefficients that point at the coarse ring, and those are written as zeros: values up to 1e30 leave no trace"""
+    L = 6
+    st5 = random_stencil5(L, 7)
+    zeroed = [x.copy() for x in st5]
+    zeroed[1][0, :], zeroed[2][-1, :], zeroed[3][:, 0], zeroed[4][:, -1] = 0.0, 0.0, 0.0, 0.0
+    junk = with_ring_values(st5, 8)
+    assert np.max(np.abs(junk[1][0])) > 1e20 and np.isfinite(np.asarray(junk, dtype=dt)).all()
+    a = gr.rap(gr.nine([x.astype(dt) for x in zeroed]), 1 << L, mode)
+    b = gr.rap(gr.nine([x.astype(dt) for x in junk]), 1 << L, mode)
+    for o in range(9):
+        assert np.array_equal(a[o], b[o]), gr.SLOTS[o]
+
+
+def test_fmg_then_v22_converges_on_the_jump_problem(po):
+    """schedule = FMG in the reference: one FMG pass, then V(2,2) cycles, L = 7 down to 4, contrast 100.
+    Recorded: 44 cycles to 1e-8, the FMG pass counted as the first (plain V(2,2) cycles from zero: 45).  Bound: a third
+    over, as for the V-cycle counts below"""
+    L = 7
+    h = gr.Hierarchy(po, po.stencil_from_nodes(coefficient(L, "jump"), L, L), L, 4)
+    u, hist = h.solve(po.rhs_constant(L), tol=1e-8, max_cycles=58, schedule=gr.FMG)
+    print(f"FMG + V(2,2), jump, L = 7: {len(hist) - 1} cycles, final {hist[-1] / hist[0]:.3e}")
+    assert hist[-1] <= 1e-8 * hist[0] and len(hist) - 1 <= 58
+    # the first cycle is the FMG pass, not a V-cycle from the zero guess
+    assert not np.isclose(hist[1], h.solve(po.rhs_constant(L), max_cycles=1)[1][1], rtol=1e-3)
+
+
+@pytest.mark.parametrize("bottom", [gr.EXACT, gr.SMOOTH])
+def test_fw16_and_consistent_give_the_same_fmg_iterate(po, bottom):
+    """mgx.h: the two modes give coarse operators that differ by an exact factor 4 per level, "and the same
+    iterates": the restricted right-hand sides carry the same factor"""
+    L = 7
+    st5 = po.stencil_from_nodes(coefficient(L, "jump"), L, L)
+    b = po.rhs_sine(L)
+    u = [gr.Hierarchy(po, st5, L, 4, mode=mode, mu0=1, bottom=bottom).fmg(b) for mode in (gr.CONSISTENT, gr.FW16)]
+    assert np.max(np.abs(u[0] - u[1])) <= 1e-12 * np.max(np.abs(u[0]))
+    # ... and not a trivial one: the pass reduced the residual of the zero guess
+    h = gr.Hierarchy(po, st5, L, 4, mu0=1, bottom=bottom)
+    assert po.norm2(h.residual(L, u[0], b)) < po.norm2(b)
+
+
+def test_bottom_smooth_is_mu1_plus_mu2_sweeps_from_the_guess(po):
+    L = 5
+    st5 = po.stencil_from_nodes(coefficient(L, "smooth"), L, L)
+    h = gr.Hierarchy(po, st5, L, 3, mu1=3, mu2=1, bottom=gr.SMOOTH)
+    rng = np.random.default_rng(0)
+    v, b = rng.uniform(-1, 1, (7, 7)), rng.uniform(-1, 1, (7, 7))
+    assert np.array_equal(h.vcycle(3, v, b), gr.jacobi9(v, b, 4, h.omega, h.jac[3]))
 
 
 def test_poisson_coarse_stencil_is_3_half_quarter(po):
