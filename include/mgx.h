@@ -201,6 +201,35 @@ MGX_API int mgx_build_galerkin(mgx_handle h);
  * mgx_get_stencil keeps its meaning on the finest level and returns MGX_ERR_STATE for the nine-point levels. */
 MGX_API int mgx_get_stencil9(mgx_handle h, int level, int which, void* dst, size_t count);
 
+/* ---- the prolongation of the Galerkin hierarchy (csrc/mgx_opdep.hpp) ------------------------------------------
+ * BILINEAR: the weights 1, 1/2, 1/4 on every level.  OPERATOR: the operator-dependent ("black box", Alcouffe / Dendy)
+ * prolongation, its weights read off the stencil (c, n, s, w, e, nw, ne, sw, se) of the fine point they belong to:
+ *   a fine point on a coarse row, between two coarse columns: the stencil collapsed in y, den = n + c + s, from the
+ *     west coarse point -(nw + w + sw) / den, from the east one -(ne + e + se) / den;
+ *   a fine point on a coarse column: the same with x and y exchanged (den = w + c + e);
+ *   a cell centre: its row of A solved for the centre value, the four edge neighbours replaced by their own formula
+ *     above, e.g. from the north-west coarse point -(nw + n hW + w vN) / c with hW / vN the west / north weights of
+ *     its north / west neighbour;
+ *   a denominator (den, or c at a centre) that is zero or not finite: that weight is the bilinear one (1/2, 1/4).
+ * Coefficients that point at the Dirichlet ring are never read.  For the constant Poisson stencil and its Galerkin
+ * coarse operators the weights are exactly 1/2 and 1/4.  The hierarchy keeps eight weight grids per coarse level (two
+ * more words per fine point for each transfer); restriction and prolongation of every general-operator level, in
+ * every schedule and stand-alone entry point, then use them (R = c P^T, c = 1 for CONSISTENT, 1/4 for FW16).
+ * The weight grids are allocated by the first OPERATOR build, kept (unused) through a later BILINEAR build so that
+ * switching back allocates nothing, and freed by mgx_destroy. */
+enum { MGX_TRANSFER_BILINEAR = 0, MGX_TRANSFER_OPERATOR = 1 };
+/* mgx_build_galerkin with a choice of P.  BILINEAR: exactly mgx_build_galerkin (same bits).  OPERATOR: on every
+ * level l = finest .. coarsest + 1 first the weights of P_l from A_l, then A_{l-1} = R_l A_l P_l with R_l = c P_l^T.
+ * Handles with op = MGX_OPERATOR_GALERKIN only (others: MGX_ERR_STATE); other values of `transfer`: MGX_ERR_INVALID. */
+MGX_API int mgx_build_galerkin_transfer(mgx_handle h, int transfer);
+/* 0 / 1: what the hierarchy was built with; MGX_ERR_STATE before a build and on a handle whose op is not GALERKIN */
+MGX_API int mgx_get_transfer(mgx_handle h, int* transfer);
+/* read back the weights of P between `level` (fine) and level - 1: eight grids in the host layout of level - 1
+ * (n_c x n_c interior, row-major, the handle's working type), which = 0..7 in the order n, s, w, e, nw, ne, sw, se:
+ * the weight with which coarse point (I, J) contributes to fine point (2I + di, 2J + dj).  The coincident weight is 1
+ * and is not stored.  MGX_ERR_STATE on a BILINEAR hierarchy or before a build. */
+MGX_API int mgx_get_prolongation(mgx_handle h, int level, int which, void* dst, size_t count);
+
 /* ---- grid operators (one call = the reference function named) ------------
  * On a dtype MIXED handle the finest level holds double data for the accessors above and a
  * float correction / residual pair for the inner cycle, so the operators and schedules below

@@ -26,6 +26,7 @@ SCHEDULE_V, SCHEDULE_FMG = 0, 1
 RESTRICT_CONSISTENT, RESTRICT_FW16, RESTRICT_INJECT, RESTRICT_INJECT4 = 0, 1, 2, 3
 OPERATOR_POISSON, OPERATOR_STENCIL5 = 0, 1
 OPERATOR_GALERKIN = OP_GALERKIN = 3      # coarse operators R A P (nine-point), built on the device by build_galerkin()
+TRANSFER_BILINEAR, TRANSFER_OPERATOR = 0, 1     # P of the Galerkin hierarchy: weights 1/2, 1/4, or read off the operator's stencil
 BOTTOM_EXACT, BOTTOM_SMOOTH = 0, 1
 ARITH_SEPARATE, ARITH_FMA = 0, 1
 VEC_U, VEC_B, VEC_R = 0, 1, 2
@@ -46,6 +47,7 @@ EXPORTS = [
     "mgx_create_rank", "mgx_dist_exchanges", "mgx_dist_overlapped", "mgx_memcpy_d2h", "mgx_memcpy_h2d", "mgx_runtime_libs",
     "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg",
     "mgx_build_galerkin", "mgx_get_stencil9",
+    "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation",
 ]
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
@@ -198,6 +200,9 @@ def lib() -> C.CDLL:
     L.mgx_get_stencil.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.mgx_build_galerkin.argtypes = [vp]
     L.mgx_get_stencil9.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
+    L.mgx_build_galerkin_transfer.argtypes = [vp, C.c_int]
+    L.mgx_get_transfer.argtypes = [vp, ip]
+    L.mgx_get_prolongation.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     _lib = L
     return L
 
@@ -414,10 +419,29 @@ class Multigrid:
         return a
 
     # -- Galerkin coarse operators (op = OPERATOR_GALERKIN) ------------------------------
-    def build_galerkin(self):
+    def build_galerkin(self, transfer=None):
         """A_{l-1} = R A_l P below the finest operator (set_stencil / set_coefficient), every level's Jacobi splitting
-        and the coarsest operator's dense inverse"""
-        self._chk(lib().mgx_build_galerkin(self._h), "mgx_build_galerkin")
+        and the coarsest operator's dense inverse.  transfer: None / TRANSFER_BILINEAR (P with the weights 1/2, 1/4) or
+        TRANSFER_OPERATOR (the operator-dependent P, its weights read off A_l on every level; R = c P^T)"""
+        if transfer is None:
+            self._chk(lib().mgx_build_galerkin(self._h), "mgx_build_galerkin")
+        else:
+            self._chk(lib().mgx_build_galerkin_transfer(self._h, int(transfer)), "mgx_build_galerkin_transfer")
+
+    @property
+    def transfer(self):
+        """TRANSFER_BILINEAR / TRANSFER_OPERATOR: what the Galerkin hierarchy was built with"""
+        out = C.c_int()
+        self._chk(lib().mgx_get_transfer(self._h, C.byref(out)), "mgx_get_transfer")
+        return out.value
+
+    def get_prolongation(self, level, which):
+        """weights of P between `level` and level - 1 (TRANSFER_OPERATOR hierarchies): which = 0..7: n, s, w, e, nw,
+        ne, sw, se, on the interior of level - 1"""
+        n = self.n(level - 1) if level >= 2 else 1
+        a = np.empty((n, n), dtype=self.level_dtype(level))
+        self._chk(lib().mgx_get_prolongation(self._h, level, which, a.ctypes.data, a.size), "mgx_get_prolongation")
+        return a
 
     def get_stencil9(self, level, which):
         """which = 0..8: c, n, s, w, e, nw, ne, sw, se;  9: D_inv;  10..17: the off-diagonals of R_omega (n .. se)"""

@@ -17,6 +17,7 @@
 #include "mgx_launch.hpp"
 #include "mgx_var.hpp"
 #include "mgx_galerkin.hpp"
+#include "mgx_opdep.hpp"
 #include "mgx_krylov.hpp"
 #include "mgx_dist_plan.hpp"
 
@@ -58,6 +59,9 @@ struct Level {
     // nine-point operator R A P and of its R_omega
     void* corner[4] = {nullptr, nullptr, nullptr, nullptr};
     void* jcorner[4] = {nullptr, nullptr, nullptr, nullptr};
+    // MGX_TRANSFER_OPERATOR (mgx_opdep.hpp): the eight weight grids (n, s, w, e, nw, ne, sw, se) of P between level
+    // L + 1 and this level, allocated by the first OPERATOR build
+    void* wt[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool nine = false;
     bool stencil_set = false;
     size_t esize() const { return f64 ? 8 : 4; }
@@ -113,6 +117,7 @@ struct mgx_solver {
     bool var = false;               // cfg.op == MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN
     bool galerkin = false;          // cfg.op == MGX_OPERATOR_GALERKIN: coarse operators are R A P (mgx_build_galerkin)
     bool gal_built = false;         // ... and have been built from the current finest operator
+    int transfer = MGX_TRANSFER_BILINEAR;   // ... with this prolongation (mgx_build_galerkin_transfer)
     // mgx_solve_pcg (allocated by its first call): iterate x, directions p / p' (ping-pong), q = A p, the caller's b
     // while r occupies lv[finest].b, per-block partials of the Krylov passes, the device scalars and their host copy
     void *pcg_x = nullptr, *pcg_p[2] = {nullptr, nullptr}, *pcg_q = nullptr, *pcg_b = nullptr;
@@ -242,7 +247,8 @@ void free_level(Level& l)
 {
     for (void** p : {&l.u, &l.b, &l.tmp, &l.r, &l.coef[0], &l.coef[1], &l.coef[2], &l.coef[3], &l.coef[4],
                      &l.jac[0], &l.jac[1], &l.jac[2], &l.jac[3], &l.jac[4], &l.corner[0], &l.corner[1], &l.corner[2], &l.corner[3],
-                     &l.jcorner[0], &l.jcorner[1], &l.jcorner[2], &l.jcorner[3]}) {
+                     &l.jcorner[0], &l.jcorner[1], &l.jcorner[2], &l.jcorner[3], &l.wt[0], &l.wt[1], &l.wt[2], &l.wt[3], &l.wt[4], &l.wt[5],
+                     &l.wt[6], &l.wt[7]}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -368,18 +374,56 @@ template <typename T> Op9Out<T> out9(const Op9<T>& o)
     return w;
 }
 
-// A_{l-1} = R A_l P for l = finest .. coarsest + 1, then {D_inv, R_omega} of every level and the dense inverse of
-// the coarsest operator
+template <typename T> Wt8<T> wt8_of(const Level& c)
+{
+    Wt8<T> w;
+    for (int x = 0; x < 8; ++x) w.w[x] = (const T*)c.wt[x];
+    return w;
+}
+template <typename T> Wt8Out<T> wt8_out(const Level& c)
+{
+    Wt8Out<T> w;
+    for (int x = 0; x < 8; ++x) w.w[x] = (T*)c.wt[x];
+    return w;
+}
+
+// the hierarchy in use has operator-dependent transfers (mgx_opdep.hpp)
+inline bool opdep(const mgx_solver* s) { return s->galerkin && s->gal_built && s->transfer == MGX_TRANSFER_OPERATOR; }
+
+// A_{l-1} = R A_l P for l = finest .. coarsest + 1 (transfer = OPERATOR: the weights of P_l from A_l first), then
+// {D_inv, R_omega} of every level and the dense inverse of the coarsest operator
 template <typename T>
-int galerkin_build_t(mgx_solver* s)
+int galerkin_build_t(mgx_solver* s, int transfer)
 {
     const int lo = s->cfg.coarsest_level, hi = s->cfg.finest_level;
     const T rscale = (s->cfg.restrict_mode == MGX_RESTRICT_FW16) ? (T)0.25 : (T)1;
+    // every allocation before the first launch: a failure here leaves the previous hierarchy, gal_built and transfer as
+    // they were (grids already allocated stay for the next attempt; mgx_destroy frees them)
+    if (transfer == MGX_TRANSFER_OPERATOR)
+        for (int lv = lo; lv < hi; ++lv)
+            for (void*& p : s->lv[lv].wt) {
+                if (p) continue;
+                if (hipMalloc(&p, s->lv[lv].bytes) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the prolongation's weight arrays");
+                HIPCHK(s, hipMemsetAsync(p, 0, s->lv[lv].bytes, s->stream));      // the ring and the padding stay zero from here on
+            }
     for (int lv = hi; lv > lo; --lv) {
         const Level& f = s->lv[lv];
         const Level& c = s->lv[lv - 1];
         const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
-        if (f.nine) hipLaunchKernelGGL((k_galerkin_rap<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), out9(op9_of<T>(c)),
+        if (transfer == MGX_TRANSFER_OPERATOR) {
+            if (f.nine) {
+                hipLaunchKernelGGL((k_opdep_weights<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), wt8_out<T>(c), c.N,
+                                   f.pitch, c.pitch, g.strips);
+                hipLaunchKernelGGL((k_galerkin_rap_opdep<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), wt8_of<T>(c),
+                                   out9(op9_of<T>(c)), c.N, f.pitch, c.pitch, g.strips, rscale);
+            } else {
+                hipLaunchKernelGGL((k_opdep_weights<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), wt8_out<T>(c), c.N,
+                                   f.pitch, c.pitch, g.strips);
+                hipLaunchKernelGGL((k_galerkin_rap_opdep<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), wt8_of<T>(c),
+                                   out9(op9_of<T>(c)), c.N, f.pitch, c.pitch, g.strips, rscale);
+            }
+        }
+        else if (f.nine) hipLaunchKernelGGL((k_galerkin_rap<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), out9(op9_of<T>(c)),
                                        c.N, f.pitch, c.pitch, g.strips, rscale);
         else hipLaunchKernelGGL((k_galerkin_rap<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), out9(op9_of<T>(c)),
                                 c.N, f.pitch, c.pitch, g.strips, rscale);
@@ -406,7 +450,8 @@ int galerkin_build_t(mgx_solver* s)
     HIPCHK(s, hipStreamSynchronize(s->stream));
     for (int lv = lo; lv <= hi; ++lv) s->lv[lv].stencil_set = true;
     s->gal_built = true;
-    drop_graphs(s);          // the buffers have not moved, but a new hierarchy is a new problem: recapture
+    s->transfer = transfer;
+    drop_graphs(s);          // the buffers have not moved, but a new hierarchy (or another P) is a new problem: recapture
     return MGX_OK;
 }
 
@@ -431,6 +476,9 @@ int var_ready(mgx_solver* s, int lo, int hi)
             return s->fail(MGX_ERR_STATE, "operator of level " + std::to_string(l) + " not set (mgx_set_stencil / mgx_set_coefficient)");
     return MGX_OK;
 }
+
+// f(double{}) or f(float{}): the working type as a tag
+template <typename F> void with_float_type(bool f64, F&& f) { if (f64) f(double{}); else f(float{}); }
 
 // MF:75-96: mu sweeps, one launch each, u <-> tmp
 template <typename T>
@@ -633,6 +681,23 @@ void restrict_level(mgx_solver* s, int level, bool fused, bool zero_guess)
     Prof p(s, fine ? MGX_PROF_RESTRICT_FINE : MGX_PROF_COARSE, 1);
     const int rpc = s->rows_per_chunk;
     const int mode = s->cfg.restrict_mode;
+    if (opdep(s)) {
+        // B_c = c P^T (B - A U) or c P^T B with the hierarchy's own weights, the residual formed in the same pass
+        with_float_type(f.f64, [&](auto tag) {
+            using T = decltype(tag);
+            const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
+            const T rscale = (mode == MGX_RESTRICT_FW16) ? (T)0.25 : (T)1;
+            T* cz = zero_guess ? (T*)c.u : nullptr;
+            const dim3 grd(g.blocks), blk(kBlock);
+            if (!fused) hipLaunchKernelGGL((k_restrict_opdep<T, 0>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b, op9_of<T>(f), wt8_of<T>(c),
+                                           (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
+            else if (f.nine) hipLaunchKernelGGL((k_restrict_opdep<T, 2>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b, op9_of<T>(f),
+                                                wt8_of<T>(c), (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
+            else hipLaunchKernelGGL((k_restrict_opdep<T, 1>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b, op9_of<T>(f), wt8_of<T>(c),
+                                    (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
+        });
+        return;
+    }
     if (s->var || mode >= MGX_RESTRICT_INJECT) {
         // general operator and / or injection (MF:122-130): the residual is formed first (MF:150-153; f.r was
         // allocated with the handle), then restricted by full weighting (PS:531-546) or injected
@@ -674,6 +739,17 @@ void prolong_level(mgx_solver* s, int level, bool add)
     const bool fine = (level == s->cfg.finest_level);
     Prof p(s, fine ? MGX_PROF_PROLONG_FINE : MGX_PROF_COARSE, 1);
     const int rpc = s->rows_per_chunk;
+    if (opdep(s)) {
+        with_float_type(f.f64, [&](auto tag) {
+            using T = decltype(tag);
+            const Launch g = make_launch(c.N, VecOf<T>::W, c.N, 1);
+            if (add) hipLaunchKernelGGL((k_prolong_opdep<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)f.u, (const T*)c.u, wt8_of<T>(c),
+                                        c.N, f.pitch, c.pitch, g.strips);
+            else hipLaunchKernelGGL((k_prolong_opdep<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)f.u, (const T*)c.u, wt8_of<T>(c),
+                                    c.N, f.pitch, c.pitch, g.strips);
+        });
+        return;
+    }
     if (f.f64)
         launch_prolong<double>((double*)f.u, (const double*)c.u, f.N, f.pitch, c.pitch, 1, f.N, 0, add, rpc, s->stream);
     else
@@ -1537,7 +1613,43 @@ int mgx_build_galerkin(mgx_handle s)
     if (!s->galerkin) return s->fail(MGX_ERR_STATE, "handle was not created with op = MGX_OPERATOR_GALERKIN");
     if (!s->lv[s->cfg.finest_level].stencil_set)
         return s->fail(MGX_ERR_STATE, "finest operator not set (mgx_set_stencil / mgx_set_coefficient)");
-    return s->work_f64 ? galerkin_build_t<double>(s) : galerkin_build_t<float>(s);
+    return s->work_f64 ? galerkin_build_t<double>(s, MGX_TRANSFER_BILINEAR) : galerkin_build_t<float>(s, MGX_TRANSFER_BILINEAR);
+}
+
+int mgx_build_galerkin_transfer(mgx_handle s, int transfer)
+{
+    if (!s) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (!s->galerkin) return s->fail(MGX_ERR_STATE, "handle was not created with op = MGX_OPERATOR_GALERKIN");
+    if (transfer != MGX_TRANSFER_BILINEAR && transfer != MGX_TRANSFER_OPERATOR)
+        return s->fail(MGX_ERR_INVALID, "transfer must be MGX_TRANSFER_BILINEAR or MGX_TRANSFER_OPERATOR");
+    if (!s->lv[s->cfg.finest_level].stencil_set)
+        return s->fail(MGX_ERR_STATE, "finest operator not set (mgx_set_stencil / mgx_set_coefficient)");
+    return s->work_f64 ? galerkin_build_t<double>(s, transfer) : galerkin_build_t<float>(s, transfer);
+}
+
+int mgx_get_transfer(mgx_handle s, int* transfer)
+{
+    if (!s || !transfer) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (!s->galerkin) return s->fail(MGX_ERR_STATE, "handle was not created with op = MGX_OPERATOR_GALERKIN");
+    if (!s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
+    *transfer = s->transfer;
+    return MGX_OK;
+}
+
+int mgx_get_prolongation(mgx_handle s, int level, int which, void* dst, size_t count)
+{
+    if (!s || !dst) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (!s->galerkin) return s->fail(MGX_ERR_STATE, "handle was not created with op = MGX_OPERATOR_GALERKIN");
+    if (level <= s->cfg.coarsest_level || level > s->cfg.finest_level || which < 0 || which > 7)
+        return s->fail(MGX_ERR_INVALID, "level or array selector out of range");
+    if (!s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
+    if (s->transfer != MGX_TRANSFER_OPERATOR)
+        return s->fail(MGX_ERR_STATE, "the hierarchy was built with MGX_TRANSFER_BILINEAR: its weights are 1/2 and 1/4 and are not stored");
+    Level& c = s->lv[level - 1];
+    return copy_out(s, c, c.wt[which], dst, count);
 }
 
 int mgx_get_stencil9(mgx_handle s, int level, int which, void* dst, size_t count)

@@ -7,7 +7,11 @@ markdown kept as profiles/galerkin_kernel_trace_summary.md:
   - time to 1e-8 (sine right-hand side as tools/pcg_bench.py): mgx_solve and mgx_solve_pcg at 2047^2 contrast 10 and
     511^2 contrast 100.
 Wall times around calls that end in a device synchronise (40 sweeps or 20 residuals per timed call).
-    python tools/galerkin_bench.py [--quick]"""
+    python tools/galerkin_bench.py [--quick]
+--transfer: instead, the tables of profiles/opdep_kernel_trace_summary.md - BILINEAR against OPERATOR prolongation
+(mgx_build_galerkin_transfer, csrc/mgx_opdep.hpp): mgx_restrict / mgx_prolong_add on the finest level and the one below,
+the build, and time and cycles to 1e-8 (constant right-hand side; 2047^2: the random one of seed 3).
+--transfer --trace-only: the builds and five calls of each transfer only, for a rocprofv3 --kernel-trace --stats run."""
 import os
 import statistics
 import sys
@@ -23,6 +27,7 @@ from pcg_ref import contrast_coefficient  # noqa: E402
 
 pkg = ge.load_package()
 QUICK = "--quick" in sys.argv
+TRACE_ONLY = "--trace-only" in sys.argv
 LF = 9 if QUICK else 13          # finest level of the kernel / set-up handles; the timed nine-point level is LF - 1
 LK = LF - 1
 
@@ -110,7 +115,76 @@ def solves():
             print(f"| {(1 << L) - 1}^2 contrast {contrast:g} | {cells[0]} | {cells[1]} |", flush=True)
 
 
+def transfers():
+    """words per fine point moved by the algorithm (OPERATOR): fused restriction U, B, A (5 or 9 grids), B_c (1/4), weights
+    (2); prolongation U in and out, e (1/4), weights (2).  BILINEAR runs the restriction as two kernels (residual, then
+    k_restrict) and its times are the pair's"""
+    x = np.linspace(0.0, 1.0, (1 << LF) + 1)
+    a = 1.0 + 0.8 * np.sin(3 * np.pi * x)[None, :] * np.cos(2 * np.pi * x)[:, None]
+    rng = np.random.default_rng(0)
+    print("| call | fine grid | transfer | ms per call (one host synchronise each) | words per fine point | achieved GB/s | fraction of 8 TB/s |")
+    print("|---|---|---|---|---|---|---|")
+    with pkg.Multigrid(finest_level=LF, coarsest_level=5, mu1=2, mu2=2, schedule=0, op=pkg.OP_GALERKIN, omega=0.8) as mg:
+        mg.set_coefficient(a)
+        lib, h = pkg.lib(), mg._h
+        for lv in (LK, LF):
+            n = (1 << lv) - 1
+            mg.set_level(lv, pkg.VEC_U, rng.uniform(-1, 1, (n, n)))
+            mg.set_level(lv, pkg.VEC_B, rng.uniform(-1, 1, (n, n)))
+        for transfer, tname in ((pkg.TRANSFER_BILINEAR, "BILINEAR"), (pkg.TRANSFER_OPERATOR, "OPERATOR")):
+            mg.build_galerkin(transfer)
+            build_ms = wall(lambda: mg.build_galerkin(transfer))
+            if TRACE_ONLY:                              # under rocprofv3 --kernel-trace --stats: five launches of each kernel
+                for lv in (LK, LF):
+                    for fn in (lib.mgx_restrict, lib.mgx_prolong_add):
+                        for _ in range(5):
+                            fn(h, lv)
+                continue
+            for lv in (LK, LF):
+                n = (1 << lv) - 1
+                agrids = 9 if lv < LF else 5
+                extra = 2.0 if transfer == pkg.TRANSFER_OPERATOR else 0.0
+                for fn, label, words in ((lib.mgx_restrict, "mgx_restrict (residual fused in)", 2 + agrids + 0.25 + extra),
+                                         (lib.mgx_prolong_add, "mgx_prolong_add", 2 + 0.25 + extra)):
+                    fn(h, lv)
+
+                    def rep20():
+                        for _ in range(20):
+                            fn(h, lv)
+                    ms = wall(rep20) / 20
+                    gbs = words * 8 * n * n / (ms * 1e-3) / 1e9
+                    print(f"| {label} | {1 << lv}^2 | {tname} | {ms:.4f} | {words:g} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
+            print(f"| mgx_build_galerkin_transfer, levels {LF}..5 | {1 << LF}^2 | {tname} | {build_ms:.1f} | | | |", flush=True)
+    if TRACE_ONLY:
+        return
+    print("\n| problem, V(2,2), levels L..5, f64 | transfer | mgx_solve | mgx_solve_pcg |\n|---|---|---|---|")
+    for L, contrast in ((9, 10.0), (9, 100.0), (9, 1000.0)) if QUICK else ((11, 10.0), (9, 100.0), (9, 1000.0)):
+        n = (1 << L) - 1
+        b = np.random.default_rng(3).standard_normal((n, n)) if L == 11 else None
+        with pkg.Multigrid(finest_level=L, coarsest_level=5, mu1=2, mu2=2, schedule=0, op=pkg.OP_GALERKIN) as mg:
+            mg.set_coefficient(contrast_coefficient(L, contrast))
+            for transfer, tname in ((pkg.TRANSFER_BILINEAR, "BILINEAR"), (pkg.TRANSFER_OPERATOR, "OPERATOR")):
+                mg.build_galerkin(transfer)
+                if b is None:
+                    mg.fill_rhs(0)
+                else:
+                    mg.set_rhs(b)
+                cells = []
+                for f in (lambda: mg.solve(tol=1e-8, max_cycles=150), lambda: mg.solve_pcg(tol=1e-8, max_iters=200)):
+                    ts = []
+                    for rep in range(6):                    # the first run captures the graphs: not timed
+                        mg.set_guess(np.zeros((n, n)))
+                        st, hist = f()
+                        if rep:
+                            ts.append(st.seconds * 1e3)
+                    cells.append(f"{st.cycles} {'it' if len(cells) else 'cycles'}, {statistics.median(ts):.2f} ms (min {min(ts):.2f}, max {max(ts):.2f}), converged {st.converged}")
+                print(f"| {n}^2 contrast {contrast:g} | {tname} | {cells[0]} | {cells[1]} |", flush=True)
+
+
 if __name__ == "__main__":
-    r = kernels()
-    setup(r)
-    solves()
+    if "--transfer" in sys.argv:
+        transfers()
+    else:
+        r = kernels()
+        setup(r)
+        solves()
