@@ -42,7 +42,17 @@ typedef enum {
     MGX_ERR_STATE = 5         /* call not valid in the handle's current state */
 } mgx_status;
 
-enum { MGX_SMOOTHER_JACOBI = 0, MGX_SMOOTHER_RBGS = 1 };
+enum { MGX_SMOOTHER_JACOBI = 0, MGX_SMOOTHER_RBGS = 1,
+       /* CHEBYSHEV: a Chebyshev polynomial in omega D^-1 A on the interval [lmax / 4, lmax], lmax = omega g_l with g_l the
+        * Gershgorin bound of the level's D^-1 A (mgx_get_lambda_max); csrc/mgx_cheby.hpp states the iteration.  mu1 / mu2
+        * (and the mu of mgx_smooth, the sweeps of mgx_time_smoother) are then the DEGREES of the pre- / post-smoothing
+        * blocks: a block of degree k is k launches and damps [lmax / 4, lmax] by 1 / T_k(5/3) (0.22, 0.074, 0.025 for
+        * k = 2, 3, 4 against (2/3)^k of Jacobi with omega = 2/3); every block starts afresh; degree 0 is no smoothing.
+        * The iterates do not depend on omega beyond rounding.  Handles with op = MGX_OPERATOR_STENCIL5 or
+        * MGX_OPERATOR_GALERKIN only, dtype F64 or F32, arith SEPARATE, one GPU; with op = MGX_OPERATOR_POISSON, in
+        * mgx_create_rank, mgx_plan_create and mgx_slab_cycle it is MGX_ERR_INVALID.  One more array per level (the
+        * direction d) and 10 / 14 sizeof(T) per point and step on five- / nine-point levels (Jacobi: 8 / 12). */
+       MGX_SMOOTHER_CHEBYSHEV = 2 };
 enum { MGX_DTYPE_F32 = 0, MGX_DTYPE_F64 = 1, MGX_DTYPE_MIXED = 2 };
 enum { MGX_SCHEDULE_V = 0, MGX_SCHEDULE_FMG = 1 };
 enum { MGX_RESTRICT_CONSISTENT = 0, MGX_RESTRICT_FW16 = 1,
@@ -53,7 +63,7 @@ enum { MGX_RESTRICT_CONSISTENT = 0, MGX_RESTRICT_FW16 = 1,
  * general five-point operator PER LEVEL (A_sp_dict[level]) given by the caller as five coefficient grids
  * (mgx_set_stencil) or re-discretised from a nodal coefficient a(x, y) of -div(a grad u) (mgx_set_coefficient),
  * smoothed in MF's form  v <- R_omega v + omega D^-1 b  (MF:86-93), residual b - A v (MF:150-153), direct solve of
- * the coarsest operator (MF:63-72: dense inverse; coarsest_level <= 5).  dtype F64 / F32, Jacobi, one GPU.
+ * the coarsest operator (MF:63-72: dense inverse; coarsest_level <= 5).  dtype F64 / F32, Jacobi or Chebyshev, one GPU.
  * Algorithmic bytes per point and sweep: 8 sizeof(T) (v, b, D_inv, four R arrays in; v' out). */
 enum { MGX_OPERATOR_POISSON = 0, MGX_OPERATOR_STENCIL5 = 1,
        /* GALERKIN: the variational hierarchy.  The finest level is a general five-point operator given as for STENCIL5;
@@ -83,8 +93,8 @@ typedef struct {
     int coarsest_level;   /* PS:18; >= 2, and <= 8 with bottom = EXACT (the dense sine-transform
                              solve holds (2^L - 1)^2 matrices: 255^2 at level 8; PS:18 uses 7) */
     int mu0;              /* PS:20  FMG runs mu0+1 V-cycles per level (PS:646) */
-    int mu1;              /* PS:21  pre-smoothing sweeps  */
-    int mu2;              /* PS:22  post-smoothing sweeps */
+    int mu1;              /* PS:21  pre-smoothing sweeps  (smoother = CHEBYSHEV: degree of the pre-smoothing block) */
+    int mu2;              /* PS:22  post-smoothing sweeps (smoother = CHEBYSHEV: degree of the post-smoothing block) */
     double omega;         /* PS:127 Jacobi weight */
     int smoother;         /* MGX_SMOOTHER_*  (RBGS: BASELINE config 3) */
     int dtype;            /* MGX_DTYPE_*     (PS is f32, MF is f64; MIXED: config 5) */
@@ -230,13 +240,23 @@ MGX_API int mgx_get_transfer(mgx_handle h, int* transfer);
  * and is not stored.  MGX_ERR_STATE on a BILINEAR hierarchy or before a build. */
 MGX_API int mgx_get_prolongation(mgx_handle h, int level, int which, void* dst, size_t count);
 
+/* ---- the eigenvalue bound of a general-operator level (csrc/mgx_cheby.hpp) --------------------------------------
+ * g_l = max over the level's interior points of  1 + sum_x |D_inv a_x|  (x: the four off-diagonals n, s, w, e of a
+ * five-point level, the eight n, s, w, e, nw, ne, sw, se of a nine-point one; accumulated in double in that order;
+ * coefficients that point at the Dirichlet ring are not counted): the Gershgorin bound of the spectrum of D^-1 A, which
+ * the Chebyshev smoother uses as lmax / omega.  Computed on the device whenever the level's operator is (re)built
+ * (mgx_set_stencil, mgx_set_coefficient, mgx_build_galerkin, mgx_build_galerkin_transfer), for either smoother.
+ * 2 exactly for the constant Poisson stencil.  MGX_ERR_STATE before the level's operator exists (before mgx_set_stencil
+ * on a STENCIL5 level, before the build on a GALERKIN handle) and on a handle with op = MGX_OPERATOR_POISSON. */
+MGX_API int mgx_get_lambda_max(mgx_handle h, int level, double* out);
+
 /* ---- grid operators (one call = the reference function named) ------------
  * On a dtype MIXED handle the finest level holds double data for the accessors above and a
  * float correction / residual pair for the inner cycle, so the operators and schedules below
  * return MGX_ERR_STATE when asked to act on the finest level (use mgx_solve there, or a F64 /
  * F32 handle); the coarser levels of a MIXED handle are ordinary float levels. */
 /* jacobirelaxation(q, a_lu, size, v, f, mu)  PS:125-147 / MF:75-96; with
- * smoother = RBGS: mu red-black Gauss-Seidel sweeps.  Acts on U,B of `level`. */
+ * smoother = RBGS: mu red-black Gauss-Seidel sweeps; smoother = CHEBYSHEV: one block of degree mu.  Acts on U,B of `level`. */
 MGX_API int mgx_smooth(mgx_handle h, int level, int mu);
 /* residual block of vcyclemultigrid  PS:591-608 / MF:145-153:  R = B - A U. */
 MGX_API int mgx_residual(mgx_handle h, int level);

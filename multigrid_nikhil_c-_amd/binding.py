@@ -21,6 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGX_LIBMGX_PATH") or os.path.join(_HERE, "libmgx.so")
 
 SMOOTHER_JACOBI, SMOOTHER_RBGS = 0, 1
+SMOOTHER_CHEBYSHEV = 2      # Chebyshev polynomial smoother of the general-operator hierarchies (mu1 / mu2: degrees)
 DTYPE_F32, DTYPE_F64, DTYPE_MIXED = 0, 1, 2
 SCHEDULE_V, SCHEDULE_FMG = 0, 1
 RESTRICT_CONSISTENT, RESTRICT_FW16, RESTRICT_INJECT, RESTRICT_INJECT4 = 0, 1, 2, 3
@@ -47,7 +48,7 @@ EXPORTS = [
     "mgx_create_rank", "mgx_dist_exchanges", "mgx_dist_overlapped", "mgx_memcpy_d2h", "mgx_memcpy_h2d", "mgx_runtime_libs",
     "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg",
     "mgx_build_galerkin", "mgx_get_stencil9",
-    "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation",
+    "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max",
 ]
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
@@ -203,6 +204,7 @@ def lib() -> C.CDLL:
     L.mgx_build_galerkin_transfer.argtypes = [vp, C.c_int]
     L.mgx_get_transfer.argtypes = [vp, ip]
     L.mgx_get_prolongation.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
+    L.mgx_get_lambda_max.argtypes = [vp, C.c_int, dp]
     _lib = L
     return L
 
@@ -442,6 +444,12 @@ class Multigrid:
         a = np.empty((n, n), dtype=self.level_dtype(level))
         self._chk(lib().mgx_get_prolongation(self._h, level, which, a.ctypes.data, a.size), "mgx_get_prolongation")
         return a
+
+    def lambda_max(self, level):
+        """g_l: the Gershgorin bound of the spectrum of D^-1 A of the level's current operator (mgx_get_lambda_max)"""
+        out = C.c_double()
+        self._chk(lib().mgx_get_lambda_max(self._h, level, C.byref(out)), "mgx_get_lambda_max")
+        return out.value
 
     def get_stencil9(self, level, which):
         """which = 0..8: c, n, s, w, e, nw, ne, sw, se;  9: D_inv;  10..17: the off-diagonals of R_omega (n .. se)"""

@@ -18,6 +18,7 @@
 #include "mgx_var.hpp"
 #include "mgx_galerkin.hpp"
 #include "mgx_opdep.hpp"
+#include "mgx_cheby.hpp"
 #include "mgx_krylov.hpp"
 #include "mgx_dist_plan.hpp"
 
@@ -64,6 +65,10 @@ struct Level {
     void* wt[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool nine = false;
     bool stencil_set = false;
+    // MGX_SMOOTHER_CHEBYSHEV (mgx_cheby.hpp): the direction d of a smoothing block (allocated at create for that smoother
+    // only) and, for either smoother, the bound g_l of the spectrum of D^-1 A of the level's current operator
+    void* cheb = nullptr;
+    double lambda_g = 0.0;
     size_t esize() const { return f64 ? 8 : 4; }
 };
 
@@ -248,7 +253,7 @@ void free_level(Level& l)
     for (void** p : {&l.u, &l.b, &l.tmp, &l.r, &l.coef[0], &l.coef[1], &l.coef[2], &l.coef[3], &l.coef[4],
                      &l.jac[0], &l.jac[1], &l.jac[2], &l.jac[3], &l.jac[4], &l.corner[0], &l.corner[1], &l.corner[2], &l.corner[3],
                      &l.jcorner[0], &l.jcorner[1], &l.jcorner[2], &l.jcorner[3], &l.wt[0], &l.wt[1], &l.wt[2], &l.wt[3], &l.wt[4], &l.wt[5],
-                     &l.wt[6], &l.wt[7]}) {
+                     &l.wt[6], &l.wt[7], &l.cheb}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -333,30 +338,6 @@ void drop_graphs(mgx_solver* s)
     s->graphs.clear();
 }
 
-// the level's operator has been written into l.coef[]: build {D_inv, R_omega} (MF:28-32) and, on the coarsest
-// level with an exact bottom solve, the dense inverse (MF:63-72)
-template <typename T>
-int var_build_t(mgx_solver* s, Level& l)
-{
-    const dim3 blk(256), grd((l.N + 1 + 255) / 256, l.N + 1);
-    hipLaunchKernelGGL((k_var_build_jacobi<T>), grd, blk, 0, s->stream, (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2],
-                       (const T*)l.coef[3], (const T*)l.coef[4], (T*)l.jac[0], (T*)l.jac[1], (T*)l.jac[2], (T*)l.jac[3], (T*)l.jac[4],
-                       l.N, l.pitch, (T)s->cfg.omega);
-    if (l.L == s->cfg.coarsest_level && s->cfg.bottom == MGX_BOTTOM_EXACT) {
-        const int n = l.N - 1, NN = n * n;
-        hipLaunchKernelGGL((k_var_dense_fill<T>), dim3((NN + 255) / 256, NN), dim3(256), 0, s->stream, s->var_M, s->var_inv,
-                           (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3], (const T*)l.coef[4], n, l.pitch);
-        gj_invert(s, NN);
-    }
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    l.stencil_set = true;
-    drop_graphs(s);          // (the kernels' coefficient pointers are unchanged, but a new operator is a new problem: recapture)
-    return MGX_OK;
-}
-int var_build(mgx_solver* s, Level& l) { return l.f64 ? var_build_t<double>(s, l) : var_build_t<float>(s, l); }
-
-// ---- Galerkin hierarchy (cfg.op = MGX_OPERATOR_GALERKIN; kernels in mgx_galerkin.hpp) ---------------------
 template <typename T> Op9<T> op9_of(const Level& l)
 {
     return Op9<T>{{(const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3], (const T*)l.coef[4],
@@ -374,6 +355,51 @@ template <typename T> Op9Out<T> out9(const Op9<T>& o)
     return w;
 }
 
+template <typename T> ChebyLevel<T> cheby_level(const Level& l)
+{
+    return ChebyLevel<T>{op9_of<T>(l), jac9_of<T>(l), (const T*)l.jac[0], l.nine, l.N, l.rows, l.pitch};
+}
+
+// g_l of the operator and splitting just built on level l (k_lambda_partials, k_reduce_max): one 8-byte copy to the
+// host per level, at set-up only
+int lambda_update(mgx_solver* s, Level& l)
+{
+    if (l.f64) launch_lambda_max<double>(cheby_level<double>(l), s->partial, s->partial_cap, s->sum_dev, s->stream);
+    else launch_lambda_max<float>(cheby_level<float>(l), s->partial, s->partial_cap, s->sum_dev, s->stream);
+    HIPCHK(s, hipGetLastError());
+    HIPCHK(s, hipMemcpyAsync(s->sum_host, s->sum_dev, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    l.lambda_g = *s->sum_host;
+    return MGX_OK;
+}
+
+// the level's operator has been written into l.coef[]: build {D_inv, R_omega} (MF:28-32) and, on the coarsest
+// level with an exact bottom solve, the dense inverse (MF:63-72)
+template <typename T>
+int var_build_t(mgx_solver* s, Level& l)
+{
+    const dim3 blk(256), grd((l.N + 1 + 255) / 256, l.N + 1);
+    hipLaunchKernelGGL((k_var_build_jacobi<T>), grd, blk, 0, s->stream, (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2],
+                       (const T*)l.coef[3], (const T*)l.coef[4], (T*)l.jac[0], (T*)l.jac[1], (T*)l.jac[2], (T*)l.jac[3], (T*)l.jac[4],
+                       l.N, l.pitch, (T)s->cfg.omega);
+    if (l.L == s->cfg.coarsest_level && s->cfg.bottom == MGX_BOTTOM_EXACT) {
+        const int n = l.N - 1, NN = n * n;
+        hipLaunchKernelGGL((k_var_dense_fill<T>), dim3((NN + 255) / 256, NN), dim3(256), 0, s->stream, s->var_M, s->var_inv,
+                           (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3], (const T*)l.coef[4], n, l.pitch);
+        gj_invert(s, NN);
+    }
+    HIPCHK(s, hipGetLastError());
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    if (int rc = lambda_update(s, l)) return rc;
+    l.stencil_set = true;
+    // the kernels' coefficient pointers are unchanged, but a new operator is a new problem, and the Chebyshev scalars
+    // (from g_l) are kernel arguments of a captured cycle: recapture
+    drop_graphs(s);
+    return MGX_OK;
+}
+int var_build(mgx_solver* s, Level& l) { return l.f64 ? var_build_t<double>(s, l) : var_build_t<float>(s, l); }
+
+// ---- Galerkin hierarchy (cfg.op = MGX_OPERATOR_GALERKIN; kernels in mgx_galerkin.hpp) ---------------------
 template <typename T> Wt8<T> wt8_of(const Level& c)
 {
     Wt8<T> w;
@@ -448,6 +474,8 @@ int galerkin_build_t(mgx_solver* s, int transfer)
     }
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipStreamSynchronize(s->stream));
+    for (int lv = lo; lv <= hi; ++lv)
+        if (int rc = lambda_update(s, s->lv[lv])) return rc;
     for (int lv = lo; lv <= hi; ++lv) s->lv[lv].stencil_set = true;
     s->gal_built = true;
     s->transfer = transfer;
@@ -496,6 +524,30 @@ void smooth_var_t(mgx_solver* s, Level& l, int mu)
         std::swap(l.u, l.tmp);
     }
     s->last_smooth_launches = mu;
+}
+
+// a Chebyshev block of degree mu (mgx_cheby.hpp), one launch per step, u <-> tmp; every block starts afresh (step 0
+// overwrites the level's d)
+template <typename T>
+void smooth_cheby_t(mgx_solver* s, Level& l, int mu)
+{
+    const T om = (T)s->cfg.omega;
+    const T rc = (T)(1.0 - (double)om);
+    const std::vector<ChebyStep> st = cheby_scalars(s->cfg.omega, l.lambda_g, mu);
+    const ChebyLevel<T> cl = cheby_level<T>(l);
+    for (int i = 0; i < mu; ++i) {
+        launch_cheby<T>(cl, (const T*)l.u, (const T*)l.b, (T*)l.tmp, (T*)l.cheb, i == 0, rc, om, (T)st[i].a, (T)st[i].c, s->stream);
+        std::swap(l.u, l.tmp);
+    }
+    s->last_smooth_launches = mu;
+}
+
+// the level smoother of a general-operator handle
+void smooth_var(mgx_solver* s, Level& l, int mu)
+{
+    if (s->cfg.smoother == MGX_SMOOTHER_CHEBYSHEV) { if (l.f64) smooth_cheby_t<double>(s, l, mu); else smooth_cheby_t<float>(s, l, mu); }
+    else if (l.f64) smooth_var_t<double>(s, l, mu);       // MF:75-96
+    else smooth_var_t<float>(s, l, mu);
 }
 
 // MF:150-153: r = b - A u into `out` (MODE 0) or sum r^2 -> sum_dev (MODE 1)
@@ -666,7 +718,7 @@ void smooth(mgx_solver* s, int level, int mu)
     Level& l = s->lv[level];
     const bool fine = (level == s->cfg.finest_level);
     Prof p(s, fine ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, mu);
-    if (s->var) { if (l.f64) smooth_var_t<double>(s, l, mu); else smooth_var_t<float>(s, l, mu); }       // MF:75-96
+    if (s->var) smooth_var(s, l, mu);
     else smooth_t(s, l, mu);
     p.set(s->last_smooth_launches, mu);
     if (fine) s->fine_updates += (double)mu * (double)(l.N - 1) * (double)(l.N - 1);
@@ -1267,7 +1319,7 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     // in both precisions; level 8 (255^2) bounds the dense sine-transform solve.
     if (cfg->coarsest_level < 2 || cfg->finest_level < cfg->coarsest_level || cfg->finest_level > 15 ||
         cfg->mu0 < 0 || cfg->mu1 < 0 || cfg->mu2 < 0 || !(cfg->omega > 0.0 && cfg->omega < 2.0) ||
-        cfg->smoother < 0 || cfg->smoother > 1 || cfg->dtype < 0 || cfg->dtype > 2 ||
+        cfg->smoother < 0 || cfg->smoother > MGX_SMOOTHER_CHEBYSHEV || cfg->dtype < 0 || cfg->dtype > 2 ||
         cfg->schedule < 0 || cfg->schedule > 1 || cfg->restrict_mode < 0 || cfg->restrict_mode > MGX_RESTRICT_INJECT4 ||
         cfg->bottom < 0 || cfg->bottom > 1 || cfg->arith < 0 || cfg->arith > 1 || (cfg->op != MGX_OPERATOR_POISSON && cfg->op != MGX_OPERATOR_STENCIL5 && cfg->op != MGX_OPERATOR_GALERKIN)) {
         g_create_error = "invalid configuration";
@@ -1280,9 +1332,15 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
                              : "exact bottom solve supports coarsest_level <= 8";
         return MGX_ERR_INVALID;
     }
-    if (var && (cfg->dtype == MGX_DTYPE_MIXED || cfg->smoother != MGX_SMOOTHER_JACOBI || cfg->arith != MGX_ARITH_SEPARATE || cfg->n_gpus > 1)) {
-        g_create_error = galerkin ? "MGX_OPERATOR_GALERKIN: dtype F64 or F32, Jacobi, arith SEPARATE, one GPU"
-                                  : "MGX_OPERATOR_STENCIL5: dtype F64 or F32, Jacobi (MF:75-96), arith SEPARATE, one GPU";
+    const bool cheby = (cfg->smoother == MGX_SMOOTHER_CHEBYSHEV);
+    if (cheby && !var) {
+        g_create_error = "MGX_SMOOTHER_CHEBYSHEV: op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN only (the constant stencil has its fused and folded passes)";
+        return MGX_ERR_INVALID;
+    }
+    if (var && (cfg->dtype == MGX_DTYPE_MIXED || cfg->smoother == MGX_SMOOTHER_RBGS || cfg->arith != MGX_ARITH_SEPARATE || cfg->n_gpus > 1)) {
+        g_create_error = cheby ? "MGX_SMOOTHER_CHEBYSHEV: dtype F64 or F32, arith SEPARATE, one GPU"
+                       : galerkin ? "MGX_OPERATOR_GALERKIN: dtype F64 or F32, Jacobi or Chebyshev, arith SEPARATE, one GPU"
+                                  : "MGX_OPERATOR_STENCIL5: dtype F64 or F32, Jacobi (MF:75-96) or Chebyshev, arith SEPARATE, one GPU";
         return MGX_ERR_INVALID;
     }
     if (galerkin && cfg->restrict_mode >= MGX_RESTRICT_INJECT) {
@@ -1332,6 +1390,12 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
         for (int l = cfg->coarsest_level; l <= cfg->finest_level; ++l) {
             s->lv[l].nine = galerkin && l < cfg->finest_level;
             if ((rc = var_alloc_level(s, s->lv[l])) != MGX_OK) return bail(rc);
+            if (cheby) {
+                // the direction d of the Chebyshev blocks; zeroed once: its ring and padding are never written
+                Level& lv = s->lv[l];
+                if (hipMalloc(&lv.cheb, lv.bytes) != hipSuccess) { s->err = "hipMalloc failed for the Chebyshev direction array"; return bail(MGX_ERR_ALLOC); }
+                if (hipMemsetAsync(lv.cheb, 0, lv.bytes, s->stream) != hipSuccess) { s->err = "hipMemsetAsync failed"; return bail(MGX_ERR_HIP); }
+            }
         }
         if (cfg->bottom == MGX_BOTTOM_EXACT) {
             const size_t NN = (size_t)((1 << cfg->coarsest_level) - 1) * ((1 << cfg->coarsest_level) - 1);
@@ -1635,6 +1699,18 @@ int mgx_get_transfer(mgx_handle s, int* transfer)
     if (!s->galerkin) return s->fail(MGX_ERR_STATE, "handle was not created with op = MGX_OPERATOR_GALERKIN");
     if (!s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
     *transfer = s->transfer;
+    return MGX_OK;
+}
+
+int mgx_get_lambda_max(mgx_handle s, int level, double* out)
+{
+    if (!s || !out) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (!s->var) return s->fail(MGX_ERR_STATE, "handle was created with op = MGX_OPERATOR_POISSON (g = 2 for the constant stencil)");
+    if (!level_ok(s, level)) return s->fail(MGX_ERR_INVALID, "level out of range");
+    if (s->galerkin && !s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
+    if (!s->lv[level].stencil_set) return s->fail(MGX_ERR_STATE, "operator of this level not set");
+    *out = s->lv[level].lambda_g;
     return MGX_OK;
 }
 
@@ -2022,7 +2098,7 @@ int mgx_time_smoother(mgx_handle s, int sweeps, double* ms)
     HIPCHK(s, hipEventCreate(&b));
     Level& l = s->lv[s->cfg.finest_level];
     HIPCHK(s, hipEventRecord(a, s->stream));
-    if (s->var) { if (l.f64) smooth_var_t<double>(s, l, sweeps); else smooth_var_t<float>(s, l, sweeps); }
+    if (s->var) smooth_var(s, l, sweeps);
     else smooth_t(s, l, sweeps);
     HIPCHK(s, hipEventRecord(b, s->stream));
     HIPCHK(s, hipEventSynchronize(b));
@@ -2205,6 +2281,10 @@ int mgx_create_rank(const mgx_config* cfg, int rank, int world, const void* rccl
 {
     if (!cfg || !out) { g_create_error = "null argument"; return MGX_ERR_INVALID; }
     *out = nullptr;
+    if (cfg->smoother == MGX_SMOOTHER_CHEBYSHEV) {
+        g_create_error = "MGX_SMOOTHER_CHEBYSHEV: single-GPU handles of op = MGX_OPERATOR_STENCIL5 / MGX_OPERATOR_GALERKIN only";
+        return MGX_ERR_INVALID;
+    }
     if (cfg->coarsest_level < 2 || cfg->finest_level < cfg->coarsest_level || cfg->finest_level > 15 ||
         cfg->mu1 < 0 || cfg->mu2 < 0 || !(cfg->omega > 0.0 && cfg->omega < 2.0) || cfg->smoother < 0 || cfg->smoother > 1 ||
         cfg->dtype < 0 || cfg->dtype > 2 || cfg->restrict_mode < 0 || cfg->restrict_mode > 1 || cfg->bottom < 0 || cfg->bottom > 1 || cfg->arith < 0 || cfg->arith > 1 ||
@@ -2302,6 +2382,10 @@ int mgx_plan_create(const mgx_config* cfg, int n_slabs, int g, int fold, int dee
 {
     if (!cfg || !out) { g_plan_error = "null argument"; return MGX_ERR_INVALID; }
     *out = nullptr;
+    if (cfg->smoother == MGX_SMOOTHER_CHEBYSHEV) {
+        g_plan_error = "MGX_SMOOTHER_CHEBYSHEV: the slab plan runs the constant stencil (Jacobi or red-black GS) only";
+        return MGX_ERR_INVALID;
+    }
     const int cut = dist_cut_level(*cfg, n_slabs);
     mgx_dist_planner* h = new (std::nothrow) mgx_dist_planner();
     if (!h) return MGX_ERR_ALLOC;

@@ -4,8 +4,12 @@
 //   -DMGX_INST_KIND=1  launch_cycle<T, PRE, POST, SM, AR> for the (PRE, POST) pair number MGX_INST_PP
 //   -DMGX_INST_KIND=2  launch_fused<T, SM, AR>
 //   -DMGX_INST_KIND=3  launch_tile_pass<T, SM, AR>  (all six (PRE, POST) pairs of k_tile_smooth and k_tile_wide)
+//   -DMGX_INST_KIND=4  launch_cheby<T>, launch_lambda_max<T>  (mgx_cheby.hpp: k_cheby_var, k_cheby_var9, k_lambda_partials)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
+#if MGX_INST_KIND == 4
+#include "mgx_cheby.hpp"
+#endif
 
 namespace mgx {
 using T_ = MGX_INST_T;
@@ -26,7 +30,10 @@ template int launch_cycle<T_, PP_, MGX_INST_SM, MGX_INST_AR>(int, const T_*, con
 template bool launch_fused<T_, MGX_INST_SM, MGX_INST_AR>(int, const T_*, const T_*, T_*, int, long, int, int, T_, T_, int, int, int, int, hipStream_t, int, int);
 #elif MGX_INST_KIND == 3
 template int launch_tile_pass<T_, MGX_INST_SM, MGX_INST_AR>(const T_*, const T_*, T_*, const FoldArgs&, int, long, T_, T_, int, int, bool, int, hipStream_t);
+#elif MGX_INST_KIND == 4
+template void launch_cheby<T_>(const ChebyLevel<T_>&, const T_*, const T_*, T_*, T_*, bool, T_, T_, T_, T_, hipStream_t);
+template void launch_lambda_max<T_>(const ChebyLevel<T_>&, double*, long, double*, hipStream_t);
 #else
-#error "MGX_INST_KIND must be 1, 2 or 3"
+#error "MGX_INST_KIND must be 1, 2, 3 or 4"
 #endif
 } // namespace mgx

@@ -11,7 +11,14 @@ Wall times around calls that end in a device synchronise (40 sweeps or 20 residu
 --transfer: instead, the tables of profiles/opdep_kernel_trace_summary.md - BILINEAR against OPERATOR prolongation
 (mgx_build_galerkin_transfer, csrc/mgx_opdep.hpp): mgx_restrict / mgx_prolong_add on the finest level and the one below,
 the build, and time and cycles to 1e-8 (constant right-hand side; 2047^2: the random one of seed 3).
---transfer --trace-only: the builds and five calls of each transfer only, for a rocprofv3 --kernel-trace --stats run."""
+--transfer --trace-only: the builds and five calls of each transfer only, for a rocprofv3 --kernel-trace --stats run.
+--smoother {jacobi,chebyshev}: instead, the tables of profiles/cheby_kernel_trace_summary.md.  chebyshev: k_cheby_var /
+k_cheby_var9 (csrc/mgx_cheby.hpp, 10 / 14 sizeof(T) per point and step, one word less on a block's first step) next to
+k_jacobi_var / k_jacobi_var9 at 4096^2 in the same process, then cycles and time to 1e-8 of mgx_solve and mgx_solve_pcg
+with the Chebyshev V(2,2) and V(2,1) cycles (V(2,1): the degrees whose bytes per cycle, 41 words per finest point, are
+closest to Jacobi V(2,2)'s 48; V(2,2) moves 56) for both transfers, median of 5.  jacobi: the same solves with the Jacobi
+V(2,2) cycle.  --smoother chebyshev --trace-only: five blocks of degree 4 per level and type only, for a
+rocprofv3 --kernel-trace --stats run."""
 import os
 import statistics
 import sys
@@ -181,8 +188,87 @@ def transfers():
                 print(f"| {n}^2 contrast {contrast:g} | {tname} | {cells[0]} | {cells[1]} |", flush=True)
 
 
+def smoother_kernels():
+    n = (1 << LK) - 1
+    x = np.linspace(0.0, 1.0, (1 << LF) + 1)
+    a = 1.0 + 0.8 * np.sin(3 * np.pi * x)[None, :] * np.cos(2 * np.pi * x)[:, None]
+    rng = np.random.default_rng(0)
+    u, b = rng.uniform(-1, 1, (n, n)), rng.uniform(-1, 1, (n, n))
+    if not TRACE_ONLY:
+        print("| kernel | grid | dtype | ms per step | bytes per point | achieved GB/s | fraction of the 8 TB/s HBM peak |")
+        print("|---|---|---|---|---|---|---|")
+    rate = {}
+    steps = 40
+    for dtype, name, es in ((pkg.DTYPE_F64, "f64", 8), (pkg.DTYPE_F32, "f32", 4)):
+        for op, tag, finest in ((pkg.OPERATOR_STENCIL5, "var", LK), (pkg.OP_GALERKIN, "var9", LF)):
+            for sm, kname, words in ((pkg.SMOOTHER_JACOBI, "k_jacobi_", 8 if tag == "var" else 12),
+                                     (pkg.SMOOTHER_CHEBYSHEV, "k_cheby_", 10 if tag == "var" else 14)):
+                with pkg.Multigrid(finest_level=finest, coarsest_level=5, mu1=2, mu2=2, schedule=pkg.SCHEDULE_V, op=op, dtype=dtype, omega=0.8,
+                                   smoother=sm) as mg:
+                    if op == pkg.OP_GALERKIN:
+                        mg.set_coefficient(a)
+                        mg.build_galerkin()
+                    else:
+                        mg.set_coefficient(a[::2, ::2])
+                    mg.set_level(LK, pkg.VEC_U, u)
+                    mg.set_level(LK, pkg.VEC_B, b)
+                    mg.smooth(LK, 4)
+                    if TRACE_ONLY:
+                        for _ in range(5):
+                            mg.smooth(LK, 4)
+                        continue
+                    ms = wall(lambda: mg.smooth(LK, steps), reps=5) / steps
+                    # a Chebyshev block's first step does not read d: one word less in `steps` steps
+                    per_step = words - (1.0 / steps if sm == pkg.SMOOTHER_CHEBYSHEV else 0.0)
+                    gbs = per_step * es * n * n / (ms * 1e-3) / 1e9
+                    rate[(kname, tag, name)] = gbs
+                    print(f"| {kname}{tag}<{name}> | {1 << LK}^2 | {name} | {ms:.4f} | {per_step * es:.1f} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
+    if TRACE_ONLY:
+        return
+    print()
+    for name in ("f64", "f32"):
+        for tag in ("var", "var9"):
+            r = rate[("k_cheby_", tag, name)] / rate[("k_jacobi_", tag, name)]
+            print(f"k_cheby_{tag} / k_jacobi_{tag} bytes/s, {name}: {r:.3f} (accepted: >= 0.9{'' if r >= 0.9 else ': NOT MET'})")
+
+
+def smoother_solves(which):
+    sm = pkg.SMOOTHER_CHEBYSHEV if which == "chebyshev" else pkg.SMOOTHER_JACOBI
+    print(f"\n| problem, levels L..5, f64, smoother {which} | cycle | transfer | mgx_solve | mgx_solve_pcg |\n|---|---|---|---|---|")
+    for L, contrast in ((9, 10.0), (9, 100.0), (9, 1000.0)) if QUICK else ((11, 10.0), (9, 100.0), (9, 1000.0)):
+        n = (1 << L) - 1
+        b = np.random.default_rng(3).standard_normal((n, n)) if L == 11 else None
+        for mu1, mu2 in ((2, 2), (2, 1)) if which == "chebyshev" else ((2, 2),):
+            with pkg.Multigrid(finest_level=L, coarsest_level=5, mu1=mu1, mu2=mu2, schedule=0, op=pkg.OP_GALERKIN, smoother=sm) as mg:
+                mg.set_coefficient(contrast_coefficient(L, contrast))
+                for transfer, tname in ((pkg.TRANSFER_BILINEAR, "BILINEAR"), (pkg.TRANSFER_OPERATOR, "OPERATOR")):
+                    mg.build_galerkin(transfer)
+                    if b is None:
+                        mg.fill_rhs(0)
+                    else:
+                        mg.set_rhs(b)
+                    cells = []
+                    for f in (lambda: mg.solve(tol=1e-8, max_cycles=150), lambda: mg.solve_pcg(tol=1e-8, max_iters=200)):
+                        ts = []
+                        for rep in range(6):                    # the first run captures the graphs: not timed
+                            mg.set_guess(np.zeros((n, n)))
+                            st, hist = f()
+                            if rep:
+                                ts.append(st.seconds * 1e3)
+                        cells.append(f"{st.cycles} {'it' if len(cells) else 'cycles'}, {statistics.median(ts):.2f} ms (min {min(ts):.2f}, max {max(ts):.2f}), converged {st.converged}")
+                    print(f"| {n}^2 contrast {contrast:g} | V({mu1},{mu2}) | {tname} | {cells[0]} | {cells[1]} |", flush=True)
+
+
 if __name__ == "__main__":
-    if "--transfer" in sys.argv:
+    if "--smoother" in sys.argv:
+        which = sys.argv[sys.argv.index("--smoother") + 1]
+        if which not in ("jacobi", "chebyshev"):
+            sys.exit("--smoother jacobi or --smoother chebyshev")
+        if which == "chebyshev":
+            smoother_kernels()
+        if not TRACE_ONLY:
+            smoother_solves(which)
+    elif "--transfer" in sys.argv:
         transfers()
     else:
         r = kernels()
