@@ -52,14 +52,11 @@ struct Level {
     size_t bytes = 0;
     bool f64 = true;
     void *u = nullptr, *b = nullptr, *tmp = nullptr, *r = nullptr;
-    // MGX_OPERATOR_STENCIL5 (mgx_var.hpp): A = (c, n, s, w, e)  [ProblemVar::A_sp_dict, MF:19] and its Jacobi
-    // splitting (D_inv, R_n, R_s, R_w, R_e)  [A_jacobi_sp_dict, MF:20, 28-32]
-    void* coef[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    void* jac[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    // MGX_OPERATOR_GALERKIN (mgx_galerkin.hpp), levels below the finest: the corner grids (nw, ne, sw, se) of the
-    // nine-point operator R A P and of its R_omega
-    void* corner[4] = {nullptr, nullptr, nullptr, nullptr};
-    void* jcorner[4] = {nullptr, nullptr, nullptr, nullptr};
+    // MGX_OPERATOR_STENCIL5 / GALERKIN (mgx_var.hpp), in the slot order c, n, s, w, e, nw, ne, sw, se: the operator A
+    // [ProblemVar::A_sp_dict, MF:19] and its Jacobi splitting J = (D_inv, R_n, R_s, ..., R_se)  [A_jacobi_sp_dict, MF:20,
+    // 28-32].  The corner slots 5..8 exist on nine-point levels only (`nine`: R A P, below the finest GALERKIN level)
+    void* A[9] = {};
+    void* J[9] = {};
     // MGX_TRANSFER_OPERATOR (mgx_opdep.hpp): the eight weight grids (n, s, w, e, nw, ne, sw, se) of P between level
     // L + 1 and this level, allocated by the first OPERATOR build
     void* wt[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -250,10 +247,10 @@ int alloc_level(mgx_solver* s, Level& l, int level, bool f64)
 
 void free_level(Level& l)
 {
-    for (void** p : {&l.u, &l.b, &l.tmp, &l.r, &l.coef[0], &l.coef[1], &l.coef[2], &l.coef[3], &l.coef[4],
-                     &l.jac[0], &l.jac[1], &l.jac[2], &l.jac[3], &l.jac[4], &l.corner[0], &l.corner[1], &l.corner[2], &l.corner[3],
-                     &l.jcorner[0], &l.jcorner[1], &l.jcorner[2], &l.jcorner[3], &l.wt[0], &l.wt[1], &l.wt[2], &l.wt[3], &l.wt[4], &l.wt[5],
-                     &l.wt[6], &l.wt[7], &l.cheb}) {
+    std::vector<void**> all = {&l.u, &l.b, &l.tmp, &l.r, &l.cheb};
+    for (int q = 0; q < 9; ++q) { all.push_back(&l.A[q]); all.push_back(&l.J[q]); }
+    for (void*& w : l.wt) all.push_back(&w);
+    for (void** p : all) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -311,19 +308,17 @@ BlockReq level_req(const mgx_solver* s, const Level& l, int mu, bool pre, int po
 // ---- general per-level operators (cfg.op = MGX_OPERATOR_STENCIL5; kernels in mgx_var.hpp) ---------------
 int var_alloc_level(mgx_solver* s, Level& l)
 {
-    for (void** p : {&l.coef[0], &l.coef[1], &l.coef[2], &l.coef[3], &l.coef[4], &l.jac[0], &l.jac[1], &l.jac[2], &l.jac[3], &l.jac[4]}) {
-        if (hipMalloc(p, l.bytes) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the operator's coefficient arrays");
-        HIPCHK(s, hipMemsetAsync(*p, 0, l.bytes, s->stream));
-    }
-    if (!l.nine) return MGX_OK;
-    for (void** p : {&l.corner[0], &l.corner[1], &l.corner[2], &l.corner[3], &l.jcorner[0], &l.jcorner[1], &l.jcorner[2], &l.jcorner[3]}) {
-        if (hipMalloc(p, l.bytes) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the nine-point operator's corner arrays");
-        HIPCHK(s, hipMemsetAsync(*p, 0, l.bytes, s->stream));
-    }
+    for (int q = 0; q < (l.nine ? 9 : 5); ++q)
+        for (void** p : {&l.A[q], &l.J[q]}) {
+            if (hipMalloc(p, l.bytes) != hipSuccess)
+                return s->fail(MGX_ERR_ALLOC, q < 5 ? "hipMalloc failed for the operator's coefficient arrays"
+                                                    : "hipMalloc failed for the nine-point operator's corner arrays");
+            HIPCHK(s, hipMemsetAsync(*p, 0, l.bytes, s->stream));
+        }
     return MGX_OK;
 }
 
-// dense inverse of the NN x NN matrix in var_M (k_var_dense_fill / k_var_dense_fill9 wrote it) into var_inv
+// dense inverse of the NN x NN matrix in var_M (k_var_dense_fill wrote it) into var_inv
 void gj_invert(mgx_solver* s, int NN)
 {
     for (int k = 0; k < NN; ++k) {
@@ -340,13 +335,15 @@ void drop_graphs(mgx_solver* s)
 
 template <typename T> Op9<T> op9_of(const Level& l)
 {
-    return Op9<T>{{(const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3], (const T*)l.coef[4],
-                   (const T*)l.corner[0], (const T*)l.corner[1], (const T*)l.corner[2], (const T*)l.corner[3]}};
+    Op9<T> o;
+    for (int q = 0; q < 9; ++q) o.a[q] = (const T*)l.A[q];
+    return o;
 }
-template <typename T> Op9<T> jac9_of(const Level& l)      // slot 0 (the diagonal of R_omega) is a scalar: unused
+template <typename T> Op9<T> jac9_of(const Level& l)      // slot 0 is D_inv (the diagonal of R_omega is a scalar)
 {
-    return Op9<T>{{nullptr, (const T*)l.jac[1], (const T*)l.jac[2], (const T*)l.jac[3], (const T*)l.jac[4],
-                   (const T*)l.jcorner[0], (const T*)l.jcorner[1], (const T*)l.jcorner[2], (const T*)l.jcorner[3]}};
+    Op9<T> o;
+    for (int q = 0; q < 9; ++q) o.a[q] = (const T*)l.J[q];
+    return o;
 }
 template <typename T> Op9Out<T> out9(const Op9<T>& o)
 {
@@ -355,17 +352,17 @@ template <typename T> Op9Out<T> out9(const Op9<T>& o)
     return w;
 }
 
-template <typename T> ChebyLevel<T> cheby_level(const Level& l)
+template <typename T> VarLevel<T> var_level(const Level& l)
 {
-    return ChebyLevel<T>{op9_of<T>(l), jac9_of<T>(l), (const T*)l.jac[0], l.nine, l.N, l.rows, l.pitch};
+    return VarLevel<T>{op9_of<T>(l), jac9_of<T>(l), (const T*)l.J[0], l.nine, l.N, l.rows, l.pitch};
 }
 
 // g_l of the operator and splitting just built on level l (k_lambda_partials, k_reduce_max): one 8-byte copy to the
 // host per level, at set-up only
 int lambda_update(mgx_solver* s, Level& l)
 {
-    if (l.f64) launch_lambda_max<double>(cheby_level<double>(l), s->partial, s->partial_cap, s->sum_dev, s->stream);
-    else launch_lambda_max<float>(cheby_level<float>(l), s->partial, s->partial_cap, s->sum_dev, s->stream);
+    if (l.f64) launch_lambda_max<double>(var_level<double>(l), s->partial, s->partial_cap, s->sum_dev, s->stream);
+    else launch_lambda_max<float>(var_level<float>(l), s->partial, s->partial_cap, s->sum_dev, s->stream);
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipMemcpyAsync(s->sum_host, s->sum_dev, sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(s, hipStreamSynchronize(s->stream));
@@ -373,21 +370,35 @@ int lambda_update(mgx_solver* s, Level& l)
     return MGX_OK;
 }
 
-// the level's operator has been written into l.coef[]: build {D_inv, R_omega} (MF:28-32) and, on the coarsest
-// level with an exact bottom solve, the dense inverse (MF:63-72)
+// {D_inv, R_omega} of the operator in l.A[] (MF:28-32)
+template <typename T>
+void build_splitting(mgx_solver* s, const Level& l)
+{
+    const dim3 blk(256), grd((l.N + 1 + 255) / 256, l.N + 1);
+    with_point_count(l.nine, [&](auto nq) {
+        hipLaunchKernelGGL((k_var_build_jacobi<T, decltype(nq)::value>), grd, blk, 0, s->stream, op9_of<T>(l), out9(jac9_of<T>(l)), l.N, l.pitch,
+                           (T)s->cfg.omega);
+    });
+}
+// the dense inverse of the coarsest operator, for the exact bottom solve (MF:63-72)
+template <typename T>
+void build_bottom_inverse(mgx_solver* s, const Level& l)
+{
+    const int n = l.N - 1, NN = n * n;
+    with_point_count(l.nine, [&](auto nq) {
+        hipLaunchKernelGGL((k_var_dense_fill<T, decltype(nq)::value>), dim3((NN + 255) / 256, NN), dim3(256), 0, s->stream, s->var_M, s->var_inv,
+                           op9_of<T>(l), n, l.pitch);
+    });
+    gj_invert(s, NN);
+}
+
+// the level's operator has been written into l.A[]: build its splitting and, on the coarsest level with an exact
+// bottom solve, the dense inverse
 template <typename T>
 int var_build_t(mgx_solver* s, Level& l)
 {
-    const dim3 blk(256), grd((l.N + 1 + 255) / 256, l.N + 1);
-    hipLaunchKernelGGL((k_var_build_jacobi<T>), grd, blk, 0, s->stream, (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2],
-                       (const T*)l.coef[3], (const T*)l.coef[4], (T*)l.jac[0], (T*)l.jac[1], (T*)l.jac[2], (T*)l.jac[3], (T*)l.jac[4],
-                       l.N, l.pitch, (T)s->cfg.omega);
-    if (l.L == s->cfg.coarsest_level && s->cfg.bottom == MGX_BOTTOM_EXACT) {
-        const int n = l.N - 1, NN = n * n;
-        hipLaunchKernelGGL((k_var_dense_fill<T>), dim3((NN + 255) / 256, NN), dim3(256), 0, s->stream, s->var_M, s->var_inv,
-                           (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3], (const T*)l.coef[4], n, l.pitch);
-        gj_invert(s, NN);
-    }
+    build_splitting<T>(s, l);
+    if (l.L == s->cfg.coarsest_level && s->cfg.bottom == MGX_BOTTOM_EXACT) build_bottom_inverse<T>(s, l);
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipStreamSynchronize(s->stream));
     if (int rc = lambda_update(s, l)) return rc;
@@ -436,42 +447,20 @@ int galerkin_build_t(mgx_solver* s, int transfer)
         const Level& f = s->lv[lv];
         const Level& c = s->lv[lv - 1];
         const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
-        if (transfer == MGX_TRANSFER_OPERATOR) {
-            if (f.nine) {
-                hipLaunchKernelGGL((k_opdep_weights<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), wt8_out<T>(c), c.N,
-                                   f.pitch, c.pitch, g.strips);
-                hipLaunchKernelGGL((k_galerkin_rap_opdep<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), wt8_of<T>(c),
-                                   out9(op9_of<T>(c)), c.N, f.pitch, c.pitch, g.strips, rscale);
-            } else {
-                hipLaunchKernelGGL((k_opdep_weights<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), wt8_out<T>(c), c.N,
-                                   f.pitch, c.pitch, g.strips);
-                hipLaunchKernelGGL((k_galerkin_rap_opdep<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), wt8_of<T>(c),
-                                   out9(op9_of<T>(c)), c.N, f.pitch, c.pitch, g.strips, rscale);
+        const dim3 grd(g.blocks), blk(kBlock);
+        with_point_count(f.nine, [&](auto nq) {
+            constexpr bool CORNERS = decltype(nq)::value == 9;
+            if (transfer == MGX_TRANSFER_OPERATOR) {
+                hipLaunchKernelGGL((k_opdep_weights<T, CORNERS>), grd, blk, 0, s->stream, op9_of<T>(f), wt8_out<T>(c), c.N, f.pitch, c.pitch, g.strips);
+                hipLaunchKernelGGL((k_galerkin_rap_opdep<T, CORNERS>), grd, blk, 0, s->stream, op9_of<T>(f), wt8_of<T>(c), out9(op9_of<T>(c)), c.N,
+                                   f.pitch, c.pitch, g.strips, rscale);
             }
-        }
-        else if (f.nine) hipLaunchKernelGGL((k_galerkin_rap<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), out9(op9_of<T>(c)),
-                                       c.N, f.pitch, c.pitch, g.strips, rscale);
-        else hipLaunchKernelGGL((k_galerkin_rap<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, op9_of<T>(f), out9(op9_of<T>(c)),
-                                c.N, f.pitch, c.pitch, g.strips, rscale);
+            else hipLaunchKernelGGL((k_galerkin_rap<T, CORNERS>), grd, blk, 0, s->stream, op9_of<T>(f), out9(op9_of<T>(c)), c.N, f.pitch, c.pitch,
+                                    g.strips, rscale);
+        });
     }
-    for (int lv = lo; lv <= hi; ++lv) {
-        const Level& l = s->lv[lv];
-        const dim3 blk(256), grd((l.N + 1 + 255) / 256, l.N + 1);
-        if (l.nine) hipLaunchKernelGGL((k_var_build_jacobi9<T>), grd, blk, 0, s->stream, op9_of<T>(l), (T*)l.jac[0], out9(jac9_of<T>(l)),
-                                       l.N, l.pitch, (T)s->cfg.omega);
-        else hipLaunchKernelGGL((k_var_build_jacobi<T>), grd, blk, 0, s->stream, (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2],
-                                (const T*)l.coef[3], (const T*)l.coef[4], (T*)l.jac[0], (T*)l.jac[1], (T*)l.jac[2], (T*)l.jac[3], (T*)l.jac[4],
-                                l.N, l.pitch, (T)s->cfg.omega);
-    }
-    if (s->cfg.bottom == MGX_BOTTOM_EXACT) {
-        const Level& l = s->lv[lo];
-        const int n = l.N - 1, NN = n * n;
-        if (l.nine) hipLaunchKernelGGL((k_var_dense_fill9<T>), dim3((NN + 255) / 256, NN), dim3(256), 0, s->stream, s->var_M, s->var_inv,
-                                       op9_of<T>(l), n, l.pitch);
-        else hipLaunchKernelGGL((k_var_dense_fill<T>), dim3((NN + 255) / 256, NN), dim3(256), 0, s->stream, s->var_M, s->var_inv,
-                                (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3], (const T*)l.coef[4], n, l.pitch);
-        gj_invert(s, NN);
-    }
+    for (int lv = lo; lv <= hi; ++lv) build_splitting<T>(s, s->lv[lv]);
+    if (s->cfg.bottom == MGX_BOTTOM_EXACT) build_bottom_inverse<T>(s, s->lv[lo]);
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipStreamSynchronize(s->stream));
     for (int lv = lo; lv <= hi; ++lv)
@@ -505,9 +494,6 @@ int var_ready(mgx_solver* s, int lo, int hi)
     return MGX_OK;
 }
 
-// f(double{}) or f(float{}): the working type as a tag
-template <typename F> void with_float_type(bool f64, F&& f) { if (f64) f(double{}); else f(float{}); }
-
 // MF:75-96: mu sweeps, one launch each, u <-> tmp
 template <typename T>
 void smooth_var_t(mgx_solver* s, Level& l, int mu)
@@ -515,12 +501,12 @@ void smooth_var_t(mgx_solver* s, Level& l, int mu)
     const T om = (T)s->cfg.omega;
     const T rc = (T)(1.0 - (double)om);
     const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
+    const VarLevel<T> v = var_level<T>(l);
     for (int i = 0; i < mu; ++i) {
-        if (l.nine) hipLaunchKernelGGL((k_jacobi_var9<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.u, (const T*)l.b, (T*)l.tmp,
-                                       (const T*)l.jac[0], jac9_of<T>(l), l.N, l.pitch, 1, l.N, g.strips, rc, om, l.rows);
-        else hipLaunchKernelGGL((k_jacobi_var<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.u, (const T*)l.b, (T*)l.tmp,
-                           (const T*)l.jac[0], (const T*)l.jac[1], (const T*)l.jac[2], (const T*)l.jac[3], (const T*)l.jac[4],
-                           l.N, l.pitch, 1, l.N, g.strips, rc, om, l.rows);
+        with_point_count(v.nine, [&](auto nq) {
+            hipLaunchKernelGGL((k_jacobi_var<T, decltype(nq)::value>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.u, (const T*)l.b,
+                               (T*)l.tmp, v.dinv, v.r, v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
+        });
         std::swap(l.u, l.tmp);
     }
     s->last_smooth_launches = mu;
@@ -534,7 +520,7 @@ void smooth_cheby_t(mgx_solver* s, Level& l, int mu)
     const T om = (T)s->cfg.omega;
     const T rc = (T)(1.0 - (double)om);
     const std::vector<ChebyStep> st = cheby_scalars(s->cfg.omega, l.lambda_g, mu);
-    const ChebyLevel<T> cl = cheby_level<T>(l);
+    const VarLevel<T> cl = var_level<T>(l);
     for (int i = 0; i < mu; ++i) {
         launch_cheby<T>(cl, (const T*)l.u, (const T*)l.b, (T*)l.tmp, (T*)l.cheb, i == 0, rc, om, (T)st[i].a, (T)st[i].c, s->stream);
         std::swap(l.u, l.tmp);
@@ -555,11 +541,11 @@ template <typename T, int MODE>
 void residual_var_t(mgx_solver* s, const Level& l, const void* u, const void* b, void* out)
 {
     const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
-    if (l.nine) hipLaunchKernelGGL((k_residual_var9<T, MODE>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)u, (const T*)b, (T*)out,
-                                   s->partial, op9_of<T>(l), l.N, l.pitch, 1, l.N, g.strips, l.rows);
-    else hipLaunchKernelGGL((k_residual_var<T, MODE>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)u, (const T*)b, (T*)out,
-                       s->partial, (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2], (const T*)l.coef[3],
-                       (const T*)l.coef[4], l.N, l.pitch, 1, l.N, g.strips, l.rows);
+    const VarLevel<T> v = var_level<T>(l);
+    with_point_count(v.nine, [&](auto nq) {
+        hipLaunchKernelGGL((k_residual_var<T, decltype(nq)::value, MODE>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)u, (const T*)b,
+                           (T*)out, s->partial, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
+    });
     if (MODE == 1) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, s->partial, g.blocks, s->sum_dev);
 }
 
@@ -743,10 +729,10 @@ void restrict_level(mgx_solver* s, int level, bool fused, bool zero_guess)
             const dim3 grd(g.blocks), blk(kBlock);
             if (!fused) hipLaunchKernelGGL((k_restrict_opdep<T, 0>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b, op9_of<T>(f), wt8_of<T>(c),
                                            (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
-            else if (f.nine) hipLaunchKernelGGL((k_restrict_opdep<T, 2>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b, op9_of<T>(f),
-                                                wt8_of<T>(c), (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
-            else hipLaunchKernelGGL((k_restrict_opdep<T, 1>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b, op9_of<T>(f), wt8_of<T>(c),
-                                    (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
+            else with_point_count(f.nine, [&](auto nq) {
+                hipLaunchKernelGGL((k_restrict_opdep<T, decltype(nq)::value == 9 ? 2 : 1>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b,
+                                   op9_of<T>(f), wt8_of<T>(c), (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
+            });
         });
         return;
     }
@@ -1191,12 +1177,10 @@ void pcg_step(mgx_solver* s, const Level& l, const Launch& g, bool first_it, int
     T* pn = (T*)s->pcg_p[pp ^ 1];
     if (s->var)
         hipLaunchKernelGGL((k_pcg_direction<T, 1>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, p, pn, (T*)s->pcg_q, s->pcg_sc,
-                           first_it ? 1 : 0, s->pcg_part, (const T*)l.coef[0], (const T*)l.coef[1], (const T*)l.coef[2],
-                           (const T*)l.coef[3], (const T*)l.coef[4], l.N, l.pitch, g.R, g.strips, g.chunks);
+                           first_it ? 1 : 0, s->pcg_part, op9_of<T>(l), l.N, l.pitch, g.R, g.strips, g.chunks);
     else
         hipLaunchKernelGGL((k_pcg_direction<T, 0>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, p, pn, (T*)s->pcg_q, s->pcg_sc,
-                           first_it ? 1 : 0, s->pcg_part, (const T*)nullptr, (const T*)nullptr, (const T*)nullptr,
-                           (const T*)nullptr, (const T*)nullptr, l.N, l.pitch, g.R, g.strips, g.chunks);
+                           first_it ? 1 : 0, s->pcg_part, Op9<T>{}, l.N, l.pitch, g.R, g.strips, g.chunks);
     pcg_reduce(s, g.blocks, kPcgAlphaMode);
     pp ^= 1;
     hipLaunchKernelGGL((k_pcg_update<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)s->pcg_x, (const T*)pn, (T*)l.b,
@@ -1623,7 +1607,7 @@ int mgx_set_stencil(mgx_handle s, int level, const void* c, const void* n, const
     Level& l = s->lv[level];
     const void* src[5] = {c, n, so, w, e};
     for (int q = 0; q < 5; ++q) {
-        int rc = copy_in(s, l, l.coef[q], src[q], count);
+        int rc = copy_in(s, l, l.A[q], src[q], count);
         if (rc) return rc;
     }
     if (s->galerkin) { galerkin_invalidate(s); return MGX_OK; }
@@ -1645,10 +1629,10 @@ int mgx_set_coefficient(mgx_handle s, const double* a_nodes, size_t count)
         Level& l = s->lv[lv];
         const dim3 blk(256), grd((l.N + 1 + 255) / 256, l.N + 1);
         const int q = 1 << (Lf - lv);
-        if (l.f64) hipLaunchKernelGGL((k_var_from_nodes<double>), grd, blk, 0, s->stream, dev, Nf, q, (double*)l.coef[0], (double*)l.coef[1],
-                                      (double*)l.coef[2], (double*)l.coef[3], (double*)l.coef[4], l.N, l.pitch);
-        else hipLaunchKernelGGL((k_var_from_nodes<float>), grd, blk, 0, s->stream, dev, Nf, q, (float*)l.coef[0], (float*)l.coef[1],
-                                (float*)l.coef[2], (float*)l.coef[3], (float*)l.coef[4], l.N, l.pitch);
+        with_float_type(l.f64, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL((k_var_from_nodes<T>), grd, blk, 0, s->stream, dev, Nf, q, out9(op9_of<T>(l)), l.N, l.pitch);
+        });
         if (!s->galerkin) rc = var_build(s, l);
     }
     if (hipStreamSynchronize(s->stream) != hipSuccess && rc == MGX_OK) rc = s->fail(MGX_ERR_HIP, "sampling the nodal coefficient failed");
@@ -1667,7 +1651,7 @@ int mgx_get_stencil(mgx_handle s, int level, int which, void* dst, size_t count)
     if (l.nine) return s->fail(MGX_ERR_STATE, "nine-point operator (coarse level of a GALERKIN handle): use mgx_get_stencil9");
     if (!l.stencil_set) return s->fail(MGX_ERR_STATE, "operator of this level not set");
     if (s->galerkin && which >= 5 && !s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
-    return copy_out(s, l, which < 5 ? l.coef[which] : l.jac[which - 5], dst, count);
+    return copy_out(s, l, which < 5 ? l.A[which] : l.J[which - 5], dst, count);
 }
 
 int mgx_build_galerkin(mgx_handle s)
@@ -1737,7 +1721,7 @@ int mgx_get_stencil9(mgx_handle s, int level, int which, void* dst, size_t count
     if (!s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
     Level& l = s->lv[level];
     // 0..8: c, n, s, w, e, nw, ne, sw, se;  9: D_inv;  10..17: R_n, R_s, R_w, R_e, R_nw, R_ne, R_sw, R_se
-    const void* src = which < 5 ? l.coef[which] : which < 9 ? l.corner[which - 5] : which < 14 ? l.jac[which - 9] : l.jcorner[which - 14];
+    const void* src = which < 9 ? l.A[which] : l.J[which - 9];
     if (!src) {                                               // corners of the five-point finest level
         const size_t n = (size_t)l.N - 1;
         if (count != n * n) return s->fail(MGX_ERR_INVALID, "vector length must be n*n with n = 2^level - 1");

@@ -2,7 +2,7 @@
 // MGX_SMOOTHER_CHEBYSHEV with op = MGX_OPERATOR_STENCIL5 / MGX_OPERATOR_GALERKIN) and the eigenvalue bound it needs.
 //
 // THE ITERATION (tests/cheby_ref.py states it in numpy, operation by operation).  J(v) = R_omega v + omega (D_inv b) is
-// the sweep of k_jacobi_var / k_jacobi_var9, computed exactly as there; z = J(v) - v = omega D^-1 (b - A v).  With
+// the sweep of k_jacobi_var (mgx_var.hpp: stencil_sum, jacobi_value), computed exactly as there; z = J(v) - v = omega D^-1 (b - A v).  With
 //     lmax = omega g_l,  lmin = lmax / 4,  theta = (lmax + lmin) / 2,  delta = (lmax - lmin) / 2,  sigma = theta / delta
 // a block of degree mu is, from d undefined,
 //     step 0:       d = c_0 z                      c_0 = 1 / theta,                       rho_0 = 1 / sigma
@@ -25,7 +25,7 @@
 // k_reduce_partials) the level's.
 #pragma once
 
-#include "mgx_galerkin.hpp"
+#include "mgx_var.hpp"
 
 #include <vector>
 
@@ -56,8 +56,7 @@ __device__ __forceinline__ void cheby_update(const Lanes<T>& p1, const Lanes<T>&
     constexpr int W = VecOf<T>::W;
 #pragma unroll
     for (int k = 0; k < W; ++k) {
-        const T j = p1.a[k] + omega * (dinv.a[k] * b.a[k]);
-        const T z = j - cur.a[k];
+        const T z = jacobi_value(p1.a[k], omega, dinv.a[k], b.a[k]) - cur.a[k];
         T d;
         if (FIRST) d = cc * z;
         else {
@@ -70,81 +69,29 @@ __device__ __forceinline__ void cheby_update(const Lanes<T>& p1, const Lanes<T>&
     }
 }
 
-// one Chebyshev step on a five-point level; rows [row_lo, row_hi).  r: the off-diagonals of R_omega in slots 1..4
-template <typename T, int FIRST>
+// one Chebyshev step on a level; rows [row_lo, row_hi).  r: the off-diagonals of R_omega in slots 1 .. NQ - 1
+template <typename T, int NQ, int FIRST>
 __global__ void __launch_bounds__(kBlock)
 k_cheby_var(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ vout, T* __restrict__ dir, const T* __restrict__ dinv,
             Op9<T> r, int N, long pitch, int row_lo, int row_hi, int strips, T rc, T omega, T ca, T cc, int rows_alloc)
 {
-    using V = typename VecOf<T>::type;
-    constexpr int W = VecOf<T>::W;
-    const Tile t = wave_tile(strips, row_hi - row_lo);
+    const RowTile<T> t = load_rows<T>(vin, N, pitch, row_lo, row_hi, strips, rows_alloc);
     if (!t.active) return;
-    const Cols c = lane_cols<W>(t.strip, N, pitch);
-    const int row = row_lo + t.chunk;
-    const long at = c.col + (long)row * pitch;
-    const bool in = c.ld && row >= 0 && row < rows_alloc;
-    const V up = vload<V>(vin + at - pitch, c.ld && row >= 1 && row <= rows_alloc);
-    const V cur = vload<V>(vin + at, in);
-    const V dn = vload<V>(vin + at + pitch, c.ld && row >= -1 && row + 1 < rows_alloc);
-    const V bb = vload<V>(rhs + at, in);
-    const V dv = vload<V>(dinv + at, in);
-    const Lanes<T> n = to_lanes(vload<V>(r.a[1] + at, in)), s = to_lanes(vload<V>(r.a[2] + at, in));
-    const Lanes<T> w = to_lanes(vload<V>(r.a[3] + at, in)), e = to_lanes(vload<V>(r.a[4] + at, in));
-    Lanes<T> dold = to_lanes(cur);
-    if (!FIRST) dold = to_lanes(vload<V>(dir + at, in));
-    const T left = from_left(last(cur)), right = from_right(first(cur));
-    const Lanes<T> p1 = stencil5<T>(to_lanes(up), to_lanes(cur), to_lanes(dn), left, right, n, w, [&](int) { return rc; }, e, s);
+    const Lanes<T> b = load_lanes(rhs + t.at, t.in), d = load_lanes(dinv + t.at, t.in);
+    Lanes<T> k[9];
+    load_coefs<NQ, 1>(r, t.at, t.in, k);
+    Lanes<T> dold = to_lanes(t.cur);
+    if (!FIRST) dold = load_lanes(dir + t.at, t.in);
+    const Lanes<T> p1 = stencil_sum<NQ>(rows_of<NQ>(t), k, [&](int) { return rc; });
     Lanes<T> dnew, vnew;
-    cheby_update<T, FIRST>(p1, to_lanes(cur), to_lanes(bb), to_lanes(dv), dold, omega, ca, cc, dnew, vnew);
-    V od = from_lanes(dnew), ov = from_lanes(vnew);
-    mask_cols(od, c.col, N);
-    mask_cols(ov, c.col, N);
-    vstore<V>(dir + at, od, c.st && in);
-    vstore<V>(vout + at, ov, c.st && in);
-}
-
-// one Chebyshev step on a nine-point level.  r: the eight off-diagonals of R_omega in slots 1..8
-template <typename T, int FIRST>
-__global__ void __launch_bounds__(kBlock)
-k_cheby_var9(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ vout, T* __restrict__ dir, const T* __restrict__ dinv,
-             Op9<T> r, int N, long pitch, int row_lo, int row_hi, int strips, T rc, T omega, T ca, T cc, int rows_alloc)
-{
-    using V = typename VecOf<T>::type;
-    constexpr int W = VecOf<T>::W;
-    const Tile t = wave_tile(strips, row_hi - row_lo);
-    if (!t.active) return;
-    const Cols c = lane_cols<W>(t.strip, N, pitch);
-    const int row = row_lo + t.chunk;
-    const long at = c.col + (long)row * pitch;
-    const bool in = c.ld && row >= 0 && row < rows_alloc;
-    const V up = vload<V>(vin + at - pitch, c.ld && row >= 1 && row <= rows_alloc);
-    const V cur = vload<V>(vin + at, in);
-    const V dn = vload<V>(vin + at + pitch, c.ld && row >= -1 && row + 1 < rows_alloc);
-    const V bb = vload<V>(rhs + at, in);
-    const V dv = vload<V>(dinv + at, in);
-    Lanes<T> k9[9];
-#pragma unroll
-    for (int q = 1; q < 9; ++q) k9[q] = to_lanes(vload<V>(r.a[q] + at, in));
-    Lanes<T> dold = to_lanes(cur);
-    if (!FIRST) dold = to_lanes(vload<V>(dir + at, in));
-    const T ul = from_left(last(up)), ur = from_right(first(up));
-    const T cl = from_left(last(cur)), cr = from_right(first(cur));
-    const T dl = from_left(last(dn)), dr = from_right(first(dn));
-    const Lanes<T> p1 = stencil9<T>(to_lanes(up), to_lanes(cur), to_lanes(dn), ul, ur, cl, cr, dl, dr, k9[5], k9[1], k9[6], k9[3],
-                                    [&](int) { return rc; }, k9[4], k9[7], k9[2], k9[8]);
-    Lanes<T> dnew, vnew;
-    cheby_update<T, FIRST>(p1, to_lanes(cur), to_lanes(bb), to_lanes(dv), dold, omega, ca, cc, dnew, vnew);
-    V od = from_lanes(dnew), ov = from_lanes(vnew);
-    mask_cols(od, c.col, N);
-    mask_cols(ov, c.col, N);
-    vstore<V>(dir + at, od, c.st && in);
-    vstore<V>(vout + at, ov, c.st && in);
+    cheby_update<T, FIRST>(p1, to_lanes(t.cur), b, d, dold, omega, ca, cc, dnew, vnew);
+    store_row(dir, dnew, t, N);
+    store_row(vout, vnew, t, N);
 }
 
 // per-block maxima of the Gershgorin row sums of D^-1 A: block b takes the interior rows 1 + b, 1 + b + gridDim.x, ...
-// a: the operator (slots 1..4, and 5..8 when NINE), dinv: its D_inv.  partial[b] >= 1 for every block (rows <= N - 1 blocks)
-template <typename T, bool NINE>
+// a: the operator (slots 1 .. NQ - 1), dinv: its D_inv.  partial[b] >= 1 for every block (rows <= N - 1 blocks)
+template <typename T, int NQ>
 __global__ void __launch_bounds__(kBlock)
 k_lambda_partials(Op9<T> a, const T* __restrict__ dinv, int N, long pitch, double* __restrict__ partial)
 {
@@ -160,7 +107,7 @@ k_lambda_partials(Op9<T> a, const T* __restrict__ dinv, int N, long pitch, doubl
             if (rs) acc = acc + fabs(d * (double)a.a[2][at]);
             if (cw) acc = acc + fabs(d * (double)a.a[3][at]);
             if (ce) acc = acc + fabs(d * (double)a.a[4][at]);
-            if (NINE) {
+            if (NQ == 9) {
                 if (rn && cw) acc = acc + fabs(d * (double)a.a[5][at]);
                 if (rn && ce) acc = acc + fabs(d * (double)a.a[6][at]);
                 if (rs && cw) acc = acc + fabs(d * (double)a.a[7][at]);
@@ -168,17 +115,7 @@ k_lambda_partials(Op9<T> a, const T* __restrict__ dinv, int N, long pitch, doubl
             }
             m = acc > m ? acc : m;
         }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_down(m, off, kWave);
-        m = o > m ? o : m;
-    }
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = 0.0;
-        for (int w = 0; w < kWavesPerBlock; ++w) r = wmax[w] > r ? wmax[w] : r;
-        partial[blockIdx.x] = r;
-    }
+    block_reduce<kWavesPerBlock>(m, wmax, partial + blockIdx.x, ReduceMax{});
 }
 
 // out[0] = max of n partials: one workgroup, the pattern of k_reduce_partials with max in place of sum
@@ -187,61 +124,40 @@ static __global__ void __launch_bounds__(kReduceThreads) k_reduce_max(const doub
     __shared__ double wmax[kReduceThreads / kWave];
     double m = 0.0;
     for (int i = threadIdx.x; i < n; i += kReduceThreads) m = partial[i] > m ? partial[i] : m;
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_down(m, off, kWave);
-        m = o > m ? o : m;
-    }
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = 0.0;
-        for (int w = 0; w < kReduceThreads / kWave; ++w) r = wmax[w] > r ? wmax[w] : r;
-        out[0] = r;
-    }
+    block_reduce<kReduceThreads / kWave>(m, wmax, out, ReduceMax{});
 }
 
-// ---- host side -----------------------------------------------------------------------------------------------
-// what the launches below need of a level: the operator a (slots 0..8, corners null on five-point levels), its D_inv
-// and the off-diagonals r of R_omega (slots 1..8)
-template <typename T> struct ChebyLevel {
-    Op9<T> a, r;
-    const T* dinv;
-    bool nine;
-    int N, rows;
-    long pitch;
-};
-
+// ---- host side (the level view VarLevel and the dispatchers: mgx_var.hpp) ---------------------------------------
 // one step over the whole level: v' into vout, d in place
 template <typename T>
-void launch_cheby(const ChebyLevel<T>& l, const T* vin, const T* b, T* vout, T* dir, bool first, T rc, T omega, T ca, T cc, hipStream_t st)
+void launch_cheby(const VarLevel<T>& l, const T* vin, const T* b, T* vout, T* dir, bool first, T rc, T omega, T ca, T cc, hipStream_t st)
 {
     const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
     const dim3 grd(g.blocks), blk(kBlock);
-    if (l.nine) {
-        if (first) hipLaunchKernelGGL((k_cheby_var9<T, 1>), grd, blk, 0, st, vin, b, vout, dir, l.dinv, l.r, l.N, l.pitch, 1, l.N, g.strips, rc, omega, ca, cc, l.rows);
-        else hipLaunchKernelGGL((k_cheby_var9<T, 0>), grd, blk, 0, st, vin, b, vout, dir, l.dinv, l.r, l.N, l.pitch, 1, l.N, g.strips, rc, omega, ca, cc, l.rows);
-    } else {
-        if (first) hipLaunchKernelGGL((k_cheby_var<T, 1>), grd, blk, 0, st, vin, b, vout, dir, l.dinv, l.r, l.N, l.pitch, 1, l.N, g.strips, rc, omega, ca, cc, l.rows);
-        else hipLaunchKernelGGL((k_cheby_var<T, 0>), grd, blk, 0, st, vin, b, vout, dir, l.dinv, l.r, l.N, l.pitch, 1, l.N, g.strips, rc, omega, ca, cc, l.rows);
-    }
+    with_point_count(l.nine, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        if (first) hipLaunchKernelGGL((k_cheby_var<T, NQ, 1>), grd, blk, 0, st, vin, b, vout, dir, l.dinv, l.r, l.N, l.pitch, 1, l.N, g.strips, rc, omega, ca, cc, l.rows);
+        else hipLaunchKernelGGL((k_cheby_var<T, NQ, 0>), grd, blk, 0, st, vin, b, vout, dir, l.dinv, l.r, l.N, l.pitch, 1, l.N, g.strips, rc, omega, ca, cc, l.rows);
+    });
 }
 
 // g_l into out[0] (device); partial holds at least partial_cap doubles
 template <typename T>
-void launch_lambda_max(const ChebyLevel<T>& l, double* partial, long partial_cap, double* out, hipStream_t st)
+void launch_lambda_max(const VarLevel<T>& l, double* partial, long partial_cap, double* out, hipStream_t st)
 {
     const int blocks = (int)std::max(1L, std::min<long>(std::min<long>(l.N - 1, partial_cap), 1024));
-    if (l.nine) hipLaunchKernelGGL((k_lambda_partials<T, true>), dim3(blocks), dim3(kBlock), 0, st, l.a, l.dinv, l.N, l.pitch, partial);
-    else hipLaunchKernelGGL((k_lambda_partials<T, false>), dim3(blocks), dim3(kBlock), 0, st, l.a, l.dinv, l.N, l.pitch, partial);
+    with_point_count(l.nine, [&](auto nq) {
+        hipLaunchKernelGGL((k_lambda_partials<T, decltype(nq)::value>), dim3(blocks), dim3(kBlock), 0, st, l.a, l.dinv, l.N, l.pitch, partial);
+    });
     hipLaunchKernelGGL(k_reduce_max, dim3(1), dim3(kReduceThreads), 0, st, partial, blocks, out);
 }
 
 // mgx.hip declares these instantiations; mgx_inst.hip (-DMGX_INST_KIND=4) defines them
 #if !defined(MGX_INST_KIND) && !defined(MGX_SINGLE_TU)
-extern template void launch_cheby<double>(const ChebyLevel<double>&, const double*, const double*, double*, double*, bool, double, double, double, double, hipStream_t);
-extern template void launch_cheby<float>(const ChebyLevel<float>&, const float*, const float*, float*, float*, bool, float, float, float, float, hipStream_t);
-extern template void launch_lambda_max<double>(const ChebyLevel<double>&, double*, long, double*, hipStream_t);
-extern template void launch_lambda_max<float>(const ChebyLevel<float>&, double*, long, double*, hipStream_t);
+extern template void launch_cheby<double>(const VarLevel<double>&, const double*, const double*, double*, double*, bool, double, double, double, double, hipStream_t);
+extern template void launch_cheby<float>(const VarLevel<float>&, const float*, const float*, float*, float*, bool, float, float, float, float, hipStream_t);
+extern template void launch_lambda_max<double>(const VarLevel<double>&, double*, long, double*, hipStream_t);
+extern template void launch_lambda_max<float>(const VarLevel<float>&, double*, long, double*, hipStream_t);
 #endif
 
 } // namespace mgx

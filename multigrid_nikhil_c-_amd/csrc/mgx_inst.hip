@@ -4,7 +4,7 @@
 //   -DMGX_INST_KIND=1  launch_cycle<T, PRE, POST, SM, AR> for the (PRE, POST) pair number MGX_INST_PP
 //   -DMGX_INST_KIND=2  launch_fused<T, SM, AR>
 //   -DMGX_INST_KIND=3  launch_tile_pass<T, SM, AR>  (all six (PRE, POST) pairs of k_tile_smooth and k_tile_wide)
-//   -DMGX_INST_KIND=4  launch_cheby<T>, launch_lambda_max<T>  (mgx_cheby.hpp: k_cheby_var, k_cheby_var9, k_lambda_partials)
+//   -DMGX_INST_KIND=4  launch_cheby<T>, launch_lambda_max<T>  (mgx_cheby.hpp: k_cheby_var, k_lambda_partials)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
@@ -31,8 +31,8 @@ template bool launch_fused<T_, MGX_INST_SM, MGX_INST_AR>(int, const T_*, const T
 #elif MGX_INST_KIND == 3
 template int launch_tile_pass<T_, MGX_INST_SM, MGX_INST_AR>(const T_*, const T_*, T_*, const FoldArgs&, int, long, T_, T_, int, int, bool, int, hipStream_t);
 #elif MGX_INST_KIND == 4
-template void launch_cheby<T_>(const ChebyLevel<T_>&, const T_*, const T_*, T_*, T_*, bool, T_, T_, T_, T_, hipStream_t);
-template void launch_lambda_max<T_>(const ChebyLevel<T_>&, double*, long, double*, hipStream_t);
+template void launch_cheby<T_>(const VarLevel<T_>&, const T_*, const T_*, T_*, T_*, bool, T_, T_, T_, T_, hipStream_t);
+template void launch_lambda_max<T_>(const VarLevel<T_>&, double*, long, double*, hipStream_t);
 #else
 #error "MGX_INST_KIND must be 1, 2, 3 or 4"
 #endif

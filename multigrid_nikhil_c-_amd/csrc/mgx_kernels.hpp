@@ -914,6 +914,24 @@ static __global__ void __launch_bounds__(kReduceThreads) k_reduce_partials(const
     }
 }
 
+// One double per lane -> one per workgroup, in a fixed order (no atomics): down each wave by shuffles (32, 16, .. 1),
+// the NW wave results through LDS (wsum: NW doubles), then thread 0 combines them in wave order, starting from 0, and
+// stores *out.  op(a, b): a is the value held so far, b the one that joins it.
+struct ReduceSum { __device__ __forceinline__ double operator()(double a, double b) const { return a + b; } };
+struct ReduceMax { __device__ __forceinline__ double operator()(double a, double b) const { return b > a ? b : a; } };
+template <int NW, typename OP>
+__device__ __forceinline__ void block_reduce(double acc, double* wsum, double* __restrict__ out, OP op)
+{
+    for (int off = 32; off > 0; off >>= 1) acc = op(acc, __shfl_down(acc, off, kWave));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w = 0; w < NW; ++w) s = op(s, wsum[w]);
+        *out = s;
+    }
+}
+
 // =============================================================================
 // restriction (PS:531-546 index pattern):  coarse(I,J) = w * (corners + 2 edges
 // + 4 centre) centred on fine (2I, 2J), in the reference's summation order.

@@ -59,19 +59,6 @@ __device__ __forceinline__ float4 poisson_vec(const float4& up, const float4& cu
     return make_float4(o0.x, o0.y, o1.x, o1.y);
 }
 
-// one double per wave -> one per workgroup, into partial[slot]
-__device__ __forceinline__ void pcg_block_sum(double acc, double* wsum, double* __restrict__ partial, long slot)
-{
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, kWave);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kWavesPerBlock; ++w) s += wsum[w];
-        partial[slot] = s;
-    }
-}
-
 // rho_new = r.z -> partial[b],  gamma = z.q -> partial[nb + b]   (nb = gridDim.x)
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
@@ -96,20 +83,19 @@ k_pcg_dots(const T* __restrict__ r, const T* __restrict__ z, const T* __restrict
             }
         }
     }
-    pcg_block_sum(rz, wsum[0], partial, blockIdx.x);
-    pcg_block_sum(zq, wsum[1], partial, (long)gridDim.x + blockIdx.x);
+    block_reduce<kWavesPerBlock>(rz, wsum[0], partial + blockIdx.x, ReduceSum{});
+    block_reduce<kWavesPerBlock>(zq, wsum[1], partial + (long)gridDim.x + blockIdx.x, ReduceSum{});
 }
 
 // p' = z + beta p (first_it: p' = z, p not read), q = A p', delta partials p'.q.  A lane forms p' of its row
 // neighbours from z and p as it marches down (rows r0-1 .. r1), its column neighbours come from the adjacent lanes.
 // OP 0: the constant five-point stencil in the order of residual_vec (A u = -(((N + W) + E) + S) + 4 u);
-// OP 1: the level's coefficient grids in the CSR order N, W, C, E, S of stencil5().
+// OP 1: the level's five coefficient grids a, in the order of stencil_sum<5>().
 template <typename T, int OP>
 __global__ void __launch_bounds__(kBlock)
 k_pcg_direction(const T* __restrict__ z, const T* __restrict__ p, T* __restrict__ pn, T* __restrict__ q,
-                const double* __restrict__ sc, int first_it, double* __restrict__ partial,
-                const T* __restrict__ ac, const T* __restrict__ an, const T* __restrict__ as, const T* __restrict__ aw,
-                const T* __restrict__ ae, int N, long pitch, int R, int strips, int chunks)
+                const double* __restrict__ sc, int first_it, double* __restrict__ partial, Op9<T> a,
+                int N, long pitch, int R, int strips, int chunks)
 {
     using V = typename VecOf<T>::type;
     constexpr int W = VecOf<T>::W;
@@ -139,12 +125,11 @@ k_pcg_direction(const T* __restrict__ z, const T* __restrict__ p, T* __restrict_
             if constexpr (OP == 0) {
                 o = poisson_vec(up, cur, dn);
             } else {
-                const Lanes<T> cc = to_lanes(vload<V>(ac + at, c.ld));
-                const Lanes<T> n = to_lanes(vload<V>(an + at, c.ld)), s = to_lanes(vload<V>(as + at, c.ld));
-                const Lanes<T> w = to_lanes(vload<V>(aw + at, c.ld)), e = to_lanes(vload<V>(ae + at, c.ld));
-                const T left = from_left(last(cur)), right = from_right(first(cur));
-                o = from_lanes(stencil5<T>(to_lanes(up), to_lanes(cur), to_lanes(dn), left, right, n, w,
-                                           [&](int k) { return cc.a[k]; }, e, s));
+                Lanes<T> k[9];
+                load_coefs<5, 0>(a, at, c.ld, k);
+                Rows3<T> u{to_lanes(up), to_lanes(cur), to_lanes(dn)};
+                u.cl = from_left(last(cur)); u.cr = from_right(first(cur));
+                o = from_lanes(stencil_sum<5>(u, k, [&](int x) { return k[0].a[x]; }));
             }
             mask_cols(o, c.col, N);
             vstore<V>(pn + at, cur, c.st);
@@ -153,7 +138,7 @@ k_pcg_direction(const T* __restrict__ z, const T* __restrict__ p, T* __restrict_
             up = cur; cur = dn;
         }
     }
-    pcg_block_sum(acc, wsum, partial, blockIdx.x);
+    block_reduce<kWavesPerBlock>(acc, wsum, partial + blockIdx.x, ReduceSum{});
 }
 
 // x += alpha p, r -= alpha q, partials of ||r||^2.  After a breakdown (sc[kPcgBreak] != 0) nothing is updated.
@@ -183,7 +168,7 @@ k_pcg_update(T* __restrict__ x, const T* __restrict__ p, T* __restrict__ r, cons
             }
         }
     }
-    pcg_block_sum(acc, wsum, partial, blockIdx.x);
+    block_reduce<kWavesPerBlock>(acc, wsum, partial + blockIdx.x, ReduceSum{});
 }
 
 // fixed-order sum of n partials (the order of k_reduce_partials)

@@ -31,7 +31,7 @@
 //   degree 0 in A, so CONSISTENT and FW16 still give operators that differ by an exact factor 4 per level.
 //
 // k_restrict_opdep - B_c = c P^T f, f the residual B - A U formed in registers (MODE 1: five-point A, the finest
-//   level; MODE 2: nine-point A; the sums of k_residual_var / k_residual_var9) or B itself (MODE 0: mgx_restrict_rhs,
+//   level; MODE 2: nine-point A; the sums of k_residual_var, stencil_sum<5 | 9>) or B itself (MODE 0: mgx_restrict_rhs,
 //   FMG).  Sum over the 3 x 3 fine patch row-major (NW, N, NE, W, C, E, SW, S, SE; the centre is added unmultiplied),
 //   then one multiplication by c.  Optionally zeroes the coarse guess.
 //   Bytes per fine point: MODE 0: f in, B_c out, weights: (1 + 1/4 + 2) sizeof(T);  MODE 1: U, B, five A grids:
@@ -272,22 +272,14 @@ k_restrict_opdep(const T* __restrict__ u, const T* __restrict__ b, Op9<T> a, Wt8
             const Lanes<T> b0 = to_lanes(vload<V>(b + at, ld0)), b1 = to_lanes(vload<V>(b + at + W, ld1));
             // neighbours across the vector seams: vector 0's left is the left lane's vector 1, vector 1's right the
             // right lane's vector 0
-            const T ul0 = from_left(last(u1[j - 1])), cl0 = from_left(last(u1[j])), dl0 = from_left(last(u1[j + 1]));
-            const T ur0 = first(u1[j - 1]), cr0 = first(u1[j]), dr0 = first(u1[j + 1]);
-            const T ul1 = last(u0[j - 1]), cl1 = last(u0[j]), dl1 = last(u0[j + 1]);
-            const T ur1 = from_right(first(u0[j - 1])), cr1 = from_right(first(u0[j])), dr1 = from_right(first(u0[j + 1]));
-            Lanes<T> av0, av1;
-            if constexpr (MODE == 1) {
-                av0 = stencil5<T>(to_lanes(u0[j - 1]), to_lanes(u0[j]), to_lanes(u0[j + 1]), cl0, cr0, k0[1], k0[3],
-                                  [&](int k) { return k0[0].a[k]; }, k0[4], k0[2]);
-                av1 = stencil5<T>(to_lanes(u1[j - 1]), to_lanes(u1[j]), to_lanes(u1[j + 1]), cl1, cr1, k1[1], k1[3],
-                                  [&](int k) { return k1[0].a[k]; }, k1[4], k1[2]);
-            } else {
-                av0 = stencil9<T>(to_lanes(u0[j - 1]), to_lanes(u0[j]), to_lanes(u0[j + 1]), ul0, ur0, cl0, cr0, dl0, dr0, k0[5], k0[1], k0[6],
-                                  k0[3], [&](int k) { return k0[0].a[k]; }, k0[4], k0[7], k0[2], k0[8]);
-                av1 = stencil9<T>(to_lanes(u1[j - 1]), to_lanes(u1[j]), to_lanes(u1[j + 1]), ul1, ur1, cl1, cr1, dl1, dr1, k1[5], k1[1], k1[6],
-                                  k1[3], [&](int k) { return k1[0].a[k]; }, k1[4], k1[7], k1[2], k1[8]);
-            }
+            const Rows3<T> w0{to_lanes(u0[j - 1]), to_lanes(u0[j]), to_lanes(u0[j + 1]),
+                              from_left(last(u1[j - 1])), first(u1[j - 1]), from_left(last(u1[j])), first(u1[j]),
+                              from_left(last(u1[j + 1])), first(u1[j + 1])};
+            const Rows3<T> w1{to_lanes(u1[j - 1]), to_lanes(u1[j]), to_lanes(u1[j + 1]),
+                              last(u0[j - 1]), from_right(first(u0[j - 1])), last(u0[j]), from_right(first(u0[j])),
+                              last(u0[j + 1]), from_right(first(u0[j + 1]))};
+            const Lanes<T> av0 = stencil_sum<NQ>(w0, k0, [&](int k) { return k0[0].a[k]; });
+            const Lanes<T> av1 = stencil_sum<NQ>(w1, k1, [&](int k) { return k1[0].a[k]; });
             Lanes<T> r1;
 #pragma unroll
             for (int k = 0; k < W; ++k) {

@@ -1,26 +1,36 @@
-// mgx_var.hpp - per-level GENERAL five-point operators: the data model of the reference's second draft
-// (Multigrid_functions.cpp = MF) on the structured grid, as gfx950 kernels.
+// mgx_var.hpp - per-level GENERAL operators, five- or nine-point: the data model of the reference's second draft
+// (Multigrid_functions.cpp = MF) on the structured grid, as gfx950 kernels.  The base header of the general-operator
+// path: mgx_galerkin.hpp (R A P), mgx_opdep.hpp (operator-dependent transfers), mgx_cheby.hpp and mgx_krylov.hpp build on it.
 //
 //   MF:16-26  ProblemVar { A_sp_dict[level], A_jacobi_sp_dict[level] = {D_inv, R_omega}, b_dict, coarsest_level_matrix }
-//   MF:33-41  csr_matrix_elements: CSR per level           -> five coefficient grids per level (c, n, s, w, e)
+//   MF:33-41  csr_matrix_elements: CSR per level           -> coefficient grids per level (Op9)
 //   MF:75-96  jacobirelaxation: v <- R_omega v + omega D^-1 b (gemv, gemv alpha = omega, vm::add; MF:86-90)
 //                                                          -> k_jacobi_var (one pass instead of three)
 //   MF:122-130 restriction2D: injection                    -> k_restrict_inject
 //   MF:150-153 residual = f - A v (gemv, vm::sub)          -> k_residual_var
 //   MF:63-72, 137-139 direct solve of the coarsest system  -> dense inverse by Gauss-Jordan (set-up), matvec per solve
-// (A u)_ij = c u_ij + n u_(i-1)j + s u_(i+1)j + w u_i(j-1) + e u_i(j+1); the Dirichlet ring of the grid
-// layout is zero, so boundary-adjacent points need no special case.  A CSR row of a row-major five-point
-// operator lists its columns as N, W, C, E, S, and that is the order every sum below is taken in; no
-// contraction (-ffp-contract=off): bit-identical to the oracle's restatement (oracle/mg_oracle_var.inc).
 //
-// Roofline: every coefficient is read once per sweep, so a sweep moves v, b, D_inv, R_n, R_s, R_w, R_e in
-// and v' out: 8 sizeof(T) per point (64 B in double against the constant stencil's 24 B); the residual
-// moves v, b, c, n, s, w, e in and r out, also 8 sizeof(T).  Both are single passes of independent rows
-// (one wave per row and strip, like k_jacobi_rows): HBM-bound, no temporal fusion (a K-level pass would
-// need K-row windows of five more arrays in registers).
+// AN OPERATOR (A, or the off-diagonals of R_omega) is nine coefficient grids in the level's layout, in the SLOT ORDER
+//     c, n, s, w, e, nw, ne, sw, se   (slots 0..8; op9_slot(dy, dx));
+// a five-point operator (NQ = 5: the caller's STENCIL5 levels, the finest GALERKIN level) leaves slots 5..8 null and no
+// NQ = 5 code reads them; R A P of a five-point operator is nine-point (NQ = 9: the coarse GALERKIN levels).
+// (A u)_ij = sum over (dy, dx) of a_(dy,dx) u_(i+dy)(j+dx); the Dirichlet ring of the grid layout is zero, so
+// boundary-adjacent points need no special case.  A CSR row of a row-major operator lists its columns in the CSR ORDER
+//     NW, N, NE, W, C, E, SW, S, SE   (five-point: N, W, C, E, S - the same order with the corners left out),
+// and that is the order every sum is taken in (stencil_sum, the one place that maps slots to it); no contraction
+// (-ffp-contract=off): bit-identical to the oracle's restatement (oracle/mg_oracle_var.inc, tests/galerkin_ref.py).
+//
+// Roofline: every coefficient is read once per sweep, so a sweep moves v, b, D_inv and the NQ - 1 grids of R_omega in and
+// v' out: (NQ + 3) sizeof(T) per point - 8 on five-point levels (64 B in double against the constant stencil's 24 B), 12
+// on nine-point levels; the residual moves v, b and the NQ grids of A in and r out, the same count.  Both are single
+// passes of independent rows (one wave per row and strip, like k_jacobi_rows; 16-byte lanes, the column neighbours from
+// the adjacent lanes by DPP): HBM-bound, no temporal fusion (a K-level pass would need K-row windows of NQ more arrays
+// in registers).
 #pragma once
 
 #include "mgx_kernels.hpp"
+
+#include <type_traits>
 
 namespace mgx {
 
@@ -30,111 +40,171 @@ __device__ __forceinline__ Lanes<float> to_lanes(const float4& v) { return Lanes
 __device__ __forceinline__ double2 from_lanes(const Lanes<double>& l) { return make_double2(l.a[0], l.a[1]); }
 __device__ __forceinline__ float4 from_lanes(const Lanes<float>& l) { return make_float4(l.a[0], l.a[1], l.a[2], l.a[3]); }
 
-// sum_k coef_k * neighbour_k in CSR column order N, W, C, E, S; `centre` is the coefficient of the point itself
-// (an array element for A, the scalar 1 - omega for R_omega)
-template <typename T, typename CF>
-__device__ __forceinline__ Lanes<T> stencil5(const Lanes<T>& up, const Lanes<T>& cur, const Lanes<T>& dn, T left, T right,
-                                             const Lanes<T>& cn, const Lanes<T>& cw, CF centre, const Lanes<T>& ce, const Lanes<T>& cs)
+template <typename T> struct Op9 { const T* a[9]; };     // c, n, s, w, e, nw, ne, sw, se (corners null on five-point levels)
+template <typename T> struct Op9Out { T* a[9]; };
+
+// storage slot of the coefficient that points at (dy, dx)
+__host__ __device__ constexpr int op9_slot(int dy, int dx)
 {
+    return dy < 0 ? (dx < 0 ? 5 : dx == 0 ? 1 : 6) : dy == 0 ? (dx < 0 ? 3 : dx == 0 ? 0 : 4) : (dx < 0 ? 7 : dx == 0 ? 2 : 8);
+}
+
+// slots q0 .. NQ - 1 of an operator at a lane's columns
+template <int NQ, int Q0, typename T>
+__device__ __forceinline__ void load_coefs(const Op9<T>& op, long at, bool pred, Lanes<T> (&k)[9])
+{
+    using V = typename VecOf<T>::type;
+#pragma unroll
+    for (int q = Q0; q < NQ; ++q) k[q] = to_lanes(vload<V>(op.a[q] + at, pred));
+}
+
+// what a lane's W points read of the iterate: its own vectors of the three rows (u = up, c = current, d = down) and,
+// from the adjacent lanes, the element left (l) of its first and right (r) of its last column in each row.  A five-point
+// sum reads cl and cr only
+template <typename T> struct Rows3 { Lanes<T> up, cur, dn; T ul, ur, cl, cr, dl, dr; };
+
+// sum_k coef_k * neighbour_k in CSR order, one IEEE multiplication and one addition per term, the first term present
+// starting the accumulator.  k: the coefficients in slot order; `centre` is the coefficient of the point itself (an
+// array element for A, the scalar 1 - omega for R_omega: slot 0 of k is not read here)
+template <int NQ, typename T, typename CF>
+__device__ __forceinline__ Lanes<T> stencil_sum(const Rows3<T>& u, const Lanes<T> (&k)[9], CF centre)
+{
+    static_assert(NQ == 5 || NQ == 9, "five- or nine-point operators");
     constexpr int W = VecOf<T>::W;
     Lanes<T> o;
 #pragma unroll
-    for (int k = 0; k < W; ++k) {
-        const T l = (k == 0) ? left : cur.a[k - 1];
-        const T r = (k == W - 1) ? right : cur.a[k + 1];
-        T acc = cn.a[k] * up.a[k];
-        acc = acc + cw.a[k] * l;
-        acc = acc + centre(k) * cur.a[k];
-        acc = acc + ce.a[k] * r;
-        acc = acc + cs.a[k] * dn.a[k];
-        o.a[k] = acc;
+    for (int x = 0; x < W; ++x) {
+        const int xl = x == 0 ? 0 : x - 1, xr = x == W - 1 ? x : x + 1;
+        const T nb[3][3] = {{x == 0 ? u.ul : u.up.a[xl], u.up.a[x], x == W - 1 ? u.ur : u.up.a[xr]},
+                            {x == 0 ? u.cl : u.cur.a[xl], u.cur.a[x], x == W - 1 ? u.cr : u.cur.a[xr]},
+                            {x == 0 ? u.dl : u.dn.a[xl], u.dn.a[x], x == W - 1 ? u.dr : u.dn.a[xr]}};
+        T acc = (T)0;
+        bool started = false;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                if constexpr (NQ == 5) { if (dy != 0 && dx != 0) continue; }
+                const T term = ((dy == 0 && dx == 0) ? centre(x) : k[op9_slot(dy, dx)].a[x]) * nb[1 + dy][1 + dx];
+                acc = started ? acc + term : term;
+                started = true;
+            }
+        o.a[x] = acc;
     }
     return o;
 }
 
-// MF:75-96: one sweep of v' = R_omega v + omega (D_inv b), out of place; rows [row_lo, row_hi)
+// the tile of a wave in a one-row-per-wave pass over rows [row_lo, row_hi): `at` the offset of the lane's vector in row
+// row_lo + chunk, `in` the predicate of every load at `at`, `st` that of the stores, up / cur / dn the iterate around it.
+// A wave without a tile (active = false) loads nothing: all its predicates are false
+template <typename T> struct RowTile {
+    using V = typename VecOf<T>::type;
+    bool active, in, st;
+    long at, col;
+    V up, cur, dn;
+};
+
 template <typename T>
-__global__ void __launch_bounds__(kBlock)
-k_jacobi_var(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ vout, const T* __restrict__ dinv,
-             const T* __restrict__ rn, const T* __restrict__ rs, const T* __restrict__ rw, const T* __restrict__ re,
-             int N, long pitch, int row_lo, int row_hi, int strips, T rc, T omega, int rows_alloc)
+__device__ __forceinline__ RowTile<T> load_rows(const T* __restrict__ vin, int N, long pitch, int row_lo, int row_hi, int strips, int rows_alloc)
 {
     using V = typename VecOf<T>::type;
-    constexpr int W = VecOf<T>::W;
     const Tile t = wave_tile(strips, row_hi - row_lo);
+    const Cols c = lane_cols<VecOf<T>::W>(t.strip, N, pitch);
+    const int row = row_lo + t.chunk;
+    const bool ld = c.ld && t.active;
+    RowTile<T> r;
+    r.active = t.active;
+    r.col = c.col;
+    r.at = c.col + (long)row * pitch;
+    r.in = ld && row >= 0 && row < rows_alloc;
+    r.st = c.st && r.in;
+    r.up = vload<V>(vin + r.at - pitch, ld && row >= 1 && row <= rows_alloc);
+    r.cur = vload<V>(vin + r.at, r.in);
+    r.dn = vload<V>(vin + r.at + pitch, ld && row >= -1 && row + 1 < rows_alloc);
+    return r;
+}
+
+// the three rows of a tile with their edge values from the adjacent lanes; NQ = 5 issues the DPP moves of the current
+// row only.  Called after the pass's other loads have been issued
+template <int NQ, typename T>
+__device__ __forceinline__ Rows3<T> rows_of(const RowTile<T>& t)
+{
+    Rows3<T> u{to_lanes(t.up), to_lanes(t.cur), to_lanes(t.dn)};
+    if constexpr (NQ == 9) { u.ul = from_left(last(t.up)); u.ur = from_right(first(t.up)); }
+    u.cl = from_left(last(t.cur)); u.cr = from_right(first(t.cur));
+    if constexpr (NQ == 9) { u.dl = from_left(last(t.dn)); u.dr = from_right(first(t.dn)); }
+    return u;
+}
+
+template <typename T> __device__ __forceinline__ Lanes<T> load_lanes(const T* p, bool pred)
+{
+    return to_lanes(vload<typename VecOf<T>::type>(p, pred));
+}
+// a lane's W results as a vector, columns 0 and >= N zero; store_row: into the lane's columns of the tile's row
+template <typename T> __device__ __forceinline__ typename VecOf<T>::type masked_row(const Lanes<T>& o, const RowTile<T>& t, int N)
+{
+    typename VecOf<T>::type ov = from_lanes(o);
+    mask_cols(ov, t.col, N);
+    return ov;
+}
+template <typename T> __device__ __forceinline__ void store_row(T* out, const Lanes<T>& o, const RowTile<T>& t, int N)
+{
+    vstore<typename VecOf<T>::type>(out + t.at, masked_row(o, t, N), t.st);
+}
+
+// MF:86-90: the Jacobi value J(v) = R_omega v + omega (D_inv b) of one point, p1 = (R_omega v) there
+template <typename T> __device__ __forceinline__ T jacobi_value(T p1, T omega, T dinv, T b) { return p1 + omega * (dinv * b); }
+
+// MF:75-96: one sweep of v' = J(v), out of place; rows [row_lo, row_hi).  r: the off-diagonals of R_omega in slots
+// 1 .. NQ - 1 (its diagonal is the scalar rc = 1 - omega)
+template <typename T, int NQ>
+__global__ void __launch_bounds__(kBlock)
+k_jacobi_var(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ vout, const T* __restrict__ dinv, Op9<T> r,
+             int N, long pitch, int row_lo, int row_hi, int strips, T rc, T omega, int rows_alloc)
+{
+    constexpr int W = VecOf<T>::W;
+    const RowTile<T> t = load_rows<T>(vin, N, pitch, row_lo, row_hi, strips, rows_alloc);
     if (!t.active) return;
-    const Cols c = lane_cols<W>(t.strip, N, pitch);
-    const int r = row_lo + t.chunk;
-    const long at = c.col + (long)r * pitch;
-    const bool in = c.ld && r >= 0 && r < rows_alloc;
-    const V up = vload<V>(vin + at - pitch, c.ld && r >= 1 && r <= rows_alloc);
-    const V cur = vload<V>(vin + at, in);
-    const V dn = vload<V>(vin + at + pitch, c.ld && r >= -1 && r + 1 < rows_alloc);
-    const V bb = vload<V>(rhs + at, in);
-    const V dv = vload<V>(dinv + at, in);
-    const Lanes<T> n = to_lanes(vload<V>(rn + at, in)), s = to_lanes(vload<V>(rs + at, in));
-    const Lanes<T> w = to_lanes(vload<V>(rw + at, in)), e = to_lanes(vload<V>(re + at, in));
-    const T left = from_left(last(cur)), right = from_right(first(cur));
-    const Lanes<T> p1 = stencil5<T>(to_lanes(up), to_lanes(cur), to_lanes(dn), left, right, n, w, [&](int) { return rc; }, e, s);   // MF:86
-    const Lanes<T> b = to_lanes(bb), d = to_lanes(dv);
+    const Lanes<T> b = load_lanes(rhs + t.at, t.in), d = load_lanes(dinv + t.at, t.in);
+    Lanes<T> k[9];
+    load_coefs<NQ, 1>(r, t.at, t.in, k);
+    const Lanes<T> p1 = stencil_sum<NQ>(rows_of<NQ>(t), k, [&](int) { return rc; });                                                       // MF:86
     Lanes<T> o;
 #pragma unroll
-    for (int k = 0; k < W; ++k) o.a[k] = p1.a[k] + omega * (d.a[k] * b.a[k]);                                                   // MF:88, 90
-    V ov = from_lanes(o);
-    mask_cols(ov, c.col, N);
-    vstore<V>(vout + at, ov, c.st && in);
+    for (int x = 0; x < W; ++x) o.a[x] = jacobi_value(p1.a[x], omega, d.a[x], b.a[x]);                                         // MF:88, 90
+    store_row(vout, o, t, N);
 }
 
 // MF:150-153: r = b - A v.  MODE 0: store r;  MODE 1: per-block sums of r^2 (the norm the solve reports)
-template <typename T, int MODE>
+template <typename T, int NQ, int MODE>
 __global__ void __launch_bounds__(kBlock)
-k_residual_var(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ out, double* __restrict__ partial,
-               const T* __restrict__ ac, const T* __restrict__ an, const T* __restrict__ as, const T* __restrict__ aw,
-               const T* __restrict__ ae, int N, long pitch, int row_lo, int row_hi, int strips, int rows_alloc)
+k_residual_var(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ out, double* __restrict__ partial, Op9<T> a,
+               int N, long pitch, int row_lo, int row_hi, int strips, int rows_alloc)
 {
     using V = typename VecOf<T>::type;
     constexpr int W = VecOf<T>::W;
     __shared__ double wsum[kWavesPerBlock];
-    const Tile t = wave_tile(strips, row_hi - row_lo);
+    const RowTile<T> t = load_rows<T>(vin, N, pitch, row_lo, row_hi, strips, rows_alloc);
     double acc = 0.0;
     if (t.active) {
-        const Cols c = lane_cols<W>(t.strip, N, pitch);
-        const int r = row_lo + t.chunk;
-        const long at = c.col + (long)r * pitch;
-        const bool in = c.ld && r >= 0 && r < rows_alloc;
-        const V up = vload<V>(vin + at - pitch, c.ld && r >= 1 && r <= rows_alloc);
-        const V cur = vload<V>(vin + at, in);
-        const V dn = vload<V>(vin + at + pitch, c.ld && r >= -1 && r + 1 < rows_alloc);
-        const Lanes<T> b = to_lanes(vload<V>(rhs + at, in));
-        const Lanes<T> cc = to_lanes(vload<V>(ac + at, in));
-        const Lanes<T> n = to_lanes(vload<V>(an + at, in)), s = to_lanes(vload<V>(as + at, in));
-        const Lanes<T> w = to_lanes(vload<V>(aw + at, in)), e = to_lanes(vload<V>(ae + at, in));
-        const T left = from_left(last(cur)), right = from_right(first(cur));
-        const Lanes<T> av = stencil5<T>(to_lanes(up), to_lanes(cur), to_lanes(dn), left, right, n, w, [&](int k) { return cc.a[k]; }, e, s);
+        const Lanes<T> b = load_lanes(rhs + t.at, t.in);
+        Lanes<T> k[9];
+        load_coefs<NQ, 0>(a, t.at, t.in, k);
+        const Lanes<T> av = stencil_sum<NQ>(rows_of<NQ>(t), k, [&](int x) { return k[0].a[x]; });
         Lanes<T> o;
 #pragma unroll
-        for (int k = 0; k < W; ++k) o.a[k] = b.a[k] - av.a[k];
-        V ov = from_lanes(o);
-        mask_cols(ov, c.col, N);
+        for (int x = 0; x < W; ++x) o.a[x] = b.a[x] - av.a[x];
+        const V ov = masked_row(o, t, N);
         if (MODE == 0) {
-            vstore<V>(out + at, ov, c.st && in);
-        } else if (c.st && in) {
+            vstore<V>(out + t.at, ov, t.st);
+        } else if (t.st) {
             const Lanes<T> q = to_lanes(ov);
             if constexpr (W == 2) acc = (double)q.a[0] * (double)q.a[0] + (double)q.a[1] * (double)q.a[1];
             else acc = ((double)q.a[0] * (double)q.a[0] + (double)q.a[1] * (double)q.a[1]) +
                        ((double)q.a[2] * (double)q.a[2] + (double)q.a[3] * (double)q.a[3]);
         }
     }
-    if (MODE != 0) {
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, kWave);
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double sum = 0.0;
-            for (int w2 = 0; w2 < kWavesPerBlock; ++w2) sum += wsum[w2];
-            partial[blockIdx.x] = sum;
-        }
-    }
+    if (MODE != 0) block_reduce<kWavesPerBlock>(acc, wsum, partial + blockIdx.x, ReduceSum{});
 }
 
 // MF:122-130: coarse(I, J) = wgt * fine(2I, 2J); optionally zero the coarse guess (PS:613) in the same pass
@@ -150,31 +220,26 @@ k_restrict_inject(const T* __restrict__ fine, T* __restrict__ coarse, T* __restr
     if (coarse_zero) coarse_zero[(long)I * cpitch + J] = (T)0;
 }
 
-// A_jacobi_sp_dict[level] from A_sp_dict[level] (MF:28-32): D_inv = 1 / c, R_x = -(omega (D_inv a_x)); the
-// diagonal of R_omega is 1 - omega exactly (D^-1 A has a unit diagonal) and is not stored
-template <typename T>
-__global__ void k_var_build_jacobi(const T* __restrict__ ac, const T* __restrict__ an, const T* __restrict__ as,
-                                   const T* __restrict__ aw, const T* __restrict__ ae, T* __restrict__ dinv,
-                                   T* __restrict__ rn, T* __restrict__ rs, T* __restrict__ rw, T* __restrict__ re,
-                                   int N, long pitch, T omega)
+// A_jacobi_sp_dict[level] from A_sp_dict[level] (MF:28-32): D_inv = 1 / c into slot 0 of j, R_x = -(omega (D_inv a_x))
+// for the off-diagonals into slots 1 .. NQ - 1; the diagonal of R_omega is 1 - omega exactly (D^-1 A has a unit diagonal)
+// and is not stored
+template <typename T, int NQ>
+__global__ void k_var_build_jacobi(Op9<T> a, Op9Out<T> j, int N, long pitch, T omega)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     const int r = blockIdx.y;
     if (c < 1 || c >= N || r < 1 || r >= N) return;
     const long at = (long)r * pitch + c;
-    const T d = (T)1 / ac[at];
-    dinv[at] = d;
-    rn[at] = -(omega * (d * an[at]));
-    rs[at] = -(omega * (d * as[at]));
-    rw[at] = -(omega * (d * aw[at]));
-    re[at] = -(omega * (d * ae[at]));
+    const T d = (T)1 / a.a[0][at];
+    j.a[0][at] = d;
+#pragma unroll
+    for (int q = 1; q < NQ; ++q) j.a[q][at] = -(omega * (d * a.a[q][at]));
 }
 
 // -div(a grad u) on a level from the nodal coefficient of the finest grid (rows 0..Nf of Nf + 1 doubles),
 // sampled at the level's nodes (stride q); face coefficient = mean of its two nodes (oracle: stencil_from_nodes)
 template <typename T>
-__global__ void k_var_from_nodes(const double* __restrict__ a, int Nf, int q, T* __restrict__ ac, T* __restrict__ an,
-                                 T* __restrict__ as, T* __restrict__ aw, T* __restrict__ ae, int N, long pitch)
+__global__ void k_var_from_nodes(const double* __restrict__ a, int Nf, int q, Op9Out<T> o, int N, long pitch)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     const int r = blockIdx.y;
@@ -185,31 +250,29 @@ __global__ void k_var_from_nodes(const double* __restrict__ a, int Nf, int q, T*
     const double fn = 0.5 * (ctr + node(r - 1, c)), fs = 0.5 * (ctr + node(r + 1, c));
     const double fw = 0.5 * (ctr + node(r, c - 1)), fe = 0.5 * (ctr + node(r, c + 1));
     const long at = (long)r * pitch + c;
-    ac[at] = (T)(((fn + fw) + fe) + fs);
-    an[at] = (T)(-fn); as[at] = (T)(-fs); aw[at] = (T)(-fw); ae[at] = (T)(-fe);
+    o.a[0][at] = (T)(((fn + fw) + fe) + fs);
+    o.a[1][at] = (T)(-fn); o.a[2][at] = (T)(-fs); o.a[3][at] = (T)(-fw); o.a[4][at] = (T)(-fe);
 }
 
 // ---- direct bottom solve of a general coarsest operator (MF:63-72, 137-139) ---------------------------------
 // Dense inverse of the n^2 x n^2 matrix by Gauss-Jordan elimination without pivoting (diagonally dominant
 // M-matrices), in double whatever the hierarchy's type: two launches per pivot at set-up time, one matvec per
 // solve.  Every element update is its own IEEE operations in the oracle's order (orc_dense_inverse): same bits.
-template <typename T>
-__global__ void k_var_dense_fill(double* __restrict__ M, double* __restrict__ Inv, const T* __restrict__ ac,
-                                 const T* __restrict__ an, const T* __restrict__ as, const T* __restrict__ aw,
-                                 const T* __restrict__ ae, int n, long pitch)
+
+// the coarsest operator as a dense matrix (and the identity next to it) for k_gj_prow / k_gj_elim
+template <typename T, int NQ>
+__global__ void k_var_dense_fill(double* __restrict__ M, double* __restrict__ Inv, Op9<T> a, int n, long pitch)
 {
     const int NN = n * n;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;      // column
     const int k = blockIdx.y;                                  // row = unknown (ri, rj)
     if (j >= NN) return;
     const int ri = k / n, rj = k - ri * n;
-    const long at = (long)(ri + 1) * pitch + (rj + 1);
+    const int ci = j / n, cj = j - ci * n;
+    const int dy = ci - ri, dx = cj - rj;
     double v = 0.0;
-    if (j == k) v = (double)ac[at];
-    else if (j == k - n) v = (double)an[at];
-    else if (j == k + n) v = (double)as[at];
-    else if (j == k - 1 && rj > 0) v = (double)aw[at];
-    else if (j == k + 1 && rj < n - 1) v = (double)ae[at];
+    if (dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1 && (NQ == 9 || dy == 0 || dx == 0))
+        v = (double)a.a[op9_slot(dy, dx)][(long)(ri + 1) * pitch + (rj + 1)];
     M[(long)k * NN + j] = v;
     Inv[(long)k * NN + j] = (j == k) ? 1.0 : 0.0;
 }
@@ -251,6 +314,25 @@ __global__ void k_var_dense_solve(const double* __restrict__ Inv, const T* __res
     }
     const int ri = i / n, rj = i - ri * n;
     x[(long)(ri + 1) * pitch + (rj + 1)] = (T)acc;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------
+// what a launch needs of a level: the operator a, its D_inv and the off-diagonals r of R_omega (slots 1 .. 8; both
+// with null corners on five-point levels)
+template <typename T> struct VarLevel {
+    Op9<T> a, r;
+    const T* dinv;
+    bool nine;
+    int N, rows;
+    long pitch;
+};
+
+// f(double{}) or f(float{}): the working type as a tag
+template <typename F> void with_float_type(bool f64, F&& f) { if (f64) f(double{}); else f(float{}); }
+// f(tag) with decltype(tag)::value == 9 or 5: the point count NQ of a level's operator as a compile-time constant
+template <typename F> void with_point_count(bool nine, F&& f)
+{
+    if (nine) f(std::integral_constant<int, 9>{}); else f(std::integral_constant<int, 5>{});
 }
 
 } // namespace mgx

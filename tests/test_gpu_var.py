@@ -16,7 +16,7 @@ VAR = 1
 
 
 @pytest.mark.parametrize("dtype", [1, 0])
-@pytest.mark.parametrize("level,kind", [(5, "smooth"), (7, "jump"), (9, "smooth"), (10, "smooth")])
+@pytest.mark.parametrize("level,kind", [(3, "jump"), (5, "smooth"), (7, "jump"), (8, "jump"), (9, "smooth"), (10, "smooth")])
 def test_operators_are_bit_identical_to_the_oracle(pkg, po, dtype, level, kind):
     dt = np.float64 if dtype == 1 else np.float32
     n = (1 << level) - 1

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Measurements of the Galerkin hierarchy (op = MGX_OPERATOR_GALERKIN, csrc/mgx_galerkin.hpp) on one MI355X; prints the
 markdown kept as profiles/galerkin_kernel_trace_summary.md:
-  - k_jacobi_var9 / k_residual_var9 at 4096^2 (level 12 of a 13..5 hierarchy): achieved bytes/s over their
-    12 sizeof(T) per point, next to k_jacobi_var / k_residual_var (8 sizeof(T)) on a STENCIL5 handle at the same grid;
+  - k_jacobi_var<T, 9> / k_residual_var<T, 9, 0> at 4096^2 (level 12 of a 13..5 hierarchy): achieved bytes/s over their
+    12 sizeof(T) per point, next to the five-point instances <T, 5> (8 sizeof(T)) on a STENCIL5 handle at the same grid;
   - set-up: mgx_build_galerkin at 8192^2 levels 13..5 next to mgx_set_coefficient on a STENCIL5 handle;
   - time to 1e-8 (sine right-hand side as tools/pcg_bench.py): mgx_solve and mgx_solve_pcg at 2047^2 contrast 10 and
     511^2 contrast 100.
@@ -12,9 +12,9 @@ Wall times around calls that end in a device synchronise (40 sweeps or 20 residu
 (mgx_build_galerkin_transfer, csrc/mgx_opdep.hpp): mgx_restrict / mgx_prolong_add on the finest level and the one below,
 the build, and time and cycles to 1e-8 (constant right-hand side; 2047^2: the random one of seed 3).
 --transfer --trace-only: the builds and five calls of each transfer only, for a rocprofv3 --kernel-trace --stats run.
---smoother {jacobi,chebyshev}: instead, the tables of profiles/cheby_kernel_trace_summary.md.  chebyshev: k_cheby_var /
-k_cheby_var9 (csrc/mgx_cheby.hpp, 10 / 14 sizeof(T) per point and step, one word less on a block's first step) next to
-k_jacobi_var / k_jacobi_var9 at 4096^2 in the same process, then cycles and time to 1e-8 of mgx_solve and mgx_solve_pcg
+--smoother {jacobi,chebyshev}: instead, the tables of profiles/cheby_kernel_trace_summary.md.  chebyshev: k_cheby_var<T, 5 | 9, FIRST>
+(csrc/mgx_cheby.hpp, 10 / 14 sizeof(T) per point and step, one word less on a block's first step) next to
+k_jacobi_var<T, 5 | 9> at 4096^2 in the same process, then cycles and time to 1e-8 of mgx_solve and mgx_solve_pcg
 with the Chebyshev V(2,2) and V(2,1) cycles (V(2,1): the degrees whose bytes per cycle, 41 words per finest point, are
 closest to Jacobi V(2,2)'s 48; V(2,2) moves 56) for both transfers, median of 5.  jacobi: the same solves with the Jacobi
 V(2,2) cycle.  --smoother chebyshev --trace-only: five blocks of degree 4 per level and type only, for a
@@ -48,6 +48,11 @@ def wall(f, reps=3):
     return statistics.median(out)
 
 
+def kname(prefix, tag, name, mode=""):
+    """the template spelling of a kernel: tag "var" = the five-point instance, "var9" the nine-point one"""
+    return f"{prefix}var<{name}, {9 if tag == 'var9' else 5}{mode}>"
+
+
 def kernels():
     n = (1 << LK) - 1
     x = np.linspace(0.0, 1.0, (1 << LF) + 1)
@@ -74,7 +79,7 @@ def kernels():
                 ms = wall(lambda: mg.smooth(LK, sweeps)) / sweeps
                 gbs = words * es * n * n / (ms * 1e-3) / 1e9
                 rate[(tag, name)] = gbs
-                print(f"| k_jacobi_{tag}<{name}> | {1 << LK}^2 | {name} | {ms:.4f} | {words * es} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
+                print(f"| {kname('k_jacobi_', tag, name)} | {1 << LK}^2 | {name} | {ms:.4f} | {words * es} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
                 mg.residual(LK, u, b)
                 lib, h = pkg.lib(), mg._h
 
@@ -83,9 +88,9 @@ def kernels():
                         lib.mgx_residual(h, LK)
                 ms = wall(res20) / 20
                 gbs = words * es * n * n / (ms * 1e-3) / 1e9
-                print(f"| k_residual_{tag}<{name}, 0> (one host synchronise per pass) | {1 << LK}^2 | {name} | {ms:.4f} | {words * es} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
+                print(f"| {kname('k_residual_', tag, name, ', 0')} (one host synchronise per pass) | {1 << LK}^2 | {name} | {ms:.4f} | {words * es} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
     for name in ("f64", "f32"):
-        print(f"\nk_jacobi_var9 / k_jacobi_var bytes/s, {name}: {rate[('var9', name)] / rate[('var', name)]:.3f} (accepted: >= 0.9)")
+        print(f"\nk_jacobi_var<T, 9> / k_jacobi_var<T, 5> bytes/s, {name}: {rate[('var9', name)] / rate[('var', name)]:.3f} (accepted: >= 0.9)")
     return rate
 
 
@@ -201,7 +206,7 @@ def smoother_kernels():
     steps = 40
     for dtype, name, es in ((pkg.DTYPE_F64, "f64", 8), (pkg.DTYPE_F32, "f32", 4)):
         for op, tag, finest in ((pkg.OPERATOR_STENCIL5, "var", LK), (pkg.OP_GALERKIN, "var9", LF)):
-            for sm, kname, words in ((pkg.SMOOTHER_JACOBI, "k_jacobi_", 8 if tag == "var" else 12),
+            for sm, prefix, words in ((pkg.SMOOTHER_JACOBI, "k_jacobi_", 8 if tag == "var" else 12),
                                      (pkg.SMOOTHER_CHEBYSHEV, "k_cheby_", 10 if tag == "var" else 14)):
                 with pkg.Multigrid(finest_level=finest, coarsest_level=5, mu1=2, mu2=2, schedule=pkg.SCHEDULE_V, op=op, dtype=dtype, omega=0.8,
                                    smoother=sm) as mg:
@@ -221,15 +226,15 @@ def smoother_kernels():
                     # a Chebyshev block's first step does not read d: one word less in `steps` steps
                     per_step = words - (1.0 / steps if sm == pkg.SMOOTHER_CHEBYSHEV else 0.0)
                     gbs = per_step * es * n * n / (ms * 1e-3) / 1e9
-                    rate[(kname, tag, name)] = gbs
-                    print(f"| {kname}{tag}<{name}> | {1 << LK}^2 | {name} | {ms:.4f} | {per_step * es:.1f} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
+                    rate[(prefix, tag, name)] = gbs
+                    print(f"| {kname(prefix, tag, name)} | {1 << LK}^2 | {name} | {ms:.4f} | {per_step * es:.1f} | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
     if TRACE_ONLY:
         return
     print()
     for name in ("f64", "f32"):
         for tag in ("var", "var9"):
             r = rate[("k_cheby_", tag, name)] / rate[("k_jacobi_", tag, name)]
-            print(f"k_cheby_{tag} / k_jacobi_{tag} bytes/s, {name}: {r:.3f} (accepted: >= 0.9{'' if r >= 0.9 else ': NOT MET'})")
+            print(f"{kname('k_cheby_', tag, 'T')} / {kname('k_jacobi_', tag, 'T')} bytes/s, {name}: {r:.3f} (accepted: >= 0.9{'' if r >= 0.9 else ': NOT MET'})")
 
 
 def smoother_solves(which):

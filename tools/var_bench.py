@@ -29,7 +29,7 @@ for dtype, name, es in ((pkg.DTYPE_F64, "f64", 8), (pkg.DTYPE_F32, "f32", 4)):
         sweeps = 40
         ms = mg.time_smoother(sweeps) / sweeps
         gbs = 8.0 * es * n * n / (ms * 1e-3) / 1e9
-        print(f"| k_jacobi_var<{'double' if es == 8 else 'float'}> (MF:75-96) | {1 << L}^2 | {name} | {ms:.4f} | {gbs:.0f} | {gbs / 8000:.3f} | {n * n / (ms * 1e-3) / 1e9:.1f} |", flush=True)
+        print(f"| k_jacobi_var<{'double' if es == 8 else 'float'}, 5> (MF:75-96) | {1 << L}^2 | {name} | {ms:.4f} | {gbs:.0f} | {gbs / 8000:.3f} | {n * n / (ms * 1e-3) / 1e9:.1f} |", flush=True)
         mg.fill_guess_random(12345)
         t0 = time.perf_counter()
         reps = 20
@@ -37,7 +37,7 @@ for dtype, name, es in ((pkg.DTYPE_F64, "f64", 8), (pkg.DTYPE_F32, "f32", 4)):
             mg.residual_norm(L)
         dt = (time.perf_counter() - t0) / reps * 1e3
         gbs = 7.0 * es * n * n / (dt * 1e-3) / 1e9
-        print(f"| k_residual_var<.., 1> + reduction (MF:150-153, norm only: 7 sizeof(T) per point; wall time incl. the host sync) | {1 << L}^2 | {name} | {dt:.4f} | {gbs:.0f} | {gbs / 8000:.3f} | |", flush=True)
+        print(f"| k_residual_var<.., 5, 1> + reduction (MF:150-153, norm only: 7 sizeof(T) per point; wall time incl. the host sync) | {1 << L}^2 | {name} | {dt:.4f} | {gbs:.0f} | {gbs / 8000:.3f} | |", flush=True)
         if dtype == pkg.DTYPE_F64:
             mg.fill_guess_random(12345)
             st, h = mg.solve(tol=1e-8, max_cycles=40)
