@@ -96,11 +96,10 @@ struct mgx_solver {
     int last_smooth_launches = 0;   // launches made by the most recent smoothing block
     int fold = 1;                   // fold transfers / norm into smoother passes (MGX_FOLD)
     int use_zero_in = 1;            // let first passes synthesise a known-zero iterate (MGX_ZERO_IN)
-    int zero_in_level = -1;         // level whose U is known to be all zero and has NOT been zero-filled
-    bool want_norm = false;         // the top-level post-smoothing should also produce ||r||^2 partials
     int norm_blocks_ready = 0;      // > 0: partial[] holds that many sums of r^2 for the current U
     double fine_updates = 0.0;
-    // hipGraph replay of "one V-cycle + residual norm" in mgx_solve (profiling off only)
+    // hipGraph replay of "one V-cycle + residual norm" (profiling off) or of the cycle below the finest level
+    // (cfg.profile = 2): one cache, cached_graph()
     struct CycleGraph {
         std::vector<void*> before, after;   // u / tmp of every level before and after the cycle
         hipGraphExec_t exec = nullptr;
@@ -549,6 +548,19 @@ void residual_var_t(mgx_solver* s, const Level& l, const void* u, const void* b,
     if (MODE == 1) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, s->partial, g.blocks, s->sum_dev);
 }
 
+// the same of whichever operator the handle has, on a grid pair of level l: the general operator's kernel or the
+// constant stencil's (which takes the partial-sum capacity for MODE 1 only)
+template <int MODE>
+void residual_level(mgx_solver* s, const Level& l, const void* u, const void* b, void* out)
+{
+    with_float_type(l.f64, [&](auto tag) {
+        using T = decltype(tag);
+        if (s->var) residual_var_t<T, MODE>(s, l, u, b, out);
+        else launch_residual<T, MODE>((const T*)u, (const T*)b, out, MODE ? 0 : l.pitch, MODE ? s->partial : nullptr, MODE ? s->sum_dev : nullptr,
+                                      1.0, l.N, l.pitch, 1, l.N, s->rows_per_chunk, s->stream, MODE ? s->partial_cap : -1, l.rows);
+    });
+}
+
 // ---- the executor of smoothing blocks ----------------------------------------------------------------
 // Runs the plan of q (fold_plan) on u <-> tmp, the arrays of the window q.row0 .. q.row0 + q.rows - 1 (a whole level:
 // row0 = 0, rows = N + 1).  c (may be null): the coarse window; coarse_e: the correction of q.pre; post 1: the residual
@@ -642,7 +654,8 @@ bool zero_in_ok(const mgx_solver* s, int level)
 // mu sweeps on a whole level with the prolongation+correction applied while loading (pre) and/or the
 // residual restriction (post = 1) or the residual norm (post = 2) produced by the last pass.  Returns
 // false when this level / configuration is not eligible (the caller then uses the stand-alone kernels).
-bool smooth_folded(mgx_solver* s, int level, int mu, bool pre, int post, bool zero_in = false)
+// zero_in: this level's iterate is an implicit zero;  coarse_zero_in: so is the coarse guess of post = 1.
+bool smooth_folded(mgx_solver* s, int level, int mu, bool pre, int post, bool zero_in = false, bool coarse_zero_in = false)
 {
     Level& l = s->lv[level];
     if (!fold_eligible(s, l, mu, pre, post)) return false;
@@ -663,7 +676,7 @@ bool smooth_folded(mgx_solver* s, int level, int mu, bool pre, int post, bool ze
         const Level& c = s->lv[level - 1];
         const int dt = l.f64 ? MGX_DTYPE_F64 : MGX_DTYPE_F32;
         const mgx_slab cs{level - 1, dt, c.rows, 0, s->cfg.arith};
-        void* czero = (post == 1 && s->zero_in_level == c.L) ? nullptr : c.u;
+        void* czero = (post == 1 && coarse_zero_in) ? nullptr : c.u;
         const BlockReq q = level_req(s, l, mu, pre, post, zero_in, env_int("MGX_ROWS", 0));
         int launches = 0;
         const int nb = with_kernel_set(l.f64, s->cfg.smoother, s->fuse.arith, [&](auto k) {
@@ -719,13 +732,13 @@ void restrict_level(mgx_solver* s, int level, bool fused, bool zero_guess)
     Prof p(s, fine ? MGX_PROF_RESTRICT_FINE : MGX_PROF_COARSE, 1);
     const int rpc = s->rows_per_chunk;
     const int mode = s->cfg.restrict_mode;
-    if (opdep(s)) {
-        // B_c = c P^T (B - A U) or c P^T B with the hierarchy's own weights, the residual formed in the same pass
-        with_float_type(f.f64, [&](auto tag) {
-            using T = decltype(tag);
+    with_float_type(f.f64, [&](auto tag) {
+        using T = decltype(tag);
+        T* cz = zero_guess ? (T*)c.u : nullptr;
+        if (opdep(s)) {
+            // B_c = c P^T (B - A U) or c P^T B with the hierarchy's own weights, the residual formed in the same pass
             const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
             const T rscale = (mode == MGX_RESTRICT_FW16) ? (T)0.25 : (T)1;
-            T* cz = zero_guess ? (T*)c.u : nullptr;
             const dim3 grd(g.blocks), blk(kBlock);
             if (!fused) hipLaunchKernelGGL((k_restrict_opdep<T, 0>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b, op9_of<T>(f), wt8_of<T>(c),
                                            (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
@@ -733,41 +746,22 @@ void restrict_level(mgx_solver* s, int level, bool fused, bool zero_guess)
                 hipLaunchKernelGGL((k_restrict_opdep<T, decltype(nq)::value == 9 ? 2 : 1>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b,
                                    op9_of<T>(f), wt8_of<T>(c), (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
             });
-        });
-        return;
-    }
-    if (s->var || mode >= MGX_RESTRICT_INJECT) {
-        // general operator and / or injection (MF:122-130): the residual is formed first (MF:150-153; f.r was
-        // allocated with the handle), then restricted by full weighting (PS:531-546) or injected
-        const void* src = f.b;
-        if (fused) {
-            if (s->var) { if (f.f64) residual_var_t<double, 0>(s, f, f.u, f.b, f.r); else residual_var_t<float, 0>(s, f, f.u, f.b, f.r); }
-            else if (f.f64) launch_residual<double, 0>((const double*)f.u, (const double*)f.b, f.r, f.pitch, nullptr, nullptr, 1.0, f.N, f.pitch, 1, f.N, rpc, s->stream, -1, f.rows);
-            else launch_residual<float, 0>((const float*)f.u, (const float*)f.b, f.r, f.pitch, nullptr, nullptr, 1.0, f.N, f.pitch, 1, f.N, rpc, s->stream, -1, f.rows);
-            src = f.r;
+            return;
         }
+        // general operator and / or injection (MF:122-130): the residual is formed first as a grid (MF:150-153; f.r
+        // was allocated with the handle), then restricted by full weighting (PS:531-546) or injected.  The constant
+        // stencil with full weighting forms it inside launch_restrict (fused) and reads B itself
+        const bool grid_residual = fused && (s->var || mode >= MGX_RESTRICT_INJECT);
+        if (grid_residual) residual_level<0>(s, f, f.u, f.b, f.r);
+        const T* src = (const T*)(grid_residual ? f.r : f.b);
         if (mode >= MGX_RESTRICT_INJECT) {
             const double w = (mode == MGX_RESTRICT_INJECT4) ? 4.0 : 1.0;
             const dim3 blk(256), grd((c.N + 255) / 256, c.N - 1);
-            if (f.f64) hipLaunchKernelGGL((k_restrict_inject<double>), grd, blk, 0, s->stream, (const double*)src, (double*)c.b,
-                                          zero_guess ? (double*)c.u : nullptr, c.N, f.pitch, c.pitch, w);
-            else hipLaunchKernelGGL((k_restrict_inject<float>), grd, blk, 0, s->stream, (const float*)src, (float*)c.b,
-                                    zero_guess ? (float*)c.u : nullptr, c.N, f.pitch, c.pitch, (float)w);
-        } else if (f.f64) {
-            launch_restrict<double>((const double*)f.u, (const double*)src, (double*)c.b, zero_guess ? (double*)c.u : nullptr, f.N, f.pitch, c.pitch,
-                                    1, c.N, 0, mode, false, rpc, s->stream);
+            hipLaunchKernelGGL((k_restrict_inject<T>), grd, blk, 0, s->stream, src, (T*)c.b, cz, c.N, f.pitch, c.pitch, (T)w);
         } else {
-            launch_restrict<float>((const float*)f.u, (const float*)src, (float*)c.b, zero_guess ? (float*)c.u : nullptr, f.N, f.pitch, c.pitch,
-                                   1, c.N, 0, mode, false, rpc, s->stream);
+            launch_restrict<T>((const T*)f.u, src, (T*)c.b, cz, f.N, f.pitch, c.pitch, 1, c.N, 0, mode, fused && !grid_residual, rpc, s->stream);
         }
-        return;
-    }
-    if (f.f64)
-        launch_restrict<double>((const double*)f.u, (const double*)f.b, (double*)c.b, zero_guess ? (double*)c.u : nullptr,
-                                f.N, f.pitch, c.pitch, 1, c.N, 0, s->cfg.restrict_mode, fused, rpc, s->stream);
-    else
-        launch_restrict<float>((const float*)f.u, (const float*)f.b, (float*)c.b, zero_guess ? (float*)c.u : nullptr,
-                               f.N, f.pitch, c.pitch, 1, c.N, 0, s->cfg.restrict_mode, fused, rpc, s->stream);
+    });
 }
 
 void prolong_level(mgx_solver* s, int level, bool add)
@@ -776,42 +770,68 @@ void prolong_level(mgx_solver* s, int level, bool add)
     Level& c = s->lv[level - 1];
     const bool fine = (level == s->cfg.finest_level);
     Prof p(s, fine ? MGX_PROF_PROLONG_FINE : MGX_PROF_COARSE, 1);
-    const int rpc = s->rows_per_chunk;
-    if (opdep(s)) {
-        with_float_type(f.f64, [&](auto tag) {
-            using T = decltype(tag);
-            const Launch g = make_launch(c.N, VecOf<T>::W, c.N, 1);
-            if (add) hipLaunchKernelGGL((k_prolong_opdep<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)f.u, (const T*)c.u, wt8_of<T>(c),
-                                        c.N, f.pitch, c.pitch, g.strips);
-            else hipLaunchKernelGGL((k_prolong_opdep<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)f.u, (const T*)c.u, wt8_of<T>(c),
+    with_float_type(f.f64, [&](auto tag) {
+        using T = decltype(tag);
+        if (!opdep(s)) {
+            launch_prolong<T>((T*)f.u, (const T*)c.u, f.N, f.pitch, c.pitch, 1, f.N, 0, add, s->rows_per_chunk, s->stream);
+            return;
+        }
+        const Launch g = make_launch(c.N, VecOf<T>::W, c.N, 1);
+        if (add) hipLaunchKernelGGL((k_prolong_opdep<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)f.u, (const T*)c.u, wt8_of<T>(c),
                                     c.N, f.pitch, c.pitch, g.strips);
-        });
-        return;
-    }
-    if (f.f64)
-        launch_prolong<double>((double*)f.u, (const double*)c.u, f.N, f.pitch, c.pitch, 1, f.N, 0, add, rpc, s->stream);
-    else
-        launch_prolong<float>((float*)f.u, (const float*)c.u, f.N, f.pitch, c.pitch, 1, f.N, 0, add, rpc, s->stream);
+        else hipLaunchKernelGGL((k_prolong_opdep<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)f.u, (const T*)c.u, wt8_of<T>(c),
+                                c.N, f.pitch, c.pitch, g.strips);
+    });
 }
 
 void bottom_solve(mgx_solver* s)
 {
     Level& l = s->lv[s->cfg.coarsest_level];
     Prof p(s, (l.L == s->cfg.finest_level) ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, 4);
-    if (s->var) {                                                        // MF:63-72: x = A^-1 b, A^-1 built at set-up
-        const int n = l.N - 1;
-        if (l.f64) hipLaunchKernelGGL((k_var_dense_solve<double>), dim3((n * n + 63) / 64), dim3(64), 0, s->stream, s->var_inv, (const double*)l.b, (double*)l.u, n, l.pitch);
-        else hipLaunchKernelGGL((k_var_dense_solve<float>), dim3((n * n + 63) / 64), dim3(64), 0, s->stream, s->var_inv, (const float*)l.b, (float*)l.u, n, l.pitch);
-        return;
-    }
-    if (l.f64) s->bottom.solve<double>((const double*)l.b, (double*)l.u, l.pitch, s->stream);
-    else s->bottom.solve<float>((const float*)l.b, (float*)l.u, l.pitch, s->stream);
+    const int n = l.N - 1;
+    with_float_type(l.f64, [&](auto tag) {
+        using T = decltype(tag);
+        if (s->var)                                                      // MF:63-72: x = A^-1 b, A^-1 built at set-up
+            hipLaunchKernelGGL((k_var_dense_solve<T>), dim3((n * n + 63) / 64), dim3(64), 0, s->stream, s->var_inv, (const T*)l.b, (T*)l.u, n, l.pitch);
+        else s->bottom.solve<T>((const T*)l.b, (T*)l.u, l.pitch, s->stream);
+    });
 }
 
-int zero_u(mgx_solver* s, int level);
+int zero_u(mgx_solver* s, int level)
+{
+    Level& l = s->lv[level];
+    HIPCHK(s, hipMemsetAsync(l.u, 0, l.bytes, s->stream));
+    return MGX_OK;
+}
 
-// PS:575-627 / MF:132-173
-void vcycle(mgx_solver* s, int level)
+// The two halves of a V-cycle on a level above the coarsest (PS:575-627 / MF:132-173).
+// descend: PS:581 pre-smoothing + PS:604-613 residual, restriction, zero coarse guess - one set of passes when the
+// level is eligible for folding.  zero_in_here: this level's iterate is a known zero that nobody has written.
+// Returns whether the coarse guess is one: if the coarse level's first pass can synthesise it, nobody writes or
+// reads those zeros.
+bool descend(mgx_solver* s, int level, bool zero_in_here)
+{
+    const bool zin_next = zero_in_ok(s, level - 1);
+    if (!smooth_folded(s, level, s->cfg.mu1, false, 1, zero_in_here, zin_next)) {
+        if (zero_in_here) (void)zero_u(s, level);             // cannot happen (zero_in_ok planned this block); stay correct
+        smooth(s, level, s->cfg.mu1);                         // PS:581
+        restrict_level(s, level, true, !zin_next);            // PS:604-613
+    }
+    return zin_next;
+}
+
+// ascend: PS:620-624 correction + PS:625 post-smoothing; post = 2: the last pass also sums r^2 per block (the
+// cycle's residual norm), else 0
+void ascend(mgx_solver* s, int level, int post)
+{
+    if (!smooth_folded(s, level, s->cfg.mu2, true, post)) {
+        prolong_level(s, level, true);                        // PS:620-624
+        smooth(s, level, s->cfg.mu2);                         // PS:625
+    }
+}
+
+// zero_in_here as for descend; post_top: `post` of this level's ascend (the levels below never report the norm)
+void vcycle(mgx_solver* s, int level, bool zero_in_here = false, int post_top = 0)
 {
     if (level == s->cfg.coarsest_level) {
         if (s->cfg.bottom == MGX_BOTTOM_EXACT) {
@@ -822,35 +842,9 @@ void vcycle(mgx_solver* s, int level)
         }
         return;
     }
-    // Is this level's own iterate a known, not materialised, zero (set by the caller)?
-    const bool zin_here = (s->zero_in_level == level);
-    s->zero_in_level = -1;
-    // PS:613: the coarse guess is zero.  If the coarse level's first pass can synthesise it,
-    // nobody writes or reads those zeros.
-    const bool zin_next = zero_in_ok(s, level - 1);
-    if (zin_next) s->zero_in_level = level - 1;
-    // PS:581 pre-smoothing + PS:604-613 residual, restriction, zero coarse guess:
-    // one set of passes when the level is eligible for folding
-    if (!smooth_folded(s, level, s->cfg.mu1, false, 1, zin_here)) {
-        if (zin_here) (void)zero_u(s, level);                 // cannot happen (zero_in_ok planned this block); stay correct
-        smooth(s, level, s->cfg.mu1);                         // PS:581
-        restrict_level(s, level, true, !zin_next);            // PS:604-613
-    }
-    const bool top_norm = s->want_norm && level == s->cfg.finest_level;
-    s->want_norm = false;                                     // only the outermost level reports the norm
-    vcycle(s, level - 1);                                     // PS:617
-    // PS:620-624 correction + PS:625 post-smoothing (+ the cycle's residual norm)
-    if (!smooth_folded(s, level, s->cfg.mu2, true, top_norm ? 2 : 0)) {
-        prolong_level(s, level, true);                        // PS:620-624
-        smooth(s, level, s->cfg.mu2);                         // PS:625
-    }
-}
-
-int zero_u(mgx_solver* s, int level)
-{
-    Level& l = s->lv[level];
-    HIPCHK(s, hipMemsetAsync(l.u, 0, l.bytes, s->stream));
-    return MGX_OK;
+    const bool zin_next = descend(s, level, zero_in_here);
+    vcycle(s, level - 1, zin_next);                           // PS:617
+    ascend(s, level, post_top);
 }
 
 // PS:629-650 / MF:175-191 on the working hierarchy (B[finest] must be set)
@@ -863,11 +857,11 @@ int fmg(mgx_solver* s)
     } else {
         int rc = zero_u(s, lo);                                              // PS:630
         if (rc) return rc;
-        for (int i = 0; i <= s->cfg.mu0; ++i) { s->zero_in_level = -1; vcycle(s, lo); }   // PS:635
+        for (int i = 0; i <= s->cfg.mu0; ++i) vcycle(s, lo);                 // PS:635
     }
     for (int l = lo + 1; l <= hi; ++l) {
         prolong_level(s, l, false);                                          // PS:645
-        for (int i = 0; i <= s->cfg.mu0; ++i) { s->zero_in_level = -1; vcycle(s, l); }    // PS:646-648
+        for (int i = 0; i <= s->cfg.mu0; ++i) vcycle(s, l);                  // PS:646-648
     }
     return MGX_OK;
 }
@@ -880,17 +874,9 @@ int enqueue_norm(mgx_solver* s, const Level& l, const void* u, const void* b, in
         Prof p(s, cls, 1);
         hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, s->partial, s->norm_blocks_ready,
                            s->sum_dev);
-    } else if (s->var) {
-        Prof p(s, cls, 2);
-        if (l.f64) residual_var_t<double, 1>(s, l, u, b, nullptr); else residual_var_t<float, 1>(s, l, u, b, nullptr);
     } else {
         Prof p(s, cls, 2);
-        if (l.f64)
-            launch_residual<double, 1>((const double*)u, (const double*)b, nullptr, 0, s->partial, s->sum_dev, 1.0,
-                                       l.N, l.pitch, 1, l.N, s->rows_per_chunk, s->stream, s->partial_cap, l.rows);
-        else
-            launch_residual<float, 1>((const float*)u, (const float*)b, nullptr, 0, s->partial, s->sum_dev, 1.0,
-                                      l.N, l.pitch, 1, l.N, s->rows_per_chunk, s->stream, s->partial_cap, l.rows);
+        residual_level<1>(s, l, u, b, nullptr);
     }
     s->norm_blocks_ready = 0;
     HIPCHK(s, hipMemcpyAsync(s->sum_host, s->sum_dev, sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -906,12 +892,13 @@ int residual_norm_grid(mgx_solver* s, const Level& l, const void* u, const void*
     return MGX_OK;
 }
 
-// ---- mgx_solve's loop body: one V-cycle from the finest level + the residual norm -----------
-// About 30 launches, the small levels launch-bound: with profiling off the whole body is
-// captured once into a hipGraph and replayed.  The cycle swaps each level's u / tmp buffers
-// on the host, so a graph is keyed by the buffer assignment it was captured with and carries
-// the assignment it leaves behind (a cycle with an odd number of passes on some level
-// alternates between two graphs).
+// ---- the graph cache ------------------------------------------------------------------------
+// A cycle is about 30 launches, the small levels launch-bound: what can be is captured once into a hipGraph and
+// replayed.  The cycle swaps each level's u / tmp buffers on the host, so a graph is keyed by the buffer
+// assignment it was captured with (and a tag: the kind of body) and carries the assignment it leaves behind (a
+// cycle with an odd number of passes on some level alternates between two graphs).
+constexpr size_t kMaxGraphs = 8;
+
 std::vector<void*> buffer_state(const mgx_solver* s)
 {
     std::vector<void*> v;
@@ -925,23 +912,45 @@ void set_buffer_state(mgx_solver* s, const std::vector<void*>& v)
     for (int l = s->cfg.coarsest_level; l <= s->cfg.finest_level; ++l) { s->lv[l].u = v[i++]; s->lv[l].tmp = v[i++]; }
 }
 
-// want_norm: the body ends with the residual norm (mgx_solve's loop);  zero_start: the cycle
-// starts from u = 0 (PS:613; the correction cycle of a coarse-grid solver), synthesised by the
-// first pass where it can be, so nobody writes or reads the zeros
-int cycle_body_direct(mgx_solver* s, bool want_norm, bool zero_start, double* r)
+// The graph of `enqueue` (it returns a status) for the current buffer assignment, the host-side bookkeeping of the
+// body (u / tmp, fine_updates) done: the caller launches it.  Null when the caller has to run `enqueue` itself: the
+// cache is full, or the capture or the instantiation failed - then the bookkeeping of the body that did not run is
+// undone, so that the eager launches compute the same bits, and the handle stays off graphs for good.
+template <typename Body>
+hipGraphExec_t cached_graph(mgx_solver* s, unsigned tag, Body&& enqueue)
 {
-    const int L = s->cfg.finest_level;
-    Level& l = s->lv[L];
-    s->norm_blocks_ready = 0;
-    s->want_norm = want_norm; s->zero_in_level = -1;
-    if (zero_start && L > s->cfg.coarsest_level) {
-        if (zero_in_ok(s, L)) s->zero_in_level = L;
-        else { int rc = zero_u(s, L); if (rc) return rc; }
+    std::vector<void*> key = buffer_state(s);
+    key.push_back(reinterpret_cast<void*>((uintptr_t)tag));
+    for (auto& c : s->graphs)
+        if (c.before == key) {
+            set_buffer_state(s, c.after);
+            s->fine_updates += c.fine_updates;
+            return c.exec;
+        }
+    if (s->graphs.size() >= kMaxGraphs) return nullptr;
+    const double fu0 = s->fine_updates;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipError_t e = hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        // nothing executes while capturing; the host-side bookkeeping does.  No events: they carry no time stamps there
+        s->prof_mute = true;
+        const int rc = enqueue();
+        s->prof_mute = false;
+        e = hipStreamEndCapture(s->stream, &graph);
+        if (e == hipSuccess && rc != MGX_OK) e = hipErrorUnknown;
+        if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        if (graph) (void)hipGraphDestroy(graph);
     }
-    vcycle(s, L);
-    s->want_norm = false;
-    if (!want_norm) return MGX_OK;
-    return residual_norm_grid(s, l, l.u, l.b, r, MGX_PROF_NORM_FINE);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_buffer_state(s, key);                             // (the tag at its end is not read)
+        s->fine_updates = fu0;
+        s->use_graph = 0;
+        return nullptr;
+    }
+    s->graphs.push_back({key, buffer_state(s), exec, s->fine_updates - fu0});
+    return exec;
 }
 
 // cfg.profile = 2: the finest level's passes are launched one by one between HIP events (they are
@@ -950,150 +959,93 @@ int cycle_body_direct(mgx_solver* s, bool want_norm, bool zero_start, double* r)
 // (hipEventElapsedTime: invalid resource handle - tools/probe/graph_events.hip), so this is how the
 // dominant kernel is timed with HIP events while the cycle still runs the way mgx_solve runs it
 // (cfg.profile = 1, every launch eager: 1.62 instead of 1.52 ms per cycle at 8192^2).
-int coarse_part_graph(mgx_solver* s, int level)
+int coarse_part_graph(mgx_solver* s, int level, bool zero_in_here)
 {
-    std::vector<void*> before = buffer_state(s);
-    before.push_back(reinterpret_cast<void*>((uintptr_t)(4 | (s->zero_in_level == level ? 8 : 0))));
-    mgx_solver::CycleGraph* g = nullptr;
-    for (auto& c : s->graphs)
-        if (c.before == before) { g = &c; break; }
-    if (!g) {
-        if (s->graphs.size() >= 8 || hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            vcycle(s, level);
-            return MGX_OK;
-        }
-        const double fu0 = s->fine_updates;
-        const std::vector<void*> state0 = buffer_state(s);
-        const int zin0 = s->zero_in_level;
-        s->prof_mute = true;
-        vcycle(s, level);
-        s->prof_mute = false;
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipError_t e = hipStreamEndCapture(s->stream, &graph);
-        if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            set_buffer_state(s, state0);
-            s->fine_updates = fu0;
-            s->zero_in_level = zin0;
-            s->use_graph = 0;
-            vcycle(s, level);
-            return MGX_OK;
-        }
-        mgx_solver::CycleGraph c;
-        c.before = before; c.after = buffer_state(s); c.exec = exec; c.fine_updates = s->fine_updates - fu0;
-        s->graphs.push_back(c);
-        g = &s->graphs.back();
-    } else {
-        set_buffer_state(s, g->after);
-        s->fine_updates += g->fine_updates;
-    }
-    s->zero_in_level = -1;
+    auto body = [&] { vcycle(s, level, zero_in_here); return MGX_OK; };
+    const hipGraphExec_t exec = cached_graph(s, 4u | (zero_in_here ? 8u : 0u), body);
+    if (!exec) return body();
     Prof p(s, MGX_PROF_COARSE, 1);
-    HIPCHK(s, hipGraphLaunch(g->exec, s->stream));
+    HIPCHK(s, hipGraphLaunch(exec, s->stream));
     return MGX_OK;
 }
 
-int cycle_body_split(mgx_solver* s, bool want_norm, bool zero_start, double* r)
+// ---- one V-cycle from the finest level (+ the residual norm): the loop body of mgx_solve, the preconditioner of
+// mgx_solve_pcg, mgx_vcycle_zero ---------------------------------------------------------------------------
+// A cycle that starts from u = 0 (PS:613; the correction cycle of a coarse-grid solver), three cases in order:
+//  1. the finest level's first pass can synthesise the zero (*implicit): nothing is enqueued, nobody writes or reads it;
+//  2. a one-level hierarchy outside the MIXED solve: nothing is enqueued either, the cycle is the bottom solve alone;
+//  3. otherwise (the MIXED solve's one-level correction included) u is zero-filled.
+int zero_start_u(mgx_solver* s, bool* implicit)
 {
-    struct Chain {                      // spans share their boundary events while this cycle is enqueued (mgx_solver::prof_chain)
-        mgx_solver* s;
-        explicit Chain(mgx_solver* s_) : s(s_) { s->prof_chain = env_int("MGX_PROF_CHAIN", 1) != 0; s->chain_ev = nullptr; }
-        ~Chain() { s->prof_chain = false; s->chain_ev = nullptr; }
-    } chain(s);
     const int L = s->cfg.finest_level;
-    Level& l = s->lv[L];
-    s->norm_blocks_ready = 0;
-    s->want_norm = false; s->zero_in_level = -1;
-    bool zin_here = false;
-    if (zero_start) {
-        if (zero_in_ok(s, L)) zin_here = true;
-        else { int rc = zero_u(s, L); if (rc) return rc; }
-    }
-    // the finest level's half of vcycle() (PS:581, 604-613), launch by launch
-    const bool zin_next = zero_in_ok(s, L - 1);
-    if (zin_next) s->zero_in_level = L - 1;                       // (the pre-smoothing pass then leaves the coarse guess alone)
-    if (!smooth_folded(s, L, s->cfg.mu1, false, 1, zin_here)) {
-        if (zin_here) (void)zero_u(s, L);
-        smooth(s, L, s->cfg.mu1);
-        restrict_level(s, L, true, !zin_next);
-    }
-    int rc = coarse_part_graph(s, L - 1);                         // PS:617
-    if (rc) return rc;
-    if (!smooth_folded(s, L, s->cfg.mu2, true, want_norm ? 2 : 0)) {   // PS:620-625 (+ the norm's sums)
-        prolong_level(s, L, true);
-        smooth(s, L, s->cfg.mu2);
-    }
-    if (!want_norm) return MGX_OK;
-    return residual_norm_grid(s, l, l.u, l.b, r, MGX_PROF_NORM_FINE);
+    const bool one_level = L == s->cfg.coarsest_level;
+    *implicit = zero_in_ok(s, L);
+    if (*implicit) return MGX_OK;                             // 1
+    if (one_level && !s->mixed) return MGX_OK;                // 2
+    return zero_u(s, L);                                      // 3
 }
 
+// enqueues the cycle; want_norm: and ||b - A u||^2 of its result with the copy to sum_host.  split: the submission
+// of cfg.profile = 2 (coarse_part_graph), its spans sharing their boundary events (mgx_solver::prof_chain)
+int enqueue_cycle(mgx_solver* s, bool want_norm, bool zero_start, bool split)
+{
+    struct Chain {
+        mgx_solver* s;
+        Chain(mgx_solver* s_, bool on) : s(s_) { s->prof_chain = on && env_int("MGX_PROF_CHAIN", 1) != 0; s->chain_ev = nullptr; }
+        ~Chain() { s->prof_chain = false; s->chain_ev = nullptr; }
+    } chain(s, split);
+    const int L = s->cfg.finest_level;
+    const int post = want_norm ? 2 : 0;
+    s->norm_blocks_ready = 0;
+    bool zin = false;
+    if (zero_start)
+        if (int rc = zero_start_u(s, &zin)) return rc;
+    if (split) {
+        const bool zin_next = descend(s, L, zin);
+        if (int rc = coarse_part_graph(s, L - 1, zin_next)) return rc;       // PS:617
+        ascend(s, L, post);
+    } else {
+        vcycle(s, L, zin, post);
+    }
+    return want_norm ? enqueue_norm(s, s->lv[L], s->lv[L].u, s->lv[L].b, MGX_PROF_NORM_FINE) : MGX_OK;
+}
+
+// With profiling off the whole body is one cached graph (tag: want_norm | zero_start << 1), the host synchronisation
+// that reads the norm outside it; cfg.profile = 2 splits it; cfg.profile = 1, MIXED and MGX_GRAPH=0 launch eagerly.
 int cycle_body(mgx_solver* s, bool want_norm, bool zero_start, double* r)
 {
-    if (s->cfg.profile == 2 && s->use_graph && !s->mixed && s->cfg.finest_level > s->cfg.coarsest_level)
-        return cycle_body_split(s, want_norm, zero_start, r);
-    if (!s->use_graph || s->cfg.profile || s->mixed) return cycle_body_direct(s, want_norm, zero_start, r);
-    const int L = s->cfg.finest_level;
-    std::vector<void*> before = buffer_state(s);
-    // the two flavours are different graphs: tag the key
-    before.push_back(reinterpret_cast<void*>((uintptr_t)((want_norm ? 1 : 0) | (zero_start ? 2 : 0))));
-    mgx_solver::CycleGraph* g = nullptr;
-    for (auto& c : s->graphs)
-        if (c.before == before) { g = &c; break; }
-    if (!g) {
-        if (s->graphs.size() >= 8) return cycle_body_direct(s, want_norm, zero_start, r);
-        const double fu0 = s->fine_updates;
-        const std::vector<void*> state0 = buffer_state(s);
-        if (hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            s->use_graph = 0;
-            return cycle_body_direct(s, want_norm, zero_start, r);
-        }
-        // enqueue the body (nothing executes while capturing; the host-side bookkeeping does)
-        int rc = MGX_OK;
+    const bool split = s->cfg.profile == 2 && s->use_graph && !s->mixed && s->cfg.finest_level > s->cfg.coarsest_level;
+    const bool whole = s->use_graph && !s->cfg.profile && !s->mixed;
+    auto body = [&] { return enqueue_cycle(s, want_norm, zero_start, split); };
+    const hipGraphExec_t exec = whole ? cached_graph(s, (want_norm ? 1u : 0u) | (zero_start ? 2u : 0u), body) : nullptr;
+    if (exec) {
         s->norm_blocks_ready = 0;
-        s->want_norm = want_norm; s->zero_in_level = -1;
-        if (zero_start && L > s->cfg.coarsest_level) {
-            if (zero_in_ok(s, L)) s->zero_in_level = L;
-            else rc = zero_u(s, L);
-        }
-        vcycle(s, L);
-        s->want_norm = false;
-        if (rc == MGX_OK && want_norm) rc = enqueue_norm(s, s->lv[L], s->lv[L].u, s->lv[L].b, MGX_PROF_NORM_FINE);
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipError_t e = hipStreamEndCapture(s->stream, &graph);
-        if (rc == MGX_OK && e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (rc != MGX_OK || e != hipSuccess) {
-            // undo the bookkeeping of the cycle that was not run, and stay on the direct path
-            (void)hipGetLastError();
-            set_buffer_state(s, state0);
-            s->fine_updates = fu0;
-            s->use_graph = 0;
-            return cycle_body_direct(s, want_norm, zero_start, r);
-        }
-        mgx_solver::CycleGraph c;
-        c.before = before; c.after = buffer_state(s); c.exec = exec; c.fine_updates = s->fine_updates - fu0;
-        s->graphs.push_back(c);
-        g = &s->graphs.back();
-    } else {
-        set_buffer_state(s, g->after);
-        s->fine_updates += g->fine_updates;
+        HIPCHK(s, hipGraphLaunch(exec, s->stream));
+    } else if (int rc = body()) {
+        return rc;
     }
-    s->norm_blocks_ready = 0;
-    s->zero_in_level = -1;
-    HIPCHK(s, hipGraphLaunch(g->exec, s->stream));
     if (!want_norm) return MGX_OK;
     HIPCHK(s, hipStreamSynchronize(s->stream));
     *r = std::sqrt(*s->sum_host);
     return MGX_OK;
 }
 
-inline int cycle_and_norm(mgx_solver* s, double* r) { return cycle_body(s, true, false, r); }
+// the common end of the solve entry points (the stream is idle): the statistics and the residual history
+void finish_solve(mgx_stats* stats, double* history, int history_cap, const std::vector<double>& hist, int cycles, bool converged,
+                  std::chrono::steady_clock::time_point t0, double fine_updates)
+{
+    if (stats) {
+        stats->cycles = cycles;
+        stats->initial_residual = hist.front();
+        stats->final_residual = hist.back();
+        stats->converged = converged ? 1 : 0;
+        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        stats->fine_updates = fine_updates;
+        stats->history_len = (int)hist.size();
+    }
+    if (history)
+        for (int i = 0; i < (int)hist.size() && i < history_cap; ++i) history[i] = hist[i];
+}
 
 double pow2_floor(double x)
 {
@@ -1205,9 +1157,7 @@ int pcg_run(mgx_solver* s, double tol, int max_iters, std::vector<double>& hist,
     hist.push_back(h0);
     if (h0 <= tol * h0 || max_iters == 0) return MGX_OK;               // (b = 0, u = 0: converged, nothing divided)
     // r = b - A x, into lv[L].b
-    if (s->var) residual_var_t<T, 0>(s, l, s->pcg_x, s->pcg_b, l.b);
-    else launch_residual<T, 0>((const T*)s->pcg_x, (const T*)s->pcg_b, l.b, l.pitch, nullptr, nullptr, 1.0, l.N, l.pitch, 1, l.N,
-                               s->rows_per_chunk, s->stream, s->partial_cap, l.rows);
+    residual_level<0>(s, l, s->pcg_x, s->pcg_b, l.b);
     double unused = 0.0;
     if ((rc = cycle_body(s, false, true, &unused))) return rc;         // z = M r: one V-cycle from zero, into lv[L].u
     pcg_dots<T>(s, l, g, kPcgInit);                                    // rho = r.z; p = z (first pcg_step)
@@ -1435,7 +1385,7 @@ int mgx_destroy(mgx_handle s)
     for (double* p : {s->var_M, s->var_inv, s->var_pm, s->var_pi}) if (p) (void)hipFree(p);
     for (void* p : {s->pcg_x, s->pcg_p[0], s->pcg_p[1], s->pcg_q, s->pcg_b, (void*)s->pcg_part, (void*)s->pcg_sc}) if (p) (void)hipFree(p);
     if (s->pcg_sc_host) (void)hipHostFree(s->pcg_sc_host);
-    for (auto& g : s->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    drop_graphs(s);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -1769,14 +1719,7 @@ int mgx_residual(mgx_handle s, int level)
     Level& l = s->lv[level];
     int rc = ensure_r(s, l);
     if (rc) return rc;
-    if (s->var) {
-        if (l.f64) residual_var_t<double, 0>(s, l, l.u, l.b, l.r); else residual_var_t<float, 0>(s, l, l.u, l.b, l.r);
-    } else if (l.f64)
-        launch_residual<double, 0>((const double*)l.u, (const double*)l.b, l.r, l.pitch, nullptr, nullptr, 1.0, l.N,
-                                   l.pitch, 1, l.N, s->rows_per_chunk, s->stream, -1, l.rows);
-    else
-        launch_residual<float, 0>((const float*)l.u, (const float*)l.b, l.r, l.pitch, nullptr, nullptr, 1.0, l.N,
-                                  l.pitch, 1, l.N, s->rows_per_chunk, s->stream, -1, l.rows);
+    residual_level<0>(s, l, l.u, l.b, l.r);
     OP_EPILOGUE
 }
 
@@ -1842,7 +1785,6 @@ int mgx_vcycle(mgx_handle s, int level)
         return rc ? rc : dist_sync(s, s->dist);
     }
     OP_PROLOGUE(s->cfg.coarsest_level)
-    s->zero_in_level = -1;
     vcycle(s, level);
     OP_EPILOGUE
 }
@@ -1900,7 +1842,7 @@ int mgx_solve(mgx_handle s, double tol, int max_cycles, mgx_stats* stats, double
             if (k == 0 && do_fmg) {
                 if ((rc = fmg(s))) return rc;
                 if ((rc = residual_norm_grid(s, l, l.u, l.b, &r, MGX_PROF_NORM_FINE))) return rc;
-            } else if ((rc = cycle_and_norm(s, &r))) {
+            } else if ((rc = cycle_body(s, true, false, &r))) {
                 return rc;
             }
             hist.push_back(r);
@@ -1937,10 +1879,8 @@ int mgx_solve(mgx_handle s, double tol, int max_cycles, mgx_stats* stats, double
                     launch_residual<double, 2>((const double*)d.u, (const double*)d.b, w.b, w.pitch, s->partial,
                                                s->sum_dev, 1.0 / scale, d.N, d.pitch, 1, d.N, rpc, s->stream, s->partial_cap, d.rows);
                 }
-                // PS:613-style zero guess: implicit when the first pass can synthesise it
-                if (zero_in_ok(s, L)) s->zero_in_level = L;
-                else HIPCHK(s, hipMemsetAsync(w.u, 0, w.bytes, s->stream));
-                vcycle(s, L);
+                double unused = 0.0;
+                if ((rc = cycle_body(s, false, true, &unused))) return rc;   // e = M r from a PS:613-style zero guess
                 pending_scale = scale;                        // u += scale * e still to be applied
                 if (!(s->mixed_fuse && d.tmp)) {
                     hipLaunchKernelGGL(k_axpy_f32_to_f64, dim3(g.blocks), dim3(kBlock), 0, s->stream, (double*)d.u,
@@ -1980,18 +1920,7 @@ int mgx_solve(mgx_handle s, double tol, int max_cycles, mgx_stats* stats, double
     }
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipStreamSynchronize(s->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (stats) {
-        stats->cycles = k;
-        stats->initial_residual = hist.front();
-        stats->final_residual = hist.back();
-        stats->converged = (hist.back() <= tol * hist.front()) ? 1 : 0;
-        stats->seconds = std::chrono::duration<double>(t1 - t0).count();
-        stats->fine_updates = s->fine_updates;
-        stats->history_len = (int)hist.size();
-    }
-    if (history)
-        for (int i = 0; i < (int)hist.size() && i < history_cap; ++i) history[i] = hist[i];
+    finish_solve(stats, history, history_cap, hist, k, hist.back() <= tol * hist.front(), t0, s->fine_updates);
     return MGX_OK;
 }
 
@@ -2020,18 +1949,7 @@ int mgx_solve_pcg(mgx_handle s, double tol, int max_iters, mgx_stats* stats, dou
     if (rc) return rc;
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipStreamSynchronize(s->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (stats) {
-        stats->cycles = iters;
-        stats->initial_residual = hist.front();
-        stats->final_residual = hist.back();
-        stats->converged = (!breakdown && hist.back() <= tol * hist.front()) ? 1 : 0;
-        stats->seconds = std::chrono::duration<double>(t1 - t0).count();
-        stats->fine_updates = s->fine_updates;
-        stats->history_len = (int)hist.size();
-    }
-    if (history)
-        for (int i = 0; i < (int)hist.size() && i < history_cap; ++i) history[i] = hist[i];
+    finish_solve(stats, history, history_cap, hist, iters, !breakdown && hist.back() <= tol * hist.front(), t0, s->fine_updates);
     return MGX_OK;
 }
 

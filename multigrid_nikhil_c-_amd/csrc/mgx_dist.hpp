@@ -885,18 +885,7 @@ int dist_solve(mgx_solver* s, mgx_dist* d, double tol, int max_cycles, mgx_stats
     }
     if ((rc = dist_sync(s, d))) return rc;
     for (auto& sl : d->slabs) { DCHK(s, hipSetDevice(sl.device)); DCHK(s, hipGetLastError()); }
-    const auto t1 = std::chrono::steady_clock::now();
-    if (stats) {
-        stats->cycles = k;
-        stats->initial_residual = hist.front();
-        stats->final_residual = hist.back();
-        stats->converged = (hist.back() <= tol * hist.front()) ? 1 : 0;
-        stats->seconds = std::chrono::duration<double>(t1 - t0).count();
-        stats->fine_updates = d->fine_updates;
-        stats->history_len = (int)hist.size();
-    }
-    if (history)
-        for (int i = 0; i < (int)hist.size() && i < history_cap; ++i) history[i] = hist[i];
+    finish_solve(stats, history, history_cap, hist, k, hist.back() <= tol * hist.front(), t0, d->fine_updates);
     return MGX_OK;
 }
 

@@ -186,6 +186,32 @@ def test_vcycle_zero_equals_zero_guess_then_vcycle(pkg, po, monkeypatch, cfg, gr
             assert 1 <= a.graphs_cached() <= 2
 
 
+@pytest.mark.parametrize("cfg", [dict(finest_level=9, coarsest_level=6, mu1=3, mu2=2), dict(finest_level=9, coarsest_level=6, mu1=0, mu2=2),
+                                 dict(finest_level=8, coarsest_level=5, mu1=2, mu2=1, smoother=1)])
+def test_vcycle_zero_through_the_split_submission_equals_the_whole_graph_and_eager(pkg, monkeypatch, cfg):
+    """a zero-start cycle through the split submission of cfg.profile = 2 (the finest level's halves launched
+    around one graph of the rest): the same bits as the whole-cycle graph (profile 0) and the eager launches
+    (profile 1) after every call, on changing right-hand sides and over stale iterates; graphs really cached"""
+    monkeypatch.setenv("MGX_GRAPH", "1")
+    n = (1 << cfg["finest_level"]) - 1
+    out = {}
+    for prof in (0, 1, 2):
+        rng = np.random.default_rng(7)
+        with pkg.Multigrid(profile=prof, **cfg) as mg:
+            sols = []
+            for it in range(3):
+                mg.set_rhs(rng.uniform(-1, 1, (n, n)))
+                mg.set_guess(rng.uniform(-1, 1, (n, n)))      # stale data the call must ignore
+                mg.vcycle_zero()
+                sols.append(mg.get_solution())
+            out[prof] = (sols, mg.graphs_cached())
+    for it in range(3):
+        assert np.any(out[0][0][it] != 0)
+        for prof in (1, 2):
+            assert np.array_equal(out[prof][0][it], out[0][0][it]), (cfg, prof, it)
+    assert 1 <= out[0][1] <= 2 and out[1][1] == -1 and 1 <= out[2][1] <= 2, [out[p][1] for p in (0, 1, 2)]
+
+
 def test_this_process_runs_one_rocm_stack_the_one_libmgx_was_built_against(pkg):
     """libmgx.so is built by /opt/rocm's hipcc with RUNPATH /opt/rocm/lib; the torch wheel bundles another copy of
     libamdhip64 / libhsa-runtime64 / librccl with the same SONAMEs, and whichever is loaded first serves the whole
