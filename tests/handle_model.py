@@ -1,0 +1,307 @@
+"""CPU model of ONE long-lived mgx handle: U and B of every level as numpy arrays, and every entry point of include/mgx.h
+that reads or writes them as its oracle statement.  The single operators come from oracle/pyoracle.py (POISSON) and the
+reference hierarchies of tests/galerkin_ref.py, tests/opdep_ref.py and tests/cheby_ref.py (STENCIL5, GALERKIN); the
+schedules are COMPOSED from the model's own single operators, so that the coarse levels hold after a schedule what the
+documented sequence of operators leaves there; the conjugate-gradient solve is tests/pcg_ref.py's iteration with the
+model's zero-start cycle as preconditioner.  tests/test_handle_model.py holds the compositions to the references'
+own vcycle / fmg / solve bit for bit; tests/test_gpu_handle_state.py drives a device handle and this model with the
+same calls.
+
+Every operator rounds as the device kernels do (the references are written operation by operation), so the state of
+the model is meant bit for bit, with two exceptions that are the existing suite's: norms (another summation order) and
+the exact bottom solve of the POISSON hierarchy (sine transform: tests/test_gpu_operators.py holds it to 1e-11 / two
+float ulps; the model uses the oracle's sine-transform mode, the device's method in the device's order).
+
+fine_updates follows include/mgx.h: finest-level smoother point updates (mu n^2 per block of mu sweeps or of degree
+mu), counted from the start of the last solve / solve_pcg."""
+import numpy as np
+
+import cheby_ref
+import galerkin_ref as gr
+import opdep_ref as od
+import pcg_ref
+
+JACOBI, RBGS, CHEBYSHEV = 0, 1, 2
+F32, F64, MIXED = 0, 1, 2
+V, FMG = 0, 1
+CONSISTENT, FW16 = 0, 1
+EXACT, SMOOTH = 0, 1
+SEPARATE, FMA = 0, 1
+POISSON, STENCIL5, GALERKIN = 0, 1, 3
+BILINEAR, OPERATOR = 0, 1
+
+DEFAULTS = dict(finest_level=10, coarsest_level=7, mu0=30, mu1=10, mu2=10, omega=2.0 / 3.0, smoother=JACOBI, dtype=F64,
+                schedule=FMG, restrict_mode=CONSISTENT, bottom=EXACT, arith=SEPARATE, op=POISSON)      # mgx_config_default
+
+
+class PoissonOps:
+    """the constant five-point stencil: the oracle's kernels behind the interface of galerkin_ref.Hierarchy"""
+
+    def __init__(self, po, finest, coarsest, dtype, mode, omega, smoother, arith):
+        self.po, self.L, self.Lc, self.dt, self.mode, self.omega = po, finest, coarsest, dtype, mode, omega
+        self.smoother, self.arith = smoother, arith
+        self._bottom = None
+
+    def smooth(self, lv, v, b, mu):
+        if mu == 0:
+            return v
+        if self.smoother == RBGS:
+            return self.po.rbgs(v, b, mu)
+        return self.po.jacobi(v, b, mu, self.omega, self.arith)
+
+    def residual(self, lv, v, b):
+        return self.po.residual(v, b)
+
+    def bottom(self, b):
+        if self._bottom is None:               # the sine-transform solve in the device's operation order
+            self._bottom = self.po.Solver(finest_level=self.Lc, coarsest_level=self.Lc, bottom=self.po.BOTTOM_DST,
+                                          dtype=F64 if self.dt == np.float64 else F32)
+        return self._bottom.bottom_solve(np.ascontiguousarray(b, dtype=self.dt))
+
+
+class _OracleBottom:
+    """bottom() of a STENCIL5 hierarchy through the oracle's own dense solve (orc_dense_inverse: the elimination
+    galerkin_ref.gauss_jordan_inverse states, tests/test_gpu_var.py holds the device to it bit for bit), which takes
+    a fraction of a second where the numpy statement takes several.  Mixed in BEFORE the reference class, whose
+    attributes po, Lc, dt, omega, st and _inv (cheby_ref.Stencil5.__init__) it reads: a change there has to be followed
+    here; tests/test_handle_model.py holds this bottom() to the reference's own, bit for bit"""
+
+    def bottom(self, b):
+        if self._inv is None:
+            s = self.po.Solver(finest_level=self.Lc, coarsest_level=self.Lc, op=self.po.OP_STENCIL5,
+                               dtype=F64 if self.dt == np.float64 else F32, omega=self.omega)
+            s.set_stencil(self.Lc, *[np.asarray(x, dtype=np.float64) for x in self.st[self.Lc][:5]])
+            self._inv = s
+        return self._inv.bottom_solve(np.ascontiguousarray(b, dtype=self.dt))
+
+
+class Stencil5(_OracleBottom, cheby_ref.Stencil5):
+    pass
+
+
+class Stencil5Cheby(_OracleBottom, cheby_ref.Stencil5Cheby):
+    pass
+
+
+_INVERSES = {}         # dense inverse of a coarsest nine-point operator, by its bytes: rebuilds and configurations share it
+
+
+def _shared_inverse(h):
+    """galerkin_ref.Hierarchy.bottom builds its inverse on first use (seconds at level 5): the same operator - a
+    BILINEAR rebuild after an OPERATOR one, the Chebyshev twin of a Jacobi configuration - takes it from here"""
+    if h._inv is None:
+        M = gr.dense(h.st[h.Lc])
+        key = M.tobytes()
+        if key not in _INVERSES:
+            _INVERSES[key] = gr.gauss_jordan_inverse(M)
+        h._inv = _INVERSES[key]
+
+
+class HandleModel:
+    def __init__(self, po, **cfg):
+        unknown = set(cfg) - set(DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown configuration fields {sorted(unknown)}")
+        c = dict(DEFAULTS, **cfg)
+        self.cfg = c
+        self.po = po
+        self.L, self.Lc = c["finest_level"], c["coarsest_level"]
+        if c["dtype"] == MIXED:
+            raise ValueError("dtype MIXED keeps two finest levels: not modelled")
+        self.dt = np.float64 if c["dtype"] == F64 else np.float32
+        self.op = c["op"]
+        self.U = {lv: np.zeros((self.n(lv),) * 2, dtype=self.dt) for lv in self.levels()}
+        self.B = {lv: np.zeros((self.n(lv),) * 2, dtype=self.dt) for lv in self.levels()}
+        self.R = {}
+        self.fine_updates = 0.0
+        self.st5 = None                        # GALERKIN: the finest operator, waiting for build_galerkin
+        self.transfer = None
+        self.h = None
+        if self.op == POISSON:
+            self.h = PoissonOps(po, self.L, self.Lc, self.dt, c["restrict_mode"], c["omega"], c["smoother"], c["arith"])
+
+    # -- plumbing ----------------------------------------------------------------------------------------------
+    def n(self, level):
+        return (1 << level) - 1
+
+    def levels(self):
+        return range(self.Lc, self.L + 1)
+
+    def _ops(self):
+        if self.h is None:
+            raise RuntimeError("operators not set (set_coefficient / build_galerkin): the device returns MGX_ERR_STATE")
+        return self.h
+
+    def _hier_args(self):
+        c = self.cfg
+        return dict(dtype=self.dt, mode=c["restrict_mode"], omega=c["omega"], mu1=c["mu1"], mu2=c["mu2"], mu0=c["mu0"],
+                    bottom=c["bottom"])
+
+    # -- data in and out ---------------------------------------------------------------------------------------
+    def set_level(self, level, which, a):
+        (self.U if which == 0 else self.B)[level] = np.array(a, dtype=self.dt, order="C").reshape((self.n(level),) * 2)
+
+    def get_level(self, level, which):
+        return (self.U if which == 0 else self.B)[level]
+
+    def set_rhs(self, b):
+        self.set_level(self.L, 1, b)
+
+    def set_guess(self, u):
+        self.set_level(self.L, 0, u)
+
+    def zero_level(self, level, which):
+        self.set_level(level, which, np.zeros((self.n(level),) * 2))
+
+    # -- operator changes --------------------------------------------------------------------------------------
+    def set_coefficient(self, a_nodes):
+        """STENCIL5: every level re-discretised from the nodal coefficient.  GALERKIN: the finest level only, and the
+        hierarchy is invalid until build_galerkin"""
+        a = np.ascontiguousarray(a_nodes, dtype=np.float64)
+        if self.op == STENCIL5:
+            st = {lv: self.po.stencil_from_nodes(a, lv, self.L) for lv in self.levels()}
+            cls = Stencil5Cheby if self.cfg["smoother"] == CHEBYSHEV else Stencil5
+            self.h = cls(self.po, st, self.L, self.Lc, **self._hier_args())
+        elif self.op == GALERKIN:
+            self.st5 = self.po.stencil_from_nodes(a, self.L, self.L)
+            self.h = None
+            self.transfer = None
+        else:
+            raise RuntimeError("op = POISSON: MGX_ERR_STATE")
+
+    def build_galerkin(self, transfer=BILINEAR):
+        if self.op != GALERKIN or self.st5 is None:
+            raise RuntimeError("MGX_ERR_STATE")
+        cheb = self.cfg["smoother"] == CHEBYSHEV
+        if transfer == OPERATOR:
+            cls = cheby_ref.OpdepHierarchy if cheb else od.Hierarchy
+        else:
+            cls = cheby_ref.Hierarchy if cheb else gr.Hierarchy
+        self.h = cls(self.po, self.st5, self.L, self.Lc, **self._hier_args())
+        self.transfer = transfer
+        if self.cfg["bottom"] == EXACT:
+            _shared_inverse(self.h)
+
+    # -- transfers of the current hierarchy --------------------------------------------------------------------
+    def _R(self, level, r):
+        h = self._ops()
+        if self.transfer == OPERATOR:
+            return h.restrict(level, r)
+        return self.po.restrict(r, self.cfg["restrict_mode"])
+
+    def _P(self, level, e):
+        h = self._ops()
+        if self.transfer == OPERATOR:
+            return h.prolong(level, e)
+        return self.po.prolong(e)
+
+    # -- single operators --------------------------------------------------------------------------------------
+    def smooth(self, level, mu):
+        """mu Jacobi or red-black Gauss-Seidel sweeps, or one Chebyshev block of degree mu"""
+        self.U[level] = self._ops().smooth(level, self.U[level], self.B[level], mu)
+        if level == self.L:
+            self.fine_updates += float(mu) * float(self.n(level)) * float(self.n(level))
+
+    def residual(self, level):
+        self.R[level] = self._ops().residual(level, self.U[level], self.B[level])
+        return self.R[level]
+
+    def residual_norm(self, level=None):
+        level = self.L if level is None else level
+        return self.po.norm2(self._ops().residual(level, self.U[level], self.B[level]))
+
+    def restrict(self, level):
+        """B[l-1] = R (B[l] - A U[l]),  U[l-1] = 0"""
+        self.B[level - 1] = self._R(level, self._ops().residual(level, self.U[level], self.B[level]))
+        self.U[level - 1] = np.zeros_like(self.B[level - 1])
+
+    def restrict_rhs(self, level):
+        self.B[level - 1] = self._R(level, self.B[level])
+
+    def prolong(self, level):
+        self.U[level] = self._P(level, self.U[level - 1])
+
+    def prolong_add(self, level):
+        if self.transfer == OPERATOR:
+            self.U[level] = self.U[level] + self._P(level, self.U[level - 1])
+        else:
+            self._ops()
+            self.U[level] = self.po.prolong_add(self.U[level], self.U[level - 1])
+
+    def bottom_solve(self):
+        if self.cfg["bottom"] != EXACT:
+            raise RuntimeError("bottom = SMOOTH: MGX_ERR_STATE")
+        self.U[self.Lc] = self._ops().bottom(self.B[self.Lc])
+
+    # -- schedules, composed from the operators above ----------------------------------------------------------
+    def vcycle(self, level=None):
+        level = self.L if level is None else level
+        c = self.cfg
+        if level == self.Lc:
+            if c["bottom"] == EXACT:
+                self.bottom_solve()
+            else:
+                self.smooth(level, c["mu1"])
+                self.smooth(level, c["mu2"])
+            return
+        self.smooth(level, c["mu1"])
+        self.restrict(level)
+        self.vcycle(level - 1)
+        self.prolong_add(level)
+        self.smooth(level, c["mu2"])
+
+    def vcycle_zero(self):
+        self.zero_level(self.L, 0)
+        self.vcycle(self.L)
+
+    def fmg(self):
+        c = self.cfg
+        for lv in range(self.L, self.Lc, -1):
+            self.restrict_rhs(lv)
+        if c["bottom"] == EXACT:
+            self.bottom_solve()
+        else:
+            self.zero_level(self.Lc, 0)
+            for _ in range(c["mu0"] + 1):
+                self.vcycle(self.Lc)
+        for lv in range(self.Lc + 1, self.L + 1):
+            self.prolong(lv)
+            for _ in range(c["mu0"] + 1):
+                self.vcycle(lv)
+
+    # -- solves ------------------------------------------------------------------------------------------------
+    def solve(self, tol=1e-8, max_cycles=50):
+        """(stats, history): cycles until ||r|| <= tol ||r0|| or max_cycles; schedule = FMG: the first cycle is fmg()"""
+        self.fine_updates = 0.0
+        hist = [self.residual_norm()]
+        k = 0
+        while k < max_cycles and not hist[k] <= tol * hist[0]:
+            if k == 0 and self.cfg["schedule"] == FMG:
+                self.fmg()
+            else:
+                self.vcycle(self.L)
+            hist.append(self.residual_norm())
+            k += 1
+        return dict(cycles=k, converged=int(hist[-1] <= tol * hist[0]), fine_updates=self.fine_updates), np.array(hist)
+
+    def finest_operator(self):
+        """A of the finest level as pcg_ref.Operator applies it"""
+        if self.op == POISSON:
+            return pcg_ref.Operator(None, self.dt)
+        return pcg_ref.Operator(self._ops().st[self.L][:5], self.dt)
+
+    def solve_pcg(self, tol=1e-8, max_iters=100):
+        """pcg_ref.pcg with this handle's zero-start cycle as M: r lives in B[finest] while a cycle runs, so the coarse
+        levels keep what the LAST cycle left; U[finest] = x and B[finest] = b afterwards"""
+        self.fine_updates = 0.0
+        b = self.B[self.L]
+
+        def M(r):
+            self.B[self.L] = np.ascontiguousarray(r, dtype=self.dt)
+            self.vcycle_zero()
+            return self.U[self.L]
+
+        x, hist, conv, brk = pcg_ref.pcg(self.finest_operator(), M, b, self.U[self.L], tol=tol, max_iters=max_iters)
+        self.U[self.L] = np.ascontiguousarray(x, dtype=self.dt)
+        self.B[self.L] = b
+        return dict(cycles=len(hist) - 1, converged=int(conv and not brk), fine_updates=self.fine_updates), hist
