@@ -285,6 +285,30 @@ MGX_API int mgx_fmg(mgx_handle h);
  * reads it), and with profiling off the cycle is replayed from a hipGraph. */
 MGX_API int mgx_vcycle_zero(mgx_handle h);
 
+/* ---- cycle index: V-, W- and F-cycles (absent in the reference) ------------------------------------------------
+ * The kind of every cycle the handle runs: mgx_vcycle, mgx_vcycle_zero, the loop body of mgx_solve, the inner cycles
+ * of mgx_fmg and of an FMG-schedule solve, the preconditioner of mgx_solve_pcg.  From a level l above the coarsest:
+ *   V: pre-smooth, restrict; cycle(l - 1); correct, post-smooth                       (PS:575-627; the default)
+ *   W: pre-smooth, restrict; cycle(l - 1); if l - 1 > coarsest: cycle(l - 1) again; correct, post-smooth
+ *   F: as W, but the second visit of level l - 1 is a V-cycle
+ * The second visit starts from the iterate the first one left on level l - 1, with the same right-hand side (it is
+ * never a zero guess).  The coarsest level is visited once per descent: with bottom = EXACT a second solve would return
+ * the same vector, and with bottom = SMOOTH it is one visit (mu1 + mu2 sweeps) by definition.  The finest level is still
+ * smoothed mu1 + mu2 times per cycle (mgx_stats.fine_updates is that of a V-cycle); level l is visited 2^(finest - l)
+ * times by a W-cycle.  With MGX_CYCLE_V every entry point computes the bits it computed before this call existed.
+ * The setter drops the handle's cached graphs (the next cycle is captured anew).  cfg.profile = 2: the coarse part
+ * (one graph replay between two events) is all the visits of level finest - 1.
+ * In W- and F-cycles a visit of a nine-point level with N <= 64 (level <= 6) of a GALERKIN handle with the Jacobi
+ * smoother is one launch of one workgroup (csrc/mgx_small.hpp: the iterate in LDS, the coefficients in registers),
+ * bit-identical to the per-level launches it replaces; every other level, smoother and operator runs W and F through
+ * the per-level launches, and so does everything when the environment holds MGX_SMALL_VISIT=0 at mgx_create.
+ * Handles with op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN (single GPU, dtype F64 or F32, either smoother);
+ * MGX_ERR_STATE on POISSON, MIXED and multi-GPU / rank handles, which run V-cycles only; MGX_ERR_INVALID for a NULL
+ * handle or another value.  mgx_get_cycle(NULL, ..) returns MGX_ERR_INVALID and leaves *cycle alone. */
+enum { MGX_CYCLE_V = 0, MGX_CYCLE_W = 1, MGX_CYCLE_F = 2 };
+MGX_API int mgx_set_cycle(mgx_handle h, int cycle);
+MGX_API int mgx_get_cycle(mgx_handle h, int* cycle);
+
 typedef struct {
     int cycles;                 /* cycles run (an FMG pass counts as cycle 1) */
     int converged;              /* 1 if ||r|| <= tol ||r0|| */

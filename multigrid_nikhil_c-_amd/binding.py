@@ -29,6 +29,7 @@ OPERATOR_POISSON, OPERATOR_STENCIL5 = 0, 1
 OPERATOR_GALERKIN = OP_GALERKIN = 3      # coarse operators R A P (nine-point), built on the device by build_galerkin()
 TRANSFER_BILINEAR, TRANSFER_OPERATOR = 0, 1     # P of the Galerkin hierarchy: weights 1/2, 1/4, or read off the operator's stencil
 BOTTOM_EXACT, BOTTOM_SMOOTH = 0, 1
+CYCLE_V, CYCLE_W, CYCLE_F = 0, 1, 2     # cycle index of a general-operator handle (set_cycle): one or two visits of every coarse level
 ARITH_SEPARATE, ARITH_FMA = 0, 1
 VEC_U, VEC_B, VEC_R = 0, 1, 2
 PROF_SMOOTH_FINE, PROF_RESTRICT_FINE, PROF_PROLONG_FINE, PROF_NORM_FINE, PROF_COARSE, PROF_COUNT = 0, 1, 2, 3, 4, 5
@@ -49,6 +50,7 @@ EXPORTS = [
     "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg",
     "mgx_build_galerkin", "mgx_get_stencil9",
     "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max",
+    "mgx_set_cycle", "mgx_get_cycle",
 ]
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
@@ -205,6 +207,8 @@ def lib() -> C.CDLL:
     L.mgx_get_transfer.argtypes = [vp, ip]
     L.mgx_get_prolongation.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.mgx_get_lambda_max.argtypes = [vp, C.c_int, dp]
+    L.mgx_set_cycle.argtypes = [vp, C.c_int]
+    L.mgx_get_cycle.argtypes = [vp, ip]
     _lib = L
     return L
 
@@ -449,6 +453,18 @@ class Multigrid:
         """g_l: the Gershgorin bound of the spectrum of D^-1 A of the level's current operator (mgx_get_lambda_max)"""
         out = C.c_double()
         self._chk(lib().mgx_get_lambda_max(self._h, level, C.byref(out)), "mgx_get_lambda_max")
+        return out.value
+
+    def set_cycle(self, cycle):
+        """CYCLE_V / CYCLE_W / CYCLE_F: the kind of every cycle the handle runs from here on (vcycle, vcycle_zero, solve,
+        fmg, solve_pcg).  W visits every level below the finest twice per visit of the level above, F makes the second
+        visit a V-cycle; the coarsest level is visited once per descent.  STENCIL5 and GALERKIN handles only"""
+        self._chk(lib().mgx_set_cycle(self._h, int(cycle)), "mgx_set_cycle")
+
+    @property
+    def cycle(self):
+        out = C.c_int()
+        self._chk(lib().mgx_get_cycle(self._h, C.byref(out)), "mgx_get_cycle")
         return out.value
 
     def get_stencil9(self, level, which):

@@ -19,6 +19,7 @@
 #include "mgx_galerkin.hpp"
 #include "mgx_opdep.hpp"
 #include "mgx_cheby.hpp"
+#include "mgx_small.hpp"
 #include "mgx_krylov.hpp"
 #include "mgx_dist_plan.hpp"
 
@@ -118,6 +119,9 @@ struct mgx_solver {
     bool var = false;               // cfg.op == MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN
     bool galerkin = false;          // cfg.op == MGX_OPERATOR_GALERKIN: coarse operators are R A P (mgx_build_galerkin)
     bool gal_built = false;         // ... and have been built from the current finest operator
+    int cycle = MGX_CYCLE_V;        // cycle index of every cycle the handle runs (mgx_set_cycle): V, W or F
+    int small_visit = 1;            // W / F: one-workgroup visits of the small nine-point levels (MGX_SMALL_VISIT, mgx_small.hpp)
+    int small_max_n = kSmallMaxN;   // ... of the levels with N <= this
     int transfer = MGX_TRANSFER_BILINEAR;   // ... with this prolongation (mgx_build_galerkin_transfer)
     // mgx_solve_pcg (allocated by its first call): iterate x, directions p / p' (ping-pong), q = A p, the caller's b
     // while r occupies lv[finest].b, per-block partials of the Krylov passes, the device scalars and their host copy
@@ -830,9 +834,74 @@ void ascend(mgx_solver* s, int level, int post)
     }
 }
 
-// zero_in_here as for descend; post_top: `post` of this level's ascend (the levels below never report the norm)
-void vcycle(mgx_solver* s, int level, bool zero_in_here = false, int post_top = 0)
+void vcycle(mgx_solver* s, int level, bool zero_in_here = false, int post_top = 0, int kind = -1);
+
+// Is a visit of `level` one launch of k_small_visit (mgx_small.hpp)?  Only in the W- and F-cycles of a GALERKIN handle
+// with the Jacobi smoother, on nine-point levels above the coarsest with N <= 64: the V-cycle keeps its launches and its
+// bits, and everything else runs W and F through the per-level launches
+bool small_level(const mgx_solver* s, int level)
 {
+    if (!s->small_visit || s->cycle == MGX_CYCLE_V || !s->galerkin || !s->gal_built) return false;
+    if (s->cfg.smoother != MGX_SMOOTHER_JACOBI) return false;
+    if (level <= s->cfg.coarsest_level || level > s->cfg.finest_level) return false;
+    const Level& l = s->lv[level];
+    return l.nine && l.N <= s->small_max_n;
+}
+
+// one form of the visit kernel on a small level: ascend (U += P e, mu2 sweeps), descend (mu1 sweeps, the residual
+// restricted into the coarse B, the coarse U zeroed) or, with both, the turn between two sub-cycles.  U is updated
+// in place: no u <-> tmp swap
+void small_visit(mgx_solver* s, int level, bool ascend, bool descend)
+{
+    Level& f = s->lv[level];
+    Level& c = s->lv[level - 1];
+    Prof p(s, MGX_PROF_COARSE, 1);
+    with_float_type(f.f64, [&](auto tag) {
+        using T = decltype(tag);
+        SmallVisit<T> a;
+        a.u = (T*)f.u; a.b = (const T*)f.b;
+        a.a = op9_of<T>(f); a.r = jac9_of<T>(f); a.dinv = (const T*)f.J[0];
+        a.cu = (T*)c.u; a.cb = (T*)c.b;
+        a.w = wt8_of<T>(c);
+        a.N = f.N; a.pitch = f.pitch; a.cpitch = c.pitch;
+        a.ascend = ascend; a.descend = descend; a.mu1 = s->cfg.mu1; a.mu2 = s->cfg.mu2;
+        a.opdep = opdep(s);
+        a.omega = (T)s->cfg.omega;
+        a.rc = (T)(1.0 - (double)a.omega);
+        const bool fw16 = s->cfg.restrict_mode == MGX_RESTRICT_FW16;
+        a.rscale = fw16 ? (T)0.25 : (T)1;
+        a.wgt = fw16 ? (T)0.0625 : (T)0.25;
+        launch_small_visit<T>(a, s->stream);
+    });
+    p.set(1, (ascend ? s->cfg.mu2 : 0) + (descend ? s->cfg.mu1 : 0));
+}
+
+// every visit a cycle of `kind` pays to `level` between the descend and the ascend of the level above: one (V), or two
+// on a level above the coarsest (W: both of kind W; F: the second a V-cycle).  The second visit starts from the iterate
+// the first one left, with the same right-hand side - never from an implicit zero.  The coarsest level is visited
+// once per descent: a second exact solve would return the same vector, and bottom = SMOOTH is one visit by definition.
+// On a small level (small_level) the ascend of the first visit and the descend of the second are one launch, the turn
+void coarse_visits(mgx_solver* s, int level, bool zero_in_here, int kind)
+{
+    const bool twice = kind != MGX_CYCLE_V && level > s->cfg.coarsest_level;
+    const int second = kind == MGX_CYCLE_F ? MGX_CYCLE_V : kind;
+    if (twice && small_level(s, level)) {
+        small_visit(s, level, false, true);
+        coarse_visits(s, level - 1, false, kind);
+        small_visit(s, level, true, true);
+        coarse_visits(s, level - 1, false, second);
+        small_visit(s, level, true, false);
+        return;
+    }
+    vcycle(s, level, zero_in_here, 0, kind);                  // PS:617
+    if (twice) vcycle(s, level, false, 0, second);
+}
+
+// zero_in_here as for descend; post_top: `post` of this level's ascend (the levels below never report the norm);
+// kind: MGX_CYCLE_*, < 0: the handle's (mgx_set_cycle)
+void vcycle(mgx_solver* s, int level, bool zero_in_here, int post_top, int kind)
+{
+    if (kind < 0) kind = s->cycle;
     if (level == s->cfg.coarsest_level) {
         if (s->cfg.bottom == MGX_BOTTOM_EXACT) {
             bottom_solve(s);                                  // MF:137-139
@@ -842,8 +911,14 @@ void vcycle(mgx_solver* s, int level, bool zero_in_here = false, int post_top = 
         }
         return;
     }
+    if (small_level(s, level)) {                              // (general operators: zero_in_here is never set, post_top is 0)
+        small_visit(s, level, false, true);
+        coarse_visits(s, level - 1, false, kind);
+        small_visit(s, level, true, false);
+        return;
+    }
     const bool zin_next = descend(s, level, zero_in_here);
-    vcycle(s, level - 1, zin_next);                           // PS:617
+    coarse_visits(s, level - 1, zin_next, kind);
     ascend(s, level, post_top);
 }
 
@@ -893,8 +968,11 @@ int residual_norm_grid(mgx_solver* s, const Level& l, const void* u, const void*
 }
 
 // ---- the graph cache ------------------------------------------------------------------------
-// A cycle is about 30 launches, the small levels launch-bound: what can be is captured once into a hipGraph and
-// replayed.  The cycle swaps each level's u / tmp buffers on the host, so a graph is keyed by the buffer
+// A V-cycle is about 30 launches, the small levels launch-bound: what can be is captured once into a hipGraph and
+// replayed.  A W-cycle visits level l 2^(finest - l) times, so its graph over n levels holds about 2^n times the
+// nodes of the coarsest visit (9..5 through the per-level launches: ~250 nodes; with k_small_visit three launches
+// per visit of a small level); capture time grows with it, once per buffer assignment.
+// The cycle swaps each level's u / tmp buffers on the host, so a graph is keyed by the buffer
 // assignment it was captured with (and a tag: the kind of body) and carries the assignment it leaves behind (a
 // cycle with an odd number of passes on some level alternates between two graphs).
 constexpr size_t kMaxGraphs = 8;
@@ -961,7 +1039,7 @@ hipGraphExec_t cached_graph(mgx_solver* s, unsigned tag, Body&& enqueue)
 // (cfg.profile = 1, every launch eager: 1.62 instead of 1.52 ms per cycle at 8192^2).
 int coarse_part_graph(mgx_solver* s, int level, bool zero_in_here)
 {
-    auto body = [&] { vcycle(s, level, zero_in_here); return MGX_OK; };
+    auto body = [&] { coarse_visits(s, level, zero_in_here, s->cycle); return MGX_OK; };
     const hipGraphExec_t exec = cached_graph(s, 4u | (zero_in_here ? 8u : 0u), body);
     if (!exec) return body();
     Prof p(s, MGX_PROF_COARSE, 1);
@@ -1307,6 +1385,7 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     s->fold = env_int("MGX_FOLD", 1);
     s->use_zero_in = env_int("MGX_ZERO_IN", 1);
     s->use_graph = env_int("MGX_GRAPH", 1);
+    s->small_visit = env_int("MGX_SMALL_VISIT", 1);
     int rc = MGX_OK;
     auto bail = [&](int code) { g_create_error = s->err; mgx_destroy(s); return code; };
     if (hipStreamCreate(&s->stream) != hipSuccess) { s->err = "hipStreamCreate failed"; return bail(MGX_ERR_HIP); }
@@ -1319,6 +1398,13 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
         // allocated while a cycle is being captured into a graph)
         for (int l = cfg->coarsest_level + 1; l <= cfg->finest_level; ++l)
             if ((rc = ensure_r(s, s->lv[l])) != MGX_OK) return bail(rc);
+    }
+    if (galerkin && s->small_visit) {
+        // k_small_visit's 64 KB of LDS at N = 64 in double: an attribute of the function, set outside any capture
+        if (small_visit_prepare<double>() != hipSuccess || small_visit_prepare<float>() != hipSuccess) {
+            s->err = "hipFuncSetAttribute failed for k_small_visit";
+            return bail(MGX_ERR_HIP);
+        }
     }
     if (var) {
         for (int l = cfg->coarsest_level; l <= cfg->finest_level; ++l) {
@@ -1787,6 +1873,29 @@ int mgx_vcycle(mgx_handle s, int level)
     OP_PROLOGUE(s->cfg.coarsest_level)
     vcycle(s, level);
     OP_EPILOGUE
+}
+
+int mgx_set_cycle(mgx_handle s, int cycle)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (cycle != MGX_CYCLE_V && cycle != MGX_CYCLE_W && cycle != MGX_CYCLE_F)
+        return s->fail(MGX_ERR_INVALID, "cycle must be MGX_CYCLE_V, MGX_CYCLE_W or MGX_CYCLE_F");
+    if (s->dist) return s->fail(MGX_ERR_STATE, "mgx_set_cycle: multi-GPU handles run V-cycles only (the slab plan has no second coarse visit)");
+    if (s->mixed) return s->fail(MGX_ERR_STATE, "mgx_set_cycle: dtype MIXED handles run V-cycles only; use a F64 or F32 handle");
+    if (!s->var)
+        return s->fail(MGX_ERR_STATE, "mgx_set_cycle: op = MGX_OPERATOR_POISSON handles run V-cycles only; W- and F-cycles are for "
+                                      "MGX_OPERATOR_STENCIL5 and MGX_OPERATOR_GALERKIN");
+    drop_graphs(s);                                           // a captured cycle is a cycle of the old kind: recapture
+    s->cycle = cycle;
+    return MGX_OK;
+}
+
+int mgx_get_cycle(mgx_handle s, int* cycle)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!cycle) return s->fail(MGX_ERR_INVALID, "null argument");
+    *cycle = s->cycle;
+    return MGX_OK;
 }
 
 int mgx_vcycle_zero(mgx_handle s)

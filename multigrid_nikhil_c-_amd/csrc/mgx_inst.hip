@@ -5,10 +5,13 @@
 //   -DMGX_INST_KIND=2  launch_fused<T, SM, AR>
 //   -DMGX_INST_KIND=3  launch_tile_pass<T, SM, AR>  (all six (PRE, POST) pairs of k_tile_smooth and k_tile_wide)
 //   -DMGX_INST_KIND=4  launch_cheby<T>, launch_lambda_max<T>  (mgx_cheby.hpp: k_cheby_var, k_lambda_partials)
+//   -DMGX_INST_KIND=5  launch_small_visit<T>, small_visit_prepare<T>  (mgx_small.hpp: k_small_visit)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
 #include "mgx_cheby.hpp"
+#elif MGX_INST_KIND == 5
+#include "mgx_small.hpp"
 #endif
 
 namespace mgx {
@@ -33,7 +36,10 @@ template int launch_tile_pass<T_, MGX_INST_SM, MGX_INST_AR>(const T_*, const T_*
 #elif MGX_INST_KIND == 4
 template void launch_cheby<T_>(const VarLevel<T_>&, const T_*, const T_*, T_*, T_*, bool, T_, T_, T_, T_, hipStream_t);
 template void launch_lambda_max<T_>(const VarLevel<T_>&, double*, long, double*, hipStream_t);
+#elif MGX_INST_KIND == 5
+template hipError_t small_visit_prepare<T_>();
+template void launch_small_visit<T_>(const SmallVisit<T_>&, hipStream_t);
 #else
-#error "MGX_INST_KIND must be 1, 2, 3 or 4"
+#error "MGX_INST_KIND must be 1, 2, 3, 4 or 5"
 #endif
 } // namespace mgx

@@ -945,6 +945,18 @@ __device__ __forceinline__ void block_reduce(double acc, double* wsum, double* _
 // =============================================================================
 template <typename T> struct Trip { T l, c, r; };   // residual left / centre / right of a coarse column
 
+// PS:539-542 order: wgt * ((((nw+ne)+sw)+se) + 2*(((w+e)+n)+s) + 4*c) of the three fine rows around a coarse point
+// (k_restrict and the one-workgroup visit of mgx_small.hpp)
+template <typename T> __device__ __forceinline__ T restrict_fw_value(const Trip<T>& top, const Trip<T>& mid, const Trip<T>& bot, T wgt)
+{
+    T corners = top.l + top.r; corners = corners + bot.l; corners = corners + bot.r;
+    T edges = mid.l + mid.r; edges = edges + top.c; edges = edges + bot.c;
+    return wgt * ((corners + (T)2 * edges) + (T)4 * mid.c);
+}
+// PS:398-420: the bilinear value between two coarse points, and at a cell centre ((NW + SW) + NE) + SE
+template <typename T> __device__ __forceinline__ T prolong_edge_value(T a, T b) { return (T)0.5 * (a + b); }
+template <typename T> __device__ __forceinline__ T prolong_centre_value(T nw, T sw, T ne, T se) { return (T)0.25 * (((nw + sw) + ne) + se); }
+
 template <typename T, bool FUSED>
 __global__ void __launch_bounds__(kBlock)
 k_restrict(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ coarse, T* __restrict__ coarse_zero,
@@ -1001,10 +1013,7 @@ k_restrict(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__
         T o[CW];
 #pragma unroll
         for (int k = 0; k < CW; ++k) {
-            // PS:539-542 order: ((nw+ne)+sw)+se + 2*(((w+e)+n)+s) + 4*c
-            T corners = top[k].l + top[k].r; corners = corners + bot[k].l; corners = corners + bot[k].r;
-            T edges = mid[k].l + mid[k].r; edges = edges + top[k].c; edges = edges + bot[k].c;
-            o[k] = wgt * ((corners + (T)2 * edges) + (T)4 * mid[k].c);
+            o[k] = restrict_fw_value(top[k], mid[k], bot[k], wgt);
             if (ccol + k == 0 || ccol + k >= NC) o[k] = (T)0;
         }
         if (c.st) {
@@ -1062,13 +1071,13 @@ k_prolong(T* __restrict__ v, const T* __restrict__ coarse, int N, long pitch, lo
         T o[W];
         if ((y & 1) == 0) {             // PS:398-402, 410-414
 #pragma unroll
-            for (int k = 0; k < CW; ++k) { o[2 * k] = a[k]; o[2 * k + 1] = (T)0.5 * (a[k] + a[k + 1]); }
+            for (int k = 0; k < CW; ++k) { o[2 * k] = a[k]; o[2 * k + 1] = prolong_edge_value(a[k], a[k + 1]); }
         } else {                        // PS:404-408, 416-420: ((NW + SW) + NE) + SE
             crow(I + 1, b2);
 #pragma unroll
             for (int k = 0; k < CW; ++k) {
-                o[2 * k] = (T)0.5 * (a[k] + b2[k]);
-                o[2 * k + 1] = (T)0.25 * (((a[k] + b2[k]) + a[k + 1]) + b2[k + 1]);
+                o[2 * k] = prolong_edge_value(a[k], b2[k]);
+                o[2 * k + 1] = prolong_centre_value(a[k], b2[k], a[k + 1], b2[k + 1]);
             }
         }
         if constexpr (W == 2) add = make_double2(o[0], o[1]);

@@ -230,6 +230,33 @@ k_galerkin_rap_opdep(Op9<T> f, Wt8<T> w, Op9Out<T> c, int NC, long fpitch, long 
     }
 }
 
+// c P^T f at one coarse point: r0 / r1 / r2 the three fine values (west, centre, east) of the rows 2I - 1, 2I, 2I + 1, w the
+// eight weights of the coarse point in slot order (k_restrict_opdep and the one-workgroup visit of mgx_small.hpp)
+template <typename T>
+__device__ __forceinline__ T opdep_restrict_value(const T (&w)[8], const T (&r0)[3], const T (&r1)[3], const T (&r2)[3], T rscale)
+{
+    T acc = w[4] * r0[0];
+    acc = acc + w[0] * r0[1];
+    acc = acc + w[5] * r0[2];
+    acc = acc + w[2] * r1[0];
+    acc = acc + r1[1];
+    acc = acc + w[3] * r1[2];
+    acc = acc + w[6] * r2[0];
+    acc = acc + w[1] * r2[1];
+    acc = acc + w[7] * r2[2];
+    return rscale * acc;
+}
+// P e between two coarse points (west then east, north then south) and at a cell centre ((NW + NE) + SW) + SE; every
+// argument pair: the weight of a coarse point towards the fine point, and that point's e
+template <typename T> __device__ __forceinline__ T opdep_prolong_edge(T wa, T ea, T wb, T eb) { return wa * ea + wb * eb; }
+template <typename T>
+__device__ __forceinline__ T opdep_prolong_centre(T w0, T e0, T w1, T e1, T w2, T e2, T w3, T e3)   // the coarse points NW, NE, SW, SE of the centre
+{
+    T acc = w0 * e0 + w1 * e1;
+    acc = acc + w2 * e2;
+    return acc + w3 * e3;
+}
+
 // MODE 0: f = b;  1: f = b - A u, five-point A (slots 0..4 of a);  2: nine-point A
 template <typename T, int MODE>
 __global__ void __launch_bounds__(kBlock)
@@ -297,16 +324,9 @@ k_restrict_opdep(const T* __restrict__ u, const T* __restrict__ b, Op9<T> a, Wt8
 #pragma unroll
     for (int k = 0; k < W; ++k) {
         const int m = 1 + 2 * k;
-        T acc = wv[4].a[k] * r[0][m - 1];
-        acc = acc + wv[0].a[k] * r[0][m];
-        acc = acc + wv[5].a[k] * r[0][m + 1];
-        acc = acc + wv[2].a[k] * r[1][m - 1];
-        acc = acc + r[1][m];
-        acc = acc + wv[3].a[k] * r[1][m + 1];
-        acc = acc + wv[6].a[k] * r[2][m - 1];
-        acc = acc + wv[1].a[k] * r[2][m];
-        acc = acc + wv[7].a[k] * r[2][m + 1];
-        o.a[k] = rscale * acc;
+        const T wk[8] = {wv[0].a[k], wv[1].a[k], wv[2].a[k], wv[3].a[k], wv[4].a[k], wv[5].a[k], wv[6].a[k], wv[7].a[k]};
+        const T r0[3] = {r[0][m - 1], r[0][m], r[0][m + 1]}, r1[3] = {r[1][m - 1], r[1][m], r[1][m + 1]}, r2[3] = {r[2][m - 1], r[2][m], r[2][m + 1]};
+        o.a[k] = opdep_restrict_value(wk, r0, r1, r2, rscale);
     }
     V ov = from_lanes(o);
     mask_cols(ov, cc.col, NC);
@@ -345,11 +365,10 @@ k_prolong_opdep(T* __restrict__ v, const T* __restrict__ e, Wt8<T> w, int NC, lo
     for (int k = 0; k < W; ++k) {
         const int m = 1 + k;
         f[2 * k] = e0[m];
-        f[2 * k + 1] = we[m] * e0[m] + ww[m + 1] * e0[m + 1];
-        g[2 * k] = ws[m] * e0[m] + wn[m] * e1[m];
-        T acc = wse[m] * e0[m] + wsw[m + 1] * e0[m + 1];
-        acc = acc + wne[m] * e1[m];
-        g[2 * k + 1] = acc + wnw[m + 1] * e1[m + 1];
+        f[2 * k + 1] = opdep_prolong_edge(we[m], e0[m], ww[m + 1], e0[m + 1]);
+        g[2 * k] = opdep_prolong_edge(ws[m], e0[m], wn[m], e1[m]);
+        // the cell centre south-east of coarse (I, col + k): its NW / NE / SW / SE coarse points
+        g[2 * k + 1] = opdep_prolong_centre(wse[m], e0[m], wsw[m + 1], e0[m + 1], wne[m], e1[m], wnw[m + 1], e1[m + 1]);
     }
     auto put = [&](const T* x, int row) {
         Lanes<T> a0, a1;

@@ -18,7 +18,12 @@ k_jacobi_var<T, 5 | 9> at 4096^2 in the same process, then cycles and time to 1e
 with the Chebyshev V(2,2) and V(2,1) cycles (V(2,1): the degrees whose bytes per cycle, 41 words per finest point, are
 closest to Jacobi V(2,2)'s 48; V(2,2) moves 56) for both transfers, median of 5.  jacobi: the same solves with the Jacobi
 V(2,2) cycle.  --smoother chebyshev --trace-only: five blocks of degree 4 per level and type only, for a
-rocprofv3 --kernel-trace --stats run."""
+rocprofv3 --kernel-trace --stats run.
+--cycle {v,w,f}: instead, the table of profiles/wcycle_kernel_trace_summary.md: the solves of --smoother jacobi (2047^2
+contrast 10, 511^2 contrast 100 and 1000, both transfers, Jacobi V(2,2) sweeps) with the cycle index set by
+mgx_set_cycle: cycles and median-of-5 time to 1e-8 of mgx_solve and mgx_solve_pcg.  MGX_SMALL_VISIT=0 in the environment:
+the W- and F-cycles through the per-level launches only.  --cycle w --trace-only: one solve of that kind at 511^2
+contrast 1000 (OPERATOR) only, for a rocprofv3 --kernel-trace --stats run."""
 import os
 import statistics
 import sys
@@ -237,8 +242,25 @@ def smoother_kernels():
             print(f"{kname('k_cheby_', tag, 'T')} / {kname('k_jacobi_', tag, 'T')} bytes/s, {name}: {r:.3f} (accepted: >= 0.9{'' if r >= 0.9 else ': NOT MET'})")
 
 
-def smoother_solves(which):
+CYCLES = {"v": pkg.CYCLE_V, "w": pkg.CYCLE_W, "f": pkg.CYCLE_F}
+
+
+def trace_one_solve(cycle):
+    L = 9
+    with pkg.Multigrid(finest_level=L, coarsest_level=5, mu1=2, mu2=2, schedule=0, op=pkg.OP_GALERKIN) as mg:
+        mg.set_coefficient(contrast_coefficient(L, 1000.0))
+        mg.build_galerkin(pkg.TRANSFER_OPERATOR)
+        if cycle != "v":
+            mg.set_cycle(CYCLES[cycle])
+        mg.fill_rhs(0)
+        st, hist = mg.solve(tol=1e-8, max_cycles=150)
+        print(f"one {cycle.upper()} solve at 511^2 contrast 1000, OPERATOR: {st.cycles} cycles, converged {st.converged}")
+
+
+def smoother_solves(which, cycle=None):
+    """cycle: None (the tables of --smoother) or the kind of --cycle"""
     sm = pkg.SMOOTHER_CHEBYSHEV if which == "chebyshev" else pkg.SMOOTHER_JACOBI
+    kind = (cycle or "v").upper()
     print(f"\n| problem, levels L..5, f64, smoother {which} | cycle | transfer | mgx_solve | mgx_solve_pcg |\n|---|---|---|---|---|")
     for L, contrast in ((9, 10.0), (9, 100.0), (9, 1000.0)) if QUICK else ((11, 10.0), (9, 100.0), (9, 1000.0)):
         n = (1 << L) - 1
@@ -246,6 +268,8 @@ def smoother_solves(which):
         for mu1, mu2 in ((2, 2), (2, 1)) if which == "chebyshev" else ((2, 2),):
             with pkg.Multigrid(finest_level=L, coarsest_level=5, mu1=mu1, mu2=mu2, schedule=0, op=pkg.OP_GALERKIN, smoother=sm) as mg:
                 mg.set_coefficient(contrast_coefficient(L, contrast))
+                if cycle not in (None, "v"):                # (v: the handle's default, no call)
+                    mg.set_cycle(CYCLES[cycle])
                 for transfer, tname in ((pkg.TRANSFER_BILINEAR, "BILINEAR"), (pkg.TRANSFER_OPERATOR, "OPERATOR")):
                     mg.build_galerkin(transfer)
                     if b is None:
@@ -261,11 +285,19 @@ def smoother_solves(which):
                             if rep:
                                 ts.append(st.seconds * 1e3)
                         cells.append(f"{st.cycles} {'it' if len(cells) else 'cycles'}, {statistics.median(ts):.2f} ms (min {min(ts):.2f}, max {max(ts):.2f}), converged {st.converged}")
-                    print(f"| {n}^2 contrast {contrast:g} | V({mu1},{mu2}) | {tname} | {cells[0]} | {cells[1]} |", flush=True)
+                    print(f"| {n}^2 contrast {contrast:g} | {kind}({mu1},{mu2}) | {tname} | {cells[0]} | {cells[1]} |", flush=True)
 
 
 if __name__ == "__main__":
-    if "--smoother" in sys.argv:
+    if "--cycle" in sys.argv:
+        kind = sys.argv[sys.argv.index("--cycle") + 1]
+        if kind not in CYCLES:
+            sys.exit("--cycle v, w or f")
+        if TRACE_ONLY:
+            trace_one_solve(kind)
+        else:
+            smoother_solves("jacobi", kind)
+    elif "--smoother" in sys.argv:
         which = sys.argv[sys.argv.index("--smoother") + 1]
         if which not in ("jacobi", "chebyshev"):
             sys.exit("--smoother jacobi or --smoother chebyshev")
