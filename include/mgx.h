@@ -52,7 +52,22 @@ enum { MGX_SMOOTHER_JACOBI = 0, MGX_SMOOTHER_RBGS = 1,
         * MGX_OPERATOR_GALERKIN only, dtype F64 or F32, arith SEPARATE, one GPU; with op = MGX_OPERATOR_POISSON, in
         * mgx_create_rank, mgx_plan_create and mgx_slab_cycle it is MGX_ERR_INVALID.  One more array per level (the
         * direction d) and 10 / 14 sizeof(T) per point and step on five- / nine-point levels (Jacobi: 8 / 12). */
-       MGX_SMOOTHER_CHEBYSHEV = 2 };
+       MGX_SMOOTHER_CHEBYSHEV = 2,
+       /* LINE_X / LINE_Y / LINE_ALT: zebra line Gauss-Seidel (csrc/mgx_line.hpp states the sweep).  An x-line sweep solves
+        * the tridiagonal system of every grid row exactly - the odd grid rows first, then the even ones, which read the rows
+        * just written - with the off-line terms on the right-hand side; a y-line sweep does the same down the columns; an
+        * alternating sweep is an x-sweep followed by a y-sweep.  The smoother for anisotropic operators (strong coupling
+        * along x, along y, or either in different parts of the grid), where point smoothers do not converge.  No damping:
+        * omega is validated but not used.  mu1 / mu2 (the mu of mgx_smooth, the sweeps of mgx_time_smoother) count
+        * sweeps; a sweep is two launches per direction and updates the iterate in place; mgx_stats.fine_updates counts
+        * one update per point and x- or y-sweep (an alternating sweep: two).  The tridiagonal factors are built with the
+        * operator (mgx_get_line_factor); a zero or non-finite pivot makes mgx_set_stencil / mgx_set_coefficient / the
+        * Galerkin builds return MGX_ERR_INVALID.  Handles with op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN only,
+        * dtype F64 or F32, arith SEPARATE, one GPU; with op = MGX_OPERATOR_POISSON, in mgx_create_rank, mgx_plan_create and
+        * mgx_slab_cycle they are MGX_ERR_INVALID.  Two more arrays per level and direction; 11 / 15 sizeof(T) per point
+        * and sweep direction on five- / nine-point levels (15 / 19 for y-lines on levels cut into chunks).
+        * (The value 3 stays an invalid smoother: mgx_create has always refused it and the suite pins that.) */
+       MGX_SMOOTHER_LINE_X = 4, MGX_SMOOTHER_LINE_Y = 5, MGX_SMOOTHER_LINE_ALT = 6 };
 enum { MGX_DTYPE_F32 = 0, MGX_DTYPE_F64 = 1, MGX_DTYPE_MIXED = 2 };
 enum { MGX_SCHEDULE_V = 0, MGX_SCHEDULE_FMG = 1 };
 enum { MGX_RESTRICT_CONSISTENT = 0, MGX_RESTRICT_FW16 = 1,
@@ -63,7 +78,7 @@ enum { MGX_RESTRICT_CONSISTENT = 0, MGX_RESTRICT_FW16 = 1,
  * general five-point operator PER LEVEL (A_sp_dict[level]) given by the caller as five coefficient grids
  * (mgx_set_stencil) or re-discretised from a nodal coefficient a(x, y) of -div(a grad u) (mgx_set_coefficient),
  * smoothed in MF's form  v <- R_omega v + omega D^-1 b  (MF:86-93), residual b - A v (MF:150-153), direct solve of
- * the coarsest operator (MF:63-72: dense inverse; coarsest_level <= 5).  dtype F64 / F32, Jacobi or Chebyshev, one GPU.
+ * the coarsest operator (MF:63-72: dense inverse; coarsest_level <= 5).  dtype F64 / F32, Jacobi, Chebyshev or a line smoother, one GPU.
  * Algorithmic bytes per point and sweep: 8 sizeof(T) (v, b, D_inv, four R arrays in; v' out). */
 enum { MGX_OPERATOR_POISSON = 0, MGX_OPERATOR_STENCIL5 = 1,
        /* GALERKIN: the variational hierarchy.  The finest level is a general five-point operator given as for STENCIL5;
@@ -249,6 +264,20 @@ MGX_API int mgx_get_prolongation(mgx_handle h, int level, int which, void* dst, 
  * 2 exactly for the constant Poisson stencil.  MGX_ERR_STATE before the level's operator exists (before mgx_set_stencil
  * on a STENCIL5 level, before the build on a GALERKIN handle) and on a handle with op = MGX_OPERATOR_POISSON. */
 MGX_API int mgx_get_lambda_max(mgx_handle h, int level, double* out);
+
+/* ---- the tridiagonal factors of a line smoother (csrc/mgx_line.hpp) ----------------------------------------------
+ * dir = 0: the x-lines (grid rows, T = tridiag(w, c, e)), 1: the y-lines (grid columns, T = tridiag(n, c, s));
+ * which = 0: m, the reciprocal pivots  m_0 = 1 / c_0, m_j = 1 / (c_j - w_j g_{j-1});  1: g_j = e_j m_j (0 at the line's last
+ * point).  Host layout of the level (n x n interior, row-major, element (i, j) belongs to grid point (i + 1, j + 1) in
+ * either direction), the handle's working type.  Built on the device whenever the level's operator is (re)built.
+ * MGX_ERR_STATE before the level's operator exists, on a handle whose smoother has no lines in that direction and on
+ * handles without a line smoother. */
+MGX_API int mgx_get_line_factor(mgx_handle h, int level, int dir, int which, void* dst, size_t count);
+/* how the y-line kernel cuts the columns of `level`: rows per chunk (max(64, ceil((N - 1) / 16)) unless MGX_LINE_CHUNK=<rows>
+ * was set when the handle was created; never fewer than ceil((N - 1) / 16)) and the number of chunks, ceil((N - 1) / rows);
+ * one chunk: the plain recurrence.  All chunks of a 64-column strip run in one workgroup (at most 16).  MGX_ERR_STATE on
+ * handles whose smoother has no y-lines. */
+MGX_API int mgx_get_line_chunks(mgx_handle h, int level, int* rows, int* chunks);
 
 /* ---- grid operators (one call = the reference function named) ------------
  * On a dtype MIXED handle the finest level holds double data for the accessors above and a

@@ -22,6 +22,8 @@ LIB_PATH = os.environ.get("MGX_LIBMGX_PATH") or os.path.join(_HERE, "libmgx.so")
 
 SMOOTHER_JACOBI, SMOOTHER_RBGS = 0, 1
 SMOOTHER_CHEBYSHEV = 2      # Chebyshev polynomial smoother of the general-operator hierarchies (mu1 / mu2: degrees)
+# zebra line Gauss-Seidel of the general-operator hierarchies: x-lines, y-lines, x then y (3 is not a smoother)
+SMOOTHER_LINE_X, SMOOTHER_LINE_Y, SMOOTHER_LINE_ALT = 4, 5, 6
 DTYPE_F32, DTYPE_F64, DTYPE_MIXED = 0, 1, 2
 SCHEDULE_V, SCHEDULE_FMG = 0, 1
 RESTRICT_CONSISTENT, RESTRICT_FW16, RESTRICT_INJECT, RESTRICT_INJECT4 = 0, 1, 2, 3
@@ -49,7 +51,7 @@ EXPORTS = [
     "mgx_create_rank", "mgx_dist_exchanges", "mgx_dist_overlapped", "mgx_memcpy_d2h", "mgx_memcpy_h2d", "mgx_runtime_libs",
     "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg",
     "mgx_build_galerkin", "mgx_get_stencil9",
-    "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max",
+    "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max", "mgx_get_line_factor", "mgx_get_line_chunks",
     "mgx_set_cycle", "mgx_get_cycle",
 ]
 MAX_GPUS = 16
@@ -207,6 +209,8 @@ def lib() -> C.CDLL:
     L.mgx_get_transfer.argtypes = [vp, ip]
     L.mgx_get_prolongation.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.mgx_get_lambda_max.argtypes = [vp, C.c_int, dp]
+    L.mgx_get_line_factor.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
+    L.mgx_get_line_chunks.argtypes = [vp, C.c_int, ip, ip]
     L.mgx_set_cycle.argtypes = [vp, C.c_int]
     L.mgx_get_cycle.argtypes = [vp, ip]
     _lib = L
@@ -454,6 +458,20 @@ class Multigrid:
         out = C.c_double()
         self._chk(lib().mgx_get_lambda_max(self._h, level, C.byref(out)), "mgx_get_lambda_max")
         return out.value
+
+    def line_factor(self, level, dir, which):
+        """a factor of the level's tridiagonal line systems (mgx_get_line_factor): dir 0 x-lines, 1 y-lines; which 0 m
+        (reciprocal pivots), 1 g; n x n in the level's working type"""
+        n = (1 << level) - 1
+        a = np.empty((n, n), dtype=self.level_dtype(level))
+        self._chk(lib().mgx_get_line_factor(self._h, level, dir, which, a.ctypes.data, a.size), "mgx_get_line_factor")
+        return a
+
+    def line_chunks(self, level):
+        """(rows per chunk, chunks) of the y-line kernel's columns on a level (mgx_get_line_chunks)"""
+        rows, chunks = C.c_int(), C.c_int()
+        self._chk(lib().mgx_get_line_chunks(self._h, level, C.byref(rows), C.byref(chunks)), "mgx_get_line_chunks")
+        return rows.value, chunks.value
 
     def set_cycle(self, cycle):
         """CYCLE_V / CYCLE_W / CYCLE_F: the kind of every cycle the handle runs from here on (vcycle, vcycle_zero, solve,

@@ -19,6 +19,7 @@
 #include "mgx_galerkin.hpp"
 #include "mgx_opdep.hpp"
 #include "mgx_cheby.hpp"
+#include "mgx_line.hpp"
 #include "mgx_small.hpp"
 #include "mgx_krylov.hpp"
 #include "mgx_dist_plan.hpp"
@@ -67,6 +68,11 @@ struct Level {
     // only) and, for either smoother, the bound g_l of the spectrum of D^-1 A of the level's current operator
     void* cheb = nullptr;
     double lambda_g = 0.0;
+    // MGX_SMOOTHER_LINE_* (mgx_line.hpp): the Thomas factors m, g of the level's x-lines [0] and y-lines [1] and the
+    // homogeneous factors hf, hb of k_line_y's chunks of line_R rows; allocated at create for the directions the handle
+    // smooths in, rebuilt with the operator (line_update)
+    void *line_m[2] = {nullptr, nullptr}, *line_g[2] = {nullptr, nullptr}, *line_hf = nullptr, *line_hb = nullptr;
+    int line_R = 0;
     size_t esize() const { return f64 ? 8 : 4; }
 };
 
@@ -122,6 +128,8 @@ struct mgx_solver {
     int cycle = MGX_CYCLE_V;        // cycle index of every cycle the handle runs (mgx_set_cycle): V, W or F
     int small_visit = 1;            // W / F: one-workgroup visits of the small nine-point levels (MGX_SMALL_VISIT, mgx_small.hpp)
     int small_max_n = kSmallMaxN;   // ... of the levels with N <= this
+    int line_dirs = 0;              // MGX_SMOOTHER_LINE_*: bit 0 x-lines, bit 1 y-lines (0: another smoother)
+    int* line_flag = nullptr;       // device: bit d raised by k_line_factor on a zero or non-finite pivot in direction d
     int transfer = MGX_TRANSFER_BILINEAR;   // ... with this prolongation (mgx_build_galerkin_transfer)
     // mgx_solve_pcg (allocated by its first call): iterate x, directions p / p' (ping-pong), q = A p, the caller's b
     // while r occupies lv[finest].b, per-block partials of the Krylov passes, the device scalars and their host copy
@@ -250,7 +258,7 @@ int alloc_level(mgx_solver* s, Level& l, int level, bool f64)
 
 void free_level(Level& l)
 {
-    std::vector<void**> all = {&l.u, &l.b, &l.tmp, &l.r, &l.cheb};
+    std::vector<void**> all = {&l.u, &l.b, &l.tmp, &l.r, &l.cheb, &l.line_m[0], &l.line_m[1], &l.line_g[0], &l.line_g[1], &l.line_hf, &l.line_hb};
     for (int q = 0; q < 9; ++q) { all.push_back(&l.A[q]); all.push_back(&l.J[q]); }
     for (void*& w : l.wt) all.push_back(&w);
     for (void** p : all) {
@@ -373,6 +381,33 @@ int lambda_update(mgx_solver* s, Level& l)
     return MGX_OK;
 }
 
+template <typename T> LineLevel<T> line_level(const Level& l)
+{
+    return LineLevel<T>{op9_of<T>(l), l.nine, l.N, l.pitch, (T*)l.line_m[0], (T*)l.line_g[0], (T*)l.line_m[1], (T*)l.line_g[1],
+                        (T*)l.line_hf, (T*)l.line_hb, l.line_R};
+}
+
+// the line factors of the operator just written into l.A[] (handles with a line smoother; nothing otherwise).  A zero
+// or non-finite pivot: MGX_ERR_INVALID, naming the level and the direction
+int line_update(mgx_solver* s, Level& l)
+{
+    if (!s->line_dirs) return MGX_OK;
+    HIPCHK(s, hipMemsetAsync(s->line_flag, 0, sizeof(int), s->stream));
+    for (int d = 0; d < 2; ++d) {
+        if (!(s->line_dirs & (1 << d))) continue;
+        if (l.f64) launch_line_factor<double>(line_level<double>(l), d, s->line_flag, s->stream);
+        else launch_line_factor<float>(line_level<float>(l), d, s->line_flag, s->stream);
+    }
+    HIPCHK(s, hipGetLastError());
+    int flag = 0;
+    HIPCHK(s, hipMemcpyAsync(&flag, s->line_flag, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    if (flag)
+        return s->fail(MGX_ERR_INVALID, "MGX_SMOOTHER_LINE: zero or non-finite pivot in the tridiagonal factorisation of level " +
+                                            std::to_string(l.L) + ", direction " + ((flag & 1) ? "x" : "y"));
+    return MGX_OK;
+}
+
 // {D_inv, R_omega} of the operator in l.A[] (MF:28-32)
 template <typename T>
 void build_splitting(mgx_solver* s, const Level& l)
@@ -405,6 +440,7 @@ int var_build_t(mgx_solver* s, Level& l)
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipStreamSynchronize(s->stream));
     if (int rc = lambda_update(s, l)) return rc;
+    if (int rc = line_update(s, l)) { l.stencil_set = false; drop_graphs(s); return rc; }
     l.stencil_set = true;
     // the kernels' coefficient pointers are unchanged, but a new operator is a new problem, and the Chebyshev scalars
     // (from g_l) are kernel arguments of a captured cycle: recapture
@@ -468,6 +504,13 @@ int galerkin_build_t(mgx_solver* s, int transfer)
     HIPCHK(s, hipStreamSynchronize(s->stream));
     for (int lv = lo; lv <= hi; ++lv)
         if (int rc = lambda_update(s, s->lv[lv])) return rc;
+    for (int lv = lo; lv <= hi; ++lv)
+        if (int rc = line_update(s, s->lv[lv])) {             // as after a new finest operator: nothing below it is usable
+            for (int c = lo; c < hi; ++c) s->lv[c].stencil_set = false;
+            s->gal_built = false;
+            drop_graphs(s);
+            return rc;
+        }
     for (int lv = lo; lv <= hi; ++lv) s->lv[lv].stencil_set = true;
     s->gal_built = true;
     s->transfer = transfer;
@@ -531,10 +574,21 @@ void smooth_cheby_t(mgx_solver* s, Level& l, int mu)
     s->last_smooth_launches = mu;
 }
 
+// mu zebra line sweeps (mgx_line.hpp), two launches per sweep and direction, u in place: no swap
+template <typename T>
+void smooth_line_t(mgx_solver* s, Level& l, int mu)
+{
+    const LineLevel<T> ll = line_level<T>(l);
+    int launches = 0;
+    for (int i = 0; i < mu; ++i) launches += launch_line_sweep<T>(ll, (T*)l.u, (const T*)l.b, s->line_dirs, s->stream);
+    s->last_smooth_launches = launches;
+}
+
 // the level smoother of a general-operator handle
 void smooth_var(mgx_solver* s, Level& l, int mu)
 {
-    if (s->cfg.smoother == MGX_SMOOTHER_CHEBYSHEV) { if (l.f64) smooth_cheby_t<double>(s, l, mu); else smooth_cheby_t<float>(s, l, mu); }
+    if (s->line_dirs) { if (l.f64) smooth_line_t<double>(s, l, mu); else smooth_line_t<float>(s, l, mu); }
+    else if (s->cfg.smoother == MGX_SMOOTHER_CHEBYSHEV) { if (l.f64) smooth_cheby_t<double>(s, l, mu); else smooth_cheby_t<float>(s, l, mu); }
     else if (l.f64) smooth_var_t<double>(s, l, mu);       // MF:75-96
     else smooth_var_t<float>(s, l, mu);
 }
@@ -724,7 +778,8 @@ void smooth(mgx_solver* s, int level, int mu)
     if (s->var) smooth_var(s, l, mu);
     else smooth_t(s, l, mu);
     p.set(s->last_smooth_launches, mu);
-    if (fine) s->fine_updates += (double)mu * (double)(l.N - 1) * (double)(l.N - 1);
+    // one update per point and sweep; an alternating line sweep is an x- and a y-sweep
+    if (fine) s->fine_updates += (double)(s->line_dirs == 3 ? 2 * mu : mu) * (double)(l.N - 1) * (double)(l.N - 1);
 }
 
 // B[level-1] = R (B - A U)[level]  (fused = true)  or  R B[level]  (fused = false)
@@ -1331,7 +1386,7 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     // in both precisions; level 8 (255^2) bounds the dense sine-transform solve.
     if (cfg->coarsest_level < 2 || cfg->finest_level < cfg->coarsest_level || cfg->finest_level > 15 ||
         cfg->mu0 < 0 || cfg->mu1 < 0 || cfg->mu2 < 0 || !(cfg->omega > 0.0 && cfg->omega < 2.0) ||
-        cfg->smoother < 0 || cfg->smoother > MGX_SMOOTHER_CHEBYSHEV || cfg->dtype < 0 || cfg->dtype > 2 ||
+        cfg->smoother < 0 || cfg->smoother > MGX_SMOOTHER_LINE_ALT || cfg->smoother == 3 || cfg->dtype < 0 || cfg->dtype > 2 ||
         cfg->schedule < 0 || cfg->schedule > 1 || cfg->restrict_mode < 0 || cfg->restrict_mode > MGX_RESTRICT_INJECT4 ||
         cfg->bottom < 0 || cfg->bottom > 1 || cfg->arith < 0 || cfg->arith > 1 || (cfg->op != MGX_OPERATOR_POISSON && cfg->op != MGX_OPERATOR_STENCIL5 && cfg->op != MGX_OPERATOR_GALERKIN)) {
         g_create_error = "invalid configuration";
@@ -1347,6 +1402,11 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     const bool cheby = (cfg->smoother == MGX_SMOOTHER_CHEBYSHEV);
     if (cheby && !var) {
         g_create_error = "MGX_SMOOTHER_CHEBYSHEV: op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN only (the constant stencil has its fused and folded passes)";
+        return MGX_ERR_INVALID;
+    }
+    const bool line = (cfg->smoother >= MGX_SMOOTHER_LINE_X);
+    if (line && (!var || cfg->dtype == MGX_DTYPE_MIXED || cfg->arith != MGX_ARITH_SEPARATE || cfg->n_gpus > 1)) {
+        g_create_error = "MGX_SMOOTHER_LINE_X / LINE_Y / LINE_ALT: op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN, dtype F64 or F32, arith SEPARATE, one GPU";
         return MGX_ERR_INVALID;
     }
     if (var && (cfg->dtype == MGX_DTYPE_MIXED || cfg->smoother == MGX_SMOOTHER_RBGS || cfg->arith != MGX_ARITH_SEPARATE || cfg->n_gpus > 1)) {
@@ -1386,6 +1446,7 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     s->use_zero_in = env_int("MGX_ZERO_IN", 1);
     s->use_graph = env_int("MGX_GRAPH", 1);
     s->small_visit = env_int("MGX_SMALL_VISIT", 1);
+    s->line_dirs = cfg->smoother == MGX_SMOOTHER_LINE_X ? 1 : cfg->smoother == MGX_SMOOTHER_LINE_Y ? 2 : cfg->smoother == MGX_SMOOTHER_LINE_ALT ? 3 : 0;
     int rc = MGX_OK;
     auto bail = [&](int code) { g_create_error = s->err; mgx_destroy(s); return code; };
     if (hipStreamCreate(&s->stream) != hipSuccess) { s->err = "hipStreamCreate failed"; return bail(MGX_ERR_HIP); }
@@ -1416,7 +1477,22 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
                 if (hipMalloc(&lv.cheb, lv.bytes) != hipSuccess) { s->err = "hipMalloc failed for the Chebyshev direction array"; return bail(MGX_ERR_ALLOC); }
                 if (hipMemsetAsync(lv.cheb, 0, lv.bytes, s->stream) != hipSuccess) { s->err = "hipMemsetAsync failed"; return bail(MGX_ERR_HIP); }
             }
+            if (line) {
+                // the line factors; zeroed once: their ring and padding are never written.  hf / hb: k_line_y's levels of
+                // more than one chunk only (MGX_LINE_CHUNK=<rows> overrides the launcher's rows per chunk)
+                Level& lv = s->lv[l];
+                lv.line_R = line_chunk_rows(lv.N, env_int("MGX_LINE_CHUNK", 0));
+                std::vector<void**> arrays;
+                for (int d = 0; d < 2; ++d)
+                    if (s->line_dirs & (1 << d)) { arrays.push_back(&lv.line_m[d]); arrays.push_back(&lv.line_g[d]); }
+                if ((s->line_dirs & 2) && line_chunks(lv.N, lv.line_R) > 1) { arrays.push_back(&lv.line_hf); arrays.push_back(&lv.line_hb); }
+                for (void** p : arrays) {
+                    if (hipMalloc(p, lv.bytes) != hipSuccess) { s->err = "hipMalloc failed for the line smoother's factor arrays"; return bail(MGX_ERR_ALLOC); }
+                    if (hipMemsetAsync(*p, 0, lv.bytes, s->stream) != hipSuccess) { s->err = "hipMemsetAsync failed"; return bail(MGX_ERR_HIP); }
+                }
+            }
         }
+        if (line && hipMalloc(&s->line_flag, sizeof(int)) != hipSuccess) { s->err = "hipMalloc failed for the line smoother's breakdown flag"; return bail(MGX_ERR_ALLOC); }
         if (cfg->bottom == MGX_BOTTOM_EXACT) {
             const size_t NN = (size_t)((1 << cfg->coarsest_level) - 1) * ((1 << cfg->coarsest_level) - 1);
             if (hipMalloc(&s->var_M, NN * NN * sizeof(double)) != hipSuccess || hipMalloc(&s->var_inv, NN * NN * sizeof(double)) != hipSuccess ||
@@ -1467,6 +1543,7 @@ int mgx_destroy(mgx_handle s)
     s->bottom.destroy();
     if (s->partial) (void)hipFree(s->partial);
     if (s->sum_dev) (void)hipFree(s->sum_dev);
+    if (s->line_flag) (void)hipFree(s->line_flag);
     if (s->sum_host) (void)hipHostFree(s->sum_host);
     for (double* p : {s->var_M, s->var_inv, s->var_pm, s->var_pi}) if (p) (void)hipFree(p);
     for (void* p : {s->pcg_x, s->pcg_p[0], s->pcg_p[1], s->pcg_q, s->pcg_b, (void*)s->pcg_part, (void*)s->pcg_sc}) if (p) (void)hipFree(p);
@@ -1731,6 +1808,30 @@ int mgx_get_lambda_max(mgx_handle s, int level, double* out)
     if (s->galerkin && !s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
     if (!s->lv[level].stencil_set) return s->fail(MGX_ERR_STATE, "operator of this level not set");
     *out = s->lv[level].lambda_g;
+    return MGX_OK;
+}
+
+int mgx_get_line_factor(mgx_handle s, int level, int dir, int which, void* dst, size_t count)
+{
+    if (!s || !dst) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (!s->line_dirs) return s->fail(MGX_ERR_STATE, "handle was not created with a line smoother (MGX_SMOOTHER_LINE_X / LINE_Y / LINE_ALT)");
+    if (!level_ok(s, level) || dir < 0 || dir > 1 || which < 0 || which > 1) return s->fail(MGX_ERR_INVALID, "level, direction or array selector out of range");
+    if (!(s->line_dirs & (1 << dir))) return s->fail(MGX_ERR_STATE, dir == 0 ? "the handle's smoother has no x-lines (MGX_SMOOTHER_LINE_Y)" : "the handle's smoother has no y-lines (MGX_SMOOTHER_LINE_X)");
+    if (s->galerkin && !s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
+    if (!s->lv[level].stencil_set) return s->fail(MGX_ERR_STATE, "operator of this level not set");
+    Level& l = s->lv[level];
+    return copy_out(s, l, which == 0 ? l.line_m[dir] : l.line_g[dir], dst, count);
+}
+
+int mgx_get_line_chunks(mgx_handle s, int level, int* rows, int* chunks)
+{
+    if (!s || !rows || !chunks) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (!(s->line_dirs & 2)) return s->fail(MGX_ERR_STATE, "the handle's smoother has no y-lines (MGX_SMOOTHER_LINE_Y / LINE_ALT)");
+    if (!level_ok(s, level)) return s->fail(MGX_ERR_INVALID, "level out of range");
+    *rows = s->lv[level].line_R;
+    *chunks = line_chunks(s->lv[level].N, s->lv[level].line_R);
     return MGX_OK;
 }
 
@@ -2296,6 +2397,10 @@ int mgx_create_rank(const mgx_config* cfg, int rank, int world, const void* rccl
         g_create_error = "MGX_SMOOTHER_CHEBYSHEV: single-GPU handles of op = MGX_OPERATOR_STENCIL5 / MGX_OPERATOR_GALERKIN only";
         return MGX_ERR_INVALID;
     }
+    if (cfg->smoother >= MGX_SMOOTHER_LINE_X && cfg->smoother <= MGX_SMOOTHER_LINE_ALT) {
+        g_create_error = "MGX_SMOOTHER_LINE_X / LINE_Y / LINE_ALT: single-GPU handles of op = MGX_OPERATOR_STENCIL5 / MGX_OPERATOR_GALERKIN only";
+        return MGX_ERR_INVALID;
+    }
     if (cfg->coarsest_level < 2 || cfg->finest_level < cfg->coarsest_level || cfg->finest_level > 15 ||
         cfg->mu1 < 0 || cfg->mu2 < 0 || !(cfg->omega > 0.0 && cfg->omega < 2.0) || cfg->smoother < 0 || cfg->smoother > 1 ||
         cfg->dtype < 0 || cfg->dtype > 2 || cfg->restrict_mode < 0 || cfg->restrict_mode > 1 || cfg->bottom < 0 || cfg->bottom > 1 || cfg->arith < 0 || cfg->arith > 1 ||
@@ -2395,6 +2500,10 @@ int mgx_plan_create(const mgx_config* cfg, int n_slabs, int g, int fold, int dee
     *out = nullptr;
     if (cfg->smoother == MGX_SMOOTHER_CHEBYSHEV) {
         g_plan_error = "MGX_SMOOTHER_CHEBYSHEV: the slab plan runs the constant stencil (Jacobi or red-black GS) only";
+        return MGX_ERR_INVALID;
+    }
+    if (cfg->smoother >= MGX_SMOOTHER_LINE_X && cfg->smoother <= MGX_SMOOTHER_LINE_ALT) {
+        g_plan_error = "MGX_SMOOTHER_LINE_X / LINE_Y / LINE_ALT: the slab plan runs the constant stencil (Jacobi or red-black GS) only";
         return MGX_ERR_INVALID;
     }
     const int cut = dist_cut_level(*cfg, n_slabs);

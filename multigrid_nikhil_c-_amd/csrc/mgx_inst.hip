@@ -6,12 +6,15 @@
 //   -DMGX_INST_KIND=3  launch_tile_pass<T, SM, AR>  (all six (PRE, POST) pairs of k_tile_smooth and k_tile_wide)
 //   -DMGX_INST_KIND=4  launch_cheby<T>, launch_lambda_max<T>  (mgx_cheby.hpp: k_cheby_var, k_lambda_partials)
 //   -DMGX_INST_KIND=5  launch_small_visit<T>, small_visit_prepare<T>  (mgx_small.hpp: k_small_visit)
+//   -DMGX_INST_KIND=6  launch_line_factor<T>, launch_line_sweep<T>  (mgx_line.hpp: k_line_factor, k_line_x, k_line_y)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
 #include "mgx_cheby.hpp"
 #elif MGX_INST_KIND == 5
 #include "mgx_small.hpp"
+#elif MGX_INST_KIND == 6
+#include "mgx_line.hpp"
 #endif
 
 namespace mgx {
@@ -39,7 +42,10 @@ template void launch_lambda_max<T_>(const VarLevel<T_>&, double*, long, double*,
 #elif MGX_INST_KIND == 5
 template hipError_t small_visit_prepare<T_>();
 template void launch_small_visit<T_>(const SmallVisit<T_>&, hipStream_t);
+#elif MGX_INST_KIND == 6
+template void launch_line_factor<T_>(const LineLevel<T_>&, int, int*, hipStream_t);
+template int launch_line_sweep<T_>(const LineLevel<T_>&, T_*, const T_*, int, hipStream_t);
 #else
-#error "MGX_INST_KIND must be 1, 2, 3, 4 or 5"
+#error "MGX_INST_KIND must be 1 .. 6"
 #endif
 } // namespace mgx

@@ -23,7 +23,16 @@ rocprofv3 --kernel-trace --stats run.
 contrast 10, 511^2 contrast 100 and 1000, both transfers, Jacobi V(2,2) sweeps) with the cycle index set by
 mgx_set_cycle: cycles and median-of-5 time to 1e-8 of mgx_solve and mgx_solve_pcg.  MGX_SMALL_VISIT=0 in the environment:
 the W- and F-cycles through the per-level launches only.  --cycle w --trace-only: one solve of that kind at 511^2
-contrast 1000 (OPERATOR) only, for a rocprofv3 --kernel-trace --stats run."""
+contrast 1000 (OPERATOR) only, for a rocprofv3 --kernel-trace --stats run.
+--smoother {line_x,line_y,line_alt}: instead, the tables of profiles/line_kernel_trace_summary.md.  The zebra line
+kernels k_line_x / k_line_y<T, 5 | 9> (csrc/mgx_line.hpp) at 4096^2 next to k_jacobi_var<T, 5 | 9> in the same process:
+ms per colour launch (a sweep is two) and bytes/s over the algorithmic bytes stated in mgx_line.hpp (11 / 15 sizeof(T)
+per updated point on five- / nine-point levels, 15 / 19 for k_line_y on a level cut into chunks; a colour launch updates
+half the level); k_line_y both with the launcher's chunks and with MGX_LINE_CHUNK set to the whole column.  Then, with
+--aniso EPS[,layers] (default 1e-2: the x-strong problem c = 2(1 + EPS), w = e = -1, n = s = -EPS; ",layers": x-strong in
+the upper half, y-strong in the lower half), cycles and median-of-5 time to 1e-8 at 2047^2, levels 11..5, right-hand side
+default_rng(3).uniform(-1, 1): the line smoother's V(1,1) against Jacobi V(2,2), mgx_solve and mgx_solve_pcg each.
+--smoother line_x --trace-only: five sweeps per level and type only, for a rocprofv3 --kernel-trace --stats run."""
 import os
 import statistics
 import sys
@@ -242,6 +251,96 @@ def smoother_kernels():
             print(f"{kname('k_cheby_', tag, 'T')} / {kname('k_jacobi_', tag, 'T')} bytes/s, {name}: {r:.3f} (accepted: >= 0.9{'' if r >= 0.9 else ': NOT MET'})")
 
 
+LINE = {"line_x": pkg.SMOOTHER_LINE_X, "line_y": pkg.SMOOTHER_LINE_Y, "line_alt": pkg.SMOOTHER_LINE_ALT}
+
+
+def line_kernels(which):
+    """which: line_x, line_y or line_alt (both kernels)"""
+    n = (1 << LK) - 1
+    x = np.linspace(0.0, 1.0, (1 << LF) + 1)
+    a = 1.0 + 0.8 * np.sin(3 * np.pi * x)[None, :] * np.cos(2 * np.pi * x)[:, None]
+    rng = np.random.default_rng(0)
+    u, b = rng.uniform(-1, 1, (n, n)), rng.uniform(-1, 1, (n, n))
+    chunked = (1 << LK) > 64                               # the launcher cuts the columns of this level (line_chunk_rows)
+    if not TRACE_ONLY:
+        print("| kernel | grid | dtype | ms per launch | bytes per updated point | points per launch | achieved GB/s | fraction of the 8 TB/s HBM peak |")
+        print("|---|---|---|---|---|---|---|---|")
+    rate = {}
+    sweeps = 20
+    runs = [("k_jacobi_", pkg.SMOOTHER_JACOBI, None)]
+    if which in ("line_x", "line_alt"):
+        runs.append(("k_line_x", pkg.SMOOTHER_LINE_X, None))
+    if which in ("line_y", "line_alt"):
+        runs += [("k_line_y", pkg.SMOOTHER_LINE_Y, None), ("k_line_y", pkg.SMOOTHER_LINE_Y, str(1 << LF))]
+    for dtype, name, es in ((pkg.DTYPE_F64, "f64", 8), (pkg.DTYPE_F32, "f32", 4)):
+        for op, tag, finest in ((pkg.OPERATOR_STENCIL5, "var", LK), (pkg.OP_GALERKIN, "var9", LF)):
+            nq = 9 if tag == "var9" else 5
+            for prefix, sm, chunk in runs:
+                if chunk is None:
+                    os.environ.pop("MGX_LINE_CHUNK", None)
+                else:
+                    os.environ["MGX_LINE_CHUNK"] = chunk      # read at mgx_create: the whole column as one chunk
+                with pkg.Multigrid(finest_level=finest, coarsest_level=5, mu1=2, mu2=2, schedule=pkg.SCHEDULE_V, op=op, dtype=dtype, omega=0.8,
+                                   smoother=sm) as mg:
+                    os.environ.pop("MGX_LINE_CHUNK", None)
+                    if op == pkg.OP_GALERKIN:
+                        mg.set_coefficient(a)
+                        mg.build_galerkin()
+                    else:
+                        mg.set_coefficient(a[::2, ::2])
+                    mg.set_level(LK, pkg.VEC_U, u)
+                    mg.set_level(LK, pkg.VEC_B, b)
+                    mg.smooth(LK, 2)
+                    if TRACE_ONLY:
+                        mg.smooth(LK, 5)
+                        continue
+                    ms = wall(lambda: mg.smooth(LK, sweeps), reps=5) / sweeps
+                    if sm == pkg.SMOOTHER_JACOBI:
+                        words, launches, label = (8 if nq == 5 else 12), 1, kname(prefix, tag, name)
+                    else:
+                        cut = prefix == "k_line_y" and chunked and chunk is None
+                        words, launches = (11 if nq == 5 else 15) + (4 if cut else 0), 2
+                        label = f"{prefix}<{name}, {nq}>" + ("" if prefix == "k_line_x" else " (launcher's chunks)" if cut else " (one chunk per column)")
+                    ms /= launches
+                    gbs = words * es * (n * n / launches) / (ms * 1e-3) / 1e9
+                    rate[(label, tag, name)] = gbs
+                    print(f"| {label} | {1 << LK}^2 | {name} | {ms:.4f} | {words * es} | 1/{launches} of the level | {gbs:.0f} | {gbs / 8000:.3f} |", flush=True)
+    if TRACE_ONLY:
+        return
+    print()
+    for (label, tag, name), gbs in rate.items():
+        if label.startswith("k_jacobi_"):
+            continue
+        r = gbs / rate[(kname("k_jacobi_", tag, name), tag, name)]
+        print(f"{label} / {kname('k_jacobi_', tag, name)} bytes/s: {r:.3f}{'' if r >= 0.5 else ' (BELOW HALF: open item)'}")
+
+
+def aniso_solves(which, eps, layers):
+    import line_ref
+    L = 9 if QUICK else 11
+    n = (1 << L) - 1
+    st5 = line_ref.aniso_stencil(L, eps, "layers" if layers else "x")
+    b = np.random.default_rng(3).uniform(-1, 1, (n, n))
+    what = f"layers, eps = {eps:g}" if layers else f"x-strong, eps = {eps:g}"
+    print(f"\n| {n}^2, {what}, levels {L}..5, f64, BILINEAR | mgx_solve (cap 100 cycles) | mgx_solve_pcg (cap 300 iterations) |\n|---|---|---|")
+    for label, sm, mu in ((f"{which} V(1,1)", LINE[which], 1), ("Jacobi V(2,2), omega = 2/3", pkg.SMOOTHER_JACOBI, 2)):
+        with pkg.Multigrid(finest_level=L, coarsest_level=5, mu1=mu, mu2=mu, schedule=0, op=pkg.OP_GALERKIN, smoother=sm) as mg:
+            mg.set_stencil(L, *st5)
+            mg.build_galerkin()
+            mg.set_rhs(b)
+            cells = []
+            for f in (lambda: mg.solve(tol=1e-8, max_cycles=100), lambda: mg.solve_pcg(tol=1e-8, max_iters=300)):
+                ts = []
+                for rep in range(6):                    # the first run captures the graphs: not timed
+                    mg.set_guess(np.zeros((n, n)))
+                    st, hist = f()
+                    if rep:
+                        ts.append(st.seconds * 1e3)
+                cells.append(f"{st.cycles} {'it' if len(cells) else 'cycles'}, {statistics.median(ts):.2f} ms (min {min(ts):.2f}, max {max(ts):.2f}), "
+                             f"converged {st.converged}, residual ratio {hist[-1] / hist[0]:.1e}")
+            print(f"| {label} | {cells[0]} | {cells[1]} |", flush=True)
+
+
 CYCLES = {"v": pkg.CYCLE_V, "w": pkg.CYCLE_W, "f": pkg.CYCLE_F}
 
 
@@ -299,8 +398,17 @@ if __name__ == "__main__":
             smoother_solves("jacobi", kind)
     elif "--smoother" in sys.argv:
         which = sys.argv[sys.argv.index("--smoother") + 1]
+        if which in LINE:
+            if "--aniso" in sys.argv:
+                spec = sys.argv[sys.argv.index("--aniso") + 1].split(",")
+                aniso_solves(which, float(spec[0]), "layers" in spec[1:])
+            else:
+                line_kernels(which)
+                if not TRACE_ONLY:
+                    aniso_solves(which, 1e-2, which == "line_alt")
+            sys.exit(0)
         if which not in ("jacobi", "chebyshev"):
-            sys.exit("--smoother jacobi or --smoother chebyshev")
+            sys.exit("--smoother jacobi, chebyshev, line_x, line_y or line_alt")
         if which == "chebyshev":
             smoother_kernels()
         if not TRACE_ONLY:
