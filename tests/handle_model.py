@@ -13,15 +13,25 @@ the exact bottom solve of the POISSON hierarchy (sine transform: tests/test_gpu_
 float ulps; the model uses the oracle's sine-transform mode, the device's method in the device's order).
 
 fine_updates follows include/mgx.h: finest-level smoother point updates (mu n^2 per block of mu sweeps or of degree
-mu), counted from the start of the last solve / solve_pcg."""
+mu, 2 mu n^2 per block of alternating line sweeps), counted from the start of the last solve / solve_pcg.
+
+The cycle index (mgx_set_cycle) is an attribute the composed vcycle() reads: the recursion of include/mgx.h from the
+same single operators, held to tests/wcycle_ref.py bit for bit.  The zebra line smoothers (cfg.smoother 4 / 5 / 6) run
+through tests/line_ref.py; the device joins a line's carries in another order, so calls that smooth are compared to a
+bound there (tests/test_gpu_handle_state.py), for which the model can be instantiated a second time in np.longdouble
+(real=np.longdouble: line_ref.NumpyOps in place of the oracle, the operators cast from the working type)."""
 import numpy as np
 
 import cheby_ref
 import galerkin_ref as gr
+import line_ref as lr
 import opdep_ref as od
 import pcg_ref
 
 JACOBI, RBGS, CHEBYSHEV = 0, 1, 2
+LINE_X, LINE_Y, LINE_ALT = lr.LINE_X, lr.LINE_Y, lr.LINE_ALT
+LINES = (LINE_X, LINE_Y, LINE_ALT)
+CYCLE_V, CYCLE_W, CYCLE_F = 0, 1, 2            # mgx_set_cycle
 F32, F64, MIXED = 0, 1, 2
 V, FMG = 0, 1
 CONSISTENT, FW16 = 0, 1
@@ -97,28 +107,46 @@ def _shared_inverse(h):
         h._inv = _INVERSES[key]
 
 
+def operator5(po, level, kind, dt):
+    """the five-point operators of tests/test_line_cpu.py by name (imported late: that module needs scipy)"""
+    from test_line_cpu import operator5 as op5
+    return op5(po, level, kind, dt)
+
+
 class HandleModel:
-    def __init__(self, po, **cfg):
+    def __init__(self, po, real=None, **cfg):
+        """real: the type the model computes in, when it is not the handle's own (np.longdouble: the 'exact' side of a
+        line-smoother comparison; line smoothers only - every other smoother runs through the oracle's C kernels)"""
         unknown = set(cfg) - set(DEFAULTS)
         if unknown:
             raise TypeError(f"unknown configuration fields {sorted(unknown)}")
         c = dict(DEFAULTS, **cfg)
         self.cfg = c
-        self.po = po
         self.L, self.Lc = c["finest_level"], c["coarsest_level"]
         if c["dtype"] == MIXED:
             raise ValueError("dtype MIXED keeps two finest levels: not modelled")
-        self.dt = np.float64 if c["dtype"] == F64 else np.float32
+        self.wdt = np.float64 if c["dtype"] == F64 else np.float32       # the handle's working type
+        self.dt = self.wdt if real is None else real
+        self.line = c["smoother"] in LINES
+        if self.dt is not self.wdt:
+            if not self.line:
+                raise ValueError("real= is for the line smoothers: the other smoothers are the oracle's kernels")
+        self.oracle = po                       # builds the operators, always in the working type
+        self.po = po if self.dt is self.wdt else lr.NumpyOps      # the arithmetic of the transfers, the residual and the norm
+        if self.line and c["op"] == POISSON:
+            raise ValueError("line smoothers: STENCIL5 and GALERKIN handles only")
         self.op = c["op"]
+        self.cycle = CYCLE_V
         self.U = {lv: np.zeros((self.n(lv),) * 2, dtype=self.dt) for lv in self.levels()}
         self.B = {lv: np.zeros((self.n(lv),) * 2, dtype=self.dt) for lv in self.levels()}
         self.R = {}
         self.fine_updates = 0.0
         self.st5 = None                        # GALERKIN: the finest operator, waiting for build_galerkin
+        self.stencils = None                   # STENCIL5: every level's operator
         self.transfer = None
         self.h = None
         if self.op == POISSON:
-            self.h = PoissonOps(po, self.L, self.Lc, self.dt, c["restrict_mode"], c["omega"], c["smoother"], c["arith"])
+            self.h = PoissonOps(self.po, self.L, self.Lc, self.dt, c["restrict_mode"], c["omega"], c["smoother"], c["arith"])
 
     # -- plumbing ----------------------------------------------------------------------------------------------
     def n(self, level):
@@ -154,18 +182,59 @@ class HandleModel:
         self.set_level(level, which, np.zeros((self.n(level),) * 2))
 
     # -- operator changes --------------------------------------------------------------------------------------
+    def _w(self, st5):
+        return [np.asarray(x, dtype=self.wdt) for x in st5]
+
+    def _stencil5_hierarchy(self):
+        """STENCIL5: the hierarchy of self.stencils with the configuration's smoother"""
+        c = self.cfg
+        if self.line:
+            self.h = lr.Stencil5(c["smoother"], self.po, self.stencils, self.L, self.Lc, **self._hier_args())
+            if c["bottom"] == EXACT:
+                _shared_inverse(self.h)
+        else:
+            cls = Stencil5Cheby if c["smoother"] == CHEBYSHEV else Stencil5
+            self.h = cls(self.po, self.stencils, self.L, self.Lc, **self._hier_args())
+
     def set_coefficient(self, a_nodes):
         """STENCIL5: every level re-discretised from the nodal coefficient.  GALERKIN: the finest level only, and the
         hierarchy is invalid until build_galerkin"""
         a = np.ascontiguousarray(a_nodes, dtype=np.float64)
         if self.op == STENCIL5:
-            st = {lv: self.po.stencil_from_nodes(a, lv, self.L) for lv in self.levels()}
-            cls = Stencil5Cheby if self.cfg["smoother"] == CHEBYSHEV else Stencil5
-            self.h = cls(self.po, st, self.L, self.Lc, **self._hier_args())
+            self.stencils = {lv: self._w(self.oracle.stencil_from_nodes(a, lv, self.L)) for lv in self.levels()}
+            self._stencil5_hierarchy()
         elif self.op == GALERKIN:
-            self.st5 = self.po.stencil_from_nodes(a, self.L, self.L)
+            self.st5 = self._w(self.oracle.stencil_from_nodes(a, self.L, self.L))
             self.h = None
             self.transfer = None
+        else:
+            raise RuntimeError("op = POISSON: MGX_ERR_STATE")
+
+    def set_stencil(self, level, st5):
+        """mgx_set_stencil: STENCIL5 any level (the hierarchy stands once every level has one), GALERKIN the finest only"""
+        if self.op == STENCIL5:
+            self.stencils = dict(self.stencils or {})
+            self.stencils[level] = self._w(st5)
+            self.h = None
+            if all(lv in self.stencils for lv in self.levels()):
+                self._stencil5_hierarchy()
+        elif self.op == GALERKIN and level == self.L:
+            self.st5 = self._w(st5)
+            self.h = None
+            self.transfer = None
+        else:
+            raise RuntimeError("MGX_ERR_STATE")
+
+    def set_operator(self, kind):
+        """a named operator of tests/test_line_cpu.py (operator5).  STENCIL5: set_stencil on every level.  GALERKIN:
+        set_stencil on the finest level, then build_galerkin with the transfer in use (BILINEAR at first)"""
+        if self.op == STENCIL5:
+            for lv in self.levels():
+                self.set_stencil(lv, operator5(self.oracle, lv, kind, self.wdt))
+        elif self.op == GALERKIN:
+            transfer = BILINEAR if self.transfer is None else self.transfer
+            self.set_stencil(self.L, operator5(self.oracle, self.L, kind, self.wdt))
+            self.build_galerkin(transfer)
         else:
             raise RuntimeError("op = POISSON: MGX_ERR_STATE")
 
@@ -173,14 +242,26 @@ class HandleModel:
         if self.op != GALERKIN or self.st5 is None:
             raise RuntimeError("MGX_ERR_STATE")
         cheb = self.cfg["smoother"] == CHEBYSHEV
-        if transfer == OPERATOR:
-            cls = cheby_ref.OpdepHierarchy if cheb else od.Hierarchy
+        if self.line:
+            cls = lr.OpdepHierarchy if transfer == OPERATOR else lr.Hierarchy
+            self.h = cls(self.cfg["smoother"], self.po, self.st5, self.L, self.Lc, **self._hier_args())
         else:
-            cls = cheby_ref.Hierarchy if cheb else gr.Hierarchy
-        self.h = cls(self.po, self.st5, self.L, self.Lc, **self._hier_args())
+            if transfer == OPERATOR:
+                cls = cheby_ref.OpdepHierarchy if cheb else od.Hierarchy
+            else:
+                cls = cheby_ref.Hierarchy if cheb else gr.Hierarchy
+            self.h = cls(self.po, self.st5, self.L, self.Lc, **self._hier_args())
         self.transfer = transfer
         if self.cfg["bottom"] == EXACT:
             _shared_inverse(self.h)
+
+    def set_cycle(self, kind):
+        """mgx_set_cycle: the kind of every cycle from here on; it survives build_galerkin and set_coefficient"""
+        if self.op == POISSON:
+            raise RuntimeError("op = POISSON handles run V-cycles only: MGX_ERR_STATE")
+        if kind not in (CYCLE_V, CYCLE_W, CYCLE_F):
+            raise ValueError("MGX_ERR_INVALID")
+        self.cycle = kind
 
     # -- transfers of the current hierarchy --------------------------------------------------------------------
     def _R(self, level, r):
@@ -197,10 +278,11 @@ class HandleModel:
 
     # -- single operators --------------------------------------------------------------------------------------
     def smooth(self, level, mu):
-        """mu Jacobi or red-black Gauss-Seidel sweeps, or one Chebyshev block of degree mu"""
+        """mu Jacobi, red-black Gauss-Seidel or zebra line sweeps, or one Chebyshev block of degree mu"""
         self.U[level] = self._ops().smooth(level, self.U[level], self.B[level], mu)
         if level == self.L:
-            self.fine_updates += float(mu) * float(self.n(level)) * float(self.n(level))
+            per_sweep = 2 if self.cfg["smoother"] == LINE_ALT else 1       # an alternating sweep is an x- and a y-sweep
+            self.fine_updates += float(per_sweep * mu) * float(self.n(level)) * float(self.n(level))
 
     def residual(self, level):
         self.R[level] = self._ops().residual(level, self.U[level], self.B[level])
@@ -234,8 +316,12 @@ class HandleModel:
         self.U[self.Lc] = self._ops().bottom(self.B[self.Lc])
 
     # -- schedules, composed from the operators above ----------------------------------------------------------
-    def vcycle(self, level=None):
+    def vcycle(self, level=None, kind=None):
+        """one cycle of the handle's kind (include/mgx.h, mgx_set_cycle): pre-smooth, restrict; visit level - 1; W and
+        F: if level - 1 is above the coarsest, visit it again (W: a W-cycle, F: a V-cycle) from the U the first visit
+        left, with the same B; correct, post-smooth.  The coarsest level is visited once per descent"""
         level = self.L if level is None else level
+        kind = self.cycle if kind is None else kind
         c = self.cfg
         if level == self.Lc:
             if c["bottom"] == EXACT:
@@ -246,7 +332,9 @@ class HandleModel:
             return
         self.smooth(level, c["mu1"])
         self.restrict(level)
-        self.vcycle(level - 1)
+        self.vcycle(level - 1, kind)
+        if kind != CYCLE_V and level - 1 > self.Lc:
+            self.vcycle(level - 1, CYCLE_V if kind == CYCLE_F else kind)
         self.prolong_add(level)
         self.smooth(level, c["mu2"])
 

@@ -28,11 +28,32 @@ What is compared, and how:
     test_gpu_operators.py's fp32 norm; mgx_solve_pcg to RTOL64 (+ 1e-14 ||r0||) / RTOL32 of test_gpu_pcg.py.
   * stats.cycles, stats.converged, stats.fine_updates: equal to the model's.
 
+CYCLE_CASES add the cycle index (mgx_set_cycle, csrc/mgx_small.hpp) to the sequences: the graph key carries no cycle
+kind (the setter drops the graphs), k_small_visit updates U in place where the per-level launches swap u / tmp, and a
+cycle may start from a small level with a non-zero U.  The model composes W and F from its single operators, so the
+state is still held bit for bit, on the coarse levels too; the Jacobi GALERKIN cases run with and without the visit
+kernel against the same model.
+
+LINE_CASES add the zebra line smoothers (csrc/mgx_line.hpp: in place, no parity flip; two factor arrays per level and
+direction, rebuilt with the operator).  The device joins a line's carries in another order than tests/line_ref.py, so a
+call that smooths (SMOOTHING) is held, on every array it writes, to THE TOLERANCE RULE of tests/test_line_cpu.py: 4 x
+the difference between the model in the working type and the model in np.longdouble, both run for this one call from
+the same state, relative to max |x|, floor 16 eps - against both models, never from device output.  Both models then
+take over the device's arrays.  No such bound may exceed RTOL64 / PCG32_STATE ("bound too loose" otherwise;
+tests/test_handle_model.py checks the committed seeds on the CPU).  A twin handle created with MGX_GRAPH=0 is held to
+the replaying one bit for bit after every call.  Measured on an MI355X, largest bound used / largest deviation of the
+device as a fraction of its bound: GALERKIN double LINE_ALT 1.29e-10 / 0.79; GALERKIN float LINE_X 2.69e-4 / 0.44;
+GALERKIN double LINE_Y with MGX_LINE_CHUNK=16 6.79e-11 / 0.68; STENCIL5 double LINE_ALT 1.95e-10 / 0.68 (histories: at
+most 4e-4 of their bound in double, 0.04 in float).  The dense coarsest solve of the CYCLE_CASES is bit for bit at
+levels 3 and 4 as it is at level 5.
+
 A failing sequence is reproduced from the seed, the step index and the calls so far, which the message carries."""
 import numpy as np
 import pytest
 
 import handle_model as hm
+from test_gpu_line import history_bound
+from test_line_cpu import rule_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +67,10 @@ K_MAX_GRAPHS = 8                           # kMaxGraphs of csrc/mgx.hip: the cap
 MUS = (0, 1, 2, 3, 5)
 GRAPH_USERS = ("solve", "solve_pcg", "vcycle_zero")
 KNOBS = ("MGX_TILE_MAX_N", "MGX_FUSE_MIN_N", "MGX_PLAN_MIN_N", "MGX_PLAN_PRE", "MGX_PLAN_POST", "MGX_GRAPH", "MGX_FOLD", "MGX_FUSE",
-         "MGX_ZERO_IN", "MGX_TILE_K", "MGX_FOLD_KMAX", "MGX_FOLD_KMAX_NOPOST", "MGX_FUSE_ROWS", "MGX_ROWS")
+         "MGX_ZERO_IN", "MGX_TILE_K", "MGX_FOLD_KMAX", "MGX_FOLD_KMAX_NOPOST", "MGX_FUSE_ROWS", "MGX_ROWS", "MGX_SMALL_VISIT", "MGX_LINE_CHUNK")
+SMOOTHING = ("smooth", "vcycle", "vcycle_zero", "fmg", "solve", "solve_pcg")      # the calls that run a smoother
+CYCLE_ORDER = (hm.CYCLE_W, hm.CYCLE_F, hm.CYCLE_V, hm.CYCLE_W, hm.CYCLE_F, hm.CYCLE_W, hm.CYCLE_V)
+SMALL_MAX_LEVEL = 6                        # kSmallMaxN = 64 of csrc/mgx_small.hpp
 # the marching kernels on every level (no register tiles); fused / folded passes from 128^2 up (MGX_FUSE_MIN_N=128, as
 # in test_gpu_solve.py::test_tuning_knobs_never_change_a_bit) with explicit pass plans for the folded blocks, V(3,2) as
 # [2,1] down and [1,1] up: levels 8 and 7 stream their blocks through folded passes, 6 and 5 take single sweeps
@@ -65,10 +89,39 @@ def coefficient(L, contrast, seed):
 
 
 # ---- the generator -------------------------------------------------------------------------------------------------
-def draw_sequence(seed, cfg, n_steps=40):
+def small_levels(cfg):
+    """the levels above the coarsest with N <= 64: where a W- or F-cycle may run k_small_visit, and from which a cycle
+    may start as its top"""
+    return list(range(cfg["coarsest_level"] + 1, min(cfg["finest_level"], SMALL_MAX_LEVEL) + 1))
+
+
+def kinds_at(calls):
+    """the cycle kind in force at every call of a drawn list"""
+    out, kind = [], hm.CYCLE_V
+    for c in calls:
+        if c[0] == "set_cycle":
+            kind = c[1]
+        out.append(kind)
+    return out
+
+
+def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_guess=False, short_solves=False, without=(), tail=()):
     """~n_steps calls, every one valid for `cfg` by construction (nothing is filtered afterwards): the three graph
     users five times each at least, an odd-launch smooth on every level at least once, the rest drawn with weights;
-    mu from MUS.  Operator changes of the general hierarchies are placed after every third graph user."""
+    mu from MUS.  Operator changes of the general hierarchies are placed after every third graph user.
+
+    Off by default (the sequences of the cases that do not ask are call for call what they were):
+    cycles       ("set_cycle", kind) after every second graph user, through CYCLE_ORDER, and for every small level a
+                 ("vcycle", level) placed while the kind is W and one while it is F
+    operators    (first, [change, ...]): ("set_operator", first) instead of set_coefficient (+ build_galerkin) at the
+                 start, and the given lists of calls instead of the operator changes
+    fresh_guess  a random U of the top level before every call that forms b - A u of what earlier cycles left there:
+                 ("set_guess", seed) before solve / solve_pcg, ("set_u", level, seed) before ("vcycle", level).  The
+                 iterate then never converges into the cancellation regime of b - A u, where a rounding bound relative
+                 to max |x| means nothing
+    short_solves one cycle per solve and one iteration per solve_pcg (the float line case: see LINE_CASES)
+    without      call kinds left out of the weighted draw
+    tail         calls appended after everything else"""
     rng = np.random.RandomState(seed)
     L, Lc = cfg["finest_level"], cfg["coarsest_level"]
     f64 = cfg.get("dtype", hm.F64) == hm.F64
@@ -79,9 +132,11 @@ def draw_sequence(seed, cfg, n_steps=40):
         lv = int(rng.randint(Lc, L + 1))
         up = int(rng.randint(Lc + 1, L + 1))
         if name == "solve":
-            return ("solve", float(rng.choice([0.0, 1e-2])), int(rng.randint(1, 4)))
+            tol, k = float(rng.choice([0.0, 1e-2])), int(rng.randint(1, 4))
+            return ("solve", tol, 1 if short_solves else k)
         if name == "solve_pcg":
-            return ("solve_pcg", float(rng.choice([0.0, 1e-3] if f64 else [0.0, 1e-2])), int(rng.randint(1, 4)))
+            tol, k = float(rng.choice([0.0, 1e-3] if f64 else [0.0, 1e-2])), int(rng.randint(1, 4))
+            return ("solve_pcg", tol, 1 if short_solves else k)
         if name == "smooth":
             return ("smooth", lv, int(rng.choice(MUS)))
         if name in ("vcycle", "residual", "zero_u"):
@@ -98,6 +153,8 @@ def draw_sequence(seed, cfg, n_steps=40):
                "set_guess": 2, "set_rhs": 1, "set_u": 2, "set_b": 1, "zero_u": 1, "solve": 1, "solve_pcg": 1, "vcycle_zero": 1}
     if exact:
         weights["bottom_solve"] = 2
+    for k in without:
+        del weights[k]
     names = sorted(weights)
     p = np.array([weights[k] for k in names], dtype=float)
     calls = [one(k) for k in GRAPH_USERS for _ in range(5)]
@@ -108,6 +165,8 @@ def draw_sequence(seed, cfg, n_steps=40):
     elif op == hm.GALERKIN:
         changes = [[("build_galerkin", hm.OPERATOR)], [("build_galerkin", hm.BILINEAR)], [("build_galerkin", hm.OPERATOR)],
                    [("set_coefficient", 100.0, 11), ("build_galerkin", hm.BILINEAR)]]
+    if operators is not None:
+        changes = [list(c) for c in operators[1]]
     while len(calls) + len(between) + sum(len(c) for c in changes) < n_steps:
         calls.append(one(names[int(rng.choice(len(names), p=p / p.sum()))]))
     calls = [calls[i] for i in rng.permutation(len(calls))]
@@ -115,30 +174,55 @@ def draw_sequence(seed, cfg, n_steps=40):
         users = [i for i, x in enumerate(calls) if x[0] in GRAPH_USERS]
         calls.insert(int(rng.randint(users[0] + 1, users[-1] + 1)), c)
     out, users = [], 0
+    kinds = list(CYCLE_ORDER) if cycles else []
     for c in calls:
         out.append(c)
         if c[0] in GRAPH_USERS:
             users += 1
             if users % 3 == 0 and changes:
                 out += changes.pop(0)
-    assert not changes
+            if users % 2 == 0 and kinds:
+                out.append(("set_cycle", kinds.pop(0)))
+    assert not changes and not kinds
+    if cycles:
+        # a cycle from every small level as its top, under W and under F: placed inside a span of that kind
+        rng2 = np.random.RandomState(seed + 77777)
+        for lv in small_levels(cfg):
+            for kind in (hm.CYCLE_W, hm.CYCLE_F):
+                at = [i for i, k in enumerate(kinds_at(out)) if k == kind]
+                out.insert(int(at[rng2.randint(len(at))]) + 1, ("vcycle", lv))
+        for lv in small_levels(cfg):
+            for kind in (hm.CYCLE_W, hm.CYCLE_F):
+                assert any(c == ("vcycle", lv) and k == kind for c, k in zip(out, kinds_at(out))), (seed, lv, kind)
+    if fresh_guess:
+        fresh = []
+        for c in out:
+            if c[0] in ("solve", "solve_pcg"):
+                fresh.append(("set_guess", 3000 + len(fresh)))
+            elif c[0] == "vcycle":
+                fresh.append(("set_u", c[1], 3000 + len(fresh)))
+            fresh.append(c)
+        out = fresh
     users = [i for i, x in enumerate(out) if x[0] in GRAPH_USERS]
     for lv in range(Lc, L + 1):
         assert any(c[0] == "smooth" and c[1] == lv and c[2] % 2 for c in out[users[0] + 1:users[-1]]), (seed, lv)
     # data on every level first, and the operators of the general hierarchies
     pre = []
-    if op != hm.POISSON:
+    if operators is not None:
+        pre.append(("set_operator", operators[0]))
+    elif op != hm.POISSON:
         pre.append(("set_coefficient", 10.0, 10))
-    if op == hm.GALERKIN:
+    if op == hm.GALERKIN and operators is None:
         pre.append(("build_galerkin", hm.BILINEAR))
     for lv in range(Lc, L + 1):
         pre += [("set_u", lv, 1000 + lv), ("set_b", lv, 2000 + lv)]
-    return pre + out
+    return pre + out + list(tail)
 
 
 # ---- one call on the device and on the model -------------------------------------------------------------------
-def apply_device(pkg, mg, call, L):
-    """the binding (multigrid_nikhil_c-_amd/binding.py) wraps the bare mgx_fmg, mgx_bottom_solve, mgx_residual,
+def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
+    """transfer: what a GALERKIN set_operator rebuilds with (the model's transfer in use).
+    The binding (multigrid_nikhil_c-_amd/binding.py) wraps the bare mgx_fmg, mgx_bottom_solve, mgx_residual,
     mgx_restrict*, mgx_prolong* only together with set_level calls, so those go to the C entry points through the
     wrapper's own handle and status check: Multigrid._h and Multigrid._chk - a rename there has to be followed here"""
     lib = pkg.lib()
@@ -178,6 +262,17 @@ def apply_device(pkg, mg, call, L):
         mg.set_coefficient(coefficient(L, a[0], a[1]))
     elif name == "build_galerkin":
         mg.build_galerkin(a[0])
+    elif name == "set_cycle":
+        mg.set_cycle(a[0])
+    elif name == "set_operator":
+        from oracle import pyoracle
+        dt = mg.level_dtype(L)
+        if mg.cfg.op == hm.STENCIL5:
+            for lv in range(mg.cfg.coarsest_level, L + 1):
+                mg.set_stencil(lv, *hm.operator5(pyoracle, lv, a[0], dt))
+        else:
+            mg.set_stencil(L, *hm.operator5(pyoracle, L, a[0], dt))
+            mg.build_galerkin(transfer)
     else:
         raise AssertionError(name)
     return None
@@ -225,6 +320,8 @@ def touched(cfg, call):
     name = call[0]
     if name == "bottom_solve":
         return {(Lc, "U")}
+    if name == "smooth":
+        return {(call[1], "U")} if call[2] else set()
     top = call[1] if name == "vcycle" else L                # vcycle_zero, fmg, solve, solve_pcg: from the finest level
     return {(top, "U")} | {(lv, x) for lv in range(Lc, top) for x in ("U", "B")}
 
@@ -252,16 +349,25 @@ class Tally:
         self.state = 0.0                                   # largest relative state deviation through the sine-transform bottom solve
         self.state_pcg = 0.0                               # ... after mgx_solve_pcg
         self.graph_counts = []
+        self.histories = []                                # of the device, in call order
+        self.final = None                                  # U and B of every level after the last call
+        self.bound = 0.0                                   # line cases: the largest bound of the tolerance rule used
+        self.ratio = 0.0                                   # ... and the largest device deviation / its bound
 
 
 def step(pkg, mg, m, cfg, call, tally, where):
     """one call on both sides, then every level's U and B, the history and the statistics"""
     L, Lc = cfg["finest_level"], cfg["coarsest_level"]
-    got = apply_device(pkg, mg, call, L)
+    g_before = mg.graphs_cached()
+    got = apply_device(pkg, mg, call, L, hm.BILINEAR if m.transfer is None else m.transfer)
     want = apply_model(m, call, L)
     tally.executed += 1
+    if call[0] == "set_cycle":                             # the graph key carries no kind: the setter has to drop the graphs
+        assert mg.cycle == m.cycle == call[1], where()
+        assert mg.graphs_cached() == (0 if g_before >= 0 else -1), f"{mg.graphs_cached()} graphs after mgx_set_cycle; {where()}"
     if call[0] in ("solve", "solve_pcg"):
         (st, h), (st_m, h_m) = got, want
+        tally.histories.append(np.array(h))
         ok, frac = history_check(cfg, call, h, h_m)
         tally.hist[call[0]] = max(tally.hist[call[0]], frac if np.isfinite(frac) else 0.0)
         assert ok, f"history {frac:.3g} x its bound: {h} vs {h_m}; {where()}"
@@ -306,6 +412,7 @@ def run_sequence(pkg, po, cfg, calls, seed, env=None):
         for call in calls:
             done.append(call)
             step(pkg, mg, m, cfg, call, tally, where)
+        tally.final = all_levels(pkg, mg, cfg["finest_level"], cfg["coarsest_level"])
     assert tally.executed == len(calls)                    # nothing skipped, nothing filtered
     users = {k: sum(1 for c in calls if c[0] == k) for k in GRAPH_USERS}
     assert min(users.values()) >= 5, users
@@ -380,6 +487,262 @@ def test_five_level_sequence_matches_the_model_after_every_call(pkg, po, monkeyp
     set_knobs(monkeypatch, {})
     tally = run_sequence(pkg, po, cfg, draw_sequence(9501, cfg), 9501)
     assert 1 <= tally.graphs <= K_MAX_GRAPHS
+
+
+# ---- 2b. the cycle index ---------------------------------------------------------------------------------------------
+G73 = dict(finest_level=7, coarsest_level=3, mu0=0, mu1=3, mu2=2, schedule=hm.V, op=hm.GALERKIN)
+CYCLE_CASES = {
+    # name: (configuration, seed, also with MGX_SMALL_VISIT=0)
+    # levels 6, 5, 4 take k_small_visit, with turns on each; a 15^2 and a 7^2 level; the dense solve at level 3
+    "galerkin_f64_jacobi_7_3": (dict(G73), 8531, True),
+    # float lanes (1 x 4 vectors), rscale = 1/4
+    "galerkin_f32_jacobi_fw16_7_3": (dict(G73, dtype=hm.F32, restrict_mode=hm.FW16, bottom=hm.SMOOTH), 8532, True),
+    # level 6 is the only fused level, next to the coarsest; level 7 takes the per-level launches
+    "galerkin_f64_jacobi_8_5_smooth_bottom": (dict(P85, op=hm.GALERKIN, bottom=hm.SMOOTH), 8533, True),
+    # W / F through the per-level launches only; the dense solve at level 4
+    "galerkin_f64_chebyshev_7_4": (dict(G73, coarsest_level=4, smoother=hm.CHEBYSHEV), 8534, False),
+    # no nine-point level: never the visit kernel
+    "stencil5_f64_jacobi_8_5": (dict(P85, op=hm.STENCIL5), 8535, False),
+}
+
+
+def assert_cycle_calls(calls, cfg):
+    """what draw_sequence(cycles=True) promises, on the drawn list"""
+    users = [i for i, c in enumerate(calls) if c[0] in GRAPH_USERS]
+    sets = [i for i, c in enumerate(calls) if c[0] == "set_cycle"]
+    assert tuple(calls[i][1] for i in sets) == CYCLE_ORDER
+    for k, i in enumerate(sets):                           # after every second graph user (an operator change may stand between)
+        assert sum(1 for u in users if u < i) == 2 * (k + 1), (k, i)
+    kinds = kinds_at(calls)
+    for lv in small_levels(cfg):
+        for kind in (hm.CYCLE_W, hm.CYCLE_F):
+            assert any(c == ("vcycle", lv) and k == kind for c, k in zip(calls, kinds)), (lv, kind)
+    # the first graph user after every change of kind: where a graph of the old kind would replay
+    for i in sets:
+        assert any(u > i for u in users), i
+
+
+@pytest.mark.parametrize("name", list(CYCLE_CASES))
+def test_cycle_index_sequences_match_the_model_after_every_call(pkg, po, monkeypatch, name):
+    """set_cycle W, F, V, W, F, W, V between the graph users, besides the operator changes; cycles started from every
+    small level under W and under F.  U and B of EVERY level bit for bit after every call (solve_pcg as in
+    GENERAL_CASES), so what a W- or F-cycle leaves on levels 6, 5, 4 is held, and the dense coarsest solve at levels 3
+    and 4.  The Jacobi GALERKIN cases a second time with MGX_SMALL_VISIT=0 against the same model: the in-place visit
+    kernel and the swapping per-level launches leave other buffer assignments behind, and the same bits."""
+    cfg, seed, both = CYCLE_CASES[name]
+    calls = draw_sequence(seed, cfg, cycles=True)
+    assert_cycle_calls(calls, cfg)
+    runs = []
+    for env in ([{}, {"MGX_SMALL_VISIT": "0"}] if both else [{}]):
+        set_knobs(monkeypatch, env)
+        tally = run_sequence(pkg, po, cfg, calls, seed, env)
+        assert 1 <= tally.graphs <= K_MAX_GRAPHS
+        runs.append(tally)
+    if both:
+        a, b = runs
+        for x, y in zip(a.final, b.final):
+            assert np.array_equal(x, y)
+        assert len(a.histories) == len(b.histories) and all(np.array_equal(x, y) for x, y in zip(a.histories, b.histories))
+
+
+def test_a_refused_set_cycle_leaves_the_graphs_and_the_next_solve_alone(pkg, po, monkeypatch):
+    """POISSON: mgx_set_cycle(W) is MGX_ERR_STATE.  The refusal must come before the setter drops anything: the graphs
+    stay, and the next solve is the solve of a handle that never made the call - bits, history, fine_updates"""
+    set_knobs(monkeypatch, {})
+    cfg = dict(P85)
+    L, Lc = 8, 5
+    calls = [("set_rhs", 91), ("set_guess", 92), ("solve", 0.0, 2), ("vcycle_zero",), ("smooth", 6, 1), ("solve_pcg", 0.0, 2)]
+    with pkg.Multigrid(**cfg) as plain, pkg.Multigrid(**cfg) as mg:
+        for call in calls:
+            apply_device(pkg, plain, call, L)
+            apply_device(pkg, mg, call, L)
+        g = mg.graphs_cached()
+        assert g >= 1 and plain.graphs_cached() == g
+        assert pkg.lib().mgx_set_cycle(mg._h, hm.CYCLE_W) == 5          # MGX_ERR_STATE
+        assert mg.graphs_cached() == g and mg.cycle == hm.CYCLE_V
+        with pytest.raises(RuntimeError):
+            hm.HandleModel(po, **cfg).set_cycle(hm.CYCLE_W)
+        for call in [("solve", 0.0, 2), ("vcycle_zero",), ("solve_pcg", 0.0, 1)]:
+            a, b = apply_device(pkg, plain, call, L), apply_device(pkg, mg, call, L)
+            for x, y in zip(all_levels(pkg, plain, L, Lc), all_levels(pkg, mg, L, Lc)):
+                assert np.array_equal(x, y), call
+            if a is not None:
+                assert np.array_equal(a[1], b[1]), (call, a[1], b[1])
+                assert (a[0].cycles, a[0].converged, a[0].fine_updates) == (b[0].cycles, b[0].converged, b[0].fine_updates), call
+            assert mg.graphs_cached() == plain.graphs_cached() >= g
+
+
+# ---- 2c. the line smoothers ------------------------------------------------------------------------------------------
+L63 = dict(finest_level=6, coarsest_level=3, mu0=0, mu1=1, mu2=1, schedule=hm.V)
+LINE_CASES = {
+    # name: (configuration, seed, environment, generator options)
+    "galerkin_f64_alt_6_3_cycles": (
+        dict(L63, op=hm.GALERKIN, smoother=hm.LINE_ALT), 8541, {},
+        dict(cycles=True, operators=("layers", [[("set_operator", "x1e-2")], [("build_galerkin", hm.OPERATOR)], [("set_operator", "contrast")],
+                                                [("set_operator", "layers")]]))),
+    # float: a zebra x-line sweep all but solves these operators, so every coarse right-hand side is a difference that
+    # cancels to 1e-2 .. 1e-3 of its operands and the rule's bound is within a small factor of the cap (PCG32_STATE) after ONE
+    # cycle.  Measured on the CPU (the two models alone), x1e-2: one cycle 2.4e-4, one PCG iteration 2e-4, two 7.2e-4, three
+    # 1.1e-3, fmg 5e-4 .. 2e-3; x1e-3: one cycle 1.0e-3 .. 1.8e-3, a solve of two cycles 6.8e-2.  The cap stays; the sequence
+    # keeps under it by construction: one cycle per solve, one iteration per solve_pcg, no fmg, and the x1e-3 operator at
+    # the end, followed by a sweep on every level (the rebuilt factors of every level; the bound of a sweep is 1e-4).
+    # Replays after an operator change are the double cases'
+    "galerkin_f32_x_fw16_6_3": (
+        dict(L63, op=hm.GALERKIN, smoother=hm.LINE_X, dtype=hm.F32, restrict_mode=hm.FW16), 8542, {},
+        dict(operators=("x1e-2", []), short_solves=True, without=("fmg",),
+             tail=[("set_operator", "x1e-3")] + [("smooth", lv, mu) for lv, mu in ((6, 1), (5, 3), (4, 1), (3, 2))] + [("residual", 6), ("restrict", 6)])),
+    # the carries through LDS on levels 7 and 6 (127 and 63 rows in chunks of 16), inside cycles and replays
+    "galerkin_f64_y_7_4_chunk16": (
+        dict(L63, finest_level=7, coarsest_level=4, op=hm.GALERKIN, smoother=hm.LINE_Y), 8543, {"MGX_LINE_CHUNK": "16"},
+        dict(operators=("y1e-2", [[("set_operator", "layers")]]))),
+    "stencil5_f64_alt_6_3_smooth_bottom_cycles": (
+        dict(L63, op=hm.STENCIL5, smoother=hm.LINE_ALT, bottom=hm.SMOOTH), 8544, {},
+        dict(cycles=True, operators=("x1e-2", [[("set_operator", "layers")]]))),
+}
+LINE_OPTIONS = dict(fresh_guess=True)
+
+
+def line_cap(cfg):
+    return RTOL64 if cfg.get("dtype", hm.F64) == hm.F64 else PCG32_STATE
+
+
+def line_models(po, cfg):
+    """the model in the working type and in np.longdouble"""
+    return hm.HandleModel(po, **cfg), hm.HandleModel(po, real=np.longdouble, **cfg)
+
+
+def line_call(m, mx, cfg, call):
+    """one call on both models from the state of `m`.  Returns (want, far, bounds): the two results, and for a call that
+    smooths {(level, 'U' / 'B'): (bound, scale)} of THE TOLERANCE RULE for every array it writes; scale = max |x| of
+    the long-double array (0: the array is zero in both models, nothing to scale by: bit for bit)"""
+    L = cfg["finest_level"]
+    for lv in m.levels():
+        mx.set_level(lv, 0, m.U[lv])
+        mx.set_level(lv, 1, m.B[lv])
+    mx.fine_updates = m.fine_updates
+    want, far = apply_model(m, call, L), apply_model(mx, call, L)
+    bounds = {}
+    if call[0] in SMOOTHING:
+        for lv, name in touched(cfg, call):
+            r, x = m.get_level(lv, 0 if name == "U" else 1), mx.get_level(lv, 0 if name == "U" else 1)
+            scale = float(np.max(np.abs(x)))
+            if scale == 0.0:
+                assert not r.any(), (lv, name, call)
+                bounds[lv, name] = (0.0, 0.0)
+            else:
+                bounds[lv, name] = (rule_bound(r, x)[0], scale)
+    return want, far, bounds
+
+
+def line_history_check(h, h_m, h_x):
+    """history_bound of tests/test_gpu_line.py; (ok, deviation / bound)"""
+    h, h_m, h_x = np.asarray(h), np.asarray(h_m), np.asarray(h_x, dtype=np.float64)
+    if len(h) != len(h_m):
+        return False, np.inf
+    frac = float(np.max(np.abs(h - h_m)) / np.max(h_m)) / history_bound(h_m, h_x)
+    return frac <= 1.0, frac
+
+
+def line_step(pkg, mg, twin, m, mx, cfg, call, tally, where):
+    L, Lc = cfg["finest_level"], cfg["coarsest_level"]
+    transfer = hm.BILINEAR if m.transfer is None else m.transfer
+    g_before = mg.graphs_cached()
+    got, got_t = apply_device(pkg, mg, call, L, transfer), apply_device(pkg, twin, call, L, transfer)
+    want, far, bounds = line_call(m, mx, cfg, call)
+    tally.executed += 1
+    if call[0] == "set_cycle":
+        assert mg.cycle == twin.cycle == m.cycle == call[1], where()
+        assert mg.graphs_cached() == (0 if g_before >= 0 else -1), f"{mg.graphs_cached()} graphs after mgx_set_cycle; {where()}"
+    if call[0] in ("solve", "solve_pcg"):
+        (st, h), (st_t, h_t), (st_m, h_m), (_, h_x) = got, got_t, want, far
+        ok, frac = line_history_check(h, h_m, h_x)
+        tally.hist[call[0]] = max(tally.hist[call[0]], frac if np.isfinite(frac) else 0.0)
+        assert ok, f"history {frac:.3g} x its bound: {h} vs {h_m} (long double {h_x}); {where()}"
+        assert (st.cycles, st.converged, st.fine_updates) == (st_m["cycles"], st_m["converged"], st_m["fine_updates"]), \
+            f"stats {(st.cycles, st.converged, st.fine_updates)} vs {st_m}; {where()}"
+        assert np.array_equal(h, h_t), f"replaying and eager handle: histories {h} vs {h_t}; {where()}"
+        assert (st.cycles, st.converged, st.fine_updates) == (st_t.cycles, st_t.converged, st_t.fine_updates), where()
+    elif call[0] == "residual":
+        assert np.array_equal(got, want) and np.array_equal(got, got_t), f"R of level {call[1]}; {where()}"
+    cap = line_cap(cfg)
+    for lv in range(Lc, L + 1):
+        for which, name in ((pkg.VEC_U, "U"), (pkg.VEC_B, "B")):
+            w = 0 if which == pkg.VEC_U else 1
+            a, r = mg.get_level(lv, which), m.get_level(lv, w)
+            assert a.dtype == r.dtype and a.shape == r.shape
+            assert np.array_equal(a, twin.get_level(lv, which)), f"{name} of level {lv}: the replaying and the eager handle differ; {where()}"
+            bound, scale = bounds.get((lv, name), (0.0, 0.0))
+            if scale == 0.0:
+                if not np.array_equal(a, r):
+                    bad = np.argwhere(a != r)
+                    raise AssertionError(f"{name} of level {lv} differs at {len(bad)} points, first {tuple(bad[0])}: "
+                                         f"{a[tuple(bad[0])]!r} vs {r[tuple(bad[0])]!r}; {where()}")
+                continue
+            assert bound <= cap, f"bound too loose: {bound:.3g} > {cap:g} for {name} of level {lv}; {where()}"
+            al = a.astype(np.longdouble)
+            dev = max(float(np.max(np.abs(al - r.astype(np.longdouble)))), float(np.max(np.abs(al - mx.get_level(lv, w))))) / scale
+            tally.bound = max(tally.bound, bound)
+            tally.ratio = max(tally.ratio, dev / bound)
+            assert dev <= bound, f"{name} of level {lv} off by {dev:.3g}, {dev / bound:.3g} x its bound {bound:.3g}; {where()}"
+            m.set_level(lv, w, a)                          # (mx takes m's state before its next call)
+    g = mg.graphs_cached()
+    tally.graph_counts.append(g)
+    tally.graphs = max(tally.graphs, g)
+    assert twin.graphs_cached() == -1
+
+
+@pytest.mark.parametrize("name", list(LINE_CASES))
+def test_line_smoother_sequences_follow_the_models_after_every_call(pkg, po, monkeypatch, name):
+    cfg, seed, env, options = LINE_CASES[name]
+    calls = draw_sequence(seed, cfg, **LINE_OPTIONS, **options)
+    if options.get("cycles"):
+        assert_cycle_calls(calls, cfg)
+    wanted = [options["operators"][0]] + [c[1] for g in list(options["operators"][1]) + [options.get("tail", [])] for c in g if c[0] == "set_operator"]
+    assert [c[1] for c in calls if c[0] == "set_operator"] == wanted
+    tally = Tally()
+    done = []
+
+    def where():
+        return f"seed {seed}, step {len(done) - 1} of {len(calls)}, cfg {cfg}, env {env}, calls so far {done}"
+
+    m, mx = line_models(po, cfg)
+    set_knobs(monkeypatch, dict(env, MGX_GRAPH="0"))
+    twin = pkg.Multigrid(**cfg)
+    set_knobs(monkeypatch, env)
+    try:
+        with pkg.Multigrid(**cfg) as mg:
+            assert mg.graphs_cached() == 0 and twin.graphs_cached() == -1
+            for call in calls:
+                done.append(call)
+                line_step(pkg, mg, twin, m, mx, cfg, call, tally, where)
+                if len(done) == 1 and "MGX_LINE_CHUNK" in env:
+                    chunk = int(env["MGX_LINE_CHUNK"])
+                    for lv in (7, 6):                      # the override took effect: more than one chunk on both levels
+                        assert mg.line_chunks(lv) == (chunk, -(-((1 << lv) - 1) // chunk)), mg.line_chunks(lv)
+    finally:
+        twin.close()
+    assert tally.executed == len(calls)
+    users = {k: sum(1 for c in calls if c[0] == k) for k in GRAPH_USERS}
+    assert min(users.values()) >= 5, users
+    assert 1 <= tally.graphs <= K_MAX_GRAPHS
+    print(f"\n[handle-state] line cfg={cfg} env={env} seed={seed} steps={tally.executed} of {len(calls)} drawn graph_users={users} "
+          f"max_graphs={tally.graphs} hist_solve={tally.hist['solve']:.3g}xbound hist_pcg={tally.hist['solve_pcg']:.3g}xbound "
+          f"largest_bound={tally.bound:.3g} (cap {line_cap(cfg):g}) largest_device_to_bound_ratio={tally.ratio:.3g}")
+
+
+def test_a_line_smoother_keeps_small_levels_off_the_visit_kernel(pkg, po, monkeypatch):
+    """k_small_visit is Jacobi's: a W-cycle of a LINE_ALT GALERKIN handle on 6..3 pays the same launches below the finest
+    level with MGX_SMALL_VISIT 1 and 0 (cfg.profile = 1: every launch eager and counted), and computes the same bits"""
+    cfg = dict(LINE_CASES["galerkin_f64_alt_6_3_cycles"][0], profile=1)
+    out = []
+    for small in ("1", "0"):
+        set_knobs(monkeypatch, {"MGX_SMALL_VISIT": small})
+        with pkg.Multigrid(**cfg) as mg:
+            for call in [("set_operator", "layers"), ("set_cycle", hm.CYCLE_W), ("set_rhs", 95), ("solve", 0.0, 2)]:
+                apply_device(pkg, mg, call, 6)
+            out.append((mg.profile()["launches"][4], mg.get_solution()))          # MGX_PROF_COARSE
+    assert out[0][0] == out[1][0] > 0, (out[0][0], out[1][0])
+    assert np.array_equal(out[0][1], out[1][1])
 
 
 # ---- 3. the cache bound and its fallback ---------------------------------------------------------------------------

@@ -8,8 +8,12 @@ import pytest
 import cheby_ref
 import galerkin_ref as gr
 import handle_model as hm
+import line_ref as lr
 import opdep_ref as od
 import pcg_ref
+import test_gpu_handle_state as gs
+import wcycle_ref as wr
+from test_line_cpu import as_type, operator5
 
 LEVELS = [(6, 3), (7, 4)]
 
@@ -251,3 +255,294 @@ def test_refused_configurations():
         hm.HandleModel(None, dtype=hm.MIXED)
     with pytest.raises(TypeError):
         hm.HandleModel(None, n_gpus=2)
+
+
+# ---- the sequences of tests/test_gpu_handle_state.py ------------------------------------------------------------------
+FROZEN = {
+    # seed: (length, the first ten calls) of draw_sequence(seed, cfg) before the generator learnt its optional calls
+    8501: (48, [('set_u', 5, 1005), ('set_b', 5, 2005), ('set_u', 6, 1006), ('set_b', 6, 2006), ('set_u', 7, 1007), ('set_b', 7, 2007),
+                ('set_u', 8, 1008), ('set_b', 8, 2008), ('solve', 0.0, 2), ('vcycle_zero',)]),
+    8511: (49, [('set_coefficient', 10.0, 10), ('set_u', 5, 1005), ('set_b', 5, 2005), ('set_u', 6, 1006), ('set_b', 6, 2006),
+                ('set_u', 7, 1007), ('set_b', 7, 2007), ('set_u', 8, 1008), ('set_b', 8, 2008), ('solve', 0.01, 3)]),
+    8521: (50, [('set_coefficient', 10.0, 10), ('build_galerkin', 0), ('set_u', 5, 1005), ('set_b', 5, 2005), ('set_u', 6, 1006),
+                ('set_b', 6, 2006), ('set_u', 7, 1007), ('set_b', 7, 2007), ('set_u', 8, 1008), ('set_b', 8, 2008)]),
+}
+# sha1 of repr(draw_sequence(seed, cfg)) of every case that existed then: the whole list, not its head
+FROZEN_SHA1 = {
+    8501: "1ead17fe803eb282c5491a79fcf74850c857588d", 8502: "e77d36c5b83d0d29e5e4fe8f046233e4598638a7",
+    8503: "df389ae304f4ee45bb89b741b03b2d31afe54a4f", 8504: "d3dd6f34d14631d79133c7710aac7feca88c1097",
+    8505: "0e2344a9df1b2eb2217a708729fa58c2826824a3", 8506: "80e6e1a42d59e51f72693b6e9b2f6bebe0124575",
+    8511: "99cbaaf4661cac8be3d0dbdfa9f768b6401cbb59", 8512: "1d9b2aa221966f0f6c6a3c30f0b8a48704f52b6b",
+    8513: "6a5955269e7045f5f11cdc8626bf41ed6ac9495f", 8521: "1ea724faecaa8f86dc234518a389962b818269be",
+    8522: "319fa09454b5d041b855876f9a6d9475a1257cf3", 8523: "5a7d6e073d720be41539201468df3b1aaffe10fa",
+}
+
+
+def test_the_sequences_of_the_existing_cases_are_call_for_call_what_they_were():
+    import hashlib
+    cases = dict(gs.POISSON_CASES, **gs.GENERAL_CASES)
+    by_seed = {seed: cfg for cfg, seed in cases.values()}
+    assert set(by_seed) == set(FROZEN_SHA1)
+    for seed, (length, head) in FROZEN.items():
+        calls = gs.draw_sequence(seed, by_seed[seed])
+        assert len(calls) == length and calls[:10] == head, seed
+    for seed, digest in FROZEN_SHA1.items():
+        calls = gs.draw_sequence(seed, by_seed[seed])
+        assert hashlib.sha1(repr(calls).encode()).hexdigest() == digest, seed
+        assert not any(c[0] in ("set_cycle", "set_operator") for c in calls)
+    assert "MGX_SMALL_VISIT" in gs.KNOBS and "MGX_LINE_CHUNK" in gs.KNOBS
+
+
+def test_cycle_and_line_sequences_hold_what_the_generator_promises():
+    for cfg, seed, _ in gs.CYCLE_CASES.values():
+        calls = gs.draw_sequence(seed, cfg, cycles=True)
+        gs.assert_cycle_calls(calls, cfg)
+        assert min(sum(1 for c in calls if c[0] == k) for k in gs.GRAPH_USERS) >= 5
+        assert gs.small_levels(cfg) == list(range(cfg["coarsest_level"] + 1, 7))
+    for cfg, seed, env, options in gs.LINE_CASES.values():
+        calls = gs.draw_sequence(seed, cfg, **gs.LINE_OPTIONS, **options)
+        if options.get("cycles"):
+            gs.assert_cycle_calls(calls, cfg)
+        assert calls[0] == ("set_operator", options["operators"][0])
+        assert not any(c[0] == "set_coefficient" for c in calls)
+        for i, c in enumerate(calls):
+            if c[0] in ("solve", "solve_pcg"):
+                assert calls[i - 1][0] == "set_guess", (seed, i)
+            if c[0] == "vcycle":
+                assert calls[i - 1][:2] == ("set_u", c[1]), (seed, i)
+
+
+# ---- the cycle index --------------------------------------------------------------------------------------------------
+CYCLE_REFS = {
+    # name: (reference class, op, transfer, smoother)
+    "Galerkin": (wr.Galerkin, hm.GALERKIN, hm.BILINEAR, hm.JACOBI),
+    "Opdep": (wr.Opdep, hm.GALERKIN, hm.OPERATOR, hm.JACOBI),
+    "ChebyOpdep": (wr.ChebyOpdep, hm.GALERKIN, hm.OPERATOR, hm.CHEBYSHEV),
+    "Stencil5": (wr.Stencil5, hm.STENCIL5, None, hm.JACOBI),
+    "Stencil5Cheby": (wr.Stencil5Cheby, hm.STENCIL5, None, hm.CHEBYSHEV),
+}
+
+
+@pytest.mark.parametrize("L,Lc", LEVELS)
+@pytest.mark.parametrize("dtype", [hm.F64, hm.F32])
+@pytest.mark.parametrize("kind", [hm.CYCLE_W, hm.CYCLE_F], ids=["W", "F"])
+@pytest.mark.parametrize("name", list(CYCLE_REFS))
+def test_w_and_f_compositions_equal_wcycle_ref(po, name, kind, dtype, L, Lc):
+    cls, op, transfer, smoother = CYCLE_REFS[name]
+    bottom = hm.EXACT if (L + dtype) % 2 == 0 else hm.SMOOTH
+    mode = hm.FW16 if dtype == hm.F32 else hm.CONSISTENT
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=1, mu1=2, mu2=1, smoother=smoother, dtype=dtype, restrict_mode=mode, bottom=bottom,
+               op=op, schedule=hm.FMG)
+    dt = np.float64 if dtype == hm.F64 else np.float32
+    a = contrast(L, 10.0, 4)
+    kw = dict(dtype=dt, mode=mode, omega=2.0 / 3.0, mu1=2, mu2=1, mu0=1, bottom=bottom)
+    if op == hm.STENCIL5:
+        ref = cls(po, {lv: po.stencil_from_nodes(a, lv, L) for lv in range(Lc, L + 1)}, L, Lc, **kw)
+    else:
+        ref = cls(po, po.stencil_from_nodes(a, L, L), L, Lc, **kw)
+    ref.cycle = kind
+    m = hm.HandleModel(po, **cfg)
+    assert m.cycle == hm.CYCLE_V
+    early = dtype == hm.F32                             # the kind survives set_coefficient and build_galerkin
+    if early:
+        m.set_cycle(kind)
+    m.set_coefficient(a)
+    if op == hm.GALERKIN:
+        m.build_galerkin(transfer)
+    if not early:
+        m.set_cycle(kind)
+    assert m.cycle == kind
+    u, b = data(po, L, dt, 50 + L)
+    m.set_guess(u)
+    m.set_rhs(b)
+    m.vcycle()
+    assert m.U[L].dtype == dt and np.array_equal(m.U[L], ref.vcycle(L, u, b))
+    # level L - 1 after the cycle: the restricted residual, and two visits from zero with that right-hand side
+    v = ref.smooth(L, u, b, 2)
+    rc = ref._restrict_residual(L, v, b)
+    e = ref._cycle(L - 1, np.zeros_like(rc), rc, kind)
+    e = ref._cycle(L - 1, e, rc, hm.CYCLE_V if kind == hm.CYCLE_F else kind)
+    assert np.array_equal(m.B[L - 1], rc) and np.array_equal(m.U[L - 1], e)
+    # a cycle started from an intermediate level, from a non-zero U
+    top = m.U[L].copy()
+    u1, b1 = data(po, L - 1, dt, 78)
+    m.set_level(L - 1, 0, u1)
+    m.set_level(L - 1, 1, b1)
+    m.vcycle(L - 1)
+    assert np.array_equal(m.U[L - 1], ref.vcycle(L - 1, u1, b1)) and np.array_equal(m.U[L], top)
+    m.set_rhs(b)
+    m.fmg()
+    assert np.array_equal(m.U[L], ref.fmg(b))
+    m.set_guess(u)
+    m.vcycle_zero()
+    assert np.array_equal(m.U[L], ref.vcycle(L, np.zeros_like(b), b))
+    m.set_guess(u)
+    st, h = m.solve(tol=0.0, max_cycles=2)
+    u_ref, h_ref = ref.solve(b, u, tol=0.0, max_cycles=2, schedule=gr.FMG)
+    assert np.array_equal(h, h_ref) and np.array_equal(m.U[L], u_ref) and st["cycles"] == 2
+    assert st["fine_updates"] == (2 + 1) * 3.0 * float((1 << L) - 1) ** 2        # FMG: mu0 + 1 = 2 finest cycles, then one
+    # back to V: the parent's bits
+    m.set_cycle(hm.CYCLE_V)
+    m.set_guess(u)
+    m.vcycle()
+    ref.cycle = hm.CYCLE_V
+    assert np.array_equal(m.U[L], ref.vcycle(L, u, b))
+
+
+def test_a_w_cycle_on_three_levels_by_hand(po):
+    """levels 5, 4, 3, GALERKIN with bilinear transfers, double, V(2,1) smoothing, exact bottom: level 4 is visited twice,
+    the second time from what the first visit left with the same right-hand side; level 3 once per visit of level 4.
+    Afterwards the coarse levels hold the restricted residual and the iterate of the LAST visit"""
+    L, Lc = 5, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=2, mu2=1, op=hm.GALERKIN, schedule=hm.V)
+    a = contrast(L, 10.0, 6)
+    h = gr.Hierarchy(po, po.stencil_from_nodes(a, L, L), L, Lc, mu1=2, mu2=1)
+    u, b = data(po, L, np.float64, 31)
+    S, R, A = h.smooth, (lambda r: po.restrict(r, hm.CONSISTENT)), h.residual
+    v = S(5, u, b, 2)
+    b4 = R(A(5, v, b))
+    e4 = S(4, np.zeros_like(b4), b4, 2)                 # first visit of level 4
+    b3 = R(A(4, e4, b4))
+    e3 = h.bottom(b3)
+    e4 = S(4, po.prolong_add(e4, e3), b4, 1)
+    e4_first = e4
+    e4 = S(4, e4, b4, 2)                                # second visit: from e4, with the same b4
+    b3 = R(A(4, e4, b4))
+    e3 = h.bottom(b3)
+    e4 = S(4, po.prolong_add(e4, e3), b4, 1)
+    v = S(5, po.prolong_add(v, e4), b, 1)
+    for kind in (hm.CYCLE_W, hm.CYCLE_F):               # on three levels F is W: the second visit of 4 has no level to repeat
+        m = hm.HandleModel(po, **cfg)
+        m.set_coefficient(a)
+        m.build_galerkin(hm.BILINEAR)
+        m.set_cycle(kind)
+        m.set_guess(u)
+        m.set_rhs(b)
+        m.vcycle()
+        assert np.array_equal(m.U[5], v) and np.array_equal(m.B[5], b)
+        assert np.array_equal(m.B[4], b4) and np.array_equal(m.U[4], e4) and not np.array_equal(e4, e4_first)
+        assert np.array_equal(m.B[3], b3) and np.array_equal(m.U[3], e3)
+    m.set_cycle(hm.CYCLE_V)
+    m.set_guess(u)
+    m.vcycle()
+    assert np.array_equal(m.U[4], e4_first)
+
+
+def test_set_cycle_refusals(po):
+    m = hm.HandleModel(po, finest_level=6, coarsest_level=4)
+    for kind in (hm.CYCLE_W, hm.CYCLE_F, hm.CYCLE_V):
+        with pytest.raises(RuntimeError):
+            m.set_cycle(kind)
+    assert m.cycle == hm.CYCLE_V
+    m = hm.HandleModel(po, finest_level=6, coarsest_level=4, op=hm.STENCIL5)
+    with pytest.raises(ValueError):
+        m.set_cycle(3)
+    m.set_cycle(hm.CYCLE_F)
+    assert m.cycle == hm.CYCLE_F
+
+
+# ---- the line smoothers -----------------------------------------------------------------------------------------------
+LINE_REFS = [(lr.Hierarchy, hm.GALERKIN, hm.BILINEAR), (lr.OpdepHierarchy, hm.GALERKIN, hm.OPERATOR), (lr.Stencil5, hm.STENCIL5, None)]
+
+
+def line_reference(po, cls, smoother, kind, L, Lc, dt, real, cycle, **kw):
+    ops = po if real is dt else lr.NumpyOps
+    if cls is lr.Stencil5:
+        op = {lv: as_type(operator5(po, lv, kind, dt), real) for lv in range(Lc, L + 1)}
+    else:
+        op = as_type(operator5(po, L, kind, dt), real)
+    return cls(smoother, ops, op, L, Lc, real, cycle=cycle, **kw)
+
+
+@pytest.mark.parametrize("real", ["working", "longdouble"])
+@pytest.mark.parametrize("cycle", [hm.CYCLE_V, hm.CYCLE_W], ids=["V", "W"])
+@pytest.mark.parametrize("dtype", [hm.F64, hm.F32])
+@pytest.mark.parametrize("cls,op,transfer", LINE_REFS, ids=["Hierarchy", "OpdepHierarchy", "Stencil5"])
+def test_line_model_equals_line_ref(po, cls, op, transfer, dtype, cycle, real):
+    """both sides are the same numpy statement, in the working type and in long double"""
+    L, Lc = 6, 3
+    smoother = [hm.LINE_ALT, hm.LINE_X, hm.LINE_Y][(dtype + cycle + (op == hm.STENCIL5)) % 3]
+    bottom = hm.SMOOTH if (dtype == hm.F32 and op == hm.STENCIL5) else hm.EXACT
+    mode = hm.FW16 if dtype == hm.F32 else hm.CONSISTENT
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=1, mu2=2, smoother=smoother, dtype=dtype, restrict_mode=mode, bottom=bottom,
+               op=op, schedule=hm.FMG)
+    dt = np.float64 if dtype == hm.F64 else np.float32
+    rt = dt if real == "working" else np.longdouble
+    kw = dict(mode=mode, mu1=1, mu2=2, mu0=0, bottom=bottom)
+    ref = line_reference(po, cls, smoother, "layers", L, Lc, dt, rt, cycle, **kw)
+    m = hm.HandleModel(po, real=None if real == "working" else np.longdouble, **cfg)
+    with pytest.raises(RuntimeError):
+        m.smooth(L, 1)
+    m.set_cycle(cycle)
+    m.set_operator("x1e-2")
+    if op == hm.GALERKIN and transfer == hm.OPERATOR:
+        m.build_galerkin(hm.OPERATOR)
+    m.set_operator("layers")                            # GALERKIN: rebuilt with the transfer in use
+    assert m.transfer == transfer and m.cycle == cycle
+    u, b = data(po, L, dt, 60)
+    m.set_guess(u)
+    m.set_rhs(b)
+    assert m.U[L].dtype == rt
+    m.smooth(L, 2)
+    n2 = float((1 << L) - 1) ** 2
+    per = 2 if smoother == hm.LINE_ALT else 1
+    assert m.fine_updates == per * 2 * n2
+    assert np.array_equal(m.U[L], ref.smooth(L, u.astype(rt), b.astype(rt), 2))
+    m.set_guess(u)
+    m.vcycle()
+    assert m.U[L].dtype == rt and np.array_equal(m.U[L], ref.vcycle(L, u.astype(rt), b.astype(rt)))
+    m.fmg()
+    assert np.array_equal(m.U[L], ref.fmg(b.astype(rt)))
+    m.set_guess(u)
+    st, h = m.solve(tol=0.0, max_cycles=2)
+    u_ref, h_ref = ref.solve(b.astype(rt), u.astype(rt), tol=0.0, max_cycles=2, schedule=gr.FMG)
+    assert np.array_equal(h, h_ref) and np.array_equal(m.U[L], u_ref)
+    assert st["fine_updates"] == 2 * per * 3 * n2
+    # after set_operator: a fresh model given the new operator
+    fresh = hm.HandleModel(po, real=None if real == "working" else np.longdouble, **cfg)
+    fresh.set_cycle(cycle)
+    if op == hm.GALERKIN:
+        fresh.set_stencil(L, operator5(po, L, "x1e-2", dt))
+        fresh.build_galerkin(transfer)
+    else:
+        for lv in range(Lc, L + 1):
+            fresh.set_stencil(lv, operator5(po, lv, "x1e-2", dt))
+    m.set_operator("x1e-2")
+    for x in (m, fresh):
+        x.set_guess(u)
+        x.set_rhs(b)
+        x.vcycle()
+    assert all(np.array_equal(m.U[lv], fresh.U[lv]) and np.array_equal(m.B[lv], fresh.B[lv]) for lv in m.levels())
+    assert not np.array_equal(m.U[L], ref.vcycle(L, u.astype(rt), b.astype(rt)))
+
+
+def test_line_model_refusals(po):
+    with pytest.raises(ValueError):
+        hm.HandleModel(po, smoother=hm.LINE_X)                                   # POISSON
+    with pytest.raises(ValueError):
+        hm.HandleModel(po, real=np.longdouble, op=hm.GALERKIN)                   # long double: line smoothers only
+
+
+@pytest.mark.parametrize("name", list(gs.LINE_CASES))
+def test_the_bounds_of_the_line_sequences_stay_below_the_cap(po, name):
+    """the two models alone, without a device and so without adoption: every bound of THE TOLERANCE RULE that the
+    sequence of a LINE_CASES seed uses stays at or below RTOL64 (double) / PCG32_STATE (float), so holding the device
+    to it says something.  (A bound above the cap means the iterate has converged into the cancellation regime of
+    b - A u: the sequence is changed then, never the cap.)"""
+    cfg, seed, env, options = gs.LINE_CASES[name]
+    calls = gs.draw_sequence(seed, cfg, **gs.LINE_OPTIONS, **options)
+    m, mx = gs.line_models(po, cfg)
+    cap = gs.line_cap(cfg)
+    worst, held = (0.0, None), 0
+    for i, call in enumerate(calls):
+        want, far, bounds = gs.line_call(m, mx, cfg, call)
+        if call[0] in ("solve", "solve_pcg"):
+            assert len(want[1]) == len(far[1]), (i, call, want[1], far[1])
+            assert want[0]["cycles"] == far[0]["cycles"] and want[0]["fine_updates"] == far[0]["fine_updates"]
+        for key, (bound, scale) in bounds.items():
+            held += 1
+            if bound > worst[0]:
+                worst = (bound, (i, call, key))
+    print(f"\n[handle-state] line bounds on the CPU: {name} seed={seed} steps={len(calls)} arrays held to a bound={held} "
+          f"largest bound={worst[0]:.3g} at {worst[1]} (cap {cap:g})")
+    assert held > 100 and 0.0 < worst[0] <= cap, worst
