@@ -370,6 +370,27 @@ MGX_API int mgx_solve(mgx_handle h, double tol, int max_cycles, mgx_stats* stats
 MGX_API int mgx_solve_pcg(mgx_handle h, double tol, int max_iters, mgx_stats* stats,
                           double* history, int history_cap);
 
+/* Restarted GCR with right preconditioning (FGMRES(restart) in exact arithmetic) on the finest level, around one
+ * cycle from zero (mgx_vcycle_zero: any smoother, cycle kind, transfer and bottom of the handle), run to
+ * ||r||_2 <= tol ||r0||_2 or max_iters iterations (absent in the reference).  Neither the operator nor the cycle
+ * need be symmetric; the residual norm never increases.  Per iteration k, j = k mod restart (the basis is emptied
+ * when j = 0):  z = M r;  q = A z;  h_i = (q.Q_i) / s_i for i < j (classical Gram-Schmidt, all dots from the
+ * unmodified q);  q' = ((q - h_0 Q_0) - h_1 Q_1) - ..., z' the same combination of z and Z_i;  s_j = q'.q',
+ * rho = r.q', alpha = rho / s_j;  x += alpha z', r -= alpha q';  Z_j = z', Q_j = q'.
+ * The contract of mgx_solve_pcg: starts from the current U; on return U holds the iterate (also after a breakdown)
+ * and B the caller's b, bit for bit; history[0] = ||b - A u0||, then the norm of the recursively updated residual
+ * after each iteration; stats->cycles = iterations = cycles applied; max_iters = 0 writes one history entry.
+ * Vectors in the working type, dots accumulated in double, scalars doubles on the device; deterministic
+ * (fixed-order reductions, no atomics; graph replay and MGX_GRAPH=0 give the same bits).  A breakdown (q'.q' not a
+ * positive finite number) stops the iteration with stats->converged = 0, MGX_OK and the reason in mgx_last_error.
+ * The first call allocates 2 restart vectors of the finest level (a later, larger restart adds the difference).
+ * Single-GPU handles of dtype F64 or F32, op POISSON, STENCIL5 or GALERKIN; MGX_ERR_STATE on multi-GPU and rank
+ * handles, dtype MIXED and before the operators are set / built; MGX_ERR_INVALID for tol not >= 0, max_iters < 0,
+ * restart < 1 or restart > MGX_GCR_MAX_RESTART. */
+#define MGX_GCR_MAX_RESTART 8
+MGX_API int mgx_solve_gcr(mgx_handle h, double tol, int max_iters, int restart, mgx_stats* stats,
+                          double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -391,6 +412,14 @@ MGX_API int mgx_profile_get(mgx_handle h, mgx_profile* out);
 /* `sweeps` finest-level smoother sweeps bracketed by HIP events on the
  * handle's stream; returns the elapsed milliseconds. */
 MGX_API int mgx_time_smoother(mgx_handle h, int sweeps, double* ms);
+/* Milliseconds per launch of one streaming pass of mgx_solve_gcr at basis slot j, `repeats` launches between two
+ * events on the handle's own buffers (tools/gcr_bench.py).  The scalars are zeroed first, so the passes leave U, B
+ * and the saved iterate unchanged (DIRECTION rewrites basis slot j from U; the basis has no meaning between two
+ * mgx_solve_gcr calls).  UPDATE is k_pcg_update (6 sizeof(T) per point, the yardstick),
+ * DOTS k_gcr_dots<j> (j >= 1), ORTH k_gcr_orth<j>, DIRECTION k_pcg_direction.  MGX_ERR_STATE until a mgx_solve_gcr
+ * call with restart > j has allocated the basis. */
+enum { MGX_GCR_PASS_UPDATE = 0, MGX_GCR_PASS_DOTS = 1, MGX_GCR_PASS_ORTH = 2, MGX_GCR_PASS_DIRECTION = 3 };
+MGX_API int mgx_time_gcr_pass(mgx_handle h, int pass, int j, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

@@ -25,6 +25,7 @@ SMOOTHER_CHEBYSHEV = 2      # Chebyshev polynomial smoother of the general-opera
 # zebra line Gauss-Seidel of the general-operator hierarchies: x-lines, y-lines, x then y (3 is not a smoother)
 SMOOTHER_LINE_X, SMOOTHER_LINE_Y, SMOOTHER_LINE_ALT = 4, 5, 6
 DTYPE_F32, DTYPE_F64, DTYPE_MIXED = 0, 1, 2
+GCR_MAX_RESTART = 8                       # MGX_GCR_MAX_RESTART
 SCHEDULE_V, SCHEDULE_FMG = 0, 1
 RESTRICT_CONSISTENT, RESTRICT_FW16, RESTRICT_INJECT, RESTRICT_INJECT4 = 0, 1, 2, 3
 OPERATOR_POISSON, OPERATOR_STENCIL5 = 0, 1
@@ -49,7 +50,7 @@ EXPORTS = [
     "mgx_plan_create", "mgx_plan_destroy", "mgx_plan_last_error", "mgx_plan_cut_level", "mgx_plan_level",
     "mgx_plan_cut_share", "mgx_plan_guess_set", "mgx_plan_vcycle", "mgx_plan_norm", "mgx_plan_fmg", "mgx_rccl_unique_id",
     "mgx_create_rank", "mgx_dist_exchanges", "mgx_dist_overlapped", "mgx_memcpy_d2h", "mgx_memcpy_h2d", "mgx_runtime_libs",
-    "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg",
+    "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg", "mgx_solve_gcr", "mgx_time_gcr_pass",
     "mgx_build_galerkin", "mgx_get_stencil9",
     "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max", "mgx_get_line_factor", "mgx_get_line_chunks",
     "mgx_set_cycle", "mgx_get_cycle",
@@ -169,8 +170,10 @@ def lib() -> C.CDLL:
     L.mgx_residual_norm.argtypes = [vp, C.c_int, dp]
     L.mgx_solve.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_solve_pcg.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
+    L.mgx_solve_gcr.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_profile_get.argtypes = [vp, C.POINTER(Profile)]
     L.mgx_time_smoother.argtypes = [vp, C.c_int, dp]
+    L.mgx_time_gcr_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     sp = C.POINTER(Slab)
     L.mgx_slab_jacobi.argtypes = [sp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, ip, vp]
     L.mgx_slab_rbgs.argtypes = [sp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, vp]
@@ -593,6 +596,16 @@ class Multigrid:
                                       hist.size), "mgx_solve_pcg")
         return st, hist[: st.history_len].copy()
 
+    def solve_gcr(self, tol=1e-8, max_iters=100, restart=4):
+        """restarted GCR (FGMRES(restart) in exact arithmetic) around one cycle from zero per iteration, from the
+        current guess: for operators and cycles that are not symmetric, 1 <= restart <= GCR_MAX_RESTART; returns
+        (stats, residual history) as solve_pcg() does (stats.cycles = iterations)."""
+        st = Stats()
+        hist = np.zeros(max(max_iters, 0) + 1, dtype=np.float64)
+        self._chk(lib().mgx_solve_gcr(self._h, tol, max_iters, restart, C.byref(st), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                      hist.size), "mgx_solve_gcr")
+        return st, hist[: st.history_len].copy()
+
     # -- measurement -----------------------------------------------------------------
     def profile_reset(self):
         self._chk(lib().mgx_profile_reset(self._h), "mgx_profile_reset")
@@ -605,6 +618,13 @@ class Multigrid:
     def time_smoother(self, sweeps):
         ms = C.c_double()
         self._chk(lib().mgx_time_smoother(self._h, sweeps, C.byref(ms)), "mgx_time_smoother")
+        return ms.value
+
+    def time_gcr_pass(self, which, j, repeats=20):
+        """ms per launch of one pass of solve_gcr at basis slot j: which = 0 k_pcg_update, 1 k_gcr_dots<j>, 2 k_gcr_orth<j>,
+        3 k_pcg_direction; after a solve_gcr with restart > j"""
+        ms = C.c_double()
+        self._chk(lib().mgx_time_gcr_pass(self._h, which, j, repeats, C.byref(ms)), "mgx_time_gcr_pass")
         return ms.value
 
     def graphs_cached(self):

@@ -7,6 +7,7 @@
 //   -DMGX_INST_KIND=4  launch_cheby<T>, launch_lambda_max<T>  (mgx_cheby.hpp: k_cheby_var, k_lambda_partials)
 //   -DMGX_INST_KIND=5  launch_small_visit<T>, small_visit_prepare<T>  (mgx_small.hpp: k_small_visit)
 //   -DMGX_INST_KIND=6  launch_line_factor<T>, launch_line_sweep<T>  (mgx_line.hpp: k_line_factor, k_line_x, k_line_y)
+//   -DMGX_INST_KIND=7  launch_gcr_orth<T>  (mgx_krylov.hpp: k_gcr_dots<T, 1..7>, k_gcr_orth<T, 0..7>, k_gcr_reduce)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
@@ -15,6 +16,8 @@
 #include "mgx_small.hpp"
 #elif MGX_INST_KIND == 6
 #include "mgx_line.hpp"
+#elif MGX_INST_KIND == 7
+#include "mgx_krylov.hpp"
 #endif
 
 namespace mgx {
@@ -45,7 +48,9 @@ template void launch_small_visit<T_>(const SmallVisit<T_>&, hipStream_t);
 #elif MGX_INST_KIND == 6
 template void launch_line_factor<T_>(const LineLevel<T_>&, int, int*, hipStream_t);
 template int launch_line_sweep<T_>(const LineLevel<T_>&, T_*, const T_*, int, hipStream_t);
+#elif MGX_INST_KIND == 7
+template void launch_gcr_orth<T_>(int, T_*, T_*, const T_*, const GcrBasis<T_>&, double*, double*, int, long, const Launch&, int, hipStream_t);
 #else
-#error "MGX_INST_KIND must be 1 .. 6"
+#error "MGX_INST_KIND must be 1 .. 7"
 #endif
 } // namespace mgx

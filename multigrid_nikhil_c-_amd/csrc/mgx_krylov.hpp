@@ -17,6 +17,29 @@
 // buffer): a wave's halo rows and halo lanes are another wave's output.  Dots are accumulated in double whatever
 // T is, per lane, then per wave (shuffles), per workgroup (LDS) and over the workgroups (k_pcg_reduce): the same
 // order on every call - no atomics.  alpha and beta are doubles on the device, rounded to T once where applied.
+//
+// mgx_solve_gcr: restarted GCR with right preconditioning (FGMRES(m) in exact arithmetic), for
+// operators and cycles that are not symmetric.  Vectors in T, dots in double, scalars doubles rounded to T once
+// where they are applied, every elementwise operation rounded separately:
+//   r = b - A x;  h0 = ||r||;  basis empty
+//   iteration k:  j = k mod restart;  if j == 0: basis empty
+//     z = M r                                   (zero-start cycle)
+//     q = A z                                   (stencil order of k_pcg_direction: residual_vec / stencil_sum<5>)
+//     h_i = (q.Q_i) / s_i   for i < j           (classical Gram-Schmidt: all dots from the unmodified q)
+//     q' = ((q - h_0 Q_0) - h_1 Q_1) - ... ;  z' = the same combination of z and Z_i
+//     s_j = q'.q';  rho = r.q';  breakdown unless s_j > 0 and finite;  alpha = rho / s_j
+//     x += alpha z';  r -= alpha q';  history <- sqrt(r.r);  Z_j = z', Q_j = q'
+//     stop when ||r|| <= tol h0 or k + 1 == max_iters
+// per iteration, after the cycle:
+//   k_pcg_direction  first_it = 1: Z_j = z (out of lv.u), Q_j = q = A z        as above       4 (+ 5) sizeof(T)
+//   k_gcr_dots<J>    q.Q_i, i < J (J = j >= 1)               reads q, Q_0 .. Q_{J-1}          (1 + J) sizeof(T)
+//   k_gcr_orth<J>    q', z' in place in slot J, q'.q', r.q'  reads q, z, r, J pairs; writes q', z'
+//                                                                                             (5 + 2J) sizeof(T)
+//                    (J = 0: the two dots only, reads q and r, stores nothing:                2 sizeof(T))
+//   k_pcg_update     x += alpha Z_j, r -= alpha Q_j, ||r||^2                                  6 sizeof(T)
+//   k_gcr_reduce     the partials of k_gcr_dots -> h_i, of k_gcr_orth -> s_j, rho, alpha and the breakdown flag
+// J is a template parameter (dispatched by a switch on the host): accumulators and basis pointers indexed by a
+// compile-time count stay in registers and kernel arguments, a run-time count would send them to scratch.
 #pragma once
 
 #include "mgx_kernels.hpp"
@@ -198,7 +221,7 @@ __device__ __forceinline__ double pcg_reduce_sum(const double* __restrict__ part
 //   kPcgAlphaMode:  delta = p.q; alpha = rho / delta, or a breakdown (delta not > 0 or not finite: alpha = 0)
 //   kPcgRRMode:     ||r||^2
 //   kPcgBetaMode:   rho_new = r.z, gamma = z.q; beta = -alpha gamma / rho; rho = rho_new
-__global__ void __launch_bounds__(kReduceThreads) k_pcg_reduce(const double* __restrict__ part, int n, int mode, double* __restrict__ sc)
+static __global__ void __launch_bounds__(kReduceThreads) k_pcg_reduce(const double* __restrict__ part, int n, int mode, double* __restrict__ sc)
 {
     __shared__ double wsum[kReduceThreads / kWave];
     const double s0 = pcg_reduce_sum(part, n, wsum);
@@ -219,5 +242,156 @@ __global__ void __launch_bounds__(kReduceThreads) k_pcg_reduce(const double* __r
         sc[kPcgRho] = s0;
     }
 }
+
+// ---- mgx_solve_gcr ------------------------------------------------------------------------------------------------
+constexpr int kGcrMaxRestart = 8;              // MGX_GCR_MAX_RESTART
+// the scalar block of one GCR solve: the first kPcgScalars slots are k_pcg_update's and k_pcg_reduce's (rho = r.q',
+// delta = s_j = q'.q', alpha, ||r||^2, the breakdown flag), then s_i of the basis and h_i of this iteration
+enum { kGcrS = kPcgScalars, kGcrH = kGcrS + kGcrMaxRestart, kGcrScalars = kGcrH + kGcrMaxRestart };
+enum { kGcrHMode = 0, kGcrAlphaMode = 1 };
+
+// the earlier vectors of the basis, by value: Q_i = A Z_i, i < J <= 7
+template <typename T> struct GcrBasis { const T* Q[kGcrMaxRestart - 1]; const T* Z[kGcrMaxRestart - 1]; };
+
+// q.Q_i -> partial[i nb + b], i < J   (nb = gridDim.x)
+template <typename T, int J>
+__global__ void __launch_bounds__(kBlock)
+k_gcr_dots(const T* __restrict__ q, GcrBasis<T> bs, double* __restrict__ partial, int N, long pitch, int R, int strips, int chunks)
+{
+    using V = typename VecOf<T>::type;
+    constexpr int W = VecOf<T>::W;
+    __shared__ double wsum[J][kWavesPerBlock];
+    const Tile t = wave_tile(strips, chunks);
+    double acc[J];
+#pragma unroll
+    for (int i = 0; i < J; ++i) acc[i] = 0.0;
+    if (t.active) {
+        const Cols c = lane_cols<W>(t.strip, N, pitch);
+        const int r0 = 1 + t.chunk * R;
+        const int r1 = min(r0 + R, N);
+        if (c.st) {
+            for (int y = r0; y < r1; ++y) {
+                const long at = c.col + (long)y * pitch;
+                const V qq = vload<V>(q + at, true);
+#pragma unroll
+                for (int i = 0; i < J; ++i) acc[i] += vdot(qq, vload<V>(bs.Q[i] + at, true));
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < J; ++i) block_reduce<kWavesPerBlock>(acc[i], wsum[i], partial + (long)i * gridDim.x + blockIdx.x, ReduceSum{});
+}
+
+// q' = ((q - h_0 Q_0) - h_1 Q_1) - ..., z' likewise from z and Z_i, both in place (slot J: a lane reads and writes its
+// own vector only); q'.q' -> partial[b], r.q' -> partial[nb + b].  J = 0: q' = q and z' = z, nothing is stored.
+template <typename T, int J>
+__global__ void __launch_bounds__(kBlock)
+k_gcr_orth(T* q, T* z, const T* __restrict__ r, GcrBasis<T> bs, const double* __restrict__ sc, double* __restrict__ partial,
+           int N, long pitch, int R, int strips, int chunks)
+{
+    using V = typename VecOf<T>::type;
+    constexpr int W = VecOf<T>::W;
+    __shared__ double wsum[2][kWavesPerBlock];
+    const Tile t = wave_tile(strips, chunks);
+    double ss = 0.0, rq = 0.0;
+    if (t.active) {
+        T h[J > 0 ? J : 1];
+#pragma unroll
+        for (int i = 0; i < J; ++i) h[i] = (T)sc[kGcrH + i];
+        const Cols c = lane_cols<W>(t.strip, N, pitch);
+        const int r0 = 1 + t.chunk * R;
+        const int r1 = min(r0 + R, N);
+        if (c.st) {
+            for (int y = r0; y < r1; ++y) {
+                const long at = c.col + (long)y * pitch;
+                V qq = vload<V>(q + at, true);
+                const V rr = vload<V>(r + at, true);
+                if constexpr (J > 0) {
+                    V zz = vload<V>(z + at, true);
+#pragma unroll
+                    for (int i = 0; i < J; ++i) {
+                        qq = vaxmy(qq, h[i], vload<V>(bs.Q[i] + at, true));
+                        zz = vaxmy(zz, h[i], vload<V>(bs.Z[i] + at, true));
+                    }
+                    mask_cols(qq, c.col, N);
+                    mask_cols(zz, c.col, N);
+                    vstore<V>(q + at, qq, true);
+                    vstore<V>(z + at, zz, true);
+                }
+                ss += vdot(qq, qq);
+                rq += vdot(rr, qq);
+            }
+        }
+    }
+    block_reduce<kWavesPerBlock>(ss, wsum[0], partial + blockIdx.x, ReduceSum{});
+    block_reduce<kWavesPerBlock>(rq, wsum[1], partial + (long)gridDim.x + blockIdx.x, ReduceSum{});
+}
+
+// one workgroup, after the pass whose partials it sums (n per dot, in the order of k_pcg_reduce):
+//   kGcrHMode:      h_i = (q.Q_i) / s_i for i < j
+//   kGcrAlphaMode:  s_j = q'.q' (kept for the later iterations of this restart cycle, and in k_pcg_update's delta
+//                   slot), rho = r.q'; alpha = rho / s_j, or a breakdown (s_j not > 0 or not finite: alpha = 0)
+static __global__ void __launch_bounds__(kReduceThreads) k_gcr_reduce(const double* __restrict__ part, int n, int mode, int j, double* __restrict__ sc)
+{
+    __shared__ double wsum[kReduceThreads / kWave];
+    if (mode == kGcrHMode) {
+        for (int i = 0; i < j; ++i) {
+            const double d = pcg_reduce_sum(part + (long)i * n, n, wsum);
+            if (threadIdx.x == 0) sc[kGcrH + i] = d / sc[kGcrS + i];
+        }
+        return;
+    }
+    const double s = pcg_reduce_sum(part, n, wsum);
+    const double rho = pcg_reduce_sum(part + n, n, wsum);
+    if (threadIdx.x != 0) return;
+    const bool ok = (s > 0.0) && isfinite(s);
+    sc[kPcgDelta] = s;
+    sc[kPcgRho] = rho;
+    sc[kPcgAlpha] = ok ? rho / s : 0.0;
+    sc[kPcgBreak] = ok ? 0.0 : 1.0;
+    sc[kGcrS + j] = s;
+}
+
+// the two passes of iteration j = k mod restart (after k_pcg_direction has left z in zj and q = A z in qj), each
+// followed by its reduction; bs holds the j earlier pairs.  passes: all of them in the solve; mgx_time_gcr_pass
+// launches one streaming pass alone
+enum { kGcrDotsPass = 1, kGcrOrthPass = 2, kGcrReducePass = 4, kGcrAllPasses = 7 };
+template <typename T, int J>
+void launch_gcr_orth_j(T* qj, T* zj, const T* r, const GcrBasis<T>& bs, double* sc, double* part, int N, long pitch, const Launch& g,
+                       int passes, hipStream_t st)
+{
+    const bool red = passes & kGcrReducePass;
+    if constexpr (J > 0) {
+        if (passes & kGcrDotsPass)
+            hipLaunchKernelGGL((k_gcr_dots<T, J>), dim3(g.blocks), dim3(kBlock), 0, st, (const T*)qj, bs, part, N, pitch, g.R, g.strips, g.chunks);
+        if (red) hipLaunchKernelGGL(k_gcr_reduce, dim3(1), dim3(kReduceThreads), 0, st, part, g.blocks, (int)kGcrHMode, J, sc);
+    }
+    if (passes & kGcrOrthPass)
+        hipLaunchKernelGGL((k_gcr_orth<T, J>), dim3(g.blocks), dim3(kBlock), 0, st, qj, zj, r, bs, (const double*)sc, part, N, pitch, g.R, g.strips,
+                           g.chunks);
+    if (red) hipLaunchKernelGGL(k_gcr_reduce, dim3(1), dim3(kReduceThreads), 0, st, part, g.blocks, (int)kGcrAlphaMode, J, sc);
+}
+
+template <typename T>
+void launch_gcr_orth(int j, T* qj, T* zj, const T* r, const GcrBasis<T>& bs, double* sc, double* part, int N, long pitch, const Launch& g,
+                     int passes, hipStream_t st)
+{
+    switch (j) {
+        case 0: launch_gcr_orth_j<T, 0>(qj, zj, r, bs, sc, part, N, pitch, g, passes, st); break;
+        case 1: launch_gcr_orth_j<T, 1>(qj, zj, r, bs, sc, part, N, pitch, g, passes, st); break;
+        case 2: launch_gcr_orth_j<T, 2>(qj, zj, r, bs, sc, part, N, pitch, g, passes, st); break;
+        case 3: launch_gcr_orth_j<T, 3>(qj, zj, r, bs, sc, part, N, pitch, g, passes, st); break;
+        case 4: launch_gcr_orth_j<T, 4>(qj, zj, r, bs, sc, part, N, pitch, g, passes, st); break;
+        case 5: launch_gcr_orth_j<T, 5>(qj, zj, r, bs, sc, part, N, pitch, g, passes, st); break;
+        case 6: launch_gcr_orth_j<T, 6>(qj, zj, r, bs, sc, part, N, pitch, g, passes, st); break;
+        default: launch_gcr_orth_j<T, 7>(qj, zj, r, bs, sc, part, N, pitch, g, passes, st); break;
+    }
+}
+
+// mgx.hip declares these instantiations; mgx_inst.hip (-DMGX_INST_KIND=7) defines them
+#if !defined(MGX_INST_KIND) && !defined(MGX_SINGLE_TU)
+extern template void launch_gcr_orth<double>(int, double*, double*, const double*, const GcrBasis<double>&, double*, double*, int, long, const Launch&, int, hipStream_t);
+extern template void launch_gcr_orth<float>(int, float*, float*, const float*, const GcrBasis<float>&, double*, double*, int, long, const Launch&, int, hipStream_t);
+#endif
 
 } // namespace mgx
