@@ -132,16 +132,22 @@ struct mgx_solver {
     int line_dirs = 0;              // MGX_SMOOTHER_LINE_*: bit 0 x-lines, bit 1 y-lines (0: another smoother)
     int* line_flag = nullptr;       // device: bit d raised by k_line_factor on a zero or non-finite pivot in direction d
     int transfer = MGX_TRANSFER_BILINEAR;   // ... with this prolongation (mgx_build_galerkin_transfer)
-    // mgx_solve_pcg (allocated by its first call): iterate x, directions p / p' (ping-pong), q = A p, the caller's b
-    // while r occupies lv[finest].b, per-block partials of the Krylov passes, the device scalars and their host copy
-    void *pcg_x = nullptr, *pcg_p[2] = {nullptr, nullptr}, *pcg_q = nullptr, *pcg_b = nullptr;
-    double *pcg_part = nullptr, *pcg_sc = nullptr, *pcg_sc_host = nullptr;
-    long pcg_part_cap = 0;
-    // mgx_solve_gcr (allocated by its first call, grown by a larger restart): the basis pairs Z_i, Q_i = A Z_i, its
-    // partial sums and scalar block.  x and the caller's b share pcg_x / pcg_b
-    void *gcr_z[kGcrMaxRestart] = {}, *gcr_q[kGcrMaxRestart] = {};
-    double *gcr_part = nullptr, *gcr_sc = nullptr, *gcr_sc_host = nullptr;
-    long gcr_part_cap = 0;
+    // mgx_solve_pcg and mgx_solve_gcr (mgx_krylov_host.hpp): one workspace, every piece allocated by the first call
+    // that needs it.  Both methods run on the one scalar block, PCG on its first kPcgScalars slots, and neither
+    // depends on what the other left there: GCR zeroes the block before it starts; PCG's kPcgInit reduction writes
+    // rho, beta and the breakdown flag before anything reads them; alpha and ||r||^2 are written before they are
+    // read in every iteration; mgx_time_gcr_pass zeroes the block and leaves it zeroed.
+    struct KrylovWs {
+        void *x = nullptr, *b = nullptr;            // the iterate; the caller's b while r occupies lv[finest].b
+        void *p[2] = {nullptr, nullptr}, *q = nullptr;               // PCG: the directions p / p' (ping-pong), q = A p
+        void *Z[kGcrMaxRestart] = {}, *Q[kGcrMaxRestart] = {};       // GCR: the basis pairs Z_i, Q_i = A Z_i (restart of them)
+        double* part = nullptr;                     // per-block partials of one pass, sized for the widest (k_gcr_dots<T, 7>)
+        long part_cap = 0;
+        double *sc = nullptr, *sc_host = nullptr;   // kGcrScalars device scalars (mgx_krylov.hpp) and their pinned host copy
+        int vecs(mgx_solver* s, std::initializer_list<void**> vs, size_t bytes);
+        int shared(mgx_solver* s, size_t bytes, int blocks);
+        void free();
+    } kry;
     struct mgx_dist* dist = nullptr; // multi-GPU handle (cfg.n_gpus > 1 / mgx_create_rank): mgx_dist.hpp; no levels of its own
 
     int fail(int code, const std::string& m) { err = m; return code; }
@@ -1224,240 +1230,30 @@ void fold_ring(std::vector<T>& b, const T* ring, size_t n)
         b[i * n + (n - 1)] += rig[i];
     }
 }
-// ---- conjugate gradients preconditioned by one V-cycle (absent in the reference; mgx_krylov.hpp) ----------------
-int pcg_alloc(mgx_solver* s, const Level& l, const Launch& g)
-{
-    for (void** p : {&s->pcg_x, &s->pcg_p[0], &s->pcg_p[1], &s->pcg_q, &s->pcg_b}) {
-        if (*p) continue;
-        if (hipMalloc(p, l.bytes) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the PCG vectors");
-        HIPCHK(s, hipMemsetAsync(*p, 0, l.bytes, s->stream));       // the ring and the padding stay zero from here on
-    }
-    if (!s->pcg_part) {
-        s->pcg_part_cap = 2L * g.blocks + 8;                           // k_pcg_dots writes two partials per workgroup
-        if (hipMalloc(&s->pcg_part, s->pcg_part_cap * sizeof(double)) != hipSuccess)
-            return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the PCG partial sums");
-    }
-    if (!s->pcg_sc && hipMalloc(&s->pcg_sc, kPcgScalars * sizeof(double)) != hipSuccess)
-        return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the PCG scalars");
-    if (!s->pcg_sc_host && hipHostMalloc(&s->pcg_sc_host, kPcgScalars * sizeof(double)) != hipSuccess)
-        return s->fail(MGX_ERR_ALLOC, "hipHostMalloc failed for the PCG scalars");
-    if (2L * g.blocks > s->pcg_part_cap) return s->fail(MGX_ERR_STATE, "PCG partial-sum buffer smaller than its launch");
-    return MGX_OK;
-}
 
-inline void pcg_reduce(mgx_solver* s, int n, int mode)
+// the milliseconds the GPU spends on what `enqueue` puts on the handle's stream, between two events that are
+// destroyed on every path
+template <typename Enqueue>
+int time_on_stream(mgx_solver* s, double* ms, Enqueue enqueue)
 {
-    hipLaunchKernelGGL(k_pcg_reduce, dim3(1), dim3(kReduceThreads), 0, s->stream, s->pcg_part, n, mode, s->pcg_sc);
-}
-
-// rho_new = r.z, gamma = z.q (r = B, z = U of the finest level); mode kPcgInit or kPcgBetaMode
-template <typename T>
-void pcg_dots(mgx_solver* s, const Level& l, const Launch& g, int mode)
-{
-    hipLaunchKernelGGL((k_pcg_dots<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.b, (const T*)l.u,
-                       (const T*)s->pcg_q, s->pcg_part, l.N, l.pitch, g.R, g.strips, g.chunks);
-    pcg_reduce(s, g.blocks, mode);
-}
-
-// p' = z + beta p, q = A p', alpha = rho / p'.q; then x += alpha p', r -= alpha q and ||r||^2
-template <typename T>
-void pcg_step(mgx_solver* s, const Level& l, const Launch& g, bool first_it, int& pp)
-{
-    const T* z = (const T*)l.u;
-    const T* p = (const T*)s->pcg_p[pp];
-    T* pn = (T*)s->pcg_p[pp ^ 1];
-    if (s->var)
-        hipLaunchKernelGGL((k_pcg_direction<T, 1>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, p, pn, (T*)s->pcg_q, s->pcg_sc,
-                           first_it ? 1 : 0, s->pcg_part, op9_of<T>(l), l.N, l.pitch, g.R, g.strips, g.chunks);
-    else
-        hipLaunchKernelGGL((k_pcg_direction<T, 0>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, p, pn, (T*)s->pcg_q, s->pcg_sc,
-                           first_it ? 1 : 0, s->pcg_part, Op9<T>{}, l.N, l.pitch, g.R, g.strips, g.chunks);
-    pcg_reduce(s, g.blocks, kPcgAlphaMode);
-    pp ^= 1;
-    hipLaunchKernelGGL((k_pcg_update<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)s->pcg_x, (const T*)pn, (T*)l.b,
-                       (const T*)s->pcg_q, s->pcg_sc, s->pcg_part, l.N, l.pitch, g.R, g.strips, g.chunks);
-    pcg_reduce(s, g.blocks, kPcgRRMode);
-}
-
-// The iteration proper.  r lives in lv[L].b for the whole solve: it is the V-cycle's right-hand side, and the cached
-// cycle graphs hold that pointer (they are keyed on the u / tmp pointers only).  The caller's b waits in pcg_b.
-template <typename T>
-int pcg_run(mgx_solver* s, double tol, int max_iters, std::vector<double>& hist, int* iters, int* breakdown)
-{
-    Level& l = s->lv[s->cfg.finest_level];
-    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, s->rows_per_chunk);
-    int rc = pcg_alloc(s, l, g);
-    if (rc) return rc;
-    HIPCHK(s, hipMemcpyAsync(s->pcg_x, l.u, l.bytes, hipMemcpyDeviceToDevice, s->stream));
-    HIPCHK(s, hipMemcpyAsync(s->pcg_b, l.b, l.bytes, hipMemcpyDeviceToDevice, s->stream));
-    s->norm_blocks_ready = 0;
-    double h0 = 0.0;
-    if ((rc = residual_norm_grid(s, l, s->pcg_x, s->pcg_b, &h0, MGX_PROF_NORM_FINE))) return rc;
-    hist.push_back(h0);
-    if (h0 <= tol * h0 || max_iters == 0) return MGX_OK;               // (b = 0, u = 0: converged, nothing divided)
-    // r = b - A x, into lv[L].b
-    residual_level<0>(s, l, s->pcg_x, s->pcg_b, l.b);
-    double unused = 0.0;
-    if ((rc = cycle_body(s, false, true, &unused))) return rc;         // z = M r: one V-cycle from zero, into lv[L].u
-    pcg_dots<T>(s, l, g, kPcgInit);                                    // rho = r.z; p = z (first pcg_step)
-    int pp = 0;
-    for (int k = 0; k < max_iters; ++k) {
-        pcg_step<T>(s, l, g, k == 0, pp);
+    hipEvent_t a = nullptr, b = nullptr;
+    auto timed = [&]() -> int {
+        HIPCHK(s, hipEventCreate(&a));
+        HIPCHK(s, hipEventCreate(&b));
+        HIPCHK(s, hipEventRecord(a, s->stream));
+        enqueue();
+        HIPCHK(s, hipEventRecord(b, s->stream));
+        HIPCHK(s, hipEventSynchronize(b));
         HIPCHK(s, hipGetLastError());
-        HIPCHK(s, hipMemcpyAsync(s->pcg_sc_host, s->pcg_sc, kPcgScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(s, hipStreamSynchronize(s->stream));                    // the one host synchronisation per iteration
-        if (s->pcg_sc_host[kPcgBreak] != 0.0) {
-            *breakdown = 1;
-            char m[160];
-            std::snprintf(m, sizeof m, "PCG breakdown at iteration %d: p.Ap = %.17g is not a positive finite number", k + 1,
-                          s->pcg_sc_host[kPcgDelta]);
-            s->err = m;
-            return MGX_OK;
-        }
-        *iters = k + 1;
-        const double rn = std::sqrt(s->pcg_sc_host[kPcgRR]);
-        hist.push_back(rn);
-        if (rn <= tol * h0 || k + 1 == max_iters) break;
-        if ((rc = cycle_body(s, false, true, &unused))) return rc;     // z = M r
-        pcg_dots<T>(s, l, g, kPcgBetaMode);                            // beta = -alpha z.q / rho, rho = r.z
-    }
-    return MGX_OK;
-}
-
-// ---- restarted GCR around one cycle (absent in the reference; mgx_krylov.hpp) -------------------------
-int gcr_alloc(mgx_solver* s, const Level& l, const Launch& g, int restart)
-{
-    auto vec = [&](void** p) -> int {
-        if (*p) return MGX_OK;
-        if (hipMalloc(p, l.bytes) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the GCR vectors");
-        HIPCHK(s, hipMemsetAsync(*p, 0, l.bytes, s->stream));          // the ring and the padding stay zero from here on
+        float f = 0.f;
+        HIPCHK(s, hipEventElapsedTime(&f, a, b));
+        *ms = f;
         return MGX_OK;
     };
-    for (void** p : {&s->pcg_x, &s->pcg_b})
-        if (int rc = vec(p)) return rc;
-    for (int i = 0; i < restart; ++i) {
-        if (int rc = vec(&s->gcr_z[i])) return rc;
-        if (int rc = vec(&s->gcr_q[i])) return rc;
-    }
-    if (!s->gcr_part) {
-        s->gcr_part_cap = (long)(kGcrMaxRestart - 1) * g.blocks + 8;   // k_gcr_dots<T, 7> writes seven partials per workgroup
-        if (hipMalloc(&s->gcr_part, s->gcr_part_cap * sizeof(double)) != hipSuccess)
-            return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the GCR partial sums");
-    }
-    if (!s->gcr_sc && hipMalloc(&s->gcr_sc, kGcrScalars * sizeof(double)) != hipSuccess)
-        return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the GCR scalars");
-    if (!s->gcr_sc_host && hipHostMalloc(&s->gcr_sc_host, kGcrScalars * sizeof(double)) != hipSuccess)
-        return s->fail(MGX_ERR_ALLOC, "hipHostMalloc failed for the GCR scalars");
-    if ((long)(kGcrMaxRestart - 1) * g.blocks > s->gcr_part_cap) return s->fail(MGX_ERR_STATE, "GCR partial-sum buffer smaller than its launch");
-    return MGX_OK;
-}
-
-// the earlier pairs of an iteration, by value (slots that are not allocated are never read: J < restart)
-template <typename T> GcrBasis<T> gcr_basis(const mgx_solver* s)
-{
-    GcrBasis<T> bs{};
-    for (int i = 0; i < kGcrMaxRestart - 1; ++i) { bs.Q[i] = (const T*)s->gcr_q[i]; bs.Z[i] = (const T*)s->gcr_z[i]; }
-    return bs;
-}
-
-// Z_j = z (out of lv.u), Q_j = A z: k_pcg_direction's first iteration (its own partials z.q are not used)
-template <typename T>
-void gcr_direction(mgx_solver* s, const Level& l, const Launch& g, T* zj, T* qj)
-{
-    if (s->var)
-        hipLaunchKernelGGL((k_pcg_direction<T, 1>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.u, (const T*)l.u, zj, qj,
-                           s->gcr_sc, 1, s->gcr_part, op9_of<T>(l), l.N, l.pitch, g.R, g.strips, g.chunks);
-    else
-        hipLaunchKernelGGL((k_pcg_direction<T, 0>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.u, (const T*)l.u, zj, qj,
-                           s->gcr_sc, 1, s->gcr_part, Op9<T>{}, l.N, l.pitch, g.R, g.strips, g.chunks);
-}
-
-template <typename T>
-void gcr_update(mgx_solver* s, const Level& l, const Launch& g, const T* zj, const T* qj)
-{
-    hipLaunchKernelGGL((k_pcg_update<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)s->pcg_x, zj, (T*)l.b, qj, s->gcr_sc, s->gcr_part,
-                       l.N, l.pitch, g.R, g.strips, g.chunks);
-}
-
-// mgx_time_gcr_pass: `repeats` launches of one pass between two events.  The scalar block is zeroed first, so every
-// h_i and alpha is 0 and the update and orthogonalisation leave x, r and slot j as they are (finite values: v - 0 w = v);
-// the direction pass rewrites slot j from lv.u, which no later solve reads before writing it
-template <typename T>
-int gcr_time_pass(mgx_solver* s, int pass, int j, int repeats, double* ms)
-{
-    Level& l = s->lv[s->cfg.finest_level];
-    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, s->rows_per_chunk);
-    const GcrBasis<T> bs = gcr_basis<T>(s);
-    T* zj = (T*)s->gcr_z[j];
-    T* qj = (T*)s->gcr_q[j];
-    HIPCHK(s, hipMemsetAsync(s->gcr_sc, 0, kGcrScalars * sizeof(double), s->stream));
-    hipEvent_t a, b;
-    HIPCHK(s, hipEventCreate(&a));
-    HIPCHK(s, hipEventCreate(&b));
-    HIPCHK(s, hipEventRecord(a, s->stream));
-    for (int i = 0; i < repeats; ++i) {
-        if (pass == MGX_GCR_PASS_UPDATE) gcr_update<T>(s, l, g, zj, qj);
-        else if (pass == MGX_GCR_PASS_DIRECTION) gcr_direction<T>(s, l, g, zj, qj);
-        else launch_gcr_orth<T>(j, qj, zj, (const T*)l.b, bs, s->gcr_sc, s->gcr_part, l.N, l.pitch, g,
-                                pass == MGX_GCR_PASS_DOTS ? kGcrDotsPass : kGcrOrthPass, s->stream);
-    }
-    HIPCHK(s, hipEventRecord(b, s->stream));
-    HIPCHK(s, hipEventSynchronize(b));
-    HIPCHK(s, hipGetLastError());
-    float f = 0.f;
-    HIPCHK(s, hipEventElapsedTime(&f, a, b));
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    *ms = (double)f / repeats;
-    return MGX_OK;
-}
-
-// The iteration of mgx_krylov.hpp's header.  As in pcg_run, r lives in lv[L].b for the whole solve (the cached cycle
-// graphs hold that pointer), x in pcg_x and the caller's b in pcg_b.
-template <typename T>
-int gcr_run(mgx_solver* s, double tol, int max_iters, int restart, std::vector<double>& hist, int* iters, int* breakdown)
-{
-    Level& l = s->lv[s->cfg.finest_level];
-    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, s->rows_per_chunk);
-    int rc = gcr_alloc(s, l, g, restart);
-    if (rc) return rc;
-    HIPCHK(s, hipMemcpyAsync(s->pcg_x, l.u, l.bytes, hipMemcpyDeviceToDevice, s->stream));
-    HIPCHK(s, hipMemcpyAsync(s->pcg_b, l.b, l.bytes, hipMemcpyDeviceToDevice, s->stream));
-    HIPCHK(s, hipMemsetAsync(s->gcr_sc, 0, kGcrScalars * sizeof(double), s->stream));
-    s->norm_blocks_ready = 0;
-    double h0 = 0.0;
-    if ((rc = residual_norm_grid(s, l, s->pcg_x, s->pcg_b, &h0, MGX_PROF_NORM_FINE))) return rc;
-    hist.push_back(h0);
-    if (h0 <= tol * h0 || max_iters == 0) return MGX_OK;               // (b = 0, u = 0: converged, nothing divided)
-    residual_level<0>(s, l, s->pcg_x, s->pcg_b, l.b);                  // r = b - A x, into lv[L].b
-    const GcrBasis<T> bs = gcr_basis<T>(s);
-    double unused = 0.0;
-    for (int k = 0; k < max_iters; ++k) {
-        const int j = k % restart;
-        if ((rc = cycle_body(s, false, true, &unused))) return rc;     // z = M r: one cycle from zero, into lv[L].u
-        T* zj = (T*)s->gcr_z[j];
-        T* qj = (T*)s->gcr_q[j];
-        gcr_direction<T>(s, l, g, zj, qj);
-        launch_gcr_orth<T>(j, qj, zj, (const T*)l.b, bs, s->gcr_sc, s->gcr_part, l.N, l.pitch, g, kGcrAllPasses, s->stream);
-        gcr_update<T>(s, l, g, (const T*)zj, (const T*)qj);
-        hipLaunchKernelGGL(k_pcg_reduce, dim3(1), dim3(kReduceThreads), 0, s->stream, s->gcr_part, g.blocks, (int)kPcgRRMode, s->gcr_sc);
-        HIPCHK(s, hipGetLastError());
-        HIPCHK(s, hipMemcpyAsync(s->gcr_sc_host, s->gcr_sc, kGcrScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(s, hipStreamSynchronize(s->stream));                    // the one host synchronisation per iteration
-        if (s->gcr_sc_host[kPcgBreak] != 0.0) {
-            *breakdown = 1;
-            char m[160];
-            std::snprintf(m, sizeof m, "GCR breakdown at iteration %d: q'.q' = %.17g is not a positive finite number", k + 1,
-                          s->gcr_sc_host[kPcgDelta]);
-            s->err = m;
-            return MGX_OK;
-        }
-        *iters = k + 1;
-        const double rn = std::sqrt(s->gcr_sc_host[kPcgRR]);
-        hist.push_back(rn);
-        if (rn <= tol * h0 || k + 1 == max_iters) break;
-    }
-    return MGX_OK;
+    const int rc = timed();
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+    return rc;
 }
 
 } // namespace
@@ -1467,6 +1263,8 @@ int gcr_run(mgx_solver* s, double tol, int max_iters, int restart, std::vector<d
 // entry points that make no sense on a multi-GPU handle
 #define NO_DIST(s)                                                                        \
     if ((s)->dist) return (s)->fail(MGX_ERR_STATE, "not available on a multi-GPU handle (see mgx.h, Multi-GPU)");
+
+#include "mgx_krylov_host.hpp"
 
 // =====================================================================================
 // C-ABI
@@ -1688,12 +1486,7 @@ int mgx_destroy(mgx_handle s)
     if (s->line_flag) (void)hipFree(s->line_flag);
     if (s->sum_host) (void)hipHostFree(s->sum_host);
     for (double* p : {s->var_M, s->var_inv, s->var_pm, s->var_pi}) if (p) (void)hipFree(p);
-    for (void* p : {s->pcg_x, s->pcg_p[0], s->pcg_p[1], s->pcg_q, s->pcg_b, (void*)s->pcg_part, (void*)s->pcg_sc}) if (p) (void)hipFree(p);
-    if (s->pcg_sc_host) (void)hipHostFree(s->pcg_sc_host);
-    for (int i = 0; i < kGcrMaxRestart; ++i)
-        for (void* p : {s->gcr_z[i], s->gcr_q[i]}) if (p) (void)hipFree(p);
-    for (double* p : {s->gcr_part, s->gcr_sc}) if (p) (void)hipFree(p);
-    if (s->gcr_sc_host) (void)hipHostFree(s->gcr_sc_host);
+    s->kry.free();
     drop_graphs(s);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2282,62 +2075,15 @@ int mgx_solve(mgx_handle s, double tol, int max_cycles, mgx_stats* stats, double
 
 int mgx_solve_pcg(mgx_handle s, double tol, int max_iters, mgx_stats* stats, double* history, int history_cap)
 {
-    if (!s) return MGX_ERR_INVALID;
-    NO_DIST(s)
-    if (s->mixed) return s->fail(MGX_ERR_STATE, "mgx_solve_pcg: dtype MIXED is not supported (F64 or F32 handles)");
-    if (max_iters < 0 || !(tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_solve_pcg: tol >= 0 and max_iters >= 0 required");
-    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
-    Level& l = s->lv[s->cfg.finest_level];
-    std::vector<double> hist;
-    hist.reserve(max_iters + 1);
-    s->fine_updates = 0.0;
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    int iters = 0, breakdown = 0;
-    const int rc = s->work_f64 ? pcg_run<double>(s, tol, max_iters, hist, &iters, &breakdown)
-                               : pcg_run<float>(s, tol, max_iters, hist, &iters, &breakdown);
-    // U = x, B = the caller's b again (also after a failure part way, where they were saved)
-    if (s->pcg_x && !hist.empty()) {
-        (void)hipMemcpyAsync(l.u, s->pcg_x, l.bytes, hipMemcpyDeviceToDevice, s->stream);
-        (void)hipMemcpyAsync(l.b, s->pcg_b, l.bytes, hipMemcpyDeviceToDevice, s->stream);
-    }
-    s->norm_blocks_ready = 0;
-    if (rc) return rc;
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    finish_solve(stats, history, history_cap, hist, iters, !breakdown && hist.back() <= tol * hist.front(), t0, s->fine_updates);
-    return MGX_OK;
+    return krylov_solve(s, "mgx_solve_pcg", nullptr, tol, max_iters, stats, history, history_cap, [](auto t) { return PcgMethod<decltype(t)>{}; });
 }
 
 int mgx_solve_gcr(mgx_handle s, double tol, int max_iters, int restart, mgx_stats* stats, double* history, int history_cap)
 {
     static_assert(kGcrMaxRestart == MGX_GCR_MAX_RESTART, "mgx_krylov.hpp and mgx.h disagree");
-    if (!s) return MGX_ERR_INVALID;
-    NO_DIST(s)
-    if (s->mixed) return s->fail(MGX_ERR_STATE, "mgx_solve_gcr: dtype MIXED is not supported (F64 or F32 handles)");
-    if (max_iters < 0 || !(tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_solve_gcr: tol >= 0 and max_iters >= 0 required");
-    if (restart < 1 || restart > MGX_GCR_MAX_RESTART) return s->fail(MGX_ERR_INVALID, "mgx_solve_gcr: 1 <= restart <= MGX_GCR_MAX_RESTART required");
-    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
-    Level& l = s->lv[s->cfg.finest_level];
-    std::vector<double> hist;
-    hist.reserve(max_iters + 1);
-    s->fine_updates = 0.0;
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    int iters = 0, breakdown = 0;
-    const int rc = s->work_f64 ? gcr_run<double>(s, tol, max_iters, restart, hist, &iters, &breakdown)
-                               : gcr_run<float>(s, tol, max_iters, restart, hist, &iters, &breakdown);
-    // U = x, B = the caller's b again (also after a failure part way, where they were saved)
-    if (s->pcg_x && s->pcg_b && !hist.empty()) {
-        (void)hipMemcpyAsync(l.u, s->pcg_x, l.bytes, hipMemcpyDeviceToDevice, s->stream);
-        (void)hipMemcpyAsync(l.b, s->pcg_b, l.bytes, hipMemcpyDeviceToDevice, s->stream);
-    }
-    s->norm_blocks_ready = 0;
-    if (rc) return rc;
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    finish_solve(stats, history, history_cap, hist, iters, !breakdown && hist.back() <= tol * hist.front(), t0, s->fine_updates);
-    return MGX_OK;
+    const char* bad_restart = (restart < 1 || restart > MGX_GCR_MAX_RESTART) ? "1 <= restart <= MGX_GCR_MAX_RESTART required" : nullptr;
+    return krylov_solve(s, "mgx_solve_gcr", bad_restart, tol, max_iters, stats, history, history_cap,
+                        [restart](auto t) { return GcrMethod<decltype(t)>{restart}; });
 }
 
 int mgx_time_gcr_pass(mgx_handle s, int pass, int j, int repeats, double* ms)
@@ -2350,7 +2096,7 @@ int mgx_time_gcr_pass(mgx_handle s, int pass, int j, int repeats, double* ms)
     if (s->mixed) return s->fail(MGX_ERR_STATE, "mgx_time_gcr_pass: dtype MIXED is not supported");
     if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
     for (int i = 0; i <= j; ++i)
-        if (!s->gcr_z[i] || !s->gcr_q[i] || !s->pcg_x || !s->gcr_sc)
+        if (!s->kry.Z[i] || !s->kry.Q[i] || !s->kry.x || !s->kry.sc)
             return s->fail(MGX_ERR_STATE, "mgx_time_gcr_pass: call mgx_solve_gcr with restart > j first (it allocates the basis)");
     return s->work_f64 ? gcr_time_pass<double>(s, pass, j, repeats, ms) : gcr_time_pass<float>(s, pass, j, repeats, ms);
 }
@@ -2397,21 +2143,11 @@ int mgx_time_smoother(mgx_handle s, int sweeps, double* ms)
     if (!s || !ms || sweeps < 1) return MGX_ERR_INVALID;
     NO_DIST(s)
     if (int vr = var_ready(s, s->cfg.finest_level, s->cfg.finest_level)) return vr;
-    hipEvent_t a, b;
-    HIPCHK(s, hipEventCreate(&a));
-    HIPCHK(s, hipEventCreate(&b));
     Level& l = s->lv[s->cfg.finest_level];
-    HIPCHK(s, hipEventRecord(a, s->stream));
-    if (s->var) smooth_var(s, l, sweeps);
-    else smooth_t(s, l, sweeps);
-    HIPCHK(s, hipEventRecord(b, s->stream));
-    HIPCHK(s, hipEventSynchronize(b));
-    float f = 0.f;
-    HIPCHK(s, hipEventElapsedTime(&f, a, b));
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    *ms = f;
-    return MGX_OK;
+    return time_on_stream(s, ms, [&] {
+        if (s->var) smooth_var(s, l, sweeps);
+        else smooth_t(s, l, sweeps);
+    });
 }
 
 // =====================================================================================

@@ -1,5 +1,7 @@
-// mgx_krylov.hpp - the Krylov passes of mgx_solve_pcg: conjugate gradients on the finest level, preconditioned
-// by one V-cycle from zero (absent in the reference).
+// mgx_krylov.hpp - the device side of the Krylov solves (their host side: mgx_krylov_host.hpp).
+//
+// mgx_solve_pcg: conjugate gradients on the finest level, preconditioned by one V-cycle from zero (absent in the
+// reference).
 //
 // Flexible PCG with the Polak-Ribiere beta; per iteration, after the V-cycle z = M r:
 //   k_pcg_dots       rho_new = r.z and gamma = z.q                         reads r, z, q           3 sizeof(T)
@@ -47,7 +49,7 @@
 
 namespace mgx {
 
-// the device-side scalars of one solve (mgx_solver::pcg_sc)
+// the device-side scalars of one PCG solve: the first slots of the block both methods share (mgx_solver::kry.sc)
 enum { kPcgRho = 0, kPcgDelta, kPcgAlpha, kPcgBeta, kPcgGamma, kPcgRR, kPcgBreak, kPcgScalars = 8 };
 enum { kPcgInit = 0, kPcgAlphaMode = 1, kPcgRRMode = 2, kPcgBetaMode = 3 };
 
@@ -245,7 +247,7 @@ static __global__ void __launch_bounds__(kReduceThreads) k_pcg_reduce(const doub
 
 // ---- mgx_solve_gcr ------------------------------------------------------------------------------------------------
 constexpr int kGcrMaxRestart = 8;              // MGX_GCR_MAX_RESTART
-// the scalar block of one GCR solve: the first kPcgScalars slots are k_pcg_update's and k_pcg_reduce's (rho = r.q',
+// the whole scalar block, as a GCR solve uses it: the first kPcgScalars slots are k_pcg_update's and k_pcg_reduce's (rho = r.q',
 // delta = s_j = q'.q', alpha, ||r||^2, the breakdown flag), then s_i of the basis and h_i of this iteration
 enum { kGcrS = kPcgScalars, kGcrH = kGcrS + kGcrMaxRestart, kGcrScalars = kGcrH + kGcrMaxRestart };
 enum { kGcrHMode = 0, kGcrAlphaMode = 1 };
@@ -388,7 +390,7 @@ void launch_gcr_orth(int j, T* qj, T* zj, const T* r, const GcrBasis<T>& bs, dou
     }
 }
 
-// mgx.hip declares these instantiations; mgx_inst.hip (-DMGX_INST_KIND=7) defines them
+// mgx.hip (through mgx_krylov_host.hpp) uses these instantiations; mgx_inst.hip (-DMGX_INST_KIND=7) defines them
 #if !defined(MGX_INST_KIND) && !defined(MGX_SINGLE_TU)
 extern template void launch_gcr_orth<double>(int, double*, double*, const double*, const GcrBasis<double>&, double*, double*, int, long, const Launch&, int, hipStream_t);
 extern template void launch_gcr_orth<float>(int, float*, float*, const float*, const GcrBasis<float>&, double*, double*, int, long, const Launch&, int, hipStream_t);

@@ -307,6 +307,44 @@ def test_interleaved_entry_points_on_one_handle_equal_fresh_handles(pkg, po):
         assert mg.graphs_cached() == graphs
 
 
+def test_pcg_first_then_gcr_and_timed_passes_on_one_handle_equal_fresh_handles(pkg, po):
+    """solve_pcg -> solve_gcr(3) -> time_gcr_pass (dots, orth, update) -> solve_pcg -> solve_gcr(2): GCR on the buffers PCG
+    allocated, and PCG on the scalar block mgx_time_gcr_pass has just zeroed"""
+    cfg = CONFIGS["poisson_V11"]
+    b = rhs(L9)
+    u0 = po.fill_uniform(b.shape, 99)
+    steps = [("pcg", dict(tol=1e-8, max_iters=4)), ("gcr", dict(tol=1e-3, max_iters=5, restart=3)), ("time", None),
+             ("pcg", dict(tol=1e-10, max_iters=4)), ("gcr", dict(tol=1e-12, max_iters=6, restart=2))]
+
+    def step(mg, what, kw):
+        return (mg.solve_gcr if what == "gcr" else mg.solve_pcg)(**kw)[1]
+
+    one = []
+    with pkg.Multigrid(**cfg) as mg:
+        mg.set_rhs(b)
+        mg.set_guess(u0)
+        for what, kw in steps:
+            if what == "time":
+                for which, j in ((1, 1), (1, 2), (2, 0), (2, 2), (0, 2)):
+                    assert mg.time_gcr_pass(which, j, 2) > 0.0
+            else:
+                one.append(step(mg, what, kw))
+        u_one = mg.get_solution()
+    u = u0
+    fresh = []
+    for what, kw in steps:
+        if what == "time":
+            continue
+        with pkg.Multigrid(**cfg) as mg:
+            mg.set_rhs(b)
+            mg.set_guess(u)
+            fresh.append(step(mg, what, kw))
+            u = mg.get_solution()
+    for a, c in zip(one, fresh):
+        assert np.array_equal(a, c), (a, c)
+    assert np.array_equal(u_one, u)
+
+
 def test_zero_rhs_and_zero_iterations(pkg, po):
     cfg = CONFIGS["poisson_V11"]
     n = (1 << L9) - 1

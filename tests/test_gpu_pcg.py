@@ -227,6 +227,51 @@ def test_repeated_calls_and_eager_launches_give_the_same_bits(pkg, po, op):
         assert np.array_equal(h, out[0][0]) and np.array_equal(u, out[0][1])
 
 
+@pytest.mark.parametrize("seed", [None, 7])
+@pytest.mark.parametrize("dtype", [1, 0])
+def test_breakdown_exit_and_the_solves_after_it(pkg, po, dtype, seed):
+    """The negated operator (nodal coefficient -1): every p.Ap is negative, so the first iteration breaks down whatever
+    the guess - arithmetic on finite data.  The reference reports a breakdown, a one-entry history and an untouched x.
+    Then the positive operator on the same handle: solve_pcg and solve_gcr(restart 2) from the guess are bit for bit
+    those of fresh handles, so the breakdown flag left in the scalar block both methods share stops neither."""
+    cfg = dict(finest_level=7, coarsest_level=4, mu0=0, mu1=2, mu2=1, op=1, dtype=dtype)
+    L = 7
+    tol = 1e-8 if dtype == 1 else 1e-5
+    b = po.rhs_sine(L)
+    u0 = np.zeros_like(b) if seed is None else po.fill_uniform(b.shape, seed)
+    minus, plus = -np.ones((129, 129)), np.ones((129, 129))
+    x_ref, h_ref, conv_ref, brk_ref = pcg_ref.run(po, cfg, b, u0, a_nodes=minus, tol=tol)
+    assert brk_ref and not conv_ref and len(h_ref) == 1 and np.array_equal(x_ref, u0.astype(x_ref.dtype))
+
+    def after(mg, method):
+        """one solve with the positive operator from the guess: (history, U)"""
+        mg.set_coefficient(plus)
+        mg.set_guess(u0)
+        st, h = mg.solve_pcg(tol=tol, max_iters=30) if method == "pcg" else mg.solve_gcr(tol=tol, max_iters=30, restart=2)
+        assert st.converged == 1
+        return h, mg.get_solution()
+
+    with pkg.Multigrid(**cfg) as mg:
+        mg.set_coefficient(minus)
+        mg.set_rhs(b)
+        mg.set_guess(u0)
+        u_before, b_before = mg.get_solution(), mg.get_level(L, pkg.VEC_B)
+        st, h = mg.solve_pcg(tol=tol, max_iters=30)          # MGX_OK: anything else raises
+        msg = pkg.lib().mgx_last_error(mg._h).decode()
+        print(f"dtype {dtype} seed {seed}: history {h} (reference {h_ref}), '{msg}'")
+        assert st.converged == 0 and st.cycles == 0 and st.history_len == 1
+        assert_hist(h, h_ref, RTOL64 if dtype == 1 else RTOL32)
+        assert "PCG breakdown at iteration 1" in msg and "p.Ap" in msg
+        assert np.array_equal(u_before, u0.astype(u_before.dtype))
+        assert np.array_equal(mg.get_solution(), u_before) and np.array_equal(mg.get_level(L, pkg.VEC_B), b_before)
+        same_handle = [after(mg, "pcg"), after(mg, "gcr")]
+    for method, (h1, u1) in zip(("pcg", "gcr"), same_handle):
+        with pkg.Multigrid(**cfg) as mg:
+            mg.set_rhs(b)
+            h2, u2 = after(mg, method)
+        assert np.array_equal(h1, h2) and np.array_equal(u1, u2), method
+
+
 def test_refusals_leave_the_handle_usable(pkg, po):
     L = pkg.lib()
     st = pkg.binding.Stats()
