@@ -13,7 +13,7 @@ the exact bottom solve of the POISSON hierarchy (sine transform: tests/test_gpu_
 float ulps; the model uses the oracle's sine-transform mode, the device's method in the device's order).
 
 fine_updates follows include/mgx.h: finest-level smoother point updates (mu n^2 per block of mu sweeps or of degree
-mu, 2 mu n^2 per block of alternating line sweeps), counted from the start of the last solve / solve_pcg.
+mu, 2 mu n^2 per block of alternating line sweeps), counted from the start of the last solve / solve_pcg / solve_gcr.
 
 The cycle index (mgx_set_cycle) is an attribute the composed vcycle() reads: the recursion of include/mgx.h from the
 same single operators, held to tests/wcycle_ref.py bit for bit.  The zebra line smoothers (cfg.smoother 4 / 5 / 6) run
@@ -24,6 +24,7 @@ import numpy as np
 
 import cheby_ref
 import galerkin_ref as gr
+import gcr_ref
 import line_ref as lr
 import opdep_ref as od
 import pcg_ref
@@ -390,6 +391,24 @@ class HandleModel:
             return self.U[self.L]
 
         x, hist, conv, brk = pcg_ref.pcg(self.finest_operator(), M, b, self.U[self.L], tol=tol, max_iters=max_iters)
+        self.U[self.L] = np.ascontiguousarray(x, dtype=self.dt)
+        self.B[self.L] = b
+        return dict(cycles=len(hist) - 1, converged=int(conv and not brk), fine_updates=self.fine_updates), hist
+
+    def solve_gcr(self, tol=1e-8, max_iters=100, restart=4, dot=pcg_ref.dot):
+        """gcr_ref.gcr with this handle's zero-start cycle as M, as solve_pcg: r lives in B[finest] while a cycle runs, so
+        the coarse levels keep what the LAST cycle left; U[finest] = x and B[finest] = b afterwards, also after a
+        breakdown.  dot: the inner product handed to gcr_ref.gcr (the tests measure what another rounding of the scalars
+        is worth)"""
+        self.fine_updates = 0.0
+        b = self.B[self.L]
+
+        def M(r):
+            self.B[self.L] = np.ascontiguousarray(r, dtype=self.dt)
+            self.vcycle_zero()
+            return self.U[self.L]
+
+        x, hist, conv, brk = gcr_ref.gcr(self.finest_operator(), M, b, self.U[self.L], tol=tol, max_iters=max_iters, restart=restart, dot=dot)
         self.U[self.L] = np.ascontiguousarray(x, dtype=self.dt)
         self.B[self.L] = b
         return dict(cycles=len(hist) - 1, converged=int(conv and not brk), fine_updates=self.fine_updates), hist

@@ -10,7 +10,22 @@ relative with the count within one.  The zebra line sweeps agree with numpy to r
 so the line cycles are held to counts, monotonicity and the true residual, not entry by entry.
 
 Shapes: 511^2 (four column strips in double, two in float, 64 row chunks: several workgroups and a one-workgroup
-reduction over more partials than threads) for the parity cases; 63^2 and 127^2 for the line cycles."""
+reduction over more partials than threads) for the parity cases; 63^2 and 127^2 for the line cycles.
+
+Deep bases (DEEP): GCR(8), nine iterations from a zero guess with tol 0, so both sides run slots 0 .. 7 and a wrap and no
+tolerance decides the count; in float at 511^2 on the three hierarchies, in both types at 1023^2 (another strip count, a
+masked tail strip) and at 31^2 (one strip, a handful of workgroups: fewer partials than reduction threads).  Every
+reference is asserted first to end at or above 1e-4 of its first entry, well above the float floor: measured on the CPU,
+POISSON V(1,0) ends at 1.7e-4 (9..5 and 10..6), STENCIL5 contrast 10 V(1,1) at 1.2e-3, GALERKIN V(1,0) with omega = 0.3 at
+2.6e-4, POISSON 5..3 V(1,0) with bottom = SMOOTH at 5.1e-3 (DEEP says what the stronger variants reach).
+The float iterate is held to X_TOL32 = 1e-4 of the reference's largest entry.  Measured on the CPU, gcr_ref against itself
+with every scalar moved independently by up to one float ulp (a factor 1 + 1.2e-7 u, u uniform in (-1, 1); the largest
+of three seeds): the iterate moves by 4.6e-6 (POISSON 9..5), 3.4e-6 (STENCIL5), 2.5e-7 (GALERKIN), 5.5e-6 (POISSON 10..6),
+3.1e-7 (POISSON 5..3) of its largest entry, the history by at most 3.0e-5 relative (RTOL32 is 33 times that).  1e-4 is 18
+times the largest of these figures and 21 times or more the others; it is not raised to make that 20, because it is also
+bounded from above: gcr_ref with the update of z' by the last basis vector left out in slots 5 .. 7 moves the iterate
+by 8.3e-4 (POISSON 10..6) .. 1.2e-1 (5..3) and the history not at all, so the iterate bound is what catches a skipped
+basis vector, with a factor 8 to spare.  In double the bound is this file's 1e-9."""
 import ctypes as C
 import functools
 
@@ -140,6 +155,167 @@ def reference_fp32():
         return gcr_ref.gcr(pcg_ref.Operator(None, np.float32), lambda r: s.vcycle(L9, zeros, r), b, zeros, 1e-5, 40, 4)
     finally:
         s.close()
+
+
+# ---- deep bases in float, other strip counts, fewer partials than reduction threads ------------------------------------
+F32, F64 = np.float32, np.float64
+DEEP = {
+    # name: (type, operator, finest, coarsest, mu1, mu2): restart 8, nine iterations from a zero guess, tol 0 - slots 0 .. 7
+    # and a wrap, so k_gcr_dots<T, 1..7>, k_gcr_orth<T, 0..7> and k_pcg_direction<T, 0 / 1> (first pass) all run with
+    # the scalars of a real iteration, and the count does not hang on a tolerance.  Weak smoothing keeps the ninth
+    # entry far above the float rounding floor of the first
+    "f32_poisson_9_5": (F32, "poisson", 9, 5, 1, 0, {}),
+    "f32_stencil5_9_5": (F32, "stencil5", 9, 5, 1, 1, {}),
+    # (V(1,1) with omega = 2/3 ends at 1.9e-8 of the first entry, at the float floor, V(1,0) at 1.9e-5; omega = 0.3: 2.6e-4)
+    "f32_galerkin_9_5": (F32, "galerkin", 9, 5, 1, 0, dict(omega=0.3)),
+    # 1023^2: another strip count than 511^2 and a masked tail strip (columns >= N)
+    "f32_poisson_10_6": (F32, "poisson", 10, 6, 1, 0, {}),
+    "f64_poisson_10_6": (F64, "poisson", 10, 6, 1, 0, {}),
+    # 31^2: one strip, a handful of workgroups - pcg_reduce_sum with far fewer partials than threads.  (With the exact
+    # bottom solve on these three levels the ninth entry is 9.1e-5 of the first; bottom = SMOOTH: 5.1e-3)
+    "f64_poisson_5_3": (F64, "poisson", 5, 3, 1, 0, dict(bottom=1)),
+    "f32_poisson_5_3": (F32, "poisson", 5, 3, 1, 0, dict(bottom=1)),
+}
+DEEP_ITERS, DEEP_RESTART = 9, 8
+X_TOL64 = 1e-9                                  # the iterate in double: this file's bound
+X_TOL32 = 1e-4                                  # ... in float: module docstring
+
+
+def deep_cfg(name):
+    dt, kind, L, Lc, mu1, mu2, extra = DEEP[name]
+    return dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=mu1, mu2=mu2, schedule=0, dtype=1 if dt is F64 else 0,
+                op={"poisson": 0, "stencil5": 1, "galerkin": 3}[kind], **extra)
+
+
+def deep_operator(name):
+    dt, kind, L = DEEP[name][:3]
+    assert kind == "poisson" or L == L9
+    return operator_of(kind)
+
+
+@functools.lru_cache(maxsize=None)
+def deep_reference(name, dot=pcg_ref.dot):
+    """(x, history, converged, breakdown) of gcr_ref.gcr: GCR(8), nine iterations, zero guess, the reference's cycle as M"""
+    from oracle import pyoracle as po
+    dt, kind, L, Lc, mu1, mu2, extra = DEEP[name]
+    cfg, op = deep_cfg(name), deep_operator(name)
+    b = rhs(L, dt)
+    zeros = np.zeros_like(b)
+    if kind == "galerkin":
+        M = gcr_ref.cycle_preconditioner(gr.Hierarchy(po, op, L, Lc, dt, mu1=mu1, mu2=mu2, **extra))
+        return gcr_ref.gcr(pcg_ref.Operator(op, dt), M, b, zeros, 0.0, DEEP_ITERS, DEEP_RESTART, dot=dot)
+    s = pcg_ref.oracle_solver(po, cfg, op)
+    try:
+        coef = None if op is None else po.stencil_from_nodes(op, L, L)
+        return gcr_ref.gcr(pcg_ref.Operator(coef, dt), lambda r: s.vcycle(L, zeros, r), b, zeros, 0.0, DEEP_ITERS, DEEP_RESTART, dot=dot)
+    finally:
+        s.close()
+
+
+@pytest.mark.parametrize("name", list(DEEP))
+def test_deep_bases_match_the_reference_entry_by_entry(pkg, po, name):
+    dt, kind, L, Lc = DEEP[name][:4]
+    x_ref, h_ref, conv_ref, brk_ref = deep_reference(name)
+    assert not brk_ref and not conv_ref and len(h_ref) == DEEP_ITERS + 1
+    assert h_ref[-1] >= 1e-4 * h_ref[0], h_ref          # well above the float floor: the comparison means something
+    b = rhs(L, dt)
+    with pkg.Multigrid(**deep_cfg(name)) as mg:
+        op = deep_operator(name)
+        if kind == "stencil5":
+            mg.set_coefficient(op)
+        elif kind == "galerkin":
+            mg.set_stencil(L, *op)
+            mg.build_galerkin()
+        mg.set_rhs(b)
+        b0 = mg.get_level(L, pkg.VEC_B)
+        st, h = mg.solve_gcr(tol=0.0, max_iters=DEEP_ITERS, restart=DEEP_RESTART)
+        u = mg.get_solution()
+        b1 = mg.get_level(L, pkg.VEC_B)
+    rtol, xtol = (RTOL64, X_TOL64) if dt is F64 else (RTOL32, X_TOL32)
+    dx = float(np.max(np.abs(u.astype(F64) - x_ref.astype(F64))) / np.max(np.abs(x_ref)))
+    k = min(len(h), len(h_ref))
+    dh = float(np.max(np.abs(h[:k] - h_ref[:k]) / h_ref[:k]))
+    print(f"\n[gcr-deep] {name}: {st.cycles} iterations, last / first {h[-1] / h[0]:.3g} (reference {h_ref[-1] / h_ref[0]:.3g}); largest history "
+          f"deviation {dh:.3g} ({dh / rtol:.3g} x {rtol:g}); iterate off by {dx:.3g} of the largest entry ({dx / xtol:.3g} x {xtol:g})")
+    assert st.cycles == DEEP_ITERS and st.converged == 0 and st.history_len == DEEP_ITERS + 1
+    assert u.dtype == dt
+    if dt is F64:
+        assert_hist(h, h_ref, RTOL64)
+    else:
+        assert len(h) == len(h_ref) and np.all(np.abs(h - h_ref) <= RTOL32 * h_ref), (h, h_ref)
+    assert np.array_equal(b0, b1) and np.array_equal(b0, b)          # B is the caller's b again, bit for bit
+    assert np.all(h[1:] <= h[:-1] * (1 + 1e-12)), h
+    assert dx <= xtol, (dx, xtol)
+
+
+# ---- the breakdown exit ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", [None, 7])
+@pytest.mark.parametrize("dtype", [1, 0])
+def test_breakdown_exit_and_the_calls_after_it(pkg, po, dtype, seed):
+    """POISSON 7..4 with mu1 = mu2 = 0 and bottom = SMOOTH: the zero-start cycle returns exactly zero (and runs with no
+    smoothing pass to synthesise its zero guess), so z = 0, q' = A z = 0 and q'.q' = 0 at iteration 1 - arithmetic on finite
+    data.  gcr_ref around the oracle's cycle reports a breakdown, a history of one entry and an untouched x.  The device:
+    k_gcr_reduce raises the flag, k_pcg_update skips, the driver returns MGX_OK with the reason, U and B are restored.
+    Then solve_pcg on the same handle breaks down too (p = 0: p.Ap = 0), and a smoothing block and a norm afterwards are
+    those of a fresh handle.
+    (A breakdown at a later basis slot needs q' = 0 after a successful iteration, an input no natural problem provides:
+    out of scope here.)"""
+    L = 7
+    cfg = dict(finest_level=L, coarsest_level=4, mu0=0, mu1=0, mu2=0, bottom=1, schedule=0, dtype=dtype)
+    dt = F64 if dtype == 1 else F32
+    tol = 1e-8 if dtype == 1 else 1e-5
+    rtol = RTOL64 if dtype == 1 else RTOL32
+    b = rhs(L, dt)
+    u0 = np.zeros_like(b) if seed is None else po.fill_uniform(b.shape, seed).astype(dt)
+    zeros = np.zeros_like(b)
+    s = pcg_ref.oracle_solver(po, cfg)
+    try:
+        A = pcg_ref.Operator(None, dt)
+        x_ref, h_ref, conv_ref, brk_ref = gcr_ref.gcr(A, lambda r: s.vcycle(L, zeros, r), b, u0, tol, 30, 4)
+        xp_ref, hp_ref, convp_ref, brkp_ref = pcg_ref.pcg(A, lambda r: s.vcycle(L, zeros, r), b, u0, tol, 30)
+    finally:
+        s.close()
+    assert brk_ref and not conv_ref and len(h_ref) == 1 and np.array_equal(x_ref, u0)
+    assert brkp_ref and not convp_ref and len(hp_ref) == 1 and np.array_equal(xp_ref, u0)
+
+    def state(mg):
+        return mg.get_solution(), mg.get_level(L, pkg.VEC_B)
+
+    with pkg.Multigrid(**cfg) as mg:
+        mg.set_rhs(b)
+        mg.set_guess(u0)
+        u_before, b_before = state(mg)
+        assert np.array_equal(u_before, u0) and np.array_equal(b_before, b)
+        seen = []
+        for _ in range(2):                               # the second call: from the flag and the scalars the first one left
+            st, h = mg.solve_gcr(tol=tol, max_iters=30, restart=4)          # MGX_OK: anything else raises
+            msg = pkg.lib().mgx_last_error(mg._h).decode()
+            print(f"dtype {dtype} seed {seed}: history {h} (reference {h_ref}), '{msg}'")
+            assert st.converged == 0 and st.cycles == 0 and st.history_len == 1 and len(h) == 1
+            assert_hist(h, h_ref, rtol)
+            assert "GCR breakdown at iteration 1" in msg and "q'.q'" in msg
+            u1, b1 = state(mg)
+            assert np.array_equal(u1, u_before), "U is not the guess"
+            assert np.array_equal(b1, b_before), "B is not the caller's b"
+            seen.append((h, msg))
+        assert np.array_equal(seen[0][0], seen[1][0]) and seen[0][1] == seen[1][1]
+        st, h = mg.solve_pcg(tol=tol, max_iters=30)
+        msg = pkg.lib().mgx_last_error(mg._h).decode()
+        assert st.converged == 0 and st.cycles == 0 and st.history_len == 1
+        assert_hist(h, hp_ref, rtol)
+        assert np.array_equal(h, seen[0][0])             # the same norm kernel on the same data
+        assert "PCG breakdown at iteration 1" in msg and "p.Ap" in msg
+        u1, b1 = state(mg)
+        assert np.array_equal(u1, u_before) and np.array_equal(b1, b_before)
+        mg.smooth(L, 2)
+        after = state(mg) + (mg.residual_norm(),)
+    with pkg.Multigrid(**cfg) as mg:
+        mg.set_rhs(b)
+        mg.set_guess(u0)
+        mg.smooth(L, 2)
+        fresh = state(mg) + (mg.residual_norm(),)
+    assert np.array_equal(after[0], fresh[0]) and np.array_equal(after[1], fresh[1]) and after[2] == fresh[2]
+    assert not np.array_equal(after[0], u0)
 
 
 # ---- line cycles -------------------------------------------------------------------------------------------------------

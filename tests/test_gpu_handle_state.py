@@ -47,6 +47,33 @@ GALERKIN double LINE_Y with MGX_LINE_CHUNK=16 6.79e-11 / 0.68; STENCIL5 double L
 most 4e-4 of their bound in double, 0.04 in float).  The dense coarsest solve of the CYCLE_CASES is bit for bit at
 levels 3 and 4 as it is at level 5.
 
+GCR_CASES add mgx_solve_gcr (csrc/mgx_krylov_host.hpp) as a fourth graph user: it runs cycle_body through the same graph
+cache with lv[L].b repointed at r, on the workspace mgx_solve_pcg shares (one scalar block, one partial-sum buffer, a basis
+that grows with the restart asked for), so what it leaves on the coarse levels, a stale graph after mgx_set_cycle or a
+rebuild under it, and either method on the buffers the other allocated are held here.  It is compared as mgx_solve_pcg is,
+for the same reason (the device differs from the model only in the summation order of the dots): the history through
+the solve_pcg branch of history_check, the arrays it writes to RTOL64 / PCG32_STATE, everything else bit for bit.  In
+double one call per sequence is DEEP_GCR (nine iterations of GCR(8) after shorter bases: every slot, then a wrap); float
+sequences stop at four iterations (after nine the coarse levels hold images of a residual near the float rounding floor
+of the first one; deep float bases are held in tests/test_gpu_gcr.py on the history and the iterate).
+What these bounds rest on is measured on the CPU, the model against itself, never from device output
+(tests/test_handle_model.py::test_the_gcr_sequences_meet_the_conditions_their_bounds_rest_on, which asserts it):
+  * PCG32_STATE for solve_gcr: every float solve_gcr call run a second time from the same state with every scalar moved
+    independently by up to one float ulp (a factor 1 + 1.2e-7 u, u uniform in (-1, 1)) moves an array the call writes by
+    at most 4.6e-6 of its largest entry (POISSON float RB-GS 8..5: B of level 7 after four iterations of GCR(2)) and
+    1.6e-5 (GALERKIN float FW16 7..3 with W / F cycles: U of level 6 after four iterations of GCR(2)), a history entry by
+    at most 5.0e-7 relative.  The cap there is PCG32_STATE / 4 = 2.5e-4: 16 times the larger figure.
+  * no double Krylov call ends below 1e-6 of its first history entry (the iterate stays out of the cancellation regime of
+    b - A u): the lowest are 6.0e-5 (POISSON V(1,0) 8..5, the deep call), 1.1e-4 (STENCIL5 Chebyshev, a solve_pcg of three
+    iterations), 1.2e-4 (GALERKIN 7..3, the deep call), 5.3e-6 (the line case, whose deep call is shortened to four
+    iterations for this: GCR_CASES).  The cases smooth weakly, V(1,0), to get there.
+  * the line case: the largest rule bound used is 1.3e-11 (cap 1e-9).
+Measured on an MI355X, largest deviation as a fraction of its bound, history of solve_gcr / written state after it:
+POISSON double 2.9e-6 / 1.6e-3 (STREAMING: 4.0e-6 / 1.7e-3); STENCIL5 double Chebyshev 7.5e-6 / 3.2e-4; GALERKIN double 7..3
+6.7e-6 / 5.3e-5, the same bits with MGX_SMALL_VISIT=0; both float cases: histories 4e-13, state bit for bit (the float
+products are exact in the double accumulators, and their sums round to the same floats); the line case 1.7e-4 of the
+history bound, 0.55 of the rule bound.
+
 A failing sequence is reproduced from the seed, the step index and the calls so far, which the message carries."""
 import numpy as np
 import pytest
@@ -60,15 +87,20 @@ pytestmark = pytest.mark.gpu
 HIST_TOL, HIST_FLOOR = 1e-10, 1e-13        # tests/test_gpu_solve.py (fp64 histories)
 NORM32 = 1e-5                              # tests/test_gpu_operators.py::test_residual_matches_oracle (fp32 norms)
 RTOL64, RTOL32, PCG_FLOOR = 1e-9, 1e-3, 1e-14      # tests/test_gpu_pcg.py (assert_hist)
-PCG32_STATE = 1e-3                         # this file's: U and the coarse levels after an fp32 mgx_solve_pcg (module docstring)
+PCG32_STATE = 1e-3                         # this file's: U and the coarse levels after an fp32 mgx_solve_pcg / mgx_solve_gcr (module docstring)
 BOTTOM64, CYCLE64, SOLVE64 = 1e-11, 1e-12, 1e-11   # the POISSON sine-transform bottom solve and what runs through it (see above)
 K_MAX_GRAPHS = 8                           # kMaxGraphs of csrc/mgx.hip: the capacity of a handle's graph cache
 
 MUS = (0, 1, 2, 3, 5)
 GRAPH_USERS = ("solve", "solve_pcg", "vcycle_zero")
+GCR_USERS = GRAPH_USERS + ("solve_gcr",)     # the sequences drawn with gcr=True
+SOLVES = ("solve", "solve_pcg", "solve_gcr")  # the calls that return (stats, history)
+KRYLOV = ("solve_pcg", "solve_gcr")
+GCR_RESTARTS = (1, 2, 3)
+DEEP_GCR = ("solve_gcr", 0.0, 9, 8)          # nine iterations of GCR(8): every slot of the full basis, then slot 0 again
 KNOBS = ("MGX_TILE_MAX_N", "MGX_FUSE_MIN_N", "MGX_PLAN_MIN_N", "MGX_PLAN_PRE", "MGX_PLAN_POST", "MGX_GRAPH", "MGX_FOLD", "MGX_FUSE",
          "MGX_ZERO_IN", "MGX_TILE_K", "MGX_FOLD_KMAX", "MGX_FOLD_KMAX_NOPOST", "MGX_FUSE_ROWS", "MGX_ROWS", "MGX_SMALL_VISIT", "MGX_LINE_CHUNK")
-SMOOTHING = ("smooth", "vcycle", "vcycle_zero", "fmg", "solve", "solve_pcg")      # the calls that run a smoother
+SMOOTHING = ("smooth", "vcycle", "vcycle_zero", "fmg", "solve", "solve_pcg", "solve_gcr")      # the calls that run a smoother
 CYCLE_ORDER = (hm.CYCLE_W, hm.CYCLE_F, hm.CYCLE_V, hm.CYCLE_W, hm.CYCLE_F, hm.CYCLE_W, hm.CYCLE_V)
 SMALL_MAX_LEVEL = 6                        # kSmallMaxN = 64 of csrc/mgx_small.hpp
 # the marching kernels on every level (no register tiles); fused / folded passes from 128^2 up (MGX_FUSE_MIN_N=128, as
@@ -105,9 +137,14 @@ def kinds_at(calls):
     return out
 
 
-def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_guess=False, short_solves=False, without=(), tail=()):
+def graph_users(calls):
+    """the kinds of graph user a drawn list holds each five times at least"""
+    return GCR_USERS if any(c[0] == "solve_gcr" for c in calls) else GRAPH_USERS
+
+
+def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_guess=False, short_solves=False, without=(), tail=(), gcr=False, deep_iters=DEEP_GCR[2]):
     """~n_steps calls, every one valid for `cfg` by construction (nothing is filtered afterwards): the three graph
-    users five times each at least, an odd-launch smooth on every level at least once, the rest drawn with weights;
+    users (four with gcr) five times each at least, an odd-launch smooth on every level at least once, the rest drawn with weights;
     mu from MUS.  Operator changes of the general hierarchies are placed after every third graph user.
 
     Off by default (the sequences of the cases that do not ask are call for call what they were):
@@ -121,12 +158,18 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
                  to max |x| means nothing
     short_solves one cycle per solve and one iteration per solve_pcg (the float line case: see LINE_CASES)
     without      call kinds left out of the weighted draw
-    tail         calls appended after everything else"""
+    tail         calls appended after everything else
+    gcr          ("solve_gcr", tol, max_iters, restart) as a fourth graph user: tol as for solve_pcg, max_iters 1..4, restart
+                 from GCR_RESTARTS (a call with max_iters > restart wraps the basis); the first one of the sequence with
+                 restart 2; double: the last one becomes DEEP_GCR after a fresh ("set_guess", 3500) - the basis grows from
+                 2 to 8 pairs on a handle the other graph users have run on
+    deep_iters   the iterations of that call, where nine take the iterate too far (the line case: see GCR_CASES)"""
     rng = np.random.RandomState(seed)
     L, Lc = cfg["finest_level"], cfg["coarsest_level"]
     f64 = cfg.get("dtype", hm.F64) == hm.F64
     exact = cfg.get("bottom", hm.EXACT) == hm.EXACT
     op = cfg.get("op", hm.POISSON)
+    user_kinds = GCR_USERS if gcr else GRAPH_USERS
 
     def one(name):
         lv = int(rng.randint(Lc, L + 1))
@@ -137,6 +180,9 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
         if name == "solve_pcg":
             tol, k = float(rng.choice([0.0, 1e-3] if f64 else [0.0, 1e-2])), int(rng.randint(1, 4))
             return ("solve_pcg", tol, 1 if short_solves else k)
+        if name == "solve_gcr":
+            tol, k = float(rng.choice([0.0, 1e-3] if f64 else [0.0, 1e-2])), int(rng.randint(1, 5))
+            return ("solve_gcr", tol, 1 if short_solves else k, int(rng.choice(GCR_RESTARTS)))
         if name == "smooth":
             return ("smooth", lv, int(rng.choice(MUS)))
         if name in ("vcycle", "residual", "zero_u"):
@@ -153,11 +199,13 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
                "set_guess": 2, "set_rhs": 1, "set_u": 2, "set_b": 1, "zero_u": 1, "solve": 1, "solve_pcg": 1, "vcycle_zero": 1}
     if exact:
         weights["bottom_solve"] = 2
+    if gcr:
+        weights["solve_gcr"] = 1
     for k in without:
         del weights[k]
     names = sorted(weights)
     p = np.array([weights[k] for k in names], dtype=float)
-    calls = [one(k) for k in GRAPH_USERS for _ in range(5)]
+    calls = [one(k) for k in user_kinds for _ in range(5)]
     between = [("smooth", lv, int(rng.choice([1, 3, 5]))) for lv in range(Lc, L + 1)]
     changes = []
     if op == hm.STENCIL5:
@@ -171,13 +219,13 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
         calls.append(one(names[int(rng.choice(len(names), p=p / p.sum()))]))
     calls = [calls[i] for i in rng.permutation(len(calls))]
     for c in between:                                      # an odd-launch smooth on every level, between two graph users
-        users = [i for i, x in enumerate(calls) if x[0] in GRAPH_USERS]
+        users = [i for i, x in enumerate(calls) if x[0] in user_kinds]
         calls.insert(int(rng.randint(users[0] + 1, users[-1] + 1)), c)
     out, users = [], 0
     kinds = list(CYCLE_ORDER) if cycles else []
     for c in calls:
         out.append(c)
-        if c[0] in GRAPH_USERS:
+        if c[0] in user_kinds:
             users += 1
             if users % 3 == 0 and changes:
                 out += changes.pop(0)
@@ -194,16 +242,23 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
         for lv in small_levels(cfg):
             for kind in (hm.CYCLE_W, hm.CYCLE_F):
                 assert any(c == ("vcycle", lv) and k == kind for c, k in zip(out, kinds_at(out))), (seed, lv, kind)
+    if gcr:
+        first = [i for i, c in enumerate(out) if c[0] == "solve_gcr"]
+        out[first[0]] = out[first[0]][:3] + (2,)
+        if f64:
+            out[first[-1]] = DEEP_GCR[:2] + (deep_iters,) + DEEP_GCR[3:]
+            if not fresh_guess:
+                out.insert(first[-1], ("set_guess", 3500))
     if fresh_guess:
         fresh = []
         for c in out:
-            if c[0] in ("solve", "solve_pcg"):
+            if c[0] in SOLVES:
                 fresh.append(("set_guess", 3000 + len(fresh)))
             elif c[0] == "vcycle":
                 fresh.append(("set_u", c[1], 3000 + len(fresh)))
             fresh.append(c)
         out = fresh
-    users = [i for i, x in enumerate(out) if x[0] in GRAPH_USERS]
+    users = [i for i, x in enumerate(out) if x[0] in user_kinds]
     for lv in range(Lc, L + 1):
         assert any(c[0] == "smooth" and c[1] == lv and c[2] % 2 for c in out[users[0] + 1:users[-1]]), (seed, lv)
     # data on every level first, and the operators of the general hierarchies
@@ -235,6 +290,8 @@ def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
         return mg.solve(tol=a[0], max_cycles=a[1])
     if name == "solve_pcg":
         return mg.solve_pcg(tol=a[0], max_iters=a[1])
+    if name == "solve_gcr":
+        return mg.solve_gcr(tol=a[0], max_iters=a[1], restart=a[2])
     if name == "vcycle_zero":
         mg.vcycle_zero()
     elif name == "smooth":
@@ -284,6 +341,8 @@ def apply_model(m, call, L):
         return m.solve(tol=a[0], max_cycles=a[1])
     if name == "solve_pcg":
         return m.solve_pcg(tol=a[0], max_iters=a[1])
+    if name == "solve_gcr":
+        return m.solve_gcr(tol=a[0], max_iters=a[1], restart=a[2])
     if name == "residual":
         return m.residual(a[0])
     if name == "set_guess":
@@ -305,7 +364,7 @@ def state_tolerance(cfg, call):
     """0: bit for bit; else the relative bound of the module docstring for this call"""
     name = call[0]
     f64 = cfg.get("dtype", hm.F64) == hm.F64
-    if name == "solve_pcg":
+    if name in KRYLOV:
         return RTOL64 if f64 else PCG32_STATE
     sine_bottom = cfg.get("op", hm.POISSON) == hm.POISSON and cfg.get("bottom", hm.EXACT) == hm.EXACT
     if not sine_bottom:
@@ -322,7 +381,7 @@ def touched(cfg, call):
         return {(Lc, "U")}
     if name == "smooth":
         return {(call[1], "U")} if call[2] else set()
-    top = call[1] if name == "vcycle" else L                # vcycle_zero, fmg, solve, solve_pcg: from the finest level
+    top = call[1] if name == "vcycle" else L                # vcycle_zero, fmg, solve, solve_pcg, solve_gcr: from the finest level
     return {(top, "U")} | {(lv, x) for lv in range(Lc, top) for x in ("U", "B")}
 
 
@@ -345,9 +404,10 @@ class Tally:
     def __init__(self):
         self.executed = 0
         self.graphs = -1
-        self.hist = {"solve": 0.0, "solve_pcg": 0.0}      # largest history deviation / bound
+        self.hist = {k: 0.0 for k in SOLVES}               # largest history deviation / bound
         self.state = 0.0                                   # largest relative state deviation through the sine-transform bottom solve
         self.state_pcg = 0.0                               # ... after mgx_solve_pcg
+        self.state_gcr = 0.0                               # ... after mgx_solve_gcr
         self.graph_counts = []
         self.histories = []                                # of the device, in call order
         self.final = None                                  # U and B of every level after the last call
@@ -365,7 +425,7 @@ def step(pkg, mg, m, cfg, call, tally, where):
     if call[0] == "set_cycle":                             # the graph key carries no kind: the setter has to drop the graphs
         assert mg.cycle == m.cycle == call[1], where()
         assert mg.graphs_cached() == (0 if g_before >= 0 else -1), f"{mg.graphs_cached()} graphs after mgx_set_cycle; {where()}"
-    if call[0] in ("solve", "solve_pcg"):
+    if call[0] in SOLVES:
         (st, h), (st_m, h_m) = got, want
         tally.histories.append(np.array(h))
         ok, frac = history_check(cfg, call, h, h_m)
@@ -390,6 +450,8 @@ def step(pkg, mg, m, cfg, call, tally, where):
                 dev = float(np.max(np.abs(a.astype(np.float64) - r.astype(np.float64)))) / max(float(np.max(np.abs(r))), 1e-300)
                 if call[0] == "solve_pcg":
                     tally.state_pcg = max(tally.state_pcg, dev)
+                elif call[0] == "solve_gcr":
+                    tally.state_gcr = max(tally.state_gcr, dev)
                 else:
                     tally.state = max(tally.state, dev)
                 assert dev <= rtol, f"{name} of level {lv} off by {dev:.3g} (bound {rtol:g}); {where()}"
@@ -414,11 +476,13 @@ def run_sequence(pkg, po, cfg, calls, seed, env=None):
             step(pkg, mg, m, cfg, call, tally, where)
         tally.final = all_levels(pkg, mg, cfg["finest_level"], cfg["coarsest_level"])
     assert tally.executed == len(calls)                    # nothing skipped, nothing filtered
-    users = {k: sum(1 for c in calls if c[0] == k) for k in GRAPH_USERS}
+    users = {k: sum(1 for c in calls if c[0] == k) for k in graph_users(calls)}
     assert min(users.values()) >= 5, users
+    krylov_bound = RTOL64 if cfg.get("dtype", hm.F64) == hm.F64 else PCG32_STATE
     print(f"\n[handle-state] cfg={cfg} env={env} seed={seed} steps={tally.executed} graph_users={users} "
           f"max_graphs={tally.graphs} hist_solve={tally.hist['solve']:.3g}xbound hist_pcg={tally.hist['solve_pcg']:.3g}xbound "
-          f"state_dev_bottom={tally.state:.3g} state_dev_pcg={tally.state_pcg:.3g}")
+          f"hist_gcr={tally.hist['solve_gcr']:.3g}xbound state_dev_bottom={tally.state:.3g} state_dev_pcg={tally.state_pcg:.3g} "
+          f"state_dev_gcr={tally.state_gcr:.3g} ({tally.state_gcr / krylov_bound:.3g}xbound)")
     return tally
 
 
@@ -508,7 +572,7 @@ CYCLE_CASES = {
 
 def assert_cycle_calls(calls, cfg):
     """what draw_sequence(cycles=True) promises, on the drawn list"""
-    users = [i for i, c in enumerate(calls) if c[0] in GRAPH_USERS]
+    users = [i for i, c in enumerate(calls) if c[0] in graph_users(calls)]
     sets = [i for i, c in enumerate(calls) if c[0] == "set_cycle"]
     assert tuple(calls[i][1] for i in sets) == CYCLE_ORDER
     for k, i in enumerate(sets):                           # after every second graph user (an operator change may stand between)
@@ -653,7 +717,7 @@ def line_step(pkg, mg, twin, m, mx, cfg, call, tally, where):
     if call[0] == "set_cycle":
         assert mg.cycle == twin.cycle == m.cycle == call[1], where()
         assert mg.graphs_cached() == (0 if g_before >= 0 else -1), f"{mg.graphs_cached()} graphs after mgx_set_cycle; {where()}"
-    if call[0] in ("solve", "solve_pcg"):
+    if call[0] in SOLVES:
         (st, h), (st_t, h_t), (st_m, h_m), (_, h_x) = got, got_t, want, far
         ok, frac = line_history_check(h, h_m, h_x)
         tally.hist[call[0]] = max(tally.hist[call[0]], frac if np.isfinite(frac) else 0.0)
@@ -699,6 +763,11 @@ def test_line_smoother_sequences_follow_the_models_after_every_call(pkg, po, mon
         assert_cycle_calls(calls, cfg)
     wanted = [options["operators"][0]] + [c[1] for g in list(options["operators"][1]) + [options.get("tail", [])] for c in g if c[0] == "set_operator"]
     assert [c[1] for c in calls if c[0] == "set_operator"] == wanted
+    run_line_sequence(pkg, po, monkeypatch, cfg, calls, seed, env)
+
+
+def run_line_sequence(pkg, po, monkeypatch, cfg, calls, seed, env):
+    """a replaying handle and its MGX_GRAPH=0 twin through `calls`, both models beside them (line_step)"""
     tally = Tally()
     done = []
 
@@ -722,12 +791,14 @@ def test_line_smoother_sequences_follow_the_models_after_every_call(pkg, po, mon
     finally:
         twin.close()
     assert tally.executed == len(calls)
-    users = {k: sum(1 for c in calls if c[0] == k) for k in GRAPH_USERS}
+    users = {k: sum(1 for c in calls if c[0] == k) for k in graph_users(calls)}
     assert min(users.values()) >= 5, users
     assert 1 <= tally.graphs <= K_MAX_GRAPHS
     print(f"\n[handle-state] line cfg={cfg} env={env} seed={seed} steps={tally.executed} of {len(calls)} drawn graph_users={users} "
           f"max_graphs={tally.graphs} hist_solve={tally.hist['solve']:.3g}xbound hist_pcg={tally.hist['solve_pcg']:.3g}xbound "
+          f"hist_gcr={tally.hist['solve_gcr']:.3g}xbound "
           f"largest_bound={tally.bound:.3g} (cap {line_cap(cfg):g}) largest_device_to_bound_ratio={tally.ratio:.3g}")
+    return tally
 
 
 def test_a_line_smoother_keeps_small_levels_off_the_visit_kernel(pkg, po, monkeypatch):
@@ -743,6 +814,89 @@ def test_a_line_smoother_keeps_small_levels_off_the_visit_kernel(pkg, po, monkey
             out.append((mg.profile()["launches"][4], mg.get_solution()))          # MGX_PROF_COARSE
     assert out[0][0] == out[1][0] > 0, (out[0][0], out[1][0])
     assert np.array_equal(out[0][1], out[1][1])
+
+
+# ---- 2d. mgx_solve_gcr among the graph users -------------------------------------------------------------------------
+# Weak smoothing throughout: the deep call (DEEP_GCR) must not take the iterate into the cancellation regime of b - A u,
+# where a bound relative to max |x| means nothing - tests/test_handle_model.py walks the model alone through every case
+# and holds every fp64 solve_gcr / solve_pcg to a last history entry at or above 1e-6 of its first.
+P85_WEAK = dict(P85, mu1=1, mu2=0)
+G73_WEAK = dict(G73, mu1=1, mu2=0)
+GCR_CASES = {
+    # name: (configuration, seed, environments, generator options, through line_step)
+    "poisson_f64_jacobi_8_5": (dict(P85_WEAK), 8551, [{}], {}, False),
+    "poisson_f64_jacobi_8_5_streaming": (dict(P85_WEAK), 8552, [STREAMING], {}, False),
+    "poisson_f32_rbgs_smooth_bottom_8_5": (dict(P85_WEAK, dtype=hm.F32, smoother=hm.RBGS, bottom=hm.SMOOTH), 8558, [{}], {}, False),
+    # the two set_coefficient changes between the graph users
+    "stencil5_f64_chebyshev_8_5": (dict(P85_WEAK, op=hm.STENCIL5, smoother=hm.CHEBYSHEV), 8554, [{}], {}, False),
+    # set_cycle through CYCLE_ORDER and the BILINEAR / OPERATOR rebuilds; with and without k_small_visit against the same model
+    "galerkin_f64_jacobi_7_3_cycles": (dict(G73_WEAK), 8555, [{}, {"MGX_SMALL_VISIT": "0"}], dict(cycles=True), False),
+    "galerkin_f32_jacobi_fw16_smooth_bottom_7_3_cycles": (dict(G73_WEAK, dtype=hm.F32, restrict_mode=hm.FW16, bottom=hm.SMOOTH), 8556, [{}],
+                                                          dict(cycles=True), False),
+    # the rule bound against the long-double model, and the MGX_GRAPH=0 twin.  The alternating line cycle V(1,0) reduces the
+    # residual by 5e-2 .. 7e-2 per GCR iteration: nine iterations of the deep call end at 4.5e-12 of the first entry with a
+    # rule bound of 1.2e-7, six at 2.2e-8, five at 2.8e-7, four at 5.3e-6 (bound 4.9e-13) - measured on the CPU, the two
+    # models alone.  So this case's deep call is shortened to four iterations: the basis still grows to eight pairs, slots
+    # 0 .. 3 are written; the full basis and its wrap are the other double cases'
+    "galerkin_f64_alt_6_3_line": (dict(L63, mu2=0, op=hm.GALERKIN, smoother=hm.LINE_ALT), 8557, [{}],
+                                  dict(LINE_OPTIONS, operators=("layers", [[("set_operator", "x1e-2")], [("build_galerkin", hm.OPERATOR)],
+                                                                           [("set_operator", "contrast")]]), deep_iters=4), True),
+}
+
+
+def assert_gcr_calls(calls, cfg, fresh_guess=False, deep_iters=DEEP_GCR[2]):
+    """what draw_sequence(gcr=True) promises, on the drawn list"""
+    f64 = cfg.get("dtype", hm.F64) == hm.F64
+    at = [i for i, c in enumerate(calls) if c[0] == "solve_gcr"]
+    assert len(at) >= 5 and min(sum(1 for c in calls if c[0] == k) for k in GCR_USERS) >= 5
+    assert calls[at[0]][3] == 2                                   # the basis of the first call: two pairs
+    deep = [i for i in at if calls[i] == DEEP_GCR[:2] + (deep_iters,) + DEEP_GCR[3:]]
+    for i in at:
+        tol, iters, restart = calls[i][1:]
+        if i in deep:
+            continue
+        assert tol in ((0.0, 1e-3) if f64 else (0.0, 1e-2)) and 1 <= iters <= 4 and restart in GCR_RESTARTS, calls[i]
+        if fresh_guess:
+            assert calls[i - 1][0] == "set_guess", i
+    if f64:
+        assert len(deep) == 1 and deep[0] > at[0] and calls[deep[0] - 1][0] == "set_guess"
+        before = {c[0] for c in calls[:deep[0]]}
+        assert "solve" in before and "solve_pcg" in before        # the basis grows on a handle the others have used
+    else:
+        assert not deep and all(c[2] <= 4 for c in calls if c[0] == "solve_gcr")
+    assert any(calls[i][2] > calls[i][3] for i in at if i not in deep)          # a wrap of a short basis
+
+
+def krylov_order(calls):
+    """'pcg' / 'gcr': which of the two Krylov solves a sequence runs first (they share one workspace)"""
+    return next("pcg" if c[0] == "solve_pcg" else "gcr" for c in calls if c[0] in KRYLOV)
+
+
+@pytest.mark.parametrize("name", list(GCR_CASES))
+def test_gcr_sequences_match_the_model_after_every_call(pkg, po, monkeypatch, name):
+    """mgx_solve_gcr as a fourth graph user: cycle_body through the graph cache with lv[L].b repointed at r, on the
+    workspace mgx_solve_pcg shares (csrc/mgx_krylov_host.hpp).  U and B of every level after every call as for solve_pcg
+    (module docstring); the Jacobi GALERKIN case with and without the visit kernel, bit-equal between the two runs; the
+    line case through line_step"""
+    cfg, seed, envs, options, line = GCR_CASES[name]
+    calls = draw_sequence(seed, cfg, gcr=True, **options)
+    assert_gcr_calls(calls, cfg, options.get("fresh_guess", False), options.get("deep_iters", DEEP_GCR[2]))
+    if options.get("cycles"):
+        assert_cycle_calls(calls, cfg)
+    runs = []
+    for env in envs:
+        if line:
+            runs.append(run_line_sequence(pkg, po, monkeypatch, cfg, calls, seed, env))
+            continue
+        set_knobs(monkeypatch, env)
+        tally = run_sequence(pkg, po, cfg, calls, seed, env)
+        assert 1 <= tally.graphs <= K_MAX_GRAPHS
+        runs.append(tally)
+    if len(runs) == 2:
+        a, b = runs
+        for x, y in zip(a.final, b.final):
+            assert np.array_equal(x, y)
+        assert len(a.histories) == len(b.histories) and all(np.array_equal(x, y) for x, y in zip(a.histories, b.histories))
 
 
 # ---- 3. the cache bound and its fallback ---------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import pytest
 
 import cheby_ref
 import galerkin_ref as gr
+import gcr_ref
 import handle_model as hm
 import line_ref as lr
 import opdep_ref as od
@@ -257,6 +258,144 @@ def test_refused_configurations():
         hm.HandleModel(None, n_gpus=2)
 
 
+# ---- solve_gcr ----------------------------------------------------------------------------------------------------------
+def gcr_with_record(A, M, b, x0, **kw):
+    """gcr_ref.gcr, and the residuals it handed to M"""
+    seen = []
+
+    def recording(r):
+        seen.append(np.array(r, copy=True))
+        return M(r)
+
+    return gcr_ref.gcr(A, recording, b, x0, **kw), seen
+
+
+def assert_gcr_equals(po, m, A, M, u, b, calls):
+    """the model's solve_gcr against gcr_ref.gcr around the reference's own cycle M, for every (tol, max_iters, restart) of
+    `calls` from the guess u: history, x, B, the statistics, and the coarse levels - those of ONE zero-start cycle on the
+    last residual the iteration handed to M (nothing, where it handed none over)"""
+    L = m.L
+    n2 = float((1 << L) - 1) ** 2
+    per = (2 if m.cfg["smoother"] == hm.LINE_ALT else 1) * (m.cfg["mu1"] + m.cfg["mu2"])
+    for tol, max_iters, restart in calls:
+        (x_ref, h_ref, conv, brk), seen = gcr_with_record(A, M, b, u, tol=tol, max_iters=max_iters, restart=restart)
+        m.set_guess(u)
+        m.set_rhs(b)
+        before = {lv: (m.U[lv].copy(), m.B[lv].copy()) for lv in m.levels() if lv < L}
+        st, h = m.solve_gcr(tol=tol, max_iters=max_iters, restart=restart)
+        assert np.array_equal(h, h_ref) and np.array_equal(m.U[L], x_ref) and m.U[L].dtype == x_ref.dtype, (tol, max_iters, restart)
+        assert np.array_equal(m.B[L], b)                    # B is the caller's b again
+        assert st == dict(cycles=len(h_ref) - 1, converged=int(conv and not brk), fine_updates=len(seen) * per * n2), (st, len(seen))
+        if seen:
+            one = hm.HandleModel(po, **m.cfg)
+            one.cycle, one.h, one.transfer = m.cycle, m.h, m.transfer
+            one.set_rhs(seen[-1])
+            one.vcycle_zero()
+            for lv in before:
+                assert np.array_equal(m.U[lv], one.U[lv]) and np.array_equal(m.B[lv], one.B[lv]), (lv, tol, max_iters, restart)
+        else:
+            for lv, (uu, bb) in before.items():
+                assert np.array_equal(m.U[lv], uu) and np.array_equal(m.B[lv], bb), lv
+
+
+def GCR_CALLS(tol):
+    """(tol, max_iters, restart): to convergence; stopped by the count after a restart wrap (slots 0, 1, 0, 1); no iteration;
+    a basis of one"""
+    return [(tol, 30, 4), (0.0, 4, 2), (0.0, 0, 4), (tol, 30, 1)]
+
+
+@pytest.mark.parametrize("smoother", [hm.JACOBI, hm.RBGS])
+@pytest.mark.parametrize("dtype", [hm.F64, hm.F32])
+def test_poisson_solve_gcr_equals_gcr_ref(po, dtype, smoother):
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=2, mu2=1, dtype=dtype, smoother=smoother, schedule=hm.V)
+    dt = np.float64 if dtype == hm.F64 else np.float32
+    u, b = data(po, L, dt, 21)
+    s = pcg_ref.oracle_solver(po, cfg)
+    zeros = np.zeros_like(b)
+    m = hm.HandleModel(po, **cfg)
+    try:
+        assert_gcr_equals(po, m, pcg_ref.Operator(None, dt), lambda r: s.vcycle(L, zeros, r), u, b, GCR_CALLS(1e-8 if dtype == hm.F64 else 1e-4))
+    finally:
+        s.close()
+    st, h = m.solve_gcr(tol=0.0, max_iters=4, restart=2)
+    assert st["cycles"] == 4 and st["converged"] == 0 and len(h) == 5
+    assert st["fine_updates"] == 4 * 3.0 * float((1 << L) - 1) ** 2     # counted from zero: one cycle per iteration
+
+
+def test_stencil5_solve_gcr_equals_gcr_ref(po):
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=2, mu2=2, op=hm.STENCIL5, schedule=hm.V)
+    a = contrast(L, 10.0, 3)
+    u, b = data(po, L, np.float64, 8)
+    s = pcg_ref.oracle_solver(po, cfg, a)
+    zeros = np.zeros_like(b)
+    m = hm.HandleModel(po, **cfg)
+    m.set_coefficient(a)
+    try:
+        assert_gcr_equals(po, m, pcg_ref.Operator(po.stencil_from_nodes(a, L, L), np.float64), lambda r: s.vcycle(L, zeros, r), u, b, GCR_CALLS(1e-8))
+    finally:
+        s.close()
+
+
+def test_galerkin_w_cycle_solve_gcr_equals_gcr_ref_around_wcycle_ref(po):
+    from test_galerkin_cpu import random_stencil5
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=2, mu2=2, op=hm.GALERKIN, schedule=hm.V)
+    st5 = random_stencil5(L, 100 + L)
+    u, b = data(po, L, np.float64, 12)
+    ref = wr.with_cycle(wr.Galerkin, wr.W, po, st5, L, Lc, np.float64, mu1=2, mu2=2)
+    m = hm.HandleModel(po, **cfg)
+    m.set_stencil(L, st5)
+    m.build_galerkin(hm.BILINEAR)
+    m.set_cycle(hm.CYCLE_W)
+    assert_gcr_equals(po, m, pcg_ref.Operator(st5, np.float64), gcr_ref.cycle_preconditioner(ref), u, b, GCR_CALLS(1e-10))
+
+
+def test_line_solve_gcr_equals_gcr_ref_around_line_ref(po):
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=1, mu2=1, op=hm.GALERKIN, smoother=hm.LINE_ALT, schedule=hm.V)
+    ref = line_reference(po, lr.Hierarchy, hm.LINE_ALT, "layers", L, Lc, np.float64, np.float64, hm.CYCLE_V, mu1=1, mu2=1)
+    u, b = data(po, L, np.float64, 14)
+    m = hm.HandleModel(po, **cfg)
+    m.set_operator("layers")
+    assert_gcr_equals(po, m, pcg_ref.Operator(operator5(po, L, "layers", np.float64), np.float64), gcr_ref.cycle_preconditioner(ref), u, b,
+                      GCR_CALLS(1e-8))
+
+
+# POISSON with no smoothing anywhere and bottom = SMOOTH: the zero-start cycle returns exactly zero, M = 0
+M0 = dict(finest_level=7, coarsest_level=4, mu0=0, mu1=0, mu2=0, bottom=hm.SMOOTH, schedule=hm.V)
+
+
+@pytest.mark.parametrize("seed", [None, 7])
+@pytest.mark.parametrize("dtype", [hm.F64, hm.F32])
+def test_solve_gcr_breaks_down_where_the_cycle_returns_zero(po, dtype, seed):
+    """q = A M r = 0, so q'.q' = 0 at iteration 1: gcr_ref around the oracle's cycle reports a breakdown, a history of one
+    entry and an untouched x, and so does the model - U the guess, B the caller's b, the coarse levels those of the one
+    cycle that ran"""
+    L = M0["finest_level"]
+    cfg = dict(M0, dtype=dtype)
+    dt = np.float64 if dtype == hm.F64 else np.float32
+    u, b = data(po, L, dt, 33)
+    if seed is None:
+        u = np.zeros_like(u)
+    s = pcg_ref.oracle_solver(po, cfg)
+    zeros = np.zeros_like(b)
+    A = pcg_ref.Operator(None, dt)
+    try:
+        assert not s.vcycle(L, zeros, b).any()
+        x_ref, h_ref, conv, brk = gcr_ref.gcr(A, lambda r: s.vcycle(L, zeros, r), b, u, 1e-8, 30, 4)
+        assert brk and not conv and len(h_ref) == 1 and np.array_equal(x_ref, u)
+        m = hm.HandleModel(po, **cfg)
+        assert_gcr_equals(po, m, A, lambda r: s.vcycle(L, zeros, r), u, b, [(1e-8, 30, 4)])
+    finally:
+        s.close()
+    assert np.array_equal(m.U[L], u) and np.array_equal(m.B[L], b)
+    assert np.array_equal(m.B[L - 1], po.restrict(b - A(u), hm.CONSISTENT)) and not m.U[L - 1].any()
+    st, h = m.solve_pcg(tol=1e-8, max_iters=30)         # p = M r = 0: p.Ap = 0
+    assert st == dict(cycles=0, converged=0, fine_updates=0.0) and np.array_equal(h, h_ref) and np.array_equal(m.U[L], u)
+
+
 # ---- the sequences of tests/test_gpu_handle_state.py ------------------------------------------------------------------
 FROZEN = {
     # seed: (length, the first ten calls) of draw_sequence(seed, cfg) before the generator learnt its optional calls
@@ -310,6 +449,34 @@ def test_cycle_and_line_sequences_hold_what_the_generator_promises():
                 assert calls[i - 1][0] == "set_guess", (seed, i)
             if c[0] == "vcycle":
                 assert calls[i - 1][:2] == ("set_u", c[1]), (seed, i)
+
+
+def test_gcr_sequences_hold_what_the_generator_promises():
+    orders = set()
+    for name, (cfg, seed, envs, options, line) in gs.GCR_CASES.items():
+        calls = gs.draw_sequence(seed, cfg, gcr=True, **options)
+        assert calls == gs.draw_sequence(seed, cfg, gcr=True, **options)
+        gs.assert_gcr_calls(calls, cfg, options.get("fresh_guess", False), options.get("deep_iters", 9))
+        assert options.get("deep_iters", 9) == 9 or line    # every other double case: nine iterations of GCR(8)
+        assert gs.graph_users(calls) == gs.GCR_USERS
+        if options.get("cycles"):
+            gs.assert_cycle_calls(calls, cfg)
+            users = [i for i, c in enumerate(calls) if c[0] in gs.GCR_USERS]
+            after = [next(calls[u][0] for u in users if u > i) for i, c in enumerate(calls) if c[0] == "set_cycle"]
+            if cfg.get("dtype", hm.F64) == hm.F64:          # where a graph of the old kind would replay under GCR
+                assert "solve_gcr" in after, (name, after)
+        if cfg.get("op", hm.POISSON) == hm.STENCIL5:
+            assert [c[1] for c in calls if c[0] == "set_coefficient"] == [10.0, 100.0, 1000.0]
+        if cfg.get("op", hm.POISSON) == hm.GALERKIN and not line:
+            assert [c[1] for c in calls if c[0] == "build_galerkin"] == [hm.BILINEAR, hm.OPERATOR, hm.BILINEAR, hm.OPERATOR, hm.BILINEAR]
+        if line:
+            assert calls[0] == ("set_operator", options["operators"][0]) and not any(c[0] == "set_coefficient" for c in calls)
+        orders.add(gs.krylov_order(calls))
+    assert orders == {"pcg", "gcr"}                         # the shared workspace allocated by either method first
+    assert len({seed for _, seed, _, _, _ in gs.GCR_CASES.values()}) == len(gs.GCR_CASES)
+    # the option is off by default, and a sequence drawn without it holds no such call
+    for cfg, seed in list(gs.POISSON_CASES.values()) + list(gs.GENERAL_CASES.values()):
+        assert not any(c[0] == "solve_gcr" for c in gs.draw_sequence(seed, cfg))
 
 
 # ---- the cycle index --------------------------------------------------------------------------------------------------
@@ -546,3 +713,80 @@ def test_the_bounds_of_the_line_sequences_stay_below_the_cap(po, name):
     print(f"\n[handle-state] line bounds on the CPU: {name} seed={seed} steps={len(calls)} arrays held to a bound={held} "
           f"largest bound={worst[0]:.3g} at {worst[1]} (cap {cap:g})")
     assert held > 100 and 0.0 < worst[0] <= cap, worst
+
+
+# ---- the conditions the bounds of GCR_CASES rest on ----------------------------------------------------------------------
+def ulp_dot(seed):
+    """pcg_ref.dot with every scalar moved independently by up to one float ulp"""
+    rng = np.random.RandomState(seed)
+
+    def dot(a, b):
+        return pcg_ref.dot(a, b) * (1.0 + 1.2e-7 * rng.uniform(-1.0, 1.0))
+
+    return dot
+
+
+def sync(dst, src):
+    for lv in src.levels():
+        dst.set_level(lv, 0, src.U[lv])
+        dst.set_level(lv, 1, src.B[lv])
+    dst.fine_updates = src.fine_updates
+
+
+@pytest.mark.parametrize("name", list(gs.GCR_CASES))
+def test_the_gcr_sequences_meet_the_conditions_their_bounds_rest_on(po, name):
+    """the model alone through every GCR_CASES sequence, without a device:
+      * double: every solve_gcr and solve_pcg call ends with its last history entry at or above 1e-6 of its first - the
+        iterate never sits in the cancellation regime of b - A u, where a bound relative to max |x| means nothing
+        (the smoothing of the cases is chosen for this; the sequence is changed if it fails, never the bound);
+      * float: PCG32_STATE is fit for solve_gcr.  Every solve_gcr call is run a second time from the same state with
+        every scalar moved independently by up to one float ulp (ulp_dot); the largest movement of any array the call
+        writes, relative to its largest entry, stays at or below PCG32_STATE / 4;
+      * the line case: no bound of THE TOLERANCE RULE above RTOL64"""
+    cfg, seed, envs, options, line = gs.GCR_CASES[name]
+    calls = gs.draw_sequence(seed, cfg, gcr=True, **options)
+    f64 = cfg.get("dtype", hm.F64) == hm.F64
+    L = cfg["finest_level"]
+    if line:
+        m, mx = gs.line_models(po, cfg)
+    else:
+        m, mx = hm.HandleModel(po, **cfg), (None if f64 else hm.HandleModel(po, **cfg))
+    lowest, moved, moved_hist, worst, held, dot = (1.0, None), (0.0, None), 0.0, (0.0, None), 0, ulp_dot(seed)
+    for i, call in enumerate(calls):
+        if line:
+            want, far, bounds = gs.line_call(m, mx, cfg, call)
+            for key, (bound, scale) in bounds.items():
+                held += 1
+                if bound > worst[0]:
+                    worst = (bound, (i, call, key))
+        elif mx is not None:
+            sync(mx, m)
+            want = gs.apply_model(m, call, L)
+            if call[0] == "solve_gcr":
+                st_x, h_x = mx.solve_gcr(tol=call[1], max_iters=call[2], restart=call[3], dot=dot)
+                assert len(h_x) == len(want[1]), (i, call, h_x, want[1])
+                moved_hist = max(moved_hist, float(np.max(np.abs(h_x - want[1]) / want[1])))
+                for lv, which in gs.touched(cfg, call):
+                    a, r = mx.get_level(lv, which == "B").astype(np.float64), m.get_level(lv, which == "B").astype(np.float64)
+                    d = float(np.max(np.abs(a - r))) / float(np.max(np.abs(r)))
+                    if d > moved[0]:
+                        moved = (d, (i, call, lv, which))
+            else:
+                gs.apply_model(mx, call, L)
+        else:
+            want = gs.apply_model(m, call, L)
+        if call[0] in gs.KRYLOV:
+            h = want[1]
+            if f64 and h[-1] / h[0] < lowest[0]:
+                lowest = (float(h[-1] / h[0]), (i, call))
+    print(f"\n[handle-state] GCR conditions on the CPU: {name} seed={seed} steps={len(calls)} lowest last/first of a Krylov call={lowest[0]:.3g} "
+          f"at {lowest[1]}; one-ulp scalars move a written array by {moved[0]:.3g} at {moved[1]}, a history entry by {moved_hist:.3g}; "
+          f"arrays held to a rule bound={held} largest={worst[0]:.3g} at {worst[1]}")
+    if f64:
+        assert 1e-6 <= lowest[0] < 1.0, lowest
+        assert calls[lowest[1][0]][0] in gs.KRYLOV
+    else:
+        assert 0.0 < moved[0] <= gs.PCG32_STATE / 4, moved
+        assert moved_hist <= gs.RTOL32 / 4, moved_hist
+    if line:
+        assert held > 100 and 0.0 < worst[0] <= gs.line_cap(cfg), worst
