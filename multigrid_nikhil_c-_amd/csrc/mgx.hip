@@ -2403,6 +2403,19 @@ __attribute__((visibility("default"))) int mgx_debug_wave_trace(void* out, int c
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mgx::g_wave_trace), (size_t)n * sizeof(mgx::WaveTrace)) != hipSuccess) return -1;
     return n;
 }
+// debug build only: the phase records of k_dst_pair / k_tile_wide (mgx_phase_trace.hpp), oldest first; returns their number
+__attribute__((visibility("default"))) int mgx_debug_phase_trace(void* out, int cap)
+{
+    unsigned n = 0;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(mgx::g_phase_trace_n), sizeof(n)) != hipSuccess) return -1;
+    std::vector<mgx::PhaseTrace> ring(mgx::kPhaseCap);
+    if (hipMemcpyFromSymbol(ring.data(), HIP_SYMBOL(mgx::g_phase_trace), ring.size() * sizeof(mgx::PhaseTrace)) != hipSuccess) return -1;
+    const unsigned have = std::min<unsigned>(n, mgx::kPhaseCap), take = std::min<unsigned>(have, (unsigned)std::max(cap, 0));
+    for (unsigned q = 0; q < take; ++q)
+        static_cast<mgx::PhaseTrace*>(out)[q] = ring[(n - take + q) & (mgx::kPhaseCap - 1)];
+    return (int)take;
+}
 #endif
 
 long mgx_dist_exchanges(mgx_handle s) { return (s && s->dist) ? s->dist->exchanges : -1; }

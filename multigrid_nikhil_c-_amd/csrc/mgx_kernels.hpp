@@ -35,6 +35,7 @@
 
 #include <hip/hip_runtime.h>
 #include "mgx_geom.hpp"
+#include "mgx_phase_trace.hpp"
 #include <stdint.h>
 #include <type_traits>
 
@@ -2072,6 +2073,7 @@ k_tile_wide(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict_
     constexpr int NW = kTileWideWaves;
     __shared__ V edge[2][NW][2][kWave];             // [buffer][wave][first / last row][lane]
     __shared__ double wsum[NW];
+    MGX_PHASE_BEGIN();
     const TileWideGeom g = tile_wide_geom(N, row_lo, row_hi, levels + tile_extra<POST>(), W, RW);
     const int He = g.He, TH = g.TH, TW = g.TW;
     const int lane = threadIdx.x & 63;
@@ -2088,6 +2090,7 @@ k_tile_wide(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict_
 #pragma unroll
     for (int e = 0; e < W; ++e) cu[e] = e == 0 ? cu0 : vld;
     const int NC = N / 2;
+    MGX_PHASE_AFTER(gx0 + gy0);
 
     // ---- load the band (with the correction, PRE) -----------------------------------------------------
     T u[RW][W], b[RW][W];
@@ -2153,6 +2156,9 @@ k_tile_wide(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict_
         else correct(std::integral_constant<int, 0>{});
     }
 
+    MGX_PHASE_AFTER(b[RW - 1][W - 1]);
+    MGX_PHASE_AFTER(u[RW - 1][W - 1]);
+
     // ---- the smoother levels, in lockstep over the workgroup ---------------------------
     int buf = 0;
     auto halo_rows = [&](const T (&a)[RW][W], T (&up)[W], T (&dn)[W]) {
@@ -2195,6 +2201,7 @@ k_tile_wide(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict_
 #pragma unroll
             for (int e = 0; e < W; ++e) prev[e] = cur[e];
         }
+        MGX_PHASE_AFTER(u[RW - 1][W - 1]);
     }
     // u is the result on array rows [levels, SY - levels) and columns [levels, SX - levels)
 
@@ -2206,6 +2213,7 @@ k_tile_wide(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict_
         if (y >= He && y < He + TH && gy < N && gy >= row_lo && gy < row_hi && colout)
             *reinterpret_cast<V*>(vout + (long)gy * pitch + gx0) = vmake(u[i]);
     }
+    MGX_PHASE();
 
     if (POST != 0) {
         // residual of the result: r = b - A u on the tile (+- 1 node for the restriction)
@@ -2235,6 +2243,7 @@ k_tile_wide(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict_
 #pragma unroll
             for (int e = 0; e < W; ++e) prev[e] = u[i][e];
         }
+        MGX_PHASE_AFTER(res[RW - 1][W - 1]);
         if (POST == 2) {
             for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, kWave);
             if (lane == 0) wsum[wv] = acc;
@@ -2281,6 +2290,7 @@ k_tile_wide(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict_
             }
         }
     }
+    MGX_PHASE_END(kPhaseTile, N | (PRE << 16) | (POST << 20) | (RW << 24));
 }
 
 // mixed precision (config 5): u64 += scale * (double) e32, rows [row_lo,row_hi)
