@@ -133,3 +133,37 @@ def test_reference_signatures_compile_as_the_reference_calls_them(tmp_path):
     r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
+
+
+def test_reference_level_inference_from_vector_lengths(pkg, tmp_path):
+    """mgxref::level_of_size: the reference infers a vector's level as int(log2(sqrt(size) + 1)) in floating
+    point (PS:583, 616, 634); for n = 2^L - 1 the argument of log2 is exactly 2^L only if sqrt and log2 are
+    exact there - every level the library accepts (2..15) must come out as L, not L - 1"""
+    import subprocess
+
+    src = tmp_path / "levels.cpp"
+    src.write_text(
+        '#include "mgx_reference_api.hpp"\n'
+        '#include <cstdio>\n'
+        'int main() {\n'
+        '    int bad = 0;\n'
+        '    for (int L = 2; L <= 15; ++L) {\n'
+        '        const std::size_t n = (std::size_t(1) << L) - 1;\n'
+        '        const int got = mgxref::level_of_size(n * n);\n'
+        '        std::printf("%d %d\\n", L, got);\n'
+        '        bad += got != L;\n'
+        '    }\n'
+        '    return bad;\n'
+        '}\n')
+    exe = tmp_path / "levels"
+    cmd = ["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0 and "undefined reference" in r.stderr:
+        # a compiler that emits the header's unused inline wrappers wants the library they call
+        libdir = os.path.dirname(pkg.LIB_PATH)
+        r = subprocess.run(cmd + ["-L", libdir, "-lmgx", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"],
+                           capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout
+    assert [ln.split() for ln in out.stdout.splitlines()] == [[str(L), str(L)] for L in range(2, 16)]
