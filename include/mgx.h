@@ -81,11 +81,13 @@ enum { MGX_RESTRICT_CONSISTENT = 0, MGX_RESTRICT_FW16 = 1,
  * the coarsest operator (MF:63-72: dense inverse; coarsest_level <= 5).  dtype F64 / F32, Jacobi, Chebyshev or a line smoother, one GPU.
  * Algorithmic bytes per point and sweep: 8 sizeof(T) (v, b, D_inv, four R arrays in; v' out). */
 enum { MGX_OPERATOR_POISSON = 0, MGX_OPERATOR_STENCIL5 = 1,
-       /* GALERKIN: the variational hierarchy.  The finest level is a general five-point operator given as for STENCIL5;
-        * every coarser level is the NINE-point operator A_{l-1} = R A_l P built on the device by mgx_build_galerkin
-        * (P: the bilinear prolongation, R: the handle's full weighting; csrc/mgx_galerkin.hpp).  Same restrictions as
-        * STENCIL5, and restrict_mode CONSISTENT or FW16 only.  Coarse levels move 12 sizeof(T) per point and sweep
-        * (v, b, D_inv, eight R arrays in; v' out); the finest keeps 8 sizeof(T).
+       /* GALERKIN: the variational hierarchy.  The finest level is a general five-point operator given as for STENCIL5,
+        * or a general NINE-point operator (mgx_set_stencil9, mgx_set_tensor: mixed derivatives, rotated anisotropy, Q1
+        * stiffness matrices, compact fourth-order stencils); every coarser level is the NINE-point operator
+        * A_{l-1} = R A_l P built on the device by mgx_build_galerkin (P: the bilinear prolongation, R: the handle's full
+        * weighting; csrc/mgx_galerkin.hpp).  Same restrictions as STENCIL5, and restrict_mode CONSISTENT or FW16 only.
+        * Nine-point levels move 12 sizeof(T) per point and sweep (v, b, D_inv, eight R arrays in; v' out); a five-point
+        * finest level keeps 8 sizeof(T).
         * (The value 2 stays an invalid operator: mgx_create has always refused it and the suite pins that.) */
        MGX_OPERATOR_GALERKIN = 3 };
 enum { MGX_BOTTOM_EXACT = 0, MGX_BOTTOM_SMOOTH = 1 };
@@ -222,9 +224,50 @@ MGX_API int mgx_get_stencil(mgx_handle h, int level, int which, void* dst, size_
  * been given or the handle's op is not GALERKIN. */
 MGX_API int mgx_build_galerkin(mgx_handle h);
 /* read back (after mgx_build_galerkin): which = 0..8 the level's operator (c, n, s, w, e, nw, ne, sw, se; the corners
- * are zero on the finest level), 9 = D_inv, 10..17 = the off-diagonals of R_omega in the same order (n .. se).
- * mgx_get_stencil keeps its meaning on the finest level and returns MGX_ERR_STATE for the nine-point levels. */
+ * are zero on a five-point finest level), 9 = D_inv, 10..17 = the off-diagonals of R_omega in the same order (n .. se).
+ * mgx_get_stencil keeps its meaning on a five-point finest level and returns MGX_ERR_STATE for the nine-point levels
+ * (a nine-point finest level among them). */
 MGX_API int mgx_get_stencil9(mgx_handle h, int level, int which, void* dst, size_t count);
+
+/* ---- nine-point finest operators: handles with op = MGX_OPERATOR_GALERKIN ----------------------------------------
+ * The finest operator as nine coefficient grids, in the layout and slot order of mgx_get_stencil9 (interior n x n,
+ * row-major, the handle's working type):
+ *     (A u)_ij = nw u_(i-1)(j-1) + n u_(i-1)j + ne u_(i-1)(j+1) + w u_i(j-1) + c u_ij + e u_i(j+1)
+ *              + sw u_(i+1)(j-1) + s u_(i+1)j + se u_(i+1)(j+1)        (summed in this order, as on every nine-point level).
+ * The operator need not be symmetric.  `level` must be the finest (a coarser one: MGX_ERR_STATE, as in mgx_set_stencil);
+ * MGX_ERR_STATE on handles whose op is not GALERKIN (STENCIL5 re-discretises every level as a five-point operator,
+ * POISSON has no coefficients); MGX_ERR_INVALID for a NULL pointer or count != n * n.  The call invalidates the
+ * hierarchy exactly as mgx_set_stencil does (schedules return MGX_ERR_STATE until mgx_build_galerkin[_transfer] has
+ * run; cached graphs are dropped) and makes the finest level a nine-point level: every smoother, transfer, cycle and
+ * solver (mgx_solve_pcg and mgx_solve_gcr included) then runs the nine-point kernels there, mgx_get_stencil9 returns
+ * its nine grids, D_inv and the eight off-diagonals of R_omega, and mgx_get_stencil returns MGX_ERR_STATE on it.  In
+ * W- and F-cycles the finest level always keeps the per-level launches, whatever its size.
+ * A later mgx_set_stencil or mgx_set_coefficient makes the finest level five-point again; the handle then computes
+ * the bits of a handle that never saw a nine-point operator.  The first of mgx_set_stencil9 / mgx_set_tensor allocates
+ * the finest level's eight corner arrays (before anything else is done: MGX_ERR_ALLOC leaves the previous operator
+ * and hierarchy usable); they are kept, unread on a five-point level, until mgx_destroy.
+ * Coefficients that point at the eliminated Dirichlet ring (n on the first row, nw on the first row and the first
+ * column, ...) are ignored: every result is that of the same operator with zeros there.  They are STORED AS GIVEN, as
+ * mgx_set_stencil stores them: mgx_get_stencil9 returns the caller's values in those places of the finest operator
+ * (and the R_omega entries computed from them); the coarse operators hold zeros there. */
+MGX_API int mgx_set_stencil9(mgx_handle h, int level, const void* c, const void* n, const void* s, const void* w, const void* e,
+                             const void* nw, const void* ne, const void* sw, const void* se, size_t count);
+/* The finest operator of the full-tensor diffusion problem
+ *     - d_x(axx d_x u) - d_y(ayy d_y u) - d_x(axy d_y u) - d_y(axy d_x u)
+ * from the nodal values of axx, axy, ayy on the finest grid's (N + 1)^2 nodes (double, row-major, boundary nodes
+ * included, as for mgx_set_coefficient; x runs along a row, y grows with the row index), discretised on the device
+ * (k_var_from_tensor), all arithmetic in double, each coefficient rounded to the working type once.  At node (r, c),
+ * with aN, aS, aW, aE = axy at (r-1, c), (r+1, c), (r, c-1), (r, c+1):
+ *     fn = 0.5 (ayy(r,c) + ayy(r-1,c)),  fs = 0.5 (ayy(r,c) + ayy(r+1,c)),
+ *     fw = 0.5 (axx(r,c) + axx(r,c-1)),  fe = 0.5 (axx(r,c) + axx(r,c+1)),
+ *     c = ((fn + fw) + fe) + fs,   n = -fn,  s = -fs,  w = -fw,  e = -fe      (mgx_set_coefficient's five-point part),
+ *     nw = -(0.25 (aW + aN)),  ne = 0.25 (aE + aN),  sw = 0.25 (aW + aS),  se = -(0.25 (aE + aS)).
+ * Like mgx_set_coefficient it carries no h^-2.  The four corners of a point sum to zero, so the row sum is that of the
+ * five-point part; the assembled operator is symmetric bit for bit (e(i,j) = w(i,j+1), se(i,j) = nw(i+1,j+1),
+ * ne(i,j) = sw(i-1,j+1)) and exact on quadratics.  It is a central discretisation of the mixed term: for strong
+ * mixed terms it is not an M-matrix (no upwinding).  axy = 0 and axx = ayy = a give mgx_set_coefficient(a)'s operator.
+ * State model, errors and ring-pointing coefficients as for mgx_set_stencil9; count != (N + 1)^2: MGX_ERR_INVALID. */
+MGX_API int mgx_set_tensor(mgx_handle h, const double* axx, const double* axy, const double* ayy, size_t count);
 
 /* ---- the prolongation of the Galerkin hierarchy (csrc/mgx_opdep.hpp) ------------------------------------------
  * BILINEAR: the weights 1, 1/2, 1/4 on every level.  OPERATOR: the operator-dependent ("black box", Alcouffe / Dendy)
@@ -327,8 +370,8 @@ MGX_API int mgx_vcycle_zero(mgx_handle h);
  * times by a W-cycle.  With MGX_CYCLE_V every entry point computes the bits it computed before this call existed.
  * The setter drops the handle's cached graphs (the next cycle is captured anew).  cfg.profile = 2: the coarse part
  * (one graph replay between two events) is all the visits of level finest - 1.
- * In W- and F-cycles a visit of a nine-point level with N <= 64 (level <= 6) of a GALERKIN handle with the Jacobi
- * smoother is one launch of one workgroup (csrc/mgx_small.hpp: the iterate in LDS, the coefficients in registers),
+ * In W- and F-cycles a visit of a nine-point level below the finest with N <= 64 (level <= 6) of a GALERKIN handle with
+ * the Jacobi smoother is one launch of one workgroup (csrc/mgx_small.hpp: the iterate in LDS, the coefficients in registers),
  * bit-identical to the per-level launches it replaces; every other level, smoother and operator runs W and F through
  * the per-level launches, and so does everything when the environment holds MGX_SMALL_VISIT=0 at mgx_create.
  * Handles with op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN (single GPU, dtype F64 or F32, either smoother);
@@ -416,7 +459,8 @@ MGX_API int mgx_time_smoother(mgx_handle h, int sweeps, double* ms);
  * events on the handle's own buffers (tools/gcr_bench.py).  The scalars are zeroed first, so the passes leave U, B
  * and the saved iterate unchanged (DIRECTION rewrites basis slot j from U; the basis has no meaning between two
  * mgx_solve_gcr calls).  UPDATE is k_pcg_update (6 sizeof(T) per point, the yardstick),
- * DOTS k_gcr_dots<j> (j >= 1), ORTH k_gcr_orth<j>, DIRECTION k_pcg_direction.  MGX_ERR_STATE until a mgx_solve_gcr
+ * DOTS k_gcr_dots<j> (j >= 1), ORTH k_gcr_orth<j>, DIRECTION k_pcg_direction (4 sizeof(T) per point plus the coefficient
+ * grids of the finest operator: none for POISSON, 5 on a five-point, 9 on a nine-point finest level).  MGX_ERR_STATE until a mgx_solve_gcr
  * call with restart > j has allocated the basis. */
 enum { MGX_GCR_PASS_UPDATE = 0, MGX_GCR_PASS_DOTS = 1, MGX_GCR_PASS_ORTH = 2, MGX_GCR_PASS_DIRECTION = 3 };
 MGX_API int mgx_time_gcr_pass(mgx_handle h, int pass, int j, int repeats, double* ms);

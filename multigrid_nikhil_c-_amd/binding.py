@@ -51,7 +51,7 @@ EXPORTS = [
     "mgx_plan_cut_share", "mgx_plan_guess_set", "mgx_plan_vcycle", "mgx_plan_norm", "mgx_plan_fmg", "mgx_rccl_unique_id",
     "mgx_create_rank", "mgx_dist_exchanges", "mgx_dist_overlapped", "mgx_memcpy_d2h", "mgx_memcpy_h2d", "mgx_runtime_libs",
     "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg", "mgx_solve_gcr", "mgx_time_gcr_pass",
-    "mgx_build_galerkin", "mgx_get_stencil9",
+    "mgx_build_galerkin", "mgx_get_stencil9", "mgx_set_stencil9", "mgx_set_tensor",
     "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max", "mgx_get_line_factor", "mgx_get_line_chunks",
     "mgx_set_cycle", "mgx_get_cycle",
 ]
@@ -205,6 +205,8 @@ def lib() -> C.CDLL:
     L.mgx_runtime_libs.argtypes = [C.c_char_p, C.c_size_t]
     L.mgx_set_stencil.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_size_t]
     L.mgx_set_coefficient.argtypes = [vp, vp, C.c_size_t]
+    L.mgx_set_stencil9.argtypes = [vp, C.c_int] + [vp] * 9 + [C.c_size_t]
+    L.mgx_set_tensor.argtypes = [vp, vp, vp, vp, C.c_size_t]
     L.mgx_get_stencil.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L.mgx_build_galerkin.argtypes = [vp]
     L.mgx_get_stencil9.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
@@ -424,6 +426,20 @@ class Multigrid:
         """every level's operator from the nodal coefficient of -div(a grad u) on the finest grid ((N + 1)^2 doubles)"""
         a = np.ascontiguousarray(a_nodes, dtype=np.float64)
         self._chk(lib().mgx_set_coefficient(self._h, a.ctypes.data, a.size), "mgx_set_coefficient")
+
+    def set_stencil9(self, level, c, n, s, w, e, nw, ne, sw, se):
+        """a nine-point finest operator of a GALERKIN handle: nine interior n x n coefficient arrays in the slot order
+        of get_stencil9 (mgx_set_stencil9); build_galerkin() then builds the hierarchy below it"""
+        dt = self.level_dtype(level)
+        a = [np.ascontiguousarray(x, dtype=dt) for x in (c, n, s, w, e, nw, ne, sw, se)]
+        self._chk(lib().mgx_set_stencil9(self._h, level, *[x.ctypes.data for x in a], a[0].size), "mgx_set_stencil9")
+
+    def set_tensor(self, axx, axy, ayy):
+        """the nine-point finest operator of -d_x(axx d_x u) - d_y(ayy d_y u) - d_x(axy d_y u) - d_y(axy d_x u) from the
+        nodal values of the three coefficients on the finest grid ((N + 1)^2 doubles each; mgx_set_tensor)"""
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (axx, axy, ayy)]
+        assert a[0].size == a[1].size == a[2].size, "axx, axy, ayy must have the same size"
+        self._chk(lib().mgx_set_tensor(self._h, *[x.ctypes.data for x in a], a[0].size), "mgx_set_tensor")
 
     def get_stencil(self, level, which):
         n = self.n(level)

@@ -57,7 +57,9 @@ struct Level {
     void *u = nullptr, *b = nullptr, *tmp = nullptr, *r = nullptr;
     // MGX_OPERATOR_STENCIL5 / GALERKIN (mgx_var.hpp), in the slot order c, n, s, w, e, nw, ne, sw, se: the operator A
     // [ProblemVar::A_sp_dict, MF:19] and its Jacobi splitting J = (D_inv, R_n, R_s, ..., R_se)  [A_jacobi_sp_dict, MF:20,
-    // 28-32].  The corner slots 5..8 exist on nine-point levels only (`nine`: R A P, below the finest GALERKIN level)
+    // 28-32].  The corner slots 5..8 exist on the levels below the finest GALERKIN level (R A P) and, from the first
+    // mgx_set_stencil9 / mgx_set_tensor on, on the finest one; `nine`: the level's current operator is nine-point (the
+    // NQ = 5 instances never read slots 5..8)
     void* A[9] = {};
     void* J[9] = {};
     // MGX_TRANSFER_OPERATOR (mgx_opdep.hpp): the eight weight grids (n, s, w, e, nw, ne, sw, se) of P between level
@@ -341,6 +343,20 @@ int var_alloc_level(mgx_solver* s, Level& l)
     return MGX_OK;
 }
 
+// the corner arrays A[5..8], J[5..8] of the finest GALERKIN level, allocated and zeroed by the first nine-point finest
+// operator and kept until mgx_destroy.  Nothing is launched before all eight exist: a failure leaves the level's
+// operator, `nine` and the hierarchy as they were (arrays already allocated stay for the next attempt)
+int finest_corners(mgx_solver* s, Level& l)
+{
+    for (int q = 5; q < 9; ++q)
+        for (void** p : {&l.A[q], &l.J[q]}) {
+            if (*p) continue;
+            if (hipMalloc(p, l.bytes) != hipSuccess) { *p = nullptr; return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the nine-point operator's corner arrays"); }
+            HIPCHK(s, hipMemsetAsync(*p, 0, l.bytes, s->stream));         // the ring and the padding stay zero from here on
+        }
+    return MGX_OK;
+}
+
 // dense inverse of the NN x NN matrix in var_M (k_var_dense_fill wrote it) into var_inv
 void gj_invert(mgx_solver* s, int NN)
 {
@@ -545,7 +561,7 @@ int var_ready(mgx_solver* s, int lo, int hi)
     if (!s->var) return MGX_OK;
     if (s->galerkin && !s->gal_built)
         return s->fail(MGX_ERR_STATE, s->lv[s->cfg.finest_level].stencil_set ? "Galerkin hierarchy not built (mgx_build_galerkin)"
-                                                                             : "finest operator not set (mgx_set_stencil / mgx_set_coefficient)");
+                                                                             : "finest operator not set (mgx_set_stencil / mgx_set_coefficient / mgx_set_stencil9 / mgx_set_tensor)");
     for (int l = lo; l <= hi; ++l)
         if (!s->lv[l].stencil_set)
             return s->fail(MGX_ERR_STATE, "operator of level " + std::to_string(l) + " not set (mgx_set_stencil / mgx_set_coefficient)");
@@ -904,13 +920,14 @@ void ascend(mgx_solver* s, int level, int post)
 void vcycle(mgx_solver* s, int level, bool zero_in_here = false, int post_top = 0, int kind = -1);
 
 // Is a visit of `level` one launch of k_small_visit (mgx_small.hpp)?  Only in the W- and F-cycles of a GALERKIN handle
-// with the Jacobi smoother, on nine-point levels above the coarsest with N <= 64: the V-cycle keeps its launches and its
-// bits, and everything else runs W and F through the per-level launches
+// with the Jacobi smoother, on nine-point levels above the coarsest and below the finest with N <= 64: the V-cycle keeps
+// its launches and its bits, and everything else - a nine-point FINEST level too, whatever its size: it is visited once
+// per cycle, by the cycle's own entry and exit - runs W and F through the per-level launches
 bool small_level(const mgx_solver* s, int level)
 {
     if (!s->small_visit || s->cycle == MGX_CYCLE_V || !s->galerkin || !s->gal_built) return false;
     if (s->cfg.smoother != MGX_SMOOTHER_JACOBI) return false;
-    if (level <= s->cfg.coarsest_level || level > s->cfg.finest_level) return false;
+    if (level <= s->cfg.coarsest_level || level >= s->cfg.finest_level) return false;
     const Level& l = s->lv[level];
     return l.nine && l.N <= s->small_max_n;
 }
@@ -1662,8 +1679,65 @@ int mgx_set_stencil(mgx_handle s, int level, const void* c, const void* n, const
         int rc = copy_in(s, l, l.A[q], src[q], count);
         if (rc) return rc;
     }
-    if (s->galerkin) { galerkin_invalidate(s); return MGX_OK; }
+    if (s->galerkin) { l.nine = false; galerkin_invalidate(s); return MGX_OK; }     // (corner arrays of an earlier nine-point operator: kept, not read)
     return var_build(s, l);
+}
+
+// the guards mgx_set_stencil9 and mgx_set_tensor share; nullptr: the handle takes a nine-point finest operator
+static const char* nine_finest_refusal(const mgx_solver* s)
+{
+    if (!s->galerkin)
+        return "nine-point finest operators need op = MGX_OPERATOR_GALERKIN (STENCIL5 and POISSON hierarchies are five-point on every level)";
+    return nullptr;
+}
+
+int mgx_set_stencil9(mgx_handle s, int level, const void* c, const void* n, const void* so, const void* w, const void* e, const void* nw,
+                     const void* ne, const void* sw, const void* se, size_t count)
+{
+    if (!s || !c || !n || !so || !w || !e || !nw || !ne || !sw || !se) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (const char* why = nine_finest_refusal(s)) return s->fail(MGX_ERR_STATE, why);
+    if (!level_ok(s, level)) return s->fail(MGX_ERR_INVALID, "level out of range");
+    if (level != s->cfg.finest_level)
+        return s->fail(MGX_ERR_STATE, "MGX_OPERATOR_GALERKIN: only the finest operator is the caller's (coarse levels are R A P: mgx_build_galerkin)");
+    Level& l = s->lv[level];
+    const size_t nn = (size_t)l.N - 1;
+    if (count != nn * nn) return s->fail(MGX_ERR_INVALID, "vector length must be n*n with n = 2^level - 1");
+    if (int rc = finest_corners(s, l)) return rc;
+    const void* src[9] = {c, n, so, w, e, nw, ne, sw, se};
+    for (int q = 0; q < 9; ++q)
+        if (int rc = copy_in(s, l, l.A[q], src[q], count)) return rc;
+    l.nine = true;
+    galerkin_invalidate(s);
+    return MGX_OK;
+}
+
+int mgx_set_tensor(mgx_handle s, const double* axx, const double* axy, const double* ayy, size_t count)
+{
+    if (!s || !axx || !axy || !ayy) return MGX_ERR_INVALID;
+    NO_DIST(s)
+    if (const char* why = nine_finest_refusal(s)) return s->fail(MGX_ERR_STATE, why);
+    Level& l = s->lv[s->cfg.finest_level];
+    if (count != (size_t)(l.N + 1) * (size_t)(l.N + 1)) return s->fail(MGX_ERR_INVALID, "every tensor component must hold (N + 1)^2 nodal values, N = 2^finest_level");
+    double* dev = nullptr;
+    if (hipMalloc(&dev, 3 * count * sizeof(double)) != hipSuccess) return s->fail(MGX_ERR_ALLOC, "hipMalloc failed for the nodal tensor");
+    int rc = finest_corners(s, l);
+    const double* src[3] = {axx, axy, ayy};
+    for (int k = 0; k < 3 && rc == MGX_OK; ++k)
+        if (hipMemcpyAsync(dev + k * count, src[k], count * sizeof(double), hipMemcpyHostToDevice, s->stream) != hipSuccess)
+            rc = s->fail(MGX_ERR_HIP, "copy of the nodal tensor failed");
+    if (rc == MGX_OK) {
+        const dim3 blk(256), grd((l.N + 1 + 255) / 256, l.N + 1);
+        with_float_type(l.f64, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL((k_var_from_tensor<T>), grd, blk, 0, s->stream, dev, dev + count, dev + 2 * count, out9(op9_of<T>(l)), l.N, l.pitch);
+        });
+        if (hipGetLastError() != hipSuccess) rc = s->fail(MGX_ERR_HIP, "launch of the tensor discretisation failed");
+    }
+    if (hipStreamSynchronize(s->stream) != hipSuccess && rc == MGX_OK) rc = s->fail(MGX_ERR_HIP, "discretising the nodal tensor failed");
+    (void)hipFree(dev);
+    if (rc == MGX_OK) { l.nine = true; galerkin_invalidate(s); }
+    return rc;
 }
 
 int mgx_set_coefficient(mgx_handle s, const double* a_nodes, size_t count)
@@ -1689,7 +1763,7 @@ int mgx_set_coefficient(mgx_handle s, const double* a_nodes, size_t count)
     }
     if (hipStreamSynchronize(s->stream) != hipSuccess && rc == MGX_OK) rc = s->fail(MGX_ERR_HIP, "sampling the nodal coefficient failed");
     (void)hipFree(dev);
-    if (s->galerkin && rc == MGX_OK) galerkin_invalidate(s);
+    if (s->galerkin && rc == MGX_OK) { s->lv[Lf].nine = false; galerkin_invalidate(s); }
     return rc;
 }
 
@@ -1700,7 +1774,7 @@ int mgx_get_stencil(mgx_handle s, int level, int which, void* dst, size_t count)
     if (!s->var) return s->fail(MGX_ERR_STATE, "handle was created with op = MGX_OPERATOR_POISSON");
     if (!level_ok(s, level) || which < 0 || which > 9) return s->fail(MGX_ERR_INVALID, "level or array selector out of range");
     Level& l = s->lv[level];
-    if (l.nine) return s->fail(MGX_ERR_STATE, "nine-point operator (coarse level of a GALERKIN handle): use mgx_get_stencil9");
+    if (l.nine) return s->fail(MGX_ERR_STATE, "nine-point operator (a coarse level, or a nine-point finest level, of a GALERKIN handle): use mgx_get_stencil9");
     if (!l.stencil_set) return s->fail(MGX_ERR_STATE, "operator of this level not set");
     if (s->galerkin && which >= 5 && !s->gal_built) return s->fail(MGX_ERR_STATE, "Galerkin hierarchy not built (mgx_build_galerkin)");
     return copy_out(s, l, which < 5 ? l.A[which] : l.J[which - 5], dst, count);
@@ -1712,7 +1786,7 @@ int mgx_build_galerkin(mgx_handle s)
     NO_DIST(s)
     if (!s->galerkin) return s->fail(MGX_ERR_STATE, "handle was not created with op = MGX_OPERATOR_GALERKIN");
     if (!s->lv[s->cfg.finest_level].stencil_set)
-        return s->fail(MGX_ERR_STATE, "finest operator not set (mgx_set_stencil / mgx_set_coefficient)");
+        return s->fail(MGX_ERR_STATE, "finest operator not set (mgx_set_stencil / mgx_set_coefficient / mgx_set_stencil9 / mgx_set_tensor)");
     return s->work_f64 ? galerkin_build_t<double>(s, MGX_TRANSFER_BILINEAR) : galerkin_build_t<float>(s, MGX_TRANSFER_BILINEAR);
 }
 
@@ -1724,7 +1798,7 @@ int mgx_build_galerkin_transfer(mgx_handle s, int transfer)
     if (transfer != MGX_TRANSFER_BILINEAR && transfer != MGX_TRANSFER_OPERATOR)
         return s->fail(MGX_ERR_INVALID, "transfer must be MGX_TRANSFER_BILINEAR or MGX_TRANSFER_OPERATOR");
     if (!s->lv[s->cfg.finest_level].stencil_set)
-        return s->fail(MGX_ERR_STATE, "finest operator not set (mgx_set_stencil / mgx_set_coefficient)");
+        return s->fail(MGX_ERR_STATE, "finest operator not set (mgx_set_stencil / mgx_set_coefficient / mgx_set_stencil9 / mgx_set_tensor)");
     return s->work_f64 ? galerkin_build_t<double>(s, transfer) : galerkin_build_t<float>(s, transfer);
 }
 
@@ -1798,7 +1872,8 @@ int mgx_get_stencil9(mgx_handle s, int level, int which, void* dst, size_t count
     Level& l = s->lv[level];
     // 0..8: c, n, s, w, e, nw, ne, sw, se;  9: D_inv;  10..17: R_n, R_s, R_w, R_e, R_nw, R_ne, R_sw, R_se
     const void* src = which < 9 ? l.A[which] : l.J[which - 9];
-    if (!src) {                                               // corners of the five-point finest level
+    const int slot = which < 9 ? which : which - 9;
+    if (!src || (!l.nine && slot >= 5)) {                     // corners of a five-point finest level (arrays of an earlier nine-point operator: not read)
         const size_t n = (size_t)l.N - 1;
         if (count != n * n) return s->fail(MGX_ERR_INVALID, "vector length must be n*n with n = 2^level - 1");
         std::memset(dst, 0, count * l.esize());

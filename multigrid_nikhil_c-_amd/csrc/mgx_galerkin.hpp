@@ -1,4 +1,4 @@
-// mgx_galerkin.hpp - the variational hierarchy of a general five-point operator (cfg.op = MGX_OPERATOR_GALERKIN):
+// mgx_galerkin.hpp - the variational hierarchy of a general five- or nine-point operator (cfg.op = MGX_OPERATOR_GALERKIN):
 // A_{l-1} = R A_l P with P the bilinear prolongation (k_prolong) and R the handle's own full weighting
 // (CONSISTENT: R = P^T, weights 1, 1/2, 1/4; FW16: R = P^T / 4).  R A P of a five-point operator is a NINE-point
 // operator, so every level below the finest carries nine coefficient grids and runs the NQ = 9 instances of the
@@ -25,7 +25,7 @@ __host__ __device__ constexpr int iabs(int x) { return x < 0 ? -x : x; }
 
 // one coarse row per wave and strip; each lane owns W coarse points and reads the 2W + 1 fine columns under them as
 // two 16-byte vectors plus the last element of its left neighbour's second vector.  CORNERS: the fine operator has
-// corner grids (false on the finest level: slots 5..8 are not read)
+// corner grids (false on a five-point finest level: slots 5..8 are not read)
 template <typename T, bool CORNERS>
 __global__ void __launch_bounds__(kBlock)
 k_galerkin_rap(Op9<T> f, Op9Out<T> c, int NC, long fpitch, long cpitch, int strips, T rscale)

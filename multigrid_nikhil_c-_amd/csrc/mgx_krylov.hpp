@@ -6,12 +6,14 @@
 // Flexible PCG with the Polak-Ribiere beta; per iteration, after the V-cycle z = M r:
 //   k_pcg_dots       rho_new = r.z and gamma = z.q                         reads r, z, q           3 sizeof(T)
 //   k_pcg_direction  p' = z + beta p, q = A p', delta = p'.q               reads z, p; writes p', q 4 sizeof(T)
-//                    (STENCIL5: + the five coefficient grids)              (+ 5 sizeof(T))
+//                    (general operators: + the five / nine coefficient     (+ 5 / 9 sizeof(T))
+//                    grids of a five- / nine-point finest level)
 //   k_pcg_update     x += alpha p, r -= alpha q, ||r||^2                   reads x, p, r, q;
 //                                                                          writes x, r             6 sizeof(T)
 //   k_pcg_reduce     the per-block partials of one pass summed in a fixed order by one workgroup, and the scalar
 //                    that depends on them (alpha after delta; beta and rho after the dots): no host round trip
-// 13 sizeof(T) per fine point and iteration: 104 B in double, 52 B in float.
+// 13 sizeof(T) per fine point and iteration: 104 B in double, 52 B in float (18 / 22 with the coefficient grids of a
+// five- / nine-point finest operator: the direction pass alone moves 4 / 9 / 13 sizeof(T)).
 //
 // Every pass covers rows 1 .. N-1 in the geometry of k_residual (row chunks marching down a column strip,
 // W-wide vectors, halo lanes 0 and 63 never store) and masks columns 0 and >= N, so the Dirichlet ring and the
@@ -26,14 +28,14 @@
 //   r = b - A x;  h0 = ||r||;  basis empty
 //   iteration k:  j = k mod restart;  if j == 0: basis empty
 //     z = M r                                   (zero-start cycle)
-//     q = A z                                   (stencil order of k_pcg_direction: residual_vec / stencil_sum<5>)
+//     q = A z                                   (stencil order of k_pcg_direction: residual_vec / stencil_sum<5 | 9>)
 //     h_i = (q.Q_i) / s_i   for i < j           (classical Gram-Schmidt: all dots from the unmodified q)
 //     q' = ((q - h_0 Q_0) - h_1 Q_1) - ... ;  z' = the same combination of z and Z_i
 //     s_j = q'.q';  rho = r.q';  breakdown unless s_j > 0 and finite;  alpha = rho / s_j
 //     x += alpha z';  r -= alpha q';  history <- sqrt(r.r);  Z_j = z', Q_j = q'
 //     stop when ||r|| <= tol h0 or k + 1 == max_iters
 // per iteration, after the cycle:
-//   k_pcg_direction  first_it = 1: Z_j = z (out of lv.u), Q_j = q = A z        as above       4 (+ 5) sizeof(T)
+//   k_pcg_direction  first_it = 1: Z_j = z (out of lv.u), Q_j = q = A z        as above       4 (+ 5 | 9) sizeof(T)
 //   k_gcr_dots<J>    q.Q_i, i < J (J = j >= 1)               reads q, Q_0 .. Q_{J-1}          (1 + J) sizeof(T)
 //   k_gcr_orth<J>    q', z' in place in slot J, q'.q', r.q'  reads q, z, r, J pairs; writes q', z'
 //                                                                                             (5 + 2J) sizeof(T)
@@ -115,7 +117,10 @@ k_pcg_dots(const T* __restrict__ r, const T* __restrict__ z, const T* __restrict
 // p' = z + beta p (first_it: p' = z, p not read), q = A p', delta partials p'.q.  A lane forms p' of its row
 // neighbours from z and p as it marches down (rows r0-1 .. r1), its column neighbours come from the adjacent lanes.
 // OP 0: the constant five-point stencil in the order of residual_vec (A u = -(((N + W) + E) + S) + 4 u);
-// OP 1: the level's five coefficient grids a, in the order of stencil_sum<5>().
+// OP 1: the level's five coefficient grids a, in the order of stencil_sum<5>();
+// OP 2: its nine coefficient grids, in the order of stencil_sum<9>() (the CSR order of mgx_var.hpp): a lane then also
+// needs the elements left and right of its vector in the rows above and below (Rows3::ul, ur, dl, dr), p' of the
+// adjacent lanes in those rows; ring rows and columns are zero without a load, as for the other two.
 template <typename T, int OP>
 __global__ void __launch_bounds__(kBlock)
 k_pcg_direction(const T* __restrict__ z, const T* __restrict__ p, T* __restrict__ pn, T* __restrict__ q,
@@ -143,18 +148,32 @@ k_pcg_direction(const T* __restrict__ z, const T* __restrict__ p, T* __restrict_
         };
         V up = prow(r0 - 1);
         V cur = prow(r0);
+        // OP 2: the edge values of the rows above and at y from the adjacent lanes, two moves per new row: those of
+        // row y + 1 are taken when it is formed and handed up as the march goes down
+        T ul = (T)0, ur = (T)0, cl = (T)0, cr = (T)0;
+        if constexpr (OP == 2) {
+            ul = from_left(last(up)); ur = from_right(first(up));
+            cl = from_left(last(cur)); cr = from_right(first(cur));
+        }
         for (int y = r0; y < r1; ++y) {
             const V dn = prow(y + 1);
             const long at = c.col + (long)y * pitch;
             V o;
             if constexpr (OP == 0) {
                 o = poisson_vec(up, cur, dn);
-            } else {
+            } else if constexpr (OP == 1) {
                 Lanes<T> k[9];
                 load_coefs<5, 0>(a, at, c.ld, k);
                 Rows3<T> u{to_lanes(up), to_lanes(cur), to_lanes(dn)};
                 u.cl = from_left(last(cur)); u.cr = from_right(first(cur));
                 o = from_lanes(stencil_sum<5>(u, k, [&](int x) { return k[0].a[x]; }));
+            } else {
+                Lanes<T> k[9];
+                load_coefs<9, 0>(a, at, c.ld, k);
+                const T dl = from_left(last(dn)), dr = from_right(first(dn));
+                const Rows3<T> u{to_lanes(up), to_lanes(cur), to_lanes(dn), ul, ur, cl, cr, dl, dr};
+                o = from_lanes(stencil_sum<9>(u, k, [&](int x) { return k[0].a[x]; }));
+                ul = cl; ur = cr; cl = dl; cr = dr;
             }
             mask_cols(o, c.col, N);
             vstore<V>(pn + at, cur, c.st);

@@ -57,7 +57,10 @@ inline void krylov_reduce(mgx_solver* s, int n, int mode)
 template <typename T>
 void krylov_direction(mgx_solver* s, const Level& l, const Launch& g, const T* z, const T* p, T* pn, T* q, bool first)
 {
-    if (s->var)
+    if (s->var && l.nine)
+        hipLaunchKernelGGL((k_pcg_direction<T, 2>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, p, pn, q, s->kry.sc, first ? 1 : 0, s->kry.part,
+                           op9_of<T>(l), l.N, l.pitch, g.R, g.strips, g.chunks);
+    else if (s->var)
         hipLaunchKernelGGL((k_pcg_direction<T, 1>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, p, pn, q, s->kry.sc, first ? 1 : 0, s->kry.part,
                            op9_of<T>(l), l.N, l.pitch, g.R, g.strips, g.chunks);
     else

@@ -12,8 +12,9 @@
 //
 // AN OPERATOR (A, or the off-diagonals of R_omega) is nine coefficient grids in the level's layout, in the SLOT ORDER
 //     c, n, s, w, e, nw, ne, sw, se   (slots 0..8; op9_slot(dy, dx));
-// a five-point operator (NQ = 5: the caller's STENCIL5 levels, the finest GALERKIN level) leaves slots 5..8 null and no
-// NQ = 5 code reads them; R A P of a five-point operator is nine-point (NQ = 9: the coarse GALERKIN levels).
+// a five-point operator (NQ = 5: the caller's STENCIL5 levels, a five-point finest GALERKIN level) leaves slots 5..8 null
+// or stale and no NQ = 5 code reads them; R A P is nine-point (NQ = 9: the coarse GALERKIN levels, and the finest one
+// after mgx_set_stencil9 / mgx_set_tensor).
 // (A u)_ij = sum over (dy, dx) of a_(dy,dx) u_(i+dy)(j+dx); the Dirichlet ring of the grid layout is zero, so
 // boundary-adjacent points need no special case.  A CSR row of a row-major operator lists its columns in the CSR ORDER
 //     NW, N, NE, W, C, E, SW, S, SE   (five-point: N, W, C, E, S - the same order with the corners left out),
@@ -252,6 +253,31 @@ __global__ void k_var_from_nodes(const double* __restrict__ a, int Nf, int q, Op
     const long at = (long)r * pitch + c;
     o.a[0][at] = (T)(((fn + fw) + fe) + fs);
     o.a[1][at] = (T)(-fn); o.a[2][at] = (T)(-fs); o.a[3][at] = (T)(-fw); o.a[4][at] = (T)(-fe);
+}
+
+// -d_x(axx d_x u) - d_y(ayy d_y u) - d_x(axy d_y u) - d_y(axy d_x u) on the finest level from the three nodal
+// coefficients of its own grid (rows 0..N of N + 1 doubles each; x along a row, y grows with the row index): the
+// five-point part is k_var_from_nodes' with ayy on the n / s faces and axx on the w / e faces; the mixed term is the
+// central difference of central differences, a corner coefficient = a quarter of the sum of axy at the two edge
+// neighbours it lies between, negative towards nw and se (tests/nine_ref.py: tensor9).  The four corners of a point sum
+// to zero; e(i,j) = w(i,j+1), se(i,j) = nw(i+1,j+1), ne(i,j) = sw(i-1,j+1) bit for bit.  All in double, one rounding to T
+template <typename T>
+__global__ void k_var_from_tensor(const double* __restrict__ axx, const double* __restrict__ axy, const double* __restrict__ ayy,
+                                  Op9Out<T> o, int N, long pitch)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = blockIdx.y;
+    if (c < 1 || c >= N || r < 1 || r >= N) return;
+    const long ld = (long)N + 1;
+    const long nd = (long)r * ld + c;
+    const double fn = 0.5 * (ayy[nd] + ayy[nd - ld]), fs = 0.5 * (ayy[nd] + ayy[nd + ld]);
+    const double fw = 0.5 * (axx[nd] + axx[nd - 1]), fe = 0.5 * (axx[nd] + axx[nd + 1]);
+    const double aN = axy[nd - ld], aS = axy[nd + ld], aW = axy[nd - 1], aE = axy[nd + 1];
+    const long at = (long)r * pitch + c;
+    o.a[0][at] = (T)(((fn + fw) + fe) + fs);
+    o.a[1][at] = (T)(-fn); o.a[2][at] = (T)(-fs); o.a[3][at] = (T)(-fw); o.a[4][at] = (T)(-fe);
+    o.a[5][at] = (T)(-(0.25 * (aW + aN))); o.a[6][at] = (T)(0.25 * (aE + aN));
+    o.a[7][at] = (T)(0.25 * (aW + aS)); o.a[8][at] = (T)(-(0.25 * (aE + aS)));
 }
 
 // ---- direct bottom solve of a general coarsest operator (MF:63-72, 137-139) ---------------------------------
