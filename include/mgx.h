@@ -67,7 +67,29 @@ enum { MGX_SMOOTHER_JACOBI = 0, MGX_SMOOTHER_RBGS = 1,
         * mgx_slab_cycle they are MGX_ERR_INVALID.  Two more arrays per level and direction; 11 / 15 sizeof(T) per point
         * and sweep direction on five- / nine-point levels (15 / 19 for y-lines on levels cut into chunks).
         * (The value 3 stays an invalid smoother: mgx_create has always refused it and the suite pins that.) */
-       MGX_SMOOTHER_LINE_X = 4, MGX_SMOOTHER_LINE_Y = 5, MGX_SMOOTHER_LINE_ALT = 6 };
+       MGX_SMOOTHER_LINE_X = 4, MGX_SMOOTHER_LINE_Y = 5, MGX_SMOOTHER_LINE_ALT = 6,
+       /* COLOR_GS / COLOR_SGS: multicolour point Gauss-Seidel (csrc/mgx_colour.hpp states the sweep).  A sweep updates the
+        * colours of a level one after the other, every point x_ij = (b_ij - S_ij) * D_inv_ij from the current state of
+        * its neighbours: S the sum of the off-diagonal terms a_k u_k of A in CSR order (NW, N, NE, W, E, SW, S, SE;
+        * five-point levels N, W, E, S), the first term starting the accumulator, every product and sum rounded on its
+        * own; D_inv the level's stored 1 / c (mgx_get_stencil which 5, mgx_get_stencil9 which 9).  Five-point levels have
+        * two colours: (grid row + grid column) even first, then odd.  Nine-point levels have four, by (row parity, column
+        * parity): (odd, odd), (odd, even), (even, odd), (even, even) - the coarse points last.  Coefficients that point
+        * at the Dirichlet ring multiply the ring of the iterate, which is zero.  A reverse sweep takes the colours in the
+        * opposite order.  COLOR_GS: every block sweeps forward.  COLOR_SGS: the blocks before a restriction, mgx_smooth,
+        * mgx_time_smoother and the first mu1 sweeps of a bottom = SMOOTH visit sweep forward, the blocks after a
+        * correction and the last mu2 sweeps of a bottom = SMOOTH visit in reverse (in W- and F-cycles each block by its
+        * position: before the descent or after the ascent) - with mu1 = mu2 that cycle is a symmetric preconditioner
+        * for mgx_solve_pcg, which the forward-only one is not.  mu1 / mu2 (the mu of mgx_smooth) count sweeps; omega
+        * is validated but not used; mgx_stats.fine_updates counts one update per point and sweep.  A five-point level of
+        * N >= 16 sweeps both colours in one launch, out of place like a Jacobi pass (8 sizeof(T) per point; with
+        * MGX_GS_FUSED=0 in the environment at mgx_create: one launch per colour, in place, as on nine-point and smaller
+        * levels) - the same bits either way.  Nothing is allocated beyond what a Jacobi handle has.  Handles with op =
+        * MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN only, dtype F64 or F32, arith SEPARATE, one GPU; with op =
+        * MGX_OPERATOR_POISSON (which has RBGS), in mgx_create_rank, mgx_plan_create and mgx_slab_cycle they are
+        * MGX_ERR_INVALID.  (The value 1, RBGS, stays refused on general-operator handles.  The value 7 stays an invalid smoother, like 3:
+        * mgx_create has always refused it and the suite pins that.) */
+       MGX_SMOOTHER_COLOR_GS = 8, MGX_SMOOTHER_COLOR_SGS = 9 };
 enum { MGX_DTYPE_F32 = 0, MGX_DTYPE_F64 = 1, MGX_DTYPE_MIXED = 2 };
 enum { MGX_SCHEDULE_V = 0, MGX_SCHEDULE_FMG = 1 };
 enum { MGX_RESTRICT_CONSISTENT = 0, MGX_RESTRICT_FW16 = 1,
@@ -78,7 +100,7 @@ enum { MGX_RESTRICT_CONSISTENT = 0, MGX_RESTRICT_FW16 = 1,
  * general five-point operator PER LEVEL (A_sp_dict[level]) given by the caller as five coefficient grids
  * (mgx_set_stencil) or re-discretised from a nodal coefficient a(x, y) of -div(a grad u) (mgx_set_coefficient),
  * smoothed in MF's form  v <- R_omega v + omega D^-1 b  (MF:86-93), residual b - A v (MF:150-153), direct solve of
- * the coarsest operator (MF:63-72: dense inverse; coarsest_level <= 5).  dtype F64 / F32, Jacobi, Chebyshev or a line smoother, one GPU.
+ * the coarsest operator (MF:63-72: dense inverse; coarsest_level <= 5).  dtype F64 / F32, Jacobi, Chebyshev, a line smoother or multicolour Gauss-Seidel, one GPU.
  * Algorithmic bytes per point and sweep: 8 sizeof(T) (v, b, D_inv, four R arrays in; v' out). */
 enum { MGX_OPERATOR_POISSON = 0, MGX_OPERATOR_STENCIL5 = 1,
        /* GALERKIN: the variational hierarchy.  The finest level is a general five-point operator given as for STENCIL5,
@@ -374,6 +396,8 @@ MGX_API int mgx_vcycle_zero(mgx_handle h);
  * the Jacobi smoother is one launch of one workgroup (csrc/mgx_small.hpp: the iterate in LDS, the coefficients in registers),
  * bit-identical to the per-level launches it replaces; every other level, smoother and operator runs W and F through
  * the per-level launches, and so does everything when the environment holds MGX_SMALL_VISIT=0 at mgx_create.
+ * (The one-workgroup visit is Jacobi only: MGX_SMOOTHER_COLOR_GS / COLOR_SGS smooth those levels through their per-level
+ * launches like the Chebyshev and line smoothers.)
  * Handles with op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN (single GPU, dtype F64 or F32, either smoother);
  * MGX_ERR_STATE on POISSON, MIXED and multi-GPU / rank handles, which run V-cycles only; MGX_ERR_INVALID for a NULL
  * handle or another value.  mgx_get_cycle(NULL, ..) returns MGX_ERR_INVALID and leaves *cycle alone. */

@@ -24,6 +24,8 @@ SMOOTHER_JACOBI, SMOOTHER_RBGS = 0, 1
 SMOOTHER_CHEBYSHEV = 2      # Chebyshev polynomial smoother of the general-operator hierarchies (mu1 / mu2: degrees)
 # zebra line Gauss-Seidel of the general-operator hierarchies: x-lines, y-lines, x then y (3 is not a smoother)
 SMOOTHER_LINE_X, SMOOTHER_LINE_Y, SMOOTHER_LINE_ALT = 4, 5, 6
+# multicolour point Gauss-Seidel of the general-operator hierarchies: every block forward / post-smoothing blocks in reverse
+SMOOTHER_COLOR_GS, SMOOTHER_COLOR_SGS = 8, 9          # (7, like 3, is not a smoother)
 DTYPE_F32, DTYPE_F64, DTYPE_MIXED = 0, 1, 2
 GCR_MAX_RESTART = 8                       # MGX_GCR_MAX_RESTART
 SCHEDULE_V, SCHEDULE_FMG = 0, 1

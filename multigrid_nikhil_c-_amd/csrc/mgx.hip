@@ -21,6 +21,7 @@
 #include "mgx_opdep.hpp"
 #include "mgx_cheby.hpp"
 #include "mgx_line.hpp"
+#include "mgx_colour.hpp"
 #include "mgx_small.hpp"
 #include "mgx_krylov.hpp"
 #include "mgx_dist_plan.hpp"
@@ -132,6 +133,8 @@ struct mgx_solver {
     int small_visit = 1;            // W / F: one-workgroup visits of the small nine-point levels (MGX_SMALL_VISIT, mgx_small.hpp)
     int small_max_n = kSmallMaxN;   // ... of the levels with N <= this
     int line_dirs = 0;              // MGX_SMOOTHER_LINE_*: bit 0 x-lines, bit 1 y-lines (0: another smoother)
+    int colour = 0;                 // MGX_SMOOTHER_COLOR_GS: 1, COLOR_SGS: 2 (post-smoothing blocks in reverse colour order); 0: another smoother
+    int gs_fused = 1;               // ... five-point levels sweep both colours in one launch of k_gs_rb (MGX_GS_FUSED, mgx_colour.hpp)
     int* line_flag = nullptr;       // device: bit d raised by k_line_factor on a zero or non-finite pivot in direction d
     int transfer = MGX_TRANSFER_BILINEAR;   // ... with this prolongation (mgx_build_galerkin_transfer)
     // mgx_solve_pcg and mgx_solve_gcr (mgx_krylov_host.hpp): one workspace, every piece allocated by the first call
@@ -612,10 +615,35 @@ void smooth_line_t(mgx_solver* s, Level& l, int mu)
     s->last_smooth_launches = launches;
 }
 
-// the level smoother of a general-operator handle
-void smooth_var(mgx_solver* s, Level& l, int mu)
+// mu multicolour Gauss-Seidel sweeps (mgx_colour.hpp), the colours in reverse order if `reverse`.  A five-point level
+// with a chunk's worth of rows: one launch per sweep, u <-> tmp; otherwise one launch per colour, u in place
+template <typename T>
+void smooth_colour_t(mgx_solver* s, Level& l, int mu, bool reverse)
 {
-    if (s->line_dirs) { if (l.f64) smooth_line_t<double>(s, l, mu); else smooth_line_t<float>(s, l, mu); }
+    const ColourLevel<T> cl{op9_of<T>(l), (const T*)l.J[0], l.nine, l.N, l.pitch};
+    const bool fused = s->gs_fused && !l.nine && gs_fused_level(l.N);
+    int launches = 0;
+    for (int i = 0; i < mu; ++i) {
+        if (fused) {
+            launch_gs_rb<T>(cl, (const T*)l.u, (const T*)l.b, (T*)l.tmp, reverse, s->stream);
+            std::swap(l.u, l.tmp);
+            ++launches;
+        } else {
+            launches += launch_gs_colours<T>(cl, (T*)l.u, (const T*)l.b, reverse, s->stream);
+        }
+    }
+    s->last_smooth_launches = launches;
+}
+
+// the level smoother of a general-operator handle; post: the block follows a correction (MGX_SMOOTHER_COLOR_SGS sweeps
+// it in reverse colour order; nothing else looks at it)
+void smooth_var(mgx_solver* s, Level& l, int mu, bool post = false)
+{
+    if (s->colour) {
+        const bool reverse = s->colour == 2 && post;
+        if (l.f64) smooth_colour_t<double>(s, l, mu, reverse); else smooth_colour_t<float>(s, l, mu, reverse);
+    }
+    else if (s->line_dirs) { if (l.f64) smooth_line_t<double>(s, l, mu); else smooth_line_t<float>(s, l, mu); }
     else if (s->cfg.smoother == MGX_SMOOTHER_CHEBYSHEV) { if (l.f64) smooth_cheby_t<double>(s, l, mu); else smooth_cheby_t<float>(s, l, mu); }
     else if (l.f64) smooth_var_t<double>(s, l, mu);       // MF:75-96
     else smooth_var_t<float>(s, l, mu);
@@ -797,13 +825,13 @@ void smooth_t(mgx_solver* s, Level& l, int mu)
     if (launches & 1) std::swap(l.u, l.tmp);
 }
 
-void smooth(mgx_solver* s, int level, int mu)
+void smooth(mgx_solver* s, int level, int mu, bool post = false)
 {
     if (mu <= 0) return;
     Level& l = s->lv[level];
     const bool fine = (level == s->cfg.finest_level);
     Prof p(s, fine ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, mu);
-    if (s->var) smooth_var(s, l, mu);
+    if (s->var) smooth_var(s, l, mu, post);
     else smooth_t(s, l, mu);
     p.set(s->last_smooth_launches, mu);
     // one update per point and sweep; an alternating line sweep is an x- and a y-sweep
@@ -913,7 +941,7 @@ void ascend(mgx_solver* s, int level, int post)
 {
     if (!smooth_folded(s, level, s->cfg.mu2, true, post)) {
         prolong_level(s, level, true);                        // PS:620-624
-        smooth(s, level, s->cfg.mu2);                         // PS:625
+        smooth(s, level, s->cfg.mu2, true);                   // PS:625
     }
 }
 
@@ -991,7 +1019,7 @@ void vcycle(mgx_solver* s, int level, bool zero_in_here, int post_top, int kind)
             bottom_solve(s);                                  // MF:137-139
         } else {
             smooth(s, level, s->cfg.mu1);                     // PS:581
-            smooth(s, level, s->cfg.mu2);                     // PS:585
+            smooth(s, level, s->cfg.mu2, true);               // PS:585
         }
         return;
     }
@@ -1343,7 +1371,7 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     // in both precisions; level 8 (255^2) bounds the dense sine-transform solve.
     if (cfg->coarsest_level < 2 || cfg->finest_level < cfg->coarsest_level || cfg->finest_level > 15 ||
         cfg->mu0 < 0 || cfg->mu1 < 0 || cfg->mu2 < 0 || !(cfg->omega > 0.0 && cfg->omega < 2.0) ||
-        cfg->smoother < 0 || cfg->smoother > MGX_SMOOTHER_LINE_ALT || cfg->smoother == 3 || cfg->dtype < 0 || cfg->dtype > 2 ||
+        cfg->smoother < 0 || cfg->smoother > MGX_SMOOTHER_COLOR_SGS || cfg->smoother == 3 || cfg->smoother == 7 || cfg->dtype < 0 || cfg->dtype > 2 ||
         cfg->schedule < 0 || cfg->schedule > 1 || cfg->restrict_mode < 0 || cfg->restrict_mode > MGX_RESTRICT_INJECT4 ||
         cfg->bottom < 0 || cfg->bottom > 1 || cfg->arith < 0 || cfg->arith > 1 || (cfg->op != MGX_OPERATOR_POISSON && cfg->op != MGX_OPERATOR_STENCIL5 && cfg->op != MGX_OPERATOR_GALERKIN)) {
         g_create_error = "invalid configuration";
@@ -1361,7 +1389,12 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
         g_create_error = "MGX_SMOOTHER_CHEBYSHEV: op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN only (the constant stencil has its fused and folded passes)";
         return MGX_ERR_INVALID;
     }
-    const bool line = (cfg->smoother >= MGX_SMOOTHER_LINE_X);
+    const bool line = (cfg->smoother >= MGX_SMOOTHER_LINE_X && cfg->smoother <= MGX_SMOOTHER_LINE_ALT);
+    const bool colour = (cfg->smoother == MGX_SMOOTHER_COLOR_GS || cfg->smoother == MGX_SMOOTHER_COLOR_SGS);
+    if (colour && (!var || cfg->dtype == MGX_DTYPE_MIXED || cfg->arith != MGX_ARITH_SEPARATE || cfg->n_gpus > 1)) {
+        g_create_error = "MGX_SMOOTHER_COLOR_GS / COLOR_SGS: op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN, dtype F64 or F32, arith SEPARATE, one GPU";
+        return MGX_ERR_INVALID;
+    }
     if (line && (!var || cfg->dtype == MGX_DTYPE_MIXED || cfg->arith != MGX_ARITH_SEPARATE || cfg->n_gpus > 1)) {
         g_create_error = "MGX_SMOOTHER_LINE_X / LINE_Y / LINE_ALT: op = MGX_OPERATOR_STENCIL5 or MGX_OPERATOR_GALERKIN, dtype F64 or F32, arith SEPARATE, one GPU";
         return MGX_ERR_INVALID;
@@ -1403,6 +1436,8 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     s->use_zero_in = env_int("MGX_ZERO_IN", 1);
     s->use_graph = env_int("MGX_GRAPH", 1);
     s->small_visit = env_int("MGX_SMALL_VISIT", 1);
+    s->colour = cfg->smoother == MGX_SMOOTHER_COLOR_GS ? 1 : cfg->smoother == MGX_SMOOTHER_COLOR_SGS ? 2 : 0;
+    s->gs_fused = env_int("MGX_GS_FUSED", 1);
     s->line_dirs = cfg->smoother == MGX_SMOOTHER_LINE_X ? 1 : cfg->smoother == MGX_SMOOTHER_LINE_Y ? 2 : cfg->smoother == MGX_SMOOTHER_LINE_ALT ? 3 : 0;
     int rc = MGX_OK;
     auto bail = [&](int code) { g_create_error = s->err; mgx_destroy(s); return code; };
@@ -2400,6 +2435,10 @@ int mgx_create_rank(const mgx_config* cfg, int rank, int world, const void* rccl
         g_create_error = "MGX_SMOOTHER_CHEBYSHEV: single-GPU handles of op = MGX_OPERATOR_STENCIL5 / MGX_OPERATOR_GALERKIN only";
         return MGX_ERR_INVALID;
     }
+    if (cfg->smoother == MGX_SMOOTHER_COLOR_GS || cfg->smoother == MGX_SMOOTHER_COLOR_SGS) {
+        g_create_error = "MGX_SMOOTHER_COLOR_GS / COLOR_SGS: single-GPU handles of op = MGX_OPERATOR_STENCIL5 / MGX_OPERATOR_GALERKIN only";
+        return MGX_ERR_INVALID;
+    }
     if (cfg->smoother >= MGX_SMOOTHER_LINE_X && cfg->smoother <= MGX_SMOOTHER_LINE_ALT) {
         g_create_error = "MGX_SMOOTHER_LINE_X / LINE_Y / LINE_ALT: single-GPU handles of op = MGX_OPERATOR_STENCIL5 / MGX_OPERATOR_GALERKIN only";
         return MGX_ERR_INVALID;
@@ -2516,6 +2555,10 @@ int mgx_plan_create(const mgx_config* cfg, int n_slabs, int g, int fold, int dee
     *out = nullptr;
     if (cfg->smoother == MGX_SMOOTHER_CHEBYSHEV) {
         g_plan_error = "MGX_SMOOTHER_CHEBYSHEV: the slab plan runs the constant stencil (Jacobi or red-black GS) only";
+        return MGX_ERR_INVALID;
+    }
+    if (cfg->smoother == MGX_SMOOTHER_COLOR_GS || cfg->smoother == MGX_SMOOTHER_COLOR_SGS) {
+        g_plan_error = "MGX_SMOOTHER_COLOR_GS / COLOR_SGS: the slab plan runs the constant stencil (Jacobi or red-black GS) only";
         return MGX_ERR_INVALID;
     }
     if (cfg->smoother >= MGX_SMOOTHER_LINE_X && cfg->smoother <= MGX_SMOOTHER_LINE_ALT) {

@@ -8,6 +8,7 @@
 //   -DMGX_INST_KIND=5  launch_small_visit<T>, small_visit_prepare<T>  (mgx_small.hpp: k_small_visit)
 //   -DMGX_INST_KIND=6  launch_line_factor<T>, launch_line_sweep<T>  (mgx_line.hpp: k_line_factor, k_line_x, k_line_y)
 //   -DMGX_INST_KIND=7  launch_gcr_orth<T>  (mgx_krylov.hpp: k_gcr_dots<T, 1..7>, k_gcr_orth<T, 0..7>, k_gcr_reduce)
+//   -DMGX_INST_KIND=8  launch_gs_colours<T>, launch_gs_rb<T>  (mgx_colour.hpp: k_gs_colour<T, 5 | 9>, k_gs_rb)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
@@ -18,6 +19,8 @@
 #include "mgx_line.hpp"
 #elif MGX_INST_KIND == 7
 #include "mgx_krylov.hpp"
+#elif MGX_INST_KIND == 8
+#include "mgx_colour.hpp"
 #endif
 
 namespace mgx {
@@ -50,7 +53,10 @@ template void launch_line_factor<T_>(const LineLevel<T_>&, int, int*, hipStream_
 template int launch_line_sweep<T_>(const LineLevel<T_>&, T_*, const T_*, int, hipStream_t);
 #elif MGX_INST_KIND == 7
 template void launch_gcr_orth<T_>(int, T_*, T_*, const T_*, const GcrBasis<T_>&, double*, double*, int, long, const Launch&, int, hipStream_t);
+#elif MGX_INST_KIND == 8
+template int launch_gs_colours<T_>(const ColourLevel<T_>&, T_*, const T_*, bool, hipStream_t);
+template void launch_gs_rb<T_>(const ColourLevel<T_>&, const T_*, const T_*, T_*, bool, hipStream_t);
 #else
-#error "MGX_INST_KIND must be 1 .. 7"
+#error "MGX_INST_KIND must be 1 .. 8"
 #endif
 } // namespace mgx

@@ -32,7 +32,16 @@ half the level); k_line_y both with the launcher's chunks and with MGX_LINE_CHUN
 --aniso EPS[,layers] (default 1e-2: the x-strong problem c = 2(1 + EPS), w = e = -1, n = s = -EPS; ",layers": x-strong in
 the upper half, y-strong in the lower half), cycles and median-of-5 time to 1e-8 at 2047^2, levels 11..5, right-hand side
 default_rng(3).uniform(-1, 1): the line smoother's V(1,1) against Jacobi V(2,2), mgx_solve and mgx_solve_pcg each.
---smoother line_x --trace-only: five sweeps per level and type only, for a rocprofv3 --kernel-trace --stats run."""
+--smoother line_x --trace-only: five sweeps per level and type only, for a rocprofv3 --kernel-trace --stats run.
+--smoother {color_gs,color_sgs}: instead, the tables of profiles/colour_gs_kernel_trace_summary.md.  The multicolour
+Gauss-Seidel kernels (csrc/mgx_colour.hpp) at 4096^2 next to k_jacobi_var<T, 5 | 9> in the same process, ms per SWEEP:
+k_gs_colour<T, 5> (two launches; a handle created under MGX_GS_FUSED=0), k_gs_rb<T> (one launch) and k_gs_colour<T, 9>
+(four launches), with the bytes/s over the algorithmic bytes of mgx_colour.hpp (16 / 8 / 24 sizeof(T) per point and
+sweep).  Then cycles and median-of-5 time to 1e-8 at 2047^2, levels 11..5, right-hand side default_rng(3).uniform(-1, 1),
+of mgx_solve with the smoother's V(1,1) and V(2,2) against Jacobi V(2,2) and Chebyshev V(2,2), on Poisson, contrast 10
+with the operator-dependent P, and the rotated anisotropy (45 degrees, eps = 0.5; nine-point finest level).
+--smoother color_gs --trace-only: five sweeps per level, type and kernel form only, for a rocprofv3 --kernel-trace
+--stats run."""
 import os
 import statistics
 import sys
@@ -341,6 +350,84 @@ def aniso_solves(which, eps, layers):
             print(f"| {label} | {cells[0]} | {cells[1]} |", flush=True)
 
 
+COLOUR = {"color_gs": pkg.SMOOTHER_COLOR_GS, "color_sgs": pkg.SMOOTHER_COLOR_SGS}
+
+
+def colour_kernels(which):
+    n = (1 << LK) - 1
+    x = np.linspace(0.0, 1.0, (1 << LF) + 1)
+    a = 1.0 + 0.8 * np.sin(3 * np.pi * x)[None, :] * np.cos(2 * np.pi * x)[:, None]
+    rng = np.random.default_rng(0)
+    u, b = rng.uniform(-1, 1, (n, n)), rng.uniform(-1, 1, (n, n))
+    if not TRACE_ONLY:
+        print("| kernel | grid | dtype | launches per sweep | ms per sweep | bytes per point and sweep | achieved GB/s | fraction of the 8 TB/s HBM peak | sweep time / Jacobi sweep time |")
+        print("|---|---|---|---|---|---|---|---|---|")
+    sweeps = 20
+    for dtype, name, es in ((pkg.DTYPE_F64, "f64", 8), (pkg.DTYPE_F32, "f32", 4)):
+        for op, tag, finest in ((pkg.OPERATOR_STENCIL5, "var", LK), (pkg.OP_GALERKIN, "var9", LF)):
+            nq = 9 if tag == "var9" else 5
+            runs = [(kname("k_jacobi_", tag, name), pkg.SMOOTHER_JACOBI, None, 1, nq + 3)]
+            if nq == 5:
+                runs += [(f"k_gs_colour<{name}, 5>", COLOUR[which], "0", 2, 16), (f"k_gs_rb<{name}>", COLOUR[which], None, 1, 8)]
+            else:
+                runs += [(f"k_gs_colour<{name}, 9>", COLOUR[which], None, 4, 24)]
+            jacobi_ms = None
+            for label, sm, fused, launches, words in runs:
+                if fused is None:
+                    os.environ.pop("MGX_GS_FUSED", None)
+                else:
+                    os.environ["MGX_GS_FUSED"] = fused          # read at mgx_create
+                with pkg.Multigrid(finest_level=finest, coarsest_level=5, mu1=2, mu2=2, schedule=pkg.SCHEDULE_V, op=op, dtype=dtype, omega=0.8,
+                                   smoother=sm) as mg:
+                    os.environ.pop("MGX_GS_FUSED", None)
+                    if op == pkg.OP_GALERKIN:
+                        mg.set_coefficient(a)
+                        mg.build_galerkin()
+                    else:
+                        mg.set_coefficient(a[::2, ::2])
+                    mg.set_level(LK, pkg.VEC_U, u)
+                    mg.set_level(LK, pkg.VEC_B, b)
+                    mg.smooth(LK, 2)
+                    if TRACE_ONLY:
+                        mg.smooth(LK, 5)
+                        continue
+                    ms = wall(lambda: mg.smooth(LK, sweeps), reps=5) / sweeps
+                    if jacobi_ms is None:
+                        jacobi_ms = ms
+                    gbs = words * es * n * n / (ms * 1e-3) / 1e9
+                    print(f"| {label} | {1 << LK}^2 | {name} | {launches} | {ms:.4f} | {words * es} | {gbs:.0f} | {gbs / 8000:.3f} | {ms / jacobi_ms:.3f} |", flush=True)
+
+
+def colour_solves(which):
+    import nine_ref
+    L = 9 if QUICK else 11
+    n = (1 << L) - 1
+    b = np.random.default_rng(3).uniform(-1, 1, (n, n))
+    one = np.ones((n, n))
+    problems = (("Poisson", "BILINEAR", lambda mg: mg.set_stencil(L, 4 * one, -one, -one, -one, -one), None),
+                ("contrast 10", "OPERATOR", lambda mg: mg.set_coefficient(contrast_coefficient(L, 10.0)), pkg.TRANSFER_OPERATOR),
+                ("rotated anisotropy 45 degrees, eps = 0.5", "BILINEAR", lambda mg: mg.set_tensor(*nine_ref.rotated_tensor(L, 45.0, 0.5)), None))
+    cycles = ((f"{which} V(1,1)", COLOUR[which], 1), (f"{which} V(2,2)", COLOUR[which], 2), ("Jacobi V(2,2), omega = 2/3", pkg.SMOOTHER_JACOBI, 2),
+              ("Chebyshev V(2,2)", pkg.SMOOTHER_CHEBYSHEV, 2))
+    print(f"\n| {n}^2, levels {L}..5, f64, mgx_solve to 1e-8 (cap 100 cycles) | transfer | " + " | ".join(c[0] for c in cycles) + " |")
+    print("|---|---|" + "---|" * len(cycles))
+    for pname, tname, setter, transfer in problems:
+        cells = []
+        for label, sm, mu in cycles:
+            with pkg.Multigrid(finest_level=L, coarsest_level=5, mu1=mu, mu2=mu, schedule=0, op=pkg.OP_GALERKIN, smoother=sm) as mg:
+                setter(mg)
+                mg.build_galerkin(transfer)
+                mg.set_rhs(b)
+                ts = []
+                for rep in range(6):                    # the first run captures the graphs: not timed
+                    mg.set_guess(np.zeros((n, n)))
+                    st, hist = mg.solve(tol=1e-8, max_cycles=100)
+                    if rep:
+                        ts.append(st.seconds * 1e3)
+                cells.append(f"{st.cycles} cycles, {statistics.median(ts):.2f} ms (min {min(ts):.2f}, max {max(ts):.2f}), converged {st.converged}")
+        print(f"| {pname} | {tname} | " + " | ".join(cells) + " |", flush=True)
+
+
 CYCLES = {"v": pkg.CYCLE_V, "w": pkg.CYCLE_W, "f": pkg.CYCLE_F}
 
 
@@ -407,8 +494,13 @@ if __name__ == "__main__":
                 if not TRACE_ONLY:
                     aniso_solves(which, 1e-2, which == "line_alt")
             sys.exit(0)
+        if which in COLOUR:
+            colour_kernels(which)
+            if not TRACE_ONLY:
+                colour_solves(which)
+            sys.exit(0)
         if which not in ("jacobi", "chebyshev"):
-            sys.exit("--smoother jacobi, chebyshev, line_x, line_y or line_alt")
+            sys.exit("--smoother jacobi, chebyshev, line_x, line_y, line_alt, color_gs or color_sgs")
         if which == "chebyshev":
             smoother_kernels()
         if not TRACE_ONLY:
