@@ -19,19 +19,33 @@ The cycle index (mgx_set_cycle) is an attribute the composed vcycle() reads: the
 same single operators, held to tests/wcycle_ref.py bit for bit.  The zebra line smoothers (cfg.smoother 4 / 5 / 6) run
 through tests/line_ref.py; the device joins a line's carries in another order, so calls that smooth are compared to a
 bound there (tests/test_gpu_handle_state.py), for which the model can be instantiated a second time in np.longdouble
-(real=np.longdouble: line_ref.NumpyOps in place of the oracle, the operators cast from the working type)."""
+(real=np.longdouble: line_ref.NumpyOps in place of the oracle, the operators cast from the working type).
+
+The multicolour Gauss-Seidel smoothers (cfg.smoother 8 / 9) run through tests/colour_ref.py, bit for bit.  They are the one
+smoother whose result depends on the block's position: smooth(level, mu, post) hands `post` to the hierarchy, and the
+composed vcycle() sets it where the device does - the block after a correction and the last mu2 sweeps of a
+bottom = SMOOTH visit; mgx_smooth itself is always forward.
+
+A GALERKIN handle takes a nine-point finest operator (set_stencil9, set_tensor): the hierarchies of tests/nine_ref.py
+(Jacobi, Chebyshev) and colour_ref's Nine* classes; a later set_stencil or set_coefficient makes the level five-point
+again.  The line smoothers on a nine-point finest level are not modelled (their tolerance rule is measured for
+five-point finest operators only): set_stencil9 / set_tensor refuse there with a ValueError."""
 import numpy as np
 
 import cheby_ref
+import colour_ref as cf
 import galerkin_ref as gr
 import gcr_ref
 import line_ref as lr
+import nine_ref as nr
 import opdep_ref as od
 import pcg_ref
 
 JACOBI, RBGS, CHEBYSHEV = 0, 1, 2
 LINE_X, LINE_Y, LINE_ALT = lr.LINE_X, lr.LINE_Y, lr.LINE_ALT
 LINES = (LINE_X, LINE_Y, LINE_ALT)
+COLOR_GS, COLOR_SGS = cf.COLOR_GS, cf.COLOR_SGS   # 8, 9
+COLOURS = (COLOR_GS, COLOR_SGS)
 CYCLE_V, CYCLE_W, CYCLE_F = 0, 1, 2            # mgx_set_cycle
 F32, F64, MIXED = 0, 1, 2
 V, FMG = 0, 1
@@ -94,6 +108,10 @@ class Stencil5Cheby(_OracleBottom, cheby_ref.Stencil5Cheby):
     pass
 
 
+class Stencil5Colour(_OracleBottom, cf.Stencil5):
+    """H(smoother, po, stencils, finest, coarsest, ...)"""
+
+
 _INVERSES = {}         # dense inverse of a coarsest nine-point operator, by its bytes: rebuilds and configurations share it
 
 
@@ -114,6 +132,25 @@ def operator5(po, level, kind, dt):
     return op5(po, level, kind, dt)
 
 
+TENSORS = {"rot45": lambda level: nr.rotated_tensor(level, 45.0, 0.5), "smooth9": nr.smooth_tensor, "jump9": nr.jump_tensor}
+RANDOM9_SEED = 900                             # "random9": nr.random_stencil9(level, RANDOM9_SEED + level)
+OPERATORS9 = tuple(TENSORS) + ("random9",)
+
+
+def tensor_nodes(level, kind):
+    """nodal (axx, axy, ayy) of a tensor kind: what mgx_set_tensor is handed"""
+    return tuple(np.ascontiguousarray(np.broadcast_to(a, ((1 << level) + 1,) * 2), dtype=np.float64) for a in TENSORS[kind](level))
+
+
+def operator9(level, kind, dt):
+    """the nine-point finest operators by name, beside operator5: three symmetric ones, discretised from a nodal tensor
+    (rot45: the constant anisotropy 1 : 0.5 at 45 degrees; smooth9; jump9), and random9, which is unsymmetric and holds
+    values in the places that point at the Dirichlet ring"""
+    if kind == "random9":
+        return nr.random_stencil9(level, RANDOM9_SEED + level, dt)
+    return nr.tensor9(*tensor_nodes(level, kind), dtype=dt)
+
+
 class HandleModel:
     def __init__(self, po, real=None, **cfg):
         """real: the type the model computes in, when it is not the handle's own (np.longdouble: the 'exact' side of a
@@ -129,6 +166,9 @@ class HandleModel:
         self.wdt = np.float64 if c["dtype"] == F64 else np.float32       # the handle's working type
         self.dt = self.wdt if real is None else real
         self.line = c["smoother"] in LINES
+        self.colour = c["smoother"] in COLOURS
+        if self.colour and c["op"] == POISSON:
+            raise ValueError("colour smoothers: STENCIL5 and GALERKIN handles only")
         if self.dt is not self.wdt:
             if not self.line:
                 raise ValueError("real= is for the line smoothers: the other smoothers are the oracle's kernels")
@@ -142,7 +182,8 @@ class HandleModel:
         self.B = {lv: np.zeros((self.n(lv),) * 2, dtype=self.dt) for lv in self.levels()}
         self.R = {}
         self.fine_updates = 0.0
-        self.st5 = None                        # GALERKIN: the finest operator, waiting for build_galerkin
+        self.st5 = None                        # GALERKIN: the finest operator, waiting for build_galerkin: five arrays,
+        self.st9 = None                        # ... or nine (set_stencil9 / set_tensor); the later call decides
         self.stencils = None                   # STENCIL5: every level's operator
         self.transfer = None
         self.h = None
@@ -193,6 +234,8 @@ class HandleModel:
             self.h = lr.Stencil5(c["smoother"], self.po, self.stencils, self.L, self.Lc, **self._hier_args())
             if c["bottom"] == EXACT:
                 _shared_inverse(self.h)
+        elif self.colour:
+            self.h = Stencil5Colour(c["smoother"], self.po, self.stencils, self.L, self.Lc, **self._hier_args())
         else:
             cls = Stencil5Cheby if c["smoother"] == CHEBYSHEV else Stencil5
             self.h = cls(self.po, self.stencils, self.L, self.Lc, **self._hier_args())
@@ -205,7 +248,7 @@ class HandleModel:
             self.stencils = {lv: self._w(self.oracle.stencil_from_nodes(a, lv, self.L)) for lv in self.levels()}
             self._stencil5_hierarchy()
         elif self.op == GALERKIN:
-            self.st5 = self._w(self.oracle.stencil_from_nodes(a, self.L, self.L))
+            self.st5, self.st9 = self._w(self.oracle.stencil_from_nodes(a, self.L, self.L)), None
             self.h = None
             self.transfer = None
         else:
@@ -220,16 +263,44 @@ class HandleModel:
             if all(lv in self.stencils for lv in self.levels()):
                 self._stencil5_hierarchy()
         elif self.op == GALERKIN and level == self.L:
-            self.st5 = self._w(st5)
+            self.st5, self.st9 = self._w(st5), None
             self.h = None
             self.transfer = None
         else:
             raise RuntimeError("MGX_ERR_STATE")
 
+    def _nine_finest(self, level, st9):
+        if self.op != GALERKIN or level != self.L:
+            raise RuntimeError("nine-point operators: the finest level of a GALERKIN handle only: MGX_ERR_STATE")
+        if self.line:
+            raise ValueError("line smoothers on a nine-point finest level are out of scope: THE TOLERANCE RULE of "
+                             "tests/test_line_cpu.py is measured for five-point finest operators")
+        assert len(st9) == 9
+        self.st5, self.st9 = None, self._w(st9)
+        self.h = None
+        self.transfer = None
+
+    def set_stencil9(self, level, st9):
+        """mgx_set_stencil9: the finest level of a GALERKIN handle becomes nine-point; invalid until build_galerkin"""
+        self._nine_finest(level, st9)
+
+    def set_tensor(self, axx, axy, ayy):
+        """mgx_set_tensor: the nine-point discretisation of the nodal tensor (nine_ref.tensor9: double arithmetic, every
+        coefficient rounded to the working type once)"""
+        self._nine_finest(self.L, nr.tensor9(axx, axy, ayy, dtype=self.wdt))
+
     def set_operator(self, kind):
-        """a named operator of tests/test_line_cpu.py (operator5).  STENCIL5: set_stencil on every level.  GALERKIN:
-        set_stencil on the finest level, then build_galerkin with the transfer in use (BILINEAR at first)"""
-        if self.op == STENCIL5:
+        """a named operator of tests/test_line_cpu.py (operator5) or a nine-point one (operator9).  STENCIL5: set_stencil
+        on every level.  GALERKIN: set_stencil on the finest level - a tensor kind: set_tensor, random9: set_stencil9 -
+        then build_galerkin with the transfer in use (BILINEAR at first)"""
+        if kind in OPERATORS9:
+            transfer = BILINEAR if self.transfer is None else self.transfer
+            if kind in TENSORS:
+                self.set_tensor(*tensor_nodes(self.L, kind))
+            else:
+                self.set_stencil9(self.L, operator9(self.L, kind, self.wdt))
+            self.build_galerkin(transfer)
+        elif self.op == STENCIL5:
             for lv in self.levels():
                 self.set_stencil(lv, operator5(self.oracle, lv, kind, self.wdt))
         elif self.op == GALERKIN:
@@ -240,10 +311,22 @@ class HandleModel:
             raise RuntimeError("op = POISSON: MGX_ERR_STATE")
 
     def build_galerkin(self, transfer=BILINEAR):
-        if self.op != GALERKIN or self.st5 is None:
+        if self.op != GALERKIN or (self.st5 is None and self.st9 is None):
             raise RuntimeError("MGX_ERR_STATE")
         cheb = self.cfg["smoother"] == CHEBYSHEV
-        if self.line:
+        opdep = transfer == OPERATOR
+        if self.st9 is not None:                # a nine-point finest level: every level through the nine-point routines
+            if self.colour:
+                self.h = (cf.NineOpdepHierarchy if opdep else cf.NineHierarchy)(self.cfg["smoother"], self.po, self.st9, self.L, self.Lc, **self._hier_args())
+            else:
+                if opdep:
+                    cls = nr.ChebyOpdepHierarchy if cheb else nr.OpdepHierarchy
+                else:
+                    cls = nr.ChebyHierarchy if cheb else nr.Hierarchy
+                self.h = cls(self.po, self.st9, self.L, self.Lc, **self._hier_args())
+        elif self.colour:
+            self.h = (cf.OpdepHierarchy if opdep else cf.Hierarchy)(self.cfg["smoother"], self.po, self.st5, self.L, self.Lc, **self._hier_args())
+        elif self.line:
             cls = lr.OpdepHierarchy if transfer == OPERATOR else lr.Hierarchy
             self.h = cls(self.cfg["smoother"], self.po, self.st5, self.L, self.Lc, **self._hier_args())
         else:
@@ -278,9 +361,14 @@ class HandleModel:
         return self.po.prolong(e)
 
     # -- single operators --------------------------------------------------------------------------------------
-    def smooth(self, level, mu):
-        """mu Jacobi, red-black Gauss-Seidel or zebra line sweeps, or one Chebyshev block of degree mu"""
-        self.U[level] = self._ops().smooth(level, self.U[level], self.B[level], mu)
+    def smooth(self, level, mu, post=False):
+        """mu Jacobi, red-black Gauss-Seidel, zebra line or colour sweeps, or one Chebyshev block of degree mu.  post: the
+        block follows a correction, or is the second one of a bottom = SMOOTH visit (COLOR_SGS sweeps it in reverse colour
+        order; no other smoother looks at it).  mgx_smooth is post = False"""
+        if self.colour:
+            self.U[level] = self._ops().smooth(level, self.U[level], self.B[level], mu, post)
+        else:
+            self.U[level] = self._ops().smooth(level, self.U[level], self.B[level], mu)
         if level == self.L:
             per_sweep = 2 if self.cfg["smoother"] == LINE_ALT else 1       # an alternating sweep is an x- and a y-sweep
             self.fine_updates += float(per_sweep * mu) * float(self.n(level)) * float(self.n(level))
@@ -329,7 +417,7 @@ class HandleModel:
                 self.bottom_solve()
             else:
                 self.smooth(level, c["mu1"])
-                self.smooth(level, c["mu2"])
+                self.smooth(level, c["mu2"], post=True)
             return
         self.smooth(level, c["mu1"])
         self.restrict(level)
@@ -337,7 +425,7 @@ class HandleModel:
         if kind != CYCLE_V and level - 1 > self.Lc:
             self.vcycle(level - 1, CYCLE_V if kind == CYCLE_F else kind)
         self.prolong_add(level)
-        self.smooth(level, c["mu2"])
+        self.smooth(level, c["mu2"], post=True)
 
     def vcycle_zero(self):
         self.zero_level(self.L, 0)
@@ -377,6 +465,8 @@ class HandleModel:
         """A of the finest level as pcg_ref.Operator applies it"""
         if self.op == POISSON:
             return pcg_ref.Operator(None, self.dt)
+        if self.st9 is not None:
+            return nr.Operator9(self._ops().st[self.L], self.dt)
         return pcg_ref.Operator(self._ops().st[self.L][:5], self.dt)
 
     def solve_pcg(self, tol=1e-8, max_iters=100):

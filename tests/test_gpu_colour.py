@@ -123,7 +123,7 @@ def test_a_nine_point_finest_level_with_corners(pkg, po, dtype, L):
 
 
 # ---- 2. fused equals unfused, forward and reverse ----------------------------------------------------------------------
-def one_level_sweeps(pkg, po, L, dtype, monkeypatch, fused):
+def one_level_sweeps(pkg, po, L, dtype, monkeypatch, fused, kind="contrast", mus=(1, 2, 3)):
     """{(direction, mu): iterate} of mu = 1, 2, 3 sweeps on the five-point level L, and the launches of three forward
     sweeps.  Forward: mgx_smooth.  Reverse: a COLOR_SGS handle with finest = coarsest = L, bottom = SMOOTH, mu1 = 0: its
     'cycle' is mu2 post-smoothing sweeps"""
@@ -132,10 +132,10 @@ def one_level_sweeps(pkg, po, L, dtype, monkeypatch, fused):
         monkeypatch.delenv("MGX_GS_FUSED", raising=False)
     else:
         monkeypatch.setenv("MGX_GS_FUSED", "0")
-    st5 = five_point(po, L, "contrast", dt)
+    st5 = five_point(po, L, kind, dt)
     v, b = rand(L, 31, dt), rand(L, 32, dt)
     out = {}
-    for mu in (1, 2, 3):
+    for mu in mus:
         with pkg.Multigrid(finest_level=L, coarsest_level=L, op=pkg.OPERATOR_STENCIL5, smoother=cf.COLOR_SGS, dtype=dtype, mu1=0, mu2=mu,
                            bottom=1, schedule=0, profile=1) as mg:
             mg.set_stencil(L, *st5)
@@ -159,6 +159,30 @@ def test_the_fused_pass_equals_the_per_colour_launches(pkg, po, monkeypatch, dty
     for (direction, mu), got in fused.items():
         assert np.array_equal(got, plain[direction, mu]), (direction, mu)
         assert np.array_equal(got, cf.smooth(st9, dinv, v, b, mu, False, reverse=direction == "reverse")), (direction, mu)
+    assert not np.array_equal(fused["forward", 1], fused["reverse", 1])
+
+
+@pytest.mark.parametrize("kind", ["contrast", "random"])
+@pytest.mark.parametrize("dtype", [1, 0], ids=["f64", "f32"])
+def test_the_sixteen_row_chunks_of_the_fused_pass(pkg, po, monkeypatch, dtype, kind):
+    """from N = 1024 up gs_chunk_rows is 16: a rolling window of 16 rows, and a last chunk of 15.  Level 10 is the smallest
+    level that takes this path (level 9: 8 rows, above), so it is the size of this test: one and three sweeps, forward
+    and in reverse, against colour_ref and against the per-colour launches, bit for bit"""
+    L = 10
+    N = 1 << L
+    assert chunk_rows(N) == 16 and chunk_rows(N // 2) == 8 and (N - 1) % 16 == 15 and (N - 1) // 16 >= 3
+    strip = 62 * 16 // np.dtype(np_dtype(dtype)).itemsize
+    assert strip == (124 if dtype == 1 else 248) and -(-(N - 1) // strip) > 1          # more than one strip in either type
+    fused, n_fused, st9, v, b = one_level_sweeps(pkg, po, L, dtype, monkeypatch, True, kind, mus=(1, 3))
+    plain, n_plain, _, _, _ = one_level_sweeps(pkg, po, L, dtype, monkeypatch, False, kind, mus=(1, 3))
+    assert n_fused == 3 and n_plain == 6, (n_fused, n_plain)           # one launch a sweep against one a colour
+    dinv = cf.dinv_of(st9)
+    assert set(fused) == {(d, mu) for d in ("forward", "reverse") for mu in (1, 3)}
+    for (direction, mu), got in fused.items():
+        assert got.dtype == np_dtype(dtype)
+        want = cf.smooth(st9, dinv, v, b, mu, False, reverse=direction == "reverse")
+        assert np.array_equal(got, want), (direction, mu, np.argwhere(got != want)[:4])
+        assert np.array_equal(got, plain[direction, mu]), (direction, mu)
     assert not np.array_equal(fused["forward", 1], fused["reverse", 1])
 
 

@@ -74,11 +74,43 @@ POISSON double 2.9e-6 / 1.6e-3 (STREAMING: 4.0e-6 / 1.7e-3); STENCIL5 double Che
 products are exact in the double accumulators, and their sums round to the same floats); the line case 1.7e-4 of the
 history bound, 0.55 of the rule bound.
 
+COLOUR_CASES add the multicolour Gauss-Seidel smoothers (csrc/mgx_colour.hpp), the first smoother that mixes both buffer
+regimes on one handle - a five-point level with a chunk's worth of rows runs k_gs_rb out of place and swaps u / tmp once per
+sweep, a nine-point or smaller level runs k_gs_colour in place - and the first whose blocks depend on their position:
+COLOR_SGS reverses the colour order after a correction, in the last mu2 sweeps of a bottom = SMOOTH visit and so in every
+second visit of a W / F cycle, a flag that travels through capture, cycle_body under PCG / GCR, mgx_fmg and mgx_vcycle from
+any level.  The model hands `post` to tests/colour_ref.py, so everything stays bit for bit, on the coarse levels too.
+stencil5_f64_gs_8_5: V(3,2), every level swaps, an odd and an even block; stencil5_f32_sgs_7_3_smooth_bottom_cycles: levels
+7..4 swap, level 3 is in place, the bottom visit runs forward then in reverse, W / F second visits, cycles from levels 6, 5,
+4; galerkin_f64_sgs_7_3_cycles: only the finest level swaps, the dense solve at level 3, the same bits with
+MGX_SMALL_VISIT=0 (the visit kernel is Jacobi's); galerkin_f32_gs_fw16_8_5_smooth_bottom.  The first and the third a second
+time with MGX_GS_FUSED=0 (no level swaps): the same final state and histories.
+NINE_CASES flip lv[finest].nine between graph users (mgx_set_tensor / mgx_set_stencil9 against mgx_set_coefficient /
+mgx_set_stencil): every kernel of that level changes, the Krylov direction kernel on a workspace that survives, and under a
+colour smoother whether the level swaps.  galerkin_f64_jacobi_7_3_nine_cycles (rot45 -> OPERATOR -> set_coefficient ->
+smooth9 -> jump9, with and without the visit kernel), galerkin_f32_chebyshev_fw16_7_4_nine_smooth_bottom (smooth9 ->
+contrast -> rot45), galerkin_f64_sgs_7_3_nine_gcr (V(1,1); solve_pcg and solve_gcr before the first and after the last
+flip, each of them once the first Krylov call after a flip), galerkin_f64_gs_8_5_nine_gcr (V(1,0), bottom = SMOOTH).  The
+unsymmetric random9 runs through one list written by hand, without solve_pcg, on a COLOR_GS and a Jacobi handle: 9 -> 5
+(the unsymmetric five-point operator of tests/test_gpu_colour.py) -> 9 with other ring-pointing values than the model's.
+The Krylov calls are held as above; the condition, measured on the CPU from the model alone (tests/test_handle_model.py::
+test_the_model_walks_the_colour_and_nine_sequences and the GCR conditions test, which the two new GCR cases join): lowest
+last / first history entry of a double Krylov call 8.7e-3 (stencil5 gs), 3.4e-4 (galerkin sgs), 8.3e-4 (jacobi nine), 4.0e-6
+(sgs nine gcr: its deep call is five iterations of GCR(8) for this - six end at 3.5e-7), 1.4e-3 (gs nine gcr, the deep call of
+nine iterations), 8.1e-5 / 1.5e-3 (random9 gs / jacobi); float: 2.3e-2 at the lowest.  Measured on an MI355X, largest
+deviation as a fraction of its bound, history of solve_pcg / of solve_gcr / written state after either: stencil5 gs 1.0e-6 /
+- / 4.7e-5; galerkin sgs 1.8e-4 / - / 1.7e-4; jacobi nine 2.4e-5 / - / 1.4e-4; sgs nine gcr 3.9e-6 / 4.8e-6 / 8.5e-5; gs nine
+gcr 2.4e-6 / 2.7e-6 / 5.6e-5; random9 - / 6.3e-7 / 2.3e-4 (gs), - / 2.5e-7 / 3.0e-5 (jacobi); the three float cases: histories
+4e-13, state bit for bit.  The runs under MGX_SMALL_VISIT=0 and MGX_GS_FUSED=0 give the same figures to the digit.  The
+dense coarsest solve stays bit for bit under these operators at levels 3 and 4.
+
 A failing sequence is reproduced from the seed, the step index and the calls so far, which the message carries."""
 import numpy as np
 import pytest
 
 import handle_model as hm
+import nine_ref as nr
+from test_gpu_colour import random5
 from test_gpu_line import history_bound
 from test_line_cpu import rule_bound
 
@@ -99,7 +131,8 @@ KRYLOV = ("solve_pcg", "solve_gcr")
 GCR_RESTARTS = (1, 2, 3)
 DEEP_GCR = ("solve_gcr", 0.0, 9, 8)          # nine iterations of GCR(8): every slot of the full basis, then slot 0 again
 KNOBS = ("MGX_TILE_MAX_N", "MGX_FUSE_MIN_N", "MGX_PLAN_MIN_N", "MGX_PLAN_PRE", "MGX_PLAN_POST", "MGX_GRAPH", "MGX_FOLD", "MGX_FUSE",
-         "MGX_ZERO_IN", "MGX_TILE_K", "MGX_FOLD_KMAX", "MGX_FOLD_KMAX_NOPOST", "MGX_FUSE_ROWS", "MGX_ROWS", "MGX_SMALL_VISIT", "MGX_LINE_CHUNK")
+         "MGX_ZERO_IN", "MGX_TILE_K", "MGX_FOLD_KMAX", "MGX_FOLD_KMAX_NOPOST", "MGX_FUSE_ROWS", "MGX_ROWS", "MGX_SMALL_VISIT", "MGX_LINE_CHUNK",
+         "MGX_GS_FUSED")
 SMOOTHING = ("smooth", "vcycle", "vcycle_zero", "fmg", "solve", "solve_pcg", "solve_gcr")      # the calls that run a smoother
 CYCLE_ORDER = (hm.CYCLE_W, hm.CYCLE_F, hm.CYCLE_V, hm.CYCLE_W, hm.CYCLE_F, hm.CYCLE_W, hm.CYCLE_V)
 SMALL_MAX_LEVEL = 6                        # kSmallMaxN = 64 of csrc/mgx_small.hpp
@@ -275,6 +308,25 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
 
 
 # ---- one call on the device and on the model -------------------------------------------------------------------
+RANDOM5_SEED, RING_SEED = 70, 17
+
+
+def stencil5(L, kind, dt):
+    """("set_stencil", kind): "random5", the unsymmetric five-point operator of tests/test_gpu_colour.py"""
+    assert kind == "random5", kind
+    return random5(L, RANDOM5_SEED + L, dt)
+
+
+def stencil9(L, kind, dt, device):
+    """("set_stencil9", kind): a nine-point operator of handle_model.operator9.  "random9_ring": the DEVICE is handed
+    random9 with other values, up to 1e30, in the places that point at the Dirichlet ring (nine_ref.with_ring_values9),
+    the model the plain random9 - those coefficients multiply the zero ring of the iterate and must change no bit"""
+    if kind == "random9_ring":
+        st9 = hm.operator9(L, "random9", dt)
+        return [x.astype(dt) for x in nr.with_ring_values9(st9, RING_SEED)] if device else st9
+    return hm.operator9(L, kind, dt)
+
+
 def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
     """transfer: what a GALERKIN set_operator rebuilds with (the model's transfer in use).
     The binding (multigrid_nikhil_c-_amd/binding.py) wraps the bare mgx_fmg, mgx_bottom_solve, mgx_residual,
@@ -321,6 +373,18 @@ def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
         mg.build_galerkin(a[0])
     elif name == "set_cycle":
         mg.set_cycle(a[0])
+    elif name == "set_stencil":                           # GALERKIN: the finest level becomes five-point
+        mg.set_stencil(L, *stencil5(L, a[0], mg.level_dtype(L)))
+    elif name == "set_stencil9":
+        mg.set_stencil9(L, *stencil9(L, a[0], mg.level_dtype(L), device=True))
+    elif name == "set_tensor":
+        mg.set_tensor(*hm.tensor_nodes(L, a[0]))
+    elif name == "set_operator" and a[0] in hm.OPERATORS9:
+        if a[0] in hm.TENSORS:
+            mg.set_tensor(*hm.tensor_nodes(L, a[0]))
+        else:
+            mg.set_stencil9(L, *hm.operator9(L, a[0], mg.level_dtype(L)))
+        mg.build_galerkin(transfer)
     elif name == "set_operator":
         from oracle import pyoracle
         dt = mg.level_dtype(L)
@@ -355,6 +419,12 @@ def apply_model(m, call, L):
         m.zero_level(a[0], 0)
     elif name == "set_coefficient":
         m.set_coefficient(coefficient(L, a[0], a[1]))
+    elif name == "set_stencil":
+        m.set_stencil(L, stencil5(L, a[0], m.wdt))
+    elif name == "set_stencil9":
+        m.set_stencil9(L, stencil9(L, a[0], m.wdt, device=False))
+    elif name == "set_tensor":
+        m.set_tensor(*hm.tensor_nodes(L, a[0]))
     else:
         getattr(m, name)(*a)
     return None
@@ -897,6 +967,163 @@ def test_gcr_sequences_match_the_model_after_every_call(pkg, po, monkeypatch, na
         for x, y in zip(a.final, b.final):
             assert np.array_equal(x, y)
         assert len(a.histories) == len(b.histories) and all(np.array_equal(x, y) for x, y in zip(a.histories, b.histories))
+
+
+# ---- 2e. the colour smoothers and nine-point finest levels -----------------------------------------------------------
+def run_under(pkg, po, monkeypatch, cfg, calls, seed, envs):
+    """the sequence once per environment against a fresh model each; every run leaves the final state and the histories
+    of the first one, bit for bit"""
+    runs = []
+    for env in envs:
+        set_knobs(monkeypatch, env)
+        tally = run_sequence(pkg, po, cfg, calls, seed, env)
+        assert 1 <= tally.graphs <= K_MAX_GRAPHS
+        runs.append(tally)
+    a = runs[0]
+    for b, env in zip(runs[1:], envs[1:]):
+        for x, y in zip(a.final, b.final):
+            assert np.array_equal(x, y), env
+        assert len(a.histories) == len(b.histories) and all(np.array_equal(x, y) for x, y in zip(a.histories, b.histories)), env
+    return runs
+
+
+S73 = dict(G73, op=hm.STENCIL5)
+UNFUSED, NO_VISIT = {"MGX_GS_FUSED": "0"}, {"MGX_SMALL_VISIT": "0"}
+COLOUR_CASES = {
+    # name: (configuration, seed, environments, generator options)
+    # V(3,2): every level (N = 256 .. 32) runs k_gs_rb out of place, an odd and an even number of swaps per block; the in-place
+    # per-colour form (MGX_GS_FUSED=0) leaves other buffer assignments behind and the same bits
+    "stencil5_f64_gs_8_5": (dict(P85, op=hm.STENCIL5, smoother=hm.COLOR_GS), 8561, [{}, UNFUSED], {}),
+    # levels 7 .. 4 swap, level 3 (N = 8) runs per colour in place; the bottom visit sweeps forward, then in reverse; W / F
+    # pay second visits, whose blocks keep the direction of their position; cycles started from levels 6, 5, 4
+    "stencil5_f32_sgs_7_3_smooth_bottom_cycles": (dict(S73, dtype=hm.F32, smoother=hm.COLOR_SGS, bottom=hm.SMOOTH), 8562, [{}], dict(cycles=True)),
+    # only the finest level swaps; 6 .. 4 are nine-point, in place; the dense solve at level 3.  MGX_SMALL_VISIT: the
+    # visit kernel is Jacobi's and must be bypassed, whatever the knob says
+    "galerkin_f64_sgs_7_3_cycles": (dict(G73, smoother=hm.COLOR_SGS), 8563, [{}, NO_VISIT, UNFUSED], dict(cycles=True)),
+    "galerkin_f32_gs_fw16_8_5_smooth_bottom": (dict(P85, op=hm.GALERKIN, dtype=hm.F32, smoother=hm.COLOR_GS, restrict_mode=hm.FW16, bottom=hm.SMOOTH),
+                                               8564, [{}], {}),
+}
+
+
+@pytest.mark.parametrize("name", list(COLOUR_CASES))
+def test_colour_smoother_sequences_match_the_model_after_every_call(pkg, po, monkeypatch, name):
+    """COLOR_GS / COLOR_SGS (csrc/mgx_colour.hpp): the one smoother that swaps u / tmp on some levels of a handle and not
+    on others, and whose blocks depend on their position in the cycle - a flag that travels through graph capture,
+    cycle_body under PCG, mgx_fmg and mgx_vcycle(level) from any level.  U and B of EVERY level bit for bit after every
+    call (solve_pcg as in GENERAL_CASES)"""
+    cfg, seed, envs, options = COLOUR_CASES[name]
+    calls = draw_sequence(seed, cfg, **options)
+    if options.get("cycles"):
+        assert_cycle_calls(calls, cfg)
+    run_under(pkg, po, monkeypatch, cfg, calls, seed, envs)
+
+
+def point_counts(calls):
+    """9 / 5 / None: the point count of a GALERKIN handle's finest level after every call of a list"""
+    out, count = [], None
+    for c in calls:
+        if c[0] in ("set_stencil9", "set_tensor") or (c[0] == "set_operator" and c[1] in hm.OPERATORS9):
+            count = 9
+        elif c[0] in ("set_stencil", "set_coefficient", "set_operator"):
+            count = 5
+        out.append(count)
+    return out
+
+
+def flips(calls):
+    """the indices of the calls that change the finest level's point count"""
+    counts = point_counts(calls)
+    return [i for i in range(1, len(calls)) if counts[i] != counts[i - 1] and counts[i - 1] is not None]
+
+
+def assert_nine_calls(calls, cfg, first, changes, krylov=False):
+    """what a NINE_CASES sequence promises, on the drawn list: the operator changes in their order, every flip of the point
+    count between two graph users - so the first user after it replays, or captures, on the flipped level.  krylov:
+    solve_pcg and solve_gcr both run before the first flip and after the last one, and the first of the two after a flip
+    is solve_pcg once and solve_gcr once: either method on the workspace the other point count left"""
+    users = [i for i, c in enumerate(calls) if c[0] in graph_users(calls)]
+    assert calls[0] == ("set_operator", first) and first in hm.OPERATORS9
+    assert [c for c in calls[1:] if c[0] in ("set_operator", "set_coefficient", "build_galerkin", "set_tensor", "set_stencil9", "set_stencil")] == \
+        [c for g in changes for c in g]
+    at = flips(calls)
+    assert len(at) >= 2 and {point_counts(calls)[i] for i in at} == {5, 9}, at
+    for i in at:
+        assert any(u < i for u in users) and any(u > i for u in users), i
+    if krylov:
+        for part in (calls[:at[0]], calls[at[-1]:]):
+            assert {"solve_pcg", "solve_gcr"} <= {c[0] for c in part}
+        firsts = [next(c[0] for c in calls[i:] if c[0] in KRYLOV) for i in at]
+        assert set(firsts) == set(KRYLOV), firsts
+
+
+NINE_CASES = {
+    # name: (configuration, seed, environments, generator options); options["operators"] = (first, changes)
+    # set_tensor; OPERATOR transfers; 9 -> 5 through set_coefficient; 5 -> 9 through set_tensor; another tensor
+    "galerkin_f64_jacobi_7_3_nine_cycles": (
+        dict(G73), 8571, [{}, NO_VISIT],
+        dict(cycles=True, operators=("rot45", [[("build_galerkin", hm.OPERATOR)], [("set_coefficient", 100.0, 11), ("build_galerkin", hm.BILINEAR)],
+                                               [("set_operator", "smooth9")], [("set_operator", "jump9")]]))),
+    "galerkin_f32_chebyshev_fw16_7_4_nine_smooth_bottom": (
+        dict(G73, coarsest_level=4, dtype=hm.F32, smoother=hm.CHEBYSHEV, restrict_mode=hm.FW16, bottom=hm.SMOOTH), 8572, [{}],
+        dict(operators=("smooth9", [[("set_operator", "contrast")], [("set_operator", "rot45")]]))),
+    # V(1,1): the reverse blocks exist; the finest level flips between in place (nine-point) and swapping (five-point), the
+    # Krylov direction kernel between k_pcg_direction<T, 2> and <T, 1> on one workspace
+    "galerkin_f64_sgs_7_3_nine_gcr": (
+        dict(G73, mu1=1, mu2=1, smoother=hm.COLOR_SGS), 8580, [{}],
+        dict(gcr=True, deep_iters=5, operators=("smooth9", [[("set_coefficient", 100.0, 11), ("build_galerkin", hm.BILINEAR)],
+                                                            [("set_operator", "rot45")], [("build_galerkin", hm.OPERATOR)]]))),
+    "galerkin_f64_gs_8_5_nine_gcr": (
+        dict(P85_WEAK, op=hm.GALERKIN, smoother=hm.COLOR_GS, bottom=hm.SMOOTH), 8587, [{}],
+        dict(gcr=True, operators=("rot45", [[("set_operator", "contrast")], [("set_operator", "smooth9")]]))),
+}
+
+
+@pytest.mark.parametrize("name", list(NINE_CASES))
+def test_nine_point_finest_sequences_match_the_model_after_every_call(pkg, po, monkeypatch, name):
+    """mgx_set_tensor / mgx_set_stencil9 and back (mgx_set_coefficient, mgx_set_stencil) between the graph users of one
+    handle: lv[finest].nine flips, and with it every kernel on that level, the Krylov direction kernel, and under a colour
+    smoother whether the level swaps.  U and B of EVERY level bit for bit after every call, the Krylov calls as in
+    GCR_CASES (module docstring)"""
+    cfg, seed, envs, options = NINE_CASES[name]
+    calls = draw_sequence(seed, cfg, **options)
+    assert_nine_calls(calls, cfg, *options["operators"], krylov=options.get("gcr", False))
+    if options.get("cycles"):
+        assert_cycle_calls(calls, cfg)
+    if options.get("gcr"):
+        assert_gcr_calls(calls, cfg, False, options.get("deep_iters", DEEP_GCR[2]))
+    run_under(pkg, po, monkeypatch, cfg, calls, seed, envs)
+
+
+# "random9" is unsymmetric: no solve_pcg.  One list, written by hand
+RANDOM9_CALLS = (
+    [("set_stencil9", "random9"), ("build_galerkin", hm.BILINEAR)] + [c for lv in range(3, 7) for c in (("set_u", lv, 1000 + lv), ("set_b", lv, 2000 + lv))]
+    + [("solve", 0.0, 2), ("vcycle_zero",), ("smooth", 6, 1), ("solve_gcr", 0.0, 3, 3), ("vcycle", 6),
+       ("set_stencil", "random5"), ("build_galerkin", hm.BILINEAR), ("solve", 0.0, 2), ("solve_gcr", 0.0, 3, 3),
+       ("set_stencil9", "random9_ring"), ("build_galerkin", hm.BILINEAR), ("solve", 0.0, 2), ("solve_gcr", 0.0, 3, 3)])
+
+
+@pytest.mark.parametrize("smoother", [hm.COLOR_GS, hm.JACOBI], ids=["gs", "jacobi"])
+def test_an_unsymmetric_nine_point_operator_on_one_handle(pkg, po, monkeypatch, smoother):
+    """mgx_set_stencil9 with corners, no symmetry and values in the ring-pointing places; then the unsymmetric five-point
+    operator of tests/test_gpu_colour.py (9 -> 5); then the nine-point one again with other ring-pointing values, against
+    the model that keeps the plain ones.  solve and solve_gcr run on both sides of either flip"""
+    cfg = dict(finest_level=6, coarsest_level=3, mu0=0, mu1=1, mu2=1, schedule=hm.V, op=hm.GALERKIN, smoother=smoother)
+    calls = list(RANDOM9_CALLS)
+    assert not any(c[0] == "solve_pcg" for c in calls) and [point_counts(calls)[i] for i in flips(calls)] == [5, 9]
+    set_knobs(monkeypatch, {})
+    tally, done = Tally(), []
+
+    def where():
+        return f"random9 sequence, step {len(done) - 1} of {len(calls)}, cfg {cfg}, calls so far {done}"
+
+    m = hm.HandleModel(po, **cfg)
+    with pkg.Multigrid(**cfg) as mg:
+        for call in calls:
+            done.append(call)
+            step(pkg, mg, m, cfg, call, tally, where)
+    assert tally.executed == len(calls) and tally.graphs >= 1
+    print(f"\n[handle-state] random9 cfg={cfg} steps={tally.executed} max_graphs={tally.graphs} hist_solve={tally.hist['solve']:.3g}xbound "
+          f"hist_gcr={tally.hist['solve_gcr']:.3g}xbound state_dev_gcr={tally.state_gcr:.3g} ({tally.state_gcr / RTOL64:.3g}xbound)")
 
 
 # ---- 3. the cache bound and its fallback ---------------------------------------------------------------------------

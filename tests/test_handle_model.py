@@ -1,15 +1,20 @@
 """Keeps tests/handle_model.py honest (no GPU): the schedules it composes from its own single operators must give
 the bits of the references' own schedules - oracle/pyoracle.py's Solver for the constant stencil, the hierarchies of
-tests/galerkin_ref.py, tests/opdep_ref.py and tests/cheby_ref.py for the general operators - and its solves their
-histories; the coarse levels must hold afterwards what the documented operator sequence leaves there."""
+tests/galerkin_ref.py, tests/opdep_ref.py and tests/cheby_ref.py for the general operators, tests/colour_ref.py for the
+colour smoothers and tests/nine_ref.py for nine-point finest levels - and its solves their histories; the coarse levels
+must hold afterwards what the documented operator sequence leaves there.  The sequences of
+tests/test_gpu_handle_state.py are drawn and walked here without a device: what the generator promises, and the
+conditions the Krylov bounds rest on."""
 import numpy as np
 import pytest
 
 import cheby_ref
+import colour_ref as cf
 import galerkin_ref as gr
 import gcr_ref
 import handle_model as hm
 import line_ref as lr
+import nine_ref as nr
 import opdep_ref as od
 import pcg_ref
 import test_gpu_handle_state as gs
@@ -733,7 +738,11 @@ def sync(dst, src):
     dst.fine_updates = src.fine_updates
 
 
-@pytest.mark.parametrize("name", list(gs.GCR_CASES))
+# the GCR cases of NINE_CASES join: (configuration, seed, environments, generator options, through line_step)
+GCR_CONDITION_CASES = dict(gs.GCR_CASES, **{k: v + (False,) for k, v in gs.NINE_CASES.items() if v[3].get("gcr")})
+
+
+@pytest.mark.parametrize("name", list(GCR_CONDITION_CASES))
 def test_the_gcr_sequences_meet_the_conditions_their_bounds_rest_on(po, name):
     """the model alone through every GCR_CASES sequence, without a device:
       * double: every solve_gcr and solve_pcg call ends with its last history entry at or above 1e-6 of its first - the
@@ -743,8 +752,8 @@ def test_the_gcr_sequences_meet_the_conditions_their_bounds_rest_on(po, name):
         every scalar moved independently by up to one float ulp (ulp_dot); the largest movement of any array the call
         writes, relative to its largest entry, stays at or below PCG32_STATE / 4;
       * the line case: no bound of THE TOLERANCE RULE above RTOL64"""
-    cfg, seed, envs, options, line = gs.GCR_CASES[name]
-    calls = gs.draw_sequence(seed, cfg, gcr=True, **options)
+    cfg, seed, envs, options, line = GCR_CONDITION_CASES[name]
+    calls = gs.draw_sequence(seed, cfg, **dict(options, gcr=True))
     f64 = cfg.get("dtype", hm.F64) == hm.F64
     L = cfg["finest_level"]
     if line:
@@ -790,3 +799,390 @@ def test_the_gcr_sequences_meet_the_conditions_their_bounds_rest_on(po, name):
         assert moved_hist <= gs.RTOL32 / 4, moved_hist
     if line:
         assert held > 100 and 0.0 < worst[0] <= gs.line_cap(cfg), worst
+
+
+# ---- the colour smoothers and nine-point finest levels -----------------------------------------------------------------
+def assert_model_equals_reference(po, m, ref, u, b, mu1, mu2, mu0, colour):
+    """the model's composed schedules against the reference's own, for the cycle kinds V, W and F: a cycle from (u, b),
+    level L - 1 afterwards, a cycle from L - 1 with a non-zero U, fmg, a zero-start cycle, a solve with its statistics"""
+    L = m.L
+    dt = u.dtype
+    n2 = float((1 << L) - 1) ** 2
+    for kind in (hm.CYCLE_V, hm.CYCLE_W, hm.CYCLE_F):
+        m.set_cycle(kind)
+        ref.cycle = kind
+        m.set_guess(u)
+        m.set_rhs(b)
+        m.vcycle()
+        assert m.U[L].dtype == dt and np.array_equal(m.U[L], ref.vcycle(L, u, b)), kind
+        assert np.array_equal(m.B[L], b)
+        v = ref.smooth(L, u, b, mu1, False) if colour else ref.smooth(L, u, b, mu1)
+        assert np.array_equal(m.B[L - 1], ref._restrict_residual(L, v, b)), kind
+        top = m.U[L].copy()
+        u1, b1 = data(po, L - 1, dt, 78)
+        m.set_level(L - 1, 0, u1)
+        m.set_level(L - 1, 1, b1)
+        m.vcycle(L - 1)
+        assert np.array_equal(m.U[L - 1], ref.vcycle(L - 1, u1, b1)) and np.array_equal(m.U[L], top), kind
+        m.fmg()
+        assert np.array_equal(m.U[L], ref.fmg(b)), kind
+        m.set_guess(u)
+        m.vcycle_zero()
+        assert np.array_equal(m.U[L], ref.vcycle(L, np.zeros_like(b), b)), kind
+        m.set_guess(u)
+        st, h = m.solve(tol=0.0, max_cycles=2)
+        u_ref, h_ref = ref.solve(b, u, tol=0.0, max_cycles=2, schedule=gr.FMG)
+        assert np.array_equal(h, h_ref) and np.array_equal(m.U[L], u_ref) and st["cycles"] == 2, kind
+        assert st["fine_updates"] == (mu0 + 2) * (mu1 + mu2) * n2          # FMG: mu0 + 1 finest cycles, then one; one update per point and sweep
+    m.set_cycle(hm.CYCLE_V)
+
+
+COLOUR_REFS = {
+    # name: (reference class, op, transfer)
+    "Stencil5": (cf.Stencil5, hm.STENCIL5, None),
+    "Hierarchy": (cf.Hierarchy, hm.GALERKIN, hm.BILINEAR),
+    "OpdepHierarchy": (cf.OpdepHierarchy, hm.GALERKIN, hm.OPERATOR),
+}
+
+
+@pytest.mark.parametrize("bottom", [hm.EXACT, hm.SMOOTH], ids=["exact", "smooth"])
+@pytest.mark.parametrize("dtype", [hm.F64, hm.F32], ids=["f64", "f32"])
+@pytest.mark.parametrize("smoother", [hm.COLOR_GS, hm.COLOR_SGS], ids=["gs", "sgs"])
+@pytest.mark.parametrize("name", list(COLOUR_REFS))
+@pytest.mark.parametrize("L,Lc", LEVELS)
+def test_colour_models_equal_colour_ref(po, L, Lc, name, smoother, dtype, bottom):
+    cls, op, transfer = COLOUR_REFS[name]
+    mode = hm.FW16 if (L + dtype) % 2 else hm.CONSISTENT
+    mu0, mu1, mu2 = 1, 2, 1
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=mu0, mu1=mu1, mu2=mu2, smoother=smoother, dtype=dtype, restrict_mode=mode, bottom=bottom,
+               op=op, schedule=hm.FMG)
+    dt = np.float64 if dtype == hm.F64 else np.float32
+    a = contrast(L, 10.0, 4)
+    kw = dict(dtype=dt, mode=mode, omega=2.0 / 3.0, mu1=mu1, mu2=mu2, mu0=mu0, bottom=bottom)
+    if op == hm.STENCIL5:
+        ref = cls(smoother, po, {lv: po.stencil_from_nodes(a, lv, L) for lv in range(Lc, L + 1)}, L, Lc, **kw)
+    else:
+        ref = cls(smoother, po, po.stencil_from_nodes(a, L, L), L, Lc, **kw)
+    m = hm.HandleModel(po, **cfg)
+    with pytest.raises(RuntimeError):
+        m.smooth(L, 1)
+    m.set_coefficient(a)
+    if op == hm.GALERKIN:
+        m.build_galerkin(transfer)
+    u, b = data(po, L, dt, 90 + L)
+    # mgx_smooth is forward under either smoother, on the finest level and on a coarse one (nine-point under GALERKIN)
+    for lv in (L, L - 1):
+        x, f = data(po, lv, dt, 91 + lv)
+        m.set_level(lv, 0, x)
+        m.set_level(lv, 1, f)
+        m.smooth(lv, 3)
+        assert np.array_equal(m.U[lv], ref.smooth(lv, x, f, 3, False))
+        if smoother == hm.COLOR_SGS:
+            assert not np.array_equal(m.U[lv], ref.smooth(lv, x, f, 3, True))
+    assert m.fine_updates == 3.0 * float((1 << L) - 1) ** 2
+    assert_model_equals_reference(po, m, ref, u, b, mu1, mu2, mu0, True)
+    if bottom == hm.EXACT:
+        f = data(po, Lc, dt, 9)[1]
+        m.set_level(Lc, 1, f)
+        m.bottom_solve()
+        assert np.array_equal(m.U[Lc], ref.bottom(f))       # the oracle's dense solve (STENCIL5) against the numpy elimination
+
+
+def nine_reference(po, family, transfer, st9, L, Lc, **kw):
+    opdep = transfer == hm.OPERATOR
+    if family in (hm.COLOR_GS, hm.COLOR_SGS):
+        return (cf.NineOpdepHierarchy if opdep else cf.NineHierarchy)(family, po, st9, L, Lc, **kw)
+    if family == hm.CHEBYSHEV:
+        return (nr.ChebyOpdepHierarchy if opdep else nr.ChebyHierarchy)(po, st9, L, Lc, **kw)
+    return (nr.OpdepHierarchy if opdep else nr.Hierarchy)(po, st9, L, Lc, **kw)
+
+
+@pytest.mark.parametrize("dtype", [hm.F64, hm.F32], ids=["f64", "f32"])
+@pytest.mark.parametrize("transfer", [hm.BILINEAR, hm.OPERATOR], ids=["bilinear", "operator"])
+@pytest.mark.parametrize("smoother", [hm.JACOBI, hm.CHEBYSHEV, hm.COLOR_GS, hm.COLOR_SGS], ids=["jacobi", "chebyshev", "gs", "sgs"])
+@pytest.mark.parametrize("L,Lc", LEVELS)
+def test_nine_point_finest_models_equal_their_references(po, L, Lc, smoother, transfer, dtype):
+    """set_tensor (smooth9) and set_stencil9 (random9, unsymmetric) by turns; EXACT and SMOOTH bottoms by turns"""
+    tensor = (L + transfer) % 2 == 0
+    bottom = hm.EXACT if (L + dtype + smoother) % 2 == 0 else hm.SMOOTH
+    mode = hm.FW16 if dtype == hm.F32 else hm.CONSISTENT
+    mu0, mu1, mu2 = 0, 2, 1
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=mu0, mu1=mu1, mu2=mu2, smoother=smoother, dtype=dtype, restrict_mode=mode, bottom=bottom,
+               op=hm.GALERKIN, schedule=hm.FMG)
+    dt = np.float64 if dtype == hm.F64 else np.float32
+    st9 = hm.operator9(L, "smooth9" if tensor else "random9", dt)
+    ref = nine_reference(po, smoother, transfer, st9, L, Lc, dtype=dt, mode=mode, omega=2.0 / 3.0, mu1=mu1, mu2=mu2, mu0=mu0, bottom=bottom)
+    m = hm.HandleModel(po, **cfg)
+    if tensor:
+        m.set_tensor(*hm.tensor_nodes(L, "smooth9"))
+    else:
+        m.set_stencil9(L, st9)
+    with pytest.raises(RuntimeError):
+        m.vcycle()                                          # invalid until the build, as after set_stencil
+    m.build_galerkin(transfer)
+    assert all(np.array_equal(x, y) and x.dtype == dt for x, y in zip(m.h.st[L], st9)) and len(m.h.st[L]) == 9
+    A = m.finest_operator()
+    u, b = data(po, L, dt, 95 + L)
+    assert isinstance(A, nr.Operator9) and np.array_equal(A(u), ref.apply(u))
+    colour = smoother in hm.COLOURS
+    assert_model_equals_reference(po, m, ref, u, b, mu1, mu2, mu0, colour)
+    # single operators between two levels, with the hierarchy's transfers
+    e = data(po, L - 1, dt, 11)[0]
+    m.set_level(L - 1, 0, e)
+    m.set_guess(u)
+    m.prolong_add(L)
+    want = u + ref.prolong(L, e) if transfer == hm.OPERATOR else po.prolong_add(u, e)
+    assert np.array_equal(m.U[L], want)
+    m.restrict(L)
+    r = ref.residual(L, want, b)
+    assert np.array_equal(m.B[L - 1], ref.restrict(L, r) if transfer == hm.OPERATOR else po.restrict(r, mode)) and not m.U[L - 1].any()
+
+
+def test_solve_pcg_equals_pcg_ref_around_the_symmetric_colour_cycle(po):
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=1, mu2=1, op=hm.GALERKIN, smoother=hm.COLOR_SGS, schedule=hm.V)
+    st5 = operator5(po, L, "contrast", np.float64)
+    ref = cf.Hierarchy(hm.COLOR_SGS, po, st5, L, Lc, np.float64, mu1=1, mu2=1)
+    u, b = data(po, L, np.float64, 16)
+    x_ref, h_ref, conv, brk = pcg_ref.pcg(pcg_ref.Operator(st5, np.float64), gcr_ref.cycle_preconditioner(ref), b, u, tol=1e-8, max_iters=40)
+    m = hm.HandleModel(po, **cfg)
+    m.set_operator("contrast")
+    m.set_guess(u)
+    m.set_rhs(b)
+    st, h = m.solve_pcg(tol=1e-8, max_iters=40)
+    assert conv and not brk and np.array_equal(h, h_ref) and np.array_equal(m.U[L], x_ref) and np.array_equal(m.B[L], b)
+    assert st == dict(cycles=len(h_ref) - 1, converged=1, fine_updates=(len(h_ref) - 1) * 2.0 * float((1 << L) - 1) ** 2)
+    # the forward-only cycle is another preconditioner: the direction is part of what solve_pcg runs
+    gs_twin = hm.HandleModel(po, **dict(cfg, smoother=hm.COLOR_GS))
+    gs_twin.set_operator("contrast")
+    gs_twin.set_guess(u)
+    gs_twin.set_rhs(b)
+    assert not np.array_equal(gs_twin.solve_pcg(tol=0.0, max_iters=2)[1], h_ref[:3])
+
+
+@pytest.mark.parametrize("smoother", [hm.COLOR_GS, hm.COLOR_SGS], ids=["gs", "sgs"])
+def test_solve_gcr_equals_gcr_ref_around_a_nine_point_colour_hierarchy(po, smoother):
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=1, mu2=1, op=hm.GALERKIN, smoother=smoother, schedule=hm.V)
+    st9 = hm.operator9(L, "random9", np.float64)
+    ref = cf.NineHierarchy(smoother, po, st9, L, Lc, np.float64, mu1=1, mu2=1)
+    u, b = data(po, L, np.float64, 18)
+    m = hm.HandleModel(po, **cfg)
+    m.set_operator("random9")
+    assert m.transfer == hm.BILINEAR
+    assert_gcr_equals(po, m, nr.Operator9(st9), gcr_ref.cycle_preconditioner(ref), u, b, GCR_CALLS(1e-8))
+
+
+@pytest.mark.parametrize("op", [hm.STENCIL5, hm.GALERKIN], ids=["stencil5", "galerkin"])
+def test_the_direction_of_the_bottom_visit_is_modelled(po, op):
+    """COLOR_SGS, bottom = SMOOTH, mu2 >= 1: the coarsest level sweeps mu1 times forward, then mu2 times in reverse.  One
+    cycle differs from the COLOR_GS twin's - on the coarsest level already, and with mu1 = 0 and two levels nowhere else:
+    the only reverse blocks a zero-start cycle then runs are the bottom's and the finest level's"""
+    L, Lc = 5, 3
+    out = {}
+    for smoother in (hm.COLOR_GS, hm.COLOR_SGS):
+        m = hm.HandleModel(po, finest_level=L, coarsest_level=Lc, mu0=0, mu1=2, mu2=1, op=op, smoother=smoother, bottom=hm.SMOOTH, schedule=hm.V)
+        m.set_operator("contrast")
+        u, b = data(po, L, np.float64, 19)
+        m.set_guess(u)
+        m.set_rhs(b)
+        m.vcycle()
+        out[smoother] = {lv: (m.U[lv].copy(), m.B[lv].copy()) for lv in m.levels()}
+        # the visit of the coarsest level by hand
+        h, f = m.h, m.B[Lc]
+        v = h.smooth(Lc, np.zeros_like(f), f, 2, False)
+        assert np.array_equal(m.U[Lc], h.smooth(Lc, v, f, 1, True))
+        if smoother == hm.COLOR_SGS:
+            assert not np.array_equal(m.U[Lc], h.smooth(Lc, v, f, 1, False))
+    gs_state, sgs_state = out[hm.COLOR_GS], out[hm.COLOR_SGS]
+    for lv in range(Lc, L):
+        assert np.array_equal(gs_state[lv][1], sgs_state[lv][1])               # the way down is forward under both
+    for lv in range(Lc, L + 1):
+        assert not np.array_equal(gs_state[lv][0], sgs_state[lv][0]), lv
+
+
+@pytest.mark.parametrize("smoother", [hm.JACOBI, hm.COLOR_SGS], ids=["jacobi", "sgs"])
+def test_tensor_coefficient_tensor_on_one_model_equals_fresh_models(po, smoother):
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=1, mu2=1, op=hm.GALERKIN, smoother=smoother, schedule=hm.V)
+    a = contrast(L, 100.0, 5)
+    u, b = data(po, L, np.float64, 23)
+    changes = [lambda m: m.set_tensor(*hm.tensor_nodes(L, "rot45")), lambda m: m.set_coefficient(a), lambda m: m.set_tensor(*hm.tensor_nodes(L, "jump9"))]
+
+    def state(m):
+        m.set_guess(u)
+        m.set_rhs(b)
+        out = [m.solve(tol=0.0, max_cycles=2)[1], m.solve_pcg(tol=0.0, max_iters=2)[1], m.solve_gcr(tol=0.0, max_iters=3, restart=2)[1]]
+        return out + [m.U[lv].copy() for lv in m.levels()] + [m.B[lv].copy() for lv in m.levels()]
+
+    one = hm.HandleModel(po, **cfg)
+    got, want, nines = [], [], []
+    for change in changes:
+        change(one)
+        with pytest.raises(RuntimeError):
+            one.vcycle()
+        one.build_galerkin(hm.OPERATOR if len(got) == 2 else hm.BILINEAR)
+        nines.append((one.st9 is not None, isinstance(one.finest_operator(), nr.Operator9), len([x for x in one.h.st[L][5:] if x.any()])))
+        got.append(state(one))
+        fresh = hm.HandleModel(po, **cfg)
+        change(fresh)
+        fresh.build_galerkin(hm.OPERATOR if len(want) == 2 else hm.BILINEAR)
+        want.append(state(fresh))
+    assert nines == [(True, True, 4), (False, False, 0), (True, True, 4)]
+    for g, w in zip(got, want):
+        assert len(g) == len(w) and all(np.array_equal(x, y) for x, y in zip(g, w))
+    assert not np.array_equal(got[0][3 + L - Lc], got[2][3 + L - Lc])
+
+
+def test_nine_point_refusals(po):
+    L = 5
+    st9 = hm.operator9(L, "random9", np.float64)
+    nodes = hm.tensor_nodes(L, "rot45")
+    for op in (hm.STENCIL5, hm.POISSON):                    # the device: MGX_ERR_STATE
+        m = hm.HandleModel(po, finest_level=L, coarsest_level=3, op=op)
+        with pytest.raises(RuntimeError):
+            m.set_stencil9(L, st9)
+        with pytest.raises(RuntimeError):
+            m.set_tensor(*nodes)
+        with pytest.raises(RuntimeError):
+            m.set_operator("rot45")
+    m = hm.HandleModel(po, finest_level=L, coarsest_level=3, op=hm.GALERKIN)
+    with pytest.raises(RuntimeError):
+        m.set_stencil9(L - 1, hm.operator9(L - 1, "random9", np.float64))      # a coarse level is R A P
+    with pytest.raises(RuntimeError):
+        m.build_galerkin()
+    for line in hm.LINES:                                   # out of scope, and the message says so
+        m = hm.HandleModel(po, finest_level=L, coarsest_level=3, op=hm.GALERKIN, smoother=line)
+        with pytest.raises(ValueError, match="out of scope"):
+            m.set_tensor(*nodes)
+        with pytest.raises(ValueError, match="out of scope"):
+            m.set_stencil9(L, st9)
+        m.set_operator("layers")                            # five-point: as before
+    with pytest.raises(ValueError):
+        hm.HandleModel(po, smoother=hm.COLOR_GS)            # POISSON
+    assert (hm.COLOR_GS, hm.COLOR_SGS) == (8, 9)
+
+
+def test_the_named_nine_point_operators():
+    L = 5
+    for kind in hm.TENSORS:
+        st9 = hm.operator9(L, kind, np.float64)
+        assert len(st9) == 9 and all(x.shape == (31, 31) and x.dtype == np.float64 for x in st9)
+        assert any(x.any() for x in st9[5:])                # corners
+        assert np.array_equal(st9[4][:, :-1], st9[3][:, 1:]) and np.array_equal(st9[8][:-1, :-1], st9[5][1:, 1:])      # symmetric
+    assert all(np.array_equal(x, y) for x, y in zip(hm.operator9(L, "rot45", np.float32), nr.tensor9(*nr.rotated_tensor(L, 45.0, 0.5), dtype=np.float32)))
+    st9 = hm.operator9(L, "random9", np.float64)
+    assert np.max(np.abs(st9[4][:, :-1] - st9[3][:, 1:])) > 0.1 and np.max(np.abs(st9[8][:-1, :-1] - st9[5][1:, 1:])) > 0.1    # not symmetric
+    assert st9[1][0, :].all() and st9[5][:, 0].all() and st9[8][-1, :].all()            # values in ring-pointing places
+    ring = gs.stencil9(L, "random9_ring", np.float64, device=True)
+    plain = gs.stencil9(L, "random9_ring", np.float64, device=False)
+    assert all(np.array_equal(x, y) for x, y in zip(plain, st9))
+    assert all(np.array_equal(x, y) for x, y in zip(nr.zero_ring(ring), nr.zero_ring(st9))) and np.max(np.abs(ring[1][0, :])) > 1e6
+
+
+# ---- the sequences of COLOUR_CASES, NINE_CASES and the random9 list ------------------------------------------------------
+def test_colour_and_nine_sequences_hold_what_the_generator_promises():
+    assert "MGX_GS_FUSED" in gs.KNOBS
+    seeds = [c[1] for d in (gs.POISSON_CASES, gs.GENERAL_CASES, gs.CYCLE_CASES, gs.LINE_CASES, gs.GCR_CASES, gs.COLOUR_CASES, gs.NINE_CASES) for c in d.values()]
+    assert len(set(seeds)) == len(seeds)
+    nine_calls = ("set_stencil9", "set_tensor", "set_stencil")
+    # every new call kind is off by default: no sequence drawn without the operators option holds one
+    for cfg, seed in list(gs.POISSON_CASES.values()) + list(gs.GENERAL_CASES.values()):
+        calls = gs.draw_sequence(seed, cfg)
+        assert not any(c[0] in nine_calls or (c[0] == "set_operator") for c in calls)
+    for name, (cfg, seed, envs, options) in gs.COLOUR_CASES.items():
+        calls = gs.draw_sequence(seed, cfg, **options)
+        assert calls == gs.draw_sequence(seed, cfg, **options)
+        assert set(options) <= {"cycles"} and envs[0] == {}
+        users = [i for i, c in enumerate(calls) if c[0] in gs.GRAPH_USERS]
+        assert gs.graph_users(calls) == gs.GRAPH_USERS and min(sum(1 for c in calls if c[0] == k) for k in gs.GRAPH_USERS) >= 5
+        for lv in range(cfg["coarsest_level"], cfg["finest_level"] + 1):     # an odd-launch smooth on every level between graph users
+            assert any(c[0] == "smooth" and c[1] == lv and c[2] % 2 for c in calls[users[0] + 1:users[-1]]), (name, lv)
+        if options.get("cycles"):
+            gs.assert_cycle_calls(calls, cfg)
+        changes = [i for i, c in enumerate(calls) if c[0] in ("set_coefficient", "build_galerkin")]
+        if cfg["op"] == hm.STENCIL5:
+            assert [calls[i][1] for i in changes] == [10.0, 100.0, 1000.0]
+        else:
+            assert [calls[i][1] for i in changes if calls[i][0] == "build_galerkin"] == [hm.BILINEAR, hm.OPERATOR, hm.BILINEAR, hm.OPERATOR, hm.BILINEAR]
+        for i in changes[2 if cfg["op"] == hm.GALERKIN else 1:]:             # the changes after the first operator: between graph users
+            assert users[0] < i < users[-1], (name, i)
+        assert not any(c[0] in nine_calls or c[0] == "set_operator" for c in calls)
+    # which levels swap (k_gs_rb: five-point, a chunk of 8 rows at least - gs_fused_level of csrc/mgx_colour.hpp) and which
+    # sweep in place, as the cases say
+    fused = lambda cfg, lv: (cfg["op"] == hm.STENCIL5 or lv == cfg["finest_level"]) and (1 << lv) - 1 >= 8
+    c = gs.COLOUR_CASES["stencil5_f64_gs_8_5"][0]
+    assert all(fused(c, lv) for lv in range(5, 9)) and c["mu1"] % 2 == 1 and c["mu2"] % 2 == 0 and c["smoother"] == hm.COLOR_GS
+    c = gs.COLOUR_CASES["stencil5_f32_sgs_7_3_smooth_bottom_cycles"][0]
+    assert [fused(c, lv) for lv in range(3, 8)] == [False, True, True, True, True] and c["bottom"] == hm.SMOOTH and c["mu2"] >= 1 and c["dtype"] == hm.F32
+    c = gs.COLOUR_CASES["galerkin_f64_sgs_7_3_cycles"][0]
+    assert [fused(c, lv) for lv in range(3, 8)] == [False, False, False, False, True] and c.get("bottom", hm.EXACT) == hm.EXACT
+    assert gs.COLOUR_CASES["galerkin_f64_sgs_7_3_cycles"][2] == [{}, {"MGX_SMALL_VISIT": "0"}, {"MGX_GS_FUSED": "0"}]
+    assert gs.COLOUR_CASES["stencil5_f64_gs_8_5"][2] == [{}, {"MGX_GS_FUSED": "0"}]
+    c = gs.COLOUR_CASES["galerkin_f32_gs_fw16_8_5_smooth_bottom"][0]
+    assert c["restrict_mode"] == hm.FW16 and c["bottom"] == hm.SMOOTH and c["dtype"] == hm.F32 and c["smoother"] == hm.COLOR_GS
+    orders = set()
+    for name, (cfg, seed, envs, options) in gs.NINE_CASES.items():
+        calls = gs.draw_sequence(seed, cfg, **options)
+        assert calls == gs.draw_sequence(seed, cfg, **options)
+        assert cfg["op"] == hm.GALERKIN and cfg["finest_level"] <= 8 and (cfg["coarsest_level"] <= 4 or cfg["bottom"] == hm.SMOOTH)
+        gcr = options.get("gcr", False)
+        gs.assert_nine_calls(calls, cfg, *options["operators"], krylov=gcr)
+        if options.get("cycles"):
+            gs.assert_cycle_calls(calls, cfg)
+        if gcr:
+            gs.assert_gcr_calls(calls, cfg, False, options.get("deep_iters", 9))
+            assert gs.graph_users(calls) == gs.GCR_USERS
+            orders.add(gs.krylov_order(calls))
+        else:
+            assert not any(c[0] == "solve_gcr" for c in calls)
+        # every operator of a sequence that holds solve_pcg is symmetric
+        assert "random9" not in [c[1] for c in calls if c[0] == "set_operator"] and not any(c[0] in ("set_stencil9", "set_stencil") for c in calls)
+    assert orders == {"pcg", "gcr"}
+    n = gs.NINE_CASES
+    assert [c[1] for c in gs.draw_sequence(n["galerkin_f64_jacobi_7_3_nine_cycles"][1], n["galerkin_f64_jacobi_7_3_nine_cycles"][0],
+                                           **n["galerkin_f64_jacobi_7_3_nine_cycles"][3]) if c[0] == "set_operator"] == ["rot45", "smooth9", "jump9"]
+    assert n["galerkin_f64_sgs_7_3_nine_gcr"][0]["mu1"] == n["galerkin_f64_sgs_7_3_nine_gcr"][0]["mu2"] == 1      # the reverse blocks exist
+    c = n["galerkin_f64_gs_8_5_nine_gcr"][0]
+    assert (c["mu1"], c["mu2"], c["bottom"]) == (1, 0, hm.SMOOTH)
+    # the list written by hand
+    calls = list(gs.RANDOM9_CALLS)
+    at = gs.flips(calls)
+    assert [gs.point_counts(calls)[i] for i in at] == [5, 9] and not any(c[0] == "solve_pcg" for c in calls)
+    for part in (calls[:at[0]], calls[at[0]:at[1]], calls[at[1]:]):
+        assert {"solve", "solve_gcr"} <= {c[0] for c in part}
+    assert calls[at[1]] == ("set_stencil9", "random9_ring")
+
+
+def walk(po, cfg, calls):
+    """the model alone through a sequence: every array of every level finite after every call; the lowest last / first
+    history entry of a Krylov call"""
+    m = hm.HandleModel(po, **cfg)
+    L = cfg["finest_level"]
+    lowest = (1.0, None)
+    for i, call in enumerate(calls):
+        out = gs.apply_model(m, call, L)
+        for lv in m.levels():
+            assert np.isfinite(m.U[lv]).all() and np.isfinite(m.B[lv]).all(), (i, call, lv)
+        if call[0] in gs.SOLVES:
+            assert np.isfinite(out[1]).all(), (i, call)
+        if call[0] in gs.KRYLOV and out[1][-1] / out[1][0] < lowest[0]:
+            lowest = (float(out[1][-1] / out[1][0]), (i, call))
+    return lowest
+
+
+NEW_SEQUENCES = ([(name, c[0], c[1], c[3]) for d in (gs.COLOUR_CASES, gs.NINE_CASES) for name, c in d.items()]
+                 + [("random9_" + k, dict(finest_level=6, coarsest_level=3, mu0=0, mu1=1, mu2=1, schedule=hm.V, op=hm.GALERKIN, smoother=s), None, None)
+                    for k, s in (("gs", hm.COLOR_GS), ("jacobi", hm.JACOBI))])
+
+
+@pytest.mark.parametrize("name,cfg,seed,options", NEW_SEQUENCES, ids=[c[0] for c in NEW_SEQUENCES])
+def test_the_model_walks_the_colour_and_nine_sequences(po, name, cfg, seed, options):
+    """without a device.  Double: every Krylov call ends at or above 1e-6 of its first history entry, the condition RTOL64
+    rests on for the arrays such a call writes (test_the_gcr_sequences_meet_the_conditions_their_bounds_rest_on); float:
+    at or above 1e-3, where a scalar one float ulp off moves the last residual by 1e-7 / 1e-3 = 1e-4 of itself, a tenth of
+    PCG32_STATE.  The sequence is changed if this fails, never the bound"""
+    calls = list(gs.RANDOM9_CALLS) if seed is None else gs.draw_sequence(seed, cfg, **options)
+    lowest = walk(po, cfg, calls)
+    print(f"\n[handle-state] model alone: {name} steps={len(calls)} lowest last/first of a Krylov call={lowest[0]:.3g} at {lowest[1]}")
+    assert (1e-6 if cfg.get("dtype", hm.F64) == hm.F64 else 1e-3) <= lowest[0] < 1.0, lowest
