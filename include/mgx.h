@@ -458,6 +458,34 @@ MGX_API int mgx_solve_pcg(mgx_handle h, double tol, int max_iters, mgx_stats* st
 MGX_API int mgx_solve_gcr(mgx_handle h, double tol, int max_iters, int restart, mgx_stats* stats,
                           double* history, int history_cap);
 
+/* Iterative refinement (defect correction) on the finest level of a general-operator handle: residual and iterate in
+ * fp64 around one cycle from zero of a FLOAT copy of the hierarchy (absent in the reference; what dtype MIXED is for
+ * the Poisson operator), run to ||r||_2 <= tol ||r0||_2 or max_cycles cycles:
+ *     u += s_k * M32( (b - A u) / s_k ),   s_k = 2^floor(log2( hist[max(k - 1, 0)] / n )),  n = 2^finest_level - 1,
+ * M32 the cycle mgx_vcycle_zero runs on an F32 handle (every smoother, the cycle kind of mgx_set_cycle, either transfer,
+ * either bottom, a five- or nine-point finest level), the scaling by a power of two exact.  Per cycle one fp64 pass
+ * (k_refine_pass: the update, the residual of the new iterate, its norm and the scaled float residual; 72 B per point
+ * on a five-point, 104 B on a nine-point finest level) and the float cycle, at about half the bytes of the fp64 one.
+ * The contract of mgx_solve_pcg: starts from the current U; on return U holds the fp64 iterate and B the caller's b,
+ * bit for bit; history[0] = ||b - A u0||, then the TRUE fp64 residual norm after each cycle; stats as for mgx_solve,
+ * stats->cycles = history_len - 1, fine_updates those of the float cycle; max_cycles = 0 writes one history entry and
+ * leaves U alone.  cfg.schedule is ignored.  Deterministic (fixed-order reductions, no atomics; graph replay and
+ * MGX_GRAPH=0 give the same bits).  The handle's own mgx_solve / mgx_vcycle / mgx_solve_pcg / mgx_solve_gcr compute,
+ * before and after a call, the bits of a handle that never refined.
+ * The float copy: the first call creates, inside the handle, an F32 solver of the same cfg and knobs on the handle's
+ * stream (it does not read the environment again; cfg.profile does not extend to it) - about half the device memory
+ * the handle already holds, freed by mgx_destroy.  Its operator is the handle's, rounded once to float on the device:
+ * the five coefficient grids of every level (STENCIL5), or the finest level's five or nine grids, the coarse operators
+ * then built in float with the handle's transfer (GALERKIN); splittings, lambda bounds, line factors and the dense
+ * bottom inverse come from the F32 build - bit for bit what a public F32 handle holds after mgx_set_stencil /
+ * mgx_set_stencil9 (and mgx_build_galerkin_transfer) with the float32 of the handle's coefficients.  It is rebuilt by
+ * the next call after the handle's operator or hierarchy has changed; mgx_set_cycle reaches it at once.
+ * Single-GPU handles of dtype F64, op STENCIL5 or GALERKIN.  MGX_ERR_STATE (reason in mgx_last_error) on POISSON handles
+ * (use dtype MIXED), F32 and MIXED handles, multi-GPU and rank handles and before the operators are set / built;
+ * MGX_ERR_INVALID for tol not >= 0 or max_cycles < 0; MGX_ERR_ALLOC when the float copy cannot be allocated, and the
+ * F32 build's error when its line factors break down in float - the fp64 state stays usable in both cases. */
+MGX_API int mgx_solve_refine(mgx_handle h, double tol, int max_cycles, mgx_stats* stats, double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -488,6 +516,12 @@ MGX_API int mgx_time_smoother(mgx_handle h, int sweeps, double* ms);
  * call with restart > j has allocated the basis. */
 enum { MGX_GCR_PASS_UPDATE = 0, MGX_GCR_PASS_DOTS = 1, MGX_GCR_PASS_ORTH = 2, MGX_GCR_PASS_DIRECTION = 3 };
 MGX_API int mgx_time_gcr_pass(mgx_handle h, int pass, int j, int repeats, double* ms);
+/* ms per launch of the fp64 update + residual pass of mgx_solve_refine (k_refine_pass<NQ, true> and its k_reduce_partials)
+ * on the handle's own buffers, `repeats` launches between two events (tools/refine_bench.py).  Scale 0, and the updated
+ * iterate stays in the scratch grid: U and B are unchanged bit for bit; the float residual of the shadow is rewritten (it has
+ * no meaning between two mgx_solve_refine calls).  MGX_ERR_STATE where mgx_solve_refine is, and until a mgx_solve_refine
+ * call has created the float copy; MGX_ERR_INVALID for repeats < 1. */
+MGX_API int mgx_time_refine_pass(mgx_handle h, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

@@ -55,7 +55,7 @@ EXPORTS = [
     "mgx_set_stencil", "mgx_set_coefficient", "mgx_get_stencil", "mgx_solve_pcg", "mgx_solve_gcr", "mgx_time_gcr_pass",
     "mgx_build_galerkin", "mgx_get_stencil9", "mgx_set_stencil9", "mgx_set_tensor",
     "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max", "mgx_get_line_factor", "mgx_get_line_chunks",
-    "mgx_set_cycle", "mgx_get_cycle",
+    "mgx_set_cycle", "mgx_get_cycle", "mgx_solve_refine", "mgx_time_refine_pass",
 ]
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
@@ -173,6 +173,8 @@ def lib() -> C.CDLL:
     L.mgx_solve.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_solve_pcg.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_solve_gcr.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(Stats), dp, C.c_int]
+    L.mgx_solve_refine.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
+    L.mgx_time_refine_pass.argtypes = [vp, C.c_int, dp]
     L.mgx_profile_get.argtypes = [vp, C.POINTER(Profile)]
     L.mgx_time_smoother.argtypes = [vp, C.c_int, dp]
     L.mgx_time_gcr_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
@@ -624,6 +626,16 @@ class Multigrid:
                                       hist.size), "mgx_solve_gcr")
         return st, hist[: st.history_len].copy()
 
+    def solve_refine(self, tol=1e-8, max_cycles=50):
+        """iterative refinement of a general-operator F64 handle: the fp64 residual and iterate around one cycle from
+        zero of a float copy of the hierarchy (mgx_solve_refine), from the current guess; returns (stats, history of the
+        true fp64 residual norm) as solve() does."""
+        st = Stats()
+        hist = np.zeros(max(max_cycles, 0) + 1, dtype=np.float64)
+        self._chk(lib().mgx_solve_refine(self._h, tol, max_cycles, C.byref(st), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                         hist.size), "mgx_solve_refine")
+        return st, hist[: st.history_len].copy()
+
     # -- measurement -----------------------------------------------------------------
     def profile_reset(self):
         self._chk(lib().mgx_profile_reset(self._h), "mgx_profile_reset")
@@ -643,6 +655,13 @@ class Multigrid:
         3 k_pcg_direction; after a solve_gcr with restart > j"""
         ms = C.c_double()
         self._chk(lib().mgx_time_gcr_pass(self._h, which, j, repeats, C.byref(ms)), "mgx_time_gcr_pass")
+        return ms.value
+
+    def time_refine_pass(self, repeats=20):
+        """ms per launch of solve_refine's fp64 update + residual pass (k_refine_pass) on the handle's own buffers, U and B
+        unchanged; after a solve_refine"""
+        ms = C.c_double()
+        self._chk(lib().mgx_time_refine_pass(self._h, repeats, C.byref(ms)), "mgx_time_refine_pass")
         return ms.value
 
     def graphs_cached(self):

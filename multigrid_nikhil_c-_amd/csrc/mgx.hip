@@ -10,6 +10,8 @@
 //   mgx_solve           PS:727 (main's call) / MF:193-197 multigrid_solver
 //   mgx_solve_pcg       (absent in the reference) CG preconditioned by one V-cycle, mgx_krylov.hpp
 //   mgx_solve_gcr       (absent in the reference) restarted GCR around one cycle, mgx_krylov.hpp
+//   mgx_solve_refine    (absent in the reference) fp64 defect correction around the cycle of a float copy of the
+//                       hierarchy, mgx_refine.hpp
 // There is no CPU fallback anywhere in this file.
 
 #include "../../include/mgx.h"
@@ -24,6 +26,7 @@
 #include "mgx_colour.hpp"
 #include "mgx_small.hpp"
 #include "mgx_krylov.hpp"
+#include "mgx_refine.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -154,6 +157,13 @@ struct mgx_solver {
         void free();
     } kry;
     struct mgx_dist* dist = nullptr; // multi-GPU handle (cfg.n_gpus > 1 / mgx_create_rank): mgx_dist.hpp; no levels of its own
+    // mgx_solve_refine: the float copy of a general-operator F64 handle's hierarchy, an F32 solver of the same cfg and
+    // knobs on the parent's stream (own_stream = false there), created by the first call.  op_gen counts the changes of
+    // the handle's operator or hierarchy (operator_changed); the shadow holds the operator of generation shadow_gen and
+    // is rebuilt when the two differ (< 0: never built)
+    mgx_solver* shadow = nullptr;
+    long long op_gen = 0, shadow_gen = -1;
+    bool own_stream = true;
 
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -375,6 +385,14 @@ void drop_graphs(mgx_solver* s)
     s->graphs.clear();
 }
 
+// the handle's operator or hierarchy is no longer what it was: captured cycles are cycles of the old problem, and the
+// float copy of mgx_solve_refine is stale
+void operator_changed(mgx_solver* s)
+{
+    ++s->op_gen;
+    drop_graphs(s);
+}
+
 template <typename T> Op9<T> op9_of(const Level& l)
 {
     Op9<T> o;
@@ -471,11 +489,11 @@ int var_build_t(mgx_solver* s, Level& l)
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipStreamSynchronize(s->stream));
     if (int rc = lambda_update(s, l)) return rc;
-    if (int rc = line_update(s, l)) { l.stencil_set = false; drop_graphs(s); return rc; }
+    if (int rc = line_update(s, l)) { l.stencil_set = false; operator_changed(s); return rc; }
     l.stencil_set = true;
     // the kernels' coefficient pointers are unchanged, but a new operator is a new problem, and the Chebyshev scalars
     // (from g_l) are kernel arguments of a captured cycle: recapture
-    drop_graphs(s);
+    operator_changed(s);
     return MGX_OK;
 }
 int var_build(mgx_solver* s, Level& l) { return l.f64 ? var_build_t<double>(s, l) : var_build_t<float>(s, l); }
@@ -539,13 +557,13 @@ int galerkin_build_t(mgx_solver* s, int transfer)
         if (int rc = line_update(s, s->lv[lv])) {             // as after a new finest operator: nothing below it is usable
             for (int c = lo; c < hi; ++c) s->lv[c].stencil_set = false;
             s->gal_built = false;
-            drop_graphs(s);
+            operator_changed(s);
             return rc;
         }
     for (int lv = lo; lv <= hi; ++lv) s->lv[lv].stencil_set = true;
     s->gal_built = true;
     s->transfer = transfer;
-    drop_graphs(s);          // the buffers have not moved, but a new hierarchy (or another P) is a new problem: recapture
+    operator_changed(s);     // the buffers have not moved, but a new hierarchy (or another P) is a new problem: recapture
     return MGX_OK;
 }
 
@@ -555,7 +573,7 @@ void galerkin_invalidate(mgx_solver* s)
     for (int lv = s->cfg.coarsest_level; lv < s->cfg.finest_level; ++lv) s->lv[lv].stencil_set = false;
     s->lv[s->cfg.finest_level].stencil_set = true;
     s->gal_built = false;
-    drop_graphs(s);
+    operator_changed(s);
 }
 
 // every level's operator must have been given before a schedule or operator runs
@@ -1363,7 +1381,9 @@ long mgx_level_pitch(int level, int dtype)
     return level_pitch(level, dtype);
 }
 
-int mgx_create(const mgx_config* cfg, mgx_handle* out)
+// mgx_create.  like (may be null): the handle whose float copy this one is (mgx_solve_refine) - its stream and its knobs
+// instead of a stream of its own and the environment's
+static int create_solver(const mgx_config* cfg, const mgx_solver* like, mgx_handle* out)
 {
     if (!cfg || !out) { g_create_error = "null argument"; return MGX_ERR_INVALID; }
     *out = nullptr;
@@ -1429,19 +1449,20 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     s->var = var;
     s->galerkin = galerkin;
     s->work_f64 = (cfg->dtype == MGX_DTYPE_F64);
-    s->rows_per_chunk = env_int("MGX_ROWS", 0);
-    s->fuse = fuse_cfg();
+    s->rows_per_chunk = like ? like->rows_per_chunk : env_int("MGX_ROWS", 0);
+    s->fuse = like ? like->fuse : fuse_cfg();
     s->fuse.arith = cfg->arith;
-    s->fold = env_int("MGX_FOLD", 1);
-    s->use_zero_in = env_int("MGX_ZERO_IN", 1);
-    s->use_graph = env_int("MGX_GRAPH", 1);
-    s->small_visit = env_int("MGX_SMALL_VISIT", 1);
+    s->fold = like ? like->fold : env_int("MGX_FOLD", 1);
+    s->use_zero_in = like ? like->use_zero_in : env_int("MGX_ZERO_IN", 1);
+    s->use_graph = like ? like->use_graph : env_int("MGX_GRAPH", 1);
+    s->small_visit = like ? like->small_visit : env_int("MGX_SMALL_VISIT", 1);
     s->colour = cfg->smoother == MGX_SMOOTHER_COLOR_GS ? 1 : cfg->smoother == MGX_SMOOTHER_COLOR_SGS ? 2 : 0;
-    s->gs_fused = env_int("MGX_GS_FUSED", 1);
+    s->gs_fused = like ? like->gs_fused : env_int("MGX_GS_FUSED", 1);
     s->line_dirs = cfg->smoother == MGX_SMOOTHER_LINE_X ? 1 : cfg->smoother == MGX_SMOOTHER_LINE_Y ? 2 : cfg->smoother == MGX_SMOOTHER_LINE_ALT ? 3 : 0;
     int rc = MGX_OK;
     auto bail = [&](int code) { g_create_error = s->err; mgx_destroy(s); return code; };
-    if (hipStreamCreate(&s->stream) != hipSuccess) { s->err = "hipStreamCreate failed"; return bail(MGX_ERR_HIP); }
+    if (like) { s->stream = like->stream; s->own_stream = false; }
+    else if (hipStreamCreate(&s->stream) != hipSuccess) { s->err = "hipStreamCreate failed"; return bail(MGX_ERR_HIP); }
     s->lv.resize(cfg->finest_level + 1);
     for (int l = cfg->coarsest_level; l <= cfg->finest_level; ++l)
         if ((rc = alloc_level(s, s->lv[l], l, s->work_f64)) != MGX_OK) return bail(rc);
@@ -1473,7 +1494,7 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
                 // the line factors; zeroed once: their ring and padding are never written.  hf / hb: k_line_y's levels of
                 // more than one chunk only (MGX_LINE_CHUNK=<rows> overrides the launcher's rows per chunk)
                 Level& lv = s->lv[l];
-                lv.line_R = line_chunk_rows(lv.N, env_int("MGX_LINE_CHUNK", 0));
+                lv.line_R = like ? like->lv[l].line_R : line_chunk_rows(lv.N, env_int("MGX_LINE_CHUNK", 0));
                 std::vector<void**> arrays;
                 for (int d = 0; d < 2; ++d)
                     if (s->line_dirs & (1 << d)) { arrays.push_back(&lv.line_m[d]); arrays.push_back(&lv.line_g[d]); }
@@ -1494,7 +1515,7 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
             }
         }
     }
-    s->mixed_fuse = env_int("MGX_MIXED_FUSE", 1);
+    s->mixed_fuse = like ? like->mixed_fuse : env_int("MGX_MIXED_FUSE", 1);
     // fine64.tmp: the out-of-place target of the fused update + residual pass
     if (s->mixed && !s->mixed_fuse) { (void)hipFree(s->fine64.tmp); s->fine64.tmp = nullptr; }
     // partial sums: the largest launch any norm kernel can make on the finest level
@@ -1525,9 +1546,12 @@ int mgx_create(const mgx_config* cfg, mgx_handle* out)
     return MGX_OK;
 }
 
+int mgx_create(const mgx_config* cfg, mgx_handle* out) { return create_solver(cfg, nullptr, out); }
+
 int mgx_destroy(mgx_handle s)
 {
     if (!s) return MGX_OK;
+    if (s->shadow) { mgx_destroy(s->shadow); s->shadow = nullptr; }
     if (s->dist) { dist_free(s->dist); s->dist = nullptr; }
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     for (auto& l : s->lv) free_level(l);
@@ -1542,7 +1566,7 @@ int mgx_destroy(mgx_handle s)
     drop_graphs(s);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+    if (s->stream && s->own_stream) (void)hipStreamDestroy(s->stream);
     delete s;
     return MGX_OK;
 }
@@ -2037,6 +2061,7 @@ int mgx_set_cycle(mgx_handle s, int cycle)
                                       "MGX_OPERATOR_STENCIL5 and MGX_OPERATOR_GALERKIN");
     drop_graphs(s);                                           // a captured cycle is a cycle of the old kind: recapture
     s->cycle = cycle;
+    if (s->shadow) { drop_graphs(s->shadow); s->shadow->cycle = cycle; }      // mgx_solve_refine's float cycle: the same kind
     return MGX_OK;
 }
 
@@ -2209,6 +2234,150 @@ int mgx_time_gcr_pass(mgx_handle s, int pass, int j, int repeats, double* ms)
         if (!s->kry.Z[i] || !s->kry.Q[i] || !s->kry.x || !s->kry.sc)
             return s->fail(MGX_ERR_STATE, "mgx_time_gcr_pass: call mgx_solve_gcr with restart > j first (it allocates the basis)");
     return s->work_f64 ? gcr_time_pass<double>(s, pass, j, repeats, ms) : gcr_time_pass<float>(s, pass, j, repeats, ms);
+}
+
+// ---- mgx_solve_refine: fp64 defect correction around the cycle of a float copy of the hierarchy ---------------
+// which handles refine (the message names the reason); then the operators must be set / built
+static int refine_guard(mgx_solver* s, const char* fn)
+{
+    NO_DIST(s)
+    if (!s->var)
+        return s->fail(MGX_ERR_STATE, std::string(fn) + ": op = MGX_OPERATOR_POISSON handles refine with dtype MIXED (use dtype MIXED and mgx_solve); "
+                                                        "this entry point is for MGX_OPERATOR_STENCIL5 and MGX_OPERATOR_GALERKIN");
+    if (s->mixed || !s->work_f64)
+        return s->fail(MGX_ERR_STATE, std::string(fn) + ": dtype F64 handles only (the float cycle runs in a copy of the hierarchy inside the handle)");
+    return MGX_OK;
+}
+
+// the whole grids of slots 0 .. nq - 1 of the operator of level lv, rounded to float into the shadow's
+static int refine_round_level(mgx_solver* s, int lv, int nq)
+{
+    const Level& d = s->lv[lv];
+    const Level& w = s->shadow->lv[lv];
+    const dim3 blk(256), grd((unsigned)((d.pitch + 255) / 256), d.rows);
+    for (int q = 0; q < nq; ++q)
+        hipLaunchKernelGGL(k_grid_f64_to_f32, grd, blk, 0, s->stream, (const double*)d.A[q], (float*)w.A[q], d.pitch, w.pitch);
+    HIPCHK(s, hipGetLastError());
+    return MGX_OK;
+}
+
+// The shadow exists and holds the float32 of the handle's current operator: what a public F32 handle of the same cfg
+// holds after mgx_set_stencil on every level (STENCIL5), or after mgx_set_stencil / mgx_set_stencil9 on the finest level
+// and mgx_build_galerkin_transfer with the parent's transfer (GALERKIN) - its splittings, lambda bounds, line factors
+// and dense bottom inverse come from those build paths in float.  A failure (allocation; a breakdown of the float
+// line factors) is returned with the F32 build's message and leaves the fp64 handle as it was; the next call tries again
+static int refine_shadow(mgx_solver* s)
+{
+    if (!s->shadow) {
+        mgx_config c = s->cfg;
+        c.dtype = MGX_DTYPE_F32;
+        c.profile = 0;                                        // (the float cycle is not timed span by span: one graph replay)
+        mgx_handle sh = nullptr;
+        if (int rc = create_solver(&c, s, &sh)) return s->fail(rc, "mgx_solve_refine: float copy of the hierarchy: " + g_create_error);
+        sh->cycle = s->cycle;
+        s->shadow = sh;
+        s->shadow_gen = -1;
+    }
+    if (s->shadow_gen == s->op_gen) return MGX_OK;
+    mgx_solver* f = s->shadow;
+    const int lo = s->cfg.coarsest_level, hi = s->cfg.finest_level;
+    auto failed = [&](int rc) { return s->fail(rc, "mgx_solve_refine: float copy of the hierarchy: " + f->err); };
+    s->shadow_gen = -1;
+    if (s->galerkin) {
+        const bool nine = s->lv[hi].nine;
+        if (nine)
+            if (int rc = finest_corners(f, f->lv[hi])) return failed(rc);
+        if (int rc = refine_round_level(s, hi, nine ? 9 : 5)) return rc;
+        f->lv[hi].nine = nine;
+        galerkin_invalidate(f);
+        if (int rc = galerkin_build_t<float>(f, s->transfer)) return failed(rc);
+    } else {
+        for (int lv = lo; lv <= hi; ++lv) {
+            if (int rc = refine_round_level(s, lv, 5)) return rc;
+            if (int rc = var_build(f, f->lv[lv])) return failed(rc);
+        }
+    }
+    s->shadow_gen = s->op_gen;
+    return MGX_OK;
+}
+
+// one launch of k_refine_pass on the finest level, u -> tmp (has_e) with r32 into the shadow's right-hand side, and
+// the sum of its partials into sum_dev; the caller swaps u and tmp
+static void refine_pass(mgx_solver* s, bool has_e, double scale, double inv_scale)
+{
+    const Level& d = s->lv[s->cfg.finest_level];
+    const Level& w = s->shadow->lv[s->cfg.finest_level];
+    with_point_count(d.nine, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        const auto launch = has_e ? launch_refine_pass<NQ, true> : launch_refine_pass<NQ, false>;
+        const int nb = launch((const double*)d.u, (const float*)w.u, (const double*)d.b, op9_of<double>(d), (double*)d.tmp, (float*)w.b, scale,
+                              inv_scale, s->partial, s->partial_cap, d.N, d.pitch, w.pitch, s->rows_per_chunk, s->stream);
+        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, s->partial, nb, s->sum_dev);
+    });
+}
+
+int mgx_solve_refine(mgx_handle s, double tol, int max_cycles, mgx_stats* stats, double* history, int history_cap)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (int rc = refine_guard(s, "mgx_solve_refine")) return rc;
+    if (max_cycles < 0 || !(tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_solve_refine: tol >= 0 and max_cycles >= 0 required");
+    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
+    if (int rc = refine_shadow(s)) return rc;
+    mgx_solver* f = s->shadow;
+    Level& d = s->lv[s->cfg.finest_level];
+    const double n = (double)(d.N - 1);
+    std::vector<double> hist;
+    hist.reserve(max_cycles + 1);
+    s->fine_updates = 0.0;
+    f->fine_updates = 0.0;
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    double r = 0.0;
+    if (int rc = residual_norm_grid(s, d, d.u, d.b, &r, MGX_PROF_NORM_FINE)) return rc;
+    hist.push_back(r);
+    int k = 0;
+    for (k = 0; k < max_cycles; ++k) {
+        if (hist[k] <= tol * hist[0]) break;
+        // s_k: a power of two near the rms of the residual the float cycle is given (exact scaling, the rule of dtype MIXED)
+        const double scale = pow2_floor(hist[k > 0 ? k - 1 : 0] / n);
+        if (k == 0) {
+            // no scaled residual is pending yet: produce it now
+            Prof p(s, MGX_PROF_NORM_FINE, 2);
+            refine_pass(s, false, 0.0, 1.0 / scale);
+        }
+        double unused = 0.0;
+        if (int rc = cycle_body(f, false, true, &unused)) return s->fail(rc, "mgx_solve_refine: float cycle: " + f->err);    // e = M32 r32 from zero
+        {
+            // u += s_k e, the residual of the new iterate (its norm is hist[k + 1]) and the float residual the next cycle
+            // consumes, scaled by the power of two derived from hist[k] (known now): one out-of-place pass
+            Prof p(s, MGX_PROF_NORM_FINE, 2);
+            refine_pass(s, true, scale, 1.0 / pow2_floor(hist[k] / n));
+            std::swap(d.u, d.tmp);
+        }
+        HIPCHK(s, hipMemcpyAsync(s->sum_host, s->sum_dev, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(s, hipStreamSynchronize(s->stream));
+        hist.push_back(std::sqrt(*s->sum_host));
+    }
+    s->norm_blocks_ready = 0;                                 // partial[] holds this pass's sums, not a smoothing block's
+    HIPCHK(s, hipGetLastError());
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    finish_solve(stats, history, history_cap, hist, k, hist.back() <= tol * hist.front(), t0, f->fine_updates);
+    return MGX_OK;
+}
+
+int mgx_time_refine_pass(mgx_handle s, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!ms || repeats < 1) return s->fail(MGX_ERR_INVALID, "mgx_time_refine_pass: repeats >= 1 required");
+    if (int rc = refine_guard(s, "mgx_time_refine_pass")) return rc;
+    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
+    if (!s->shadow) return s->fail(MGX_ERR_STATE, "mgx_time_refine_pass: call mgx_solve_refine first (it creates the float copy of the hierarchy)");
+    // scale 0, and the updated iterate stays in tmp (no swap): U and B are unchanged; the shadow's right-hand side is
+    // rewritten (it has no meaning between two mgx_solve_refine calls)
+    const int rc = time_on_stream(s, ms, [&] { for (int i = 0; i < repeats; ++i) refine_pass(s, true, 0.0, 1.0); });
+    s->norm_blocks_ready = 0;
+    if (rc == MGX_OK) *ms /= repeats;
+    return rc;
 }
 
 // ---- measurement ------------------------------------------------------------------------
