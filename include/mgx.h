@@ -469,7 +469,8 @@ MGX_API int mgx_solve_gcr(mgx_handle h, double tol, int max_iters, int restart, 
  * The contract of mgx_solve_pcg: starts from the current U; on return U holds the fp64 iterate and B the caller's b,
  * bit for bit; history[0] = ||b - A u0||, then the TRUE fp64 residual norm after each cycle; stats as for mgx_solve,
  * stats->cycles = history_len - 1, fine_updates those of the float cycle; max_cycles = 0 writes one history entry and
- * leaves U alone.  cfg.schedule is ignored.  Deterministic (fixed-order reductions, no atomics; graph replay and
+ * leaves U alone.  U and B of the levels below the finest are left as they were (the cycle runs in the float copy).
+ * cfg.schedule is ignored.  Deterministic (fixed-order reductions, no atomics; graph replay and
  * MGX_GRAPH=0 give the same bits).  The handle's own mgx_solve / mgx_vcycle / mgx_solve_pcg / mgx_solve_gcr compute,
  * before and after a call, the bits of a handle that never refined.
  * The float copy: the first call creates, inside the handle, an F32 solver of the same cfg and knobs on the handle's

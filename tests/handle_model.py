@@ -29,7 +29,14 @@ bottom = SMOOTH visit; mgx_smooth itself is always forward.
 A GALERKIN handle takes a nine-point finest operator (set_stencil9, set_tensor): the hierarchies of tests/nine_ref.py
 (Jacobi, Chebyshev) and colour_ref's Nine* classes; a later set_stencil or set_coefficient makes the level five-point
 again.  The line smoothers on a nine-point finest level are not modelled (their tolerance rule is measured for
-five-point finest operators only): set_stencil9 / set_tensor refuse there with a ValueError."""
+five-point finest operators only): set_stencil9 / set_tensor refuse there with a ValueError.
+
+solve_refine (mgx_solve_refine) is tests/refine_ref.py's loop around the model's own fp64 residual and the zero-start
+cycle of a PRIVATE SECOND MODEL of dtype F32 with the same configuration and cycle index: the statement of
+include/mgx.h, "bit for bit what a public F32 handle holds after mgx_set_stencil / mgx_set_stencil9 (and
+mgx_build_galerkin_transfer) with the float32 of the handle's coefficients".  The float model is rebuilt by the next
+solve_refine after the operator, the hierarchy or the transfer has changed; set_cycle reaches it at once.  Only U of the
+finest level moves: the cycle runs on the float model's levels, the model's own coarse levels stay as they were."""
 import numpy as np
 
 import cheby_ref
@@ -40,6 +47,7 @@ import line_ref as lr
 import nine_ref as nr
 import opdep_ref as od
 import pcg_ref
+import refine_ref
 
 JACOBI, RBGS, CHEBYSHEV = 0, 1, 2
 LINE_X, LINE_Y, LINE_ALT = lr.LINE_X, lr.LINE_Y, lr.LINE_ALT
@@ -187,6 +195,8 @@ class HandleModel:
         self.stencils = None                   # STENCIL5: every level's operator
         self.transfer = None
         self.h = None
+        self.f32 = None                        # solve_refine: the float model, created by the first call ...
+        self.f32_of = None                     # ... and the hierarchy (self.h at the time) whose float copy it holds
         if self.op == POISSON:
             self.h = PoissonOps(self.po, self.L, self.Lc, self.dt, c["restrict_mode"], c["omega"], c["smoother"], c["arith"])
 
@@ -346,6 +356,8 @@ class HandleModel:
         if kind not in (CYCLE_V, CYCLE_W, CYCLE_F):
             raise ValueError("MGX_ERR_INVALID")
         self.cycle = kind
+        if self.f32 is not None:
+            self.f32.cycle = kind
 
     # -- transfers of the current hierarchy --------------------------------------------------------------------
     def _R(self, level, r):
@@ -502,3 +514,69 @@ class HandleModel:
         self.U[self.L] = np.ascontiguousarray(x, dtype=self.dt)
         self.B[self.L] = b
         return dict(cycles=len(hist) - 1, converged=int(conv and not brk), fine_updates=self.fine_updates), hist
+
+    # -- mgx_solve_refine --------------------------------------------------------------------------------------
+    def _refine_guard(self):
+        """the handles include/mgx.h refuses (the device: MGX_ERR_STATE), and the line smoothers, which this model leaves
+        out: a device handle with a line smoother is held to a tolerance rule between the model in the working type and
+        in np.longdouble, not bit for bit, so a refine call there needs a long-double twin of the FLOAT model as well"""
+        if self.op == POISSON:
+            raise ValueError("mgx_solve_refine: op = POISSON handles refine with dtype MIXED")
+        if self.line:
+            raise ValueError("solve_refine under a line smoother is not modelled (it needs a long-double float twin)")
+        if self.cfg["dtype"] != F64:
+            raise ValueError("mgx_solve_refine: dtype F64 handles only")
+        if self.h is None:
+            raise ValueError("mgx_solve_refine: operators not set / hierarchy not built")
+
+    def _float_model(self):
+        """the float copy of the hierarchy as include/mgx.h states it: an F32 model of the same configuration and cycle
+        index, given the float32 of the five coefficient arrays of every level (STENCIL5), or of the finest level's five or
+        nine arrays and then built in float with the transfer in use (GALERKIN)"""
+        if self.f32 is not None and self.f32_of is self.h:
+            return self.f32
+        f = HandleModel(self.oracle, **dict(self.cfg, dtype=F32))
+        f.cycle = self.cycle
+        if self.op == STENCIL5:
+            for lv in self.levels():
+                f.set_stencil(lv, [np.asarray(x, dtype=np.float32) for x in self.stencils[lv][:5]])
+        else:
+            if self.st9 is not None:
+                f.set_stencil9(self.L, [np.asarray(x, dtype=np.float32) for x in self.st9])
+            else:
+                f.set_stencil(self.L, [np.asarray(x, dtype=np.float32) for x in self.st5[:5]])
+            f.build_galerkin(self.transfer)
+        self.f32, self.f32_of = f, self.h
+        return f
+
+    def solve_refine(self, tol=1e-8, max_cycles=50, history=None):
+        """(stats, history): refine_ref.refine with the model's fp64 finest-level residual and the zero-start cycle of the
+        float model; fine_updates are the float cycle's.  U[finest] is the iterate afterwards, B and every other level are
+        untouched; max_cycles = 0: one history entry, U untouched.  history: the history a device returned for this
+        call - the scales s_k are then derived from IT (the norm is the only place where the device's order of summation
+        reaches the iterate); the stop decision and the history returned stay the model's own.
+        Not modelled: the line smoothers (ValueError, see _refine_guard)"""
+        self._refine_guard()
+        f = self._float_model()
+        f.fine_updates = 0.0
+        h, L = self.h, self.L
+
+        def cycle32(r32):
+            f.set_rhs(r32)
+            f.vcycle_zero()
+            return f.U[L]
+
+        u, hist = refine_ref.refine(lambda v, b: h.residual(L, v, b), cycle32, self.B[L], self.U[L], tol=tol, max_cycles=max_cycles,
+                                    norm=self.po.norm2, scales=history)
+        self.U[L] = np.ascontiguousarray(u, dtype=self.dt)
+        self.fine_updates = f.fine_updates
+        return dict(cycles=len(hist) - 1, converged=int(hist[-1] <= tol * hist[0]), fine_updates=self.fine_updates), hist
+
+    def time_refine_pass(self, repeats):
+        """mgx_time_refine_pass: nothing moves.  Refused where solve_refine is, and until a solve_refine has created the
+        float model (the device: MGX_ERR_STATE)"""
+        self._refine_guard()
+        if repeats < 1:
+            raise ValueError("MGX_ERR_INVALID")
+        if self.f32 is None:
+            raise ValueError("mgx_time_refine_pass: call mgx_solve_refine first")

@@ -25,11 +25,13 @@ def norm2(r):
     return float(np.sqrt(np.sum(np.asarray(r, dtype=np.float64) ** 2)))
 
 
-def refine(residual, cycle, b, u0, tol=0.0, max_cycles=50, history=None, norm=norm2):
+def refine(residual, cycle, b, u0, tol=0.0, max_cycles=50, history=None, norm=norm2, scales=None):
     """(u, history of ||b - A u||).  residual(u, b) -> float64 array; cycle(r32) -> float32 array, the correction of one
     cycle from zero for the float32 right-hand side r32.  history = None: the scales come from this loop's own norms
     and it stops at hist[k] <= tol * hist[0] or after max_cycles cycles; history given (len = cycles + 1): that many
-    cycles with the scales derived from IT, as a device that reported it has used them."""
+    cycles with the scales derived from IT, as a device that reported it has used them.  scales (a history, with
+    history = None): the loop stops by its own norms, and s_k is derived from scales[max(k - 1, 0)] where that entry
+    exists, from its own history where it does not."""
     b = np.ascontiguousarray(b, dtype=np.float64)
     u = np.array(u0, dtype=np.float64, order="C")
     n = b.shape[0]
@@ -40,7 +42,10 @@ def refine(residual, cycle, b, u0, tol=0.0, max_cycles=50, history=None, norm=no
     for k in range(cycles):
         if given is None and hist[k] <= tol * hist[0]:
             break
-        s = scale(hist if given is None else given, k, n)
+        src = hist if given is None else given
+        if given is None and scales is not None and max(k - 1, 0) < len(scales):
+            src = scales
+        s = scale(src, k, n)
         r32 = (r / s).astype(np.float32)
         e = np.asarray(cycle(r32))
         assert e.dtype == np.float32

@@ -104,6 +104,34 @@ gcr 2.4e-6 / 2.7e-6 / 5.6e-5; random9 - / 6.3e-7 / 2.3e-4 (gs), - / 2.5e-7 / 3.0
 4e-13, state bit for bit.  The runs under MGX_SMALL_VISIT=0 and MGX_GS_FUSED=0 give the same figures to the digit.  The
 dense coarsest solve stays bit for bit under these operators at levels 3 and 4.
 
+REFINE_CASES add mgx_solve_refine (csrc/mgx.hip, csrc/mgx_refine.hpp) as one more graph user, drawn with refine=True
+(refine_stage; what it promises: draw_sequence).  The call hides more state in a handle than any before it: a second solver
+(the float copy of the hierarchy, on the parent's stream, with a graph cache of its own) that is rebuilt lazily when the
+parent's operator generation has moved and is told the cycle kind by hand; one u <-> tmp swap of the finest level per cycle
+under the parent's graph key; and the pass's sums in the partial-sum buffer and the scalar that mgx_solve, mgx_solve_pcg and
+mgx_solve_gcr use.  The model (handle_model.HandleModel.solve_refine) keeps a private F32 model beside itself and takes the
+scales s_k from the history the device returned; U and B of EVERY level are compared bit for bit after the call - so the
+parent's coarse levels are held untouched, which include/mgx.h states - the history through the solve branch of
+history_check (the same residual bits, another order of the sum), the statistics for equality.
+stencil5_f64_jacobi_8_5_refine and stencil5_f64_chebyshev_8_5_refine (V(3,2); set_coefficient 100 and 1000 rewrite every level of
+the float copy; the Chebyshev bounds of the float cycle are arguments of its captured kernels; the float dense solve at level 5
+is held by GENERAL_CASES' stencil5_f32_chebyshev); galerkin_f64_jacobi_7_3_refine_cycles (set_cycle through CYCLE_ORDER, two
+transfer-only rebuilds between refines; a second and third time with MGX_SMALL_VISIT=0 and with MGX_GRAPH=0: the same final
+state and histories, the float copy takes the parent's knobs); galerkin_f64_sgs_7_3_nine_refine (rot45 -> set_coefficient ->
+smooth9; again with MGX_GS_FUSED=0); galerkin_f64_gs_8_5_smooth_bottom_refine_gcr (V(1,0), refine between Krylov calls on the
+shared workspace).  The three GALERKIN cases use bottom = SMOOTH: no F32 sequence holds the float dense solve of a GALERKIN
+hierarchy against the model.  The sequences are 60, 60, 83, 61 and 67 calls long with 9, 9, 13, 9 and 12 refines (n_steps = 30:
+the mandatory calls alone, data, graph users, operator changes, set_cycle and the refine stage, come to more than fifty).
+Both STENCIL5 cases fill the graph cache (8 graphs; the odd swaps add buffer assignments) and run their last calls through the
+eager fallback; the GALERKIN cases reach 4.  On the CPU, the model alone (tests/test_handle_model.py::
+test_the_model_walks_the_refine_sequences): every refine history decreases over its call - from the set_coefficient 1000 of
+the STENCIL5 cases on, whose re-discretised hierarchy DIVERGES under V(3,2) after a first cycle, by construction of the
+sequence (refine_stage) - and the lowest last / first entry of a Krylov call is 1.0e-3, 2.6e-2, 5.5e-4, 1.2e-3, 1.3e-4.
+Measured on an MI355X, largest deviation as a fraction of its bound, history of solve_refine / of solve_pcg / written state
+after solve_pcg, in the order above: 2.1e-6 / 3.7e-6 / 2.1e-5; 1.3e-6 / 8.3e-6 / 1.7e-5; 1.9e-6 / 1.0e-5 / 1.5e-4; 1.5e-6 / 4.5e-6 /
+5.2e-6; 2.0e-6 / 2.2e-6 / 8.3e-7 (solve_gcr there: 2.8e-6 / 1.3e-4); mgx_solve's histories at most 2.2e-6.  The runs under
+MGX_SMALL_VISIT=0, MGX_GRAPH=0 and MGX_GS_FUSED=0 give the same figures to the digit.
+
 A failing sequence is reproduced from the seed, the step index and the calls so far, which the message carries."""
 import numpy as np
 import pytest
@@ -126,8 +154,9 @@ K_MAX_GRAPHS = 8                           # kMaxGraphs of csrc/mgx.hip: the cap
 MUS = (0, 1, 2, 3, 5)
 GRAPH_USERS = ("solve", "solve_pcg", "vcycle_zero")
 GCR_USERS = GRAPH_USERS + ("solve_gcr",)     # the sequences drawn with gcr=True
-SOLVES = ("solve", "solve_pcg", "solve_gcr")  # the calls that return (stats, history)
+SOLVES = ("solve", "solve_pcg", "solve_gcr", "solve_refine")  # the calls that return (stats, history)
 KRYLOV = ("solve_pcg", "solve_gcr")
+OPERATOR_CHANGES = ("set_coefficient", "build_galerkin", "set_stencil", "set_stencil9", "set_tensor", "set_operator")
 GCR_RESTARTS = (1, 2, 3)
 DEEP_GCR = ("solve_gcr", 0.0, 9, 8)          # nine iterations of GCR(8): every slot of the full basis, then slot 0 again
 KNOBS = ("MGX_TILE_MAX_N", "MGX_FUSE_MIN_N", "MGX_PLAN_MIN_N", "MGX_PLAN_PRE", "MGX_PLAN_POST", "MGX_GRAPH", "MGX_FOLD", "MGX_FUSE",
@@ -172,10 +201,100 @@ def kinds_at(calls):
 
 def graph_users(calls):
     """the kinds of graph user a drawn list holds each five times at least"""
-    return GCR_USERS if any(c[0] == "solve_gcr" for c in calls) else GRAPH_USERS
+    users = GCR_USERS if any(c[0] == "solve_gcr" for c in calls) else GRAPH_USERS
+    return users + ("solve_refine",) if any(c[0] == "solve_refine" for c in calls) else users
 
 
-def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_guess=False, short_solves=False, without=(), tail=(), gcr=False, deep_iters=DEEP_GCR[2]):
+def refine_stage(seed, cfg, out, gcr):
+    """draw_sequence(refine=True): ("solve_refine", tol, max_cycles) and one ("time_refine_pass", 2) placed INTO a drawn list,
+    with a generator of its own (the draws of the list itself are untouched).  The list is cut into spans that stay
+    together, and whole spans are put between spans, so every promise of draw_sequence's docstring holds by
+    construction.  A ("set_guess", seed) stands before a refine wherever the promise does not forbid it: the iterate
+    then never sits at the rounding floor of b - A u, where a history cannot decrease"""
+    rng = np.random.RandomState(seed + 55555)
+    L, Lc = cfg["finest_level"], cfg["coarsest_level"]
+    fresh = [0]
+
+    def refine(k=None, tol=None, guess=True):
+        k = int(rng.randint(1, 5)) if k is None else k
+        tol = float(rng.choice([0.0, 1e-3])) if tol is None else tol
+        fresh[0] += 1
+        return ([("set_guess", 4000 + fresh[0])] if guess else []) + [("solve_refine", tol, k)]
+
+    spans = []
+    for c in out:                                          # (a group of operator changes is one span: set_coefficient + build_galerkin)
+        if spans and c[0] in OPERATOR_CHANGES and spans[-1][-1][0] in OPERATOR_CHANGES:
+            spans[-1].append(c)
+        else:
+            spans.append([c])
+    at = lambda name: [i for i, s in enumerate(spans) if s[0][0] == name]
+    # (c), (d): three of the drawn solves, each with a refine directly before it - tol 0, so that the count is the cycles run
+    odd, even, timed = (int(i) for i in rng.choice(at("solve"), 3, replace=False))
+    spans[odd] = refine(int(rng.choice([1, 3])), 0.0) + spans[odd]
+    spans[even] = refine(int(rng.choice([2, 4])), 0.0) + spans[even]
+    spans[timed] = refine() + [("time_refine_pass", 2)] + spans[timed]
+    # (e): a drawn solve_pcg and a drawn solve_gcr (not the deep one: a fresh guess stands before that) directly after a refine
+    for name in KRYLOV if gcr else KRYLOV[:1]:
+        i = int(rng.choice([i for i in at(name) if len(spans[i][0]) < 4 or spans[i][0][3] != DEEP_GCR[3]]))
+        spans[i] = refine(int(rng.choice([1, 2])), 0.0) + spans[i]
+    # (a): after every group of operator changes, and after a set_cycle that directly follows it; (b): after two more set_cycle
+    ends = [i for i, s in enumerate(spans) if s[0][0] in OPERATOR_CHANGES]
+    ends =[i + 1 if i + 1 < len(spans) and spans[i + 1][0][0] == "set_cycle" else i for i in ends]
+    others = [i for i in at("set_cycle") if i not in ends]
+    if others:
+        ends += [int(i) for i in rng.choice(others, 2, replace=False)]
+    for i in ends:
+        spans[i] = spans[i] + refine()
+    # (f): a cycle from a coarse level, a restriction of the finest residual and a correction of the finest U between two
+    # refines, the second one from what they left; and a call that runs no cycle
+    users = [i for i, s in enumerate(spans) if any(c[0] in GCR_USERS for c in s)]
+    coarse = int(rng.randint(Lc + 1, L)) if L - 1 > Lc else Lc
+    between = refine() + [("vcycle", coarse), ("restrict", L), ("prolong_add", L)] + refine(guess=False)
+    for extra in (between, refine(0, 1e-3, guess=False)):
+        spans.insert(int(rng.randint(users[0] + 1, users[-1] + 1)), extra)
+    # STENCIL5 with the contrast 1000: the cycle of the re-discretised hierarchy DIVERGES (the model alone, V(3,2), Jacobi and
+    # Chebyshev: the first cycle from a random guess reduces the residual to 2e-2 .. 4e-2, every later one multiplies it by 5
+    # to 20).  From that change on every refine that cycles starts from a fresh guess and runs one cycle for an odd, two for
+    # an even count, tol 0 - the histories then still decrease over the call
+    flat, diverging = [], False
+    for c in (c for s in spans for c in s):
+        diverging = diverging or (cfg.get("op") == hm.STENCIL5 and c[0] == "set_coefficient" and c[1] >= 1000.0)
+        if diverging and c[0] == "solve_refine" and c[2]:
+            flat += refine(2 - c[2] % 2, 0.0, guess=flat[-1][0] != "set_guess")
+        else:
+            flat.append(c)
+    return flat
+
+
+def assert_refine_calls(calls, cfg, gcr=False):
+    """what draw_sequence(refine=True) promises, on the drawn list"""
+    L = cfg["finest_level"]
+    users = [i for i, c in enumerate(calls) if c[0] in graph_users(calls)]
+    refines = [i for i, c in enumerate(calls) if c[0] == "solve_refine"]
+    assert "solve_refine" in graph_users(calls) and len(refines) >= 5
+    counts = [calls[i][2] for i in refines]
+    assert all(calls[i][1] in (0.0, 1e-3) and 0 <= calls[i][2] <= 4 for i in refines)
+    assert 0 in counts and any(k % 2 for k in counts) and any(k and k % 2 == 0 for k in counts), counts
+    timed = [i for i, c in enumerate(calls) if c[0] == "time_refine_pass"]
+    assert len(timed) == 1 and calls[timed[0]] == ("time_refine_pass", 2) and timed[0] > refines[0]
+    next_user = lambda i: next(calls[u][0] for u in users if u > i)
+    changes = [i for i in range(users[0], len(calls)) if calls[i][0] in OPERATOR_CHANGES]
+    assert changes and all(next_user(i) == "solve_refine" for i in changes)                                   # (a)
+    sets = [i for i, c in enumerate(calls) if c[0] == "set_cycle"]
+    assert not sets or sum(1 for i in sets if next_user(i) == "solve_refine") >= 2                             # (b)
+    follower = lambda i: calls[i + 1][0] if i + 1 < len(calls) else None
+    after = [calls[i][2] for i in refines if calls[i][1] == 0.0 and follower(i) == "solve"]
+    assert any(k % 2 for k in after) and any(k and k % 2 == 0 for k in after), after                          # (c)
+    assert follower(timed[0]) == "solve"                                                                       # (d)
+    for name in KRYLOV if gcr else KRYLOV[:1]:                                                                 # (e)
+        assert any(follower(i) == name for i in refines), name
+    assert any(len(calls) > i + 4 and calls[i + 1][0] == "vcycle" and calls[i + 1][1] < L and calls[i + 2] == ("restrict", L)
+               and calls[i + 3] == ("prolong_add", L) and [c[0] for c in calls[i + 4:i + 6] if c[0] != "set_guess"][:1] == ["solve_refine"]
+               for i in refines)                                                                               # (f)
+
+
+def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_guess=False, short_solves=False, without=(), tail=(), gcr=False, deep_iters=DEEP_GCR[2],
+                  refine=False):
     """~n_steps calls, every one valid for `cfg` by construction (nothing is filtered afterwards): the three graph
     users (four with gcr) five times each at least, an odd-launch smooth on every level at least once, the rest drawn with weights;
     mu from MUS.  Operator changes of the general hierarchies are placed after every third graph user.
@@ -196,7 +315,19 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
                  from GCR_RESTARTS (a call with max_iters > restart wraps the basis); the first one of the sequence with
                  restart 2; double: the last one becomes DEEP_GCR after a fresh ("set_guess", 3500) - the basis grows from
                  2 to 8 pairs on a handle the other graph users have run on
-    deep_iters   the iterations of that call, where nine take the iterate too far (the line case: see GCR_CASES)"""
+    deep_iters   the iterations of that call, where nine take the iterate too far (the line case: see GCR_CASES)
+    refine       ("solve_refine", tol, max_cycles) as one more graph user (refine_stage; dtype F64, general operators): five
+                 calls at least, tol 0 or 1e-3, max_cycles 0 .. 4 with 0, an odd and an even count among them, and one
+                 ("time_refine_pass", 2) after the first of them.  Held by construction (assert_refine_calls):
+                 (a) the next graph user after every operator change is a solve_refine (the float copy has to follow);
+                 (b) so it is after two set_cycle calls at least;
+                 (c) a solve directly follows a solve_refine, once after an odd and once after an even number of cycles
+                     (u <-> tmp swaps; sums in the shared partial-sum buffer that are not a smoothing block's);
+                 (d) a solve directly follows time_refine_pass;
+                 (e) solve_pcg, and with gcr solve_gcr, directly follows a solve_refine once;
+                 (f) a ("vcycle", level) from a coarse level, ("restrict", finest) and ("prolong_add", finest) stand between
+                     two refines"""
+    assert not (refine and fresh_guess)
     rng = np.random.RandomState(seed)
     L, Lc = cfg["finest_level"], cfg["coarsest_level"]
     f64 = cfg.get("dtype", hm.F64) == hm.F64
@@ -282,6 +413,8 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
             out[first[-1]] = DEEP_GCR[:2] + (deep_iters,) + DEEP_GCR[3:]
             if not fresh_guess:
                 out.insert(first[-1], ("set_guess", 3500))
+    if refine:
+        out = refine_stage(seed, cfg, out, gcr)
     if fresh_guess:
         fresh = []
         for c in out:
@@ -344,7 +477,11 @@ def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
         return mg.solve_pcg(tol=a[0], max_iters=a[1])
     if name == "solve_gcr":
         return mg.solve_gcr(tol=a[0], max_iters=a[1], restart=a[2])
-    if name == "vcycle_zero":
+    if name == "solve_refine":
+        return mg.solve_refine(tol=a[0], max_cycles=a[1])
+    if name == "time_refine_pass":
+        assert mg.time_refine_pass(a[0]) > 0.0
+    elif name == "vcycle_zero":
         mg.vcycle_zero()
     elif name == "smooth":
         mg.smooth(a[0], a[1])
@@ -399,8 +536,13 @@ def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
     return None
 
 
-def apply_model(m, call, L):
+def apply_model(m, call, L, device=None):
+    """device: what apply_device returned for this call.  solve_refine takes its scales s_k from the history the device
+    reported (a norm is the one place where the device's order of summation reaches the iterate), as
+    tests/test_gpu_refine.py's composition does; everything else about the call is the model's own"""
     name, a = call[0], call[1:]
+    if name == "solve_refine":
+        return m.solve_refine(tol=a[0], max_cycles=a[1], history=None if device is None else device[1])
     if name == "solve":
         return m.solve(tol=a[0], max_cycles=a[1])
     if name == "solve_pcg":
@@ -461,7 +603,7 @@ def history_check(cfg, call, h, ref):
     h, ref = np.asarray(h), np.asarray(ref)
     if len(h) != len(ref):
         return False, np.inf
-    if call[0] == "solve":
+    if call[0] in ("solve", "solve_refine"):               # (solve_refine: norms of the same residual bits in another order, as solve's)
         bound = HIST_TOL * ref + HIST_FLOOR * ref[0] if f64 else NORM32 * ref
     else:
         bound = RTOL64 * ref + PCG_FLOOR * ref[0] if f64 else RTOL32 * ref
@@ -490,7 +632,7 @@ def step(pkg, mg, m, cfg, call, tally, where):
     L, Lc = cfg["finest_level"], cfg["coarsest_level"]
     g_before = mg.graphs_cached()
     got = apply_device(pkg, mg, call, L, hm.BILINEAR if m.transfer is None else m.transfer)
-    want = apply_model(m, call, L)
+    want = apply_model(m, call, L, got)
     tally.executed += 1
     if call[0] == "set_cycle":                             # the graph key carries no kind: the setter has to drop the graphs
         assert mg.cycle == m.cycle == call[1], where()
@@ -551,8 +693,9 @@ def run_sequence(pkg, po, cfg, calls, seed, env=None):
     krylov_bound = RTOL64 if cfg.get("dtype", hm.F64) == hm.F64 else PCG32_STATE
     print(f"\n[handle-state] cfg={cfg} env={env} seed={seed} steps={tally.executed} graph_users={users} "
           f"max_graphs={tally.graphs} hist_solve={tally.hist['solve']:.3g}xbound hist_pcg={tally.hist['solve_pcg']:.3g}xbound "
-          f"hist_gcr={tally.hist['solve_gcr']:.3g}xbound state_dev_bottom={tally.state:.3g} state_dev_pcg={tally.state_pcg:.3g} "
-          f"state_dev_gcr={tally.state_gcr:.3g} ({tally.state_gcr / krylov_bound:.3g}xbound)")
+          f"hist_gcr={tally.hist['solve_gcr']:.3g}xbound hist_refine={tally.hist['solve_refine']:.3g}xbound state_dev_bottom={tally.state:.3g} "
+          f"state_dev_pcg={tally.state_pcg:.3g} ({tally.state_pcg / krylov_bound:.3g}xbound) state_dev_gcr={tally.state_gcr:.3g} "
+          f"({tally.state_gcr / krylov_bound:.3g}xbound) graphs={tally.graph_counts}")
     return tally
 
 
@@ -645,8 +788,8 @@ def assert_cycle_calls(calls, cfg):
     users = [i for i, c in enumerate(calls) if c[0] in graph_users(calls)]
     sets = [i for i, c in enumerate(calls) if c[0] == "set_cycle"]
     assert tuple(calls[i][1] for i in sets) == CYCLE_ORDER
-    for k, i in enumerate(sets):                           # after every second graph user (an operator change may stand between)
-        assert sum(1 for u in users if u < i) == 2 * (k + 1), (k, i)
+    for k, i in enumerate(sets):                           # after every second graph user (an operator change may stand between;
+        assert sum(1 for u in users if u < i and calls[u][0] != "solve_refine") == 2 * (k + 1), (k, i)      # refines are placed later)
     kinds = kinds_at(calls)
     for lv in small_levels(cfg):
         for kind in (hm.CYCLE_W, hm.CYCLE_F):
@@ -1124,6 +1267,58 @@ def test_an_unsymmetric_nine_point_operator_on_one_handle(pkg, po, monkeypatch, 
     assert tally.executed == len(calls) and tally.graphs >= 1
     print(f"\n[handle-state] random9 cfg={cfg} steps={tally.executed} max_graphs={tally.graphs} hist_solve={tally.hist['solve']:.3g}xbound "
           f"hist_gcr={tally.hist['solve_gcr']:.3g}xbound state_dev_gcr={tally.state_gcr:.3g} ({tally.state_gcr / RTOL64:.3g}xbound)")
+
+
+# ---- 2f. mgx_solve_refine among the graph users ----------------------------------------------------------------------
+EAGER = {"MGX_GRAPH": "0"}
+REFINE_OPTIONS = dict(refine=True, n_steps=30)             # (few calls drawn by weight: the refine stage adds about twenty-five)
+REFINE_CASES = {
+    # name: (configuration, seed, environments, generator options).  All double: the handles mgx_solve_refine takes
+    # V(3,2); set_coefficient 100 and 1000 rewrite EVERY level of the float copy.  The float dense solve at level 5 of a
+    # STENCIL5 handle: held bit for bit by test_general_operator_sequences_match_the_model_after_every_call[stencil5_f32_chebyshev]
+    "stencil5_f64_jacobi_8_5_refine": (dict(P85, op=hm.STENCIL5), 8591, [{}], {}),
+    # the float lambda bounds are kernel arguments of the float copy's captured cycle
+    "stencil5_f64_chebyshev_8_5_refine": (dict(P85, op=hm.STENCIL5, smoother=hm.CHEBYSHEV), 8592, [{}], {}),
+    # set_cycle through CYCLE_ORDER; BILINEAR -> OPERATOR -> BILINEAR -> OPERATOR with the same coefficients (the float copy
+    # follows a transfer-only rebuild), then set_coefficient + BILINEAR.  The float copy takes the handle's knobs, not the
+    # environment's: the same bits without the visit kernel and without graphs.  bottom = SMOOTH: no F32 sequence holds the
+    # float dense solve of a GALERKIN hierarchy at level 3 against the model
+    "galerkin_f64_jacobi_7_3_refine_cycles": (dict(G73, bottom=hm.SMOOTH), 8593, [{}, NO_VISIT, EAGER], dict(cycles=True)),
+    # the finest level flips nine-point (in place) -> five-point (swapping) -> nine-point under the pass and under the float
+    # cycle; bottom = SMOOTH for the same reason
+    "galerkin_f64_sgs_7_3_nine_refine": (
+        dict(G73, smoother=hm.COLOR_SGS, bottom=hm.SMOOTH), 8594, [{}, UNFUSED],
+        dict(operators=("rot45", [[("set_coefficient", 100.0, 11), ("build_galerkin", hm.BILINEAR)], [("set_operator", "smooth9")]]))),
+    # refine between Krylov calls on the shared workspace (one partial-sum buffer, one scalar block)
+    "galerkin_f64_gs_8_5_smooth_bottom_refine_gcr": (dict(P85_WEAK, op=hm.GALERKIN, smoother=hm.COLOR_GS, bottom=hm.SMOOTH), 8595, [{}], dict(gcr=True)),
+}
+
+
+@pytest.mark.parametrize("name", list(REFINE_CASES))
+def test_refine_sequences_match_the_model_after_every_call(pkg, po, monkeypatch, name):
+    """mgx_solve_refine as one more graph user of a long-lived handle: a second solver inside the handle (the float copy,
+    with a graph cache of its own, rebuilt lazily from a generation counter and told the cycle kind by hand), one u <-> tmp
+    swap of the finest level per cycle under the parent's graph key, and the pass's sums in the partial-sum buffer
+    mgx_solve, mgx_solve_pcg and mgx_solve_gcr share.  U and B of EVERY level bit for bit after every refine - so the
+    parent's coarse levels are held untouched (the cycle runs in the float copy) - its history as mgx_solve's, its
+    statistics equal; the model takes the scales from the device's history (apply_model)"""
+    cfg, seed, envs, options = REFINE_CASES[name]
+    calls = draw_sequence(seed, cfg, **REFINE_OPTIONS, **options)
+    assert_refine_calls(calls, cfg, options.get("gcr", False))
+    if options.get("cycles"):
+        assert_cycle_calls(calls, cfg)
+    if options.get("gcr"):
+        assert_gcr_calls(calls, cfg)
+    runs = []
+    for env in envs:
+        set_knobs(monkeypatch, env)
+        tally = run_sequence(pkg, po, cfg, calls, seed, env)
+        assert tally.graphs == -1 if env == EAGER else 1 <= tally.graphs <= K_MAX_GRAPHS, tally.graphs
+        runs.append(tally)
+    for b, env in zip(runs[1:], envs[1:]):
+        for x, y in zip(runs[0].final, b.final):
+            assert np.array_equal(x, y), env
+        assert len(runs[0].histories) == len(b.histories) and all(np.array_equal(x, y) for x, y in zip(runs[0].histories, b.histories)), env
 
 
 # ---- 3. the cache bound and its fallback ---------------------------------------------------------------------------

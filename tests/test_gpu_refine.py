@@ -7,9 +7,13 @@ parent's coefficients (mgx_vcycle_zero), and the scales recomputed from the hist
 kernel, a wrong float hierarchy or a wrong scale changes the final iterate; the history then has to agree with numpy's
 norms of those residuals to tests/test_gpu_solve.py's HIST_TOL (only the order of the sum differs).
 
-Shapes: a wave of the pass covers 62 output lanes = 124 columns and marches down 4 rows per chunk at these sizes
-(make_launch).  (4, 3): 15^2 unknowns, a partial strip, four chunks; (7, 3): 127 columns, two strips, the second a
-sliver; (8, 4): 255 columns, three strips, 64 chunks per strip and more than one workgroup per strip."""
+Shapes: a wave of the pass covers 62 output lanes = 124 columns and marches down R rows per chunk, R = clamp(rows / 128,
+4, 8) (make_launch) unless MGX_ROWS says otherwise: 4 at every size of CASES.  (4, 3): 15^2 unknowns, a partial strip, four
+chunks; (7, 3): 127 columns, two strips, the second a sliver; (8, 4): 255 columns, three strips, 64 chunks per strip and
+more than one workgroup per strip.  ROWS_CASES run the other heights: MGX_ROWS 1, 3, 5, 8 and 64 on 63 rows, and level 10
+at its own R = 7 (the benchmarked sizes, 2047^2 and 4095^2, run R = 8).
+The fallback of launch_refine_pass to taller chunks (more blocks than the partial-sum buffer holds) cannot be entered:
+the buffer is sized at creation for a launch of one row per chunk, the largest there is.  No test tries to."""
 import ctypes as C
 
 import numpy as np
@@ -135,6 +139,40 @@ def test_refine_is_the_composition_of_public_pieces_bit_for_bit(pkg, name):
         assert st.cycles == 6 and st.history_len == 7 and len(hist) == 7
         assert np.isfinite(hist).all() and hist[-1] < hist[0], hist
         u_ref, hist_ref = composition(pkg, mg, cfg, nine, transfer, cycle, b, u0, hist)
+    print(f"{name}: history {hist}, largest relative difference to numpy's norms {np.max(np.abs(hist - hist_ref) / hist_ref):.2e}")
+    assert_same(u, u_ref, name)
+    assert hist_close(hist, hist_ref, HIST_TOL), (hist, hist_ref)
+
+
+# ---- 1b. the chunk heights of the pass ------------------------------------------------------------------------------
+ROWS_CASES = {
+    # name: (MGX_ROWS or None, L, Lc, op, cfg, operator, nine).  63 rows: R = 1: both neighbour rows of every row are
+    # recomputed; 3: divides the rows exactly; 5: a last chunk of three rows; 8: the R of the benchmarked sizes; 64: one chunk
+    **{f"stencil5-6-3-rows-{r}": (r, 6, 3, "s5", dict(mu1=2, mu2=1), "contrast10", False) for r in (1, 3, 5, 8, 64)},
+    **{f"galerkin-nine-6-3-rows-{r}": (r, 6, 3, "gal", dict(), "rot45", True) for r in (3, 8)},
+    # 1023 rows, the smallest level at which make_launch leaves R = 4 on its own: R = 7, 147 chunks, the last of one row; nine
+    # strips, the last partial; several workgroups per strip.  bottom = SMOOTH (the dense solve stops at level 5)
+    "galerkin-10-4-rows-default": (None, 10, 4, "gal", dict(bottom=1), "contrast10", False),
+    "galerkin-nine-10-4-rows-default": (None, 10, 4, "gal", dict(bottom=1), "rot45", True),
+}
+
+
+@pytest.mark.parametrize("name", list(ROWS_CASES))
+def test_refine_is_the_composition_at_every_chunk_height(pkg, monkeypatch, name):
+    """the rolling window of k_refine_pass recomputes the row above and the row below a chunk from u and e: what depends
+    on R.  MGX_ROWS is read when a handle is created, so it is set before all three are; random guess, six cycles"""
+    rows, L, Lc, op, extra, kind, nine = ROWS_CASES[name]
+    if rows is None:
+        monkeypatch.delenv("MGX_ROWS", raising=False)
+        assert ((1 << L) - 1) // 128 == 7                    # make_launch: R = clamp(rows / 128, 4, 8)
+    else:
+        monkeypatch.setenv("MGX_ROWS", str(rows))
+    cfg = config(pkg, L, Lc, pkg.OPERATOR_STENCIL5 if op == "s5" else pkg.OP_GALERKIN, **extra)
+    b, u0 = rand(L, 3), rand(L, 4)
+    with parent(pkg, cfg, kind) as mg:
+        st, hist, u = refine(mg, b, u0, 0.0, 6)
+        assert st.cycles == 6 and len(hist) == 7 and np.isfinite(hist).all() and hist[-1] < hist[0], hist
+        u_ref, hist_ref = composition(pkg, mg, cfg, nine, BILINEAR, None, b, u0, hist)
     print(f"{name}: history {hist}, largest relative difference to numpy's norms {np.max(np.abs(hist - hist_ref) / hist_ref):.2e}")
     assert_same(u, u_ref, name)
     assert hist_close(hist, hist_ref, HIST_TOL), (hist, hist_ref)

@@ -2,7 +2,8 @@
 the bits of the references' own schedules - oracle/pyoracle.py's Solver for the constant stencil, the hierarchies of
 tests/galerkin_ref.py, tests/opdep_ref.py and tests/cheby_ref.py for the general operators, tests/colour_ref.py for the
 colour smoothers and tests/nine_ref.py for nine-point finest levels - and its solves their histories; the coarse levels
-must hold afterwards what the documented operator sequence leaves there.  The sequences of
+must hold afterwards what the documented operator sequence leaves there.  solve_refine is held to tests/refine_ref.py's
+loop around an fp64 and an independently built float32 reference hierarchy.  The sequences of
 tests/test_gpu_handle_state.py are drawn and walked here without a device: what the generator promises, and the
 conditions the Krylov bounds rest on."""
 import numpy as np
@@ -1186,3 +1187,256 @@ def test_the_model_walks_the_colour_and_nine_sequences(po, name, cfg, seed, opti
     lowest = walk(po, cfg, calls)
     print(f"\n[handle-state] model alone: {name} steps={len(calls)} lowest last/first of a Krylov call={lowest[0]:.3g} at {lowest[1]}")
     assert (1e-6 if cfg.get("dtype", hm.F64) == hm.F64 else 1e-3) <= lowest[0] < 1.0, lowest
+
+
+# ---- solve_refine ---------------------------------------------------------------------------------------------------------
+def f32(st):
+    return [np.asarray(x, dtype=np.float32) for x in st]
+
+
+def refine_references(po, name, L, Lc):
+    """(cfg of the model, how the model is given its operator, the fp64 reference hierarchy, the float32 one): the two
+    hierarchies are built independently of each other and of the model, the float one IN float32 from the float32 of the
+    coefficients - what include/mgx.h says the float copy holds"""
+    base = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=2, mu2=1, schedule=hm.V, dtype=hm.F64)
+    a = contrast(L, 10.0, 4)
+    kw = dict(mu1=2, mu2=1)
+    st5 = po.stencil_from_nodes(a, L, L)
+    both = lambda make: (make(np.float64, lambda st: st), make(np.float32, f32))
+    if name in ("stencil5-jacobi", "stencil5-chebyshev"):
+        cheb = name.endswith("chebyshev")
+        cls = cheby_ref.Stencil5Cheby if cheb else cheby_ref.Stencil5
+        st = {lv: po.stencil_from_nodes(a, lv, L) for lv in range(Lc, L + 1)}
+        refs = both(lambda dt, cast: cls(po, {lv: cast(st[lv]) for lv in st}, L, Lc, dtype=dt, **kw))
+        return dict(base, op=hm.STENCIL5, smoother=hm.CHEBYSHEV if cheb else hm.JACOBI), (lambda m: m.set_coefficient(a)), refs
+    give5 = lambda transfer: (lambda m: (m.set_coefficient(a), m.build_galerkin(transfer)))
+    if name == "galerkin-bilinear":
+        return dict(base, op=hm.GALERKIN), give5(hm.BILINEAR), both(lambda dt, cast: gr.Hierarchy(po, cast(st5), L, Lc, dtype=dt, **kw))
+    if name == "galerkin-operator":
+        return dict(base, op=hm.GALERKIN), give5(hm.OPERATOR), both(lambda dt, cast: od.Hierarchy(po, cast(st5), L, Lc, dtype=dt, **kw))
+    if name == "nine-point":
+        st9 = hm.operator9(L, "rot45", np.float64)
+        return (dict(base, op=hm.GALERKIN), (lambda m: m.set_operator("rot45")),
+                both(lambda dt, cast: nr.Hierarchy(po, cast(st9), L, Lc, dtype=dt, **kw)))
+    if name == "colour-sgs":
+        return (dict(base, op=hm.GALERKIN, smoother=hm.COLOR_SGS), give5(hm.BILINEAR),
+                both(lambda dt, cast: cf.Hierarchy(hm.COLOR_SGS, po, cast(st5), L, Lc, dtype=dt, **kw)))
+    if name == "w-cycle":
+        return (dict(base, op=hm.GALERKIN), (lambda m: (m.set_coefficient(a), m.build_galerkin(hm.BILINEAR), m.set_cycle(hm.CYCLE_W))),
+                both(lambda dt, cast: wr.with_cycle(wr.Galerkin, wr.W, po, cast(st5), L, Lc, dtype=dt, **kw)))
+    if name == "bottom-smooth":
+        return (dict(base, op=hm.GALERKIN, bottom=hm.SMOOTH), give5(hm.BILINEAR),
+                both(lambda dt, cast: gr.Hierarchy(po, cast(st5), L, Lc, dtype=dt, bottom=hm.SMOOTH, **kw)))
+    raise KeyError(name)
+
+
+REFINE_REFS = ["stencil5-jacobi", "stencil5-chebyshev", "galerkin-bilinear", "galerkin-operator", "nine-point", "colour-sgs", "w-cycle", "bottom-smooth"]
+
+
+@pytest.mark.parametrize("name", REFINE_REFS)
+def test_solve_refine_equals_refine_ref_around_independent_hierarchies(po, name):
+    """iterate and history bit for bit; B and every coarse level untouched; fine_updates those of the float cycle; the
+    stop by the tolerance; max_cycles = 0; the scales of a history handed in"""
+    import refine_ref as rr
+    L, Lc = 6, 3
+    cfg, give, (h64, h32) = refine_references(po, name, L, Lc)
+    assert all(x.dtype == np.float32 for x in h32.st[L]) and all(x.dtype == np.float64 for x in h64.st[L])
+    u, b = data(po, L, np.float64, 61)
+    cycle32 = gcr_ref.cycle_preconditioner(h32)
+    residual = lambda v, f: h64.residual(L, v, f)
+    m = hm.HandleModel(po, **cfg)
+    give(m)
+    for lv in m.levels():
+        if lv < L:
+            m.set_level(lv, 0, data(po, lv, np.float64, 70 + lv)[0])
+            m.set_level(lv, 1, data(po, lv, np.float64, 80 + lv)[0])
+    coarse = {lv: (m.U[lv].copy(), m.B[lv].copy()) for lv in m.levels() if lv < L}
+    n2 = float((1 << L) - 1) ** 2
+    for tol, k in ((0.0, 4), (1e-2, 30), (0.5, 0)):
+        u_ref, h_ref = rr.refine(residual, cycle32, b, u, tol=tol, max_cycles=k, norm=po.norm2)
+        m.set_guess(u)
+        m.set_rhs(b)
+        st, h = m.solve_refine(tol=tol, max_cycles=k)
+        assert np.array_equal(h, h_ref) and np.array_equal(m.U[L], u_ref) and m.U[L].dtype == np.float64, (name, tol, k)
+        assert np.array_equal(m.B[L], b)
+        assert st == dict(cycles=len(h_ref) - 1, converged=int(h_ref[-1] <= tol * h_ref[0]), fine_updates=(len(h_ref) - 1) * 3.0 * n2), st
+        for lv, (uu, bb) in coarse.items():
+            assert np.array_equal(m.U[lv], uu) and np.array_equal(m.B[lv], bb), lv
+    assert len(h) == 1 and np.array_equal(m.U[L], u) and st["converged"] == 0          # max_cycles = 0
+    assert np.isfinite(h_ref).all()
+    # a history handed in gives the scales and nothing else.  (Scaling by a power of two is exact: the iterate changes only
+    # where the scale pushes the float residual out of the normal range - 2^120 too large here)
+    _, h4 = m.solve_refine(tol=0.0, max_cycles=4)
+    m.set_guess(u)
+    far = h4 * 2.0 ** 120
+    st, h = m.solve_refine(tol=0.0, max_cycles=4, history=far)
+    u_ref, h_ref = rr.refine(residual, cycle32, b, u, history=far, norm=po.norm2)
+    assert st["cycles"] == 4 and np.array_equal(m.U[L], u_ref) and np.array_equal(h, h_ref) and not np.array_equal(h, h4)
+    m.set_guess(u)
+    assert np.array_equal(m.solve_refine(tol=0.0, max_cycles=4, history=h4)[1], h4)       # its own history: the same call
+
+
+def refined(m, u, b, k=3):
+    m.set_guess(u)
+    m.set_rhs(b)
+    st, h = m.solve_refine(tol=0.0, max_cycles=k)
+    return st, h, m.U[m.L].copy()
+
+
+def test_the_float_model_follows_operator_transfer_and_cycle_changes(po):
+    """operator A -> refine -> operator B -> refine -> the other transfer with the same coefficients -> refine ->
+    set_cycle(W) -> refine on ONE model: every refine is that of a fresh model in the same state"""
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=2, mu2=1, op=hm.GALERKIN, schedule=hm.V)
+    a1, a2 = contrast(L, 10.0, 1), contrast(L, 100.0, 2)
+    u, b = data(po, L, np.float64, 62)
+    steps = [lambda m: (m.set_coefficient(a1), m.build_galerkin(hm.BILINEAR)), lambda m: (m.set_coefficient(a2), m.build_galerkin(hm.BILINEAR)),
+             lambda m: m.build_galerkin(hm.OPERATOR), lambda m: m.set_cycle(hm.CYCLE_W)]
+    one = hm.HandleModel(po, **cfg)
+    seen, floats = [], []
+    for i, change in enumerate(steps):
+        change(one)
+        if i == 0:
+            with pytest.raises(ValueError):
+                one.time_refine_pass(2)                     # before the first solve_refine
+        st, h, x = refined(one, u, b)
+        floats.append(one.f32)
+        fresh = hm.HandleModel(po, **cfg)
+        for earlier in steps[:i + 1]:
+            if not (i >= 1 and earlier is steps[0]):        # (operator A is overwritten by B)
+                earlier(fresh)
+        st_f, h_f, x_f = refined(fresh, u, b)
+        assert st == st_f and np.array_equal(h, h_f) and np.array_equal(x, x_f), i
+        assert all(not np.array_equal(x, y) for y in seen), i
+        seen.append(x)
+        before = [one.U[lv].copy() for lv in one.levels()] + [one.B[lv].copy() for lv in one.levels()]
+        one.time_refine_pass(2)
+        assert all(np.array_equal(p, q) for p, q in zip(before, [one.U[lv] for lv in one.levels()] + [one.B[lv] for lv in one.levels()]))
+    assert floats[0] is not floats[1] and floats[1] is not floats[2]       # rebuilt after an operator and after a transfer change
+    assert floats[2] is floats[3] and one.f32.cycle == hm.CYCLE_W            # set_cycle reaches it at once, nothing is rebuilt
+    assert one.f32.cfg["dtype"] == hm.F32 and one.f32.transfer == hm.OPERATOR and all(x.dtype == np.float32 for x in one.f32.h.st[L])
+
+
+def test_stencil5_float_model_holds_the_float32_of_every_level(po):
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=2, mu2=1, op=hm.STENCIL5, schedule=hm.V)
+    m = hm.HandleModel(po, **cfg)
+    m.set_coefficient(contrast(L, 10.0, 1))
+    u, b = data(po, L, np.float64, 63)
+    x1 = refined(m, u, b)[2]
+    m.set_coefficient(contrast(L, 1000.0, 3))
+    x2 = refined(m, u, b)[2]
+    for lv in m.levels():
+        for p, q in zip(m.f32.stencils[lv], m.stencils[lv]):
+            assert p.dtype == np.float32 and np.array_equal(p, q.astype(np.float32)), lv
+    assert not np.array_equal(x1, x2)
+
+
+def test_solve_refine_refusals(po):
+    L, Lc = 5, 3
+    base = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=1, mu2=1, schedule=hm.V)
+    a = contrast(L, 10.0, 1)
+    for m in (hm.HandleModel(po, **base), hm.HandleModel(po, dtype=hm.F32, **base)):                        # POISSON
+        with pytest.raises(ValueError):
+            m.solve_refine(1e-8, 3)
+        with pytest.raises(ValueError):
+            m.time_refine_pass(2)
+    m = hm.HandleModel(po, op=hm.STENCIL5, dtype=hm.F32, **base)                                             # F32 (MIXED: no model at all)
+    m.set_coefficient(a)
+    with pytest.raises(ValueError):
+        m.solve_refine(1e-8, 3)
+    m = hm.HandleModel(po, op=hm.GALERKIN, **base)
+    with pytest.raises(ValueError):
+        m.solve_refine(1e-8, 3)                             # unset
+    m.set_coefficient(a)
+    with pytest.raises(ValueError):
+        m.solve_refine(1e-8, 3)                             # unbuilt
+    m.build_galerkin()
+    m.set_rhs(data(po, L, np.float64, 64)[1])
+    assert m.solve_refine(0.0, 1)[0]["cycles"] == 1
+    m.set_coefficient(a)
+    with pytest.raises(ValueError):
+        m.time_refine_pass(2)                               # invalid again until the build
+    m = hm.HandleModel(po, op=hm.STENCIL5, **base)
+    m.set_stencil(L, operator5(po, L, "layers", np.float64))
+    with pytest.raises(ValueError):
+        m.solve_refine(1e-8, 3)                             # a STENCIL5 handle with levels missing
+    for line in hm.LINES:                                   # not modelled, and the message says so
+        for real in (None, np.longdouble):
+            m = hm.HandleModel(po, real=real, op=hm.GALERKIN, smoother=line, **base)
+            m.set_operator("layers")
+            with pytest.raises(ValueError, match="not modelled"):
+                m.solve_refine(1e-8, 3)
+
+
+def test_refine_sequences_hold_what_the_generator_promises():
+    seeds = [c[1] for d in (gs.POISSON_CASES, gs.GENERAL_CASES, gs.CYCLE_CASES, gs.LINE_CASES, gs.GCR_CASES, gs.COLOUR_CASES, gs.NINE_CASES, gs.REFINE_CASES)
+             for c in d.values()]
+    assert len(set(seeds)) == len(seeds)
+    # off by default: no sequence drawn without the option holds either call
+    for cfg, seed in list(gs.POISSON_CASES.values()) + list(gs.GENERAL_CASES.values()):
+        assert not any(c[0] in ("solve_refine", "time_refine_pass") for c in gs.draw_sequence(seed, cfg))
+    for name, (cfg, seed, envs, options) in gs.REFINE_CASES.items():
+        calls = gs.draw_sequence(seed, cfg, **gs.REFINE_OPTIONS, **options)
+        assert calls == gs.draw_sequence(seed, cfg, **gs.REFINE_OPTIONS, **options)
+        assert cfg.get("dtype", hm.F64) == hm.F64 and envs[0] == {}
+        gcr = options.get("gcr", False)
+        gs.assert_refine_calls(calls, cfg, gcr)
+        assert gs.graph_users(calls) == (gs.GCR_USERS if gcr else gs.GRAPH_USERS) + ("solve_refine",)
+        assert min(sum(1 for c in calls if c[0] == k) for k in gs.graph_users(calls)) >= 5
+        # without the option: the same list with the refine stage's calls taken out
+        plain = gs.draw_sequence(seed, cfg, **dict(gs.REFINE_OPTIONS, refine=False), **options)
+        rest = [c for c in calls if c[0] not in ("solve_refine", "time_refine_pass") and not (c[0] == "set_guess" and 4000 < c[1] < 4100)]
+        extra = [("vcycle", next(calls[i + 1][1] for i, c in enumerate(calls) if c[0] == "solve_refine" and calls[i + 1][0] == "vcycle"
+                                 and calls[i + 2] == ("restrict", cfg["finest_level"]))), ("restrict", cfg["finest_level"]), ("prolong_add", cfg["finest_level"])]
+        assert len(rest) == len(plain) + 3 and sorted(map(repr, rest)) == sorted(map(repr, plain + extra)), name
+        if options.get("cycles"):
+            gs.assert_cycle_calls(calls, cfg)
+        if gcr:
+            gs.assert_gcr_calls(calls, cfg)
+        if cfg["op"] == hm.STENCIL5:
+            assert [c[1] for c in calls if c[0] == "set_coefficient"] == [10.0, 100.0, 1000.0]
+        if cfg.get("bottom", hm.EXACT) == hm.EXACT:         # the float dense solve: held by an F32 sequence for STENCIL5 at level 5 only
+            assert cfg["op"] == hm.STENCIL5 and cfg["coarsest_level"] == 5 and gs.GENERAL_CASES["stencil5_f32_chebyshev"][0]["dtype"] == hm.F32
+    c = gs.REFINE_CASES["galerkin_f64_jacobi_7_3_refine_cycles"]
+    calls = gs.draw_sequence(c[1], c[0], **gs.REFINE_OPTIONS, **c[3])
+    builds = [i for i, x in enumerate(calls) if x[0] == "build_galerkin"]
+    assert [calls[i][1] for i in builds] == [hm.BILINEAR, hm.OPERATOR, hm.BILINEAR, hm.OPERATOR, hm.BILINEAR]
+    transfer_only = [i for i in builds[1:] if calls[i - 1][0] != "set_coefficient"]
+    assert len(transfer_only) >= 2                          # ... each followed by a refine before any other graph user: (a)
+    assert c[2] == [{}, {"MGX_SMALL_VISIT": "0"}, {"MGX_GRAPH": "0"}]
+    c = gs.REFINE_CASES["galerkin_f64_sgs_7_3_nine_refine"]
+    calls = gs.draw_sequence(c[1], c[0], **gs.REFINE_OPTIONS, **c[3])
+    assert [gs.point_counts(calls)[i] for i in gs.flips(calls)] == [5, 9] and c[2] == [{}, {"MGX_GS_FUSED": "0"}]
+    c = gs.REFINE_CASES["galerkin_f64_gs_8_5_smooth_bottom_refine_gcr"][0]
+    assert (c["mu1"], c["mu2"], c["bottom"], c["smoother"]) == (1, 0, hm.SMOOTH, hm.COLOR_GS)
+
+
+@pytest.mark.parametrize("name", list(gs.REFINE_CASES))
+def test_the_model_walks_the_refine_sequences(po, name):
+    """without a device: every array finite after every call (walk); every solve_refine history finite and lower at its end
+    than at its start (a call of no cycle aside); every double Krylov call at or above 1e-6 of its first entry"""
+    cfg, seed, envs, options = gs.REFINE_CASES[name]
+    calls = gs.draw_sequence(seed, cfg, **gs.REFINE_OPTIONS, **options)
+    m = hm.HandleModel(po, **cfg)
+    lowest, slowest = (1.0, None), (0.0, None)
+    for i, call in enumerate(calls):
+        before = {lv: (m.U[lv], m.B[lv]) for lv in m.levels()}
+        out = gs.apply_model(m, call, cfg["finest_level"])
+        for lv in m.levels():
+            assert np.isfinite(m.U[lv]).all() and np.isfinite(m.B[lv]).all(), (i, call, lv)
+        if call[0] in gs.SOLVES:
+            assert np.isfinite(out[1]).all(), (i, call)
+        if call[0] == "solve_refine":
+            st, h = out
+            assert st["cycles"] == len(h) - 1 <= call[2] and (call[1] > 0.0 or st["cycles"] == call[2]), (i, call, st)
+            if call[2]:
+                assert st["cycles"] >= 1 and h[-1] < h[0], (i, call, h)
+                slowest = max(slowest, (float(h[-1] / h[0]), (i, call)))
+            for lv in m.levels():                           # only U of the finest level moves
+                assert m.B[lv] is before[lv][1] and (lv == m.L or m.U[lv] is before[lv][0]), (i, call, lv)
+        if call[0] in gs.KRYLOV and out[1][-1] / out[1][0] < lowest[0]:
+            lowest = (float(out[1][-1] / out[1][0]), (i, call))
+    print(f"\n[handle-state] model alone: {name} steps={len(calls)} lowest last/first of a Krylov call={lowest[0]:.3g} at {lowest[1]}; "
+          f"highest last/first of a solve_refine={slowest[0]:.3g} at {slowest[1]}")
+    assert 1e-6 <= lowest[0] < 1.0, lowest
