@@ -487,6 +487,39 @@ MGX_API int mgx_solve_gcr(mgx_handle h, double tol, int max_iters, int restart, 
  * F32 build's error when its line factors break down in float - the fp64 state stays usable in both cases. */
 MGX_API int mgx_solve_refine(mgx_handle h, double tol, int max_cycles, mgx_stats* stats, double* history, int history_cap);
 
+/* mgx_solve_gcr's iteration in fp64 around the FLOAT cycle of mgx_solve_refine: restarted GCR with right preconditioning
+ * on the finest level of a general-operator F64 handle, the preconditioner one cycle from zero of the handle's float copy
+ * of the hierarchy (the one mgx_solve_refine creates and shares), scaled by mgx_solve_refine's power of two (absent in the
+ * reference).  Run to ||r||_2 <= tol ||r0||_2 or max_iters iterations:
+ *     r = b - A x;  hist[0] = ||r||;  n = 2^finest_level - 1
+ *     iteration k, j = k mod restart (the basis is emptied when j = 0):
+ *       s_k = 2^floor(log2( hist[max(k - 1, 0)] / n ))
+ *       z = s_k * (double) M32( (float)(r / s_k) );  q = A z          (fp64, the handle's finest operator)
+ *       h_i, q', z', s_j = q'.q', rho = r.q', alpha = rho / s_j       (exactly mgx_solve_gcr's passes on double vectors)
+ *       x += alpha z';  r -= alpha q';  hist[k + 1] = ||r||;  Z_j = z', Q_j = q'
+ * M32 is the cycle mgx_vcycle_zero runs on an F32 handle (any smoother, cycle kind, transfer, bottom, a five- or
+ * nine-point finest level); the scaling is exact.  Two passes sit on the precision boundary: k_refine_direction
+ * (z from the float correction and q = A z: 60 B per point on a five-point, 92 B on a nine-point finest level) and
+ * k_refine_update (mgx_solve_gcr's update plus the scaled float residual of the next cycle: 52 B per point); the
+ * orthogonalisation passes and reductions are mgx_solve_gcr's.
+ * The contract of mgx_solve_gcr: starts from the current U; on return U holds the fp64 iterate (also after a breakdown)
+ * and B the caller's b, bit for bit; history[0] = ||b - A u0||, then the norm of the recursively updated fp64 residual
+ * after each iteration; stats->cycles = iterations = float cycles applied, fine_updates those of the float cycle (as for
+ * mgx_solve_refine); max_iters = 0 writes one history entry and leaves U alone.  A breakdown (q'.q' not a positive
+ * finite number) stops the iteration with stats->converged = 0, MGX_OK and the reason in mgx_last_error.  Deterministic
+ * (fixed-order reductions, no atomics; graph replay and MGX_GRAPH=0 give the same bits); one host synchronisation per
+ * iteration.  The handle's own mgx_solve / mgx_vcycle / mgx_solve_pcg / mgx_solve_gcr / mgx_solve_refine compute, before
+ * and after a call, the bits of a handle that never made it.
+ * Memory: the float copy (shared with mgx_solve_refine, rebuilt by the next call after the handle's operator or
+ * hierarchy has changed; mgx_set_cycle reaches it at once) and mgx_solve_gcr's workspace, shared with it: x, b and
+ * 2 restart fp64 vectors of the finest level.
+ * MGX_ERR_STATE exactly where mgx_solve_refine returns it (POISSON, F32 and MIXED handles, multi-GPU and rank handles,
+ * before the operators are set / built); MGX_ERR_INVALID for tol not >= 0, max_iters < 0, restart < 1 or
+ * restart > MGX_GCR_MAX_RESTART; MGX_ERR_ALLOC, and the F32 build's error from the float copy - the fp64 state stays
+ * usable in both cases. */
+MGX_API int mgx_solve_refine_gcr(mgx_handle h, double tol, int max_iters, int restart, mgx_stats* stats,
+                                 double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -523,6 +556,14 @@ MGX_API int mgx_time_gcr_pass(mgx_handle h, int pass, int j, int repeats, double
  * no meaning between two mgx_solve_refine calls).  MGX_ERR_STATE where mgx_solve_refine is, and until a mgx_solve_refine
  * call has created the float copy; MGX_ERR_INVALID for repeats < 1. */
 MGX_API int mgx_time_refine_pass(mgx_handle h, int repeats, double* ms);
+/* ms per launch of one of mgx_solve_refine_gcr's two mixed passes on the handle's own buffers, `repeats` launches between
+ * two events (tools/refine_gcr_bench.py): UPDATE is k_refine_update, DIRECTION k_refine_direction<5 | 9> with scale 1.  The
+ * scalars are zeroed first, so U, B and the saved iterate are unchanged bit for bit; the float residual of the shadow
+ * (UPDATE) and basis slot 0 (DIRECTION) are rewritten - neither has a meaning between two solves.  MGX_ERR_STATE where
+ * mgx_solve_refine_gcr is, and until a mgx_solve_refine_gcr call has created the float copy and basis slot 0;
+ * MGX_ERR_INVALID for another pass or repeats < 1. */
+enum { MGX_REFINE_GCR_PASS_UPDATE = 0, MGX_REFINE_GCR_PASS_DIRECTION = 1 };
+MGX_API int mgx_time_refine_gcr_pass(mgx_handle h, int pass, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

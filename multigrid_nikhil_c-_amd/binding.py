@@ -56,6 +56,7 @@ EXPORTS = [
     "mgx_build_galerkin", "mgx_get_stencil9", "mgx_set_stencil9", "mgx_set_tensor",
     "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max", "mgx_get_line_factor", "mgx_get_line_chunks",
     "mgx_set_cycle", "mgx_get_cycle", "mgx_solve_refine", "mgx_time_refine_pass",
+    "mgx_solve_refine_gcr", "mgx_time_refine_gcr_pass",
 ]
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
@@ -175,6 +176,8 @@ def lib() -> C.CDLL:
     L.mgx_solve_gcr.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_solve_refine.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_time_refine_pass.argtypes = [vp, C.c_int, dp]
+    L.mgx_solve_refine_gcr.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(Stats), dp, C.c_int]
+    L.mgx_time_refine_gcr_pass.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mgx_profile_get.argtypes = [vp, C.POINTER(Profile)]
     L.mgx_time_smoother.argtypes = [vp, C.c_int, dp]
     L.mgx_time_gcr_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
@@ -636,6 +639,16 @@ class Multigrid:
                                          hist.size), "mgx_solve_refine")
         return st, hist[: st.history_len].copy()
 
+    def solve_refine_gcr(self, tol=1e-8, max_iters=100, restart=4):
+        """solve_gcr's iteration in fp64 around the float cycle of solve_refine (mgx_solve_refine_gcr): general-operator F64
+        handles, from the current guess; returns (stats, history of the recursively updated fp64 residual norm) as
+        solve_gcr() does (stats.cycles = iterations = float cycles)."""
+        st = Stats()
+        hist = np.zeros(max(max_iters, 0) + 1, dtype=np.float64)
+        self._chk(lib().mgx_solve_refine_gcr(self._h, tol, max_iters, restart, C.byref(st), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                             hist.size), "mgx_solve_refine_gcr")
+        return st, hist[: st.history_len].copy()
+
     # -- measurement -----------------------------------------------------------------
     def profile_reset(self):
         self._chk(lib().mgx_profile_reset(self._h), "mgx_profile_reset")
@@ -662,6 +675,13 @@ class Multigrid:
         unchanged; after a solve_refine"""
         ms = C.c_double()
         self._chk(lib().mgx_time_refine_pass(self._h, repeats, C.byref(ms)), "mgx_time_refine_pass")
+        return ms.value
+
+    def time_refine_gcr_pass(self, which, repeats=20):
+        """ms per launch of one mixed pass of solve_refine_gcr: which = 0 k_refine_update, 1 k_refine_direction; U and B
+        unchanged; after a solve_refine_gcr"""
+        ms = C.c_double()
+        self._chk(lib().mgx_time_refine_gcr_pass(self._h, which, repeats, C.byref(ms)), "mgx_time_refine_gcr_pass")
         return ms.value
 
     def graphs_cached(self):

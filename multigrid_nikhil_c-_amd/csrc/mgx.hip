@@ -12,6 +12,7 @@
 //   mgx_solve_gcr       (absent in the reference) restarted GCR around one cycle, mgx_krylov.hpp
 //   mgx_solve_refine    (absent in the reference) fp64 defect correction around the cycle of a float copy of the
 //                       hierarchy, mgx_refine.hpp
+//   mgx_solve_refine_gcr  (absent in the reference) fp64 restarted GCR around that float cycle, mgx_refine_gcr.hpp
 // There is no CPU fallback anywhere in this file.
 
 #include "../../include/mgx.h"
@@ -27,6 +28,7 @@
 #include "mgx_small.hpp"
 #include "mgx_krylov.hpp"
 #include "mgx_refine.hpp"
+#include "mgx_refine_gcr.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -2376,6 +2378,149 @@ int mgx_time_refine_pass(mgx_handle s, int repeats, double* ms)
     // rewritten (it has no meaning between two mgx_solve_refine calls)
     const int rc = time_on_stream(s, ms, [&] { for (int i = 0; i < repeats; ++i) refine_pass(s, true, 0.0, 1.0); });
     s->norm_blocks_ready = 0;
+    if (rc == MGX_OK) *ms /= repeats;
+    return rc;
+}
+
+// ---- mgx_solve_refine_gcr: fp64 restarted GCR (mgx_krylov.hpp) around the float cycle of the shadow ---------------
+// Z_j = z = scale * (double) z32 out of the shadow's U, Q_j = A z on the handle's finest operator
+static void refine_gcr_direction(mgx_solver* s, const Launch& g, int j, double scale)
+{
+    const Level& d = s->lv[s->cfg.finest_level];
+    const Level& w = s->shadow->lv[s->cfg.finest_level];
+    with_point_count(d.nine, [&](auto nq) {
+        hipLaunchKernelGGL((k_refine_direction<decltype(nq)::value>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const float*)w.u,
+                           op9_of<double>(d), (double*)s->kry.Z[j], (double*)s->kry.Q[j], scale, d.N, d.pitch, w.pitch, g.R, g.strips, g.chunks);
+    });
+}
+
+// x += alpha Z_j, r -= alpha Q_j (r in lv.b), the partials of ||r||^2 and r32 = (float)(r * inv_scale_next) into the
+// shadow's right-hand side
+static void refine_gcr_update(mgx_solver* s, const Launch& g, int j, double inv_scale_next)
+{
+    const Level& d = s->lv[s->cfg.finest_level];
+    const Level& w = s->shadow->lv[s->cfg.finest_level];
+    hipLaunchKernelGGL(k_refine_update, dim3(g.blocks), dim3(kBlock), 0, s->stream, (double*)s->kry.x, (const double*)s->kry.Z[j], (double*)d.b,
+                       (const double*)s->kry.Q[j], (float*)w.b, inv_scale_next, (const double*)s->kry.sc, s->kry.part, d.N, d.pitch, w.pitch,
+                       g.R, g.strips, g.chunks);
+}
+
+// The iteration: krylov_run's loop over the same workspace (x in kry.x, the caller's b in kry.b, r in lv[L].b for the
+// whole solve) with the cycle replaced by the scaled float cycle of the shadow: r32 is the shadow's lv[L].b and z32 its
+// lv[L].u, the pointers its cached cycle graphs hold.  The orthogonalisation and the reductions are mgx_solve_gcr's
+static int refine_gcr_run(mgx_solver* s, double tol, int max_iters, int restart, std::vector<double>& hist, int* iters, int* breakdown)
+{
+    mgx_solver* f = s->shadow;
+    mgx_solver::KrylovWs& w = s->kry;
+    Level& l = s->lv[s->cfg.finest_level];
+    const Level& fl = f->lv[s->cfg.finest_level];
+    const double n = (double)(l.N - 1);
+    const Launch g = make_launch(l.N, 2, l.N - 1, s->rows_per_chunk);
+    int rc = w.shared(s, l.bytes, g.blocks);
+    if (!rc) rc = GcrMethod<double>{restart}.prepare(s, l.bytes);
+    if (rc) return rc;
+    HIPCHK(s, hipMemcpyAsync(w.x, l.u, l.bytes, hipMemcpyDeviceToDevice, s->stream));
+    HIPCHK(s, hipMemcpyAsync(w.b, l.b, l.bytes, hipMemcpyDeviceToDevice, s->stream));
+    s->norm_blocks_ready = 0;
+    double h0 = 0.0;
+    if ((rc = residual_norm_grid(s, l, w.x, w.b, &h0, MGX_PROF_NORM_FINE))) return rc;
+    hist.push_back(h0);
+    if (h0 <= tol * h0 || max_iters == 0) return MGX_OK;               // (b = 0, u = 0: converged, nothing divided)
+    residual_level<0>(s, l, w.x, w.b, l.b);                            // r = b - A x, into lv[L].b
+    for (int k = 0; k < max_iters; ++k) {
+        // s_k: mgx_solve_refine's rule, a power of two near the rms of the residual the float cycle is given
+        const double scale = pow2_floor(hist[k > 0 ? k - 1 : 0] / n);
+        if (k == 0) {
+            // no scaled residual is pending yet: r32 = (float)((b - A x) / s_0), the bits of r above
+            Prof p(s, MGX_PROF_NORM_FINE, 1);
+            with_point_count(l.nine, [&](auto nq) {
+                launch_refine_pass<decltype(nq)::value, false>((const double*)w.x, (const float*)fl.u, (const double*)w.b, op9_of<double>(l),
+                                                               (double*)l.tmp, (float*)fl.b, 0.0, 1.0 / scale, s->partial, s->partial_cap,
+                                                               l.N, l.pitch, fl.pitch, s->rows_per_chunk, s->stream);
+            });
+        }
+        double unused = 0.0;
+        if ((rc = cycle_body(f, false, true, &unused))) return s->fail(rc, "mgx_solve_refine_gcr: float cycle: " + f->err);   // z32 = M32 r32 from zero
+        {
+            const int j = k % restart;
+            Prof p(s, MGX_PROF_NORM_FINE, j ? 7 : 5);                  // direction, (dots, reduce,) orth, reduce, update, reduce
+            refine_gcr_direction(s, g, j, scale);
+            launch_gcr_orth<double>(j, (double*)w.Q[j], (double*)w.Z[j], (const double*)l.b, gcr_basis<double>(s), w.sc, w.part, l.N, l.pitch, g,
+                                    kGcrAllPasses, s->stream);
+            refine_gcr_update(s, g, j, 1.0 / pow2_floor(hist[k] / n));
+            krylov_reduce(s, g.blocks, kPcgRRMode);
+        }
+        HIPCHK(s, hipGetLastError());
+        HIPCHK(s, hipMemcpyAsync(w.sc_host, w.sc, kPcgScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(s, hipStreamSynchronize(s->stream));                    // the one host synchronisation per iteration
+        if (w.sc_host[kPcgBreak] != 0.0) {
+            *breakdown = 1;
+            char msg[200];
+            std::snprintf(msg, sizeof msg, "mgx_solve_refine_gcr: GCR breakdown at iteration %d: q'.q' = %.17g is not a positive finite number", k + 1,
+                          w.sc_host[kPcgDelta]);
+            s->err = msg;
+            return MGX_OK;
+        }
+        *iters = k + 1;
+        const double rn = std::sqrt(w.sc_host[kPcgRR]);
+        hist.push_back(rn);
+        if (rn <= tol * h0 || k + 1 == max_iters) break;
+    }
+    return MGX_OK;
+}
+
+int mgx_solve_refine_gcr(mgx_handle s, double tol, int max_iters, int restart, mgx_stats* stats, double* history, int history_cap)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (int rc = refine_guard(s, "mgx_solve_refine_gcr")) return rc;
+    if (max_iters < 0 || !(tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_solve_refine_gcr: tol >= 0 and max_iters >= 0 required");
+    if (restart < 1 || restart > MGX_GCR_MAX_RESTART)
+        return s->fail(MGX_ERR_INVALID, "mgx_solve_refine_gcr: 1 <= restart <= MGX_GCR_MAX_RESTART required");
+    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
+    if (int rc = refine_shadow(s)) return rc;
+    mgx_solver* f = s->shadow;
+    Level& l = s->lv[s->cfg.finest_level];
+    std::vector<double> hist;
+    hist.reserve(max_iters + 1);
+    s->fine_updates = 0.0;
+    f->fine_updates = 0.0;
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    int iters = 0, breakdown = 0;
+    const int rc = refine_gcr_run(s, tol, max_iters, restart, hist, &iters, &breakdown);
+    // U = x, B = the caller's b again (also after a failure part way, where they were saved)
+    if (s->kry.x && s->kry.b && !hist.empty()) {
+        (void)hipMemcpyAsync(l.u, s->kry.x, l.bytes, hipMemcpyDeviceToDevice, s->stream);
+        (void)hipMemcpyAsync(l.b, s->kry.b, l.bytes, hipMemcpyDeviceToDevice, s->stream);
+    }
+    s->norm_blocks_ready = 0;
+    if (rc) return rc;
+    HIPCHK(s, hipGetLastError());
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    finish_solve(stats, history, history_cap, hist, iters, !breakdown && hist.back() <= tol * hist.front(), t0, f->fine_updates);
+    return MGX_OK;
+}
+
+int mgx_time_refine_gcr_pass(mgx_handle s, int pass, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!ms || repeats < 1 || pass < MGX_REFINE_GCR_PASS_UPDATE || pass > MGX_REFINE_GCR_PASS_DIRECTION)
+        return s->fail(MGX_ERR_INVALID, "mgx_time_refine_gcr_pass: pass 0 or 1 and repeats >= 1 required");
+    if (int rc = refine_guard(s, "mgx_time_refine_gcr_pass")) return rc;
+    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
+    if (!s->shadow || !s->kry.Z[0] || !s->kry.Q[0] || !s->kry.x || !s->kry.sc)
+        return s->fail(MGX_ERR_STATE, "mgx_time_refine_gcr_pass: call mgx_solve_refine_gcr first (it creates the float copy of the hierarchy and the basis)");
+    const Level& l = s->lv[s->cfg.finest_level];
+    const Launch g = make_launch(l.N, 2, l.N - 1, s->rows_per_chunk);
+    // the scalars zeroed, as in gcr_time_pass: alpha = 0, so the update leaves x and lv.b (the caller's b here) as they are; it
+    // rewrites the shadow's right-hand side, the direction pass basis slot 0 (neither has a meaning between two solves)
+    HIPCHK(s, hipMemsetAsync(s->kry.sc, 0, kGcrScalars * sizeof(double), s->stream));
+    const int rc = time_on_stream(s, ms, [&] {
+        for (int i = 0; i < repeats; ++i) {
+            if (pass == MGX_REFINE_GCR_PASS_UPDATE) refine_gcr_update(s, g, 0, 1.0);
+            else refine_gcr_direction(s, g, 0, 1.0);
+        }
+    });
     if (rc == MGX_OK) *ms /= repeats;
     return rc;
 }
