@@ -560,8 +560,9 @@ MGX_API int mgx_time_refine_pass(mgx_handle h, int repeats, double* ms);
  * two events (tools/refine_gcr_bench.py): UPDATE is k_refine_update, DIRECTION k_refine_direction<5 | 9> with scale 1.  The
  * scalars are zeroed first, so U, B and the saved iterate are unchanged bit for bit; the float residual of the shadow
  * (UPDATE) and basis slot 0 (DIRECTION) are rewritten - neither has a meaning between two solves.  MGX_ERR_STATE where
- * mgx_solve_refine_gcr is, and until a mgx_solve_refine_gcr call has created the float copy and basis slot 0;
- * MGX_ERR_INVALID for another pass or repeats < 1. */
+ * mgx_solve_refine_gcr is, and until the float copy and basis slot 0 exist: a mgx_solve_refine_gcr call creates both, and
+ * so do a mgx_solve_refine and a mgx_solve_gcr call between them - the call is accepted after those two as well, and is as
+ * harmless there; MGX_ERR_INVALID for another pass or repeats < 1. */
 enum { MGX_REFINE_GCR_PASS_UPDATE = 0, MGX_REFINE_GCR_PASS_DIRECTION = 1 };
 MGX_API int mgx_time_refine_gcr_pass(mgx_handle h, int pass, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);

@@ -36,7 +36,13 @@ cycle of a PRIVATE SECOND MODEL of dtype F32 with the same configuration and cyc
 include/mgx.h, "bit for bit what a public F32 handle holds after mgx_set_stencil / mgx_set_stencil9 (and
 mgx_build_galerkin_transfer) with the float32 of the handle's coefficients".  The float model is rebuilt by the next
 solve_refine after the operator, the hierarchy or the transfer has changed; set_cycle reaches it at once.  Only U of the
-finest level moves: the cycle runs on the float model's levels, the model's own coarse levels stay as they were."""
+finest level moves: the cycle runs on the float model's levels, the model's own coarse levels stay as they were.
+
+solve_refine_gcr (mgx_solve_refine_gcr) is tests/refine_gcr_ref.py's loop around the model's fp64 finest operator and the
+cycle of THE SAME float model: a solve_refine and a solve_refine_gcr share it, either one rebuilds it.  The loop's residual
+lives in vectors of its own, so B stays the caller's and the coarse levels stay untouched, as for solve_refine; U of the
+finest level is x, also after a breakdown.  time_refine_gcr_pass moves nothing and refuses where the device's guard does:
+until a float model (solve_refine or solve_refine_gcr) AND a GCR basis (solve_gcr or solve_refine_gcr) exist."""
 import numpy as np
 
 import cheby_ref
@@ -47,6 +53,7 @@ import line_ref as lr
 import nine_ref as nr
 import opdep_ref as od
 import pcg_ref
+import refine_gcr_ref
 import refine_ref
 
 JACOBI, RBGS, CHEBYSHEV = 0, 1, 2
@@ -197,6 +204,7 @@ class HandleModel:
         self.h = None
         self.f32 = None                        # solve_refine: the float model, created by the first call ...
         self.f32_of = None                     # ... and the hierarchy (self.h at the time) whose float copy it holds
+        self.basis = False                     # slot 0 of the GCR basis exists: after a solve_gcr or a solve_refine_gcr
         if self.op == POISSON:
             self.h = PoissonOps(self.po, self.L, self.Lc, self.dt, c["restrict_mode"], c["omega"], c["smoother"], c["arith"])
 
@@ -510,6 +518,7 @@ class HandleModel:
             self.vcycle_zero()
             return self.U[self.L]
 
+        self.basis = True
         x, hist, conv, brk = gcr_ref.gcr(self.finest_operator(), M, b, self.U[self.L], tol=tol, max_iters=max_iters, restart=restart, dot=dot)
         self.U[self.L] = np.ascontiguousarray(x, dtype=self.dt)
         self.B[self.L] = b
@@ -580,3 +589,41 @@ class HandleModel:
             raise ValueError("MGX_ERR_INVALID")
         if self.f32 is None:
             raise ValueError("mgx_time_refine_pass: call mgx_solve_refine first")
+
+    # -- mgx_solve_refine_gcr ----------------------------------------------------------------------------------
+    def solve_refine_gcr(self, tol=1e-8, max_iters=100, restart=4, history=None, dot=pcg_ref.dot):
+        """(stats, history): refine_gcr_ref.refine_gcr with the model's fp64 finest operator as A and the zero-start cycle of
+        the float model (solve_refine's: _float_model) as the cycle; fine_updates are the float cycle's.  U[finest] is x
+        afterwards, also after a breakdown (converged = 0, the history stops at the entry before it); B and every other
+        level are untouched; max_iters = 0: one history entry, U untouched.  history: the history a device returned for
+        this call - the scales s_k are derived from IT; dot: the inner product (refine_gcr_ref.device_dot: the device's
+        order of summation).  The stop decision and the history returned stay the model's own.
+        Refused where solve_refine is (_refine_guard); MGX_ERR_INVALID as the device's"""
+        self._refine_guard()
+        if not 1 <= restart <= 8 or not tol >= 0.0 or max_iters < 0:
+            raise ValueError("MGX_ERR_INVALID")
+        f = self._float_model()
+        f.fine_updates = 0.0
+        L = self.L
+
+        def cycle32(r32):
+            f.set_rhs(r32)
+            f.vcycle_zero()
+            return f.U[L]
+
+        self.basis = True
+        x, hist, conv, brk = refine_gcr_ref.refine_gcr(self.finest_operator(), cycle32, self.B[L], self.U[L], tol=tol, max_iters=max_iters,
+                                                       restart=restart, history=history, dot=dot)
+        self.U[L] = np.ascontiguousarray(x, dtype=self.dt)
+        self.fine_updates = f.fine_updates
+        return dict(cycles=len(hist) - 1, converged=int(conv and not brk), fine_updates=self.fine_updates), hist
+
+    def time_refine_gcr_pass(self, which, repeats):
+        """mgx_time_refine_gcr_pass: nothing moves (both passes rewrite buffers that mean nothing between two solves).
+        Refused where solve_refine_gcr is, and - what the device's guard looks at - until the float model AND slot 0 of the
+        GCR basis exist: a solve_refine_gcr creates both, so do a solve_refine and a solve_gcr together"""
+        if which not in (0, 1) or repeats < 1:
+            raise ValueError("MGX_ERR_INVALID")
+        self._refine_guard()
+        if self.f32 is None or not self.basis:
+            raise ValueError("mgx_time_refine_gcr_pass: call mgx_solve_refine_gcr first")

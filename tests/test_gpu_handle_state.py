@@ -132,12 +132,40 @@ after solve_pcg, in the order above: 2.1e-6 / 3.7e-6 / 2.1e-5; 1.3e-6 / 8.3e-6 /
 5.2e-6; 2.0e-6 / 2.2e-6 / 8.3e-7 (solve_gcr there: 2.8e-6 / 1.3e-4); mgx_solve's histories at most 2.2e-6.  The runs under
 MGX_SMALL_VISIT=0, MGX_GRAPH=0 and MGX_GS_FUSED=0 give the same figures to the digit.
 
+REFINE_GCR_CASES add mgx_solve_refine_gcr (csrc/mgx.hip: refine_gcr_run, csrc/mgx_refine_gcr.hpp) and mgx_time_refine_gcr_pass,
+drawn with refine_gcr=True on top of refine and gcr (refine_gcr_stage; what it promises: draw_sequence).  The call shares the float
+copy of the hierarchy - r32, z32, the cached cycle graphs - with mgx_solve_refine, the Krylov workspace, the scalar block and the
+partial sums with mgx_solve_gcr and mgx_solve_pcg, and keeps its residual in B of the finest level for the whole solve.  The model
+(handle_model.HandleModel.solve_refine_gcr: tests/refine_gcr_ref.py around the model's fp64 operator and the float model that
+solve_refine uses) is given the device's history for the scales and refine_gcr_ref.device_dot for the dots, as
+tests/test_gpu_refine_gcr.py's composition is.  touched() is U of the finest level alone, held to RTOL64; B and EVERY other level
+stay bit for bit, which is where the call differs from mgx_solve_gcr; the history is held as mgx_solve_gcr's (RTOL64 h + PCG_FLOOR
+h0), the statistics for equality; mgx_time_refine_gcr_pass moves nothing.
+stencil5_f64_jacobi_8_5_refine_gcr (V(3,2); the first graph user after set_coefficient 100 is a solve_refine, after 1000 a
+solve_refine_gcr of one iteration - the calls stay short where the float cycle diverges); galerkin_f64_jacobi_7_3_smooth_bottom_
+refine_gcr_cycles (V(1,0); set_cycle through CYCLE_ORDER with a call directly after one of them, the transfer-only rebuilds in
+turn through either entry; again with MGX_SMALL_VISIT=0 and with MGX_GRAPH=0: the same final state and histories);
+galerkin_f64_sgs_7_3_nine_refine_gcr (V(1,1), bottom = SMOOTH; set_tensor rot45 -> set_coefficient -> set_stencil9 smooth9:
+k_refine_direction<9>, <5>, <9> on one workspace).  The sequences are 80, 108 and 83 calls long with 9, 12 and 10 calls of
+mgx_solve_refine_gcr and 11, 15 and 11 of mgx_solve_refine.  On the CPU, the model alone with numpy's dots
+(tests/test_handle_model.py::test_the_model_walks_the_refine_gcr_sequences): no history of a solve_refine_gcr increases, every one
+ends below its first entry (0.81 at the slowest: two iterations of GCR(1) under the diverging STENCIL5 cycle), and the lowest
+last / first entry of a Krylov call is 7.6e-4, 1.2e-4, 1.2e-4 (the deep solve_gcr each time).
+Measured on an MI355X, in the order above: 2.8 s, 0.7 s (its three environments together), 0.3 s; 8, 4 and 4 graphs (the STENCIL5 case
+fills the cache and ends in the eager fallback).  Largest deviation as a fraction of its bound, history of solve_refine_gcr / U of
+the finest level after it: 1.3e-7 / 0; 0 / 0; 2.2e-7 / 0 - with the device's order of summation the iterate is the model's bit
+for bit, and only the first history entry, which the device takes from its residual-norm kernel, is summed in another order.
+The other calls there: history of solve / solve_pcg / solve_gcr / solve_refine at most 2.2e-6 / 1.7e-5 / 3.8e-6 / 2.0e-6, written
+state after solve_pcg / solve_gcr at most 3.3e-5 / 3.6e-4 of RTOL64.  The runs under MGX_SMALL_VISIT=0 and MGX_GRAPH=0 give the same
+figures to the digit.
+
 A failing sequence is reproduced from the seed, the step index and the calls so far, which the message carries."""
 import numpy as np
 import pytest
 
 import handle_model as hm
 import nine_ref as nr
+from refine_gcr_ref import device_dot
 from test_gpu_colour import random5
 from test_gpu_line import history_bound
 from test_line_cpu import rule_bound
@@ -154,8 +182,9 @@ K_MAX_GRAPHS = 8                           # kMaxGraphs of csrc/mgx.hip: the cap
 MUS = (0, 1, 2, 3, 5)
 GRAPH_USERS = ("solve", "solve_pcg", "vcycle_zero")
 GCR_USERS = GRAPH_USERS + ("solve_gcr",)     # the sequences drawn with gcr=True
-SOLVES = ("solve", "solve_pcg", "solve_gcr", "solve_refine")  # the calls that return (stats, history)
+SOLVES = ("solve", "solve_pcg", "solve_gcr", "solve_refine", "solve_refine_gcr")  # the calls that return (stats, history)
 KRYLOV = ("solve_pcg", "solve_gcr")
+REFINE_USERS = ("solve_refine", "solve_refine_gcr")          # the graph users that cycle in the float copy of the hierarchy
 OPERATOR_CHANGES = ("set_coefficient", "build_galerkin", "set_stencil", "set_stencil9", "set_tensor", "set_operator")
 GCR_RESTARTS = (1, 2, 3)
 DEEP_GCR = ("solve_gcr", 0.0, 9, 8)          # nine iterations of GCR(8): every slot of the full basis, then slot 0 again
@@ -202,7 +231,7 @@ def kinds_at(calls):
 def graph_users(calls):
     """the kinds of graph user a drawn list holds each five times at least"""
     users = GCR_USERS if any(c[0] == "solve_gcr" for c in calls) else GRAPH_USERS
-    return users + ("solve_refine",) if any(c[0] == "solve_refine" for c in calls) else users
+    return users + tuple(k for k in REFINE_USERS if any(c[0] == k for c in calls))
 
 
 def refine_stage(seed, cfg, out, gcr):
@@ -267,9 +296,11 @@ def refine_stage(seed, cfg, out, gcr):
 
 
 def assert_refine_calls(calls, cfg, gcr=False):
-    """what draw_sequence(refine=True) promises, on the drawn list"""
+    """what draw_sequence(refine=True) promises, on the drawn list.  (With refine_gcr=True, which places its calls later and
+    keeps out of the pairs promised here, a solve_refine_gcr is not counted as a graph user: assert_refine_gcr_calls says
+    which of the two refining calls comes first after an operator change)"""
     L = cfg["finest_level"]
-    users = [i for i, c in enumerate(calls) if c[0] in graph_users(calls)]
+    users = [i for i, c in enumerate(calls) if c[0] in graph_users(calls) and c[0] != "solve_refine_gcr"]
     refines = [i for i, c in enumerate(calls) if c[0] == "solve_refine"]
     assert "solve_refine" in graph_users(calls) and len(refines) >= 5
     counts = [calls[i][2] for i in refines]
@@ -293,8 +324,121 @@ def assert_refine_calls(calls, cfg, gcr=False):
                for i in refines)                                                                               # (f)
 
 
+REFINE_GCR_RESTARTS = GCR_RESTARTS + (8,)
+
+
+def refine_gcr_stage(seed, cfg, out, cycles):
+    """draw_sequence(refine_gcr=True): ("solve_refine_gcr", 0.0, max_iters, restart) and the two ("time_refine_gcr_pass", which, 2)
+    placed INTO a list that refine_stage has been through (drawn with gcr=True), with a generator of its own.  Calls are put
+    between two calls of the list, never between two that a promise of refine_stage keeps together (glued), so those
+    promises still hold, and every promise of draw_sequence's docstring for this option holds by construction.
+    A ("set_guess", seed) stands before a call wherever the promise does not say "directly after"."""
+    rng = np.random.RandomState(seed + 66666)
+    L = cfg["finest_level"]
+    fresh = [0]
+
+    def call(k=None, restart=None, guess=True):
+        k = int(rng.randint(1, 6)) if k is None else k
+        restart = int(rng.choice(GCR_RESTARTS)) if restart is None else restart
+        fresh[0] += 1
+        return ([("set_guess", 5000 + fresh[0])] if guess else []) + [("solve_refine_gcr", 0.0, k, restart)]
+
+    def glued(i):
+        """nothing may be put between out[i - 1] and out[i]"""
+        a, b = out[i - 1], out[i] if i < len(out) else (None,)
+        return (a[0] in ("solve_refine", "time_refine_pass", "set_guess") or (a[0] in OPERATOR_CHANGES and b[0] in OPERATOR_CHANGES)
+                or (a[0] == "vcycle" and b == ("restrict", L)) or (a == ("restrict", L) and b == ("prolong_add", L))
+                or (a == ("prolong_add", L) and b[0] in ("solve_refine", "set_guess")))
+
+    # between an operator change and the graph user after it nothing is put but (a)'s own call: which call rebuilds the float
+    # copy is what (a) decides
+    waiting, pending = [], False
+    for c in out + [(None,)]:
+        waiting.append(pending)
+        pending = c[0] in OPERATOR_CHANGES or (pending and c[0] not in GCR_USERS + ("solve_refine",))
+    put = {}                                               # position in `out` -> the calls that go in front of it
+    free = lambda i: 0 <= i <= len(out) and i not in put and (i == 0 or not glued(i)) and not waiting[i]
+
+    def place(i, calls):
+        assert free(i), (seed, i)
+        put[i] = calls
+        return i
+
+    users = [i for i, c in enumerate(out) if c[0] in GCR_USERS + ("solve_refine",)]
+    # STENCIL5: the cycle of the contrast-1000 hierarchy diverges (refine_stage).  GCR does not, but a solve_refine that
+    # continues from what a call left would: the pair of (c) stands before that change, and the calls after it are short
+    far = [i for i, c in enumerate(out) if cfg.get("op") == hm.STENCIL5 and c[0] == "set_coefficient" and c[1] >= 1000.0]
+    limit = far[0] if far else len(out)
+    gcrs = [i for i, c in enumerate(out) if c[0] == "solve_gcr"]
+    shallow = [i for i in gcrs if out[i][3] != DEEP_GCR[3]]
+    deep = [i for i in gcrs if out[i][3] == DEEP_GCR[3]]
+    # (b): restart 1 directly before a solve_gcr; restart 8, five iterations, directly after a solve_gcr of a short basis (the
+    # call grows the workspace itself; before the diverging change where one stands there); a restart from GCR_RESTARTS, four
+    # iterations, directly after the deep solve_gcr (a short basis in the grown workspace, wrapped)
+    place(deep[0] + 1, call(4, int(rng.choice(GCR_RESTARTS)), guess=False))
+    first = place(next(i for i in shallow if free(i)), call(restart=1))
+    grow = [i + 1 for i in shallow if i >= first and free(i + 1)]
+    place(next((i for i in grow if i <= limit), grow[0]), call(5, 8, guess=False))
+    # (e): both timing passes after the first call; DIRECTION directly before a solve_gcr, UPDATE directly before a call
+    place(int(rng.choice([i for i in shallow if i > first and free(i)])), [("time_refine_gcr_pass", 1, 2)])
+    later = [i for i in range(first + 1, len(out) + 1) if free(i)]
+    place(int(rng.choice(later)), [("set_guess", 5900), ("time_refine_gcr_pass", 0, 2)] + call(guess=False))
+    # (d): a drawn solve and a drawn solve_pcg directly after a call
+    for name in ("solve", "solve_pcg"):
+        if not any(i < len(out) and out[i][0] == name and put[i][-1][0] == "solve_refine_gcr" for i in put):    # (a call of (b), (e) may do)
+            place(int(rng.choice([i for i, c in enumerate(out) if c[0] == name and free(i)])), call())
+    # (c): a solve_refine between two calls, no set_guess between the three
+    early = [i for i in range(users[0] + 1, limit) if free(i)]
+    place(int(rng.choice(early)), call(int(rng.choice([2, 3]))) + [("solve_refine", 0.0, 2)] + call(int(rng.choice([2, 3])), guess=False))
+    # (f): a call that runs no iteration
+    place(int(rng.choice([i for i in range(users[0] + 1, len(out)) if free(i)])), [("solve_refine_gcr", 0.0, 0, 2)])
+    # (g): directly after a set_cycle
+    if cycles:
+        place(int(rng.choice([i + 1 for i, c in enumerate(out) if c[0] == "set_cycle" and free(i + 1)])), call(guess=False))
+    # (a): the first graph user after every second group of operator changes (the others: refine_stage's solve_refine)
+    ends = [i for i, c in enumerate(out) if c[0] in OPERATOR_CHANGES and (i + 1 == len(out) or out[i + 1][0] not in OPERATOR_CHANGES)]
+    for i in ends[1::2]:
+        assert (i + 1) not in put and not glued(i + 1), (seed, i)
+        put[i + 1] = call()
+    for i in sorted(put, reverse=True):
+        out = out[:i] + put[i] + out[i:]
+    flat, diverging = [], False
+    for c in out:
+        diverging = diverging or (cfg.get("op") == hm.STENCIL5 and c[0] == "set_coefficient" and c[1] >= 1000.0)
+        flat.append(c[:2] + (2 - c[2] % 2,) + c[3:] if diverging and c[0] == "solve_refine_gcr" and c[2] > 2 else c)
+    return flat
+
+
+def assert_refine_gcr_calls(calls, cfg, cycles=False):
+    """what draw_sequence(refine_gcr=True) promises, on the drawn list"""
+    at = [i for i, c in enumerate(calls) if c[0] == "solve_refine_gcr"]
+    assert len(at) >= 5 and all(calls[i][1] == 0.0 and 0 <= calls[i][2] <= 5 and calls[i][3] in REFINE_GCR_RESTARTS for i in at)
+    before = lambda i: calls[i - 1]
+    after = lambda i: calls[i + 1] if i + 1 < len(calls) else (None,)
+    users = [i for i, c in enumerate(calls) if c[0] in graph_users(calls)]
+    ends = [i for i in range(users[0], len(calls)) if calls[i][0] in OPERATOR_CHANGES and after(i)[0] not in OPERATOR_CHANGES]
+    firsts = [next(calls[u][0] for u in users if u > i) for i in ends]
+    assert len(firsts) >= 2 and firsts == [REFINE_USERS[g % 2] for g in range(len(firsts))], firsts                            # (a)
+    is_deep = lambda c: c[0] == "solve_gcr" and c[3] == DEEP_GCR[3]
+    assert any(after(i)[0] == "solve_gcr" and calls[i][3] == 1 for i in at)                                                   # (b)
+    assert any(before(i)[0] == "solve_gcr" and not is_deep(before(i)) and calls[i][3] == 8 for i in at)
+    assert any(is_deep(before(i)) and calls[i][3] in GCR_RESTARTS for i in at)
+    assert any(c[0] == "solve_refine" and c[2] >= 1 and before(i)[0] == after(i)[0] == "solve_refine_gcr" for i, c in enumerate(calls))   # (c)
+    for name in ("solve", "solve_pcg"):                                                                                       # (d)
+        assert any(after(i)[0] == name for i in at), name
+    timed = [i for i, c in enumerate(calls) if c[0] == "time_refine_gcr_pass"]                                                # (e)
+    assert sorted(calls[i][1:] for i in timed) == [(0, 2), (1, 2)] and min(timed) > at[0]
+    assert {calls[i][1]: after(i)[0] for i in timed} == {1: "solve_gcr", 0: "solve_refine_gcr"}
+    assert sum(1 for i in at if calls[i][2] == 0) == 1                                                                        # (f)
+    if cycles:
+        assert any(before(i)[0] == "set_cycle" for i in at)                                                                   # (g)
+    # a fresh guess wherever no promise says "directly after"
+    bare = [i for i in at if before(i)[0] != "set_guess"]
+    assert all(before(i)[0] in ("solve_gcr", "solve_refine", "set_cycle", "time_refine_gcr_pass") or calls[i][2] == 0 for i in bare), bare
+
+
 def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_guess=False, short_solves=False, without=(), tail=(), gcr=False, deep_iters=DEEP_GCR[2],
-                  refine=False):
+                  refine=False, refine_gcr=False):
     """~n_steps calls, every one valid for `cfg` by construction (nothing is filtered afterwards): the three graph
     users (four with gcr) five times each at least, an odd-launch smooth on every level at least once, the rest drawn with weights;
     mu from MUS.  Operator changes of the general hierarchies are placed after every third graph user.
@@ -326,8 +470,25 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
                  (d) a solve directly follows time_refine_pass;
                  (e) solve_pcg, and with gcr solve_gcr, directly follows a solve_refine once;
                  (f) a ("vcycle", level) from a coarse level, ("restrict", finest) and ("prolong_add", finest) stand between
-                     two refines"""
-    assert not (refine and fresh_guess)
+                     two refines
+    refine_gcr   (with refine and gcr) ("solve_refine_gcr", 0.0, max_iters, restart) as one more graph user and
+                 ("time_refine_gcr_pass", which, 2) for both passes (refine_gcr_stage): tol 0, so the count is the work done,
+                 1 .. 5 iterations, restart from GCR_RESTARTS and 8; a fresh ("set_guess", seed) before a call wherever no
+                 promise says "directly".  Held by construction (assert_refine_gcr_calls):
+                 (a) the first graph user after the groups of operator changes is in turn a solve_refine and a
+                     solve_refine_gcr: the float copy is rebuilt through either entry;
+                 (b) a call with restart 1 directly before a solve_gcr; a call with restart 8 directly after a solve_gcr of
+                     a short basis (the call grows the workspace); a call with a restart from GCR_RESTARTS directly after
+                     the deep solve_gcr (a short basis, wrapped, in the grown workspace);
+                 (c) a call directly before and a call directly after one solve_refine, no set_guess between the three
+                     (the same r32 / z32 and cycle graphs; the second call starts from what the first two left);
+                 (d) a solve and a solve_pcg each directly follow a call once (norm_blocks_ready, the partial sums, the
+                     scalar block);
+                 (e) both timing passes after the first call: DIRECTION (basis slot 0 rewritten) directly before a
+                     solve_gcr, UPDATE (the float right-hand side rewritten, the scalars zeroed) directly before a call;
+                 (f) one call with max_iters = 0;
+                 (g) with cycles: a call directly after a set_cycle"""
+    assert not (refine and fresh_guess) and (not refine_gcr or (refine and gcr))
     rng = np.random.RandomState(seed)
     L, Lc = cfg["finest_level"], cfg["coarsest_level"]
     f64 = cfg.get("dtype", hm.F64) == hm.F64
@@ -415,6 +576,8 @@ def draw_sequence(seed, cfg, n_steps=40, cycles=False, operators=None, fresh_gue
                 out.insert(first[-1], ("set_guess", 3500))
     if refine:
         out = refine_stage(seed, cfg, out, gcr)
+    if refine_gcr:
+        out = refine_gcr_stage(seed, cfg, out, cycles)
     if fresh_guess:
         fresh = []
         for c in out:
@@ -479,8 +642,12 @@ def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
         return mg.solve_gcr(tol=a[0], max_iters=a[1], restart=a[2])
     if name == "solve_refine":
         return mg.solve_refine(tol=a[0], max_cycles=a[1])
+    if name == "solve_refine_gcr":
+        return mg.solve_refine_gcr(tol=a[0], max_iters=a[1], restart=a[2])
     if name == "time_refine_pass":
         assert mg.time_refine_pass(a[0]) > 0.0
+    elif name == "time_refine_gcr_pass":
+        assert mg.time_refine_gcr_pass(a[0], a[1]) > 0.0
     elif name == "vcycle_zero":
         mg.vcycle_zero()
     elif name == "smooth":
@@ -536,13 +703,20 @@ def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
     return None
 
 
-def apply_model(m, call, L, device=None):
+def apply_model(m, call, L, device=None, rows=0):
     """device: what apply_device returned for this call.  solve_refine takes its scales s_k from the history the device
     reported (a norm is the one place where the device's order of summation reaches the iterate), as
-    tests/test_gpu_refine.py's composition does; everything else about the call is the model's own"""
+    tests/test_gpu_refine.py's composition does; everything else about the call is the model's own.  solve_refine_gcr takes
+    the scales the same way and, beside a device, sums its dots in the device's order (refine_gcr_ref.device_dot with the
+    rows per chunk of the handle, rows: MGX_ROWS when the handle was created, 0 for make_launch's own choice), as
+    tests/test_gpu_refine_gcr.py's composition does; without a device numpy's order"""
     name, a = call[0], call[1:]
     if name == "solve_refine":
         return m.solve_refine(tol=a[0], max_cycles=a[1], history=None if device is None else device[1])
+    if name == "solve_refine_gcr":
+        if device is None:
+            return m.solve_refine_gcr(tol=a[0], max_iters=a[1], restart=a[2])
+        return m.solve_refine_gcr(tol=a[0], max_iters=a[1], restart=a[2], history=device[1], dot=lambda p, q: device_dot(p, q, rows))
     if name == "solve":
         return m.solve(tol=a[0], max_cycles=a[1])
     if name == "solve_pcg":
@@ -578,6 +752,8 @@ def state_tolerance(cfg, call):
     f64 = cfg.get("dtype", hm.F64) == hm.F64
     if name in KRYLOV:
         return RTOL64 if f64 else PCG32_STATE
+    if name == "solve_refine_gcr":                          # (F64 handles only; U of the finest level: touched)
+        return RTOL64
     sine_bottom = cfg.get("op", hm.POISSON) == hm.POISSON and cfg.get("bottom", hm.EXACT) == hm.EXACT
     if not sine_bottom:
         return 0.0
@@ -593,7 +769,9 @@ def touched(cfg, call):
         return {(Lc, "U")}
     if name == "smooth":
         return {(call[1], "U")} if call[2] else set()
-    top = call[1] if name == "vcycle" else L                # vcycle_zero, fmg, solve, solve_pcg, solve_gcr: from the finest level
+    if name == "solve_refine_gcr":                          # the iterate alone: B holds the residual during the solve and the caller's
+        return {(L, "U")}                                   # b again after it, the cycle runs in the float copy - bit for bit
+    top =call[1] if name == "vcycle" else L                # vcycle_zero, fmg, solve, solve_pcg, solve_gcr: from the finest level
     return {(top, "U")} | {(lv, x) for lv in range(Lc, top) for x in ("U", "B")}
 
 
@@ -620,6 +798,7 @@ class Tally:
         self.state = 0.0                                   # largest relative state deviation through the sine-transform bottom solve
         self.state_pcg = 0.0                               # ... after mgx_solve_pcg
         self.state_gcr = 0.0                               # ... after mgx_solve_gcr
+        self.state_refine_gcr = 0.0                        # ... of U[finest] after mgx_solve_refine_gcr
         self.graph_counts = []
         self.histories = []                                # of the device, in call order
         self.final = None                                  # U and B of every level after the last call
@@ -627,12 +806,13 @@ class Tally:
         self.ratio = 0.0                                   # ... and the largest device deviation / its bound
 
 
-def step(pkg, mg, m, cfg, call, tally, where):
-    """one call on both sides, then every level's U and B, the history and the statistics"""
+def step(pkg, mg, m, cfg, call, tally, where, rows=0):
+    """one call on both sides, then every level's U and B, the history and the statistics.  rows: MGX_ROWS of the
+    environment the handle was created under (apply_model)"""
     L, Lc = cfg["finest_level"], cfg["coarsest_level"]
     g_before = mg.graphs_cached()
     got = apply_device(pkg, mg, call, L, hm.BILINEAR if m.transfer is None else m.transfer)
-    want = apply_model(m, call, L, got)
+    want = apply_model(m, call, L, got, rows)
     tally.executed += 1
     if call[0] == "set_cycle":                             # the graph key carries no kind: the setter has to drop the graphs
         assert mg.cycle == m.cycle == call[1], where()
@@ -664,6 +844,8 @@ def step(pkg, mg, m, cfg, call, tally, where):
                     tally.state_pcg = max(tally.state_pcg, dev)
                 elif call[0] == "solve_gcr":
                     tally.state_gcr = max(tally.state_gcr, dev)
+                elif call[0] == "solve_refine_gcr":
+                    tally.state_refine_gcr = max(tally.state_refine_gcr, dev)
                 else:
                     tally.state = max(tally.state, dev)
                 assert dev <= rtol, f"{name} of level {lv} off by {dev:.3g} (bound {rtol:g}); {where()}"
@@ -685,7 +867,7 @@ def run_sequence(pkg, po, cfg, calls, seed, env=None):
     with pkg.Multigrid(**cfg) as mg:
         for call in calls:
             done.append(call)
-            step(pkg, mg, m, cfg, call, tally, where)
+            step(pkg, mg, m, cfg, call, tally, where, int((env or {}).get("MGX_ROWS", 0)))
         tally.final = all_levels(pkg, mg, cfg["finest_level"], cfg["coarsest_level"])
     assert tally.executed == len(calls)                    # nothing skipped, nothing filtered
     users = {k: sum(1 for c in calls if c[0] == k) for k in graph_users(calls)}
@@ -693,9 +875,11 @@ def run_sequence(pkg, po, cfg, calls, seed, env=None):
     krylov_bound = RTOL64 if cfg.get("dtype", hm.F64) == hm.F64 else PCG32_STATE
     print(f"\n[handle-state] cfg={cfg} env={env} seed={seed} steps={tally.executed} graph_users={users} "
           f"max_graphs={tally.graphs} hist_solve={tally.hist['solve']:.3g}xbound hist_pcg={tally.hist['solve_pcg']:.3g}xbound "
-          f"hist_gcr={tally.hist['solve_gcr']:.3g}xbound hist_refine={tally.hist['solve_refine']:.3g}xbound state_dev_bottom={tally.state:.3g} "
+          f"hist_gcr={tally.hist['solve_gcr']:.3g}xbound hist_refine={tally.hist['solve_refine']:.3g}xbound "
+          f"hist_refine_gcr={tally.hist['solve_refine_gcr']:.3g}xbound state_dev_bottom={tally.state:.3g} "
           f"state_dev_pcg={tally.state_pcg:.3g} ({tally.state_pcg / krylov_bound:.3g}xbound) state_dev_gcr={tally.state_gcr:.3g} "
-          f"({tally.state_gcr / krylov_bound:.3g}xbound) graphs={tally.graph_counts}")
+          f"({tally.state_gcr / krylov_bound:.3g}xbound) state_dev_refine_gcr={tally.state_refine_gcr:.3g} "
+          f"({tally.state_refine_gcr / RTOL64:.3g}xbound) graphs={tally.graph_counts}")
     return tally
 
 
@@ -789,7 +973,7 @@ def assert_cycle_calls(calls, cfg):
     sets = [i for i, c in enumerate(calls) if c[0] == "set_cycle"]
     assert tuple(calls[i][1] for i in sets) == CYCLE_ORDER
     for k, i in enumerate(sets):                           # after every second graph user (an operator change may stand between;
-        assert sum(1 for u in users if u < i and calls[u][0] != "solve_refine") == 2 * (k + 1), (k, i)      # refines are placed later)
+        assert sum(1 for u in users if u < i and calls[u][0] not in REFINE_USERS) == 2 * (k + 1), (k, i)    # refines are placed later)
     kinds = kinds_at(calls)
     for lv in small_levels(cfg):
         for kind in (hm.CYCLE_W, hm.CYCLE_F):
@@ -1309,6 +1493,53 @@ def test_refine_sequences_match_the_model_after_every_call(pkg, po, monkeypatch,
         assert_cycle_calls(calls, cfg)
     if options.get("gcr"):
         assert_gcr_calls(calls, cfg)
+    runs = []
+    for env in envs:
+        set_knobs(monkeypatch, env)
+        tally = run_sequence(pkg, po, cfg, calls, seed, env)
+        assert tally.graphs == -1 if env == EAGER else 1 <= tally.graphs <= K_MAX_GRAPHS, tally.graphs
+        runs.append(tally)
+    for b, env in zip(runs[1:], envs[1:]):
+        for x, y in zip(runs[0].final, b.final):
+            assert np.array_equal(x, y), env
+        assert len(runs[0].histories) == len(b.histories) and all(np.array_equal(x, y) for x, y in zip(runs[0].histories, b.histories)), env
+
+
+# ---- 2g. mgx_solve_refine_gcr among the graph users ------------------------------------------------------------------
+REFINE_GCR_OPTIONS = dict(refine=True, gcr=True, refine_gcr=True, n_steps=30)
+REFINE_GCR_CASES = {
+    # name: (configuration, seed, environments, generator options).  All double.  The deep solve_gcr must stay out of the
+    # cancellation regime of b - A u (GCR_CASES): weak smoothing in the GALERKIN cases.  The STENCIL5 case keeps V(3,2), as in
+    # REFINE_CASES: its deep call comes after set_coefficient 1000, where GCR converges slowly (7.6e-4 over nine iterations),
+    # and under V(1,0) a solve_refine of two cycles there grows from a fresh guess (x 5), which refine_stage relies on not
+    # happening.  Every level of the float copy is rewritten by set_coefficient 100 (first user: solve_refine) and 1000
+    # (solve_refine_gcr)
+    "stencil5_f64_jacobi_8_5_refine_gcr": (dict(P85, op=hm.STENCIL5), 8601, [{}], {}),
+    # set_cycle through CYCLE_ORDER, the transfer-only rebuilds; the same bits without the visit kernel and without graphs
+    "galerkin_f64_jacobi_7_3_smooth_bottom_refine_gcr_cycles": (dict(G73_WEAK, bottom=hm.SMOOTH), 8602, [{}, NO_VISIT, EAGER], dict(cycles=True)),
+    # k_refine_direction<9> -> <5> -> <9> on one workspace: set_tensor, set_coefficient, set_stencil9
+    "galerkin_f64_sgs_7_3_nine_refine_gcr": (
+        dict(G73, mu1=1, mu2=1, smoother=hm.COLOR_SGS, bottom=hm.SMOOTH), 8603, [{}],
+        dict(deep_iters=5, operators=("rot45", [[("set_coefficient", 100.0, 11), ("build_galerkin", hm.BILINEAR)],
+                                                [("set_stencil9", "smooth9"), ("build_galerkin", hm.BILINEAR)]]))),
+}
+
+
+@pytest.mark.parametrize("name", list(REFINE_GCR_CASES))
+def test_refine_gcr_sequences_match_the_model_after_every_call(pkg, po, monkeypatch, name):
+    """mgx_solve_refine_gcr as one more graph user of a long-lived handle.  It shares the float copy of the hierarchy (r32,
+    z32, the cached cycle graphs) with mgx_solve_refine, the Krylov workspace, the scalar block and the partial sums with
+    mgx_solve_gcr and mgx_solve_pcg, and keeps its residual in B of the finest level while it runs.  After every call U
+    of the finest level to RTOL64 against the model (its dots summed in the device's order, its scales from the device's
+    history), B and EVERY other level bit for bit - the call moves nothing else, which is where it differs from mgx_solve_gcr -
+    the history as mgx_solve_gcr's, the statistics equal; mgx_time_refine_gcr_pass moves nothing"""
+    cfg, seed, envs, options = REFINE_GCR_CASES[name]
+    calls = draw_sequence(seed, cfg, **REFINE_GCR_OPTIONS, **options)
+    assert_refine_calls(calls, cfg, True)
+    assert_refine_gcr_calls(calls, cfg, options.get("cycles", False))
+    assert_gcr_calls(calls, cfg, False, options.get("deep_iters", DEEP_GCR[2]))
+    if options.get("cycles"):
+        assert_cycle_calls(calls, cfg)
     runs = []
     for env in envs:
         set_knobs(monkeypatch, env)

@@ -1440,3 +1440,256 @@ def test_the_model_walks_the_refine_sequences(po, name):
     print(f"\n[handle-state] model alone: {name} steps={len(calls)} lowest last/first of a Krylov call={lowest[0]:.3g} at {lowest[1]}; "
           f"highest last/first of a solve_refine={slowest[0]:.3g} at {slowest[1]}")
     assert 1e-6 <= lowest[0] < 1.0, lowest
+
+
+# ---- solve_refine_gcr -----------------------------------------------------------------------------------------------------
+REFINE_GCR_REFS = ["stencil5-jacobi", "galerkin-bilinear", "galerkin-operator", "nine-point", "colour-sgs", "w-cycle", "bottom-smooth"]
+
+
+@pytest.mark.parametrize("name", REFINE_GCR_REFS)
+def test_solve_refine_gcr_equals_refine_gcr_ref_around_independent_hierarchies(po, name):
+    """iterate and history bit for bit against refine_gcr_ref.refine_gcr over reference hierarchies built independently of
+    the model - A from the float64 one's residual (the sign flip is exact), the cycle from the float32 one; B (the same
+    array) and every coarse level untouched; fine_updates those of the float cycle; the stop by the tolerance;
+    max_iters = 0; a history and a dot handed in are passed through"""
+    import refine_gcr_ref as rg
+    L, Lc = 6, 3
+    cfg, give, (h64, h32) = refine_references(po, name, L, Lc)
+    assert all(x.dtype == np.float32 for x in h32.st[L]) and all(x.dtype == np.float64 for x in h64.st[L])
+    u, b = data(po, L, np.float64, 61)
+    zero = np.zeros_like(b)
+    A = lambda v: -h64.residual(L, v, zero)
+    cycle32 = gcr_ref.cycle_preconditioner(h32)
+    m = hm.HandleModel(po, **cfg)
+    give(m)
+    for lv in m.levels():
+        if lv < L:
+            m.set_level(lv, 0, data(po, lv, np.float64, 70 + lv)[0])
+            m.set_level(lv, 1, data(po, lv, np.float64, 80 + lv)[0])
+    coarse = {lv: (m.U[lv], m.B[lv]) for lv in m.levels() if lv < L}
+    n2 = float((1 << L) - 1) ** 2
+    for tol, k, restart in ((0.0, 5, 3), (1e-2, 30, 4), (0.0, 3, 1), (0.5, 0, 2)):
+        x_ref, h_ref, conv, brk = rg.refine_gcr(A, cycle32, b, u, tol, k, restart)
+        m.set_guess(u)
+        m.set_rhs(b)
+        held = m.B[L]
+        st, h = m.solve_refine_gcr(tol=tol, max_iters=k, restart=restart)
+        assert not brk and np.array_equal(h, h_ref) and np.array_equal(m.U[L], x_ref) and m.U[L].dtype == np.float64, (name, tol, k, restart)
+        assert m.B[L] is held and np.array_equal(m.B[L], b)
+        assert st == dict(cycles=len(h_ref) - 1, converged=int(conv), fine_updates=(len(h_ref) - 1) * 3.0 * n2), st
+        assert np.all(h[1:] <= h[:-1])
+        for lv, (uu, bb) in coarse.items():
+            assert m.U[lv] is uu and m.B[lv] is bb, lv
+    assert len(h) == 1 and np.array_equal(m.U[L], u) and st["converged"] == 0          # max_iters = 0
+    # a history handed in gives the scales, a dot the scalars, and nothing else
+    _, h5 = m.solve_refine_gcr(tol=0.0, max_iters=5, restart=3)
+    far = h5 * 2.0 ** 120
+    for kw in (dict(history=far), dict(dot=gcr_ref.dot_reversed), dict(history=h5, dot=rg.device_dot)):
+        m.set_guess(u)
+        st, h = m.solve_refine_gcr(tol=0.0, max_iters=5, restart=3, **kw)
+        x_ref, h_ref, _, _ = rg.refine_gcr(A, cycle32, b, u, 0.0, 5, 3, **kw)
+        assert st["cycles"] == 5 and np.array_equal(m.U[L], x_ref) and np.array_equal(h, h_ref), kw
+        assert not np.array_equal(h, h5), kw
+    m.set_guess(u)
+    assert np.array_equal(m.solve_refine_gcr(tol=0.0, max_iters=5, restart=3, history=h5)[1], h5)       # its own history: the same call
+
+
+def refined_gcr(m, u, b, k=4, restart=3):
+    m.set_guess(u)
+    m.set_rhs(b)
+    st, h = m.solve_refine_gcr(tol=0.0, max_iters=k, restart=restart)
+    return st, h, m.U[m.L].copy()
+
+
+def test_solve_refine_gcr_follows_operator_transfer_and_cycle_changes_and_shares_the_float_model(po):
+    """operator A -> call -> operator B -> call -> the other transfer -> call -> set_cycle(W) -> call on ONE model, a
+    solve_refine before every second of them: every call is that of a fresh model in the same state, and the float model
+    is one object for both entry points - rebuilt by whichever comes first after a change"""
+    L, Lc = 6, 3
+    cfg = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=2, mu2=1, op=hm.GALERKIN, schedule=hm.V)
+    a1, a2 = contrast(L, 10.0, 1), contrast(L, 100.0, 2)
+    u, b = data(po, L, np.float64, 62)
+    steps = [lambda m: (m.set_coefficient(a1), m.build_galerkin(hm.BILINEAR)), lambda m: (m.set_coefficient(a2), m.build_galerkin(hm.BILINEAR)),
+             lambda m: m.build_galerkin(hm.OPERATOR), lambda m: m.set_cycle(hm.CYCLE_W)]
+    one = hm.HandleModel(po, **cfg)
+    seen, floats = [], []
+    for i, change in enumerate(steps):
+        change(one)
+        if i % 2:                                           # solve_refine rebuilds the float model, the call finds it current
+            refined(one, u, b)
+            shared = one.f32
+        st, h, x = refined_gcr(one, u, b)
+        assert i % 2 == 0 or one.f32 is shared
+        floats.append(one.f32)
+        fresh = hm.HandleModel(po, **cfg)
+        for earlier in steps[:i + 1]:
+            if not (i >= 1 and earlier is steps[0]):        # (operator A is overwritten by B)
+                earlier(fresh)
+        st_f, h_f, x_f = refined_gcr(fresh, u, b)
+        assert st == st_f and np.array_equal(h, h_f) and np.array_equal(x, x_f), i
+        assert all(not np.array_equal(x, y) for y in seen), i
+        seen.append(x)
+        # ... and the solve_refine after it is a fresh model's too: the call left the float model as solve_refine needs it
+        s2, h2, x2 = refined(one, u, b)
+        s2f, h2f, x2f = refined(fresh, u, b)
+        assert s2 == s2f and np.array_equal(h2, h2f) and np.array_equal(x2, x2f) and one.f32 is floats[-1], i
+    assert floats[0] is not floats[1] and floats[1] is not floats[2]       # rebuilt after an operator and after a transfer change
+    assert floats[2] is floats[3] and one.f32.cycle == hm.CYCLE_W            # set_cycle reaches it at once, nothing is rebuilt
+    assert one.f32.cfg["dtype"] == hm.F32 and one.f32.transfer == hm.OPERATOR
+
+
+def test_solve_refine_gcr_and_its_timing_call_refuse_where_the_device_does(po):
+    L, Lc = 5, 3
+    base = dict(finest_level=L, coarsest_level=Lc, mu0=0, mu1=1, mu2=1, schedule=hm.V)
+    a = contrast(L, 10.0, 1)
+    for m in (hm.HandleModel(po, **base), hm.HandleModel(po, dtype=hm.F32, **base)):                        # POISSON
+        with pytest.raises(ValueError):
+            m.solve_refine_gcr(1e-8, 3, 2)
+        with pytest.raises(ValueError):
+            m.time_refine_gcr_pass(0, 2)
+    m = hm.HandleModel(po, op=hm.STENCIL5, dtype=hm.F32, **base)
+    m.set_coefficient(a)
+    with pytest.raises(ValueError):
+        m.solve_refine_gcr(1e-8, 3, 2)
+    m = hm.HandleModel(po, op=hm.GALERKIN, **base)
+    with pytest.raises(ValueError):
+        m.solve_refine_gcr(1e-8, 3, 2)                      # unset
+    m.set_coefficient(a)
+    with pytest.raises(ValueError):
+        m.solve_refine_gcr(1e-8, 3, 2)                      # unbuilt
+    m.build_galerkin()
+    u, b = data(po, L, np.float64, 64)
+    m.set_rhs(b)
+    m.set_guess(u)
+    for kw in (dict(restart=0), dict(restart=9), dict(tol=-1.0), dict(tol=float("nan")), dict(max_iters=-1)):
+        with pytest.raises(ValueError, match="MGX_ERR_INVALID"):
+            m.solve_refine_gcr(**dict(dict(tol=1e-8, max_iters=3, restart=2), **kw))
+    assert np.array_equal(m.U[L], u) and m.f32 is None      # a refused call has touched nothing
+    # the timing call: the float model AND slot 0 of the basis - what the device's guard looks at, not which call made them
+    with pytest.raises(ValueError):
+        m.time_refine_gcr_pass(0, 2)
+    m.solve_refine(0.0, 1)
+    with pytest.raises(ValueError):
+        m.time_refine_gcr_pass(0, 2)                        # the float model alone
+    m.solve_gcr(0.0, 1, 1)
+    state = lambda: [m.U[lv] for lv in m.levels()] + [m.B[lv] for lv in m.levels()]
+    before = state()
+    for which in (0, 1):
+        m.time_refine_gcr_pass(which, 2)                    # solve_refine + solve_gcr: accepted, as the device does
+    assert all(p is q for p, q in zip(before, state()))     # nothing moves
+    for which, reps in ((2, 1), (-1, 1), (0, 0)):
+        with pytest.raises(ValueError, match="MGX_ERR_INVALID"):
+            m.time_refine_gcr_pass(which, reps)
+    other = hm.HandleModel(po, op=hm.GALERKIN, **base)
+    other.set_coefficient(a)
+    other.build_galerkin()
+    other.set_rhs(b)
+    other.solve_gcr(0.0, 1, 1)
+    with pytest.raises(ValueError):
+        other.time_refine_gcr_pass(1, 2)                    # the basis alone
+    assert other.solve_refine_gcr(0.0, 0, 1)[0]["cycles"] == 0
+    other.time_refine_gcr_pass(1, 2)                        # a call of no iteration has created both
+    other.set_coefficient(a)
+    with pytest.raises(ValueError):
+        other.time_refine_gcr_pass(1, 2)                    # invalid again until the build
+    for line in hm.LINES:                                   # not modelled, and the message says so
+        m = hm.HandleModel(po, op=hm.GALERKIN, smoother=line, **base)
+        m.set_operator("layers")
+        with pytest.raises(ValueError, match="not modelled"):
+            m.solve_refine_gcr(1e-8, 3, 2)
+
+
+def test_a_breakdown_leaves_the_model_where_the_device_is_left(po):
+    """tests/test_gpu_refine_gcr.py's breakdown: no smoothing, full weighting of a checkerboard is zero at every coarse
+    point, so the float cycle returns zero and q'.q' = 0 at iteration 1 - one history entry, U the guess, converged 0"""
+    L, Lc = 6, 3
+    m = hm.HandleModel(po, finest_level=L, coarsest_level=Lc, mu0=0, mu1=0, mu2=0, schedule=hm.V, op=hm.GALERKIN)
+    m.set_coefficient(contrast(L, 10.0, 1))
+    m.build_galerkin()
+    n = m.n(L)
+    i = np.arange(n)
+    b = np.where((i[:, None] + i[None, :]) % 2 == 0, 1.0, -1.0)
+    m.set_rhs(b)
+    m.set_guess(np.zeros((n, n)))
+    st, h = m.solve_refine_gcr(0.0, 6, 4)
+    assert st == dict(cycles=0, converged=0, fine_updates=0.0) and np.array_equal(h, [float(n)]) and not m.U[L].any() and np.array_equal(m.B[L], b)
+    m.set_guess(data(po, L, np.float64, 65)[0])             # a residual that is no checkerboard: the exit depends on it alone
+    st, h = m.solve_refine_gcr(0.0, 3, 4)
+    assert st["cycles"] == 3 and h[-1] < h[0]
+
+
+def test_refine_gcr_sequences_hold_what_the_generator_promises():
+    seeds = [c[1] for d in (gs.POISSON_CASES, gs.GENERAL_CASES, gs.CYCLE_CASES, gs.LINE_CASES, gs.GCR_CASES, gs.COLOUR_CASES, gs.NINE_CASES, gs.REFINE_CASES,
+                            gs.REFINE_GCR_CASES) for c in d.values()]
+    assert len(set(seeds)) == len(seeds)
+    stage = ("solve_refine_gcr", "time_refine_gcr_pass")
+    # off by default: no sequence drawn without the option holds either call
+    for cfg, seed, envs, options in gs.REFINE_CASES.values():
+        assert not any(c[0] in stage for c in gs.draw_sequence(seed, cfg, **gs.REFINE_OPTIONS, **options))
+    for name, (cfg, seed, envs, options) in gs.REFINE_GCR_CASES.items():
+        calls = gs.draw_sequence(seed, cfg, **gs.REFINE_GCR_OPTIONS, **options)
+        assert calls == gs.draw_sequence(seed, cfg, **gs.REFINE_GCR_OPTIONS, **options)
+        assert cfg.get("dtype", hm.F64) == hm.F64 and envs[0] == {}
+        cycles = options.get("cycles", False)
+        gs.assert_refine_gcr_calls(calls, cfg, cycles)
+        gs.assert_refine_calls(calls, cfg, True)            # the stage keeps out of what refine_stage promised ...
+        gs.assert_gcr_calls(calls, cfg, False, options.get("deep_iters", gs.DEEP_GCR[2]))
+        if cycles:
+            gs.assert_cycle_calls(calls, cfg)
+        assert gs.graph_users(calls) == gs.GCR_USERS + gs.REFINE_USERS
+        assert min(sum(1 for c in calls if c[0] == k) for k in gs.graph_users(calls)) >= 5
+        # ... and without the option the list is the same with the stage's calls taken out: its calls, their fresh guesses,
+        # and the one solve_refine of promise (c)
+        plain = gs.draw_sequence(seed, cfg, **dict(gs.REFINE_GCR_OPTIONS, refine_gcr=False), **options)
+        mid = [j for j, c in enumerate(calls) if c == ("solve_refine", 0.0, 2) and calls[j - 1][0] == calls[j + 1][0] == "solve_refine_gcr"]
+        assert len(mid) == 1
+        rest = [c for j, c in enumerate(calls) if j != mid[0] and c[0] not in stage and not (c[0] == "set_guess" and 5000 < c[1] < 6000)]
+        assert rest == plain, name
+        if cfg["op"] == hm.STENCIL5:
+            assert [c[1] for c in calls if c[0] == "set_coefficient"] == [10.0, 100.0, 1000.0]
+            far = next(i for i, c in enumerate(calls) if c[0] == "set_coefficient" and c[1] == 1000.0)
+            assert all(c[2] <= 2 for c in calls[far:] if c[0] == "solve_refine_gcr")           # short where the cycle diverges
+        if cfg.get("bottom", hm.EXACT) == hm.EXACT:         # the float dense solve: held by an F32 sequence for STENCIL5 at level 5 only
+            assert cfg["op"] == hm.STENCIL5 and cfg["coarsest_level"] == 5
+    c = gs.REFINE_GCR_CASES["galerkin_f64_jacobi_7_3_smooth_bottom_refine_gcr_cycles"]
+    assert c[2] == [{}, {"MGX_SMALL_VISIT": "0"}, {"MGX_GRAPH": "0"}] and c[0]["bottom"] == hm.SMOOTH and c[3] == dict(cycles=True)
+    c = gs.REFINE_GCR_CASES["galerkin_f64_sgs_7_3_nine_refine_gcr"]
+    calls = gs.draw_sequence(c[1], c[0], **gs.REFINE_GCR_OPTIONS, **c[3])
+    assert calls[0] == ("set_operator", "rot45") and [gs.point_counts(calls)[i] for i in gs.flips(calls)] == [5, 9]
+    assert [x[0] for x in calls if x[0] in ("set_coefficient", "set_stencil9")] == ["set_coefficient", "set_stencil9"]
+
+
+@pytest.mark.parametrize("name", list(gs.REFINE_GCR_CASES))
+def test_the_model_walks_the_refine_gcr_sequences(po, name):
+    """without a device (numpy's order of the dots): every array finite after every call; every solve_refine_gcr runs the
+    iterations it was asked for, its history never increases and ends below its first entry, and only U of the finest level
+    moves; every solve_refine history ends below its first entry; every double Krylov call at or above 1e-6 of its first
+    entry.  The sequence is changed if this fails, never a bound"""
+    cfg, seed, envs, options = gs.REFINE_GCR_CASES[name]
+    calls = gs.draw_sequence(seed, cfg, **gs.REFINE_GCR_OPTIONS, **options)
+    m = hm.HandleModel(po, **cfg)
+    lowest, slowest = (1.0, None), (0.0, None)
+    for i, call in enumerate(calls):
+        before = {lv: (m.U[lv], m.B[lv]) for lv in m.levels()}
+        out = gs.apply_model(m, call, cfg["finest_level"])
+        for lv in m.levels():
+            assert np.isfinite(m.U[lv]).all() and np.isfinite(m.B[lv]).all(), (i, call, lv)
+        if call[0] in gs.SOLVES:
+            assert np.isfinite(out[1]).all(), (i, call)
+        if call[0] in gs.REFINE_USERS:
+            st, h = out
+            if call[0] == "solve_refine_gcr":
+                assert st["cycles"] == len(h) - 1 == call[2] and st["converged"] == 0, (i, call, st)
+                assert np.all(h[1:] <= h[:-1]), (i, call, h)
+            if call[2]:
+                assert st["cycles"] >= 1 and h[-1] < h[0], (i, call, h)
+                slowest = max(slowest, (float(h[-1] / h[0]), (i, call)))
+            for lv in m.levels():
+                assert m.B[lv] is before[lv][1] and (lv == m.L or m.U[lv] is before[lv][0]), (i, call, lv)
+        if call[0].startswith("time_refine"):
+            assert all(m.U[lv] is before[lv][0] and m.B[lv] is before[lv][1] for lv in m.levels()), (i, call)
+        if call[0] in gs.KRYLOV and out[1][-1] / out[1][0] < lowest[0]:
+            lowest = (float(out[1][-1] / out[1][0]), (i, call))
+    print(f"\n[handle-state] model alone: {name} steps={len(calls)} lowest last/first of a Krylov call={lowest[0]:.3g} at {lowest[1]}; "
+          f"highest last/first of a refining call={slowest[0]:.3g} at {slowest[1]}")
+    assert 1e-6 <= lowest[0] < 1.0, lowest

@@ -124,6 +124,31 @@ def test_another_summation_order_is_a_small_fraction_of_the_gpu_bound():
     assert dh <= ORDER_FRACTION and dx <= ORDER_FRACTION, (dh, dx)
 
 
+# ---- the scales: invariance under a power of two -----------------------------------------------------------------------------
+@pytest.mark.parametrize("dot", [rg.dot, rg.device_dot], ids=["numpy-order", "device-order"])
+@pytest.mark.parametrize("loop", ["refine_gcr", "refine"])
+def test_the_references_commute_with_a_power_of_two_beyond_float_range(loop, dot):
+    """refine_gcr_ref.refine_gcr and refine_ref.refine on (2^e b, 2^e u0), e = -160 and +160, return 2^e x and 2^e hist of the
+    unscaled call BIT FOR BIT, with the same iteration count, at tol 0 and run to 1e-10: every float64 operation of the loops
+    commutes with a power of two while nothing overflows or goes subnormal (squares reach 2^+-320), and r / s_k is the same
+    float32 array for every e.  2^+-160 is beyond float32's range (2^-149 .. 2^128): a loop that skipped the scale would hand
+    the cycle zeros or infinities.  tests/test_gpu_refine_gcr.py holds the device to the same statement"""
+    import refine_ref as rr
+    A, _, cycle32, b = problem(6, 3, 10.0)
+    u0 = np.random.default_rng(4).uniform(-1, 1, b.shape)
+    if loop == "refine_gcr":
+        run = lambda bb, uu, tol, k: rg.refine_gcr(A, cycle32, bb, uu, tol, k, 4, dot=dot)[:2]
+    else:
+        run = lambda bb, uu, tol, k: rr.refine(lambda u, f: f - A(u), cycle32, bb, uu, tol=tol, max_cycles=k, norm=lambda r: float(np.sqrt(dot(r, r))))
+    for tol, k in ((0.0, 6), (1e-10, 60)):
+        x, h = run(b, u0, tol, k)
+        assert len(h) == 7 if tol == 0.0 else (6 < len(h) - 1 < 60 and h[-1] <= tol * h[0]), h
+        for e in (-160, 160):
+            xe, he = run(np.ldexp(b, e), np.ldexp(u0, e), tol, k)
+            assert np.array_equal(he, np.ldexp(h, e)), (loop, e, he, np.ldexp(h, e))
+            assert np.array_equal(xe, np.ldexp(x, e)) and np.isfinite(xe).all(), (loop, e)
+
+
 @pytest.mark.parametrize("n,rows", [(15, 0), (63, 1), (63, 5), (127, 0), (255, 0), (511, 0), (1023, 0), (2047, 0)])
 def test_the_device_order_dot_counts_every_product_once(n, rows):
     """integers: every order gives the same exact sum; and on random data it agrees with numpy's dot to rounding"""
