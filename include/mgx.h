@@ -520,6 +520,35 @@ MGX_API int mgx_solve_refine(mgx_handle h, double tol, int max_cycles, mgx_stats
 MGX_API int mgx_solve_refine_gcr(mgx_handle h, double tol, int max_iters, int restart, mgx_stats* stats,
                                  double* history, int history_cap);
 
+/* Up to MGX_MAX_RHS right-hand sides for one operator: solves A u_j = b_j, j < nrhs, on the finest level with the
+ * handle's cycle, every coefficient grid read once per pass for all the columns still iterating (a Jacobi sweep moves
+ * (NQ + 3 nrhs) sizeof(T) per point instead of nrhs (NQ + 3); the transfer weights and the dense coarsest inverse are
+ * read once as well).  b: nrhs host vectors back to back, each n * n in the reference layout and the handle's working
+ * type; u: the same shape, the initial guesses on entry, the iterates on return; stats: NULL or nrhs entries;
+ * history: NULL or nrhs slots of history_cap doubles, column j from history + j * history_cap.
+ * What column j returns - iterate, history, cycles, converged, initial_residual, final_residual, history_len,
+ * fine_updates - is bit for bit what mgx_set_rhs(b_j); mgx_set_guess(u_j); mgx_solve(h, tol, max_cycles, ..) returns
+ * on the same handle as a plain cycle loop: cfg.schedule is ignored (as in mgx_solve_pcg; no FMG).  A column is frozen
+ * as soon as its history meets hist[k] <= tol * hist[0]: no later launch reads or writes it; the call ends when every
+ * column is frozen or after max_cycles.  stats[j].seconds is the wall time of the whole call in every entry;
+ * max_cycles = 0 writes one history entry per column and returns the guesses.  Deterministic; one host
+ * synchronisation per cycle; launched eagerly (cfg.profile does not extend to the call).
+ * The handle's own U, B, R of every level and its cached graphs are left as they were, and every other entry point
+ * computes, before and after, the bits of a handle that never made the call.  Memory: the first call allocates, inside
+ * the handle, nrhs copies of each level's u, tmp, b, r, per-column partial sums and the pinned sums; a later call with
+ * a larger nrhs adds the difference; mgx_destroy frees it.  The workspace holds no copy of the operator: a call after
+ * mgx_set_* and a rebuild uses the new operator.
+ * Single-GPU handles of dtype F64 or F32, op STENCIL5 or GALERKIN, smoother JACOBI: every cycle kind (W and F through
+ * the per-level launches, whose bits k_small_visit shares), either transfer, every restriction mode the handle
+ * accepts, either bottom, a five- or nine-point finest level.  MGX_ERR_STATE (reason in mgx_last_error) on POISSON
+ * handles (their kernels read no coefficient grids: nothing to share), MIXED handles, multi-GPU and rank handles, every
+ * other smoother (multi-column Chebyshev, line and colour smoothers are a follow-up) and before the operators are set
+ * / built; MGX_ERR_INVALID for nrhs < 1 or nrhs > MGX_MAX_RHS, NULL b or u, tol not >= 0, max_cycles < 0;
+ * MGX_ERR_ALLOC leaves the handle (and the columns that existed) usable. */
+#define MGX_MAX_RHS 4
+MGX_API int mgx_solve_multi(mgx_handle h, int nrhs, const void* b, void* u, double tol, int max_cycles,
+                            mgx_stats* stats, double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -565,6 +594,12 @@ MGX_API int mgx_time_refine_pass(mgx_handle h, int repeats, double* ms);
  * harmless there; MGX_ERR_INVALID for another pass or repeats < 1. */
 enum { MGX_REFINE_GCR_PASS_UPDATE = 0, MGX_REFINE_GCR_PASS_DIRECTION = 1 };
 MGX_API int mgx_time_refine_gcr_pass(mgx_handle h, int pass, int repeats, double* ms);
+/* `sweeps` finest-level Jacobi sweeps on the first nrhs workspace columns of mgx_solve_multi between two events; returns
+ * the elapsed milliseconds (tools/multi_bench.py).  nrhs = 1 runs k_jacobi_var on a workspace column - the yardstick, in
+ * the same run; nrhs = 2..4 one launch of k_jacobi_var_multi per sweep.  The handle's own vectors are untouched.
+ * MGX_ERR_STATE where mgx_solve_multi returns it, and until a mgx_solve_multi call with at least that nrhs has
+ * allocated the columns; MGX_ERR_INVALID for sweeps < 1, nrhs < 1 or nrhs > MGX_MAX_RHS. */
+MGX_API int mgx_time_multi_smoother(mgx_handle h, int nrhs, int sweeps, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

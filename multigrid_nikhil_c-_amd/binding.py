@@ -56,8 +56,9 @@ EXPORTS = [
     "mgx_build_galerkin", "mgx_get_stencil9", "mgx_set_stencil9", "mgx_set_tensor",
     "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max", "mgx_get_line_factor", "mgx_get_line_chunks",
     "mgx_set_cycle", "mgx_get_cycle", "mgx_solve_refine", "mgx_time_refine_pass",
-    "mgx_solve_refine_gcr", "mgx_time_refine_gcr_pass",
+    "mgx_solve_refine_gcr", "mgx_time_refine_gcr_pass", "mgx_solve_multi", "mgx_time_multi_smoother",
 ]
+MAX_RHS = 4
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
  DOP_ALLREDUCE_NORM, DOP_RESTRICT_RHS, DOP_PROLONG_SET, DOP_COARSE_FMG) = range(1, 14)
@@ -178,6 +179,8 @@ def lib() -> C.CDLL:
     L.mgx_time_refine_pass.argtypes = [vp, C.c_int, dp]
     L.mgx_solve_refine_gcr.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_time_refine_gcr_pass.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.mgx_solve_multi.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
+    L.mgx_time_multi_smoother.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mgx_profile_get.argtypes = [vp, C.POINTER(Profile)]
     L.mgx_time_smoother.argtypes = [vp, C.c_int, dp]
     L.mgx_time_gcr_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
@@ -649,6 +652,28 @@ class Multigrid:
                                              hist.size), "mgx_solve_refine_gcr")
         return st, hist[: st.history_len].copy()
 
+    def solve_multi(self, b, u0=None, tol=1e-8, max_cycles=50):
+        """k <= MAX_RHS right-hand sides b[j] (k x n x n) for the handle's operator in one call, every coefficient grid read
+        once per pass for the columns still iterating (mgx_solve_multi): general-operator Jacobi handles, F64 or F32.  u0:
+        the initial guesses (None: zero).  Returns (list of stats, list of residual histories, u of shape (k, n, n)); column
+        j is bit for bit what set_rhs(b[j]); set_guess(u0[j]); solve(tol, max_cycles) returns as a plain cycle loop."""
+        dt = self.level_dtype(self.cfg.finest_level)
+        n = self.n()
+        b = np.ascontiguousarray(b, dtype=dt).reshape(-1, n, n)
+        k = b.shape[0]
+        u = np.zeros_like(b) if u0 is None else np.array(u0, dtype=dt, order="C").reshape(k, n, n)
+        st = (Stats * max(k, 1))()
+        cap = max(max_cycles, 0) + 1
+        hist = np.zeros((max(k, 1), cap), dtype=np.float64)
+        self._chk(lib().mgx_solve_multi(self._h, k, b.ctypes.data, u.ctypes.data, tol, max_cycles, st,
+                                        hist.ctypes.data_as(C.POINTER(C.c_double)), cap), "mgx_solve_multi")
+        stats = []
+        for j in range(k):
+            one = Stats()
+            C.memmove(C.byref(one), C.byref(st[j]), C.sizeof(Stats))
+            stats.append(one)
+        return stats, [hist[j, : stats[j].history_len].copy() for j in range(k)], u
+
     # -- measurement -----------------------------------------------------------------
     def profile_reset(self):
         self._chk(lib().mgx_profile_reset(self._h), "mgx_profile_reset")
@@ -682,6 +707,13 @@ class Multigrid:
         unchanged; after a solve_refine_gcr"""
         ms = C.c_double()
         self._chk(lib().mgx_time_refine_gcr_pass(self._h, which, repeats, C.byref(ms)), "mgx_time_refine_gcr_pass")
+        return ms.value
+
+    def time_multi_smoother(self, nrhs, sweeps):
+        """ms of `sweeps` finest-level Jacobi sweeps on the first nrhs workspace columns of solve_multi (nrhs = 1:
+        k_jacobi_var, the yardstick); after a solve_multi with at least nrhs columns"""
+        ms = C.c_double()
+        self._chk(lib().mgx_time_multi_smoother(self._h, nrhs, sweeps, C.byref(ms)), "mgx_time_multi_smoother")
         return ms.value
 
     def graphs_cached(self):

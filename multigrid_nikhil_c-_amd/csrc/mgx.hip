@@ -13,6 +13,8 @@
 //   mgx_solve_refine    (absent in the reference) fp64 defect correction around the cycle of a float copy of the
 //                       hierarchy, mgx_refine.hpp
 //   mgx_solve_refine_gcr  (absent in the reference) fp64 restarted GCR around that float cycle, mgx_refine_gcr.hpp
+//   mgx_solve_multi     (absent in the reference) mgx_solve's cycle loop on up to four right-hand sides per operator
+//                       read, mgx_multi.hpp
 // There is no CPU fallback anywhere in this file.
 
 #include "../../include/mgx.h"
@@ -29,6 +31,7 @@
 #include "mgx_krylov.hpp"
 #include "mgx_refine.hpp"
 #include "mgx_refine_gcr.hpp"
+#include "mgx_multi.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -166,6 +169,16 @@ struct mgx_solver {
     mgx_solver* shadow = nullptr;
     long long op_gen = 0, shadow_gen = -1;
     bool own_stream = true;
+    // mgx_solve_multi: MGX_MAX_RHS columns of u, tmp, b, r on every level (index = level, then column), each column's
+    // per-block sums of r^2 and the reduced sums with their pinned copy; columns [0, cols) exist.  Allocated by the first
+    // call, grown by a call with more columns, freed by mgx_destroy.  No copy of the operator: nothing to invalidate
+    struct MultiWs {
+        struct Grids { void *u[MGX_MAX_RHS] = {}, *tmp[MGX_MAX_RHS] = {}, *b[MGX_MAX_RHS] = {}, *r[MGX_MAX_RHS] = {}; };
+        std::vector<Grids> lv;
+        double* part[MGX_MAX_RHS] = {};
+        double *sums = nullptr, *sums_host = nullptr;
+        int cols = 0;
+    } multi;
 
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -1321,6 +1334,336 @@ int time_on_stream(mgx_solver* s, double* ms, Enqueue enqueue)
     return rc;
 }
 
+// ---- mgx_solve_multi: the cycle of a general-operator Jacobi handle on a set of workspace columns ---------------
+// Host code only: the recursion of vcycle / coarse_visits / descend / ascend as a general-operator handle runs it
+// (fold_eligible and zero_in_ok are false there: every block is plain per-level launches, every coarse guess is zeroed by
+// the restriction), on the columns act[0 .. m) of s->multi.  W- and F-cycles go through the per-level launches on every
+// level (k_small_visit is bit-identical to them).  One active column runs the single-column kernels; two to four run
+// one launch of the K-column kernels of mgx_multi.hpp wherever a coefficient is read, and the existing kernels once per
+// column where none is (the bilinear transfers, the injection).  No Prof scopes: cfg.profile does not extend to the call.
+void multi_free_column(mgx_solver::MultiWs& w, int c)
+{
+    auto& lv = w.lv;
+    auto& part = w.part;
+    for (auto& g : lv)
+        for (void** p : {&g.u[c], &g.tmp[c], &g.b[c], &g.r[c]}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+    if (part[c]) (void)hipFree(part[c]);
+    part[c] = nullptr;
+}
+
+void multi_free(mgx_solver::MultiWs& w)
+{
+    for (int c = 0; c < MGX_MAX_RHS; ++c) multi_free_column(w, c);
+    if (w.sums) (void)hipFree(w.sums);
+    if (w.sums_host) (void)hipHostFree(w.sums_host);
+    w.sums = w.sums_host = nullptr;
+    w.cols = 0;
+}
+
+// columns [0, nrhs) of the workspace exist afterwards.  A failure frees the column it was allocating and leaves the
+// columns that existed: the handle and the smaller workspace stay usable
+int multi_ensure(mgx_solver* s, int nrhs)
+{
+    auto& w = s->multi;
+    const int lo = s->cfg.coarsest_level, hi = s->cfg.finest_level;
+    if (w.lv.empty()) w.lv.resize(s->lv.size());
+    if (!w.sums && hipMalloc((void**)&w.sums, MGX_MAX_RHS * sizeof(double)) != hipSuccess) {
+        w.sums = nullptr;
+        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi: hipMalloc failed for the column sums");
+    }
+    if (!w.sums_host && hipHostMalloc((void**)&w.sums_host, MGX_MAX_RHS * sizeof(double)) != hipSuccess) {
+        w.sums_host = nullptr;
+        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi: hipHostMalloc failed for the column sums");
+    }
+    const Level& f = s->lv[hi];
+    const size_t blocks = (size_t)make_launch(f.N, f.f64 ? 2 : 4, f.N - 1, 1).blocks;
+    for (int c = w.cols; c < nrhs; ++c) {
+        bool ok = hipMalloc((void**)&w.part[c], blocks * sizeof(double)) == hipSuccess;
+        if (!ok) w.part[c] = nullptr;
+        for (int l = lo; ok && l <= hi; ++l)
+            for (void** p : {&w.lv[l].u[c], &w.lv[l].tmp[c], &w.lv[l].b[c], &w.lv[l].r[c]}) {
+                if (hipMalloc(p, s->lv[l].bytes) != hipSuccess) { *p = nullptr; ok = false; break; }
+                // the ring and the padding stay zero from here on, as in the handle's own arrays
+                if (hipMemsetAsync(*p, 0, s->lv[l].bytes, s->stream) != hipSuccess) { ok = false; break; }
+            }
+        if (!ok) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(s->stream);
+            multi_free_column(w, c);
+            return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi: hipMalloc failed for the arrays of column " + std::to_string(c));
+        }
+        w.cols = c + 1;
+    }
+    return MGX_OK;
+}
+
+// the active columns of a launch: act[0 .. m), m >= 1, ascending
+struct MultiSet { int act[MGX_MAX_RHS]; int m; };
+
+template <typename T, int K> MultiIn<T, K> multi_in(void* const* grids, const MultiSet& a)
+{
+    MultiIn<T, K> o;
+    for (int j = 0; j < K; ++j) o.p[j] = (const T*)grids[a.act[j]];
+    return o;
+}
+template <typename T, int K> MultiOut<T, K> multi_out(void* const* grids, const MultiSet& a)
+{
+    MultiOut<T, K> o;
+    for (int j = 0; j < K; ++j) o.p[j] = grids ? (T*)grids[a.act[j]] : nullptr;
+    return o;
+}
+
+// smooth_var_t on the set; fu (may be null): each column's fine_updates, counted as smooth() counts them
+template <typename T>
+void multi_smooth(mgx_solver* s, int level, const MultiSet& a, int mu, double* fu)
+{
+    if (mu <= 0) return;
+    const Level& l = s->lv[level];
+    auto& w = s->multi.lv[level];
+    const T om = (T)s->cfg.omega;
+    const T rc = (T)(1.0 - (double)om);
+    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
+    const VarLevel<T> v = var_level<T>(l);
+    const dim3 grd(g.blocks), blk(kBlock);
+    for (int i = 0; i < mu; ++i) {
+        with_point_count(v.nine, [&](auto nq) {
+            constexpr int NQ = decltype(nq)::value;
+            if (a.m == 1) {
+                const int c = a.act[0];
+                hipLaunchKernelGGL((k_jacobi_var<T, NQ>), grd, blk, 0, s->stream, (const T*)w.u[c], (const T*)w.b[c], (T*)w.tmp[c], v.dinv, v.r,
+                                   v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
+            } else with_column_count(a.m, [&](auto kc) {
+                constexpr int K = decltype(kc)::value;
+                hipLaunchKernelGGL((k_jacobi_var_multi<T, NQ, K>), grd, blk, 0, s->stream, multi_in<T, K>(w.u, a), multi_in<T, K>(w.b, a),
+                                   multi_out<T, K>(w.tmp, a), v.dinv, v.r, v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
+            });
+        });
+        for (int j = 0; j < a.m; ++j) std::swap(w.u[a.act[j]], w.tmp[a.act[j]]);
+    }
+    if (fu && level == s->cfg.finest_level)
+        for (int j = 0; j < a.m; ++j) fu[a.act[j]] += (double)mu * (double)(l.N - 1) * (double)(l.N - 1);
+}
+
+// residual_var_t on the set.  MODE 0: r_j = b_j - A u_j into the level's r;  MODE 1: per-block sums of r_j^2 into the
+// column's partials (finest level), each reduced by k_reduce_partials in its own order into sums[column]
+template <typename T, int MODE>
+void multi_residual(mgx_solver* s, int level, const MultiSet& a)
+{
+    const Level& l = s->lv[level];
+    auto& ws = s->multi;
+    auto& w = ws.lv[level];
+    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
+    const VarLevel<T> v = var_level<T>(l);
+    const dim3 grd(g.blocks), blk(kBlock);
+    with_point_count(v.nine, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        if (a.m == 1) {
+            const int c = a.act[0];
+            hipLaunchKernelGGL((k_residual_var<T, NQ, MODE>), grd, blk, 0, s->stream, (const T*)w.u[c], (const T*)w.b[c], MODE ? (T*)nullptr : (T*)w.r[c],
+                               MODE ? ws.part[c] : (double*)nullptr, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
+        } else with_column_count(a.m, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            MultiOut<double, K> part;
+            for (int j = 0; j < K; ++j) part.p[j] = MODE ? ws.part[a.act[j]] : nullptr;
+            hipLaunchKernelGGL((k_residual_var_multi<T, NQ, MODE, K>), grd, blk, 0, s->stream, multi_in<T, K>(w.u, a), multi_in<T, K>(w.b, a),
+                               multi_out<T, K>(MODE ? nullptr : w.r, a), part, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
+        });
+    });
+    if (MODE == 1)
+        for (int j = 0; j < a.m; ++j)
+            hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, ws.part[a.act[j]], g.blocks, ws.sums + a.act[j]);
+}
+
+// restrict_level(level, fused = true, zero_guess = true) on the set
+template <typename T>
+void multi_restrict(mgx_solver* s, int level, const MultiSet& a)
+{
+    const Level& f = s->lv[level];
+    const Level& c = s->lv[level - 1];
+    auto& wf = s->multi.lv[level];
+    auto& wc = s->multi.lv[level - 1];
+    const int mode = s->cfg.restrict_mode;
+    if (opdep(s)) {
+        const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
+        const T rscale = (mode == MGX_RESTRICT_FW16) ? (T)0.25 : (T)1;
+        const dim3 grd(g.blocks), blk(kBlock);
+        with_point_count(f.nine, [&](auto nq) {
+            constexpr int MODE = decltype(nq)::value == 9 ? 2 : 1;
+            if (a.m == 1) {
+                const int j = a.act[0];
+                hipLaunchKernelGGL((k_restrict_opdep<T, MODE>), grd, blk, 0, s->stream, (const T*)wf.u[j], (const T*)wf.b[j], op9_of<T>(f), wt8_of<T>(c),
+                                   (T*)wc.b[j], (T*)wc.u[j], c.N, f.pitch, c.pitch, g.strips, rscale);
+            } else with_column_count(a.m, [&](auto kc) {
+                constexpr int K = decltype(kc)::value;
+                hipLaunchKernelGGL((k_restrict_opdep_multi<T, MODE, K>), grd, blk, 0, s->stream, multi_in<T, K>(wf.u, a), multi_in<T, K>(wf.b, a),
+                                   op9_of<T>(f), wt8_of<T>(c), multi_out<T, K>(wc.b, a), multi_out<T, K>(wc.u, a), c.N, f.pitch, c.pitch,
+                                   g.strips, rscale);
+            });
+        });
+        return;
+    }
+    // the residual as a grid (the operator's grids read once for the set), then the coefficient-free transfer of each
+    // column with the single-column kernel
+    multi_residual<T, 0>(s, level, a);
+    for (int i = 0; i < a.m; ++i) {
+        const int j = a.act[i];
+        if (mode >= MGX_RESTRICT_INJECT) {
+            const double wgt = (mode == MGX_RESTRICT_INJECT4) ? 4.0 : 1.0;
+            const dim3 blk(256), grd((c.N + 255) / 256, c.N - 1);
+            hipLaunchKernelGGL((k_restrict_inject<T>), grd, blk, 0, s->stream, (const T*)wf.r[j], (T*)wc.b[j], (T*)wc.u[j], c.N, f.pitch, c.pitch, (T)wgt);
+        } else {
+            launch_restrict<T>((const T*)wf.u[j], (const T*)wf.r[j], (T*)wc.b[j], (T*)wc.u[j], f.N, f.pitch, c.pitch, 1, c.N, 0, mode, false,
+                               s->rows_per_chunk, s->stream);
+        }
+    }
+}
+
+// prolong_level(level, add = true) on the set
+template <typename T>
+void multi_prolong(mgx_solver* s, int level, const MultiSet& a)
+{
+    const Level& f = s->lv[level];
+    const Level& c = s->lv[level - 1];
+    auto& wf = s->multi.lv[level];
+    auto& wc = s->multi.lv[level - 1];
+    if (!opdep(s)) {
+        for (int i = 0; i < a.m; ++i)
+            launch_prolong<T>((T*)wf.u[a.act[i]], (const T*)wc.u[a.act[i]], f.N, f.pitch, c.pitch, 1, f.N, 0, true, s->rows_per_chunk, s->stream);
+        return;
+    }
+    const Launch g = make_launch(c.N, VecOf<T>::W, c.N, 1);
+    const dim3 grd(g.blocks), blk(kBlock);
+    if (a.m == 1)
+        hipLaunchKernelGGL((k_prolong_opdep<T, true>), grd, blk, 0, s->stream, (T*)wf.u[a.act[0]], (const T*)wc.u[a.act[0]], wt8_of<T>(c), c.N, f.pitch,
+                           c.pitch, g.strips);
+    else with_column_count(a.m, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL((k_prolong_opdep_multi<T, true, K>), grd, blk, 0, s->stream, multi_out<T, K>(wf.u, a), multi_in<T, K>(wc.u, a), wt8_of<T>(c),
+                           c.N, f.pitch, c.pitch, g.strips);
+    });
+}
+
+// the visit of the coarsest level: bottom_solve, or the two blocks of bottom = SMOOTH
+template <typename T>
+void multi_bottom(mgx_solver* s, const MultiSet& a, double* fu)
+{
+    const int level = s->cfg.coarsest_level;
+    if (s->cfg.bottom != MGX_BOTTOM_EXACT) {
+        multi_smooth<T>(s, level, a, s->cfg.mu1, fu);
+        multi_smooth<T>(s, level, a, s->cfg.mu2, fu);
+        return;
+    }
+    const Level& l = s->lv[level];
+    auto& w = s->multi.lv[level];
+    const int n = l.N - 1;
+    const dim3 grd((n * n + 63) / 64), blk(64);
+    if (a.m == 1)
+        hipLaunchKernelGGL((k_var_dense_solve<T>), grd, blk, 0, s->stream, s->var_inv, (const T*)w.b[a.act[0]], (T*)w.u[a.act[0]], n, l.pitch);
+    else with_column_count(a.m, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL((k_var_dense_solve_multi<T, K>), grd, blk, 0, s->stream, s->var_inv, multi_in<T, K>(w.b, a), multi_out<T, K>(w.u, a), n, l.pitch);
+    });
+}
+
+template <typename T> void multi_vcycle(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu);
+
+// coarse_visits on the set (no k_small_visit)
+template <typename T>
+void multi_visits(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu)
+{
+    const bool twice = kind != MGX_CYCLE_V && level > s->cfg.coarsest_level;
+    multi_vcycle<T>(s, level, a, kind, fu);
+    if (twice) multi_vcycle<T>(s, level, a, kind == MGX_CYCLE_F ? MGX_CYCLE_V : kind, fu);
+}
+
+// vcycle on the set: descend (mu1 sweeps, the residual restricted, the coarse guess zeroed), the visits of the level
+// below, ascend (the correction, mu2 sweeps)
+template <typename T>
+void multi_vcycle(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu)
+{
+    if (level == s->cfg.coarsest_level) { multi_bottom<T>(s, a, fu); return; }
+    multi_smooth<T>(s, level, a, s->cfg.mu1, fu);
+    multi_restrict<T>(s, level, a);
+    multi_visits<T>(s, level - 1, a, kind, fu);
+    multi_prolong<T>(s, level, a);
+    multi_smooth<T>(s, level, a, s->cfg.mu2, fu);
+}
+
+// ||b_j - A u_j|| of the set's columns on the finest level into r[column]: one copy, one host synchronisation
+template <typename T>
+int multi_norms(mgx_solver* s, const MultiSet& a, double* r)
+{
+    multi_residual<T, 1>(s, s->cfg.finest_level, a);
+    HIPCHK(s, hipMemcpyAsync(s->multi.sums_host, s->multi.sums, MGX_MAX_RHS * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    for (int j = 0; j < a.m; ++j) r[a.act[j]] = std::sqrt(s->multi.sums_host[a.act[j]]);
+    return MGX_OK;
+}
+
+// which handles solve blocks of right-hand sides (the message names the reason); then the operators must be set / built
+int multi_guard(mgx_solver* s, const char* fn)
+{
+    const std::string f(fn);
+    if (s->dist) return s->fail(MGX_ERR_STATE, f + ": not available on a multi-GPU handle (see mgx.h, Multi-GPU)");
+    if (!s->var)
+        return s->fail(MGX_ERR_STATE, f + ": op = MGX_OPERATOR_POISSON kernels read no coefficient grids, there is nothing for the columns to "
+                                          "share; this entry point is for MGX_OPERATOR_STENCIL5 and MGX_OPERATOR_GALERKIN");
+    if (s->mixed) return s->fail(MGX_ERR_STATE, f + ": dtype MIXED is not supported (F64 or F32)");
+    if (s->cfg.smoother != MGX_SMOOTHER_JACOBI)
+        return s->fail(MGX_ERR_STATE, f + ": smoother MGX_SMOOTHER_JACOBI only (multi-column Chebyshev, line and colour smoothers are a follow-up)");
+    return var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level);
+}
+
+template <typename T>
+int multi_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double tol, int max_cycles, mgx_stats* stats, double* history, int history_cap)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = multi_ensure(s, nrhs)) return rc;
+    const int L = s->cfg.finest_level;
+    Level& l = s->lv[L];
+    auto& w = s->multi.lv[L];
+    const size_t nn = (size_t)(l.N - 1) * (size_t)(l.N - 1);
+    for (int j = 0; j < nrhs; ++j) {
+        if (int rc = copy_in(s, l, w.b[j], (const T*)b + (size_t)j * nn, nn)) return rc;
+        if (int rc = copy_in(s, l, w.u[j], (const T*)u + (size_t)j * nn, nn)) return rc;
+    }
+    std::vector<double> hist[MGX_MAX_RHS];
+    double r[MGX_MAX_RHS] = {}, fu[MGX_MAX_RHS] = {};
+    int cycles[MGX_MAX_RHS] = {};
+    MultiSet a{};
+    for (int j = 0; j < nrhs; ++j) { hist[j].reserve(max_cycles + 1); a.act[a.m++] = j; }
+    if (int rc = multi_norms<T>(s, a, r)) return rc;
+    for (int j = 0; j < nrhs; ++j) hist[j].push_back(r[j]);
+    for (int k = 0; k < max_cycles; ++k) {
+        // a column leaves the set for good as soon as its history meets the tolerance: nothing reads or writes it again
+        MultiSet next{};
+        for (int i = 0; i < a.m; ++i) {
+            const int j = a.act[i];
+            if (!(hist[j][k] <= tol * hist[j][0])) next.act[next.m++] = j;
+        }
+        a = next;
+        if (a.m == 0) break;
+        multi_vcycle<T>(s, L, a, s->cycle, fu);
+        if (int rc = multi_norms<T>(s, a, r)) return rc;
+        for (int i = 0; i < a.m; ++i) { hist[a.act[i]].push_back(r[a.act[i]]); cycles[a.act[i]] = k + 1; }
+    }
+    HIPCHK(s, hipGetLastError());
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    for (int j = 0; j < nrhs; ++j)
+        if (int rc = copy_out(s, l, w.u[j], (T*)u + (size_t)j * nn, nn)) return rc;
+    for (int j = 0; j < nrhs; ++j)
+        finish_solve(stats ? stats + j : nullptr, history ? history + (size_t)j * (size_t)history_cap : nullptr, history_cap, hist[j], cycles[j],
+                     hist[j].back() <= tol * hist[j].front(), t0, fu[j]);
+    if (stats) {
+        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        for (int j = 0; j < nrhs; ++j) stats[j].seconds = seconds;
+    }
+    return MGX_OK;
+}
+
 } // namespace
 
 #include "mgx_dist.hpp"
@@ -1565,6 +1908,7 @@ int mgx_destroy(mgx_handle s)
     if (s->sum_host) (void)hipHostFree(s->sum_host);
     for (double* p : {s->var_M, s->var_inv, s->var_pm, s->var_pi}) if (p) (void)hipFree(p);
     s->kry.free();
+    multi_free(s->multi);
     drop_graphs(s);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2571,6 +2915,37 @@ int mgx_time_smoother(mgx_handle s, int sweeps, double* ms)
     return time_on_stream(s, ms, [&] {
         if (s->var) smooth_var(s, l, sweeps);
         else smooth_t(s, l, sweeps);
+    });
+}
+
+// ---- mgx_solve_multi: up to MGX_MAX_RHS right-hand sides per operator read ---------------------------------------
+int mgx_solve_multi(mgx_handle s, int nrhs, const void* b, void* u, double tol, int max_cycles, mgx_stats* stats, double* history,
+                    int history_cap)
+{
+    static_assert(kMultiMax == MGX_MAX_RHS, "mgx_multi.hpp and mgx.h disagree");
+    if (!s) return MGX_ERR_INVALID;
+    if (nrhs < 1 || nrhs > MGX_MAX_RHS) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi: 1 <= nrhs <= MGX_MAX_RHS required");
+    if (!b || !u) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi: b and u must not be NULL");
+    if (!(tol >= 0.0) || max_cycles < 0) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi: tol >= 0 and max_cycles >= 0 required");
+    if (int rc = multi_guard(s, "mgx_solve_multi")) return rc;
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    return s->work_f64 ? multi_solve_t<double>(s, nrhs, b, u, tol, max_cycles, stats, history, history_cap)
+                       : multi_solve_t<float>(s, nrhs, b, u, tol, max_cycles, stats, history, history_cap);
+}
+
+int mgx_time_multi_smoother(mgx_handle s, int nrhs, int sweeps, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!ms || sweeps < 1 || nrhs < 1 || nrhs > MGX_MAX_RHS)
+        return s->fail(MGX_ERR_INVALID, "mgx_time_multi_smoother: 1 <= nrhs <= MGX_MAX_RHS, sweeps >= 1 and ms required");
+    if (int rc = multi_guard(s, "mgx_time_multi_smoother")) return rc;
+    if (s->multi.cols < nrhs)
+        return s->fail(MGX_ERR_STATE, "mgx_time_multi_smoother: call mgx_solve_multi with at least this nrhs first (it allocates the columns)");
+    MultiSet a{};
+    for (int j = 0; j < nrhs; ++j) a.act[a.m++] = j;
+    return time_on_stream(s, ms, [&] {
+        if (s->work_f64) multi_smooth<double>(s, s->cfg.finest_level, a, sweeps, nullptr);
+        else multi_smooth<float>(s, s->cfg.finest_level, a, sweeps, nullptr);
     });
 }
 
