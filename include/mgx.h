@@ -549,6 +549,36 @@ MGX_API int mgx_solve_refine_gcr(mgx_handle h, double tol, int max_iters, int re
 MGX_API int mgx_solve_multi(mgx_handle h, int nrhs, const void* b, void* u, double tol, int max_cycles,
                             mgx_stats* stats, double* history, int history_cap);
 
+/* mgx_solve_gcr's iteration on up to MGX_MAX_RHS right-hand sides for one operator: restarted GCR with right
+ * preconditioning on the finest level, the preconditioner mgx_solve_multi's cycle from zero on the columns still
+ * iterating (every coefficient grid, transfer weight and the dense coarsest inverse read once per pass for all of them),
+ * the direction pass Z_j = z, Q_j = A z one launch of k_gcr_direction_multi for the set ((NQ + 3 nrhs) sizeof(T) per point
+ * instead of nrhs (NQ + 3)).  The orthogonalisation, update and reduction passes read no coefficients and run once per
+ * column, in mgx_solve_gcr's geometry, on that column's own scalars and partial sums; all columns share the iteration
+ * index k and so the basis slot k mod restart.  Arguments as for mgx_solve_multi: b and u are nrhs host vectors back to
+ * back (u the guesses on entry, the iterates on return), stats NULL or nrhs entries, history NULL or nrhs slots of
+ * history_cap doubles.
+ * What column j returns - iterate, history, cycles, converged, initial_residual, final_residual, history_len,
+ * fine_updates - is bit for bit what mgx_set_rhs(b_j); mgx_set_guess(u_j); mgx_solve_gcr(h, tol, max_iters, restart, ..);
+ * mgx_get_solution returns on the same handle.  stats[j].seconds is the wall time of the whole call in every entry.
+ * A column leaves the active set for good - no later launch reads or writes it - when hist[0] <= tol * hist[0] or
+ * max_iters = 0 (one history entry, the guess returned), when ||r|| <= tol * hist[0] after an iteration, or on its own
+ * breakdown (q'.q' not a positive finite number: converged = 0, its x as before that iteration; the call still returns
+ * MGX_OK and mgx_last_error names the first such column and iteration).  The call ends when the set is empty or after
+ * max_iters.  Deterministic; one device-to-host copy and one host synchronisation per iteration serve all columns;
+ * launched eagerly (cfg.profile does not extend to the call).
+ * The handle's own U, B, R of every level, its mgx_solve_pcg / mgx_solve_gcr workspace, its cached graphs and its
+ * fine_updates are left as they were, and every other entry point computes, before and after, the bits of a handle that
+ * never made the call.  Memory: mgx_solve_multi's columns and, per column, x, 2 restart vectors of the finest level, the
+ * partial sums of a pass and a block of scalars (all blocks in one device buffer with one pinned mirror); a later call
+ * with a larger nrhs or restart adds the difference; mgx_destroy frees it.
+ * MGX_ERR_STATE exactly where mgx_solve_multi returns it (POISSON, MIXED, multi-GPU and rank handles, every smoother but
+ * JACOBI, before the operators are set / built); MGX_ERR_INVALID for nrhs < 1 or nrhs > MGX_MAX_RHS, NULL b or u, tol not
+ * >= 0, max_iters < 0, restart < 1 or restart > MGX_GCR_MAX_RESTART; MGX_ERR_ALLOC leaves the handle (and what existed of
+ * the workspace) usable. */
+MGX_API int mgx_solve_multi_gcr(mgx_handle h, int nrhs, const void* b, void* u, double tol, int max_iters, int restart,
+                                mgx_stats* stats, double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -600,6 +630,13 @@ MGX_API int mgx_time_refine_gcr_pass(mgx_handle h, int pass, int repeats, double
  * MGX_ERR_STATE where mgx_solve_multi returns it, and until a mgx_solve_multi call with at least that nrhs has
  * allocated the columns; MGX_ERR_INVALID for sweeps < 1, nrhs < 1 or nrhs > MGX_MAX_RHS. */
 MGX_API int mgx_time_multi_smoother(mgx_handle h, int nrhs, int sweeps, double* ms);
+/* ms per launch of the direction pass of mgx_solve_multi_gcr on its first nrhs workspace columns, from the finest u of
+ * each column into its basis slot 0, `repeats` launches between two events (tools/multi_gcr_bench.py).  nrhs = 1 runs
+ * k_pcg_direction on a workspace column - the yardstick, in the same run; nrhs = 2..4 one launch of k_gcr_direction_multi.
+ * The handle's own vectors are untouched (slot 0 has no meaning between two solves).  MGX_ERR_STATE where
+ * mgx_solve_multi_gcr returns it, and until a mgx_solve_multi_gcr call with at least that nrhs has allocated slot 0;
+ * MGX_ERR_INVALID for repeats < 1, nrhs < 1 or nrhs > MGX_MAX_RHS. */
+MGX_API int mgx_time_multi_gcr_direction(mgx_handle h, int nrhs, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

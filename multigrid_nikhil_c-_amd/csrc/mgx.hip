@@ -15,6 +15,7 @@
 //   mgx_solve_refine_gcr  (absent in the reference) fp64 restarted GCR around that float cycle, mgx_refine_gcr.hpp
 //   mgx_solve_multi     (absent in the reference) mgx_solve's cycle loop on up to four right-hand sides per operator
 //                       read, mgx_multi.hpp
+//   mgx_solve_multi_gcr (absent in the reference) mgx_solve_gcr's iteration on those columns, around that cycle
 // There is no CPU fallback anywhere in this file.
 
 #include "../../include/mgx.h"
@@ -178,6 +179,13 @@ struct mgx_solver {
         double* part[MGX_MAX_RHS] = {};
         double *sums = nullptr, *sums_host = nullptr;
         int cols = 0;
+        // mgx_solve_multi_gcr, per column beyond the above: the iterate x, the basis pairs Z_i, Q_i = A Z_i of the finest
+        // level (as many as the largest restart so far), the partial sums of one Krylov pass (sized like KrylovWs::part)
+        // and a block of kGcrScalars doubles - the blocks of all columns contiguous in gsc, one pinned mirror gsc_host
+        void* x[MGX_MAX_RHS] = {};
+        void *Z[MGX_MAX_RHS][kGcrMaxRestart] = {}, *Q[MGX_MAX_RHS][kGcrMaxRestart] = {};
+        double* gpart[MGX_MAX_RHS] = {};
+        double *gsc = nullptr, *gsc_host = nullptr;
     } multi;
 
     int fail(int code, const std::string& m) { err = m; return code; }
@@ -1352,6 +1360,15 @@ void multi_free_column(mgx_solver::MultiWs& w, int c)
         }
     if (part[c]) (void)hipFree(part[c]);
     part[c] = nullptr;
+    for (void** p : {&w.x[c], (void**)&w.gpart[c]}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    for (int i = 0; i < kGcrMaxRestart; ++i)
+        for (void** p : {&w.Z[c][i], &w.Q[c][i]}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
 }
 
 void multi_free(mgx_solver::MultiWs& w)
@@ -1360,6 +1377,9 @@ void multi_free(mgx_solver::MultiWs& w)
     if (w.sums) (void)hipFree(w.sums);
     if (w.sums_host) (void)hipHostFree(w.sums_host);
     w.sums = w.sums_host = nullptr;
+    if (w.gsc) (void)hipFree(w.gsc);
+    if (w.gsc_host) (void)hipHostFree(w.gsc_host);
+    w.gsc = w.gsc_host = nullptr;
     w.cols = 0;
 }
 
@@ -1662,6 +1682,195 @@ int multi_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double tol, i
         for (int j = 0; j < nrhs; ++j) stats[j].seconds = seconds;
     }
     return MGX_OK;
+}
+
+// ---- mgx_solve_multi_gcr: krylov_run + GcrMethod::enqueue (mgx_krylov_host.hpp) per column, around multi_vcycle ----------
+// the geometry of every Krylov pass, krylov_run's: the per-block partial sums set the summation order
+template <typename T> Launch multi_gcr_launch(const mgx_solver* s)
+{
+    const Level& l = s->lv[s->cfg.finest_level];
+    return make_launch(l.N, VecOf<T>::W, l.N - 1, s->rows_per_chunk);
+}
+
+// the Krylov pieces of columns [0, nrhs) with `restart` basis pairs each exist afterwards (multi_ensure has made the
+// columns).  Every piece is allocated once, by the first call that needs it; a failure leaves what existed
+int multi_gcr_ensure(mgx_solver* s, int nrhs, int restart, int blocks)
+{
+    auto& w = s->multi;
+    const Level& l = s->lv[s->cfg.finest_level];
+    if (!w.gsc && hipMalloc((void**)&w.gsc, MGX_MAX_RHS * kGcrScalars * sizeof(double)) != hipSuccess) {
+        w.gsc = nullptr;
+        (void)hipGetLastError();
+        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipMalloc failed for the column scalars");
+    }
+    if (!w.gsc_host && hipHostMalloc((void**)&w.gsc_host, MGX_MAX_RHS * kGcrScalars * sizeof(double)) != hipSuccess) {
+        w.gsc_host = nullptr;
+        (void)hipGetLastError();
+        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipHostMalloc failed for the column scalars");
+    }
+    for (int c = 0; c < nrhs; ++c) {
+        // k_gcr_dots<T, 7> writes seven partials per workgroup (KrylovWs::shared)
+        if (!w.gpart[c] && hipMalloc((void**)&w.gpart[c], ((size_t)(kGcrMaxRestart - 1) * blocks + 8) * sizeof(double)) != hipSuccess) {
+            w.gpart[c] = nullptr;
+            (void)hipGetLastError();
+            return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipMalloc failed for the partial sums of column " + std::to_string(c));
+        }
+        auto vec = [&](void** p) {
+            if (*p) return true;
+            if (hipMalloc(p, l.bytes) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return false; }
+            // the ring and the padding stay zero from here on
+            if (hipMemsetAsync(*p, 0, l.bytes, s->stream) == hipSuccess) return true;
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(s->stream);
+            (void)hipFree(*p);
+            *p = nullptr;
+            return false;
+        };
+        bool ok = vec(&w.x[c]);
+        for (int i = 0; ok && i < restart; ++i) ok = vec(&w.Z[c][i]) && vec(&w.Q[c][i]);
+        if (!ok) return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipMalloc failed for the Krylov vectors of column " + std::to_string(c));
+    }
+    return MGX_OK;
+}
+
+// Z_c[j] = z_c (the finest u of the column), Q_c[j] = A z_c for the columns of the set: one launch, the operator read once
+template <typename T>
+void multi_gcr_direction(mgx_solver* s, const MultiSet& a, int j, const Launch& g)
+{
+    const Level& l = s->lv[s->cfg.finest_level];
+    auto& ws = s->multi;
+    auto& w = ws.lv[s->cfg.finest_level];
+    if (a.m == 1) {
+        const int c = a.act[0];
+        const T* z = (const T*)w.u[c];
+        // k_pcg_direction's first iteration, as mgx_solve_gcr launches it (its partials z.q go where nothing reads them)
+        if (l.nine)
+            hipLaunchKernelGGL((k_pcg_direction<T, 2>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, z, (T*)ws.Z[c][j], (T*)ws.Q[c][j],
+                               (const double*)(ws.gsc + (size_t)c * kGcrScalars), 1, ws.gpart[c], op9_of<T>(l), l.N, l.pitch, g.R, g.strips, g.chunks);
+        else
+            hipLaunchKernelGGL((k_pcg_direction<T, 1>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, z, (T*)ws.Z[c][j], (T*)ws.Q[c][j],
+                               (const double*)(ws.gsc + (size_t)c * kGcrScalars), 1, ws.gpart[c], op9_of<T>(l), l.N, l.pitch, g.R, g.strips, g.chunks);
+        return;
+    }
+    const T* z[MGX_MAX_RHS];
+    T *zo[MGX_MAX_RHS], *q[MGX_MAX_RHS];
+    for (int i = 0; i < a.m; ++i) {
+        const int c = a.act[i];
+        z[i] = (const T*)w.u[c]; zo[i] = (T*)ws.Z[c][j]; q[i] = (T*)ws.Q[c][j];
+    }
+    launch_gcr_direction_multi<T>(a.m, l.nine, z, zo, q, op9_of<T>(l), l.N, l.pitch, g, s->stream);
+}
+
+template <typename T>
+int multi_gcr_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double tol, int max_iters, int restart, mgx_stats* stats,
+                      double* history, int history_cap)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const Launch g = multi_gcr_launch<T>(s);
+    if (int rc = multi_ensure(s, nrhs)) return rc;
+    if (int rc = multi_gcr_ensure(s, nrhs, restart, g.blocks)) return rc;
+    const int L = s->cfg.finest_level;
+    Level& l = s->lv[L];
+    auto& ws = s->multi;
+    auto& w = ws.lv[L];
+    const size_t nn = (size_t)(l.N - 1) * (size_t)(l.N - 1);
+    for (int j = 0; j < nrhs; ++j) {
+        if (int rc = copy_in(s, l, w.b[j], (const T*)b + (size_t)j * nn, nn)) return rc;
+        if (int rc = copy_in(s, l, w.u[j], (const T*)u + (size_t)j * nn, nn)) return rc;
+    }
+    std::vector<double> hist[MGX_MAX_RHS];
+    double r[MGX_MAX_RHS] = {}, fu[MGX_MAX_RHS] = {};
+    int iters[MGX_MAX_RHS] = {}, broke[MGX_MAX_RHS] = {};
+    MultiSet all{};
+    for (int j = 0; j < nrhs; ++j) { hist[j].reserve(max_iters + 1); all.act[all.m++] = j; }
+    if (int rc = multi_norms<T>(s, all, r)) return rc;
+    MultiSet a{};
+    for (int j = 0; j < nrhs; ++j) {
+        hist[j].push_back(r[j]);
+        // x_j: the guess, which a column that never iterates returns (b = 0, u = 0: converged, nothing divided)
+        HIPCHK(s, hipMemcpyAsync(ws.x[j], w.u[j], l.bytes, hipMemcpyDeviceToDevice, s->stream));
+        if (!(r[j] <= tol * r[j]) && max_iters > 0) a.act[a.m++] = j;
+    }
+    if (a.m > 0) {
+        // r_j = b_j - A x_j becomes the cycle's right-hand side of the finest level for the whole solve (the caller's b is
+        // on the host: nothing to restore); the scalar blocks start from zero, as GcrMethod::prepare leaves them
+        multi_residual<T, 0>(s, L, a);
+        for (int i = 0; i < a.m; ++i) std::swap(w.b[a.act[i]], w.r[a.act[i]]);
+        HIPCHK(s, hipMemsetAsync(ws.gsc, 0, MGX_MAX_RHS * kGcrScalars * sizeof(double), s->stream));
+    }
+    // zero_start_u: a one-level hierarchy starts its cycle from what the finest u holds (the guess, then the last z)
+    const bool zero_start = L > s->cfg.coarsest_level;
+    std::string first_break;
+    for (int k = 0; k < max_iters && a.m > 0; ++k) {
+        const int j = k % restart;
+        if (zero_start)
+            for (int i = 0; i < a.m; ++i) HIPCHK(s, hipMemsetAsync(w.u[a.act[i]], 0, l.bytes, s->stream));
+        multi_vcycle<T>(s, L, a, s->cycle, fu);                            // z_c = M r_c, into the finest u of the column
+        multi_gcr_direction<T>(s, a, j, g);
+        for (int i = 0; i < a.m; ++i) {
+            const int c = a.act[i];
+            double* sc = ws.gsc + (size_t)c * kGcrScalars;
+            T *zj = (T*)ws.Z[c][j], *qj = (T*)ws.Q[c][j];
+            GcrBasis<T> bs{};
+            for (int q = 0; q < kGcrMaxRestart - 1; ++q) { bs.Q[q] = (const T*)ws.Q[c][q]; bs.Z[q] = (const T*)ws.Z[c][q]; }
+            launch_gcr_orth<T>(j, qj, zj, (const T*)w.b[c], bs, sc, ws.gpart[c], l.N, l.pitch, g, kGcrAllPasses, s->stream);
+            hipLaunchKernelGGL((k_pcg_update<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)ws.x[c], (const T*)zj, (T*)w.b[c], (const T*)qj,
+                               (const double*)sc, ws.gpart[c], l.N, l.pitch, g.R, g.strips, g.chunks);
+            hipLaunchKernelGGL(k_pcg_reduce, dim3(1), dim3(kReduceThreads), 0, s->stream, (const double*)ws.gpart[c], g.blocks, (int)kPcgRRMode, sc);
+        }
+        HIPCHK(s, hipGetLastError());
+        HIPCHK(s, hipMemcpyAsync(ws.gsc_host, ws.gsc, (size_t)nrhs * kGcrScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(s, hipStreamSynchronize(s->stream));                        // the one host synchronisation per iteration
+        // a column that broke down or converged leaves the set for good: no later launch reads or writes it
+        MultiSet next{};
+        for (int i = 0; i < a.m; ++i) {
+            const int c = a.act[i];
+            const double* h = ws.gsc_host + (size_t)c * kGcrScalars;
+            if (h[kPcgBreak] != 0.0) {
+                broke[c] = 1;
+                if (first_break.empty()) {
+                    char msg[200];
+                    std::snprintf(msg, sizeof msg, "mgx_solve_multi_gcr: column %d: GCR breakdown at iteration %d: q'.q' = %.17g is not a positive finite number",
+                                  c, k + 1, h[kPcgDelta]);
+                    first_break = msg;
+                }
+                continue;
+            }
+            iters[c] = k + 1;
+            const double rn = std::sqrt(h[kPcgRR]);
+            hist[c].push_back(rn);
+            if (!(rn <= tol * hist[c][0])) next.act[next.m++] = c;
+        }
+        a = next;
+    }
+    HIPCHK(s, hipGetLastError());
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    for (int j = 0; j < nrhs; ++j)
+        if (int rc = copy_out(s, l, ws.x[j], (T*)u + (size_t)j * nn, nn)) return rc;
+    for (int j = 0; j < nrhs; ++j)
+        finish_solve(stats ? stats + j : nullptr, history ? history + (size_t)j * (size_t)history_cap : nullptr, history_cap, hist[j], iters[j],
+                     !broke[j] && hist[j].back() <= tol * hist[j].front(), t0, fu[j]);
+    if (stats) {
+        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        for (int j = 0; j < nrhs; ++j) stats[j].seconds = seconds;
+    }
+    if (!first_break.empty()) s->err = first_break;
+    return MGX_OK;
+}
+
+// mgx_time_multi_gcr_direction: `repeats` launches of the direction pass on the first nrhs columns, from the finest u of
+// each into its basis slot 0 (which has no meaning between two solves)
+template <typename T>
+int multi_gcr_time_direction(mgx_solver* s, int nrhs, int repeats, double* ms)
+{
+    const Launch g = multi_gcr_launch<T>(s);
+    MultiSet a{};
+    for (int j = 0; j < nrhs; ++j) a.act[a.m++] = j;
+    const int rc = time_on_stream(s, ms, [&] {
+        for (int i = 0; i < repeats; ++i) multi_gcr_direction<T>(s, a, 0, g);
+    });
+    if (!rc) *ms /= repeats;
+    return rc;
 }
 
 } // namespace
@@ -2947,6 +3156,36 @@ int mgx_time_multi_smoother(mgx_handle s, int nrhs, int sweeps, double* ms)
         if (s->work_f64) multi_smooth<double>(s, s->cfg.finest_level, a, sweeps, nullptr);
         else multi_smooth<float>(s, s->cfg.finest_level, a, sweeps, nullptr);
     });
+}
+
+// ---- mgx_solve_multi_gcr: restarted GCR on up to MGX_MAX_RHS right-hand sides per operator read ------------------------
+int mgx_solve_multi_gcr(mgx_handle s, int nrhs, const void* b, void* u, double tol, int max_iters, int restart, mgx_stats* stats,
+                        double* history, int history_cap)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (nrhs < 1 || nrhs > MGX_MAX_RHS) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi_gcr: 1 <= nrhs <= MGX_MAX_RHS required");
+    if (!b || !u) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi_gcr: b and u must not be NULL");
+    if (!(tol >= 0.0) || max_iters < 0) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi_gcr: tol >= 0 and max_iters >= 0 required");
+    if (restart < 1 || restart > MGX_GCR_MAX_RESTART)
+        return s->fail(MGX_ERR_INVALID, "mgx_solve_multi_gcr: 1 <= restart <= MGX_GCR_MAX_RESTART required");
+    if (int rc = multi_guard(s, "mgx_solve_multi_gcr")) return rc;
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    return s->work_f64 ? multi_gcr_solve_t<double>(s, nrhs, b, u, tol, max_iters, restart, stats, history, history_cap)
+                       : multi_gcr_solve_t<float>(s, nrhs, b, u, tol, max_iters, restart, stats, history, history_cap);
+}
+
+int mgx_time_multi_gcr_direction(mgx_handle s, int nrhs, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!ms || repeats < 1 || nrhs < 1 || nrhs > MGX_MAX_RHS)
+        return s->fail(MGX_ERR_INVALID, "mgx_time_multi_gcr_direction: 1 <= nrhs <= MGX_MAX_RHS, repeats >= 1 and ms required");
+    if (int rc = multi_guard(s, "mgx_time_multi_gcr_direction")) return rc;
+    bool ready = s->multi.cols >= nrhs && s->multi.gsc;
+    for (int c = 0; ready && c < nrhs; ++c) ready = s->multi.gpart[c] && s->multi.Z[c][0] && s->multi.Q[c][0];
+    if (!ready)
+        return s->fail(MGX_ERR_STATE, "mgx_time_multi_gcr_direction: call mgx_solve_multi_gcr with at least this nrhs first (it allocates basis slot 0 "
+                                      "of the columns)");
+    return s->work_f64 ? multi_gcr_time_direction<double>(s, nrhs, repeats, ms) : multi_gcr_time_direction<float>(s, nrhs, repeats, ms);
 }
 
 // =====================================================================================

@@ -308,4 +308,91 @@ template <typename F> void with_column_count(int k, F&& f)
     else f(std::integral_constant<int, 4>{});
 }
 
+// ---- mgx_solve_multi_gcr ------------------------------------------------------------------------------------------
+// The direction pass of GCR on K columns: Z_j = z_j, Q_j = A z_j - the first_it = 1 form of k_pcg_direction<T, 1 | 2>
+// (mgx_krylov.hpp) with the level's NQ coefficient grids loaded once per row for the K columns: (NQ + 3K) sizeof(T) per
+// point against K (NQ + 3).  The same march down R rows per wave, the same prow masking, the same edge hand-up for
+// NQ = 9, stencil_sum<NQ> with the same centre-coefficient lambda and mask_cols before the stores: per column the
+// arithmetic and its order are the single-column kernel's, whatever R is.  No partial sums: GCR never reads
+// k_pcg_direction's p'.q.  A wave without a tile returns at once (nothing below synchronises the workgroup).
+template <typename T, int NQ, int K>
+__global__ void __launch_bounds__(kBlock)
+k_gcr_direction_multi(MultiIn<T, K> z, MultiOut<T, K> zo, MultiOut<T, K> q, Op9<T> a, int N, long pitch, int R, int strips, int chunks)
+{
+    using V = typename VecOf<T>::type;
+    const Tile t = wave_tile(strips, chunks);
+    if (!t.active) return;
+    const Cols c = lane_cols<VecOf<T>::W>(t.strip, N, pitch);
+    const int r0 = 1 + t.chunk * R;
+    const int r1 = min(r0 + R, N);
+    // rows 0 and N are the Dirichlet ring: z = 0 there without a load
+    auto prow = [&](const T* zp, int y) -> V {
+        const bool in = c.ld && y >= 1 && y < N;
+        V v = vload<V>(zp + c.col + (long)y * pitch, in);
+        mask_cols(v, c.col, N);
+        return v;
+    };
+    V up[K], cur[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) { up[j] = prow(z.p[j], r0 - 1); cur[j] = prow(z.p[j], r0); }
+    // the edge values of the rows above and at y from the adjacent lanes: NQ = 9 hands those of row y + 1 up as the march
+    // goes down (two moves per new row and column), NQ = 5 needs those of row y only
+    T ul[K], ur[K], cl[K], cr[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        ul[j] = ur[j] = (T)0;
+        if constexpr (NQ == 9) { ul[j] = from_left(last(up[j])); ur[j] = from_right(first(up[j])); }
+        cl[j] = from_left(last(cur[j])); cr[j] = from_right(first(cur[j]));
+    }
+    for (int y = r0; y < r1; ++y) {
+        const long at = c.col + (long)y * pitch;
+        V dn[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) dn[j] = prow(z.p[j], y + 1);
+        Lanes<T> k[9];
+        load_coefs<NQ, 0>(a, at, c.ld, k);
+        V o[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const T dl = from_left(last(dn[j])), dr = from_right(first(dn[j]));
+            const Rows3<T> u{to_lanes(up[j]), to_lanes(cur[j]), to_lanes(dn[j]), ul[j], ur[j], cl[j], cr[j], dl, dr};
+            o[j] = from_lanes(stencil_sum<NQ>(u, k, [&](int x) { return k[0].a[x]; }));
+            mask_cols(o[j], c.col, N);
+            ul[j] = cl[j]; ur[j] = cr[j]; cl[j] = dl; cr[j] = dr;
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            vstore<V>(zo.p[j] + at, cur[j], c.st);
+            vstore<V>(q.p[j] + at, o[j], c.st);
+            up[j] = cur[j]; cur[j] = dn[j];
+        }
+    }
+}
+
+// one launch of k_gcr_direction_multi on m = 2 .. 4 columns (host arrays of m pointers) of a five- or nine-point level
+template <typename T>
+void launch_gcr_direction_multi(int m, bool nine, const T* const* z, T* const* zo, T* const* q, const Op9<T>& a, int N, long pitch,
+                                const Launch& g, hipStream_t st)
+{
+    with_point_count(nine, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        with_column_count(m, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            MultiIn<T, K> zi;
+            MultiOut<T, K> zz, qq;
+            for (int j = 0; j < K; ++j) { zi.p[j] = z[j]; zz.p[j] = zo[j]; qq.p[j] = q[j]; }
+            hipLaunchKernelGGL((k_gcr_direction_multi<T, NQ, K>), dim3(g.blocks), dim3(kBlock), 0, st, zi, zz, qq, a, N, pitch, g.R, g.strips,
+                               g.chunks);
+        });
+    });
+}
+
+// mgx.hip uses these instantiations; mgx_inst.hip (-DMGX_INST_KIND=9) defines them
+#if !defined(MGX_INST_KIND) && !defined(MGX_SINGLE_TU)
+extern template void launch_gcr_direction_multi<double>(int, bool, const double* const*, double* const*, double* const*, const Op9<double>&, int,
+                                                        long, const Launch&, hipStream_t);
+extern template void launch_gcr_direction_multi<float>(int, bool, const float* const*, float* const*, float* const*, const Op9<float>&, int, long,
+                                                       const Launch&, hipStream_t);
+#endif
+
 } // namespace mgx
