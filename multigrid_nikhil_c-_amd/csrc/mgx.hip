@@ -16,6 +16,8 @@
 //   mgx_solve_multi     (absent in the reference) mgx_solve's cycle loop on up to four right-hand sides per operator
 //                       read, mgx_multi.hpp
 //   mgx_solve_multi_gcr (absent in the reference) mgx_solve_gcr's iteration on those columns, around that cycle
+// The host side of the last six is in mgx_krylov_host.hpp (the Krylov passes, driver and entry-point body of all that
+// iterate), mgx_refine_host.hpp and mgx_multi_host.hpp; only their extern "C" entry points are here.
 // There is no CPU fallback anywhere in this file.
 
 #include "../../include/mgx.h"
@@ -1342,537 +1344,6 @@ int time_on_stream(mgx_solver* s, double* ms, Enqueue enqueue)
     return rc;
 }
 
-// ---- mgx_solve_multi: the cycle of a general-operator Jacobi handle on a set of workspace columns ---------------
-// Host code only: the recursion of vcycle / coarse_visits / descend / ascend as a general-operator handle runs it
-// (fold_eligible and zero_in_ok are false there: every block is plain per-level launches, every coarse guess is zeroed by
-// the restriction), on the columns act[0 .. m) of s->multi.  W- and F-cycles go through the per-level launches on every
-// level (k_small_visit is bit-identical to them).  One active column runs the single-column kernels; two to four run
-// one launch of the K-column kernels of mgx_multi.hpp wherever a coefficient is read, and the existing kernels once per
-// column where none is (the bilinear transfers, the injection).  No Prof scopes: cfg.profile does not extend to the call.
-void multi_free_column(mgx_solver::MultiWs& w, int c)
-{
-    auto& lv = w.lv;
-    auto& part = w.part;
-    for (auto& g : lv)
-        for (void** p : {&g.u[c], &g.tmp[c], &g.b[c], &g.r[c]}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-    if (part[c]) (void)hipFree(part[c]);
-    part[c] = nullptr;
-    for (void** p : {&w.x[c], (void**)&w.gpart[c]}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    for (int i = 0; i < kGcrMaxRestart; ++i)
-        for (void** p : {&w.Z[c][i], &w.Q[c][i]}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-}
-
-void multi_free(mgx_solver::MultiWs& w)
-{
-    for (int c = 0; c < MGX_MAX_RHS; ++c) multi_free_column(w, c);
-    if (w.sums) (void)hipFree(w.sums);
-    if (w.sums_host) (void)hipHostFree(w.sums_host);
-    w.sums = w.sums_host = nullptr;
-    if (w.gsc) (void)hipFree(w.gsc);
-    if (w.gsc_host) (void)hipHostFree(w.gsc_host);
-    w.gsc = w.gsc_host = nullptr;
-    w.cols = 0;
-}
-
-// columns [0, nrhs) of the workspace exist afterwards.  A failure frees the column it was allocating and leaves the
-// columns that existed: the handle and the smaller workspace stay usable
-int multi_ensure(mgx_solver* s, int nrhs)
-{
-    auto& w = s->multi;
-    const int lo = s->cfg.coarsest_level, hi = s->cfg.finest_level;
-    if (w.lv.empty()) w.lv.resize(s->lv.size());
-    if (!w.sums && hipMalloc((void**)&w.sums, MGX_MAX_RHS * sizeof(double)) != hipSuccess) {
-        w.sums = nullptr;
-        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi: hipMalloc failed for the column sums");
-    }
-    if (!w.sums_host && hipHostMalloc((void**)&w.sums_host, MGX_MAX_RHS * sizeof(double)) != hipSuccess) {
-        w.sums_host = nullptr;
-        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi: hipHostMalloc failed for the column sums");
-    }
-    const Level& f = s->lv[hi];
-    const size_t blocks = (size_t)make_launch(f.N, f.f64 ? 2 : 4, f.N - 1, 1).blocks;
-    for (int c = w.cols; c < nrhs; ++c) {
-        bool ok = hipMalloc((void**)&w.part[c], blocks * sizeof(double)) == hipSuccess;
-        if (!ok) w.part[c] = nullptr;
-        for (int l = lo; ok && l <= hi; ++l)
-            for (void** p : {&w.lv[l].u[c], &w.lv[l].tmp[c], &w.lv[l].b[c], &w.lv[l].r[c]}) {
-                if (hipMalloc(p, s->lv[l].bytes) != hipSuccess) { *p = nullptr; ok = false; break; }
-                // the ring and the padding stay zero from here on, as in the handle's own arrays
-                if (hipMemsetAsync(*p, 0, s->lv[l].bytes, s->stream) != hipSuccess) { ok = false; break; }
-            }
-        if (!ok) {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(s->stream);
-            multi_free_column(w, c);
-            return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi: hipMalloc failed for the arrays of column " + std::to_string(c));
-        }
-        w.cols = c + 1;
-    }
-    return MGX_OK;
-}
-
-// the active columns of a launch: act[0 .. m), m >= 1, ascending
-struct MultiSet { int act[MGX_MAX_RHS]; int m; };
-
-template <typename T, int K> MultiIn<T, K> multi_in(void* const* grids, const MultiSet& a)
-{
-    MultiIn<T, K> o;
-    for (int j = 0; j < K; ++j) o.p[j] = (const T*)grids[a.act[j]];
-    return o;
-}
-template <typename T, int K> MultiOut<T, K> multi_out(void* const* grids, const MultiSet& a)
-{
-    MultiOut<T, K> o;
-    for (int j = 0; j < K; ++j) o.p[j] = grids ? (T*)grids[a.act[j]] : nullptr;
-    return o;
-}
-
-// smooth_var_t on the set; fu (may be null): each column's fine_updates, counted as smooth() counts them
-template <typename T>
-void multi_smooth(mgx_solver* s, int level, const MultiSet& a, int mu, double* fu)
-{
-    if (mu <= 0) return;
-    const Level& l = s->lv[level];
-    auto& w = s->multi.lv[level];
-    const T om = (T)s->cfg.omega;
-    const T rc = (T)(1.0 - (double)om);
-    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
-    const VarLevel<T> v = var_level<T>(l);
-    const dim3 grd(g.blocks), blk(kBlock);
-    for (int i = 0; i < mu; ++i) {
-        with_point_count(v.nine, [&](auto nq) {
-            constexpr int NQ = decltype(nq)::value;
-            if (a.m == 1) {
-                const int c = a.act[0];
-                hipLaunchKernelGGL((k_jacobi_var<T, NQ>), grd, blk, 0, s->stream, (const T*)w.u[c], (const T*)w.b[c], (T*)w.tmp[c], v.dinv, v.r,
-                                   v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
-            } else with_column_count(a.m, [&](auto kc) {
-                constexpr int K = decltype(kc)::value;
-                hipLaunchKernelGGL((k_jacobi_var_multi<T, NQ, K>), grd, blk, 0, s->stream, multi_in<T, K>(w.u, a), multi_in<T, K>(w.b, a),
-                                   multi_out<T, K>(w.tmp, a), v.dinv, v.r, v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
-            });
-        });
-        for (int j = 0; j < a.m; ++j) std::swap(w.u[a.act[j]], w.tmp[a.act[j]]);
-    }
-    if (fu && level == s->cfg.finest_level)
-        for (int j = 0; j < a.m; ++j) fu[a.act[j]] += (double)mu * (double)(l.N - 1) * (double)(l.N - 1);
-}
-
-// residual_var_t on the set.  MODE 0: r_j = b_j - A u_j into the level's r;  MODE 1: per-block sums of r_j^2 into the
-// column's partials (finest level), each reduced by k_reduce_partials in its own order into sums[column]
-template <typename T, int MODE>
-void multi_residual(mgx_solver* s, int level, const MultiSet& a)
-{
-    const Level& l = s->lv[level];
-    auto& ws = s->multi;
-    auto& w = ws.lv[level];
-    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
-    const VarLevel<T> v = var_level<T>(l);
-    const dim3 grd(g.blocks), blk(kBlock);
-    with_point_count(v.nine, [&](auto nq) {
-        constexpr int NQ = decltype(nq)::value;
-        if (a.m == 1) {
-            const int c = a.act[0];
-            hipLaunchKernelGGL((k_residual_var<T, NQ, MODE>), grd, blk, 0, s->stream, (const T*)w.u[c], (const T*)w.b[c], MODE ? (T*)nullptr : (T*)w.r[c],
-                               MODE ? ws.part[c] : (double*)nullptr, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
-        } else with_column_count(a.m, [&](auto kc) {
-            constexpr int K = decltype(kc)::value;
-            MultiOut<double, K> part;
-            for (int j = 0; j < K; ++j) part.p[j] = MODE ? ws.part[a.act[j]] : nullptr;
-            hipLaunchKernelGGL((k_residual_var_multi<T, NQ, MODE, K>), grd, blk, 0, s->stream, multi_in<T, K>(w.u, a), multi_in<T, K>(w.b, a),
-                               multi_out<T, K>(MODE ? nullptr : w.r, a), part, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
-        });
-    });
-    if (MODE == 1)
-        for (int j = 0; j < a.m; ++j)
-            hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, ws.part[a.act[j]], g.blocks, ws.sums + a.act[j]);
-}
-
-// restrict_level(level, fused = true, zero_guess = true) on the set
-template <typename T>
-void multi_restrict(mgx_solver* s, int level, const MultiSet& a)
-{
-    const Level& f = s->lv[level];
-    const Level& c = s->lv[level - 1];
-    auto& wf = s->multi.lv[level];
-    auto& wc = s->multi.lv[level - 1];
-    const int mode = s->cfg.restrict_mode;
-    if (opdep(s)) {
-        const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
-        const T rscale = (mode == MGX_RESTRICT_FW16) ? (T)0.25 : (T)1;
-        const dim3 grd(g.blocks), blk(kBlock);
-        with_point_count(f.nine, [&](auto nq) {
-            constexpr int MODE = decltype(nq)::value == 9 ? 2 : 1;
-            if (a.m == 1) {
-                const int j = a.act[0];
-                hipLaunchKernelGGL((k_restrict_opdep<T, MODE>), grd, blk, 0, s->stream, (const T*)wf.u[j], (const T*)wf.b[j], op9_of<T>(f), wt8_of<T>(c),
-                                   (T*)wc.b[j], (T*)wc.u[j], c.N, f.pitch, c.pitch, g.strips, rscale);
-            } else with_column_count(a.m, [&](auto kc) {
-                constexpr int K = decltype(kc)::value;
-                hipLaunchKernelGGL((k_restrict_opdep_multi<T, MODE, K>), grd, blk, 0, s->stream, multi_in<T, K>(wf.u, a), multi_in<T, K>(wf.b, a),
-                                   op9_of<T>(f), wt8_of<T>(c), multi_out<T, K>(wc.b, a), multi_out<T, K>(wc.u, a), c.N, f.pitch, c.pitch,
-                                   g.strips, rscale);
-            });
-        });
-        return;
-    }
-    // the residual as a grid (the operator's grids read once for the set), then the coefficient-free transfer of each
-    // column with the single-column kernel
-    multi_residual<T, 0>(s, level, a);
-    for (int i = 0; i < a.m; ++i) {
-        const int j = a.act[i];
-        if (mode >= MGX_RESTRICT_INJECT) {
-            const double wgt = (mode == MGX_RESTRICT_INJECT4) ? 4.0 : 1.0;
-            const dim3 blk(256), grd((c.N + 255) / 256, c.N - 1);
-            hipLaunchKernelGGL((k_restrict_inject<T>), grd, blk, 0, s->stream, (const T*)wf.r[j], (T*)wc.b[j], (T*)wc.u[j], c.N, f.pitch, c.pitch, (T)wgt);
-        } else {
-            launch_restrict<T>((const T*)wf.u[j], (const T*)wf.r[j], (T*)wc.b[j], (T*)wc.u[j], f.N, f.pitch, c.pitch, 1, c.N, 0, mode, false,
-                               s->rows_per_chunk, s->stream);
-        }
-    }
-}
-
-// prolong_level(level, add = true) on the set
-template <typename T>
-void multi_prolong(mgx_solver* s, int level, const MultiSet& a)
-{
-    const Level& f = s->lv[level];
-    const Level& c = s->lv[level - 1];
-    auto& wf = s->multi.lv[level];
-    auto& wc = s->multi.lv[level - 1];
-    if (!opdep(s)) {
-        for (int i = 0; i < a.m; ++i)
-            launch_prolong<T>((T*)wf.u[a.act[i]], (const T*)wc.u[a.act[i]], f.N, f.pitch, c.pitch, 1, f.N, 0, true, s->rows_per_chunk, s->stream);
-        return;
-    }
-    const Launch g = make_launch(c.N, VecOf<T>::W, c.N, 1);
-    const dim3 grd(g.blocks), blk(kBlock);
-    if (a.m == 1)
-        hipLaunchKernelGGL((k_prolong_opdep<T, true>), grd, blk, 0, s->stream, (T*)wf.u[a.act[0]], (const T*)wc.u[a.act[0]], wt8_of<T>(c), c.N, f.pitch,
-                           c.pitch, g.strips);
-    else with_column_count(a.m, [&](auto kc) {
-        constexpr int K = decltype(kc)::value;
-        hipLaunchKernelGGL((k_prolong_opdep_multi<T, true, K>), grd, blk, 0, s->stream, multi_out<T, K>(wf.u, a), multi_in<T, K>(wc.u, a), wt8_of<T>(c),
-                           c.N, f.pitch, c.pitch, g.strips);
-    });
-}
-
-// the visit of the coarsest level: bottom_solve, or the two blocks of bottom = SMOOTH
-template <typename T>
-void multi_bottom(mgx_solver* s, const MultiSet& a, double* fu)
-{
-    const int level = s->cfg.coarsest_level;
-    if (s->cfg.bottom != MGX_BOTTOM_EXACT) {
-        multi_smooth<T>(s, level, a, s->cfg.mu1, fu);
-        multi_smooth<T>(s, level, a, s->cfg.mu2, fu);
-        return;
-    }
-    const Level& l = s->lv[level];
-    auto& w = s->multi.lv[level];
-    const int n = l.N - 1;
-    const dim3 grd((n * n + 63) / 64), blk(64);
-    if (a.m == 1)
-        hipLaunchKernelGGL((k_var_dense_solve<T>), grd, blk, 0, s->stream, s->var_inv, (const T*)w.b[a.act[0]], (T*)w.u[a.act[0]], n, l.pitch);
-    else with_column_count(a.m, [&](auto kc) {
-        constexpr int K = decltype(kc)::value;
-        hipLaunchKernelGGL((k_var_dense_solve_multi<T, K>), grd, blk, 0, s->stream, s->var_inv, multi_in<T, K>(w.b, a), multi_out<T, K>(w.u, a), n, l.pitch);
-    });
-}
-
-template <typename T> void multi_vcycle(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu);
-
-// coarse_visits on the set (no k_small_visit)
-template <typename T>
-void multi_visits(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu)
-{
-    const bool twice = kind != MGX_CYCLE_V && level > s->cfg.coarsest_level;
-    multi_vcycle<T>(s, level, a, kind, fu);
-    if (twice) multi_vcycle<T>(s, level, a, kind == MGX_CYCLE_F ? MGX_CYCLE_V : kind, fu);
-}
-
-// vcycle on the set: descend (mu1 sweeps, the residual restricted, the coarse guess zeroed), the visits of the level
-// below, ascend (the correction, mu2 sweeps)
-template <typename T>
-void multi_vcycle(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu)
-{
-    if (level == s->cfg.coarsest_level) { multi_bottom<T>(s, a, fu); return; }
-    multi_smooth<T>(s, level, a, s->cfg.mu1, fu);
-    multi_restrict<T>(s, level, a);
-    multi_visits<T>(s, level - 1, a, kind, fu);
-    multi_prolong<T>(s, level, a);
-    multi_smooth<T>(s, level, a, s->cfg.mu2, fu);
-}
-
-// ||b_j - A u_j|| of the set's columns on the finest level into r[column]: one copy, one host synchronisation
-template <typename T>
-int multi_norms(mgx_solver* s, const MultiSet& a, double* r)
-{
-    multi_residual<T, 1>(s, s->cfg.finest_level, a);
-    HIPCHK(s, hipMemcpyAsync(s->multi.sums_host, s->multi.sums, MGX_MAX_RHS * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    for (int j = 0; j < a.m; ++j) r[a.act[j]] = std::sqrt(s->multi.sums_host[a.act[j]]);
-    return MGX_OK;
-}
-
-// which handles solve blocks of right-hand sides (the message names the reason); then the operators must be set / built
-int multi_guard(mgx_solver* s, const char* fn)
-{
-    const std::string f(fn);
-    if (s->dist) return s->fail(MGX_ERR_STATE, f + ": not available on a multi-GPU handle (see mgx.h, Multi-GPU)");
-    if (!s->var)
-        return s->fail(MGX_ERR_STATE, f + ": op = MGX_OPERATOR_POISSON kernels read no coefficient grids, there is nothing for the columns to "
-                                          "share; this entry point is for MGX_OPERATOR_STENCIL5 and MGX_OPERATOR_GALERKIN");
-    if (s->mixed) return s->fail(MGX_ERR_STATE, f + ": dtype MIXED is not supported (F64 or F32)");
-    if (s->cfg.smoother != MGX_SMOOTHER_JACOBI)
-        return s->fail(MGX_ERR_STATE, f + ": smoother MGX_SMOOTHER_JACOBI only (multi-column Chebyshev, line and colour smoothers are a follow-up)");
-    return var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level);
-}
-
-template <typename T>
-int multi_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double tol, int max_cycles, mgx_stats* stats, double* history, int history_cap)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = multi_ensure(s, nrhs)) return rc;
-    const int L = s->cfg.finest_level;
-    Level& l = s->lv[L];
-    auto& w = s->multi.lv[L];
-    const size_t nn = (size_t)(l.N - 1) * (size_t)(l.N - 1);
-    for (int j = 0; j < nrhs; ++j) {
-        if (int rc = copy_in(s, l, w.b[j], (const T*)b + (size_t)j * nn, nn)) return rc;
-        if (int rc = copy_in(s, l, w.u[j], (const T*)u + (size_t)j * nn, nn)) return rc;
-    }
-    std::vector<double> hist[MGX_MAX_RHS];
-    double r[MGX_MAX_RHS] = {}, fu[MGX_MAX_RHS] = {};
-    int cycles[MGX_MAX_RHS] = {};
-    MultiSet a{};
-    for (int j = 0; j < nrhs; ++j) { hist[j].reserve(max_cycles + 1); a.act[a.m++] = j; }
-    if (int rc = multi_norms<T>(s, a, r)) return rc;
-    for (int j = 0; j < nrhs; ++j) hist[j].push_back(r[j]);
-    for (int k = 0; k < max_cycles; ++k) {
-        // a column leaves the set for good as soon as its history meets the tolerance: nothing reads or writes it again
-        MultiSet next{};
-        for (int i = 0; i < a.m; ++i) {
-            const int j = a.act[i];
-            if (!(hist[j][k] <= tol * hist[j][0])) next.act[next.m++] = j;
-        }
-        a = next;
-        if (a.m == 0) break;
-        multi_vcycle<T>(s, L, a, s->cycle, fu);
-        if (int rc = multi_norms<T>(s, a, r)) return rc;
-        for (int i = 0; i < a.m; ++i) { hist[a.act[i]].push_back(r[a.act[i]]); cycles[a.act[i]] = k + 1; }
-    }
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    for (int j = 0; j < nrhs; ++j)
-        if (int rc = copy_out(s, l, w.u[j], (T*)u + (size_t)j * nn, nn)) return rc;
-    for (int j = 0; j < nrhs; ++j)
-        finish_solve(stats ? stats + j : nullptr, history ? history + (size_t)j * (size_t)history_cap : nullptr, history_cap, hist[j], cycles[j],
-                     hist[j].back() <= tol * hist[j].front(), t0, fu[j]);
-    if (stats) {
-        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        for (int j = 0; j < nrhs; ++j) stats[j].seconds = seconds;
-    }
-    return MGX_OK;
-}
-
-// ---- mgx_solve_multi_gcr: krylov_run + GcrMethod::enqueue (mgx_krylov_host.hpp) per column, around multi_vcycle ----------
-// the geometry of every Krylov pass, krylov_run's: the per-block partial sums set the summation order
-template <typename T> Launch multi_gcr_launch(const mgx_solver* s)
-{
-    const Level& l = s->lv[s->cfg.finest_level];
-    return make_launch(l.N, VecOf<T>::W, l.N - 1, s->rows_per_chunk);
-}
-
-// the Krylov pieces of columns [0, nrhs) with `restart` basis pairs each exist afterwards (multi_ensure has made the
-// columns).  Every piece is allocated once, by the first call that needs it; a failure leaves what existed
-int multi_gcr_ensure(mgx_solver* s, int nrhs, int restart, int blocks)
-{
-    auto& w = s->multi;
-    const Level& l = s->lv[s->cfg.finest_level];
-    if (!w.gsc && hipMalloc((void**)&w.gsc, MGX_MAX_RHS * kGcrScalars * sizeof(double)) != hipSuccess) {
-        w.gsc = nullptr;
-        (void)hipGetLastError();
-        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipMalloc failed for the column scalars");
-    }
-    if (!w.gsc_host && hipHostMalloc((void**)&w.gsc_host, MGX_MAX_RHS * kGcrScalars * sizeof(double)) != hipSuccess) {
-        w.gsc_host = nullptr;
-        (void)hipGetLastError();
-        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipHostMalloc failed for the column scalars");
-    }
-    for (int c = 0; c < nrhs; ++c) {
-        // k_gcr_dots<T, 7> writes seven partials per workgroup (KrylovWs::shared)
-        if (!w.gpart[c] && hipMalloc((void**)&w.gpart[c], ((size_t)(kGcrMaxRestart - 1) * blocks + 8) * sizeof(double)) != hipSuccess) {
-            w.gpart[c] = nullptr;
-            (void)hipGetLastError();
-            return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipMalloc failed for the partial sums of column " + std::to_string(c));
-        }
-        auto vec = [&](void** p) {
-            if (*p) return true;
-            if (hipMalloc(p, l.bytes) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return false; }
-            // the ring and the padding stay zero from here on
-            if (hipMemsetAsync(*p, 0, l.bytes, s->stream) == hipSuccess) return true;
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(s->stream);
-            (void)hipFree(*p);
-            *p = nullptr;
-            return false;
-        };
-        bool ok = vec(&w.x[c]);
-        for (int i = 0; ok && i < restart; ++i) ok = vec(&w.Z[c][i]) && vec(&w.Q[c][i]);
-        if (!ok) return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipMalloc failed for the Krylov vectors of column " + std::to_string(c));
-    }
-    return MGX_OK;
-}
-
-// Z_c[j] = z_c (the finest u of the column), Q_c[j] = A z_c for the columns of the set: one launch, the operator read once
-template <typename T>
-void multi_gcr_direction(mgx_solver* s, const MultiSet& a, int j, const Launch& g)
-{
-    const Level& l = s->lv[s->cfg.finest_level];
-    auto& ws = s->multi;
-    auto& w = ws.lv[s->cfg.finest_level];
-    if (a.m == 1) {
-        const int c = a.act[0];
-        const T* z = (const T*)w.u[c];
-        // k_pcg_direction's first iteration, as mgx_solve_gcr launches it (its partials z.q go where nothing reads them)
-        if (l.nine)
-            hipLaunchKernelGGL((k_pcg_direction<T, 2>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, z, (T*)ws.Z[c][j], (T*)ws.Q[c][j],
-                               (const double*)(ws.gsc + (size_t)c * kGcrScalars), 1, ws.gpart[c], op9_of<T>(l), l.N, l.pitch, g.R, g.strips, g.chunks);
-        else
-            hipLaunchKernelGGL((k_pcg_direction<T, 1>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z, z, (T*)ws.Z[c][j], (T*)ws.Q[c][j],
-                               (const double*)(ws.gsc + (size_t)c * kGcrScalars), 1, ws.gpart[c], op9_of<T>(l), l.N, l.pitch, g.R, g.strips, g.chunks);
-        return;
-    }
-    const T* z[MGX_MAX_RHS];
-    T *zo[MGX_MAX_RHS], *q[MGX_MAX_RHS];
-    for (int i = 0; i < a.m; ++i) {
-        const int c = a.act[i];
-        z[i] = (const T*)w.u[c]; zo[i] = (T*)ws.Z[c][j]; q[i] = (T*)ws.Q[c][j];
-    }
-    launch_gcr_direction_multi<T>(a.m, l.nine, z, zo, q, op9_of<T>(l), l.N, l.pitch, g, s->stream);
-}
-
-template <typename T>
-int multi_gcr_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double tol, int max_iters, int restart, mgx_stats* stats,
-                      double* history, int history_cap)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    const Launch g = multi_gcr_launch<T>(s);
-    if (int rc = multi_ensure(s, nrhs)) return rc;
-    if (int rc = multi_gcr_ensure(s, nrhs, restart, g.blocks)) return rc;
-    const int L = s->cfg.finest_level;
-    Level& l = s->lv[L];
-    auto& ws = s->multi;
-    auto& w = ws.lv[L];
-    const size_t nn = (size_t)(l.N - 1) * (size_t)(l.N - 1);
-    for (int j = 0; j < nrhs; ++j) {
-        if (int rc = copy_in(s, l, w.b[j], (const T*)b + (size_t)j * nn, nn)) return rc;
-        if (int rc = copy_in(s, l, w.u[j], (const T*)u + (size_t)j * nn, nn)) return rc;
-    }
-    std::vector<double> hist[MGX_MAX_RHS];
-    double r[MGX_MAX_RHS] = {}, fu[MGX_MAX_RHS] = {};
-    int iters[MGX_MAX_RHS] = {}, broke[MGX_MAX_RHS] = {};
-    MultiSet all{};
-    for (int j = 0; j < nrhs; ++j) { hist[j].reserve(max_iters + 1); all.act[all.m++] = j; }
-    if (int rc = multi_norms<T>(s, all, r)) return rc;
-    MultiSet a{};
-    for (int j = 0; j < nrhs; ++j) {
-        hist[j].push_back(r[j]);
-        // x_j: the guess, which a column that never iterates returns (b = 0, u = 0: converged, nothing divided)
-        HIPCHK(s, hipMemcpyAsync(ws.x[j], w.u[j], l.bytes, hipMemcpyDeviceToDevice, s->stream));
-        if (!(r[j] <= tol * r[j]) && max_iters > 0) a.act[a.m++] = j;
-    }
-    if (a.m > 0) {
-        // r_j = b_j - A x_j becomes the cycle's right-hand side of the finest level for the whole solve (the caller's b is
-        // on the host: nothing to restore); the scalar blocks start from zero, as GcrMethod::prepare leaves them
-        multi_residual<T, 0>(s, L, a);
-        for (int i = 0; i < a.m; ++i) std::swap(w.b[a.act[i]], w.r[a.act[i]]);
-        HIPCHK(s, hipMemsetAsync(ws.gsc, 0, MGX_MAX_RHS * kGcrScalars * sizeof(double), s->stream));
-    }
-    // zero_start_u: a one-level hierarchy starts its cycle from what the finest u holds (the guess, then the last z)
-    const bool zero_start = L > s->cfg.coarsest_level;
-    std::string first_break;
-    for (int k = 0; k < max_iters && a.m > 0; ++k) {
-        const int j = k % restart;
-        if (zero_start)
-            for (int i = 0; i < a.m; ++i) HIPCHK(s, hipMemsetAsync(w.u[a.act[i]], 0, l.bytes, s->stream));
-        multi_vcycle<T>(s, L, a, s->cycle, fu);                            // z_c = M r_c, into the finest u of the column
-        multi_gcr_direction<T>(s, a, j, g);
-        for (int i = 0; i < a.m; ++i) {
-            const int c = a.act[i];
-            double* sc = ws.gsc + (size_t)c * kGcrScalars;
-            T *zj = (T*)ws.Z[c][j], *qj = (T*)ws.Q[c][j];
-            GcrBasis<T> bs{};
-            for (int q = 0; q < kGcrMaxRestart - 1; ++q) { bs.Q[q] = (const T*)ws.Q[c][q]; bs.Z[q] = (const T*)ws.Z[c][q]; }
-            launch_gcr_orth<T>(j, qj, zj, (const T*)w.b[c], bs, sc, ws.gpart[c], l.N, l.pitch, g, kGcrAllPasses, s->stream);
-            hipLaunchKernelGGL((k_pcg_update<T>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)ws.x[c], (const T*)zj, (T*)w.b[c], (const T*)qj,
-                               (const double*)sc, ws.gpart[c], l.N, l.pitch, g.R, g.strips, g.chunks);
-            hipLaunchKernelGGL(k_pcg_reduce, dim3(1), dim3(kReduceThreads), 0, s->stream, (const double*)ws.gpart[c], g.blocks, (int)kPcgRRMode, sc);
-        }
-        HIPCHK(s, hipGetLastError());
-        HIPCHK(s, hipMemcpyAsync(ws.gsc_host, ws.gsc, (size_t)nrhs * kGcrScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(s, hipStreamSynchronize(s->stream));                        // the one host synchronisation per iteration
-        // a column that broke down or converged leaves the set for good: no later launch reads or writes it
-        MultiSet next{};
-        for (int i = 0; i < a.m; ++i) {
-            const int c = a.act[i];
-            const double* h = ws.gsc_host + (size_t)c * kGcrScalars;
-            if (h[kPcgBreak] != 0.0) {
-                broke[c] = 1;
-                if (first_break.empty()) {
-                    char msg[200];
-                    std::snprintf(msg, sizeof msg, "mgx_solve_multi_gcr: column %d: GCR breakdown at iteration %d: q'.q' = %.17g is not a positive finite number",
-                                  c, k + 1, h[kPcgDelta]);
-                    first_break = msg;
-                }
-                continue;
-            }
-            iters[c] = k + 1;
-            const double rn = std::sqrt(h[kPcgRR]);
-            hist[c].push_back(rn);
-            if (!(rn <= tol * hist[c][0])) next.act[next.m++] = c;
-        }
-        a = next;
-    }
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    for (int j = 0; j < nrhs; ++j)
-        if (int rc = copy_out(s, l, ws.x[j], (T*)u + (size_t)j * nn, nn)) return rc;
-    for (int j = 0; j < nrhs; ++j)
-        finish_solve(stats ? stats + j : nullptr, history ? history + (size_t)j * (size_t)history_cap : nullptr, history_cap, hist[j], iters[j],
-                     !broke[j] && hist[j].back() <= tol * hist[j].front(), t0, fu[j]);
-    if (stats) {
-        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        for (int j = 0; j < nrhs; ++j) stats[j].seconds = seconds;
-    }
-    if (!first_break.empty()) s->err = first_break;
-    return MGX_OK;
-}
-
-// mgx_time_multi_gcr_direction: `repeats` launches of the direction pass on the first nrhs columns, from the finest u of
-// each into its basis slot 0 (which has no meaning between two solves)
-template <typename T>
-int multi_gcr_time_direction(mgx_solver* s, int nrhs, int repeats, double* ms)
-{
-    const Launch g = multi_gcr_launch<T>(s);
-    MultiSet a{};
-    for (int j = 0; j < nrhs; ++j) a.act[a.m++] = j;
-    const int rc = time_on_stream(s, ms, [&] {
-        for (int i = 0; i < repeats; ++i) multi_gcr_direction<T>(s, a, 0, g);
-    });
-    if (!rc) *ms /= repeats;
-    return rc;
-}
-
 } // namespace
 
 #include "mgx_dist.hpp"
@@ -1882,6 +1353,12 @@ int multi_gcr_time_direction(mgx_solver* s, int nrhs, int repeats, double* ms)
     if ((s)->dist) return (s)->fail(MGX_ERR_STATE, "not available on a multi-GPU handle (see mgx.h, Multi-GPU)");
 
 #include "mgx_krylov_host.hpp"
+#include "mgx_multi_host.hpp"
+
+// mgx_create behind its argument list (below): refine_shadow creates the float copy with it
+static int create_solver(const mgx_config* cfg, const mgx_solver* like, mgx_handle* out);
+
+#include "mgx_refine_host.hpp"
 
 // =====================================================================================
 // C-ABI
@@ -2765,14 +2242,15 @@ int mgx_solve(mgx_handle s, double tol, int max_cycles, mgx_stats* stats, double
 
 int mgx_solve_pcg(mgx_handle s, double tol, int max_iters, mgx_stats* stats, double* history, int history_cap)
 {
-    return krylov_solve(s, "mgx_solve_pcg", nullptr, tol, max_iters, stats, history, history_cap, [](auto t) { return PcgMethod<decltype(t)>{}; });
+    return krylov_solve(s, "mgx_solve_pcg", krylov_guard, nullptr, nullptr, tol, max_iters, stats, history, history_cap,
+                        [](auto t) { return PcgMethod<decltype(t)>{}; });
 }
 
 int mgx_solve_gcr(mgx_handle s, double tol, int max_iters, int restart, mgx_stats* stats, double* history, int history_cap)
 {
     static_assert(kGcrMaxRestart == MGX_GCR_MAX_RESTART, "mgx_krylov.hpp and mgx.h disagree");
     const char* bad_restart = (restart < 1 || restart > MGX_GCR_MAX_RESTART) ? "1 <= restart <= MGX_GCR_MAX_RESTART required" : nullptr;
-    return krylov_solve(s, "mgx_solve_gcr", bad_restart, tol, max_iters, stats, history, history_cap,
+    return krylov_solve(s, "mgx_solve_gcr", krylov_guard, bad_restart, nullptr, tol, max_iters, stats, history, history_cap,
                         [restart](auto t) { return GcrMethod<decltype(t)>{restart}; });
 }
 
@@ -2789,86 +2267,6 @@ int mgx_time_gcr_pass(mgx_handle s, int pass, int j, int repeats, double* ms)
         if (!s->kry.Z[i] || !s->kry.Q[i] || !s->kry.x || !s->kry.sc)
             return s->fail(MGX_ERR_STATE, "mgx_time_gcr_pass: call mgx_solve_gcr with restart > j first (it allocates the basis)");
     return s->work_f64 ? gcr_time_pass<double>(s, pass, j, repeats, ms) : gcr_time_pass<float>(s, pass, j, repeats, ms);
-}
-
-// ---- mgx_solve_refine: fp64 defect correction around the cycle of a float copy of the hierarchy ---------------
-// which handles refine (the message names the reason); then the operators must be set / built
-static int refine_guard(mgx_solver* s, const char* fn)
-{
-    NO_DIST(s)
-    if (!s->var)
-        return s->fail(MGX_ERR_STATE, std::string(fn) + ": op = MGX_OPERATOR_POISSON handles refine with dtype MIXED (use dtype MIXED and mgx_solve); "
-                                                        "this entry point is for MGX_OPERATOR_STENCIL5 and MGX_OPERATOR_GALERKIN");
-    if (s->mixed || !s->work_f64)
-        return s->fail(MGX_ERR_STATE, std::string(fn) + ": dtype F64 handles only (the float cycle runs in a copy of the hierarchy inside the handle)");
-    return MGX_OK;
-}
-
-// the whole grids of slots 0 .. nq - 1 of the operator of level lv, rounded to float into the shadow's
-static int refine_round_level(mgx_solver* s, int lv, int nq)
-{
-    const Level& d = s->lv[lv];
-    const Level& w = s->shadow->lv[lv];
-    const dim3 blk(256), grd((unsigned)((d.pitch + 255) / 256), d.rows);
-    for (int q = 0; q < nq; ++q)
-        hipLaunchKernelGGL(k_grid_f64_to_f32, grd, blk, 0, s->stream, (const double*)d.A[q], (float*)w.A[q], d.pitch, w.pitch);
-    HIPCHK(s, hipGetLastError());
-    return MGX_OK;
-}
-
-// The shadow exists and holds the float32 of the handle's current operator: what a public F32 handle of the same cfg
-// holds after mgx_set_stencil on every level (STENCIL5), or after mgx_set_stencil / mgx_set_stencil9 on the finest level
-// and mgx_build_galerkin_transfer with the parent's transfer (GALERKIN) - its splittings, lambda bounds, line factors
-// and dense bottom inverse come from those build paths in float.  A failure (allocation; a breakdown of the float
-// line factors) is returned with the F32 build's message and leaves the fp64 handle as it was; the next call tries again
-static int refine_shadow(mgx_solver* s)
-{
-    if (!s->shadow) {
-        mgx_config c = s->cfg;
-        c.dtype = MGX_DTYPE_F32;
-        c.profile = 0;                                        // (the float cycle is not timed span by span: one graph replay)
-        mgx_handle sh = nullptr;
-        if (int rc = create_solver(&c, s, &sh)) return s->fail(rc, "mgx_solve_refine: float copy of the hierarchy: " + g_create_error);
-        sh->cycle = s->cycle;
-        s->shadow = sh;
-        s->shadow_gen = -1;
-    }
-    if (s->shadow_gen == s->op_gen) return MGX_OK;
-    mgx_solver* f = s->shadow;
-    const int lo = s->cfg.coarsest_level, hi = s->cfg.finest_level;
-    auto failed = [&](int rc) { return s->fail(rc, "mgx_solve_refine: float copy of the hierarchy: " + f->err); };
-    s->shadow_gen = -1;
-    if (s->galerkin) {
-        const bool nine = s->lv[hi].nine;
-        if (nine)
-            if (int rc = finest_corners(f, f->lv[hi])) return failed(rc);
-        if (int rc = refine_round_level(s, hi, nine ? 9 : 5)) return rc;
-        f->lv[hi].nine = nine;
-        galerkin_invalidate(f);
-        if (int rc = galerkin_build_t<float>(f, s->transfer)) return failed(rc);
-    } else {
-        for (int lv = lo; lv <= hi; ++lv) {
-            if (int rc = refine_round_level(s, lv, 5)) return rc;
-            if (int rc = var_build(f, f->lv[lv])) return failed(rc);
-        }
-    }
-    s->shadow_gen = s->op_gen;
-    return MGX_OK;
-}
-
-// one launch of k_refine_pass on the finest level, u -> tmp (has_e) with r32 into the shadow's right-hand side, and
-// the sum of its partials into sum_dev; the caller swaps u and tmp
-static void refine_pass(mgx_solver* s, bool has_e, double scale, double inv_scale)
-{
-    const Level& d = s->lv[s->cfg.finest_level];
-    const Level& w = s->shadow->lv[s->cfg.finest_level];
-    with_point_count(d.nine, [&](auto nq) {
-        constexpr int NQ = decltype(nq)::value;
-        const auto launch = has_e ? launch_refine_pass<NQ, true> : launch_refine_pass<NQ, false>;
-        const int nb = launch((const double*)d.u, (const float*)w.u, (const double*)d.b, op9_of<double>(d), (double*)d.tmp, (float*)w.b, scale,
-                              inv_scale, s->partial, s->partial_cap, d.N, d.pitch, w.pitch, s->rows_per_chunk, s->stream);
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, s->partial, nb, s->sum_dev);
-    });
 }
 
 int mgx_solve_refine(mgx_handle s, double tol, int max_cycles, mgx_stats* stats, double* history, int history_cap)
@@ -2935,123 +2333,12 @@ int mgx_time_refine_pass(mgx_handle s, int repeats, double* ms)
     return rc;
 }
 
-// ---- mgx_solve_refine_gcr: fp64 restarted GCR (mgx_krylov.hpp) around the float cycle of the shadow ---------------
-// Z_j = z = scale * (double) z32 out of the shadow's U, Q_j = A z on the handle's finest operator
-static void refine_gcr_direction(mgx_solver* s, const Launch& g, int j, double scale)
-{
-    const Level& d = s->lv[s->cfg.finest_level];
-    const Level& w = s->shadow->lv[s->cfg.finest_level];
-    with_point_count(d.nine, [&](auto nq) {
-        hipLaunchKernelGGL((k_refine_direction<decltype(nq)::value>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const float*)w.u,
-                           op9_of<double>(d), (double*)s->kry.Z[j], (double*)s->kry.Q[j], scale, d.N, d.pitch, w.pitch, g.R, g.strips, g.chunks);
-    });
-}
-
-// x += alpha Z_j, r -= alpha Q_j (r in lv.b), the partials of ||r||^2 and r32 = (float)(r * inv_scale_next) into the
-// shadow's right-hand side
-static void refine_gcr_update(mgx_solver* s, const Launch& g, int j, double inv_scale_next)
-{
-    const Level& d = s->lv[s->cfg.finest_level];
-    const Level& w = s->shadow->lv[s->cfg.finest_level];
-    hipLaunchKernelGGL(k_refine_update, dim3(g.blocks), dim3(kBlock), 0, s->stream, (double*)s->kry.x, (const double*)s->kry.Z[j], (double*)d.b,
-                       (const double*)s->kry.Q[j], (float*)w.b, inv_scale_next, (const double*)s->kry.sc, s->kry.part, d.N, d.pitch, w.pitch,
-                       g.R, g.strips, g.chunks);
-}
-
-// The iteration: krylov_run's loop over the same workspace (x in kry.x, the caller's b in kry.b, r in lv[L].b for the
-// whole solve) with the cycle replaced by the scaled float cycle of the shadow: r32 is the shadow's lv[L].b and z32 its
-// lv[L].u, the pointers its cached cycle graphs hold.  The orthogonalisation and the reductions are mgx_solve_gcr's
-static int refine_gcr_run(mgx_solver* s, double tol, int max_iters, int restart, std::vector<double>& hist, int* iters, int* breakdown)
-{
-    mgx_solver* f = s->shadow;
-    mgx_solver::KrylovWs& w = s->kry;
-    Level& l = s->lv[s->cfg.finest_level];
-    const Level& fl = f->lv[s->cfg.finest_level];
-    const double n = (double)(l.N - 1);
-    const Launch g = make_launch(l.N, 2, l.N - 1, s->rows_per_chunk);
-    int rc = w.shared(s, l.bytes, g.blocks);
-    if (!rc) rc = GcrMethod<double>{restart}.prepare(s, l.bytes);
-    if (rc) return rc;
-    HIPCHK(s, hipMemcpyAsync(w.x, l.u, l.bytes, hipMemcpyDeviceToDevice, s->stream));
-    HIPCHK(s, hipMemcpyAsync(w.b, l.b, l.bytes, hipMemcpyDeviceToDevice, s->stream));
-    s->norm_blocks_ready = 0;
-    double h0 = 0.0;
-    if ((rc = residual_norm_grid(s, l, w.x, w.b, &h0, MGX_PROF_NORM_FINE))) return rc;
-    hist.push_back(h0);
-    if (h0 <= tol * h0 || max_iters == 0) return MGX_OK;               // (b = 0, u = 0: converged, nothing divided)
-    residual_level<0>(s, l, w.x, w.b, l.b);                            // r = b - A x, into lv[L].b
-    for (int k = 0; k < max_iters; ++k) {
-        // s_k: mgx_solve_refine's rule, a power of two near the rms of the residual the float cycle is given
-        const double scale = pow2_floor(hist[k > 0 ? k - 1 : 0] / n);
-        if (k == 0) {
-            // no scaled residual is pending yet: r32 = (float)((b - A x) / s_0), the bits of r above
-            Prof p(s, MGX_PROF_NORM_FINE, 1);
-            with_point_count(l.nine, [&](auto nq) {
-                launch_refine_pass<decltype(nq)::value, false>((const double*)w.x, (const float*)fl.u, (const double*)w.b, op9_of<double>(l),
-                                                               (double*)l.tmp, (float*)fl.b, 0.0, 1.0 / scale, s->partial, s->partial_cap,
-                                                               l.N, l.pitch, fl.pitch, s->rows_per_chunk, s->stream);
-            });
-        }
-        double unused = 0.0;
-        if ((rc = cycle_body(f, false, true, &unused))) return s->fail(rc, "mgx_solve_refine_gcr: float cycle: " + f->err);   // z32 = M32 r32 from zero
-        {
-            const int j = k % restart;
-            Prof p(s, MGX_PROF_NORM_FINE, j ? 7 : 5);                  // direction, (dots, reduce,) orth, reduce, update, reduce
-            refine_gcr_direction(s, g, j, scale);
-            launch_gcr_orth<double>(j, (double*)w.Q[j], (double*)w.Z[j], (const double*)l.b, gcr_basis<double>(s), w.sc, w.part, l.N, l.pitch, g,
-                                    kGcrAllPasses, s->stream);
-            refine_gcr_update(s, g, j, 1.0 / pow2_floor(hist[k] / n));
-            krylov_reduce(s, g.blocks, kPcgRRMode);
-        }
-        HIPCHK(s, hipGetLastError());
-        HIPCHK(s, hipMemcpyAsync(w.sc_host, w.sc, kPcgScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(s, hipStreamSynchronize(s->stream));                    // the one host synchronisation per iteration
-        if (w.sc_host[kPcgBreak] != 0.0) {
-            *breakdown = 1;
-            char msg[200];
-            std::snprintf(msg, sizeof msg, "mgx_solve_refine_gcr: GCR breakdown at iteration %d: q'.q' = %.17g is not a positive finite number", k + 1,
-                          w.sc_host[kPcgDelta]);
-            s->err = msg;
-            return MGX_OK;
-        }
-        *iters = k + 1;
-        const double rn = std::sqrt(w.sc_host[kPcgRR]);
-        hist.push_back(rn);
-        if (rn <= tol * h0 || k + 1 == max_iters) break;
-    }
-    return MGX_OK;
-}
-
 int mgx_solve_refine_gcr(mgx_handle s, double tol, int max_iters, int restart, mgx_stats* stats, double* history, int history_cap)
 {
-    if (!s) return MGX_ERR_INVALID;
-    if (int rc = refine_guard(s, "mgx_solve_refine_gcr")) return rc;
-    if (max_iters < 0 || !(tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_solve_refine_gcr: tol >= 0 and max_iters >= 0 required");
-    if (restart < 1 || restart > MGX_GCR_MAX_RESTART)
-        return s->fail(MGX_ERR_INVALID, "mgx_solve_refine_gcr: 1 <= restart <= MGX_GCR_MAX_RESTART required");
-    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
-    if (int rc = refine_shadow(s)) return rc;
-    mgx_solver* f = s->shadow;
-    Level& l = s->lv[s->cfg.finest_level];
-    std::vector<double> hist;
-    hist.reserve(max_iters + 1);
-    s->fine_updates = 0.0;
-    f->fine_updates = 0.0;
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    int iters = 0, breakdown = 0;
-    const int rc = refine_gcr_run(s, tol, max_iters, restart, hist, &iters, &breakdown);
-    // U = x, B = the caller's b again (also after a failure part way, where they were saved)
-    if (s->kry.x && s->kry.b && !hist.empty()) {
-        (void)hipMemcpyAsync(l.u, s->kry.x, l.bytes, hipMemcpyDeviceToDevice, s->stream);
-        (void)hipMemcpyAsync(l.b, s->kry.b, l.bytes, hipMemcpyDeviceToDevice, s->stream);
-    }
-    s->norm_blocks_ready = 0;
-    if (rc) return rc;
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    finish_solve(stats, history, history_cap, hist, iters, !breakdown && hist.back() <= tol * hist.front(), t0, f->fine_updates);
-    return MGX_OK;
+    const char* bad_restart = (restart < 1 || restart > MGX_GCR_MAX_RESTART) ? "1 <= restart <= MGX_GCR_MAX_RESTART required" : nullptr;
+    // (refine_guard admits F64 handles only: the method is the same for either tag)
+    return krylov_solve(s, "mgx_solve_refine_gcr", refine_guard, bad_restart, refine_cycle_of, tol, max_iters, stats, history, history_cap,
+                        [restart](auto) { return RefineGcrMethod{restart}; });
 }
 
 int mgx_time_refine_gcr_pass(mgx_handle s, int pass, int repeats, double* ms)
@@ -3067,11 +2354,12 @@ int mgx_time_refine_gcr_pass(mgx_handle s, int pass, int repeats, double* ms)
     const Launch g = make_launch(l.N, 2, l.N - 1, s->rows_per_chunk);
     // the scalars zeroed, as in gcr_time_pass: alpha = 0, so the update leaves x and lv.b (the caller's b here) as they are; it
     // rewrites the shadow's right-hand side, the direction pass basis slot 0 (neither has a meaning between two solves)
-    HIPCHK(s, hipMemsetAsync(s->kry.sc, 0, kGcrScalars * sizeof(double), s->stream));
+    const KrylovView v = krylov_view(s);
+    HIPCHK(s, hipMemsetAsync(v.sc, 0, kGcrScalars * sizeof(double), s->stream));
     const int rc = time_on_stream(s, ms, [&] {
         for (int i = 0; i < repeats; ++i) {
-            if (pass == MGX_REFINE_GCR_PASS_UPDATE) refine_gcr_update(s, g, 0, 1.0);
-            else refine_gcr_direction(s, g, 0, 1.0);
+            if (pass == MGX_REFINE_GCR_PASS_UPDATE) refine_gcr_update(s, v, g, 0, 1.0);
+            else refine_gcr_direction(s, v, g, 0, 1.0);
         }
     });
     if (rc == MGX_OK) *ms /= repeats;
@@ -3150,8 +2438,7 @@ int mgx_time_multi_smoother(mgx_handle s, int nrhs, int sweeps, double* ms)
     if (int rc = multi_guard(s, "mgx_time_multi_smoother")) return rc;
     if (s->multi.cols < nrhs)
         return s->fail(MGX_ERR_STATE, "mgx_time_multi_smoother: call mgx_solve_multi with at least this nrhs first (it allocates the columns)");
-    MultiSet a{};
-    for (int j = 0; j < nrhs; ++j) a.act[a.m++] = j;
+    const MultiSet a = multi_all(nrhs);
     return time_on_stream(s, ms, [&] {
         if (s->work_f64) multi_smooth<double>(s, s->cfg.finest_level, a, sweeps, nullptr);
         else multi_smooth<float>(s, s->cfg.finest_level, a, sweeps, nullptr);

@@ -1,0 +1,509 @@
+// mgx_multi_host.hpp - the host side of mgx_solve_multi and mgx_solve_multi_gcr (absent in the reference; the K-column
+// kernels are mgx_multi.hpp's).  Included by mgx.hip after mgx_krylov_host.hpp.
+#pragma once
+
+namespace {
+
+// ---- mgx_solve_multi: the cycle of a general-operator Jacobi handle on a set of workspace columns ---------------
+// Host code only: the recursion of vcycle / coarse_visits / descend / ascend as a general-operator handle runs it
+// (fold_eligible and zero_in_ok are false there: every block is plain per-level launches, every coarse guess is zeroed by
+// the restriction), on the columns act[0 .. m) of s->multi.  W- and F-cycles go through the per-level launches on every
+// level (k_small_visit is bit-identical to them).  One active column runs the single-column kernels; two to four run
+// one launch of the K-column kernels of mgx_multi.hpp wherever a coefficient is read, and the existing kernels once per
+// column where none is (the bilinear transfers, the injection).  No Prof scopes: cfg.profile does not extend to the call.
+void multi_free_column(mgx_solver::MultiWs& w, int c)
+{
+    auto drop = [](std::initializer_list<void**> ps) {
+        for (void** p : ps) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+    };
+    for (auto& g : w.lv) drop({&g.u[c], &g.tmp[c], &g.b[c], &g.r[c]});
+    drop({(void**)&w.part[c], &w.x[c], (void**)&w.gpart[c]});
+    for (int i = 0; i < kGcrMaxRestart; ++i) drop({&w.Z[c][i], &w.Q[c][i]});
+}
+
+void multi_free(mgx_solver::MultiWs& w)
+{
+    for (int c = 0; c < MGX_MAX_RHS; ++c) multi_free_column(w, c);
+    if (w.sums) (void)hipFree(w.sums);
+    if (w.sums_host) (void)hipHostFree(w.sums_host);
+    w.sums = w.sums_host = nullptr;
+    if (w.gsc) (void)hipFree(w.gsc);
+    if (w.gsc_host) (void)hipHostFree(w.gsc_host);
+    w.gsc = w.gsc_host = nullptr;
+    w.cols = 0;
+}
+
+// columns [0, nrhs) of the workspace exist afterwards.  A failure frees the column it was allocating and leaves the
+// columns that existed: the handle and the smaller workspace stay usable
+int multi_ensure(mgx_solver* s, int nrhs)
+{
+    auto& w = s->multi;
+    const int lo = s->cfg.coarsest_level, hi = s->cfg.finest_level;
+    if (w.lv.empty()) w.lv.resize(s->lv.size());
+    if (!w.sums && hipMalloc((void**)&w.sums, MGX_MAX_RHS * sizeof(double)) != hipSuccess) {
+        w.sums = nullptr;
+        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi: hipMalloc failed for the column sums");
+    }
+    if (!w.sums_host && hipHostMalloc((void**)&w.sums_host, MGX_MAX_RHS * sizeof(double)) != hipSuccess) {
+        w.sums_host = nullptr;
+        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi: hipHostMalloc failed for the column sums");
+    }
+    const Level& f = s->lv[hi];
+    const size_t blocks = (size_t)make_launch(f.N, f.f64 ? 2 : 4, f.N - 1, 1).blocks;
+    for (int c = w.cols; c < nrhs; ++c) {
+        bool ok = hipMalloc((void**)&w.part[c], blocks * sizeof(double)) == hipSuccess;
+        if (!ok) w.part[c] = nullptr;
+        for (int l = lo; ok && l <= hi; ++l)
+            for (void** p : {&w.lv[l].u[c], &w.lv[l].tmp[c], &w.lv[l].b[c], &w.lv[l].r[c]})
+                if (!(ok = alloc_zeroed(s, p, s->lv[l].bytes))) break;
+        if (!ok) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(s->stream);
+            multi_free_column(w, c);
+            return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi: hipMalloc failed for the arrays of column " + std::to_string(c));
+        }
+        w.cols = c + 1;
+    }
+    return MGX_OK;
+}
+
+// the active columns of a launch: act[0 .. m), m >= 1, ascending
+struct MultiSet { int act[MGX_MAX_RHS]; int m; };
+
+inline MultiSet multi_all(int nrhs)
+{
+    MultiSet a{};
+    for (int j = 0; j < nrhs; ++j) a.act[a.m++] = j;
+    return a;
+}
+
+template <typename T, int K> MultiIn<T, K> multi_in(void* const* grids, const MultiSet& a)
+{
+    MultiIn<T, K> o;
+    for (int j = 0; j < K; ++j) o.p[j] = (const T*)grids[a.act[j]];
+    return o;
+}
+template <typename T, int K> MultiOut<T, K> multi_out(void* const* grids, const MultiSet& a)
+{
+    MultiOut<T, K> o;
+    for (int j = 0; j < K; ++j) o.p[j] = grids ? (T*)grids[a.act[j]] : nullptr;
+    return o;
+}
+
+// smooth_var_t on the set; fu (may be null): each column's fine_updates, counted as smooth() counts them
+template <typename T>
+void multi_smooth(mgx_solver* s, int level, const MultiSet& a, int mu, double* fu)
+{
+    if (mu <= 0) return;
+    const Level& l = s->lv[level];
+    auto& w = s->multi.lv[level];
+    const T om = (T)s->cfg.omega;
+    const T rc = (T)(1.0 - (double)om);
+    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
+    const VarLevel<T> v = var_level<T>(l);
+    const dim3 grd(g.blocks), blk(kBlock);
+    for (int i = 0; i < mu; ++i) {
+        with_point_count(v.nine, [&](auto nq) {
+            constexpr int NQ = decltype(nq)::value;
+            if (a.m == 1) {
+                const int c = a.act[0];
+                hipLaunchKernelGGL((k_jacobi_var<T, NQ>), grd, blk, 0, s->stream, (const T*)w.u[c], (const T*)w.b[c], (T*)w.tmp[c], v.dinv, v.r,
+                                   v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
+            } else with_column_count(a.m, [&](auto kc) {
+                constexpr int K = decltype(kc)::value;
+                hipLaunchKernelGGL((k_jacobi_var_multi<T, NQ, K>), grd, blk, 0, s->stream, multi_in<T, K>(w.u, a), multi_in<T, K>(w.b, a),
+                                   multi_out<T, K>(w.tmp, a), v.dinv, v.r, v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
+            });
+        });
+        for (int j = 0; j < a.m; ++j) std::swap(w.u[a.act[j]], w.tmp[a.act[j]]);
+    }
+    if (fu && level == s->cfg.finest_level)
+        for (int j = 0; j < a.m; ++j) fu[a.act[j]] += (double)mu * (double)(l.N - 1) * (double)(l.N - 1);
+}
+
+// residual_var_t on the set.  MODE 0: r_j = b_j - A u_j into the level's r;  MODE 1: per-block sums of r_j^2 into the
+// column's partials (finest level), each reduced by k_reduce_partials in its own order into sums[column]
+template <typename T, int MODE>
+void multi_residual(mgx_solver* s, int level, const MultiSet& a)
+{
+    const Level& l = s->lv[level];
+    auto& ws = s->multi;
+    auto& w = ws.lv[level];
+    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
+    const VarLevel<T> v = var_level<T>(l);
+    const dim3 grd(g.blocks), blk(kBlock);
+    with_point_count(v.nine, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        if (a.m == 1) {
+            const int c = a.act[0];
+            hipLaunchKernelGGL((k_residual_var<T, NQ, MODE>), grd, blk, 0, s->stream, (const T*)w.u[c], (const T*)w.b[c], MODE ? (T*)nullptr : (T*)w.r[c],
+                               MODE ? ws.part[c] : (double*)nullptr, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
+        } else with_column_count(a.m, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            MultiOut<double, K> part;
+            for (int j = 0; j < K; ++j) part.p[j] = MODE ? ws.part[a.act[j]] : nullptr;
+            hipLaunchKernelGGL((k_residual_var_multi<T, NQ, MODE, K>), grd, blk, 0, s->stream, multi_in<T, K>(w.u, a), multi_in<T, K>(w.b, a),
+                               multi_out<T, K>(MODE ? nullptr : w.r, a), part, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
+        });
+    });
+    if (MODE == 1)
+        for (int j = 0; j < a.m; ++j)
+            hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, ws.part[a.act[j]], g.blocks, ws.sums + a.act[j]);
+}
+
+// restrict_level(level, fused = true, zero_guess = true) on the set
+template <typename T>
+void multi_restrict(mgx_solver* s, int level, const MultiSet& a)
+{
+    const Level& f = s->lv[level];
+    const Level& c = s->lv[level - 1];
+    auto& wf = s->multi.lv[level];
+    auto& wc = s->multi.lv[level - 1];
+    const int mode = s->cfg.restrict_mode;
+    if (opdep(s)) {
+        const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
+        const T rscale = (mode == MGX_RESTRICT_FW16) ? (T)0.25 : (T)1;
+        const dim3 grd(g.blocks), blk(kBlock);
+        with_point_count(f.nine, [&](auto nq) {
+            constexpr int MODE = decltype(nq)::value == 9 ? 2 : 1;
+            if (a.m == 1) {
+                const int j = a.act[0];
+                hipLaunchKernelGGL((k_restrict_opdep<T, MODE>), grd, blk, 0, s->stream, (const T*)wf.u[j], (const T*)wf.b[j], op9_of<T>(f), wt8_of<T>(c),
+                                   (T*)wc.b[j], (T*)wc.u[j], c.N, f.pitch, c.pitch, g.strips, rscale);
+            } else with_column_count(a.m, [&](auto kc) {
+                constexpr int K = decltype(kc)::value;
+                hipLaunchKernelGGL((k_restrict_opdep_multi<T, MODE, K>), grd, blk, 0, s->stream, multi_in<T, K>(wf.u, a), multi_in<T, K>(wf.b, a),
+                                   op9_of<T>(f), wt8_of<T>(c), multi_out<T, K>(wc.b, a), multi_out<T, K>(wc.u, a), c.N, f.pitch, c.pitch,
+                                   g.strips, rscale);
+            });
+        });
+        return;
+    }
+    // the residual as a grid (the operator's grids read once for the set), then the coefficient-free transfer of each
+    // column with the single-column kernel
+    multi_residual<T, 0>(s, level, a);
+    for (int i = 0; i < a.m; ++i) {
+        const int j = a.act[i];
+        if (mode >= MGX_RESTRICT_INJECT) {
+            const double wgt = (mode == MGX_RESTRICT_INJECT4) ? 4.0 : 1.0;
+            const dim3 blk(256), grd((c.N + 255) / 256, c.N - 1);
+            hipLaunchKernelGGL((k_restrict_inject<T>), grd, blk, 0, s->stream, (const T*)wf.r[j], (T*)wc.b[j], (T*)wc.u[j], c.N, f.pitch, c.pitch, (T)wgt);
+        } else {
+            launch_restrict<T>((const T*)wf.u[j], (const T*)wf.r[j], (T*)wc.b[j], (T*)wc.u[j], f.N, f.pitch, c.pitch, 1, c.N, 0, mode, false,
+                               s->rows_per_chunk, s->stream);
+        }
+    }
+}
+
+// prolong_level(level, add = true) on the set
+template <typename T>
+void multi_prolong(mgx_solver* s, int level, const MultiSet& a)
+{
+    const Level& f = s->lv[level];
+    const Level& c = s->lv[level - 1];
+    auto& wf = s->multi.lv[level];
+    auto& wc = s->multi.lv[level - 1];
+    if (!opdep(s)) {
+        for (int i = 0; i < a.m; ++i)
+            launch_prolong<T>((T*)wf.u[a.act[i]], (const T*)wc.u[a.act[i]], f.N, f.pitch, c.pitch, 1, f.N, 0, true, s->rows_per_chunk, s->stream);
+        return;
+    }
+    const Launch g = make_launch(c.N, VecOf<T>::W, c.N, 1);
+    const dim3 grd(g.blocks), blk(kBlock);
+    if (a.m == 1)
+        hipLaunchKernelGGL((k_prolong_opdep<T, true>), grd, blk, 0, s->stream, (T*)wf.u[a.act[0]], (const T*)wc.u[a.act[0]], wt8_of<T>(c), c.N, f.pitch,
+                           c.pitch, g.strips);
+    else with_column_count(a.m, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL((k_prolong_opdep_multi<T, true, K>), grd, blk, 0, s->stream, multi_out<T, K>(wf.u, a), multi_in<T, K>(wc.u, a), wt8_of<T>(c),
+                           c.N, f.pitch, c.pitch, g.strips);
+    });
+}
+
+// the visit of the coarsest level: bottom_solve, or the two blocks of bottom = SMOOTH
+template <typename T>
+void multi_bottom(mgx_solver* s, const MultiSet& a, double* fu)
+{
+    const int level = s->cfg.coarsest_level;
+    if (s->cfg.bottom != MGX_BOTTOM_EXACT) {
+        multi_smooth<T>(s, level, a, s->cfg.mu1, fu);
+        multi_smooth<T>(s, level, a, s->cfg.mu2, fu);
+        return;
+    }
+    const Level& l = s->lv[level];
+    auto& w = s->multi.lv[level];
+    const int n = l.N - 1;
+    const dim3 grd((n * n + 63) / 64), blk(64);
+    if (a.m == 1)
+        hipLaunchKernelGGL((k_var_dense_solve<T>), grd, blk, 0, s->stream, s->var_inv, (const T*)w.b[a.act[0]], (T*)w.u[a.act[0]], n, l.pitch);
+    else with_column_count(a.m, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL((k_var_dense_solve_multi<T, K>), grd, blk, 0, s->stream, s->var_inv, multi_in<T, K>(w.b, a), multi_out<T, K>(w.u, a), n, l.pitch);
+    });
+}
+
+template <typename T> void multi_vcycle(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu);
+
+// coarse_visits on the set (no k_small_visit)
+template <typename T>
+void multi_visits(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu)
+{
+    const bool twice = kind != MGX_CYCLE_V && level > s->cfg.coarsest_level;
+    multi_vcycle<T>(s, level, a, kind, fu);
+    if (twice) multi_vcycle<T>(s, level, a, kind == MGX_CYCLE_F ? MGX_CYCLE_V : kind, fu);
+}
+
+// vcycle on the set: descend (mu1 sweeps, the residual restricted, the coarse guess zeroed), the visits of the level
+// below, ascend (the correction, mu2 sweeps)
+template <typename T>
+void multi_vcycle(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu)
+{
+    if (level == s->cfg.coarsest_level) { multi_bottom<T>(s, a, fu); return; }
+    multi_smooth<T>(s, level, a, s->cfg.mu1, fu);
+    multi_restrict<T>(s, level, a);
+    multi_visits<T>(s, level - 1, a, kind, fu);
+    multi_prolong<T>(s, level, a);
+    multi_smooth<T>(s, level, a, s->cfg.mu2, fu);
+}
+
+// ||b_j - A u_j|| of the set's columns on the finest level into r[column]: one copy, one host synchronisation
+template <typename T>
+int multi_norms(mgx_solver* s, const MultiSet& a, double* r)
+{
+    multi_residual<T, 1>(s, s->cfg.finest_level, a);
+    HIPCHK(s, hipMemcpyAsync(s->multi.sums_host, s->multi.sums, MGX_MAX_RHS * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    for (int j = 0; j < a.m; ++j) r[a.act[j]] = std::sqrt(s->multi.sums_host[a.act[j]]);
+    return MGX_OK;
+}
+
+// which handles solve blocks of right-hand sides (the message names the reason); then the operators must be set / built
+int multi_guard(mgx_solver* s, const char* fn)
+{
+    const std::string f(fn);
+    if (s->dist) return s->fail(MGX_ERR_STATE, f + ": not available on a multi-GPU handle (see mgx.h, Multi-GPU)");
+    if (!s->var)
+        return s->fail(MGX_ERR_STATE, f + ": op = MGX_OPERATOR_POISSON kernels read no coefficient grids, there is nothing for the columns to "
+                                          "share; this entry point is for MGX_OPERATOR_STENCIL5 and MGX_OPERATOR_GALERKIN");
+    if (s->mixed) return s->fail(MGX_ERR_STATE, f + ": dtype MIXED is not supported (F64 or F32)");
+    if (s->cfg.smoother != MGX_SMOOTHER_JACOBI)
+        return s->fail(MGX_ERR_STATE, f + ": smoother MGX_SMOOTHER_JACOBI only (multi-column Chebyshev, line and colour smoothers are a follow-up)");
+    return var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level);
+}
+
+// ---- the frame of a block solve: what mgx_solve_multi and mgx_solve_multi_gcr do around their loops ------------------
+template <typename T>
+struct MultiFrame {
+    mgx_solver* s;
+    int nrhs;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    std::vector<double> hist[MGX_MAX_RHS];
+    double fu[MGX_MAX_RHS] = {};
+    int iters[MGX_MAX_RHS] = {}, broke[MGX_MAX_RHS] = {};
+
+    Level& fine() const { return s->lv[s->cfg.finest_level]; }
+    size_t nn() const { return (size_t)(fine().N - 1) * (size_t)(fine().N - 1); }
+    // the caller's b and u into the finest b and u of the columns (which exist); hist[j][0] = ||b_j - A u_j||
+    int begin(const void* b, const void* u, int max_iters)
+    {
+        auto& w = s->multi.lv[s->cfg.finest_level];
+        for (int j = 0; j < nrhs; ++j) {
+            if (int rc = copy_in(s, fine(), w.b[j], (const T*)b + (size_t)j * nn(), nn())) return rc;
+            if (int rc = copy_in(s, fine(), w.u[j], (const T*)u + (size_t)j * nn(), nn())) return rc;
+        }
+        double r[MGX_MAX_RHS] = {};
+        if (int rc = multi_norms<T>(s, multi_all(nrhs), r)) return rc;
+        for (int j = 0; j < nrhs; ++j) {
+            hist[j].reserve(max_iters + 1);
+            hist[j].push_back(r[j]);
+        }
+        return MGX_OK;
+    }
+
+    // the columns of `a` that go on: a column leaves the set for good as soon as it breaks down or its history meets the
+    // tolerance, and nothing reads or writes it again
+    MultiSet active(const MultiSet& a, double tol) const
+    {
+        MultiSet next{};
+        for (int i = 0; i < a.m; ++i) {
+            const int j = a.act[i];
+            if (!broke[j] && !(hist[j].back() <= tol * hist[j][0])) next.act[next.m++] = j;
+        }
+        return next;
+    }
+
+    // the iterates out of src[column] into the caller's u, the statistics and histories, one `seconds` for all columns
+    int finish(void* const* src, void* u, double tol, mgx_stats* stats, double* history, int history_cap)
+    {
+        HIPCHK(s, hipGetLastError());
+        HIPCHK(s, hipStreamSynchronize(s->stream));
+        for (int j = 0; j < nrhs; ++j)
+            if (int rc = copy_out(s, fine(), src[j], (T*)u + (size_t)j * nn(), nn())) return rc;
+        for (int j = 0; j < nrhs; ++j)
+            finish_solve(stats ? stats + j : nullptr, history ? history + (size_t)j * (size_t)history_cap : nullptr, history_cap, hist[j], iters[j],
+                         !broke[j] && hist[j].back() <= tol * hist[j].front(), t0, fu[j]);
+        if (stats) {
+            const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            for (int j = 0; j < nrhs; ++j) stats[j].seconds = seconds;
+        }
+        return MGX_OK;
+    }
+};
+
+template <typename T>
+int multi_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double tol, int max_cycles, mgx_stats* stats, double* history, int history_cap)
+{
+    MultiFrame<T> fr{s, nrhs};
+    if (int rc = multi_ensure(s, nrhs)) return rc;
+    if (int rc = fr.begin(b, u, max_cycles)) return rc;
+    const int L = s->cfg.finest_level;
+    MultiSet a = multi_all(nrhs);
+    for (int k = 0; k < max_cycles; ++k) {
+        a = fr.active(a, tol);
+        if (a.m == 0) break;
+        multi_vcycle<T>(s, L, a, s->cycle, fr.fu);
+        double r[MGX_MAX_RHS] = {};
+        if (int rc = multi_norms<T>(s, a, r)) return rc;
+        for (int i = 0; i < a.m; ++i) { fr.hist[a.act[i]].push_back(r[a.act[i]]); fr.iters[a.act[i]] = k + 1; }
+    }
+    return fr.finish(s->multi.lv[L].u, u, tol, stats, history, history_cap);
+}
+
+// ---- mgx_solve_multi_gcr: GcrMethod's passes (mgx_krylov_host.hpp) on the view of every active column, around multi_vcycle ----
+// the geometry of every Krylov pass, krylov_run's: the per-block partial sums set the summation order
+template <typename T> Launch multi_gcr_launch(const mgx_solver* s)
+{
+    const Level& l = s->lv[s->cfg.finest_level];
+    return make_launch(l.N, VecOf<T>::W, l.N - 1, s->rows_per_chunk);
+}
+
+// the Krylov pieces of columns [0, nrhs) with `restart` basis pairs each exist afterwards (multi_ensure has made the
+// columns).  Every piece is allocated once, by the first call that needs it; a failure leaves what existed
+int multi_gcr_ensure(mgx_solver* s, int nrhs, int restart, int blocks)
+{
+    auto& w = s->multi;
+    const Level& l = s->lv[s->cfg.finest_level];
+    if (!w.gsc && hipMalloc((void**)&w.gsc, MGX_MAX_RHS * kGcrScalars * sizeof(double)) != hipSuccess) {
+        w.gsc = nullptr;
+        (void)hipGetLastError();
+        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipMalloc failed for the column scalars");
+    }
+    if (!w.gsc_host && hipHostMalloc((void**)&w.gsc_host, MGX_MAX_RHS * kGcrScalars * sizeof(double)) != hipSuccess) {
+        w.gsc_host = nullptr;
+        (void)hipGetLastError();
+        return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipHostMalloc failed for the column scalars");
+    }
+    for (int c = 0; c < nrhs; ++c) {
+        // k_gcr_dots<T, 7> writes seven partials per workgroup (KrylovWs::shared)
+        if (!w.gpart[c] && hipMalloc((void**)&w.gpart[c], ((size_t)(kGcrMaxRestart - 1) * blocks + 8) * sizeof(double)) != hipSuccess) {
+            w.gpart[c] = nullptr;
+            (void)hipGetLastError();
+            return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipMalloc failed for the partial sums of column " + std::to_string(c));
+        }
+        auto vec = [&](void** p) { return *p || alloc_zeroed(s, p, l.bytes); };
+        bool ok = vec(&w.x[c]);
+        for (int i = 0; ok && i < restart; ++i) ok = vec(&w.Z[c][i]) && vec(&w.Q[c][i]);
+        if (!ok) return s->fail(MGX_ERR_ALLOC, "mgx_solve_multi_gcr: hipMalloc failed for the Krylov vectors of column " + std::to_string(c));
+    }
+    return MGX_OK;
+}
+
+// Z_c[j] = z_c (the finest u of the column), Q_c[j] = A z_c for the columns of the set: one launch, the operator read once
+template <typename T>
+void multi_gcr_direction(mgx_solver* s, const MultiSet& a, int j, const Launch& g)
+{
+    const Level& l = s->lv[s->cfg.finest_level];
+    auto& ws = s->multi;
+    auto& w = ws.lv[s->cfg.finest_level];
+    if (a.m == 1) {
+        // k_pcg_direction's first iteration, as mgx_solve_gcr launches it (its partials z.q go where nothing reads them)
+        const KrylovView v = krylov_view(s, a.act[0]);
+        krylov_direction<T>(s, v, l, g, (const T*)w.u[a.act[0]], (const T*)w.u[a.act[0]], (T*)v.Z[j], (T*)v.Q[j], true);
+        return;
+    }
+    const T* z[MGX_MAX_RHS];
+    T *zo[MGX_MAX_RHS], *q[MGX_MAX_RHS];
+    for (int i = 0; i < a.m; ++i) {
+        const int c = a.act[i];
+        z[i] = (const T*)w.u[c]; zo[i] = (T*)ws.Z[c][j]; q[i] = (T*)ws.Q[c][j];
+    }
+    launch_gcr_direction_multi<T>(a.m, l.nine, z, zo, q, op9_of<T>(l), l.N, l.pitch, g, s->stream);
+}
+
+template <typename T>
+int multi_gcr_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double tol, int max_iters, int restart, mgx_stats* stats,
+                      double* history, int history_cap)
+{
+    MultiFrame<T> fr{s, nrhs};
+    const Launch g = multi_gcr_launch<T>(s);
+    if (int rc = multi_ensure(s, nrhs)) return rc;
+    if (int rc = multi_gcr_ensure(s, nrhs, restart, g.blocks)) return rc;
+    if (int rc = fr.begin(b, u, max_iters)) return rc;
+    const int L = s->cfg.finest_level;
+    Level& l = s->lv[L];
+    auto& ws = s->multi;
+    auto& w = ws.lv[L];
+    // x_j: the guess, which a column that never iterates returns (b = 0, u = 0: converged, nothing divided)
+    for (int j = 0; j < nrhs; ++j) HIPCHK(s, hipMemcpyAsync(ws.x[j], w.u[j], l.bytes, hipMemcpyDeviceToDevice, s->stream));
+    MultiSet a = max_iters > 0 ? fr.active(multi_all(nrhs), tol) : MultiSet{};
+    if (a.m > 0) {
+        // r_j = b_j - A x_j becomes the cycle's right-hand side of the finest level for the whole solve (the caller's b is
+        // on the host: nothing to restore); the scalar blocks start from zero, as GcrMethod::prepare leaves them
+        multi_residual<T, 0>(s, L, a);
+        for (int i = 0; i < a.m; ++i) std::swap(w.b[a.act[i]], w.r[a.act[i]]);
+        HIPCHK(s, hipMemsetAsync(ws.gsc, 0, MGX_MAX_RHS * kGcrScalars * sizeof(double), s->stream));
+    }
+    // zero_start_u: a one-level hierarchy starts its cycle from what the finest u holds (the guess, then the last z)
+    const bool zero_start = L > s->cfg.coarsest_level;
+    std::string first_break;
+    for (int k = 0; k < max_iters && a.m > 0; ++k) {
+        const int j = k % restart;
+        if (zero_start)
+            for (int i = 0; i < a.m; ++i) HIPCHK(s, hipMemsetAsync(w.u[a.act[i]], 0, l.bytes, s->stream));
+        multi_vcycle<T>(s, L, a, s->cycle, fr.fu);                         // z_c = M r_c, into the finest u of the column
+        multi_gcr_direction<T>(s, a, j, g);
+        for (int i = 0; i < a.m; ++i) {
+            const KrylovView v = krylov_view(s, a.act[i]);
+            gcr_orth<T>(s, v, l, g, j);
+            gcr_update<T>(s, v, l, g, j);
+        }
+        HIPCHK(s, hipGetLastError());
+        HIPCHK(s, hipMemcpyAsync(ws.gsc_host, ws.gsc, (size_t)nrhs * kGcrScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(s, hipStreamSynchronize(s->stream));                        // the one host synchronisation per iteration
+        for (int i = 0; i < a.m; ++i) {
+            const int c = a.act[i];
+            const KrylovStep st = krylov_step(ws.gsc_host + (size_t)c * kGcrScalars);
+            if (st.broke) {
+                fr.broke[c] = 1;
+                if (first_break.empty())
+                    first_break = breakdown_message("mgx_solve_multi_gcr: column " + std::to_string(c) + ": GCR", k + 1, GcrMethod<T>::quantity, st.value);
+                continue;
+            }
+            fr.iters[c] = k + 1;
+            fr.hist[c].push_back(st.value);
+        }
+        a = fr.active(a, tol);
+    }
+    if (int rc = fr.finish(ws.x, u, tol, stats, history, history_cap)) return rc;
+    if (!first_break.empty()) s->err = first_break;
+    return MGX_OK;
+}
+
+// mgx_time_multi_gcr_direction: `repeats` launches of the direction pass on the first nrhs columns, from the finest u of
+// each into its basis slot 0 (which has no meaning between two solves)
+template <typename T>
+int multi_gcr_time_direction(mgx_solver* s, int nrhs, int repeats, double* ms)
+{
+    const Launch g = multi_gcr_launch<T>(s);
+    const MultiSet a = multi_all(nrhs);
+    const int rc = time_on_stream(s, ms, [&] {
+        for (int i = 0; i < repeats; ++i) multi_gcr_direction<T>(s, a, 0, g);
+    });
+    if (!rc) *ms /= repeats;
+    return rc;
+}
+
+} // namespace

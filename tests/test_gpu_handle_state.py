@@ -132,7 +132,7 @@ after solve_pcg, in the order above: 2.1e-6 / 3.7e-6 / 2.1e-5; 1.3e-6 / 8.3e-6 /
 5.2e-6; 2.0e-6 / 2.2e-6 / 8.3e-7 (solve_gcr there: 2.8e-6 / 1.3e-4); mgx_solve's histories at most 2.2e-6.  The runs under
 MGX_SMALL_VISIT=0, MGX_GRAPH=0 and MGX_GS_FUSED=0 give the same figures to the digit.
 
-REFINE_GCR_CASES add mgx_solve_refine_gcr (csrc/mgx.hip: refine_gcr_run, csrc/mgx_refine_gcr.hpp) and mgx_time_refine_gcr_pass,
+REFINE_GCR_CASES add mgx_solve_refine_gcr (csrc/mgx_refine_host.hpp: RefineGcrMethod, csrc/mgx_refine_gcr.hpp) and mgx_time_refine_gcr_pass,
 drawn with refine_gcr=True on top of refine and gcr (refine_gcr_stage; what it promises: draw_sequence).  The call shares the float
 copy of the hierarchy - r32, z32, the cached cycle graphs - with mgx_solve_refine, the Krylov workspace, the scalar block and the
 partial sums with mgx_solve_gcr and mgx_solve_pcg, and keeps its residual in B of the finest level for the whole solve.  The model

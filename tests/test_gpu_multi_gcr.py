@@ -271,6 +271,52 @@ def test_a_new_operator_is_followed_and_the_workspace_grows(pkg):
         assert_block(mg, b, u0, TOL, ITERS, 4, sequential(mg, b, u0, TOL, ITERS, 4), "after set_coefficient and a rebuild")
 
 
+def test_the_three_gcr_users_interleaved_on_one_handle(pkg):
+    """mgx_solve_gcr, mgx_solve_multi_gcr and mgx_solve_refine_gcr run the same passes on views of two workspaces (the
+    handle's own, the columns'): no call may see the scalars, partial sums or basis slots another one left, in either
+    workspace.  Every call on the one handle against the same call on a fresh handle; the bases grow between the calls
+    (restart 2, then 4 in the handle's workspace; 4, then 2 on three, then two columns).  63^2: more than one workgroup per
+    pass, three levels"""
+    L, Lc, iters = 6, 3, 6
+    b, u0 = np.stack([rand(L, 50 + j) for j in range(3)]), np.stack([rand(L, 60 + j) for j in range(3)])
+    new = lambda: handle(pkg, L, Lc, "gal", "contrast10")
+
+    def single(solve):
+        def call(mg):
+            mg.set_rhs(b[0])
+            mg.set_guess(u0[0])
+            st, hist = solve(mg)
+            u = mg.get_solution()
+            # U = the iterate, B = the caller's b again
+            assert np.array_equal(mg.get_level(L, pkg.VEC_U), u) and np.array_equal(mg.get_level(L, pkg.VEC_B), b[0])
+            return [(st, hist, u)]
+        return call
+
+    def multi(nrhs, restart):
+        def call(mg):
+            before = mg.get_level(L, pkg.VEC_U), mg.get_level(L, pkg.VEC_B)
+            got = block(mg, b[:nrhs], u0[:nrhs], 0.0, iters, restart)
+            # U and B are left as they were
+            assert np.array_equal(mg.get_level(L, pkg.VEC_U), before[0]) and np.array_equal(mg.get_level(L, pkg.VEC_B), before[1])
+            return got
+        return call
+
+    calls = [("solve_gcr(restart=2)", single(lambda mg: mg.solve_gcr(tol=0.0, max_iters=iters, restart=2))),
+             ("solve_multi_gcr(3 columns, restart=4)", multi(3, 4)),
+             ("solve_refine_gcr(restart=3)", single(lambda mg: mg.solve_refine_gcr(tol=0.0, max_iters=iters, restart=3))),
+             ("solve_gcr(restart=4)", single(lambda mg: mg.solve_gcr(tol=0.0, max_iters=iters, restart=4))),
+             ("solve_multi_gcr(2 columns, restart=2)", multi(2, 2))]
+    with new() as mg:
+        for what, call in calls:
+            got = call(mg)
+            with new() as fresh:
+                want = call(fresh)
+            assert len(got) == len(want)
+            for j, (g, w) in enumerate(zip(got, want)):
+                assert g[0].cycles == iters, (what, j, g[0].cycles)
+                assert_column(g, w, f"{what} on the long-lived handle, column {j}")
+
+
 # ---- 8. bounds -------------------------------------------------------------------------------------------------------------
 def test_a_short_history_slot_is_not_overrun(pkg):
     L, Lc, cap = 6, 3, 3

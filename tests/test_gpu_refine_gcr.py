@@ -26,7 +26,7 @@ Beyond the parity at R = 4 (sections 6 .. 9; times and fractions measured on an 
   * chunk heights: tests/test_gpu_refine.py's ROWS_CASES under check_parity with the reference's dots at the same height - MGX_ROWS
     1, 3, 5, 8, 64 on 63 rows, 3 and 8 nine-point, level 10 at its own R = 7 five- and nine-point.  0 of both bounds everywhere but
     galerkin-10-4-rows-default, 2.0e-7 of the history bound (its first entry); 0.02 s each, the level-10 cases 0.3 s.  A launch that
-    ignores MGX_ROWS in refine_gcr_run alone stays self-consistent at R = 4 and only sums in another order: it uses up to 3.0e-2 of
+    ignores MGX_ROWS in the driver's loop alone stays self-consistent at R = 4 and only sums in another order: it uses up to 3.0e-2 of
     the history and 2.0e-3 of the iterate bound here and passes - the bounds are tests/test_gpu_pcg.py's and are not tightened.
   * the breakdown exit on finite data (V(0,0), checkerboard b, zero guess: history [63.], U and B restored, twice; then random
     data against the composition, 0 of both bounds, 1162.82 -> 1161.21; then mgx_solve_gcr and mgx_solve_refine as on a handle that
