@@ -579,6 +579,47 @@ MGX_API int mgx_solve_multi(mgx_handle h, int nrhs, const void* b, void* u, doub
 MGX_API int mgx_solve_multi_gcr(mgx_handle h, int nrhs, const void* b, void* u, double tol, int max_iters, int restart,
                                 mgx_stats* stats, double* history, int history_cap);
 
+/* mgx_solve_refine_gcr's iteration on up to MGX_MAX_RHS right-hand sides for one operator: fp64 restarted GCR on the
+ * finest level, the preconditioner mgx_solve_multi's float cycle from zero on the columns of the float copy of the
+ * hierarchy still iterating (a sweep moves 4 (NQ + 3 nrhs) bytes per point where nrhs fp64 solves move 8 nrhs (NQ + 3)),
+ * the direction pass Z_j = z = s (double) z32, Q_j = A z one launch of k_refine_direction_multi for the set (8 NQ + 20 nrhs
+ * bytes per point instead of nrhs (8 NQ + 20); every instance, the nine-point one on four columns included, runs without
+ * scratch: four nine-point columns are one launch).  The orthogonalisation, the mixed update and the reductions read no
+ * coefficients and run once per column, in mgx_solve_refine_gcr's geometry, on that column's own scalars and partial sums;
+ * all columns share the iteration index k and so the basis slot k mod restart.  Arguments as for mgx_solve_multi_gcr: b
+ * and u are nrhs host vectors of doubles back to back (u the guesses on entry, the iterates on return), stats NULL or
+ * nrhs entries, history NULL or nrhs slots of history_cap doubles.
+ * What column j returns - iterate, history, cycles, converged, initial_residual, final_residual, history_len,
+ * fine_updates (those of the float cycle) - is bit for bit what mgx_set_rhs(b_j); mgx_set_guess(u_j);
+ * mgx_solve_refine_gcr(h, tol, max_iters, restart, ..); mgx_get_solution returns on the same handle.  The scale of
+ * iteration k of column j comes from that column's own history: pow2_floor(hist_j[max(k - 1, 0)] / n).
+ * stats[j].seconds is the wall time of the whole call in every entry.  A column leaves the active set for good - no
+ * later launch reads or writes it - under mgx_solve_multi_gcr's rules: hist[0] <= tol * hist[0] or max_iters = 0 (one
+ * history entry, the guess returned), ||r|| <= tol * hist[0] after an iteration, or its own breakdown (converged = 0,
+ * its x as before that iteration; the call still returns MGX_OK and mgx_last_error names the first such column and
+ * iteration).  Deterministic; one device-to-host copy and one host synchronisation per iteration serve all columns;
+ * launched eagerly (cfg.profile does not extend to the call).
+ * One configuration is defined differently and not held to the sequential bits: on a one-level hierarchy (finest =
+ * coarsest) with bottom = SMOOTH, mgx_solve_refine_gcr starts its float cycle from whatever the float copy's U held
+ * before; this call zeroes the column's float u before every cycle.  (With bottom = EXACT the dense solve overwrites it,
+ * and the contract holds.)
+ * The handle's own U, B, R of every level, its mgx_solve_pcg / mgx_solve_gcr workspace, its cached graphs and its
+ * fine_updates, and the float copy's own vectors and graphs, are left as they were; every other entry point -
+ * mgx_solve_refine, mgx_solve_refine_gcr, mgx_solve_multi and mgx_solve_multi_gcr included - computes, before and after,
+ * the bits of a handle that never made the call.  Memory: the float copy of the hierarchy (shared with
+ * mgx_solve_refine and mgx_solve_refine_gcr); mgx_solve_multi's columns of the float copy (float u, tmp, b, r of every
+ * level per column); the handle's mgx_solve_multi_gcr workspace, shared with that call (per column x, r, scratch,
+ * restart pairs Z, Q, the partial sums and a block of scalars) - its coarse fp64 columns are allocated and not used by
+ * this call: the price of one workspace.  A later call with a larger nrhs or restart adds the difference.
+ * Single-GPU handles of dtype F64, op STENCIL5 or GALERKIN, smoother JACOBI: every cycle kind, either transfer, every
+ * restriction mode the handle accepts, either bottom, a five- or nine-point finest level.  MGX_ERR_STATE (reason in
+ * mgx_last_error) on POISSON, F32, MIXED, multi-GPU and rank handles, every other smoother and before the operators are
+ * set / built; MGX_ERR_INVALID, checked first and in this order, for nrhs < 1 or nrhs > MGX_MAX_RHS, NULL b or u, tol
+ * not >= 0, max_iters < 0, restart < 1 or restart > MGX_GCR_MAX_RESTART; MGX_ERR_ALLOC and the F32 build's error from
+ * the float copy leave the fp64 state and what existed of the workspaces usable. */
+MGX_API int mgx_solve_multi_refine_gcr(mgx_handle h, int nrhs, const void* b, void* u, double tol, int max_iters, int restart,
+                                       mgx_stats* stats, double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -637,6 +678,14 @@ MGX_API int mgx_time_multi_smoother(mgx_handle h, int nrhs, int sweeps, double* 
  * mgx_solve_multi_gcr returns it, and until a mgx_solve_multi_gcr call with at least that nrhs has allocated slot 0;
  * MGX_ERR_INVALID for repeats < 1, nrhs < 1 or nrhs > MGX_MAX_RHS. */
 MGX_API int mgx_time_multi_gcr_direction(mgx_handle h, int nrhs, int repeats, double* ms);
+/* ms per launch of the direction pass of mgx_solve_multi_refine_gcr with scale 1 on its first nrhs columns, from the
+ * finest float u of each column of the float copy into basis slot 0 of the handle's column, `repeats` launches between
+ * two events (tools/multi_refine_gcr_bench.py).  nrhs = 1 runs k_refine_direction on a workspace column - the yardstick,
+ * in the same run; nrhs = 2..4 one launch of k_refine_direction_multi.  The handle's own vectors are untouched (slot 0
+ * has no meaning between two solves).  MGX_ERR_STATE where mgx_solve_multi_refine_gcr returns it, and until a
+ * mgx_solve_multi_refine_gcr call with at least that nrhs has allocated the pieces; MGX_ERR_INVALID for repeats < 1,
+ * nrhs < 1 or nrhs > MGX_MAX_RHS, NULL ms. */
+MGX_API int mgx_time_multi_refine_direction(mgx_handle h, int nrhs, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

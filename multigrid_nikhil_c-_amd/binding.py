@@ -57,7 +57,7 @@ EXPORTS = [
     "mgx_build_galerkin_transfer", "mgx_get_transfer", "mgx_get_prolongation", "mgx_get_lambda_max", "mgx_get_line_factor", "mgx_get_line_chunks",
     "mgx_set_cycle", "mgx_get_cycle", "mgx_solve_refine", "mgx_time_refine_pass",
     "mgx_solve_refine_gcr", "mgx_time_refine_gcr_pass", "mgx_solve_multi", "mgx_time_multi_smoother",
-    "mgx_solve_multi_gcr", "mgx_time_multi_gcr_direction",
+    "mgx_solve_multi_gcr", "mgx_time_multi_gcr_direction", "mgx_solve_multi_refine_gcr", "mgx_time_multi_refine_direction",
 ]
 MAX_RHS = 4
 MAX_GPUS = 16
@@ -184,6 +184,8 @@ def lib() -> C.CDLL:
     L.mgx_time_multi_smoother.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mgx_solve_multi_gcr.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_time_multi_gcr_direction.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.mgx_solve_multi_refine_gcr.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, C.POINTER(Stats), dp, C.c_int]
+    L.mgx_time_multi_refine_direction.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mgx_profile_get.argtypes = [vp, C.POINTER(Profile)]
     L.mgx_time_smoother.argtypes = [vp, C.c_int, dp]
     L.mgx_time_gcr_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
@@ -655,21 +657,19 @@ class Multigrid:
                                              hist.size), "mgx_solve_refine_gcr")
         return st, hist[: st.history_len].copy()
 
-    def solve_multi(self, b, u0=None, tol=1e-8, max_cycles=50):
-        """k <= MAX_RHS right-hand sides b[j] (k x n x n) for the handle's operator in one call, every coefficient grid read
-        once per pass for the columns still iterating (mgx_solve_multi): general-operator Jacobi handles, F64 or F32.  u0:
-        the initial guesses (None: zero).  Returns (list of stats, list of residual histories, u of shape (k, n, n)); column
-        j is bit for bit what set_rhs(b[j]); set_guess(u0[j]); solve(tol, max_cycles) returns as a plain cycle loop."""
+    def _solve_block(self, name, b, u0, tol, iters, *extra):
+        """the block entry point `name` (b, u, tol, iters, *extra, stats, history, cap) on k <= MAX_RHS columns: (list of
+        stats, list of residual histories, u of shape (k, n, n))"""
         dt = self.level_dtype(self.cfg.finest_level)
         n = self.n()
         b = np.ascontiguousarray(b, dtype=dt).reshape(-1, n, n)
         k = b.shape[0]
         u = np.zeros_like(b) if u0 is None else np.array(u0, dtype=dt, order="C").reshape(k, n, n)
         st = (Stats * max(k, 1))()
-        cap = max(max_cycles, 0) + 1
+        cap = max(iters, 0) + 1
         hist = np.zeros((max(k, 1), cap), dtype=np.float64)
-        self._chk(lib().mgx_solve_multi(self._h, k, b.ctypes.data, u.ctypes.data, tol, max_cycles, st,
-                                        hist.ctypes.data_as(C.POINTER(C.c_double)), cap), "mgx_solve_multi")
+        self._chk(getattr(lib(), name)(self._h, k, b.ctypes.data, u.ctypes.data, tol, iters, *extra, st,
+                                       hist.ctypes.data_as(C.POINTER(C.c_double)), cap), name)
         stats = []
         for j in range(k):
             one = Stats()
@@ -677,28 +677,28 @@ class Multigrid:
             stats.append(one)
         return stats, [hist[j, : stats[j].history_len].copy() for j in range(k)], u
 
+    def solve_multi(self, b, u0=None, tol=1e-8, max_cycles=50):
+        """k <= MAX_RHS right-hand sides b[j] (k x n x n) for the handle's operator in one call, every coefficient grid read
+        once per pass for the columns still iterating (mgx_solve_multi): general-operator Jacobi handles, F64 or F32.  u0:
+        the initial guesses (None: zero).  Returns (list of stats, list of residual histories, u of shape (k, n, n)); column
+        j is bit for bit what set_rhs(b[j]); set_guess(u0[j]); solve(tol, max_cycles) returns as a plain cycle loop."""
+        return self._solve_block("mgx_solve_multi", b, u0, tol, max_cycles)
+
     def solve_multi_gcr(self, b, u0=None, tol=1e-8, max_iters=50, restart=4):
         """solve_gcr's iteration on k <= MAX_RHS right-hand sides b[j] (k x n x n) in one call, the cycle and the direction
         pass reading every coefficient grid once for the columns still iterating (mgx_solve_multi_gcr): general-operator
         Jacobi handles, F64 or F32.  u0: the initial guesses (None: zero).  Returns (list of stats, list of residual
         histories, u of shape (k, n, n)) like solve_multi(); column j is bit for bit what set_rhs(b[j]); set_guess(u0[j]);
         solve_gcr(tol, max_iters, restart); get_solution() returns."""
-        dt = self.level_dtype(self.cfg.finest_level)
-        n = self.n()
-        b = np.ascontiguousarray(b, dtype=dt).reshape(-1, n, n)
-        k = b.shape[0]
-        u = np.zeros_like(b) if u0 is None else np.array(u0, dtype=dt, order="C").reshape(k, n, n)
-        st = (Stats * max(k, 1))()
-        cap = max(max_iters, 0) + 1
-        hist = np.zeros((max(k, 1), cap), dtype=np.float64)
-        self._chk(lib().mgx_solve_multi_gcr(self._h, k, b.ctypes.data, u.ctypes.data, tol, max_iters, restart, st,
-                                            hist.ctypes.data_as(C.POINTER(C.c_double)), cap), "mgx_solve_multi_gcr")
-        stats = []
-        for j in range(k):
-            one = Stats()
-            C.memmove(C.byref(one), C.byref(st[j]), C.sizeof(Stats))
-            stats.append(one)
-        return stats, [hist[j, : stats[j].history_len].copy() for j in range(k)], u
+        return self._solve_block("mgx_solve_multi_gcr", b, u0, tol, max_iters, restart)
+
+    def solve_multi_refine_gcr(self, b, u0=None, tol=1e-8, max_iters=50, restart=4):
+        """solve_refine_gcr's iteration on k <= MAX_RHS right-hand sides b[j] (k x n x n) in one call: fp64 GCR around the
+        float block cycle, the cycle and the direction pass reading every coefficient grid once for the columns still
+        iterating (mgx_solve_multi_refine_gcr): general-operator Jacobi F64 handles.  u0: the initial guesses (None: zero).
+        Returns (list of stats, list of residual histories, u of shape (k, n, n)) like solve_multi_gcr(); column j is bit for
+        bit what set_rhs(b[j]); set_guess(u0[j]); solve_refine_gcr(tol, max_iters, restart); get_solution() returns."""
+        return self._solve_block("mgx_solve_multi_refine_gcr", b, u0, tol, max_iters, restart)
 
     # -- measurement -----------------------------------------------------------------
     def profile_reset(self):
@@ -747,6 +747,13 @@ class Multigrid:
         the yardstick); after a solve_multi_gcr with at least nrhs columns"""
         ms = C.c_double()
         self._chk(lib().mgx_time_multi_gcr_direction(self._h, nrhs, repeats, C.byref(ms)), "mgx_time_multi_gcr_direction")
+        return ms.value
+
+    def time_multi_refine_direction(self, nrhs, repeats=20):
+        """ms per launch of solve_multi_refine_gcr's direction pass on the first nrhs workspace columns (nrhs = 1:
+        k_refine_direction, the yardstick); after a solve_multi_refine_gcr with at least nrhs columns"""
+        ms = C.c_double()
+        self._chk(lib().mgx_time_multi_refine_direction(self._h, nrhs, repeats, C.byref(ms)), "mgx_time_multi_refine_direction")
         return ms.value
 
     def graphs_cached(self):

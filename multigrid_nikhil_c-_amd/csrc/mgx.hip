@@ -16,8 +16,11 @@
 //   mgx_solve_multi     (absent in the reference) mgx_solve's cycle loop on up to four right-hand sides per operator
 //                       read, mgx_multi.hpp
 //   mgx_solve_multi_gcr (absent in the reference) mgx_solve_gcr's iteration on those columns, around that cycle
-// The host side of the last six is in mgx_krylov_host.hpp (the Krylov passes, driver and entry-point body of all that
-// iterate), mgx_refine_host.hpp and mgx_multi_host.hpp; only their extern "C" entry points are here.
+//   mgx_solve_multi_refine_gcr  (absent in the reference) mgx_solve_refine_gcr's iteration on those columns, around the
+//                       float block cycle, mgx_refine_multi.hpp
+// The host side of the last seven is in mgx_krylov_host.hpp (the Krylov passes, driver and entry-point body of all that
+// iterate), mgx_refine_host.hpp, mgx_multi_host.hpp and mgx_multi_refine_host.hpp; only their extern "C" entry points
+// are here.
 // There is no CPU fallback anywhere in this file.
 
 #include "../../include/mgx.h"
@@ -35,6 +38,7 @@
 #include "mgx_refine.hpp"
 #include "mgx_refine_gcr.hpp"
 #include "mgx_multi.hpp"
+#include "mgx_refine_multi.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -1359,6 +1363,7 @@ int time_on_stream(mgx_solver* s, double* ms, Enqueue enqueue)
 static int create_solver(const mgx_config* cfg, const mgx_solver* like, mgx_handle* out);
 
 #include "mgx_refine_host.hpp"
+#include "mgx_multi_refine_host.hpp"
 
 // =====================================================================================
 // C-ABI
@@ -2473,6 +2478,36 @@ int mgx_time_multi_gcr_direction(mgx_handle s, int nrhs, int repeats, double* ms
         return s->fail(MGX_ERR_STATE, "mgx_time_multi_gcr_direction: call mgx_solve_multi_gcr with at least this nrhs first (it allocates basis slot 0 "
                                       "of the columns)");
     return s->work_f64 ? multi_gcr_time_direction<double>(s, nrhs, repeats, ms) : multi_gcr_time_direction<float>(s, nrhs, repeats, ms);
+}
+
+// ---- mgx_solve_multi_refine_gcr: fp64 restarted GCR around the float block cycle, up to MGX_MAX_RHS right-hand sides ------
+int mgx_solve_multi_refine_gcr(mgx_handle s, int nrhs, const void* b, void* u, double tol, int max_iters, int restart, mgx_stats* stats,
+                               double* history, int history_cap)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (nrhs < 1 || nrhs > MGX_MAX_RHS) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi_refine_gcr: 1 <= nrhs <= MGX_MAX_RHS required");
+    if (!b || !u) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi_refine_gcr: b and u must not be NULL");
+    if (!(tol >= 0.0) || max_iters < 0) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi_refine_gcr: tol >= 0 and max_iters >= 0 required");
+    if (restart < 1 || restart > MGX_GCR_MAX_RESTART)
+        return s->fail(MGX_ERR_INVALID, "mgx_solve_multi_refine_gcr: 1 <= restart <= MGX_GCR_MAX_RESTART required");
+    if (int rc = multi_refine_guard(s, "mgx_solve_multi_refine_gcr")) return rc;
+    if (int rc = refine_shadow(s)) return rc;
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    return multi_refine_gcr_solve(s, nrhs, b, u, tol, max_iters, restart, stats, history, history_cap);
+}
+
+int mgx_time_multi_refine_direction(mgx_handle s, int nrhs, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!ms || repeats < 1 || nrhs < 1 || nrhs > MGX_MAX_RHS)
+        return s->fail(MGX_ERR_INVALID, "mgx_time_multi_refine_direction: 1 <= nrhs <= MGX_MAX_RHS, repeats >= 1 and ms required");
+    if (int rc = multi_refine_guard(s, "mgx_time_multi_refine_direction")) return rc;
+    bool ready = s->shadow && s->shadow->multi.cols >= nrhs && s->multi.cols >= nrhs && s->multi.gsc;
+    for (int c = 0; ready && c < nrhs; ++c) ready = s->multi.gpart[c] && s->multi.Z[c][0] && s->multi.Q[c][0];
+    if (!ready)
+        return s->fail(MGX_ERR_STATE, "mgx_time_multi_refine_direction: call mgx_solve_multi_refine_gcr with at least this nrhs first (it allocates "
+                                      "the float columns and basis slot 0 of the columns)");
+    return multi_refine_time_direction(s, nrhs, repeats, ms);
 }
 
 // =====================================================================================

@@ -10,6 +10,7 @@
 //   -DMGX_INST_KIND=7  launch_gcr_orth<T>  (mgx_krylov.hpp: k_gcr_dots<T, 1..7>, k_gcr_orth<T, 0..7>, k_gcr_reduce)
 //   -DMGX_INST_KIND=8  launch_gs_colours<T>, launch_gs_rb<T>  (mgx_colour.hpp: k_gs_colour<T, 5 | 9>, k_gs_rb)
 //   -DMGX_INST_KIND=9  launch_gcr_direction_multi<T>  (mgx_multi.hpp: k_gcr_direction_multi<T, 5 | 9, 2..4>)
+//   -DMGX_INST_KIND=10 launch_refine_direction_multi  (mgx_refine_multi.hpp: k_refine_direction_multi<5 | 9, 2..4>; T = double)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
@@ -24,6 +25,8 @@
 #include "mgx_colour.hpp"
 #elif MGX_INST_KIND == 9
 #include "mgx_multi.hpp"
+#elif MGX_INST_KIND == 10
+#include "mgx_refine_multi.hpp"
 #endif
 
 namespace mgx {
@@ -61,7 +64,9 @@ template int launch_gs_colours<T_>(const ColourLevel<T_>&, T_*, const T_*, bool,
 template void launch_gs_rb<T_>(const ColourLevel<T_>&, const T_*, const T_*, T_*, bool, hipStream_t);
 #elif MGX_INST_KIND == 9
 template void launch_gcr_direction_multi<T_>(int, bool, const T_* const*, T_* const*, T_* const*, const Op9<T_>&, int, long, const Launch&, hipStream_t);
+#elif MGX_INST_KIND == 10
+// (not a template: mgx_refine_multi.hpp defines launch_refine_direction_multi in this compilation)
 #else
-#error "MGX_INST_KIND must be 1 .. 9"
+#error "MGX_INST_KIND must be 1 .. 10"
 #endif
 } // namespace mgx

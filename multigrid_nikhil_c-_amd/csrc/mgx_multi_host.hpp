@@ -294,7 +294,8 @@ int multi_guard(mgx_solver* s, const char* fn)
     return var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level);
 }
 
-// ---- the frame of a block solve: what mgx_solve_multi and mgx_solve_multi_gcr do around their loops ------------------
+// ---- the frame of a block solve: what mgx_solve_multi, mgx_solve_multi_gcr and mgx_solve_multi_refine_gcr
+// (mgx_multi_refine_host.hpp) do around their loops -----------------------------------------------------------------------
 template <typename T>
 struct MultiFrame {
     mgx_solver* s;
@@ -333,6 +334,30 @@ struct MultiFrame {
             if (!broke[j] && !(hist[j].back() <= tol * hist[j][0])) next.act[next.m++] = j;
         }
         return next;
+    }
+
+    // what the host reads of GCR iteration k of the set (each column's passes up to the reduction of ||r||^2 are
+    // enqueued): the scalar blocks of all columns in one copy and one host synchronisation, then per column a breakdown
+    // (fn and the column go into first_break, which keeps the first) or the next history entry
+    int gcr_step(const MultiSet& a, int k, const char* fn, const char* quantity, std::string& first_break)
+    {
+        auto& ws = s->multi;
+        HIPCHK(s, hipGetLastError());
+        HIPCHK(s, hipMemcpyAsync(ws.gsc_host, ws.gsc, (size_t)nrhs * kGcrScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(s, hipStreamSynchronize(s->stream));                        // the one host synchronisation per iteration
+        for (int i = 0; i < a.m; ++i) {
+            const int c = a.act[i];
+            const KrylovStep st = krylov_step(ws.gsc_host + (size_t)c * kGcrScalars);
+            if (st.broke) {
+                broke[c] = 1;
+                if (first_break.empty())
+                    first_break = breakdown_message(std::string(fn) + ": column " + std::to_string(c) + ": GCR", k + 1, quantity, st.value);
+                continue;
+            }
+            iters[c] = k + 1;
+            hist[c].push_back(st.value);
+        }
+        return MGX_OK;
     }
 
     // the iterates out of src[column] into the caller's u, the statistics and histories, one `seconds` for all columns
@@ -470,21 +495,7 @@ int multi_gcr_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double to
             gcr_orth<T>(s, v, l, g, j);
             gcr_update<T>(s, v, l, g, j);
         }
-        HIPCHK(s, hipGetLastError());
-        HIPCHK(s, hipMemcpyAsync(ws.gsc_host, ws.gsc, (size_t)nrhs * kGcrScalars * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(s, hipStreamSynchronize(s->stream));                        // the one host synchronisation per iteration
-        for (int i = 0; i < a.m; ++i) {
-            const int c = a.act[i];
-            const KrylovStep st = krylov_step(ws.gsc_host + (size_t)c * kGcrScalars);
-            if (st.broke) {
-                fr.broke[c] = 1;
-                if (first_break.empty())
-                    first_break = breakdown_message("mgx_solve_multi_gcr: column " + std::to_string(c) + ": GCR", k + 1, GcrMethod<T>::quantity, st.value);
-                continue;
-            }
-            fr.iters[c] = k + 1;
-            fr.hist[c].push_back(st.value);
-        }
+        if (int rc = fr.gcr_step(a, k, "mgx_solve_multi_gcr", GcrMethod<T>::quantity, first_break)) return rc;
         a = fr.active(a, tol);
     }
     if (int rc = fr.finish(ws.x, u, tol, stats, history, history_cap)) return rc;

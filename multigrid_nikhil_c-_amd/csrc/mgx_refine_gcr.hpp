@@ -3,6 +3,7 @@
 //
 //   k_refine_direction<NQ>   Z_j = z = scale * (double) z32,  Q_j = A z          reads z32 and the NQ grids of A; writes z, q
 //   k_refine_update          x += alpha z', r -= alpha q', sum r^2 -> partial[],  r32 = (float)(r * inv_scale_next)
+// (k_refine_direction on K = 2 .. 4 columns, for mgx_solve_multi_refine_gcr: mgx_refine_multi.hpp)
 //
 // Both run in the geometry of k_refine_pass: make_launch(N, 2, N - 1, rows_per_chunk) and lane_cols<2>, one wave marching
 // down the R rows of its chunk of a strip, the float grid addressed with its own pitch (epitch >= pitch).

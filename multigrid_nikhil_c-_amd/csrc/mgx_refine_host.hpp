@@ -84,26 +84,48 @@ static void refine_pass(mgx_solver* s, bool has_e, double scale, double inv_scal
 }
 
 // ---- mgx_solve_refine_gcr: fp64 restarted GCR (mgx_krylov.hpp) around the float cycle of the shadow ---------------
-// Z_j = z = scale * (double) z32 out of the shadow's U, Q_j = A z on the handle's finest operator
-static void refine_gcr_direction(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double scale)
+// Z_j = z = scale * (double) z32, Q_j = A z on the handle's finest operator; z32 has the shadow's pitch epitch
+static void refine_gcr_direction(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double scale, const float* z32, long epitch)
 {
     const Level& d = s->lv[s->cfg.finest_level];
-    const Level& w = s->shadow->lv[s->cfg.finest_level];
     with_point_count(d.nine, [&](auto nq) {
-        hipLaunchKernelGGL((k_refine_direction<decltype(nq)::value>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const float*)w.u,
-                           op9_of<double>(d), (double*)v.Z[j], (double*)v.Q[j], scale, d.N, d.pitch, w.pitch, g.R, g.strips, g.chunks);
+        hipLaunchKernelGGL((k_refine_direction<decltype(nq)::value>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z32, op9_of<double>(d),
+                           (double*)v.Z[j], (double*)v.Q[j], scale, d.N, d.pitch, epitch, g.R, g.strips, g.chunks);
     });
 }
 
-// x += alpha Z_j, r -= alpha Q_j, the partials of ||r||^2 and r32 = (float)(r * inv_scale_next) into the shadow's
-// right-hand side
-static void refine_gcr_update(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double inv_scale_next)
+// x += alpha Z_j, r -= alpha Q_j, the partials of ||r||^2 and r32 = (float)(r * inv_scale_next), the right-hand side of
+// the next float cycle
+static void refine_gcr_update(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double inv_scale_next, float* r32, long epitch)
 {
     const Level& d = s->lv[s->cfg.finest_level];
-    const Level& w = s->shadow->lv[s->cfg.finest_level];
     hipLaunchKernelGGL(k_refine_update, dim3(g.blocks), dim3(kBlock), 0, s->stream, (double*)v.x, (const double*)v.Z[j], (double*)v.r,
-                       (const double*)v.Q[j], (float*)w.b, inv_scale_next, (const double*)v.sc, v.part, d.N, d.pitch, w.pitch, g.R, g.strips,
-                       g.chunks);
+                       (const double*)v.Q[j], r32, inv_scale_next, (const double*)v.sc, v.part, d.N, d.pitch, epitch, g.R, g.strips, g.chunks);
+}
+
+// the two on the handle's own workspace: z32 is the shadow's U, r32 the shadow's right-hand side
+static void refine_gcr_direction(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double scale)
+{
+    const Level& w = s->shadow->lv[s->cfg.finest_level];
+    refine_gcr_direction(s, v, g, j, scale, (const float*)w.u, w.pitch);
+}
+static void refine_gcr_update(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double inv_scale_next)
+{
+    const Level& w = s->shadow->lv[s->cfg.finest_level];
+    refine_gcr_update(s, v, g, j, inv_scale_next, (float*)w.b, w.pitch);
+}
+
+// no scaled residual is pending before the first float cycle of a solve: r32 = (float)((b - A x) * inv_scale), the bits
+// of r = b - A x, by k_refine_pass without a correction (e is not read; its sums of squares go into `partial`, unread)
+static void refine_gcr_first_residual(mgx_solver* s, const void* x, const void* b, const float* e, float* r32, double inv_scale, double* partial,
+                                      long partial_cap)
+{
+    const Level& l = s->lv[s->cfg.finest_level];
+    const Level& fl = s->shadow->lv[s->cfg.finest_level];
+    with_point_count(l.nine, [&](auto nq) {
+        launch_refine_pass<decltype(nq)::value, false>((const double*)x, e, (const double*)b, op9_of<double>(l), (double*)l.tmp, r32, 0.0, inv_scale,
+                                                       partial, partial_cap, l.N, l.pitch, fl.pitch, s->rows_per_chunk, s->stream);
+    });
 }
 
 // The shadow is the solver whose cycle preconditions mgx_solve_refine_gcr
@@ -131,14 +153,10 @@ struct RefineGcrMethod {
     {
         mgx_solver* f = s->shadow;
         if (k == 0) {
-            // no scaled residual is pending yet: r32 = (float)((b - A x) / s_0), the bits of r in lv[L].b
+            // r32 = (float)((b - A x) / s_0), the bits of r in lv[L].b
             const Level& fl = f->lv[s->cfg.finest_level];
             Prof p(s, MGX_PROF_NORM_FINE, 1);
-            with_point_count(l.nine, [&](auto nq) {
-                launch_refine_pass<decltype(nq)::value, false>((const double*)s->kry.x, (const float*)fl.u, (const double*)s->kry.b,
-                                                               op9_of<double>(l), (double*)l.tmp, (float*)fl.b, 0.0, 1.0 / scale(l, hist, 0),
-                                                               s->partial, s->partial_cap, l.N, l.pitch, fl.pitch, s->rows_per_chunk, s->stream);
-            });
+            refine_gcr_first_residual(s, s->kry.x, s->kry.b, (const float*)fl.u, (float*)fl.b, 1.0 / scale(l, hist, 0), s->partial, s->partial_cap);
         }
         if (int rc = krylov_cycle(f)) return s->fail(rc, "mgx_solve_refine_gcr: float cycle: " + f->err);   // z32 = M32 r32 from zero
         return MGX_OK;
