@@ -620,6 +620,42 @@ MGX_API int mgx_solve_multi_gcr(mgx_handle h, int nrhs, const void* b, void* u, 
 MGX_API int mgx_solve_multi_refine_gcr(mgx_handle h, int nrhs, const void* b, void* u, double tol, int max_iters, int restart,
                                        mgx_stats* stats, double* history, int history_cap);
 
+/* The nev <= MGX_MAX_RHS smallest eigenpairs A x_j = lambda_j x_j of the finest-level operator A of a general-operator
+ * handle, by LOBPCG (locally optimal block preconditioned conjugate gradients) whose preconditioner is
+ * mgx_solve_multi's cycle from zero, every coefficient grid read once per pass for the block (csrc/mgx_eig.hpp states
+ * the iteration operation by operation).  A must be symmetric positive definite: mgx_set_coefficient, mgx_set_tensor, or
+ * symmetric mgx_set_stencil / mgx_set_stencil9 input; symmetry is the caller's duty and is not checked.  A is the
+ * stencil AS STORED: it carries no h^-2 (multiply lambda by N^2 for the differential operator on the unit square).
+ * x: nev host vectors back to back, each n*n, in the handle's working type (mgx_solve_multi's layout); on entry the
+ * guesses, on return the Ritz vectors with unit 2-norm ordered by ascending lambda[j], sign unspecified.  stats: NULL
+ * or nev entries; history: NULL or nev slots of history_cap doubles.  hist_j[k] = ||A x_j - theta_j x_j||_2 after
+ * iteration k, entry 0 after the initial Rayleigh-Ritz step on the guesses; A x is applied afresh in every iteration, so
+ * these are the residuals of the pair returned, not of a recurrence.  stats[j]: cycles = preconditioner cycles applied
+ * to column j, initial_residual / final_residual = first and last history entry, converged = the last entry <= tol *
+ * theta_j, fine_updates as mgx_solve_multi counts them, seconds = the whole call, the same in every entry.  max_iters =
+ * 0 does the initial Rayleigh-Ritz step and writes one history entry.
+ * Soft locking: a column whose residual meets tol * theta_j gets no cycle and no search direction, but it stays in the
+ * block, is still rewritten by every Ritz rotation and iterates again if its residual rises above the tolerance - not
+ * the "frozen for good" rule of the block solvers.
+ * A Rayleigh-Ritz step whose basis [X, W, P] is numerically rank deficient (a Cholesky pivot of the scaled Gram matrix
+ * not positive and finite, or below 64 eps) is repeated once without the directions P; if it still is, the call ends:
+ * the columns still iterating report converged = 0, mgx_last_error holds the reason, the return value is MGX_OK (as for a
+ * GCR breakdown).  A Ritz value that is not a positive finite number ends the call the same way with converged = 0 in
+ * every column.  Linearly dependent guesses: MGX_ERR_INVALID.
+ * Deterministic (every sum in a fixed order, no atomics); two device-to-host copies and host synchronisations per
+ * iteration (the residual norms, the Gram sums); launched eagerly (cfg.profile does not extend to the call).
+ * The handle's own U, B, R of every level, its Krylov workspaces, its cached graphs and its fine_updates are left as
+ * they were; every other entry point computes, before and after, the bits of a handle that never made the call.
+ * Memory: mgx_solve_multi's columns (shared with that call) and five finest-level vectors per column (X, AX, AW, P,
+ * AP; W is the column's finest u, the residual its finest b), allocated on first use, grown for a larger nev, freed by
+ * mgx_destroy.
+ * Accepted and refused handles: exactly mgx_solve_multi's (MGX_ERR_STATE with the reason on POISSON, MIXED, multi-GPU
+ * and rank handles, every smoother but JACOBI, before the operators are set / built).  MGX_ERR_INVALID, checked first
+ * and in this order: nev < 1 or nev > MGX_MAX_RHS, NULL x or lambda, tol not >= 0, max_iters < 0.  MGX_ERR_ALLOC leaves
+ * the handle and what existed of the workspaces usable. */
+MGX_API int mgx_eigs(mgx_handle h, int nev, void* x, double* lambda, double tol, int max_iters, mgx_stats* stats,
+                     double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -686,6 +722,16 @@ MGX_API int mgx_time_multi_gcr_direction(mgx_handle h, int nrhs, int repeats, do
  * mgx_solve_multi_refine_gcr call with at least that nrhs has allocated the pieces; MGX_ERR_INVALID for repeats < 1,
  * nrhs < 1 or nrhs > MGX_MAX_RHS, NULL ms. */
 MGX_API int mgx_time_multi_refine_direction(mgx_handle h, int nrhs, int repeats, double* ms);
+/* ms per launch of one of mgx_eigs' four passes on its first nev workspace columns, `repeats` launches between two
+ * events (tools/eig_bench.py; the yardstick is mgx_time_gcr_pass, UPDATE, in the same run).  Per point and launch:
+ * GRAM k_eig_gram<T, nev, nev> of X against [P, AP] with the reduction of its sums, 3 nev words read; COMBINE
+ * k_eig_combine<T, 3 nev, nev>, X <- [X, W, P] with the identity on X (X keeps its bits), 3 nev read and nev written;
+ * RESIDUAL k_eig_residual<T, nev> with theta = 1 and its reductions, 2 nev read and nev written; APPLY
+ * k_apply_var_multi<T, NQ, nev>, AX <- A X, NQ + 2 nev.  The handle's own vectors are untouched (the workspace has no
+ * meaning between two calls).  MGX_ERR_STATE where mgx_eigs returns it, and until a mgx_eigs call with at least that
+ * nev has allocated the columns; MGX_ERR_INVALID for another pass, repeats < 1, nev < 1 or nev > MGX_MAX_RHS, NULL ms. */
+enum { MGX_EIG_PASS_GRAM = 0, MGX_EIG_PASS_COMBINE = 1, MGX_EIG_PASS_RESIDUAL = 2, MGX_EIG_PASS_APPLY = 3 };
+MGX_API int mgx_time_eig_pass(mgx_handle h, int pass, int nev, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

@@ -58,7 +58,9 @@ EXPORTS = [
     "mgx_set_cycle", "mgx_get_cycle", "mgx_solve_refine", "mgx_time_refine_pass",
     "mgx_solve_refine_gcr", "mgx_time_refine_gcr_pass", "mgx_solve_multi", "mgx_time_multi_smoother",
     "mgx_solve_multi_gcr", "mgx_time_multi_gcr_direction", "mgx_solve_multi_refine_gcr", "mgx_time_multi_refine_direction",
+    "mgx_eigs", "mgx_time_eig_pass",
 ]
+EIG_PASS_GRAM, EIG_PASS_COMBINE, EIG_PASS_RESIDUAL, EIG_PASS_APPLY = 0, 1, 2, 3
 MAX_RHS = 4
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
@@ -186,6 +188,8 @@ def lib() -> C.CDLL:
     L.mgx_time_multi_gcr_direction.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mgx_solve_multi_refine_gcr.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_time_multi_refine_direction.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.mgx_eigs.argtypes = [vp, C.c_int, vp, dp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
+    L.mgx_time_eig_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     L.mgx_profile_get.argtypes = [vp, C.POINTER(Profile)]
     L.mgx_time_smoother.argtypes = [vp, C.c_int, dp]
     L.mgx_time_gcr_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
@@ -701,6 +705,39 @@ class Multigrid:
         return self._solve_block("mgx_solve_multi_refine_gcr", b, u0, tol, max_iters, restart)
 
     # -- measurement -----------------------------------------------------------------
+    def eigs(self, nev, x0=None, tol=1e-8, max_iters=100, seed=0):
+        """the nev <= MAX_RHS smallest eigenpairs of the finest-level operator (as stored: no h^-2) by LOBPCG around the block
+        cycle (mgx_eigs): general-operator Jacobi handles, F64 or F32, a symmetric positive definite operator.  x0: the
+        guesses (nev x n x n); None: uniform(-1, 1) vectors of numpy's default_rng(seed).  Returns (theta, X, stats,
+        history): theta ascending, X of shape (nev, n, n) with unit 2-norm, a list of stats (cycles = preconditioner cycles
+        of the column) and a list of histories of ||A x_j - theta_j x_j||."""
+        dt = self.level_dtype(self.cfg.finest_level)
+        n = self.n()
+        if x0 is None:
+            x = np.random.default_rng(seed).uniform(-1.0, 1.0, (max(nev, 1), n, n)).astype(dt)
+        else:
+            x = np.array(x0, dtype=dt, order="C").reshape(-1, n, n)
+            assert x.shape[0] == nev, "x0 must hold nev vectors"
+        theta = np.zeros(max(nev, 1), dtype=np.float64)
+        st = (Stats * max(nev, 1))()
+        cap = max(max_iters, 0) + 1
+        hist = np.zeros((max(nev, 1), cap), dtype=np.float64)
+        self._chk(lib().mgx_eigs(self._h, nev, x.ctypes.data, theta.ctypes.data_as(C.POINTER(C.c_double)), tol, max_iters, st,
+                                 hist.ctypes.data_as(C.POINTER(C.c_double)), cap), "mgx_eigs")
+        stats = []
+        for j in range(nev):
+            one = Stats()
+            C.memmove(C.byref(one), C.byref(st[j]), C.sizeof(Stats))
+            stats.append(one)
+        return theta[:nev], x, stats, [hist[j, : stats[j].history_len].copy() for j in range(nev)]
+
+    def time_eig_pass(self, which, nev, repeats=20):
+        """ms per launch of pass `which` (EIG_PASS_GRAM / COMBINE / RESIDUAL / APPLY) of eigs() on its first nev workspace
+        columns; after an eigs() with at least nev columns"""
+        ms = C.c_double(0.0)
+        self._chk(lib().mgx_time_eig_pass(self._h, which, nev, repeats, C.byref(ms)), "mgx_time_eig_pass")
+        return ms.value
+
     def profile_reset(self):
         self._chk(lib().mgx_profile_reset(self._h), "mgx_profile_reset")
 

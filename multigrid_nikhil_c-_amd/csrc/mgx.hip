@@ -39,6 +39,7 @@
 #include "mgx_refine_gcr.hpp"
 #include "mgx_multi.hpp"
 #include "mgx_refine_multi.hpp"
+#include "mgx_eig.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -193,6 +194,15 @@ struct mgx_solver {
         double* gpart[MGX_MAX_RHS] = {};
         double *gsc = nullptr, *gsc_host = nullptr;
     } multi;
+    // mgx_eigs (mgx_eig_host.hpp), per column beyond mgx_solve_multi's: X, AX, AW, P, AP of the finest level (W is the
+    // column's finest u, R its finest b); the per-block sums of one Gram pair and the sums of the six pairs of an
+    // iteration with their pinned copy.  Columns [0, cols) exist; allocated by the first call, grown by a larger nev,
+    // freed by mgx_destroy
+    struct EigWs {
+        void *X[MGX_MAX_RHS] = {}, *AX[MGX_MAX_RHS] = {}, *AW[MGX_MAX_RHS] = {}, *P[MGX_MAX_RHS] = {}, *AP[MGX_MAX_RHS] = {};
+        double *gpart = nullptr, *gsum = nullptr, *gsum_host = nullptr;
+        int cols = 0;
+    } eig;
 
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -1364,6 +1374,7 @@ static int create_solver(const mgx_config* cfg, const mgx_solver* like, mgx_hand
 
 #include "mgx_refine_host.hpp"
 #include "mgx_multi_refine_host.hpp"
+#include "mgx_eig_host.hpp"
 
 // =====================================================================================
 // C-ABI
@@ -1600,6 +1611,7 @@ int mgx_destroy(mgx_handle s)
     for (double* p : {s->var_M, s->var_inv, s->var_pm, s->var_pi}) if (p) (void)hipFree(p);
     s->kry.free();
     multi_free(s->multi);
+    eig_free(s->eig);
     drop_graphs(s);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2478,6 +2490,30 @@ int mgx_time_multi_gcr_direction(mgx_handle s, int nrhs, int repeats, double* ms
         return s->fail(MGX_ERR_STATE, "mgx_time_multi_gcr_direction: call mgx_solve_multi_gcr with at least this nrhs first (it allocates basis slot 0 "
                                       "of the columns)");
     return s->work_f64 ? multi_gcr_time_direction<double>(s, nrhs, repeats, ms) : multi_gcr_time_direction<float>(s, nrhs, repeats, ms);
+}
+
+// ---- mgx_eigs: the smallest eigenpairs of the finest operator by LOBPCG around the block cycle (mgx_eig.hpp) -------------
+int mgx_eigs(mgx_handle s, int nev, void* x, double* lambda, double tol, int max_iters, mgx_stats* stats, double* history, int history_cap)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (nev < 1 || nev > MGX_MAX_RHS) return s->fail(MGX_ERR_INVALID, "mgx_eigs: 1 <= nev <= MGX_MAX_RHS required");
+    if (!x || !lambda) return s->fail(MGX_ERR_INVALID, "mgx_eigs: x and lambda must not be NULL");
+    if (!(tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_eigs: tol >= 0 required");
+    if (max_iters < 0) return s->fail(MGX_ERR_INVALID, "mgx_eigs: max_iters >= 0 required");
+    if (int rc = multi_guard(s, "mgx_eigs")) return rc;
+    return s->work_f64 ? eigs_t<double>(s, nev, x, lambda, tol, max_iters, stats, history, history_cap)
+                       : eigs_t<float>(s, nev, x, lambda, tol, max_iters, stats, history, history_cap);
+}
+
+int mgx_time_eig_pass(mgx_handle s, int pass, int nev, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (pass < MGX_EIG_PASS_GRAM || pass > MGX_EIG_PASS_APPLY || nev < 1 || nev > MGX_MAX_RHS || repeats < 1 || !ms)
+        return s->fail(MGX_ERR_INVALID, "mgx_time_eig_pass: a pass of MGX_EIG_PASS_*, 1 <= nev <= MGX_MAX_RHS, repeats >= 1 and ms required");
+    if (int rc = multi_guard(s, "mgx_time_eig_pass")) return rc;
+    if (s->multi.cols < nev || s->eig.cols < nev)
+        return s->fail(MGX_ERR_STATE, "mgx_time_eig_pass: call mgx_eigs with at least this nev first (it allocates the columns)");
+    return s->work_f64 ? eig_time_pass<double>(s, pass, nev, repeats, ms) : eig_time_pass<float>(s, pass, nev, repeats, ms);
 }
 
 // ---- mgx_solve_multi_refine_gcr: fp64 restarted GCR around the float block cycle, up to MGX_MAX_RHS right-hand sides ------
