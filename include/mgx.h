@@ -582,7 +582,7 @@ MGX_API int mgx_solve_multi_gcr(mgx_handle h, int nrhs, const void* b, void* u, 
 /* mgx_solve_refine_gcr's iteration on up to MGX_MAX_RHS right-hand sides for one operator: fp64 restarted GCR on the
  * finest level, the preconditioner mgx_solve_multi's float cycle from zero on the columns of the float copy of the
  * hierarchy still iterating (a sweep moves 4 (NQ + 3 nrhs) bytes per point where nrhs fp64 solves move 8 nrhs (NQ + 3)),
- * the direction pass Z_j = z = s (double) z32, Q_j = A z one launch of k_refine_direction_multi for the set (8 NQ + 20 nrhs
+ * the direction pass Z_j = z = s (double) z32, Q_j = A z one launch of k_refine_direction<NQ, nrhs> for the set (8 NQ + 20 nrhs
  * bytes per point instead of nrhs (8 NQ + 20); every instance, the nine-point one on four columns included, runs without
  * scratch: four nine-point columns are one launch).  The orthogonalisation, the mixed update and the reductions read no
  * coefficients and run once per column, in mgx_solve_refine_gcr's geometry, on that column's own scalars and partial sums;
@@ -693,7 +693,7 @@ MGX_API int mgx_time_gcr_pass(mgx_handle h, int pass, int j, int repeats, double
  * call has created the float copy; MGX_ERR_INVALID for repeats < 1. */
 MGX_API int mgx_time_refine_pass(mgx_handle h, int repeats, double* ms);
 /* ms per launch of one of mgx_solve_refine_gcr's two mixed passes on the handle's own buffers, `repeats` launches between
- * two events (tools/refine_gcr_bench.py): UPDATE is k_refine_update, DIRECTION k_refine_direction<5 | 9> with scale 1.  The
+ * two events (tools/refine_gcr_bench.py): UPDATE is k_refine_update, DIRECTION k_refine_direction<5 | 9, 1> with scale 1.  The
  * scalars are zeroed first, so U, B and the saved iterate are unchanged bit for bit; the float residual of the shadow
  * (UPDATE) and basis slot 0 (DIRECTION) are rewritten - neither has a meaning between two solves.  MGX_ERR_STATE where
  * mgx_solve_refine_gcr is, and until the float copy and basis slot 0 exist: a mgx_solve_refine_gcr call creates both, and
@@ -702,8 +702,8 @@ MGX_API int mgx_time_refine_pass(mgx_handle h, int repeats, double* ms);
 enum { MGX_REFINE_GCR_PASS_UPDATE = 0, MGX_REFINE_GCR_PASS_DIRECTION = 1 };
 MGX_API int mgx_time_refine_gcr_pass(mgx_handle h, int pass, int repeats, double* ms);
 /* `sweeps` finest-level Jacobi sweeps on the first nrhs workspace columns of mgx_solve_multi between two events; returns
- * the elapsed milliseconds (tools/multi_bench.py).  nrhs = 1 runs k_jacobi_var on a workspace column - the yardstick, in
- * the same run; nrhs = 2..4 one launch of k_jacobi_var_multi per sweep.  The handle's own vectors are untouched.
+ * the elapsed milliseconds (tools/multi_bench.py).  nrhs = 1 runs k_jacobi_var<T, NQ, 1> on a workspace column - the yardstick,
+ * in the same run; nrhs = 2..4 one launch of k_jacobi_var<T, NQ, nrhs> per sweep.  The handle's own vectors are untouched.
  * MGX_ERR_STATE where mgx_solve_multi returns it, and until a mgx_solve_multi call with at least that nrhs has
  * allocated the columns; MGX_ERR_INVALID for sweeps < 1, nrhs < 1 or nrhs > MGX_MAX_RHS. */
 MGX_API int mgx_time_multi_smoother(mgx_handle h, int nrhs, int sweeps, double* ms);
@@ -716,8 +716,8 @@ MGX_API int mgx_time_multi_smoother(mgx_handle h, int nrhs, int sweeps, double* 
 MGX_API int mgx_time_multi_gcr_direction(mgx_handle h, int nrhs, int repeats, double* ms);
 /* ms per launch of the direction pass of mgx_solve_multi_refine_gcr with scale 1 on its first nrhs columns, from the
  * finest float u of each column of the float copy into basis slot 0 of the handle's column, `repeats` launches between
- * two events (tools/multi_refine_gcr_bench.py).  nrhs = 1 runs k_refine_direction on a workspace column - the yardstick,
- * in the same run; nrhs = 2..4 one launch of k_refine_direction_multi.  The handle's own vectors are untouched (slot 0
+ * two events (tools/multi_refine_gcr_bench.py).  nrhs = 1 runs k_refine_direction<NQ, 1> on a workspace column - the
+ * yardstick, in the same run; nrhs = 2..4 one launch of k_refine_direction<NQ, nrhs>.  The handle's own vectors are untouched (slot 0
  * has no meaning between two solves).  MGX_ERR_STATE where mgx_solve_multi_refine_gcr returns it, and until a
  * mgx_solve_multi_refine_gcr call with at least that nrhs has allocated the pieces; MGX_ERR_INVALID for repeats < 1,
  * nrhs < 1 or nrhs > MGX_MAX_RHS, NULL ms. */

@@ -773,8 +773,8 @@ class Multigrid:
         return ms.value
 
     def time_multi_smoother(self, nrhs, sweeps):
-        """ms of `sweeps` finest-level Jacobi sweeps on the first nrhs workspace columns of solve_multi (nrhs = 1:
-        k_jacobi_var, the yardstick); after a solve_multi with at least nrhs columns"""
+        """ms of `sweeps` finest-level Jacobi sweeps on the first nrhs workspace columns of solve_multi (k_jacobi_var<T, NQ, nrhs>;
+        nrhs = 1 is the yardstick); after a solve_multi with at least nrhs columns"""
         ms = C.c_double()
         self._chk(lib().mgx_time_multi_smoother(self._h, nrhs, sweeps, C.byref(ms)), "mgx_time_multi_smoother")
         return ms.value
@@ -787,8 +787,8 @@ class Multigrid:
         return ms.value
 
     def time_multi_refine_direction(self, nrhs, repeats=20):
-        """ms per launch of solve_multi_refine_gcr's direction pass on the first nrhs workspace columns (nrhs = 1:
-        k_refine_direction, the yardstick); after a solve_multi_refine_gcr with at least nrhs columns"""
+        """ms per launch of solve_multi_refine_gcr's direction pass on the first nrhs workspace columns (k_refine_direction<NQ,
+        nrhs>; nrhs = 1 is the yardstick); after a solve_multi_refine_gcr with at least nrhs columns"""
         ms = C.c_double()
         self._chk(lib().mgx_time_multi_refine_direction(self._h, nrhs, repeats, C.byref(ms)), "mgx_time_multi_refine_direction")
         return ms.value

@@ -17,7 +17,7 @@
 //                       read, mgx_multi.hpp
 //   mgx_solve_multi_gcr (absent in the reference) mgx_solve_gcr's iteration on those columns, around that cycle
 //   mgx_solve_multi_refine_gcr  (absent in the reference) mgx_solve_refine_gcr's iteration on those columns, around the
-//                       float block cycle, mgx_refine_multi.hpp
+//                       float block cycle
 // The host side of the last seven is in mgx_krylov_host.hpp (the Krylov passes, driver and entry-point body of all that
 // iterate), mgx_refine_host.hpp, mgx_multi_host.hpp and mgx_multi_refine_host.hpp; only their extern "C" entry points
 // are here.
@@ -38,7 +38,6 @@
 #include "mgx_refine.hpp"
 #include "mgx_refine_gcr.hpp"
 #include "mgx_multi.hpp"
-#include "mgx_refine_multi.hpp"
 #include "mgx_eig.hpp"
 #include "mgx_dist_plan.hpp"
 
@@ -634,13 +633,12 @@ void smooth_var_t(mgx_solver* s, Level& l, int mu)
 {
     const T om = (T)s->cfg.omega;
     const T rc = (T)(1.0 - (double)om);
-    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
     const VarLevel<T> v = var_level<T>(l);
+    const T* const b = (const T*)l.b;
     for (int i = 0; i < mu; ++i) {
-        with_point_count(v.nine, [&](auto nq) {
-            hipLaunchKernelGGL((k_jacobi_var<T, decltype(nq)::value>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)l.u, (const T*)l.b,
-                               (T*)l.tmp, v.dinv, v.r, v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
-        });
+        const T* const u = (const T*)l.u;
+        T* const out = (T*)l.tmp;
+        launch_jacobi_var<T>(v, 1, &u, &b, &out, rc, om, s->stream);
         std::swap(l.u, l.tmp);
     }
     s->last_smooth_launches = mu;
@@ -710,13 +708,10 @@ void smooth_var(mgx_solver* s, Level& l, int mu, bool post = false)
 template <typename T, int MODE>
 void residual_var_t(mgx_solver* s, const Level& l, const void* u, const void* b, void* out)
 {
-    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
-    const VarLevel<T> v = var_level<T>(l);
-    with_point_count(v.nine, [&](auto nq) {
-        hipLaunchKernelGGL((k_residual_var<T, decltype(nq)::value, MODE>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (const T*)u, (const T*)b,
-                           (T*)out, s->partial, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
-    });
-    if (MODE == 1) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, s->partial, g.blocks, s->sum_dev);
+    const T* const uu = (const T*)u;
+    const T* const bb = (const T*)b;
+    T* const oo = (T*)out;
+    launch_residual_var<T, MODE>(var_level<T>(l), 1, &uu, &bb, &oo, &s->partial, &s->sum_dev, s->stream);
 }
 
 // the same of whichever operator the handle has, on a grid pair of level l: the general operator's kernel or the
@@ -948,11 +943,9 @@ void prolong_level(mgx_solver* s, int level, bool add)
             launch_prolong<T>((T*)f.u, (const T*)c.u, f.N, f.pitch, c.pitch, 1, f.N, 0, add, s->rows_per_chunk, s->stream);
             return;
         }
-        const Launch g = make_launch(c.N, VecOf<T>::W, c.N, 1);
-        if (add) hipLaunchKernelGGL((k_prolong_opdep<T, true>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)f.u, (const T*)c.u, wt8_of<T>(c),
-                                    c.N, f.pitch, c.pitch, g.strips);
-        else hipLaunchKernelGGL((k_prolong_opdep<T, false>), dim3(g.blocks), dim3(kBlock), 0, s->stream, (T*)f.u, (const T*)c.u, wt8_of<T>(c),
-                                c.N, f.pitch, c.pitch, g.strips);
+        T* const v = (T*)f.u;
+        const T* const e = (const T*)c.u;
+        launch_prolong_opdep<T>(1, add, &v, &e, wt8_of<T>(c), c.N, f.pitch, c.pitch, s->stream);
     });
 }
 
@@ -963,9 +956,10 @@ void bottom_solve(mgx_solver* s)
     const int n = l.N - 1;
     with_float_type(l.f64, [&](auto tag) {
         using T = decltype(tag);
-        if (s->var)                                                      // MF:63-72: x = A^-1 b, A^-1 built at set-up
-            hipLaunchKernelGGL((k_var_dense_solve<T>), dim3((n * n + 63) / 64), dim3(64), 0, s->stream, s->var_inv, (const T*)l.b, (T*)l.u, n, l.pitch);
-        else s->bottom.solve<T>((const T*)l.b, (T*)l.u, l.pitch, s->stream);
+        const T* const b = (const T*)l.b;
+        T* const u = (T*)l.u;
+        if (s->var) launch_var_dense_solve<T>(s->var_inv, 1, &b, &u, n, l.pitch, s->stream);     // MF:63-72: x = A^-1 b, A^-1 built at set-up
+        else s->bottom.solve<T>(b, u, l.pitch, s->stream);
     });
 }
 
@@ -2436,7 +2430,7 @@ int mgx_time_smoother(mgx_handle s, int sweeps, double* ms)
 int mgx_solve_multi(mgx_handle s, int nrhs, const void* b, void* u, double tol, int max_cycles, mgx_stats* stats, double* history,
                     int history_cap)
 {
-    static_assert(kMultiMax == MGX_MAX_RHS, "mgx_multi.hpp and mgx.h disagree");
+    static_assert(kMultiMax == MGX_MAX_RHS, "mgx_var.hpp and mgx.h disagree");
     if (!s) return MGX_ERR_INVALID;
     if (nrhs < 1 || nrhs > MGX_MAX_RHS) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi: 1 <= nrhs <= MGX_MAX_RHS required");
     if (!b || !u) return s->fail(MGX_ERR_INVALID, "mgx_solve_multi: b and u must not be NULL");

@@ -42,9 +42,9 @@
 //   k_eig_residual<T, K>          R_j = AX_j - theta_j X_j (theta rounded to T) into the finest right-hand side of the
 //                                 column, with the per-block sums of R_j^2 (k_reduce_partials ends them): 2 K in, K out.
 //   k_apply_var_multi<T, NQ, K>   out_j = A v_j, the operator read once for the set: NQ + 2 K words per point, built
-//                                 from load_rows / load_coefs / stencil_sum as k_residual_var_multi is (K = 1 included:
-//                                 there is no single-column pass that forms A v alone).  AX and AP (K = nev), AW (K = |act|).
-// The cycle itself runs multi_vcycle: one active column runs the single-column kernels.
+//                                 from load_rows / load_coefs / stencil_sum as k_residual_var is.  AX and AP (K = nev),
+//                                 AW (K = |act|).
+// The cycle itself runs multi_vcycle.
 #pragma once
 
 #include "mgx_multi.hpp"
@@ -52,15 +52,6 @@
 namespace mgx {
 
 constexpr int kEigMaxIn = 3 * kMultiMax;
-
-// f(tag) with decltype(tag)::value == k, 1 <= k <= MAX
-template <int MAX, typename F> void with_count(int k, F&& f)
-{
-    if constexpr (MAX > 1) {
-        if (k < MAX) { with_count<MAX - 1>(k, f); return; }
-    }
-    f(std::integral_constant<int, MAX>{});
-}
 
 // the per-lane products of one row, in double, left to right
 template <typename T> __device__ __forceinline__ double lane_dot(const Lanes<T>& a, const Lanes<T>& b)

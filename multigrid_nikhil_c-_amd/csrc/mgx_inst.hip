@@ -10,7 +10,7 @@
 //   -DMGX_INST_KIND=7  launch_gcr_orth<T>  (mgx_krylov.hpp: k_gcr_dots<T, 1..7>, k_gcr_orth<T, 0..7>, k_gcr_reduce)
 //   -DMGX_INST_KIND=8  launch_gs_colours<T>, launch_gs_rb<T>  (mgx_colour.hpp: k_gs_colour<T, 5 | 9>, k_gs_rb)
 //   -DMGX_INST_KIND=9  launch_gcr_direction_multi<T>  (mgx_multi.hpp: k_gcr_direction_multi<T, 5 | 9, 2..4>)
-//   -DMGX_INST_KIND=10 launch_refine_direction_multi  (mgx_refine_multi.hpp: k_refine_direction_multi<5 | 9, 2..4>; T = double)
+//   -DMGX_INST_KIND=10 launch_refine_direction  (mgx_refine_gcr.hpp: k_refine_direction<5 | 9, 1..4>; T = double)
 //   -DMGX_INST_KIND=11 launch_eig_gram<T>, launch_eig_combine<T>, launch_eig_residual<T>, launch_eig_apply<T>  (mgx_eig.hpp)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
@@ -27,7 +27,7 @@
 #elif MGX_INST_KIND == 9
 #include "mgx_multi.hpp"
 #elif MGX_INST_KIND == 10
-#include "mgx_refine_multi.hpp"
+#include "mgx_refine_gcr.hpp"
 #elif MGX_INST_KIND == 11
 #include "mgx_eig.hpp"
 #endif
@@ -68,7 +68,7 @@ template void launch_gs_rb<T_>(const ColourLevel<T_>&, const T_*, const T_*, T_*
 #elif MGX_INST_KIND == 9
 template void launch_gcr_direction_multi<T_>(int, bool, const T_* const*, T_* const*, T_* const*, const Op9<T_>&, int, long, const Launch&, hipStream_t);
 #elif MGX_INST_KIND == 10
-// (not a template: mgx_refine_multi.hpp defines launch_refine_direction_multi in this compilation)
+// (not a template: mgx_refine_gcr.hpp defines launch_refine_direction in this compilation)
 #elif MGX_INST_KIND == 11
 template void launch_eig_gram<T_>(int, int, bool, const T_* const*, const T_* const*, double*, double*, const EigGeom&, hipStream_t);
 template void launch_eig_combine<T_>(int, int, const T_* const*, T_* const*, const double*, const EigGeom&, hipStream_t);

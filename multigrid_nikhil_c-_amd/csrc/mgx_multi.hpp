@@ -1,116 +1,29 @@
-// mgx_multi.hpp - the kernels of mgx_solve_multi: the passes of a general-operator cycle (mgx_var.hpp, mgx_opdep.hpp) on
-// K = 2, 3 or 4 vectors at once.  Every pass of that cycle is bound by HBM traffic that is mostly coefficients: a Jacobi
-// sweep moves (NQ + 3) sizeof(T) per point, of which 3 belong to the vector.  These kernels load an operator's
-// coefficients (D_inv and R_omega, A, the eight transfer weights, the dense coarsest inverse) ONCE into registers and
-// apply them to K columns, so a sweep moves (NQ + 3K) sizeof(T) per point instead of K (NQ + 3):
-//     five-point, K = 4: 17 words against 32 (0.53);  nine-point, K = 4: 21 against 48 (0.44).
+// mgx_multi.hpp - the two passes of the block solves that keep a K-column kernel of their own, K = 2, 3 or 4, next to a
+// single-column one with another body.  Every other pass of mgx_solve_multi's cycle that reads an operator is the
+// K-column kernel of its own header (mgx_var.hpp: k_jacobi_var, k_residual_var, k_var_dense_solve; mgx_opdep.hpp:
+// k_prolong_opdep; mgx_refine_gcr.hpp: k_refine_direction), whose K = 1 instance is the pass of mgx_solve; mgx_var.hpp
+// (COLUMNS) has the traffic count, MultiIn / MultiOut and the load-before-store discipline that stands in for
+// __restrict__.
 //
-// K is a compile-time parameter; the column pointers arrive by value (MultiIn / MultiOut) and are indexed by unrolled
-// constants only (a run-time index would put the arrays into scratch).  One active column runs the single-column kernel.
+//   k_restrict_opdep_multi   next to k_restrict_opdep (mgx_opdep.hpp), which loads five u rows once and keeps three
+//                            residual rows live; this one walks the fine rows one at a time so that K = 3, 4 do not spill
+//   k_gcr_direction_multi    next to k_pcg_direction (mgx_krylov.hpp), which also forms the partials of p.q
 //
-// Per column the arithmetic and its order are those of the single-column kernel - the same helpers (load_rows, rows_of,
-// load_coefs, stencil_sum, jacobi_value, store_row, opdep_prolong_*), the same launch geometry
-// (make_launch(N, W, N - 1, 1)), the same block of k_residual_var<T, NQ, 1> summing the same points in the same order -
-// so a column's iterate and norm have the bits mgx_solve gives it, however the columns are grouped into launches.
-//
-// Load order: all K columns' row loads (3 K vectors), their right-hand sides and then the coefficients are issued before
-// the first stencil_sum; nothing is stored before every load of the wave has been issued (the column pointers carry no
-// __restrict__, so a store between two columns' loads would order them).
+// Per column the arithmetic and its order are those of the single-column kernel - the same helpers (stencil_sum, the
+// row-major nine-term sum of opdep_restrict_value), the same launch geometry - so a column's iterate has the bits
+// mgx_solve gives it, however the columns are grouped into launches.
 #pragma once
 
 #include "mgx_opdep.hpp"
 
 namespace mgx {
 
-constexpr int kMultiMax = 4;                              // MGX_MAX_RHS
-
-template <typename T, int K> struct MultiIn { const T* p[K]; };
-template <typename T, int K> struct MultiOut { T* p[K]; };
-
-// k_jacobi_var on K columns: v_j' = R_omega v_j + omega D^-1 b_j
-template <typename T, int NQ, int K>
-__global__ void __launch_bounds__(kBlock)
-k_jacobi_var_multi(MultiIn<T, K> vin, MultiIn<T, K> rhs, MultiOut<T, K> vout, const T* __restrict__ dinv, Op9<T> r,
-                   int N, long pitch, int row_lo, int row_hi, int strips, T rc, T omega, int rows_alloc)
-{
-    constexpr int W = VecOf<T>::W;
-    RowTile<T> t[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) t[j] = load_rows<T>(vin.p[j], N, pitch, row_lo, row_hi, strips, rows_alloc);
-    if (!t[0].active) return;
-    Lanes<T> b[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) b[j] = load_lanes(rhs.p[j] + t[0].at, t[0].in);
-    const Lanes<T> d = load_lanes(dinv + t[0].at, t[0].in);
-    Lanes<T> k[9];
-    load_coefs<NQ, 1>(r, t[0].at, t[0].in, k);
-    Lanes<T> o[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const Lanes<T> p1 = stencil_sum<NQ>(rows_of<NQ>(t[j]), k, [&](int) { return rc; });
-#pragma unroll
-        for (int x = 0; x < W; ++x) o[j].a[x] = jacobi_value(p1.a[x], omega, d.a[x], b[j].a[x]);
-    }
-#pragma unroll
-    for (int j = 0; j < K; ++j) store_row(vout.p[j], o[j], t[j], N);
-}
-
-// k_residual_var on K columns.  MODE 0: out.p[j] = b_j - A v_j;  MODE 1: partial.p[j][block] = the block's sum of r_j^2,
-// block i of column j summing what block i of k_residual_var<T, NQ, 1> sums
-template <typename T, int NQ, int MODE, int K>
-__global__ void __launch_bounds__(kBlock)
-k_residual_var_multi(MultiIn<T, K> vin, MultiIn<T, K> rhs, MultiOut<T, K> out, MultiOut<double, K> partial, Op9<T> a,
-                     int N, long pitch, int row_lo, int row_hi, int strips, int rows_alloc)
-{
-    using V = typename VecOf<T>::type;
-    constexpr int W = VecOf<T>::W;
-    __shared__ double wsum[K][kWavesPerBlock];
-    RowTile<T> t[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) t[j] = load_rows<T>(vin.p[j], N, pitch, row_lo, row_hi, strips, rows_alloc);
-    double acc[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) acc[j] = 0.0;
-    if (t[0].active) {
-        Lanes<T> b[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) b[j] = load_lanes(rhs.p[j] + t[0].at, t[0].in);
-        Lanes<T> k[9];
-        load_coefs<NQ, 0>(a, t[0].at, t[0].in, k);
-        V ov[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const Lanes<T> av = stencil_sum<NQ>(rows_of<NQ>(t[j]), k, [&](int x) { return k[0].a[x]; });
-            Lanes<T> o;
-#pragma unroll
-            for (int x = 0; x < W; ++x) o.a[x] = b[j].a[x] - av.a[x];
-            ov[j] = masked_row(o, t[j], N);
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            if (MODE == 0) {
-                vstore<V>(out.p[j] + t[j].at, ov[j], t[j].st);
-            } else if (t[j].st) {
-                const Lanes<T> q = to_lanes(ov[j]);
-                if constexpr (W == 2) acc[j] = (double)q.a[0] * (double)q.a[0] + (double)q.a[1] * (double)q.a[1];
-                else acc[j] = ((double)q.a[0] * (double)q.a[0] + (double)q.a[1] * (double)q.a[1]) +
-                              ((double)q.a[2] * (double)q.a[2] + (double)q.a[3] * (double)q.a[3]);
-            }
-        }
-    }
-    if (MODE != 0) {
-#pragma unroll
-        for (int j = 0; j < K; ++j) block_reduce<kWavesPerBlock>(acc[j], wsum[j], partial.p[j] + blockIdx.x, ReduceSum{});
-    }
-}
-
 // k_restrict_opdep on K columns: cb_j = c P^T f_j, f_j = b_j (MODE 0) or b_j - A u_j formed in registers (MODE 1: five-
 // point A, MODE 2: nine-point A); czero.p[j] (all null or none) is zeroed.  The eight weights of the coarse point are
 // read once, and each fine row's coefficients once for the K columns.  The sum of opdep_restrict_value is taken row by
 // row - the same nine terms in the same order (NW, N, NE, W, C, E, SW, S, SE, the first starting the accumulator, the
 // centre unmultiplied), then one multiplication by c - so that only one fine row of residuals is live per column.
-// (mgx_solve_multi instantiates MODE 1 and 2, and k_prolong_opdep_multi with ADD only: it has no FMG.  MODE 0 and !ADD are
-// the forms a multi-column FMG would launch; no test runs them yet)
+// (mgx_solve_multi instantiates MODE 1 and 2 only: it has no FMG.  MODE 0 is the form a multi-column FMG would launch)
 template <typename T, int MODE, int K>
 __global__ void __launch_bounds__(kBlock)
 k_restrict_opdep_multi(MultiIn<T, K> u, MultiIn<T, K> b, Op9<T> a, Wt8<T> w, MultiOut<T, K> cb, MultiOut<T, K> czero,
@@ -211,103 +124,6 @@ k_restrict_opdep_multi(MultiIn<T, K> u, MultiIn<T, K> b, Op9<T> a, Wt8<T> w, Mul
     }
 }
 
-// k_prolong_opdep on K columns: v_j (+)= P e_j, the weights read once
-template <typename T, bool ADD, int K>
-__global__ void __launch_bounds__(kBlock)
-k_prolong_opdep_multi(MultiOut<T, K> v, MultiIn<T, K> e, Wt8<T> w, int NC, long fpitch, long cpitch, int strips)
-{
-    using V = typename VecOf<T>::type;
-    constexpr int W = VecOf<T>::W;
-    const Tile t = wave_tile(strips, NC);
-    if (!t.active) return;
-    const Cols cc = lane_cols<W>(t.strip, NC, cpitch);
-    const int I = t.chunk;                                    // 0 .. NC - 1: fine rows 2I (not the ring row 0) and 2I + 1
-    const long fcol = 2 * cc.col;
-    const bool st0 = cc.st && fcol + W <= fpitch, st1 = cc.st && fcol + 2 * W <= fpitch;
-    const int NF = 2 * NC;
-    const long c0 = (long)I * cpitch + cc.col, c1 = c0 + cpitch;
-    // x[1 + m]: coarse column col + m
-    T e0[K][W + 2], e1[K][W + 2];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        load_coarse<T>(e.p[j] + c0, cc.ld, e0[j]);
-        load_coarse<T>(e.p[j] + c1, cc.ld, e1[j]);
-    }
-    T we[W + 2], ww[W + 2], ws[W + 2], wse[W + 2], wsw[W + 2], wn[W + 2], wne[W + 2], wnw[W + 2];
-    load_coarse<T>(w.w[3] + c0, cc.ld, we);
-    load_coarse<T>(w.w[2] + c0, cc.ld, ww);
-    load_coarse<T>(w.w[1] + c0, cc.ld, ws);
-    load_coarse<T>(w.w[7] + c0, cc.ld, wse);
-    load_coarse<T>(w.w[6] + c0, cc.ld, wsw);
-    load_coarse<T>(w.w[0] + c1, cc.ld, wn);
-    load_coarse<T>(w.w[5] + c1, cc.ld, wne);
-    load_coarse<T>(w.w[4] + c1, cc.ld, wnw);
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        T f[2 * W], g[2 * W];
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            const int m = 1 + k;
-            f[2 * k] = e0[j][m];
-            f[2 * k + 1] = opdep_prolong_edge(we[m], e0[j][m], ww[m + 1], e0[j][m + 1]);
-            g[2 * k] = opdep_prolong_edge(ws[m], e0[j][m], wn[m], e1[j][m]);
-            g[2 * k + 1] = opdep_prolong_centre(wse[m], e0[j][m], wsw[m + 1], e0[j][m + 1], wne[m], e1[j][m], wnw[m + 1], e1[j][m + 1]);
-        }
-        auto put = [&](const T* x, int row) {
-            Lanes<T> a0, a1;
-#pragma unroll
-            for (int k = 0; k < W; ++k) { a0.a[k] = x[k]; a1.a[k] = x[W + k]; }
-            V v0 = from_lanes(a0), v1 = from_lanes(a1);
-            mask_cols(v0, fcol, NF);
-            mask_cols(v1, fcol + W, NF);
-            T* p = v.p[j] + (long)row * fpitch + fcol;
-            if (ADD) {
-                const Lanes<T> o0 = to_lanes(vload<V>(p, st0)), o1 = to_lanes(vload<V>(p + W, st1));
-                const Lanes<T> n0 = to_lanes(v0), n1 = to_lanes(v1);
-                Lanes<T> s0, s1;
-#pragma unroll
-                for (int k = 0; k < W; ++k) { s0.a[k] = o0.a[k] + n0.a[k]; s1.a[k] = o1.a[k] + n1.a[k]; }
-                v0 = from_lanes(s0); v1 = from_lanes(s1);
-            }
-            vstore<V>(p, v0, st0);
-            vstore<V>(p + W, v1, st1);
-        };
-        if (I > 0) put(f, 2 * I);
-        put(g, 2 * I + 1);
-    }
-}
-
-// k_var_dense_solve on K columns: x_j = Inv b_j, every element of Inv read once, each column's row sum in order
-template <typename T, int K>
-__global__ void k_var_dense_solve_multi(const double* __restrict__ Inv, MultiIn<T, K> b, MultiOut<T, K> x, int n, long pitch)
-{
-    const int NN = n * n;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= NN) return;
-    const double* row = Inv + (long)i * NN;
-    double acc[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) acc[j] = 0.0;
-    for (int q = 0; q < NN; ++q) {
-        const int bi = q / n, bj = q - bi * n;
-        const double m = row[q];
-        const long at = (long)(bi + 1) * pitch + (bj + 1);
-#pragma unroll
-        for (int j = 0; j < K; ++j) acc[j] += m * (double)b.p[j][at];
-    }
-    const int ri = i / n, rj = i - ri * n;
-#pragma unroll
-    for (int j = 0; j < K; ++j) x.p[j][(long)(ri + 1) * pitch + (rj + 1)] = (T)acc[j];
-}
-
-// f(tag) with decltype(tag)::value == 2, 3 or 4: the column count of a launch as a compile-time constant
-template <typename F> void with_column_count(int k, F&& f)
-{
-    if (k == 2) f(std::integral_constant<int, 2>{});
-    else if (k == 3) f(std::integral_constant<int, 3>{});
-    else f(std::integral_constant<int, 4>{});
-}
-
 // ---- mgx_solve_multi_gcr ------------------------------------------------------------------------------------------
 // The direction pass of GCR on K columns: Z_j = z_j, Q_j = A z_j - the first_it = 1 form of k_pcg_direction<T, 1 | 2>
 // (mgx_krylov.hpp) with the level's NQ coefficient grids loaded once per row for the K columns: (NQ + 3K) sizeof(T) per
@@ -376,13 +192,10 @@ void launch_gcr_direction_multi(int m, bool nine, const T* const* z, T* const* z
 {
     with_point_count(nine, [&](auto nq) {
         constexpr int NQ = decltype(nq)::value;
-        with_column_count(m, [&](auto kc) {
+        with_count<kMultiMax, 2>(m, [&](auto kc) {
             constexpr int K = decltype(kc)::value;
-            MultiIn<T, K> zi;
-            MultiOut<T, K> zz, qq;
-            for (int j = 0; j < K; ++j) { zi.p[j] = z[j]; zz.p[j] = zo[j]; qq.p[j] = q[j]; }
-            hipLaunchKernelGGL((k_gcr_direction_multi<T, NQ, K>), dim3(g.blocks), dim3(kBlock), 0, st, zi, zz, qq, a, N, pitch, g.R, g.strips,
-                               g.chunks);
+            hipLaunchKernelGGL((k_gcr_direction_multi<T, NQ, K>), dim3(g.blocks), dim3(kBlock), 0, st, columns_in<K>(z), columns_out<K>(zo),
+                               columns_out<K>(q), a, N, pitch, g.R, g.strips, g.chunks);
         });
     });
 }

@@ -8,9 +8,10 @@ namespace {
 // Host code only: the recursion of vcycle / coarse_visits / descend / ascend as a general-operator handle runs it
 // (fold_eligible and zero_in_ok are false there: every block is plain per-level launches, every coarse guess is zeroed by
 // the restriction), on the columns act[0 .. m) of s->multi.  W- and F-cycles go through the per-level launches on every
-// level (k_small_visit is bit-identical to them).  One active column runs the single-column kernels; two to four run
-// one launch of the K-column kernels of mgx_multi.hpp wherever a coefficient is read, and the existing kernels once per
-// column where none is (the bilinear transfers, the injection).  No Prof scopes: cfg.profile does not extend to the call.
+// level (k_small_visit is bit-identical to them).  Wherever a coefficient is read the set runs one launch of the pass's
+// K-column kernel, K = m - the kernel, launch helper and geometry of mgx_solve's own pass, which is its m = 1 call
+// (mgx_var.hpp, COLUMNS) - and where none is (the bilinear transfers, the injection) the single-column kernel once per
+// column.  No Prof scopes: cfg.profile does not extend to the call.
 void multi_free_column(mgx_solver::MultiWs& w, int c)
 {
     auto drop = [](std::initializer_list<void**> ps) {
@@ -80,16 +81,12 @@ inline MultiSet multi_all(int nrhs)
     return a;
 }
 
-template <typename T, int K> MultiIn<T, K> multi_in(void* const* grids, const MultiSet& a)
+// the grids of the set's columns as a host array of m pointers (T may be const), what the launch_* helpers take
+template <typename T> struct SetPtrs { T* p[MGX_MAX_RHS]; };
+template <typename T, typename G> SetPtrs<T> set_ptrs(G* const* grids, const MultiSet& a)
 {
-    MultiIn<T, K> o;
-    for (int j = 0; j < K; ++j) o.p[j] = (const T*)grids[a.act[j]];
-    return o;
-}
-template <typename T, int K> MultiOut<T, K> multi_out(void* const* grids, const MultiSet& a)
-{
-    MultiOut<T, K> o;
-    for (int j = 0; j < K; ++j) o.p[j] = grids ? (T*)grids[a.act[j]] : nullptr;
+    SetPtrs<T> o{};
+    for (int j = 0; j < a.m; ++j) o.p[j] = (T*)grids[a.act[j]];
     return o;
 }
 
@@ -102,22 +99,9 @@ void multi_smooth(mgx_solver* s, int level, const MultiSet& a, int mu, double* f
     auto& w = s->multi.lv[level];
     const T om = (T)s->cfg.omega;
     const T rc = (T)(1.0 - (double)om);
-    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
     const VarLevel<T> v = var_level<T>(l);
-    const dim3 grd(g.blocks), blk(kBlock);
     for (int i = 0; i < mu; ++i) {
-        with_point_count(v.nine, [&](auto nq) {
-            constexpr int NQ = decltype(nq)::value;
-            if (a.m == 1) {
-                const int c = a.act[0];
-                hipLaunchKernelGGL((k_jacobi_var<T, NQ>), grd, blk, 0, s->stream, (const T*)w.u[c], (const T*)w.b[c], (T*)w.tmp[c], v.dinv, v.r,
-                                   v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
-            } else with_column_count(a.m, [&](auto kc) {
-                constexpr int K = decltype(kc)::value;
-                hipLaunchKernelGGL((k_jacobi_var_multi<T, NQ, K>), grd, blk, 0, s->stream, multi_in<T, K>(w.u, a), multi_in<T, K>(w.b, a),
-                                   multi_out<T, K>(w.tmp, a), v.dinv, v.r, v.N, v.pitch, 1, v.N, g.strips, rc, om, v.rows);
-            });
-        });
+        launch_jacobi_var<T>(v, a.m, set_ptrs<const T>(w.u, a).p, set_ptrs<const T>(w.b, a).p, set_ptrs<T>(w.tmp, a).p, rc, om, s->stream);
         for (int j = 0; j < a.m; ++j) std::swap(w.u[a.act[j]], w.tmp[a.act[j]]);
     }
     if (fu && level == s->cfg.finest_level)
@@ -132,26 +116,10 @@ void multi_residual(mgx_solver* s, int level, const MultiSet& a)
     const Level& l = s->lv[level];
     auto& ws = s->multi;
     auto& w = ws.lv[level];
-    const Launch g = make_launch(l.N, VecOf<T>::W, l.N - 1, 1);
-    const VarLevel<T> v = var_level<T>(l);
-    const dim3 grd(g.blocks), blk(kBlock);
-    with_point_count(v.nine, [&](auto nq) {
-        constexpr int NQ = decltype(nq)::value;
-        if (a.m == 1) {
-            const int c = a.act[0];
-            hipLaunchKernelGGL((k_residual_var<T, NQ, MODE>), grd, blk, 0, s->stream, (const T*)w.u[c], (const T*)w.b[c], MODE ? (T*)nullptr : (T*)w.r[c],
-                               MODE ? ws.part[c] : (double*)nullptr, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
-        } else with_column_count(a.m, [&](auto kc) {
-            constexpr int K = decltype(kc)::value;
-            MultiOut<double, K> part;
-            for (int j = 0; j < K; ++j) part.p[j] = MODE ? ws.part[a.act[j]] : nullptr;
-            hipLaunchKernelGGL((k_residual_var_multi<T, NQ, MODE, K>), grd, blk, 0, s->stream, multi_in<T, K>(w.u, a), multi_in<T, K>(w.b, a),
-                               multi_out<T, K>(MODE ? nullptr : w.r, a), part, v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
-        });
-    });
-    if (MODE == 1)
-        for (int j = 0; j < a.m; ++j)
-            hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, s->stream, ws.part[a.act[j]], g.blocks, ws.sums + a.act[j]);
+    double* sums[MGX_MAX_RHS] = {};
+    for (int j = 0; j < a.m; ++j) sums[j] = ws.sums + a.act[j];
+    launch_residual_var<T, MODE>(var_level<T>(l), a.m, set_ptrs<const T>(w.u, a).p, set_ptrs<const T>(w.b, a).p,
+                                 MODE ? nullptr : set_ptrs<T>(w.r, a).p, MODE ? set_ptrs<double>(ws.part, a).p : nullptr, sums, s->stream);
 }
 
 // restrict_level(level, fused = true, zero_guess = true) on the set
@@ -169,15 +137,20 @@ void multi_restrict(mgx_solver* s, int level, const MultiSet& a)
         const dim3 grd(g.blocks), blk(kBlock);
         with_point_count(f.nine, [&](auto nq) {
             constexpr int MODE = decltype(nq)::value == 9 ? 2 : 1;
+            // one column: mgx_solve's kernel, not the K = 1 instance of the K-column one.  The two bodies differ
+            // (k_restrict_opdep loads the five u rows once and keeps three residual rows live, 216 / 256 VGPRs in double /
+            // float, two waves per SIMD; k_restrict_opdep_multi reloads three u rows per fine row so that K = 3, 4 do not
+            // spill, 112 / 118 VGPRs at K = 1, four waves) and which is faster has not been measured: replacing one
+            // with the other would change the speed of mgx_solve or of a block solve's last column
             if (a.m == 1) {
                 const int j = a.act[0];
                 hipLaunchKernelGGL((k_restrict_opdep<T, MODE>), grd, blk, 0, s->stream, (const T*)wf.u[j], (const T*)wf.b[j], op9_of<T>(f), wt8_of<T>(c),
                                    (T*)wc.b[j], (T*)wc.u[j], c.N, f.pitch, c.pitch, g.strips, rscale);
-            } else with_column_count(a.m, [&](auto kc) {
+            } else with_count<kMultiMax, 2>(a.m, [&](auto kc) {
                 constexpr int K = decltype(kc)::value;
-                hipLaunchKernelGGL((k_restrict_opdep_multi<T, MODE, K>), grd, blk, 0, s->stream, multi_in<T, K>(wf.u, a), multi_in<T, K>(wf.b, a),
-                                   op9_of<T>(f), wt8_of<T>(c), multi_out<T, K>(wc.b, a), multi_out<T, K>(wc.u, a), c.N, f.pitch, c.pitch,
-                                   g.strips, rscale);
+                hipLaunchKernelGGL((k_restrict_opdep_multi<T, MODE, K>), grd, blk, 0, s->stream, columns_in<K>(set_ptrs<const T>(wf.u, a).p),
+                                   columns_in<K>(set_ptrs<const T>(wf.b, a).p), op9_of<T>(f), wt8_of<T>(c), columns_out<K>(set_ptrs<T>(wc.b, a).p),
+                                   columns_out<K>(set_ptrs<T>(wc.u, a).p), c.N, f.pitch, c.pitch, g.strips, rscale);
             });
         });
         return;
@@ -211,16 +184,7 @@ void multi_prolong(mgx_solver* s, int level, const MultiSet& a)
             launch_prolong<T>((T*)wf.u[a.act[i]], (const T*)wc.u[a.act[i]], f.N, f.pitch, c.pitch, 1, f.N, 0, true, s->rows_per_chunk, s->stream);
         return;
     }
-    const Launch g = make_launch(c.N, VecOf<T>::W, c.N, 1);
-    const dim3 grd(g.blocks), blk(kBlock);
-    if (a.m == 1)
-        hipLaunchKernelGGL((k_prolong_opdep<T, true>), grd, blk, 0, s->stream, (T*)wf.u[a.act[0]], (const T*)wc.u[a.act[0]], wt8_of<T>(c), c.N, f.pitch,
-                           c.pitch, g.strips);
-    else with_column_count(a.m, [&](auto kc) {
-        constexpr int K = decltype(kc)::value;
-        hipLaunchKernelGGL((k_prolong_opdep_multi<T, true, K>), grd, blk, 0, s->stream, multi_out<T, K>(wf.u, a), multi_in<T, K>(wc.u, a), wt8_of<T>(c),
-                           c.N, f.pitch, c.pitch, g.strips);
-    });
+    launch_prolong_opdep<T>(a.m, true, set_ptrs<T>(wf.u, a).p, set_ptrs<const T>(wc.u, a).p, wt8_of<T>(c), c.N, f.pitch, c.pitch, s->stream);
 }
 
 // the visit of the coarsest level: bottom_solve, or the two blocks of bottom = SMOOTH
@@ -235,14 +199,7 @@ void multi_bottom(mgx_solver* s, const MultiSet& a, double* fu)
     }
     const Level& l = s->lv[level];
     auto& w = s->multi.lv[level];
-    const int n = l.N - 1;
-    const dim3 grd((n * n + 63) / 64), blk(64);
-    if (a.m == 1)
-        hipLaunchKernelGGL((k_var_dense_solve<T>), grd, blk, 0, s->stream, s->var_inv, (const T*)w.b[a.act[0]], (T*)w.u[a.act[0]], n, l.pitch);
-    else with_column_count(a.m, [&](auto kc) {
-        constexpr int K = decltype(kc)::value;
-        hipLaunchKernelGGL((k_var_dense_solve_multi<T, K>), grd, blk, 0, s->stream, s->var_inv, multi_in<T, K>(w.b, a), multi_out<T, K>(w.u, a), n, l.pitch);
-    });
+    launch_var_dense_solve<T>(s->var_inv, a.m, set_ptrs<const T>(w.b, a).p, set_ptrs<T>(w.u, a).p, l.N - 1, l.pitch, s->stream);
 }
 
 template <typename T> void multi_vcycle(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu);
@@ -444,7 +401,8 @@ void multi_gcr_direction(mgx_solver* s, const MultiSet& a, int j, const Launch& 
     auto& ws = s->multi;
     auto& w = ws.lv[s->cfg.finest_level];
     if (a.m == 1) {
-        // k_pcg_direction's first iteration, as mgx_solve_gcr launches it (its partials z.q go where nothing reads them)
+        // k_pcg_direction's first iteration, as mgx_solve_gcr launches it (its partials z.q go where nothing reads them);
+        // that kernel also forms those partials, so it is not the K = 1 form of k_gcr_direction_multi
         const KrylovView v = krylov_view(s, a.act[0]);
         krylov_direction<T>(s, v, l, g, (const T*)w.u[a.act[0]], (const T*)w.u[a.act[0]], (T*)v.Z[j], (T*)v.Q[j], true);
         return;

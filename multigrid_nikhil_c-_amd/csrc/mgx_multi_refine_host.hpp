@@ -6,7 +6,7 @@
 //   the orthogonalisation, the mixed update, the reductions              gcr_orth, refine_gcr_update, krylov_reduce on
 //                                                                        krylov_view(s, c), r32 = the shadow column's b
 //   the host's reading of an iteration                                   MultiFrame::gcr_step
-// The one new pass is the direction pass on the set (k_refine_direction_multi, mgx_refine_multi.hpp).
+// The direction pass runs on the set (k_refine_direction<NQ, K>, mgx_refine_gcr.hpp).
 // Workspaces: the shadow (refine_shadow, shared with mgx_solve_refine*), the shadow's MultiWs float columns on every
 // level, the parent's MultiWs with its Krylov pieces (shared with mgx_solve_multi_gcr; its coarse fp64 columns are
 // allocated and not used here).  The handle's own vectors, kry workspace and graphs and the shadow's are not touched.
@@ -22,7 +22,7 @@ int multi_refine_guard(mgx_solver* s, const char* fn)
 }
 
 // Z_c[j] = z_c = scale[c] * (double) z32_c (the shadow column's finest u), Q_c[j] = A z_c for the columns of the set: one
-// launch, the operator read once; one column runs k_refine_direction on its view
+// launch of k_refine_direction, the operator read once
 void multi_refine_direction(mgx_solver* s, const MultiSet& a, int j, const Launch& g, const double* scale)
 {
     const int L = s->cfg.finest_level;
@@ -30,18 +30,13 @@ void multi_refine_direction(mgx_solver* s, const MultiSet& a, int j, const Launc
     const Level& fl = s->shadow->lv[L];
     auto& ws = s->multi;
     auto& fw = s->shadow->multi.lv[L];
-    if (a.m == 1) {
-        const int c = a.act[0];
-        refine_gcr_direction(s, krylov_view(s, c), g, j, scale[c], (const float*)fw.u[c], fl.pitch);
-        return;
-    }
     const float* z32[MGX_MAX_RHS];
     double *z[MGX_MAX_RHS], *q[MGX_MAX_RHS], sc[MGX_MAX_RHS];
     for (int i = 0; i < a.m; ++i) {
         const int c = a.act[i];
         z32[i] = (const float*)fw.u[c]; z[i] = (double*)ws.Z[c][j]; q[i] = (double*)ws.Q[c][j]; sc[i] = scale[c];
     }
-    launch_refine_direction_multi(a.m, l.nine, z32, z, q, sc, op9_of<double>(l), l.N, l.pitch, fl.pitch, g, s->stream);
+    launch_refine_direction(a.m, l.nine, z32, z, q, sc, op9_of<double>(l), l.N, l.pitch, fl.pitch, g, s->stream);
 }
 
 // the three workspaces for nrhs columns and `restart` basis pairs; a failure leaves what existed

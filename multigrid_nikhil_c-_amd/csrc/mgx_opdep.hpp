@@ -334,9 +334,11 @@ k_restrict_opdep(const T* __restrict__ u, const T* __restrict__ b, Op9<T> a, Wt8
     if (czero) vstore<V>(czero + (long)I * cpitch + cc.col, vzero((V*)nullptr), cc.st);
 }
 
-template <typename T, bool ADD>
+// on K columns (mgx_var.hpp, COLUMNS): the weights read once; a column's loads of v (ADD) follow the stores of the columns
+// before it, which no column's e or weights alias
+template <typename T, bool ADD, int K>
 __global__ void __launch_bounds__(kBlock)
-k_prolong_opdep(T* __restrict__ v, const T* __restrict__ e, Wt8<T> w, int NC, long fpitch, long cpitch, int strips)
+k_prolong_opdep(MultiOut<T, K> v, MultiIn<T, K> e, Wt8<T> w, int NC, long fpitch, long cpitch, int strips)
 {
     using V = typename VecOf<T>::type;
     constexpr int W = VecOf<T>::W;
@@ -349,9 +351,13 @@ k_prolong_opdep(T* __restrict__ v, const T* __restrict__ e, Wt8<T> w, int NC, lo
     const int NF = 2 * NC;
     const long c0 = (long)I * cpitch + cc.col, c1 = c0 + cpitch;
     // x[1 + m]: coarse column col + m
-    T e0[W + 2], e1[W + 2], we[W + 2], ww[W + 2], ws[W + 2], wse[W + 2], wsw[W + 2], wn[W + 2], wne[W + 2], wnw[W + 2];
-    load_coarse<T>(e + c0, cc.ld, e0);
-    load_coarse<T>(e + c1, cc.ld, e1);
+    T e0[K][W + 2], e1[K][W + 2];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        load_coarse<T>(e.p[j] + c0, cc.ld, e0[j]);
+        load_coarse<T>(e.p[j] + c1, cc.ld, e1[j]);
+    }
+    T we[W + 2], ww[W + 2], ws[W + 2], wse[W + 2], wsw[W + 2], wn[W + 2], wne[W + 2], wnw[W + 2];
     load_coarse<T>(w.w[3] + c0, cc.ld, we);
     load_coarse<T>(w.w[2] + c0, cc.ld, ww);
     load_coarse<T>(w.w[1] + c0, cc.ld, ws);
@@ -360,37 +366,55 @@ k_prolong_opdep(T* __restrict__ v, const T* __restrict__ e, Wt8<T> w, int NC, lo
     load_coarse<T>(w.w[0] + c1, cc.ld, wn);
     load_coarse<T>(w.w[5] + c1, cc.ld, wne);
     load_coarse<T>(w.w[4] + c1, cc.ld, wnw);
-    T f[2 * W], g[2 * W];
 #pragma unroll
-    for (int k = 0; k < W; ++k) {
-        const int m = 1 + k;
-        f[2 * k] = e0[m];
-        f[2 * k + 1] = opdep_prolong_edge(we[m], e0[m], ww[m + 1], e0[m + 1]);
-        g[2 * k] = opdep_prolong_edge(ws[m], e0[m], wn[m], e1[m]);
-        // the cell centre south-east of coarse (I, col + k): its NW / NE / SW / SE coarse points
-        g[2 * k + 1] = opdep_prolong_centre(wse[m], e0[m], wsw[m + 1], e0[m + 1], wne[m], e1[m], wnw[m + 1], e1[m + 1]);
-    }
-    auto put = [&](const T* x, int row) {
-        Lanes<T> a0, a1;
+    for (int j = 0; j < K; ++j) {
+        T f[2 * W], g[2 * W];
 #pragma unroll
-        for (int k = 0; k < W; ++k) { a0.a[k] = x[k]; a1.a[k] = x[W + k]; }
-        V v0 = from_lanes(a0), v1 = from_lanes(a1);
-        mask_cols(v0, fcol, NF);
-        mask_cols(v1, fcol + W, NF);
-        T* p = v + (long)row * fpitch + fcol;
-        if (ADD) {
-            const Lanes<T> o0 = to_lanes(vload<V>(p, st0)), o1 = to_lanes(vload<V>(p + W, st1));
-            const Lanes<T> n0 = to_lanes(v0), n1 = to_lanes(v1);
-            Lanes<T> s0, s1;
-#pragma unroll
-            for (int k = 0; k < W; ++k) { s0.a[k] = o0.a[k] + n0.a[k]; s1.a[k] = o1.a[k] + n1.a[k]; }
-            v0 = from_lanes(s0); v1 = from_lanes(s1);
+        for (int k = 0; k < W; ++k) {
+            const int m = 1 + k;
+            f[2 * k] = e0[j][m];
+            f[2 * k + 1] = opdep_prolong_edge(we[m], e0[j][m], ww[m + 1], e0[j][m + 1]);
+            g[2 * k] = opdep_prolong_edge(ws[m], e0[j][m], wn[m], e1[j][m]);
+            // the cell centre south-east of coarse (I, col + k): its NW / NE / SW / SE coarse points
+            g[2 * k + 1] = opdep_prolong_centre(wse[m], e0[j][m], wsw[m + 1], e0[j][m + 1], wne[m], e1[j][m], wnw[m + 1], e1[j][m + 1]);
         }
-        vstore<V>(p, v0, st0);
-        vstore<V>(p + W, v1, st1);
-    };
-    if (I > 0) put(f, 2 * I);
-    put(g, 2 * I + 1);
+        auto put = [&](const T* x, int row) {
+            Lanes<T> a0, a1;
+#pragma unroll
+            for (int k = 0; k < W; ++k) { a0.a[k] = x[k]; a1.a[k] = x[W + k]; }
+            V v0 = from_lanes(a0), v1 = from_lanes(a1);
+            mask_cols(v0, fcol, NF);
+            mask_cols(v1, fcol + W, NF);
+            T* p = v.p[j] + (long)row * fpitch + fcol;
+            if (ADD) {
+                const Lanes<T> o0 = to_lanes(vload<V>(p, st0)), o1 = to_lanes(vload<V>(p + W, st1));
+                const Lanes<T> n0 = to_lanes(v0), n1 = to_lanes(v1);
+                Lanes<T> s0, s1;
+#pragma unroll
+                for (int k = 0; k < W; ++k) { s0.a[k] = o0.a[k] + n0.a[k]; s1.a[k] = o1.a[k] + n1.a[k]; }
+                v0 = from_lanes(s0); v1 = from_lanes(s1);
+            }
+            vstore<V>(p, v0, st0);
+            vstore<V>(p + W, v1, st1);
+        };
+        if (I > 0) put(f, 2 * I);
+        put(g, 2 * I + 1);
+    }
+}
+
+// v_j += P e_j (add) or v_j = P e_j on m = 1 .. kMultiMax columns (host arrays of m pointers), NC the coarse level's N.
+// (Only mgx_solve's FMG launches !add, on one column; the K > 1 forms of it are what a multi-column FMG would launch)
+template <typename T>
+void launch_prolong_opdep(int m, bool add, T* const* v, const T* const* e, const Wt8<T>& w, int NC, long fpitch, long cpitch, hipStream_t st)
+{
+    const Launch g = make_launch(NC, VecOf<T>::W, NC, 1);
+    with_count<kMultiMax>(m, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if (add) hipLaunchKernelGGL((k_prolong_opdep<T, true, K>), dim3(g.blocks), dim3(kBlock), 0, st, columns_out<K>(v), columns_in<K>(e), w, NC,
+                                    fpitch, cpitch, g.strips);
+        else hipLaunchKernelGGL((k_prolong_opdep<T, false, K>), dim3(g.blocks), dim3(kBlock), 0, st, columns_out<K>(v), columns_in<K>(e), w, NC,
+                                fpitch, cpitch, g.strips);
+    });
 }
 
 } // namespace mgx

@@ -84,16 +84,6 @@ static void refine_pass(mgx_solver* s, bool has_e, double scale, double inv_scal
 }
 
 // ---- mgx_solve_refine_gcr: fp64 restarted GCR (mgx_krylov.hpp) around the float cycle of the shadow ---------------
-// Z_j = z = scale * (double) z32, Q_j = A z on the handle's finest operator; z32 has the shadow's pitch epitch
-static void refine_gcr_direction(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double scale, const float* z32, long epitch)
-{
-    const Level& d = s->lv[s->cfg.finest_level];
-    with_point_count(d.nine, [&](auto nq) {
-        hipLaunchKernelGGL((k_refine_direction<decltype(nq)::value>), dim3(g.blocks), dim3(kBlock), 0, s->stream, z32, op9_of<double>(d),
-                           (double*)v.Z[j], (double*)v.Q[j], scale, d.N, d.pitch, epitch, g.R, g.strips, g.chunks);
-    });
-}
-
 // x += alpha Z_j, r -= alpha Q_j, the partials of ||r||^2 and r32 = (float)(r * inv_scale_next), the right-hand side of
 // the next float cycle
 static void refine_gcr_update(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double inv_scale_next, float* r32, long epitch)
@@ -103,11 +93,16 @@ static void refine_gcr_update(mgx_solver* s, const KrylovView& v, const Launch& 
                        (const double*)v.Q[j], r32, inv_scale_next, (const double*)v.sc, v.part, d.N, d.pitch, epitch, g.R, g.strips, g.chunks);
 }
 
-// the two on the handle's own workspace: z32 is the shadow's U, r32 the shadow's right-hand side
+// the two on the handle's own workspace: z32 is the shadow's U (with the shadow's pitch), r32 the shadow's right-hand side.
+// Z_j = z = scale * (double) z32, Q_j = A z on the handle's finest operator: the one-column launch of k_refine_direction
 static void refine_gcr_direction(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double scale)
 {
+    const Level& d = s->lv[s->cfg.finest_level];
     const Level& w = s->shadow->lv[s->cfg.finest_level];
-    refine_gcr_direction(s, v, g, j, scale, (const float*)w.u, w.pitch);
+    const float* const z32 = (const float*)w.u;
+    double* const z = (double*)v.Z[j];
+    double* const q = (double*)v.Q[j];
+    launch_refine_direction(1, d.nine, &z32, &z, &q, &scale, op9_of<double>(d), d.N, d.pitch, w.pitch, g, s->stream);
 }
 static void refine_gcr_update(mgx_solver* s, const KrylovView& v, const Launch& g, int j, double inv_scale_next)
 {

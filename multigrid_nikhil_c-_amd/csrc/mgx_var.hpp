@@ -27,6 +27,19 @@
 // passes of independent rows (one wave per row and strip, like k_jacobi_rows; 16-byte lanes, the column neighbours from
 // the adjacent lanes by DPP): HBM-bound, no temporal fusion (a K-level pass would need K-row windows of NQ more arrays
 // in registers).
+//
+// COLUMNS.  The passes that read an operator (k_jacobi_var, k_residual_var, k_var_dense_solve here; k_prolong_opdep,
+// k_refine_direction, the kernels of mgx_multi.hpp and mgx_eig.hpp on top) run on K = 1 .. kMultiMax vectors per launch:
+// the coefficients are loaded ONCE into registers and applied to K columns, so a sweep moves (NQ + 3K) sizeof(T) per
+// point instead of K (NQ + 3) - five-point, K = 4: 17 words against 32; nine-point: 21 against 48.  K = 1 is the pass of
+// mgx_solve and its relatives on the level's own vectors; there is one body, so a column has the same bits however the
+// columns are grouped into launches.  K is a compile-time parameter; the column pointers arrive by value (MultiIn /
+// MultiOut) and are indexed by unrolled constants only (a run-time index would put the arrays into scratch).  The host
+// passes arrays of m pointers to one launch_* helper per pass, which resolves NQ and m to an instance.
+// ALIASING: distinct columns never alias, but the qualifier __restrict__ cannot sit on the elements of a by-value array,
+// so the kernels order their memory operations by hand: a row-per-wave pass issues every load of the wave (all K columns'
+// rows, their right-hand sides, then the coefficients) before its first store; a marching pass issues all loads of a
+// row before that row's stores.  A store between two columns' loads would order them.
 #pragma once
 
 #include "mgx_kernels.hpp"
@@ -43,6 +56,10 @@ __device__ __forceinline__ float4 from_lanes(const Lanes<float>& l) { return mak
 
 template <typename T> struct Op9 { const T* a[9]; };     // c, n, s, w, e, nw, ne, sw, se (corners null on five-point levels)
 template <typename T> struct Op9Out { T* a[9]; };
+
+constexpr int kMultiMax = 4;                              // MGX_MAX_RHS
+template <typename T, int K> struct MultiIn { const T* p[K]; };          // the K columns of a launch
+template <typename T, int K> struct MultiOut { T* p[K]; };
 
 // storage slot of the coefficient that points at (dy, dx)
 __host__ __device__ constexpr int op9_slot(int dy, int dx)
@@ -156,56 +173,89 @@ template <typename T> __device__ __forceinline__ void store_row(T* out, const La
 // MF:86-90: the Jacobi value J(v) = R_omega v + omega (D_inv b) of one point, p1 = (R_omega v) there
 template <typename T> __device__ __forceinline__ T jacobi_value(T p1, T omega, T dinv, T b) { return p1 + omega * (dinv * b); }
 
-// MF:75-96: one sweep of v' = J(v), out of place; rows [row_lo, row_hi).  r: the off-diagonals of R_omega in slots
-// 1 .. NQ - 1 (its diagonal is the scalar rc = 1 - omega)
-template <typename T, int NQ>
+// MF:75-96: one sweep of v_j' = J(v_j) = R_omega v_j + omega D^-1 b_j on K columns, out of place; rows [row_lo, row_hi).
+// r: the off-diagonals of R_omega in slots 1 .. NQ - 1 (its diagonal is the scalar rc = 1 - omega)
+template <typename T, int NQ, int K>
 __global__ void __launch_bounds__(kBlock)
-k_jacobi_var(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ vout, const T* __restrict__ dinv, Op9<T> r,
+k_jacobi_var(MultiIn<T, K> vin, MultiIn<T, K> rhs, MultiOut<T, K> vout, const T* __restrict__ dinv, Op9<T> r,
              int N, long pitch, int row_lo, int row_hi, int strips, T rc, T omega, int rows_alloc)
 {
     constexpr int W = VecOf<T>::W;
-    const RowTile<T> t = load_rows<T>(vin, N, pitch, row_lo, row_hi, strips, rows_alloc);
-    if (!t.active) return;
-    const Lanes<T> b = load_lanes(rhs + t.at, t.in), d = load_lanes(dinv + t.at, t.in);
-    Lanes<T> k[9];
-    load_coefs<NQ, 1>(r, t.at, t.in, k);
-    const Lanes<T> p1 = stencil_sum<NQ>(rows_of<NQ>(t), k, [&](int) { return rc; });                                                       // MF:86
-    Lanes<T> o;
+    RowTile<T> t[K];
 #pragma unroll
-    for (int x = 0; x < W; ++x) o.a[x] = jacobi_value(p1.a[x], omega, d.a[x], b.a[x]);                                         // MF:88, 90
-    store_row(vout, o, t, N);
+    for (int j = 0; j < K; ++j) t[j] = load_rows<T>(vin.p[j], N, pitch, row_lo, row_hi, strips, rows_alloc);
+    if (!t[0].active) return;
+    Lanes<T> b[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) b[j] = load_lanes(rhs.p[j] + t[0].at, t[0].in);
+    const Lanes<T> d = load_lanes(dinv + t[0].at, t[0].in);
+    Lanes<T> k[9];
+    load_coefs<NQ, 1>(r, t[0].at, t[0].in, k);
+    Lanes<T> o[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const Lanes<T> p1 = stencil_sum<NQ>(rows_of<NQ>(t[j]), k, [&](int) { return rc; });                                     // MF:86
+#pragma unroll
+        for (int x = 0; x < W; ++x) o[j].a[x] = jacobi_value(p1.a[x], omega, d.a[x], b[j].a[x]);                               // MF:88, 90
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) store_row(vout.p[j], o[j], t[j], N);
 }
 
-// MF:150-153: r = b - A v.  MODE 0: store r;  MODE 1: per-block sums of r^2 (the norm the solve reports)
-template <typename T, int NQ, int MODE>
+// the sum of the squares of a lane's W values, in double, pairwise
+template <typename T> __device__ __forceinline__ double lane_squares(const Lanes<T>& q)
+{
+    if constexpr (VecOf<T>::W == 2) return (double)q.a[0] * (double)q.a[0] + (double)q.a[1] * (double)q.a[1];
+    else return ((double)q.a[0] * (double)q.a[0] + (double)q.a[1] * (double)q.a[1]) +
+                ((double)q.a[2] * (double)q.a[2] + (double)q.a[3] * (double)q.a[3]);
+}
+
+// MF:150-153: r_j = b_j - A v_j on K columns.  MODE 0: out.p[j] = r_j;  MODE 1: partial.p[j][block] = the block's sum of
+// r_j^2 (the norm the solve reports), the same points in the same order whatever K is
+template <typename T, int NQ, int MODE, int K>
 __global__ void __launch_bounds__(kBlock)
-k_residual_var(const T* __restrict__ vin, const T* __restrict__ rhs, T* __restrict__ out, double* __restrict__ partial, Op9<T> a,
+k_residual_var(MultiIn<T, K> vin, MultiIn<T, K> rhs, MultiOut<T, K> out, MultiOut<double, K> partial, Op9<T> a,
                int N, long pitch, int row_lo, int row_hi, int strips, int rows_alloc)
 {
     using V = typename VecOf<T>::type;
     constexpr int W = VecOf<T>::W;
-    __shared__ double wsum[kWavesPerBlock];
-    const RowTile<T> t = load_rows<T>(vin, N, pitch, row_lo, row_hi, strips, rows_alloc);
-    double acc = 0.0;
-    if (t.active) {
-        const Lanes<T> b = load_lanes(rhs + t.at, t.in);
-        Lanes<T> k[9];
-        load_coefs<NQ, 0>(a, t.at, t.in, k);
-        const Lanes<T> av = stencil_sum<NQ>(rows_of<NQ>(t), k, [&](int x) { return k[0].a[x]; });
-        Lanes<T> o;
+    __shared__ double wsum[K][kWavesPerBlock];
+    RowTile<T> t[K];
 #pragma unroll
-        for (int x = 0; x < W; ++x) o.a[x] = b.a[x] - av.a[x];
-        const V ov = masked_row(o, t, N);
-        if (MODE == 0) {
-            vstore<V>(out + t.at, ov, t.st);
-        } else if (t.st) {
-            const Lanes<T> q = to_lanes(ov);
-            if constexpr (W == 2) acc = (double)q.a[0] * (double)q.a[0] + (double)q.a[1] * (double)q.a[1];
-            else acc = ((double)q.a[0] * (double)q.a[0] + (double)q.a[1] * (double)q.a[1]) +
-                       ((double)q.a[2] * (double)q.a[2] + (double)q.a[3] * (double)q.a[3]);
+    for (int j = 0; j < K; ++j) t[j] = load_rows<T>(vin.p[j], N, pitch, row_lo, row_hi, strips, rows_alloc);
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = 0.0;
+    if (t[0].active) {
+        Lanes<T> b[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) b[j] = load_lanes(rhs.p[j] + t[0].at, t[0].in);
+        Lanes<T> k[9];
+        load_coefs<NQ, 0>(a, t[0].at, t[0].in, k);
+        V ov[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const Lanes<T> av = stencil_sum<NQ>(rows_of<NQ>(t[j]), k, [&](int x) { return k[0].a[x]; });
+            Lanes<T> o;
+#pragma unroll
+            for (int x = 0; x < W; ++x) o.a[x] = b[j].a[x] - av.a[x];
+            ov[j] = masked_row(o, t[j], N);
+            // one column squares its residual here, K > 1 in the loop below: the same sums either way, but the compiler
+            // makes the float K = 1 norm pass wait for every load when the squares follow in a second loop (9 and 14
+            // s_waitcnt vmcnt against 2, 2.7 % slower at 4096^2), and taking them here for K > 1 would change the
+            // registers of those instances
+            if constexpr (MODE != 0 && K == 1) { if (t[j].st) acc[j] = lane_squares(to_lanes(ov[j])); }
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (MODE == 0) vstore<V>(out.p[j] + t[j].at, ov[j], t[j].st);
+            else if (K > 1 && t[j].st) acc[j] = lane_squares(to_lanes(ov[j]));
         }
     }
-    if (MODE != 0) block_reduce<kWavesPerBlock>(acc, wsum, partial + blockIdx.x, ReduceSum{});
+    if (MODE != 0) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) block_reduce<kWavesPerBlock>(acc[j], wsum[j], partial.p[j] + blockIdx.x, ReduceSum{});
+    }
 }
 
 // MF:122-130: coarse(I, J) = wgt * fine(2I, 2J); optionally zero the coarse guess (PS:613) in the same pass
@@ -325,21 +375,28 @@ static __global__ void k_gj_elim(double* __restrict__ M, double* __restrict__ In
         else { mi[j] = mi[j] - f * pm[j]; ii[j] = ii[j] - f * pi[j]; }
     }
 }
-// x = Inv b on the coarsest grid: one thread per unknown, in-order row sum (deterministic, n^2 <= 961 terms)
-template <typename T>
-__global__ void k_var_dense_solve(const double* __restrict__ Inv, const T* __restrict__ b, T* __restrict__ x, int n, long pitch)
+// x_j = Inv b_j on the coarsest grid, K columns: one thread per unknown, every element of Inv read once, each column's
+// row sum in order (deterministic, n^2 <= 961 terms)
+template <typename T, int K>
+__global__ void k_var_dense_solve(const double* __restrict__ Inv, MultiIn<T, K> b, MultiOut<T, K> x, int n, long pitch)
 {
     const int NN = n * n;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= NN) return;
     const double* row = Inv + (long)i * NN;
-    double acc = 0.0;
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = 0.0;
     for (int q = 0; q < NN; ++q) {
         const int bi = q / n, bj = q - bi * n;
-        acc += row[q] * (double)b[(long)(bi + 1) * pitch + (bj + 1)];
+        const double m = row[q];
+        const long at = (long)(bi + 1) * pitch + (bj + 1);
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc[j] += m * (double)b.p[j][at];
     }
     const int ri = i / n, rj = i - ri * n;
-    x[(long)(ri + 1) * pitch + (rj + 1)] = (T)acc;
+#pragma unroll
+    for (int j = 0; j < K; ++j) x.p[j][(long)(ri + 1) * pitch + (rj + 1)] = (T)acc[j];
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------
@@ -359,6 +416,72 @@ template <typename F> void with_float_type(bool f64, F&& f) { if (f64) f(double{
 template <typename F> void with_point_count(bool nine, F&& f)
 {
     if (nine) f(std::integral_constant<int, 9>{}); else f(std::integral_constant<int, 5>{});
+}
+
+// f(tag) with decltype(tag)::value == k, MIN <= k <= MAX: a count (of columns, mostly) as a compile-time constant
+template <int MAX, int MIN = 1, typename F> void with_count(int k, F&& f)
+{
+    if constexpr (MAX > MIN) {
+        if (k < MAX) { with_count<MAX - 1, MIN>(k, f); return; }
+    }
+    f(std::integral_constant<int, MAX>{});
+}
+
+// the first K pointers of a host array as kernel arguments (p null: K null pointers)
+template <int K, typename T> MultiIn<T, K> columns_in(const T* const* p)
+{
+    MultiIn<T, K> o;
+    for (int j = 0; j < K; ++j) o.p[j] = p[j];
+    return o;
+}
+template <int K, typename T> MultiOut<T, K> columns_out(T* const* p)
+{
+    MultiOut<T, K> o;
+    for (int j = 0; j < K; ++j) o.p[j] = p ? p[j] : nullptr;
+    return o;
+}
+
+// ---- the launches of the passes above: m = 1 .. kMultiMax columns as host arrays of m pointers, one wave per row and strip ----
+// one sweep vout_j = J(vin_j) with the right-hand sides rhs_j
+template <typename T>
+void launch_jacobi_var(const VarLevel<T>& v, int m, const T* const* vin, const T* const* rhs, T* const* vout, T rc, T omega, hipStream_t st)
+{
+    const Launch g = make_launch(v.N, VecOf<T>::W, v.N - 1, 1);
+    with_point_count(v.nine, [&](auto nq) {
+        with_count<kMultiMax>(m, [&](auto kc) {
+            constexpr int NQ = decltype(nq)::value, K = decltype(kc)::value;
+            hipLaunchKernelGGL((k_jacobi_var<T, NQ, K>), dim3(g.blocks), dim3(kBlock), 0, st, columns_in<K>(vin), columns_in<K>(rhs),
+                               columns_out<K>(vout), v.dinv, v.r, v.N, v.pitch, 1, v.N, g.strips, rc, omega, v.rows);
+        });
+    });
+}
+
+// MODE 0: out_j = rhs_j - A vin_j;  MODE 1: sums[j][0] = the sum of its squares through partial[j] (one double per
+// workgroup of the pass), each column reduced by its own k_reduce_partials
+template <typename T, int MODE>
+void launch_residual_var(const VarLevel<T>& v, int m, const T* const* vin, const T* const* rhs, T* const* out, double* const* partial,
+                         double* const* sums, hipStream_t st)
+{
+    const Launch g = make_launch(v.N, VecOf<T>::W, v.N - 1, 1);
+    with_point_count(v.nine, [&](auto nq) {
+        with_count<kMultiMax>(m, [&](auto kc) {
+            constexpr int NQ = decltype(nq)::value, K = decltype(kc)::value;
+            hipLaunchKernelGGL((k_residual_var<T, NQ, MODE, K>), dim3(g.blocks), dim3(kBlock), 0, st, columns_in<K>(vin), columns_in<K>(rhs),
+                               columns_out<K>(out), columns_out<K>(partial), v.a, v.N, v.pitch, 1, v.N, g.strips, v.rows);
+        });
+    });
+    if (MODE == 1)
+        for (int j = 0; j < m; ++j) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kReduceThreads), 0, st, partial[j], g.blocks, sums[j]);
+}
+
+// x_j = inv b_j on the n x n unknowns of the coarsest level
+template <typename T>
+void launch_var_dense_solve(const double* inv, int m, const T* const* b, T* const* x, int n, long pitch, hipStream_t st)
+{
+    with_count<kMultiMax>(m, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL((k_var_dense_solve<T, K>), dim3((n * n + 63) / 64), dim3(64), 0, st, inv, columns_in<K>(b), columns_out<K>(x), n, pitch);
+    });
 }
 
 } // namespace mgx

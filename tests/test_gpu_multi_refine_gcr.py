@@ -3,9 +3,9 @@ the float block cycle on up to MGX_MAX_RHS right-hand sides per operator read, o
 
 Every comparison is assert_column (== on the stats fields, np.array_equal on history and iterate) against
 mgx_solve_refine_gcr ON THE SAME HANDLE (mgx_set_rhs, mgx_set_guess, mgx_solve_refine_gcr, mgx_get_solution), column by
-column.  mgx_solve_refine_gcr replays the float cycle of the shadow hierarchy from a graph of the single-column kernels
-and runs k_refine_direction and k_refine_update on the handle's own Krylov workspace; the block call launches the K-column
-float kernels of csrc/mgx_multi.hpp eagerly on the shadow's columns, k_refine_direction_multi (csrc/mgx_refine_multi.hpp)
+column.  mgx_solve_refine_gcr replays the float cycle of the shadow hierarchy from a graph of the K = 1 kernels and runs
+k_refine_direction<NQ, 1> and k_refine_update on the handle's own Krylov workspace; the block call launches the K-column
+instances of the same float kernels eagerly on the shadow's columns, k_refine_direction<NQ, K> (csrc/mgx_refine_gcr.hpp)
 for the set, and the coefficient-free passes once per column on that column's scalars, partial sums and float right-hand
 side, each column scaled by the power of two its own history gives - the bits must not know the difference.
 

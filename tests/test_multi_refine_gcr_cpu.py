@@ -1,6 +1,6 @@
 """CPU checks of mgx_solve_multi_refine_gcr and mgx_time_multi_refine_direction (include/mgx.h): the two entry points in
 the header with their argument counts, in the library and in the binding; a NULL handle is an invalid argument without a
-GPU; and the build's resource remarks hold the six instances of k_refine_direction_multi, none with scratch (DESIGN.md
+GPU; and the build's resource remarks hold the eight instances of k_refine_direction, none with scratch (DESIGN.md
 5.8 tables their registers).  What the call computes is held to mgx_solve_refine_gcr on the GPU
 (tests/test_gpu_multi_refine_gcr.py); that the refinement loop commutes with powers of two is tests/test_refine_gcr_cpu.py's."""
 import ctypes as C
@@ -38,12 +38,12 @@ def test_a_null_handle_is_an_invalid_argument(pkg):
 
 
 def test_no_instance_of_the_direction_kernel_uses_scratch(pkg):
-    """the build leaves every kernel's resource usage in csrc/build/*.remarks: NQ = 5, 9 and K = 2, 3, 4 are there, each
-    without scratch and without spilled registers (four nine-point columns are one launch, not two of two)"""
+    """the build leaves every kernel's resource usage in csrc/build/*.remarks: NQ = 5, 9 and K = 1, 2, 3, 4 are there (K = 1 is
+    mgx_solve_refine_gcr's own pass), each without scratch and without spilled registers (four nine-point columns are one launch, not two of two)"""
     txt = "".join(open(f).read() for f in glob.glob(os.path.join(os.path.dirname(pkg.LIB_PATH), "csrc", "build", "*.remarks")))
     seen = {}
-    for m in re.finditer(r"Function Name: \S*k_refine_direction_multiILi(\d)ELi(\d)E\S*.*?ScratchSize \[bytes/lane\]: (\d+).*?VGPRs Spill: (\d+)",
+    for m in re.finditer(r"Function Name: \S*k_refine_directionILi(\d)ELi(\d)E\S*.*?ScratchSize \[bytes/lane\]: (\d+).*?VGPRs Spill: (\d+)",
                          txt, re.S):
         seen[(int(m.group(1)), int(m.group(2)))] = (int(m.group(3)), int(m.group(4)))
-    assert set(seen) == {(nq, k) for nq in (5, 9) for k in (2, 3, 4)}, sorted(seen)
+    assert set(seen) == {(nq, k) for nq in (5, 9) for k in (1, 2, 3, 4)}, sorted(seen)
     assert all(v == (0, 0) for v in seen.values()), seen

@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
 """mgx_solve_multi (up to four right-hand sides per operator read) next to four mgx_solve calls on the same
-handle, and its K-column Jacobi sweep next to k_jacobi_var, all in one process (the tables of
+handle, and its K-column Jacobi sweep next to the K = 1 sweep, all in one process (the tables of
 profiles/multi_rhs_kernel_trace_summary.md).
 
     python tools/multi_bench.py [--quick] [--only kernels|solves]
 
 Kernels: at a 4096^2 finest level (--quick: 1024^2), GALERKIN fp64 and fp32 handles with a five-point (contrast 10) and a
 nine-point (rotated anisotropy) finest operator: mgx_time_multi_smoother - HIP events around 20 sweeps, median of 5 -
-for nrhs = 1 (k_jacobi_var on a workspace column, the yardstick of the same run) and nrhs = 2, 3, 4
-(k_jacobi_var_multi<T, NQ, K>).  Bytes are the algorithm's: (NQ + 3 K) sizeof(T) per point; no counter run is made.
-Target: the K = 4 instances move their bytes at 0.8 of k_jacobi_var's bytes/s.
+for nrhs = 1 (k_jacobi_var<T, NQ, 1> on a workspace column, the yardstick of the same run) and nrhs = 2, 3, 4
+(k_jacobi_var<T, NQ, K>).  Bytes are the algorithm's: (NQ + 3 K) sizeof(T) per point; no counter run is made.
+Target: the K = 4 instances move their bytes at 0.8 of the K = 1 instance's bytes/s.
 
 Solves: time to 1e-8 at 2047^2 and 4095^2 (--quick: 511^2), GALERKIN, levels L..5, fp64, Jacobi V(2,2), four columns
 b_j = default_rng(3 + j).uniform(-1, 1) from zero guesses; contrast 10 with the operator-dependent P and rotated
@@ -48,7 +48,7 @@ def problems(L):
 
 def kernels():
     n = (1 << LK) - 1
-    print(f"\n| {1 << LK}^2 finest level | nrhs | B per point | ms per sweep | TB/s (of 8) | over k_jacobi_var | ms per column, over nrhs = 1 |")
+    print(f"\n| {1 << LK}^2 finest level | nrhs | B per point | ms per sweep | TB/s (of 8) | over nrhs = 1 | ms per column, over nrhs = 1 |")
     print("|---|---|---|---|---|---|---|")
     for dtype, tname, es in ((pkg.DTYPE_F64, "double", 8), (pkg.DTYPE_F32, "float", 4)):
         for what, _, setter, transfer, nq in problems(LK):
@@ -66,7 +66,7 @@ def kernels():
                     rate = nbytes * n * n / (t * 1e-3)
                     if nrhs == 1:
                         rate1, t1 = rate, t
-                    kernel = f"`k_jacobi_var<{tname}, {nq}>`" if nrhs == 1 else f"`k_jacobi_var_multi<{tname}, {nq}, {nrhs}>`"
+                    kernel = f"`k_jacobi_var<{tname}, {nq}, {nrhs}>`"
                     print(f"| {kernel} | {nrhs} | {nbytes} | {t:.4f} | {rate / 1e12:.2f} ({rate / 8e12:.2f}) | {rate / rate1:.2f} | "
                           f"{t / nrhs:.4f}, {t / nrhs / t1:.2f} |", flush=True)
 

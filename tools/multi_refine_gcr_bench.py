@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """mgx_solve_multi_refine_gcr (fp64 restarted GCR around the float block cycle on up to four right-hand sides)
 next to four mgx_solve_refine_gcr rounds and one mgx_solve_multi_gcr call on the same handle, and its K-column direction
-pass next to k_refine_direction (the tables of profiles/multi_refine_gcr_kernel_trace_summary.md).
+pass next to its K = 1 instance (the tables of profiles/multi_refine_gcr_kernel_trace_summary.md).
 
     python tools/multi_refine_gcr_bench.py [--quick] [--only kernels|solves] [--levels 11,12]
 
@@ -10,9 +10,9 @@ after the other, and the first step that fails or runs out of time ends the run 
 
 Kernels (one step): at a 4096^2 finest level (--quick: 1024^2), GALERKIN fp64 handles with a five-point (contrast 10) and a
 nine-point (rotated anisotropy) finest operator: mgx_time_multi_refine_direction - HIP events around 20 launches, median of
-5 - for nrhs = 1 (k_refine_direction on a workspace column, the yardstick of the same run) and nrhs = 2, 3, 4
-(k_refine_direction_multi<NQ, K>).  Bytes are the algorithm's: 8 NQ + 20 K per point; no counter run is made.
-Target: the K-column instances move their bytes at 0.8 of k_refine_direction's bytes/s.
+5 - for nrhs = 1 (k_refine_direction<NQ, 1> on a workspace column, the yardstick of the same run) and nrhs = 2, 3, 4
+(k_refine_direction<NQ, K>).  Bytes are the algorithm's: 8 NQ + 20 K per point; no counter run is made.
+Target: the K-column instances move their bytes at 0.8 of the K = 1 instance's bytes/s.
 
 Solves (one step per size): time to 1e-10 at 2047^2 and 4095^2 (--quick: 511^2; --levels: the finest levels named), GALERKIN,
 levels L..5, fp64, Jacobi V(2,2), GCR(4), four columns b_j = default_rng(3 + j).uniform(-1, 1) from zero guesses; contrast 10
@@ -48,7 +48,7 @@ def problems(pkg, L, eps_list):
 
 def kernels(pkg, np):
     n = (1 << LK) - 1
-    print(f"\n| {1 << LK}^2 finest level, fp64 | nrhs | B per point | ms per launch | TB/s (of 8) | over k_refine_direction | "
+    print(f"\n| {1 << LK}^2 finest level, fp64 | nrhs | B per point | ms per launch | TB/s (of 8) | over nrhs = 1 | "
           "ms per column, over nrhs = 1 | byte model, over nrhs = 1 |")
     print("|---|---|---|---|---|---|---|---|")
     for what, _, setter, transfer, nq in problems(pkg, LK, (0.5,)):
@@ -66,7 +66,7 @@ def kernels(pkg, np):
                 rate = nbytes * n * n / (t * 1e-3)
                 if nrhs == 1:
                     rate1, t1 = rate, t
-                kernel = f"`k_refine_direction<{nq}>`" if nrhs == 1 else f"`k_refine_direction_multi<{nq}, {nrhs}>`"
+                kernel = f"`k_refine_direction<{nq}, {nrhs}>`"
                 print(f"| {kernel} | {nrhs} | {nbytes} | {t:.4f} | {rate / 1e12:.2f} ({rate / 8e12:.2f}) | {rate / rate1:.2f} | "
                       f"{t / nrhs:.4f}, {t / nrhs / t1:.2f} | {nbytes / nrhs / (8 * nq + 20):.2f} |", flush=True)
 

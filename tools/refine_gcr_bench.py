@@ -66,7 +66,7 @@ def kernels():
                 return statistics.median(f() for _ in range(5))
 
             rows = [(f"`k_pcg_direction<double, {1 if nq == 5 else 2}>`", 8 * nq + 24, med(lambda: mg.time_gcr_pass(3, 0, 20)), None),
-                    (f"`k_refine_direction<{nq}>`", 8 * nq + 20, med(lambda: mg.time_refine_gcr_pass(1, 20)), 0),
+                    (f"`k_refine_direction<{nq}, 1>`", 8 * nq + 20, med(lambda: mg.time_refine_gcr_pass(1, 20)), 0),
                     ("`k_pcg_update<double>`", 48, med(lambda: mg.time_gcr_pass(0, 0, 20)), None),
                     ("`k_refine_update`", 52, med(lambda: mg.time_refine_gcr_pass(0, 20)), 2)]
         rates = [nbytes * n * n / (t * 1e-3) for _, nbytes, t, _ in rows]
