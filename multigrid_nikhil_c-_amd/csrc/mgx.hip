@@ -218,10 +218,11 @@ namespace {
 // ---- profiling scopes ---------------------------------------------------------
 struct Prof {
     mgx_solver* s; int idx = -1;
-    Prof(mgx_solver* s_, int cls, long long launches) : s(s_)
+    // on = false: no scope (cfg.profile covers the handle's own column, not a block call's columns)
+    Prof(mgx_solver* s_, int cls, long long launches, bool on = true) : s(s_)
     {
         static const bool mute_all = env_int("MGX_PROF_MUTE", 0) != 0;      // experiment: the split submission of cfg.profile = 2 without its events
-        if (!s->cfg.profile || s->prof_mute || mute_all) return;
+        if (!on || !s->cfg.profile || s->prof_mute || mute_all) return;
         EventPair p;
         if (!s->ev_free.empty()) { p = s->ev_free.back(); s->ev_free.pop_back(); }
         else {
@@ -627,19 +628,57 @@ int var_ready(mgx_solver* s, int lo, int hi)
     return MGX_OK;
 }
 
-// MF:75-96: mu sweeps, one launch each, u <-> tmp
+// ---- the columns a cycle works on ------------------------------------------------------------------------------------
+// The level operations and the walk below run on a set of columns: act[0 .. m), m >= 1, ascending.  Column c >= 0 is
+// column c of s->multi (mgx_multi_host.hpp); the handle's own grids are one more column, kOwn, which comes alone: the
+// set kOwnSet.  What exists for the own column only - Prof scopes, the constant stencil's kernels, the smoothers other
+// than Jacobi, the folded passes and the one-workgroup visits - asks own(a).
+struct MultiSet { int act[MGX_MAX_RHS]; int m; };
+constexpr int kOwn = -1;
+constexpr MultiSet kOwnSet{{kOwn}, 1};
+inline bool own(const MultiSet& a) { return a.act[0] == kOwn; }
+
+inline MultiSet multi_all(int nrhs)
+{
+    MultiSet a{};
+    for (int j = 0; j < nrhs; ++j) a.act[a.m++] = j;
+    return a;
+}
+
+// the pointer slot `which` of column c on a level, the storage itself: a sweep swaps u and tmp through it
+enum Slot { kU, kTmp, kB, kR };
+inline void*& slot(mgx_solver* s, int level, int c, Slot which)
+{
+    if (c == kOwn) {
+        Level& l = s->lv[level];
+        void** const own_slots[] = {&l.u, &l.tmp, &l.b, &l.r};
+        return *own_slots[which];
+    }
+    auto& w = s->multi.lv[level];
+    void** const columns[] = {w.u, w.tmp, w.b, w.r};
+    return columns[which][c];
+}
+
+// one slot of the set's columns as a host array of m pointers (T may be const), what the launch_* helpers take
+template <typename T> struct SetPtrs { T* p[MGX_MAX_RHS]; };
+template <typename T> SetPtrs<T> set_ptrs(mgx_solver* s, int level, const MultiSet& a, Slot which)
+{
+    SetPtrs<T> o{};
+    for (int j = 0; j < a.m; ++j) o.p[j] = (T*)slot(s, level, a.act[j], which);
+    return o;
+}
+
+// MF:75-96: mu sweeps, one launch each for the set, u <-> tmp
 template <typename T>
-void smooth_var_t(mgx_solver* s, Level& l, int mu)
+void smooth_var_t(mgx_solver* s, int level, const MultiSet& a, int mu)
 {
     const T om = (T)s->cfg.omega;
     const T rc = (T)(1.0 - (double)om);
-    const VarLevel<T> v = var_level<T>(l);
-    const T* const b = (const T*)l.b;
+    const VarLevel<T> v = var_level<T>(s->lv[level]);
     for (int i = 0; i < mu; ++i) {
-        const T* const u = (const T*)l.u;
-        T* const out = (T*)l.tmp;
-        launch_jacobi_var<T>(v, 1, &u, &b, &out, rc, om, s->stream);
-        std::swap(l.u, l.tmp);
+        launch_jacobi_var<T>(v, a.m, set_ptrs<const T>(s, level, a, kU).p, set_ptrs<const T>(s, level, a, kB).p, set_ptrs<T>(s, level, a, kTmp).p,
+                             rc, om, s->stream);
+        for (int j = 0; j < a.m; ++j) std::swap(slot(s, level, a.act[j], kU), slot(s, level, a.act[j], kTmp));
     }
     s->last_smooth_launches = mu;
 }
@@ -691,37 +730,56 @@ void smooth_colour_t(mgx_solver* s, Level& l, int mu, bool reverse)
 }
 
 // the level smoother of a general-operator handle; post: the block follows a correction (MGX_SMOOTHER_COLOR_SGS sweeps
-// it in reverse colour order; nothing else looks at it)
-void smooth_var(mgx_solver* s, Level& l, int mu, bool post = false)
+// it in reverse colour order; nothing else looks at it).  The Jacobi block runs on the set; the other smoothers exist for
+// the own column only (multi_guard refuses them for a block)
+void smooth_var(mgx_solver* s, int level, const MultiSet& a, int mu, bool post = false)
 {
+    Level& l = s->lv[level];
     if (s->colour) {
         const bool reverse = s->colour == 2 && post;
         if (l.f64) smooth_colour_t<double>(s, l, mu, reverse); else smooth_colour_t<float>(s, l, mu, reverse);
     }
     else if (s->line_dirs) { if (l.f64) smooth_line_t<double>(s, l, mu); else smooth_line_t<float>(s, l, mu); }
     else if (s->cfg.smoother == MGX_SMOOTHER_CHEBYSHEV) { if (l.f64) smooth_cheby_t<double>(s, l, mu); else smooth_cheby_t<float>(s, l, mu); }
-    else if (l.f64) smooth_var_t<double>(s, l, mu);       // MF:75-96
-    else smooth_var_t<float>(s, l, mu);
+    else if (l.f64) smooth_var_t<double>(s, level, a, mu);       // MF:75-96
+    else smooth_var_t<float>(s, level, a, mu);
 }
 
-// MF:150-153: r = b - A u into `out` (MODE 0) or sum r^2 -> sum_dev (MODE 1)
+// MF:150-153 on m grid pairs of level l, one per column of the set: out_j = b_j - A u_j (MODE 0), or the per-block sums
+// of its squares into the column's partials, each reduced by k_reduce_partials in its own order into the column's sum
+// (MODE 1; out may be null): s->partial and s->sum_dev for the own column, multi.part[c] and multi.sums + c for column c
 template <typename T, int MODE>
-void residual_var_t(mgx_solver* s, const Level& l, const void* u, const void* b, void* out)
+void residual_var_t(mgx_solver* s, const Level& l, const MultiSet& a, const T* const* u, const T* const* b, T* const* out)
 {
-    const T* const uu = (const T*)u;
-    const T* const bb = (const T*)b;
-    T* const oo = (T*)out;
-    launch_residual_var<T, MODE>(var_level<T>(l), 1, &uu, &bb, &oo, &s->partial, &s->sum_dev, s->stream);
+    double *part[MGX_MAX_RHS] = {}, *sums[MGX_MAX_RHS] = {};
+    for (int j = 0; j < a.m; ++j) {
+        const int c = a.act[j];
+        part[j] = c == kOwn ? s->partial : s->multi.part[c];
+        sums[j] = c == kOwn ? s->sum_dev : s->multi.sums + c;
+    }
+    launch_residual_var<T, MODE>(var_level<T>(l), a.m, u, b, out, part, sums, s->stream);
 }
 
-// the same of whichever operator the handle has, on a grid pair of level l: the general operator's kernel or the
-// constant stencil's (which takes the partial-sum capacity for MODE 1 only)
+// ... of the u and b of the set's columns, MODE 0 into their r
+template <typename T, int MODE>
+void residual_set(mgx_solver* s, int level, const MultiSet& a)
+{
+    residual_var_t<T, MODE>(s, s->lv[level], a, set_ptrs<const T>(s, level, a, kU).p, set_ptrs<const T>(s, level, a, kB).p,
+                            MODE ? nullptr : set_ptrs<T>(s, level, a, kR).p);
+}
+
+// the same of whichever operator the handle has, on a grid pair of level l (the own column's, or the Krylov and fp64
+// vectors that stand in for them): the general operator's kernel or the constant stencil's (which takes the partial-sum
+// capacity for MODE 1 only)
 template <int MODE>
 void residual_level(mgx_solver* s, const Level& l, const void* u, const void* b, void* out)
 {
     with_float_type(l.f64, [&](auto tag) {
         using T = decltype(tag);
-        if (s->var) residual_var_t<T, MODE>(s, l, u, b, out);
+        const T* const uu = (const T*)u;
+        const T* const bb = (const T*)b;
+        T* const oo = (T*)out;
+        if (s->var) residual_var_t<T, MODE>(s, l, kOwnSet, &uu, &bb, &oo);
         else launch_residual<T, MODE>((const T*)u, (const T*)b, out, MODE ? 0 : l.pitch, MODE ? s->partial : nullptr, MODE ? s->sum_dev : nullptr,
                                       1.0, l.N, l.pitch, 1, l.N, s->rows_per_chunk, s->stream, MODE ? s->partial_cap : -1, l.rows);
     });
@@ -877,96 +935,122 @@ void smooth_t(mgx_solver* s, Level& l, int mu)
     if (launches & 1) std::swap(l.u, l.tmp);
 }
 
-void smooth(mgx_solver* s, int level, int mu, bool post = false)
+// one smoothing block of the set on a level.  fu (may be null): the fine_updates of a block call's columns, fu[c] for
+// column c; the own column counts into s->fine_updates
+void smooth(mgx_solver* s, int level, int mu, bool post = false, const MultiSet& a = kOwnSet, double* fu = nullptr)
 {
     if (mu <= 0) return;
     Level& l = s->lv[level];
     const bool fine = (level == s->cfg.finest_level);
-    Prof p(s, fine ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, mu);
-    if (s->var) smooth_var(s, l, mu, post);
+    Prof p(s, fine ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, mu, own(a));
+    if (s->var) smooth_var(s, level, a, mu, post);
     else smooth_t(s, l, mu);
     p.set(s->last_smooth_launches, mu);
+    if (!fine) return;
     // one update per point and sweep; an alternating line sweep is an x- and a y-sweep
-    if (fine) s->fine_updates += (double)(s->line_dirs == 3 ? 2 * mu : mu) * (double)(l.N - 1) * (double)(l.N - 1);
+    const double updates = (double)(s->line_dirs == 3 ? 2 * mu : mu) * (double)(l.N - 1) * (double)(l.N - 1);
+    if (own(a)) s->fine_updates += updates;
+    else if (fu) for (int j = 0; j < a.m; ++j) fu[a.act[j]] += updates;
 }
 
-// B[level-1] = R (B - A U)[level]  (fused = true)  or  R B[level]  (fused = false)
-void restrict_level(mgx_solver* s, int level, bool fused, bool zero_guess)
+// B[level-1] = R (B - A U)[level]  (fused = true)  or  R B[level]  (fused = false) of the set's columns; zero_guess: and
+// U[level-1] = 0.  A block call restricts fused with zero_guess; the unfused form and the constant stencil are the own
+// column's
+void restrict_level(mgx_solver* s, int level, bool fused, bool zero_guess, const MultiSet& a = kOwnSet)
 {
     Level& f = s->lv[level];
     Level& c = s->lv[level - 1];
     const bool fine = (level == s->cfg.finest_level);
-    Prof p(s, fine ? MGX_PROF_RESTRICT_FINE : MGX_PROF_COARSE, 1);
+    Prof p(s, fine ? MGX_PROF_RESTRICT_FINE : MGX_PROF_COARSE, 1, own(a));
     const int rpc = s->rows_per_chunk;
     const int mode = s->cfg.restrict_mode;
     with_float_type(f.f64, [&](auto tag) {
         using T = decltype(tag);
-        T* cz = zero_guess ? (T*)c.u : nullptr;
+        const SetPtrs<const T> uf = set_ptrs<const T>(s, level, a, kU), bf = set_ptrs<const T>(s, level, a, kB);
+        const SetPtrs<T> cb = set_ptrs<T>(s, level - 1, a, kB);
+        const SetPtrs<T> cz = zero_guess ? set_ptrs<T>(s, level - 1, a, kU) : SetPtrs<T>{};
         if (opdep(s)) {
             // B_c = c P^T (B - A U) or c P^T B with the hierarchy's own weights, the residual formed in the same pass
             const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
             const T rscale = (mode == MGX_RESTRICT_FW16) ? (T)0.25 : (T)1;
             const dim3 grd(g.blocks), blk(kBlock);
-            if (!fused) hipLaunchKernelGGL((k_restrict_opdep<T, 0>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b, op9_of<T>(f), wt8_of<T>(c),
-                                           (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
+            if (!fused) hipLaunchKernelGGL((k_restrict_opdep<T, 0>), grd, blk, 0, s->stream, uf.p[0], bf.p[0], op9_of<T>(f), wt8_of<T>(c), cb.p[0],
+                                           cz.p[0], c.N, f.pitch, c.pitch, g.strips, rscale);
             else with_point_count(f.nine, [&](auto nq) {
-                hipLaunchKernelGGL((k_restrict_opdep<T, decltype(nq)::value == 9 ? 2 : 1>), grd, blk, 0, s->stream, (const T*)f.u, (const T*)f.b,
-                                   op9_of<T>(f), wt8_of<T>(c), (T*)c.b, cz, c.N, f.pitch, c.pitch, g.strips, rscale);
+                constexpr int MODE = decltype(nq)::value == 9 ? 2 : 1;
+                // one column: mgx_solve's kernel, not the K = 1 instance of the K-column one.  The two bodies differ
+                // (k_restrict_opdep loads the five u rows once and keeps three residual rows live, 216 / 256 VGPRs in double /
+                // float, two waves per SIMD; k_restrict_opdep_multi reloads three u rows per fine row so that K = 3, 4 do not
+                // spill, 112 / 118 VGPRs at K = 1, four waves) and which is faster has not been measured: replacing one
+                // with the other would change the speed of mgx_solve or of a block solve's last column
+                if (a.m == 1) hipLaunchKernelGGL((k_restrict_opdep<T, MODE>), grd, blk, 0, s->stream, uf.p[0], bf.p[0], op9_of<T>(f), wt8_of<T>(c),
+                                                 cb.p[0], cz.p[0], c.N, f.pitch, c.pitch, g.strips, rscale);
+                else with_count<kMultiMax, 2>(a.m, [&](auto kc) {
+                    constexpr int K = decltype(kc)::value;
+                    hipLaunchKernelGGL((k_restrict_opdep_multi<T, MODE, K>), grd, blk, 0, s->stream, columns_in<K>(uf.p), columns_in<K>(bf.p),
+                                       op9_of<T>(f), wt8_of<T>(c), columns_out<K>(cb.p), columns_out<K>(cz.p), c.N, f.pitch, c.pitch, g.strips, rscale);
+                });
             });
             return;
         }
         // general operator and / or injection (MF:122-130): the residual is formed first as a grid (MF:150-153; f.r
-        // was allocated with the handle), then restricted by full weighting (PS:531-546) or injected.  The constant
+        // was allocated with the handle; the operator's grids read once for the set), then each column's is restricted
+        // by full weighting (PS:531-546) or injected, with the coefficient-free single-column kernel.  The constant
         // stencil with full weighting forms it inside launch_restrict (fused) and reads B itself
         const bool grid_residual = fused && (s->var || mode >= MGX_RESTRICT_INJECT);
-        if (grid_residual) residual_level<0>(s, f, f.u, f.b, f.r);
-        const T* src = (const T*)(grid_residual ? f.r : f.b);
-        if (mode >= MGX_RESTRICT_INJECT) {
-            const double w = (mode == MGX_RESTRICT_INJECT4) ? 4.0 : 1.0;
-            const dim3 blk(256), grd((c.N + 255) / 256, c.N - 1);
-            hipLaunchKernelGGL((k_restrict_inject<T>), grd, blk, 0, s->stream, src, (T*)c.b, cz, c.N, f.pitch, c.pitch, (T)w);
-        } else {
-            launch_restrict<T>((const T*)f.u, src, (T*)c.b, cz, f.N, f.pitch, c.pitch, 1, c.N, 0, mode, fused && !grid_residual, rpc, s->stream);
+        if (grid_residual) {
+            if (s->var) residual_set<T, 0>(s, level, a);
+            else residual_level<0>(s, f, f.u, f.b, f.r);
+        }
+        const SetPtrs<const T> src = grid_residual ? set_ptrs<const T>(s, level, a, kR) : bf;
+        for (int j = 0; j < a.m; ++j) {
+            if (mode >= MGX_RESTRICT_INJECT) {
+                const double w = (mode == MGX_RESTRICT_INJECT4) ? 4.0 : 1.0;
+                const dim3 blk(256), grd((c.N + 255) / 256, c.N - 1);
+                hipLaunchKernelGGL((k_restrict_inject<T>), grd, blk, 0, s->stream, src.p[j], cb.p[j], cz.p[j], c.N, f.pitch, c.pitch, (T)w);
+            } else {
+                launch_restrict<T>(uf.p[j], src.p[j], cb.p[j], cz.p[j], f.N, f.pitch, c.pitch, 1, c.N, 0, mode, fused && !grid_residual, rpc, s->stream);
+            }
         }
     });
 }
 
-void prolong_level(mgx_solver* s, int level, bool add)
+// U[level] += P U[level-1] (add) or U[level] = P U[level-1] of the set's columns
+void prolong_level(mgx_solver* s, int level, bool add, const MultiSet& a = kOwnSet)
 {
     Level& f = s->lv[level];
     Level& c = s->lv[level - 1];
     const bool fine = (level == s->cfg.finest_level);
-    Prof p(s, fine ? MGX_PROF_PROLONG_FINE : MGX_PROF_COARSE, 1);
+    Prof p(s, fine ? MGX_PROF_PROLONG_FINE : MGX_PROF_COARSE, 1, own(a));
     with_float_type(f.f64, [&](auto tag) {
         using T = decltype(tag);
-        if (!opdep(s)) {
-            launch_prolong<T>((T*)f.u, (const T*)c.u, f.N, f.pitch, c.pitch, 1, f.N, 0, add, s->rows_per_chunk, s->stream);
-            return;
-        }
-        T* const v = (T*)f.u;
-        const T* const e = (const T*)c.u;
-        launch_prolong_opdep<T>(1, add, &v, &e, wt8_of<T>(c), c.N, f.pitch, c.pitch, s->stream);
+        const SetPtrs<T> v = set_ptrs<T>(s, level, a, kU);
+        const SetPtrs<const T> e = set_ptrs<const T>(s, level - 1, a, kU);
+        if (opdep(s)) launch_prolong_opdep<T>(a.m, add, v.p, e.p, wt8_of<T>(c), c.N, f.pitch, c.pitch, s->stream);
+        else for (int j = 0; j < a.m; ++j) launch_prolong<T>(v.p[j], e.p[j], f.N, f.pitch, c.pitch, 1, f.N, 0, add, s->rows_per_chunk, s->stream);
     });
 }
 
-void bottom_solve(mgx_solver* s)
+// the exact solve of the set's columns on the coarsest level (the constant stencil's is the own column's)
+void bottom_solve(mgx_solver* s, const MultiSet& a = kOwnSet)
 {
-    Level& l = s->lv[s->cfg.coarsest_level];
-    Prof p(s, (l.L == s->cfg.finest_level) ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, 4);
+    const int level = s->cfg.coarsest_level;
+    Level& l = s->lv[level];
+    Prof p(s, (l.L == s->cfg.finest_level) ? MGX_PROF_SMOOTH_FINE : MGX_PROF_COARSE, 4, own(a));
     const int n = l.N - 1;
     with_float_type(l.f64, [&](auto tag) {
         using T = decltype(tag);
-        const T* const b = (const T*)l.b;
-        T* const u = (T*)l.u;
-        if (s->var) launch_var_dense_solve<T>(s->var_inv, 1, &b, &u, n, l.pitch, s->stream);     // MF:63-72: x = A^-1 b, A^-1 built at set-up
-        else s->bottom.solve<T>(b, u, l.pitch, s->stream);
+        const SetPtrs<const T> b = set_ptrs<const T>(s, level, a, kB);
+        const SetPtrs<T> u = set_ptrs<T>(s, level, a, kU);
+        if (s->var) launch_var_dense_solve<T>(s->var_inv, a.m, b.p, u.p, n, l.pitch, s->stream);     // MF:63-72: x = A^-1 b, A^-1 built at set-up
+        else s->bottom.solve<T>(b.p[0], u.p[0], l.pitch, s->stream);
     });
 }
 
-int zero_u(mgx_solver* s, int level)
+// U[level] = 0 of the set's columns, one fill each
+int zero_u(mgx_solver* s, int level, const MultiSet& a = kOwnSet)
 {
-    Level& l = s->lv[level];
-    HIPCHK(s, hipMemsetAsync(l.u, 0, l.bytes, s->stream));
+    for (int j = 0; j < a.m; ++j) HIPCHK(s, hipMemsetAsync(slot(s, level, a.act[j], kU), 0, s->lv[level].bytes, s->stream));
     return MGX_OK;
 }
 
@@ -975,36 +1059,41 @@ int zero_u(mgx_solver* s, int level)
 // level is eligible for folding.  zero_in_here: this level's iterate is a known zero that nobody has written.
 // Returns whether the coarse guess is one: if the coarse level's first pass can synthesise it, nobody writes or
 // reads those zeros.
-bool descend(mgx_solver* s, int level, bool zero_in_here)
+// The walk runs on a set of columns (a; fu as for smooth).  Its shortcuts - the folded passes with their implicit zeros
+// and norm stage (smooth_folded, zero_in_ok, post = 2) and the one-workgroup visits (small_level) - are the own column's:
+// each asks own(a), and a block call runs the per-level launches on every level
+bool descend(mgx_solver* s, int level, bool zero_in_here, const MultiSet& a = kOwnSet, double* fu = nullptr)
 {
-    const bool zin_next = zero_in_ok(s, level - 1);
-    if (!smooth_folded(s, level, s->cfg.mu1, false, 1, zero_in_here, zin_next)) {
-        if (zero_in_here) (void)zero_u(s, level);             // cannot happen (zero_in_ok planned this block); stay correct
-        smooth(s, level, s->cfg.mu1);                         // PS:581
-        restrict_level(s, level, true, !zin_next);            // PS:604-613
+    const bool zin_next = own(a) && zero_in_ok(s, level - 1);
+    if (!own(a) || !smooth_folded(s, level, s->cfg.mu1, false, 1, zero_in_here, zin_next)) {
+        if (zero_in_here) (void)zero_u(s, level, a);          // cannot happen (zero_in_ok planned this block); stay correct
+        smooth(s, level, s->cfg.mu1, false, a, fu);           // PS:581
+        restrict_level(s, level, true, !zin_next, a);         // PS:604-613
     }
     return zin_next;
 }
 
 // ascend: PS:620-624 correction + PS:625 post-smoothing; post = 2: the last pass also sums r^2 per block (the
 // cycle's residual norm), else 0
-void ascend(mgx_solver* s, int level, int post)
+void ascend(mgx_solver* s, int level, int post, const MultiSet& a = kOwnSet, double* fu = nullptr)
 {
-    if (!smooth_folded(s, level, s->cfg.mu2, true, post)) {
-        prolong_level(s, level, true);                        // PS:620-624
-        smooth(s, level, s->cfg.mu2, true);                   // PS:625
+    if (!own(a) || !smooth_folded(s, level, s->cfg.mu2, true, post)) {
+        prolong_level(s, level, true, a);                     // PS:620-624
+        smooth(s, level, s->cfg.mu2, true, a, fu);            // PS:625
     }
 }
 
-void vcycle(mgx_solver* s, int level, bool zero_in_here = false, int post_top = 0, int kind = -1);
+void vcycle(mgx_solver* s, int level, bool zero_in_here = false, int post_top = 0, int kind = -1, const MultiSet& a = kOwnSet,
+            double* fu = nullptr);
 
 // Is a visit of `level` one launch of k_small_visit (mgx_small.hpp)?  Only in the W- and F-cycles of a GALERKIN handle
 // with the Jacobi smoother, on nine-point levels above the coarsest and below the finest with N <= 64: the V-cycle keeps
 // its launches and its bits, and everything else - a nine-point FINEST level too, whatever its size: it is visited once
-// per cycle, by the cycle's own entry and exit - runs W and F through the per-level launches
-bool small_level(const mgx_solver* s, int level)
+// per cycle, by the cycle's own entry and exit, and the columns of a block call, whose results are bit-identical to the
+// kernel's - runs W and F through the per-level launches
+bool small_level(const mgx_solver* s, int level, const MultiSet& a)
 {
-    if (!s->small_visit || s->cycle == MGX_CYCLE_V || !s->galerkin || !s->gal_built) return false;
+    if (!own(a) || !s->small_visit || s->cycle == MGX_CYCLE_V || !s->galerkin || !s->gal_built) return false;
     if (s->cfg.smoother != MGX_SMOOTHER_JACOBI) return false;
     if (level <= s->cfg.coarsest_level || level >= s->cfg.finest_level) return false;
     const Level& l = s->lv[level];
@@ -1044,11 +1133,11 @@ void small_visit(mgx_solver* s, int level, bool ascend, bool descend)
 // the first one left, with the same right-hand side - never from an implicit zero.  The coarsest level is visited
 // once per descent: a second exact solve would return the same vector, and bottom = SMOOTH is one visit by definition.
 // On a small level (small_level) the ascend of the first visit and the descend of the second are one launch, the turn
-void coarse_visits(mgx_solver* s, int level, bool zero_in_here, int kind)
+void coarse_visits(mgx_solver* s, int level, bool zero_in_here, int kind, const MultiSet& a = kOwnSet, double* fu = nullptr)
 {
     const bool twice = kind != MGX_CYCLE_V && level > s->cfg.coarsest_level;
     const int second = kind == MGX_CYCLE_F ? MGX_CYCLE_V : kind;
-    if (twice && small_level(s, level)) {
+    if (twice && small_level(s, level, a)) {
         small_visit(s, level, false, true);
         coarse_visits(s, level - 1, false, kind);
         small_visit(s, level, true, true);
@@ -1056,33 +1145,33 @@ void coarse_visits(mgx_solver* s, int level, bool zero_in_here, int kind)
         small_visit(s, level, true, false);
         return;
     }
-    vcycle(s, level, zero_in_here, 0, kind);                  // PS:617
-    if (twice) vcycle(s, level, false, 0, second);
+    vcycle(s, level, zero_in_here, 0, kind, a, fu);           // PS:617
+    if (twice) vcycle(s, level, false, 0, second, a, fu);
 }
 
 // zero_in_here as for descend; post_top: `post` of this level's ascend (the levels below never report the norm);
 // kind: MGX_CYCLE_*, < 0: the handle's (mgx_set_cycle)
-void vcycle(mgx_solver* s, int level, bool zero_in_here, int post_top, int kind)
+void vcycle(mgx_solver* s, int level, bool zero_in_here, int post_top, int kind, const MultiSet& a, double* fu)
 {
     if (kind < 0) kind = s->cycle;
     if (level == s->cfg.coarsest_level) {
         if (s->cfg.bottom == MGX_BOTTOM_EXACT) {
-            bottom_solve(s);                                  // MF:137-139
+            bottom_solve(s, a);                               // MF:137-139
         } else {
-            smooth(s, level, s->cfg.mu1);                     // PS:581
-            smooth(s, level, s->cfg.mu2, true);               // PS:585
+            smooth(s, level, s->cfg.mu1, false, a, fu);       // PS:581
+            smooth(s, level, s->cfg.mu2, true, a, fu);        // PS:585
         }
         return;
     }
-    if (small_level(s, level)) {                              // (general operators: zero_in_here is never set, post_top is 0)
+    if (small_level(s, level, a)) {                              // (general operators: zero_in_here is never set, post_top is 0)
         small_visit(s, level, false, true);
         coarse_visits(s, level - 1, false, kind);
         small_visit(s, level, true, false);
         return;
     }
-    const bool zin_next = descend(s, level, zero_in_here);
-    coarse_visits(s, level - 1, zin_next, kind);
-    ascend(s, level, post_top);
+    const bool zin_next = descend(s, level, zero_in_here, a, fu);
+    coarse_visits(s, level - 1, zin_next, kind, a, fu);
+    ascend(s, level, post_top, a, fu);
 }
 
 // PS:629-650 / MF:175-191 on the working hierarchy (B[finest] must be set)
@@ -2421,7 +2510,7 @@ int mgx_time_smoother(mgx_handle s, int sweeps, double* ms)
     if (int vr = var_ready(s, s->cfg.finest_level, s->cfg.finest_level)) return vr;
     Level& l = s->lv[s->cfg.finest_level];
     return time_on_stream(s, ms, [&] {
-        if (s->var) smooth_var(s, l, sweeps);
+        if (s->var) smooth_var(s, s->cfg.finest_level, kOwnSet, sweeps);
         else smooth_t(s, l, sweeps);
     });
 }
@@ -2451,8 +2540,7 @@ int mgx_time_multi_smoother(mgx_handle s, int nrhs, int sweeps, double* ms)
         return s->fail(MGX_ERR_STATE, "mgx_time_multi_smoother: call mgx_solve_multi with at least this nrhs first (it allocates the columns)");
     const MultiSet a = multi_all(nrhs);
     return time_on_stream(s, ms, [&] {
-        if (s->work_f64) multi_smooth<double>(s, s->cfg.finest_level, a, sweeps, nullptr);
-        else multi_smooth<float>(s, s->cfg.finest_level, a, sweeps, nullptr);
+        smooth_var(s, s->cfg.finest_level, a, sweeps);
     });
 }
 

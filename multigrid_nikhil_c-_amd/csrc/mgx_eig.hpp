@@ -44,7 +44,7 @@
 //   k_apply_var_multi<T, NQ, K>   out_j = A v_j, the operator read once for the set: NQ + 2 K words per point, built
 //                                 from load_rows / load_coefs / stencil_sum as k_residual_var is.  AX and AP (K = nev),
 //                                 AW (K = |act|).
-// The cycle itself runs multi_vcycle.
+// The cycle itself is the handle's one walk (vcycle) on the set of active columns.
 #pragma once
 
 #include "mgx_multi.hpp"

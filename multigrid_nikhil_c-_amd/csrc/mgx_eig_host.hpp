@@ -211,8 +211,8 @@ int eigs_t(mgx_solver* s, int nev, void* x, double* lambda, double tol, int max_
             if (!(r[j] <= tol * run.theta[j])) act.act[act.m++] = j;
         if (act.m == 0 || k == max_iters) break;
         // W_act = M R_act: the cycle from zero, R already the finest right-hand side of the columns
-        for (int i = 0; i < act.m; ++i) HIPCHK(s, hipMemsetAsync(w.u[act.act[i]], 0, l.bytes, s->stream));
-        multi_vcycle<T>(s, L, act, s->cycle, fu);
+        if (int rc = zero_u(s, L, act)) return rc;
+        vcycle(s, L, false, 0, s->cycle, act, fu);
         EigBlock bw{act.m, {}, {}}, bp{nev, {}, {}};
         for (int i = 0; i < act.m; ++i) {
             const int c = act.act[i];

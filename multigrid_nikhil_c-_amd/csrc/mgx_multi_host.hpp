@@ -1,17 +1,14 @@
 // mgx_multi_host.hpp - the host side of mgx_solve_multi and mgx_solve_multi_gcr (absent in the reference; the K-column
 // kernels are mgx_multi.hpp's).  Included by mgx.hip after mgx_krylov_host.hpp.
+// Here: the workspace of the columns (multi_ensure, multi_free*), their norms (multi_norms), which handles solve blocks
+// (multi_guard), the frame of a block solve (MultiFrame) and the block GCR.  The cycle is mgx.hip's one walk (vcycle)
+// on a MultiSet of these columns: wherever a coefficient is read the set runs one launch of the pass's K-column kernel,
+// K = m - the kernel, launch helper and geometry of mgx_solve's own pass, which is its m = 1 call (mgx_var.hpp, COLUMNS) -
+// and where none is (the bilinear transfers, the injection) the single-column kernel once per column.
 #pragma once
 
 namespace {
 
-// ---- mgx_solve_multi: the cycle of a general-operator Jacobi handle on a set of workspace columns ---------------
-// Host code only: the recursion of vcycle / coarse_visits / descend / ascend as a general-operator handle runs it
-// (fold_eligible and zero_in_ok are false there: every block is plain per-level launches, every coarse guess is zeroed by
-// the restriction), on the columns act[0 .. m) of s->multi.  W- and F-cycles go through the per-level launches on every
-// level (k_small_visit is bit-identical to them).  Wherever a coefficient is read the set runs one launch of the pass's
-// K-column kernel, K = m - the kernel, launch helper and geometry of mgx_solve's own pass, which is its m = 1 call
-// (mgx_var.hpp, COLUMNS) - and where none is (the bilinear transfers, the injection) the single-column kernel once per
-// column.  No Prof scopes: cfg.profile does not extend to the call.
 void multi_free_column(mgx_solver::MultiWs& w, int c)
 {
     auto drop = [](std::initializer_list<void**> ps) {
@@ -71,166 +68,11 @@ int multi_ensure(mgx_solver* s, int nrhs)
     return MGX_OK;
 }
 
-// the active columns of a launch: act[0 .. m), m >= 1, ascending
-struct MultiSet { int act[MGX_MAX_RHS]; int m; };
-
-inline MultiSet multi_all(int nrhs)
-{
-    MultiSet a{};
-    for (int j = 0; j < nrhs; ++j) a.act[a.m++] = j;
-    return a;
-}
-
-// the grids of the set's columns as a host array of m pointers (T may be const), what the launch_* helpers take
-template <typename T> struct SetPtrs { T* p[MGX_MAX_RHS]; };
-template <typename T, typename G> SetPtrs<T> set_ptrs(G* const* grids, const MultiSet& a)
-{
-    SetPtrs<T> o{};
-    for (int j = 0; j < a.m; ++j) o.p[j] = (T*)grids[a.act[j]];
-    return o;
-}
-
-// smooth_var_t on the set; fu (may be null): each column's fine_updates, counted as smooth() counts them
-template <typename T>
-void multi_smooth(mgx_solver* s, int level, const MultiSet& a, int mu, double* fu)
-{
-    if (mu <= 0) return;
-    const Level& l = s->lv[level];
-    auto& w = s->multi.lv[level];
-    const T om = (T)s->cfg.omega;
-    const T rc = (T)(1.0 - (double)om);
-    const VarLevel<T> v = var_level<T>(l);
-    for (int i = 0; i < mu; ++i) {
-        launch_jacobi_var<T>(v, a.m, set_ptrs<const T>(w.u, a).p, set_ptrs<const T>(w.b, a).p, set_ptrs<T>(w.tmp, a).p, rc, om, s->stream);
-        for (int j = 0; j < a.m; ++j) std::swap(w.u[a.act[j]], w.tmp[a.act[j]]);
-    }
-    if (fu && level == s->cfg.finest_level)
-        for (int j = 0; j < a.m; ++j) fu[a.act[j]] += (double)mu * (double)(l.N - 1) * (double)(l.N - 1);
-}
-
-// residual_var_t on the set.  MODE 0: r_j = b_j - A u_j into the level's r;  MODE 1: per-block sums of r_j^2 into the
-// column's partials (finest level), each reduced by k_reduce_partials in its own order into sums[column]
-template <typename T, int MODE>
-void multi_residual(mgx_solver* s, int level, const MultiSet& a)
-{
-    const Level& l = s->lv[level];
-    auto& ws = s->multi;
-    auto& w = ws.lv[level];
-    double* sums[MGX_MAX_RHS] = {};
-    for (int j = 0; j < a.m; ++j) sums[j] = ws.sums + a.act[j];
-    launch_residual_var<T, MODE>(var_level<T>(l), a.m, set_ptrs<const T>(w.u, a).p, set_ptrs<const T>(w.b, a).p,
-                                 MODE ? nullptr : set_ptrs<T>(w.r, a).p, MODE ? set_ptrs<double>(ws.part, a).p : nullptr, sums, s->stream);
-}
-
-// restrict_level(level, fused = true, zero_guess = true) on the set
-template <typename T>
-void multi_restrict(mgx_solver* s, int level, const MultiSet& a)
-{
-    const Level& f = s->lv[level];
-    const Level& c = s->lv[level - 1];
-    auto& wf = s->multi.lv[level];
-    auto& wc = s->multi.lv[level - 1];
-    const int mode = s->cfg.restrict_mode;
-    if (opdep(s)) {
-        const Launch g = make_launch(c.N, VecOf<T>::W, c.N - 1, 1);
-        const T rscale = (mode == MGX_RESTRICT_FW16) ? (T)0.25 : (T)1;
-        const dim3 grd(g.blocks), blk(kBlock);
-        with_point_count(f.nine, [&](auto nq) {
-            constexpr int MODE = decltype(nq)::value == 9 ? 2 : 1;
-            // one column: mgx_solve's kernel, not the K = 1 instance of the K-column one.  The two bodies differ
-            // (k_restrict_opdep loads the five u rows once and keeps three residual rows live, 216 / 256 VGPRs in double /
-            // float, two waves per SIMD; k_restrict_opdep_multi reloads three u rows per fine row so that K = 3, 4 do not
-            // spill, 112 / 118 VGPRs at K = 1, four waves) and which is faster has not been measured: replacing one
-            // with the other would change the speed of mgx_solve or of a block solve's last column
-            if (a.m == 1) {
-                const int j = a.act[0];
-                hipLaunchKernelGGL((k_restrict_opdep<T, MODE>), grd, blk, 0, s->stream, (const T*)wf.u[j], (const T*)wf.b[j], op9_of<T>(f), wt8_of<T>(c),
-                                   (T*)wc.b[j], (T*)wc.u[j], c.N, f.pitch, c.pitch, g.strips, rscale);
-            } else with_count<kMultiMax, 2>(a.m, [&](auto kc) {
-                constexpr int K = decltype(kc)::value;
-                hipLaunchKernelGGL((k_restrict_opdep_multi<T, MODE, K>), grd, blk, 0, s->stream, columns_in<K>(set_ptrs<const T>(wf.u, a).p),
-                                   columns_in<K>(set_ptrs<const T>(wf.b, a).p), op9_of<T>(f), wt8_of<T>(c), columns_out<K>(set_ptrs<T>(wc.b, a).p),
-                                   columns_out<K>(set_ptrs<T>(wc.u, a).p), c.N, f.pitch, c.pitch, g.strips, rscale);
-            });
-        });
-        return;
-    }
-    // the residual as a grid (the operator's grids read once for the set), then the coefficient-free transfer of each
-    // column with the single-column kernel
-    multi_residual<T, 0>(s, level, a);
-    for (int i = 0; i < a.m; ++i) {
-        const int j = a.act[i];
-        if (mode >= MGX_RESTRICT_INJECT) {
-            const double wgt = (mode == MGX_RESTRICT_INJECT4) ? 4.0 : 1.0;
-            const dim3 blk(256), grd((c.N + 255) / 256, c.N - 1);
-            hipLaunchKernelGGL((k_restrict_inject<T>), grd, blk, 0, s->stream, (const T*)wf.r[j], (T*)wc.b[j], (T*)wc.u[j], c.N, f.pitch, c.pitch, (T)wgt);
-        } else {
-            launch_restrict<T>((const T*)wf.u[j], (const T*)wf.r[j], (T*)wc.b[j], (T*)wc.u[j], f.N, f.pitch, c.pitch, 1, c.N, 0, mode, false,
-                               s->rows_per_chunk, s->stream);
-        }
-    }
-}
-
-// prolong_level(level, add = true) on the set
-template <typename T>
-void multi_prolong(mgx_solver* s, int level, const MultiSet& a)
-{
-    const Level& f = s->lv[level];
-    const Level& c = s->lv[level - 1];
-    auto& wf = s->multi.lv[level];
-    auto& wc = s->multi.lv[level - 1];
-    if (!opdep(s)) {
-        for (int i = 0; i < a.m; ++i)
-            launch_prolong<T>((T*)wf.u[a.act[i]], (const T*)wc.u[a.act[i]], f.N, f.pitch, c.pitch, 1, f.N, 0, true, s->rows_per_chunk, s->stream);
-        return;
-    }
-    launch_prolong_opdep<T>(a.m, true, set_ptrs<T>(wf.u, a).p, set_ptrs<const T>(wc.u, a).p, wt8_of<T>(c), c.N, f.pitch, c.pitch, s->stream);
-}
-
-// the visit of the coarsest level: bottom_solve, or the two blocks of bottom = SMOOTH
-template <typename T>
-void multi_bottom(mgx_solver* s, const MultiSet& a, double* fu)
-{
-    const int level = s->cfg.coarsest_level;
-    if (s->cfg.bottom != MGX_BOTTOM_EXACT) {
-        multi_smooth<T>(s, level, a, s->cfg.mu1, fu);
-        multi_smooth<T>(s, level, a, s->cfg.mu2, fu);
-        return;
-    }
-    const Level& l = s->lv[level];
-    auto& w = s->multi.lv[level];
-    launch_var_dense_solve<T>(s->var_inv, a.m, set_ptrs<const T>(w.b, a).p, set_ptrs<T>(w.u, a).p, l.N - 1, l.pitch, s->stream);
-}
-
-template <typename T> void multi_vcycle(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu);
-
-// coarse_visits on the set (no k_small_visit)
-template <typename T>
-void multi_visits(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu)
-{
-    const bool twice = kind != MGX_CYCLE_V && level > s->cfg.coarsest_level;
-    multi_vcycle<T>(s, level, a, kind, fu);
-    if (twice) multi_vcycle<T>(s, level, a, kind == MGX_CYCLE_F ? MGX_CYCLE_V : kind, fu);
-}
-
-// vcycle on the set: descend (mu1 sweeps, the residual restricted, the coarse guess zeroed), the visits of the level
-// below, ascend (the correction, mu2 sweeps)
-template <typename T>
-void multi_vcycle(mgx_solver* s, int level, const MultiSet& a, int kind, double* fu)
-{
-    if (level == s->cfg.coarsest_level) { multi_bottom<T>(s, a, fu); return; }
-    multi_smooth<T>(s, level, a, s->cfg.mu1, fu);
-    multi_restrict<T>(s, level, a);
-    multi_visits<T>(s, level - 1, a, kind, fu);
-    multi_prolong<T>(s, level, a);
-    multi_smooth<T>(s, level, a, s->cfg.mu2, fu);
-}
-
 // ||b_j - A u_j|| of the set's columns on the finest level into r[column]: one copy, one host synchronisation
 template <typename T>
 int multi_norms(mgx_solver* s, const MultiSet& a, double* r)
 {
-    multi_residual<T, 1>(s, s->cfg.finest_level, a);
+    residual_set<T, 1>(s, s->cfg.finest_level, a);
     HIPCHK(s, hipMemcpyAsync(s->multi.sums_host, s->multi.sums, MGX_MAX_RHS * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(s, hipStreamSynchronize(s->stream));
     for (int j = 0; j < a.m; ++j) r[a.act[j]] = std::sqrt(s->multi.sums_host[a.act[j]]);
@@ -346,7 +188,7 @@ int multi_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double tol, i
     for (int k = 0; k < max_cycles; ++k) {
         a = fr.active(a, tol);
         if (a.m == 0) break;
-        multi_vcycle<T>(s, L, a, s->cycle, fr.fu);
+        vcycle(s, L, false, 0, s->cycle, a, fr.fu);
         double r[MGX_MAX_RHS] = {};
         if (int rc = multi_norms<T>(s, a, r)) return rc;
         for (int i = 0; i < a.m; ++i) { fr.hist[a.act[i]].push_back(r[a.act[i]]); fr.iters[a.act[i]] = k + 1; }
@@ -354,7 +196,7 @@ int multi_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double tol, i
     return fr.finish(s->multi.lv[L].u, u, tol, stats, history, history_cap);
 }
 
-// ---- mgx_solve_multi_gcr: GcrMethod's passes (mgx_krylov_host.hpp) on the view of every active column, around multi_vcycle ----
+// ---- mgx_solve_multi_gcr: GcrMethod's passes (mgx_krylov_host.hpp) on the view of every active column, around the block cycle ----
 // the geometry of every Krylov pass, krylov_run's: the per-block partial sums set the summation order
 template <typename T> Launch multi_gcr_launch(const mgx_solver* s)
 {
@@ -435,7 +277,7 @@ int multi_gcr_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double to
     if (a.m > 0) {
         // r_j = b_j - A x_j becomes the cycle's right-hand side of the finest level for the whole solve (the caller's b is
         // on the host: nothing to restore); the scalar blocks start from zero, as GcrMethod::prepare leaves them
-        multi_residual<T, 0>(s, L, a);
+        residual_set<T, 0>(s, L, a);
         for (int i = 0; i < a.m; ++i) std::swap(w.b[a.act[i]], w.r[a.act[i]]);
         HIPCHK(s, hipMemsetAsync(ws.gsc, 0, MGX_MAX_RHS * kGcrScalars * sizeof(double), s->stream));
     }
@@ -444,9 +286,8 @@ int multi_gcr_solve_t(mgx_solver* s, int nrhs, const void* b, void* u, double to
     std::string first_break;
     for (int k = 0; k < max_iters && a.m > 0; ++k) {
         const int j = k % restart;
-        if (zero_start)
-            for (int i = 0; i < a.m; ++i) HIPCHK(s, hipMemsetAsync(w.u[a.act[i]], 0, l.bytes, s->stream));
-        multi_vcycle<T>(s, L, a, s->cycle, fr.fu);                         // z_c = M r_c, into the finest u of the column
+        if (int rc = zero_start ? zero_u(s, L, a) : MGX_OK) return rc;
+        vcycle(s, L, false, 0, s->cycle, a, fr.fu);                        // z_c = M r_c, into the finest u of the column
         multi_gcr_direction<T>(s, a, j, g);
         for (int i = 0; i < a.m; ++i) {
             const KrylovView v = krylov_view(s, a.act[i]);

@@ -2,7 +2,7 @@
 // iteration of mgx_solve_refine_gcr on up to four right-hand sides, each column bit for bit what that call returns for it.
 // Included by mgx.hip after mgx_refine_host.hpp and mgx_multi_host.hpp, whose pieces it puts together:
 //   the frame (copy in, fp64 norms, active set, copy out, statistics)    MultiFrame<double>
-//   the preconditioner: the float block cycle on the shadow's columns    multi_vcycle<float>(s->shadow, ..)
+//   the preconditioner: the float block cycle on the shadow's columns    vcycle(s->shadow, .., a, fu)
 //   the orthogonalisation, the mixed update, the reductions              gcr_orth, refine_gcr_update, krylov_reduce on
 //                                                                        krylov_view(s, c), r32 = the shadow column's b
 //   the host's reading of an iteration                                   MultiFrame::gcr_step
@@ -69,7 +69,7 @@ int multi_refine_gcr_solve(mgx_solver* s, int nrhs, const void* b, void* u, doub
     if (a.m > 0) {
         // r_c = b_c - A x_c becomes the column's finest b (mgx_solve_multi_gcr's step); before the swap, the first float
         // right-hand side of every column by the launch mgx_solve_refine_gcr makes at k = 0 - once per solve and column
-        multi_residual<double, 0>(s, L, a);
+        residual_set<double, 0>(s, L, a);
         const long cap = (long)(kGcrMaxRestart - 1) * g.blocks + 8;     // of gpart (multi_gcr_ensure)
         for (int i = 0; i < a.m; ++i) {
             const int c = a.act[i];
@@ -84,9 +84,8 @@ int multi_refine_gcr_solve(mgx_solver* s, int nrhs, const void* b, void* u, doub
     std::string first_break;
     for (int k = 0; k < max_iters && a.m > 0; ++k) {
         const int j = k % restart;
-        if (zero_start)
-            for (int i = 0; i < a.m; ++i) HIPCHK(s, hipMemsetAsync(fw.u[a.act[i]], 0, fl.bytes, s->stream));
-        multi_vcycle<float>(f, L, a, f->cycle, fr.fu);                     // z32_c = M32 r32_c, into the shadow column's finest u
+        if (int rc = zero_start ? zero_u(f, L, a) : MGX_OK) return s->fail(rc, f->err);
+        vcycle(f, L, false, 0, f->cycle, a, fr.fu);                        // z32_c = M32 r32_c, into the shadow column's finest u
         double sk[MGX_MAX_RHS] = {};
         for (int i = 0; i < a.m; ++i) sk[a.act[i]] = scale(a.act[i], k > 0 ? k - 1 : 0);
         multi_refine_direction(s, a, j, g, sk);

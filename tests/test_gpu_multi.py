@@ -225,6 +225,32 @@ def test_the_handle_is_left_as_it_was(pkg):
         assert_column((st, hist, mg.get_solution()), (st0, hist0, fresh.get_solution()), "mgx_solve after mgx_solve_multi")
 
 
+def test_block_calls_record_no_profile(pkg):
+    """cfg.profile covers the handle's own cycles: a block cycle and the block smoother timing run the same level
+    operations and open no scope, and the scopes of the next mgx_solve are those of a handle that never made the calls"""
+    L, Lc = 7, 3
+    with handle(pkg, L, Lc, "gal", "contrast10", OPERATOR, profile=1) as mg, handle(pkg, L, Lc, "gal", "contrast10", OPERATOR, profile=1) as fresh:
+        b = np.stack([rand(L, 3), rand(L, 4)])
+        u0 = np.zeros_like(b)
+        for h in (mg, fresh):
+            h.set_rhs(rand(L, 11))
+            h.set_guess(rand(L, 12))
+        mg.solve(tol=0.0, max_cycles=2)
+        p = mg.profile()
+        assert all(x > 0 for x in (sum(p["launches"]), sum(p["sweeps"]), sum(p["ms"]))), p
+        mg.profile_reset()
+        mg.solve_multi(b, u0, tol=1e-6, max_cycles=3)
+        ms = mg.time_multi_smoother(2, 4)
+        assert np.isfinite(ms) and ms > 0.0
+        p = mg.profile()
+        assert not any(p["launches"]) and not any(p["sweeps"]) and not any(p["ms"]), p
+        mg.solve(tol=0.0, max_cycles=2)
+        fresh.solve(tol=0.0, max_cycles=2)
+        p, p0 = mg.profile(), fresh.profile()
+        assert sum(p0["launches"]) > 0
+        assert p["launches"] == p0["launches"] and p["sweeps"] == p0["sweeps"], (p, p0)
+
+
 def test_a_new_operator_is_followed_and_the_workspace_grows(pkg):
     L, Lc = 7, 3
     with handle(pkg, L, Lc, "gal", "contrast10", OPERATOR) as mg:
