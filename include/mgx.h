@@ -656,6 +656,48 @@ MGX_API int mgx_solve_multi_refine_gcr(mgx_handle h, int nrhs, const void* b, vo
 MGX_API int mgx_eigs(mgx_handle h, int nev, void* x, double* lambda, double tol, int max_iters, mgx_stats* stats,
                      double* history, int history_cap);
 
+/* Up to MGX_EIGS_MAX smallest eigenpairs: mgx_eigs' iteration on blocks of at most MGX_MAX_RHS columns, each block
+ * iterating in the complement of the pairs found before it (deflation by locking; csrc/mgx_eig_many.hpp states it
+ * operation by operation).  The arguments and their layout are mgx_eigs', with nev up to MGX_EIGS_MAX:
+ *     Y = {}                                  (locked vectors, device resident, orthonormal)
+ *     while |Y| < nev:
+ *         kb = min(MGX_MAX_RHS, nev - |Y|);  X = the caller's guesses |Y| .. |Y| + kb - 1
+ *         X <- X - Y (Y^T X), twice           (once per block; skipped when Y is empty)
+ *         mgx_eigs' iteration on X, with one change: after W_act = M R_act,
+ *             W_act <- W_act - Y (Y^T W_act)  (once per iteration; skipped when Y is empty)
+ *         the block ends as mgx_eigs ends: every column meets hist <= tol theta, or after max_iters iterations, or
+ *         on its failures
+ *         if it did not end converged: stop.   else Y <- [Y, X]
+ *     sort the computed pairs by lambda ascending (stable); vectors, stats and history slots follow
+ * The projection: c_ij = Y_i . W_j in double, every sum in a fixed order, all from the unmodified W (classical
+ * Gram-Schmidt); then W_j = ((W_j - c_0j Y_0) - c_1j Y_1) - ..., i ascending over all locked vectors, c_ij rounded to the
+ * working type once, every product and difference rounded in it.  The coefficients stay on the device: two host
+ * synchronisations per iteration, as in mgx_eigs.
+ * max_iters is the budget of EACH block.  Per pair: hist_j[k] = ||A x_j - theta_j x_j|| after iteration k of the pair's
+ * own block, A applied afresh; stats[j] as in mgx_eigs, counted within that block; seconds = the whole call, the same in
+ * every computed entry.  nev <= MGX_MAX_RHS is one block without a constraint and returns, bit for bit, what mgx_eigs
+ * returns.
+ * A block that ends unconverged ends the call: its pairs come back as they stand (converged per column as in mgx_eigs),
+ * the pairs of the later blocks are not computed - x_j stays the caller's guess, lambda[j] = 0, stats[j] all zero with
+ * history_len = 0, their history slots untouched - and they stay behind the computed ones; the return value is MGX_OK
+ * and mgx_last_error names the block and the reason.  Guesses that are linearly dependent after the projection:
+ * MGX_ERR_INVALID, naming the block (nothing is written to x, lambda, stats or history).
+ * What deflation cannot promise: a block converges to the smallest pairs of the complement of Y THAT ITS GUESSES REACH,
+ * and the final order is that of the computed values - no Rayleigh-Ritz step over all nev vectors is made.  A tight
+ * cluster of eigenvalues that straddles a block boundary converges slowly (the gap behind a block is the cluster's
+ * width); an exactly degenerate pair cut by a boundary does not: the part of the eigenspace that is locked is gone from
+ * the complement, and what remains of it there is separated from the next eigenvalue by an ordinary gap.  The locked vectors are as orthonormal as the
+ * blocks' Ritz rotations leave them (|X^T X - I| of a few units of roundoff times the iteration count).
+ * Accepted and refused handles: mgx_solve_multi's.  MGX_ERR_INVALID, checked first and in this order: nev < 1 or
+ * nev > MGX_EIGS_MAX, NULL x or lambda, tol not >= 0, max_iters < 0.  The handle is left as it was: its own U, B, R, its
+ * Krylov workspaces, graphs and fine_updates are unchanged and every other entry point, mgx_eigs included, computes the
+ * same bits before and after.  Memory: mgx_eigs' workspace of one block, plus nev finest-level vectors Y, the table of
+ * their pointers and MGX_EIGS_MAX x MGX_MAX_RHS coefficients with their partial sums; allocated on first use, grown for
+ * a larger nev, freed by mgx_destroy; MGX_ERR_ALLOC leaves everything usable.  Deterministic; launched eagerly. */
+#define MGX_EIGS_MAX 16
+MGX_API int mgx_eigs_many(mgx_handle h, int nev, void* x, double* lambda, double tol, int max_iters,
+                          mgx_stats* stats, double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -732,6 +774,16 @@ MGX_API int mgx_time_multi_refine_direction(mgx_handle h, int nrhs, int repeats,
  * nev has allocated the columns; MGX_ERR_INVALID for another pass, repeats < 1, nev < 1 or nev > MGX_MAX_RHS, NULL ms. */
 enum { MGX_EIG_PASS_GRAM = 0, MGX_EIG_PASS_COMBINE = 1, MGX_EIG_PASS_RESIDUAL = 2, MGX_EIG_PASS_APPLY = 3 };
 MGX_API int mgx_time_eig_pass(mgx_handle h, int pass, int nev, int repeats, double* ms);
+/* ms per launch of one pass of mgx_eigs_many's projection of the first k workspace columns (their finest u, where the cycle
+ * leaves W) against the first m locked slots, `repeats` launches between two events (tools/eig_many_bench.py; the
+ * yardstick is mgx_time_gcr_pass, UPDATE, in the same run).  DOTS: k_eig_project_dots over all chunks of eight locked
+ * vectors with the reduction of their sums, m + k ceil(m / 8) words read per point; SUB: k_eig_project_sub, one launch, m + k
+ * read and k written, with the coefficient buffer zeroed, so W keeps its bits.  The handle's own vectors are untouched.
+ * MGX_ERR_STATE where mgx_eigs_many returns it, and until a mgx_eigs_many call with nev >= m + k has allocated the
+ * pieces; MGX_ERR_INVALID for another pass, repeats < 1, m outside 1 .. MGX_EIGS_MAX - 1, k outside 1 .. MGX_MAX_RHS,
+ * NULL ms. */
+enum { MGX_EIG_PROJECT_DOTS = 0, MGX_EIG_PROJECT_SUB = 1 };
+MGX_API int mgx_time_eig_project(mgx_handle h, int pass, int m, int k, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

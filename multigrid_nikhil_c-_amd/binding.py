@@ -58,9 +58,11 @@ EXPORTS = [
     "mgx_set_cycle", "mgx_get_cycle", "mgx_solve_refine", "mgx_time_refine_pass",
     "mgx_solve_refine_gcr", "mgx_time_refine_gcr_pass", "mgx_solve_multi", "mgx_time_multi_smoother",
     "mgx_solve_multi_gcr", "mgx_time_multi_gcr_direction", "mgx_solve_multi_refine_gcr", "mgx_time_multi_refine_direction",
-    "mgx_eigs", "mgx_time_eig_pass",
+    "mgx_eigs", "mgx_time_eig_pass", "mgx_eigs_many", "mgx_time_eig_project",
 ]
 EIG_PASS_GRAM, EIG_PASS_COMBINE, EIG_PASS_RESIDUAL, EIG_PASS_APPLY = 0, 1, 2, 3
+EIG_PROJECT_DOTS, EIG_PROJECT_SUB = 0, 1
+EIGS_MAX = 16
 MAX_RHS = 4
 MAX_GPUS = 16
 (DOP_EXCHANGE, DOP_ZERO_U, DOP_CYCLE, DOP_SMOOTH, DOP_RESTRICT, DOP_PROLONG, DOP_GATHER_CUT, DOP_COARSE, DOP_SUMSQ,
@@ -190,6 +192,8 @@ def lib() -> C.CDLL:
     L.mgx_time_multi_refine_direction.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mgx_eigs.argtypes = [vp, C.c_int, vp, dp, C.c_double, C.c_int, C.POINTER(Stats), dp, C.c_int]
     L.mgx_time_eig_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
+    L.mgx_eigs_many.argtypes = L.mgx_eigs.argtypes
+    L.mgx_time_eig_project.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
     L.mgx_profile_get.argtypes = [vp, C.POINTER(Profile)]
     L.mgx_time_smoother.argtypes = [vp, C.c_int, dp]
     L.mgx_time_gcr_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
@@ -711,6 +715,17 @@ class Multigrid:
         guesses (nev x n x n); None: uniform(-1, 1) vectors of numpy's default_rng(seed).  Returns (theta, X, stats,
         history): theta ascending, X of shape (nev, n, n) with unit 2-norm, a list of stats (cycles = preconditioner cycles
         of the column) and a list of histories of ||A x_j - theta_j x_j||."""
+        return self._eigs("mgx_eigs", nev, x0, tol, max_iters, seed)
+
+    def eigs_many(self, nev, x0=None, tol=1e-8, max_iters=100, seed=0):
+        """the nev <= EIGS_MAX smallest eigenpairs: eigs()' iteration on blocks of at most MAX_RHS columns, each block in the
+        complement of the pairs found before it (mgx_eigs_many).  Arguments and return value as eigs(); max_iters is the
+        budget of each block.  A block that does not converge ends the call: the pairs of the later blocks come back as the
+        guesses with theta = 0 and empty histories, behind the computed ones, and mgx_last_error names the block.  nev <=
+        MAX_RHS returns what eigs() returns, bit for bit."""
+        return self._eigs("mgx_eigs_many", nev, x0, tol, max_iters, seed)
+
+    def _eigs(self, fn, nev, x0, tol, max_iters, seed):
         dt = self.level_dtype(self.cfg.finest_level)
         n = self.n()
         if x0 is None:
@@ -722,8 +737,8 @@ class Multigrid:
         st = (Stats * max(nev, 1))()
         cap = max(max_iters, 0) + 1
         hist = np.zeros((max(nev, 1), cap), dtype=np.float64)
-        self._chk(lib().mgx_eigs(self._h, nev, x.ctypes.data, theta.ctypes.data_as(C.POINTER(C.c_double)), tol, max_iters, st,
-                                 hist.ctypes.data_as(C.POINTER(C.c_double)), cap), "mgx_eigs")
+        self._chk(getattr(lib(), fn)(self._h, nev, x.ctypes.data, theta.ctypes.data_as(C.POINTER(C.c_double)), tol, max_iters, st,
+                                     hist.ctypes.data_as(C.POINTER(C.c_double)), cap), fn)
         stats = []
         for j in range(nev):
             one = Stats()
@@ -736,6 +751,13 @@ class Multigrid:
         columns; after an eigs() with at least nev columns"""
         ms = C.c_double(0.0)
         self._chk(lib().mgx_time_eig_pass(self._h, which, nev, repeats, C.byref(ms)), "mgx_time_eig_pass")
+        return ms.value
+
+    def time_eig_project(self, which, m, k, repeats=20):
+        """ms per launch of pass `which` (EIG_PROJECT_DOTS / EIG_PROJECT_SUB) of eigs_many()'s projection of the first k
+        workspace columns against the first m locked vectors; after an eigs_many() with nev >= m + k"""
+        ms = C.c_double(0.0)
+        self._chk(lib().mgx_time_eig_project(self._h, which, m, k, repeats, C.byref(ms)), "mgx_time_eig_project")
         return ms.value
 
     def profile_reset(self):

@@ -39,6 +39,7 @@
 #include "mgx_refine_gcr.hpp"
 #include "mgx_multi.hpp"
 #include "mgx_eig.hpp"
+#include "mgx_eig_many.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -202,6 +203,16 @@ struct mgx_solver {
         double *gpart = nullptr, *gsum = nullptr, *gsum_host = nullptr;
         int cols = 0;
     } eig;
+    // mgx_eigs_many (mgx_eig_many_host.hpp), beyond mgx_eigs' workspace: the locked vectors Y of the finest level, the
+    // device table of their pointers, the MGX_EIGS_MAX x MGX_MAX_RHS coefficients of a projection and the per-block sums
+    // of one chunk of its dots.  Slots [0, slots) exist; allocated by the first call, grown by a larger nev, freed by
+    // mgx_destroy
+    struct EigManyWs {
+        void* Y[MGX_EIGS_MAX] = {};
+        void** ytab = nullptr;
+        double *coef = nullptr, *part = nullptr;
+        int slots = 0;
+    } eigm;
 
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -1458,6 +1469,7 @@ static int create_solver(const mgx_config* cfg, const mgx_solver* like, mgx_hand
 #include "mgx_refine_host.hpp"
 #include "mgx_multi_refine_host.hpp"
 #include "mgx_eig_host.hpp"
+#include "mgx_eig_many_host.hpp"
 
 // =====================================================================================
 // C-ABI
@@ -1695,6 +1707,7 @@ int mgx_destroy(mgx_handle s)
     s->kry.free();
     multi_free(s->multi);
     eig_free(s->eig);
+    eig_many_free(s->eigm);
     drop_graphs(s);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2585,6 +2598,31 @@ int mgx_eigs(mgx_handle s, int nev, void* x, double* lambda, double tol, int max
     if (int rc = multi_guard(s, "mgx_eigs")) return rc;
     return s->work_f64 ? eigs_t<double>(s, nev, x, lambda, tol, max_iters, stats, history, history_cap)
                        : eigs_t<float>(s, nev, x, lambda, tol, max_iters, stats, history, history_cap);
+}
+
+// ---- mgx_eigs_many: up to MGX_EIGS_MAX pairs, blocks of mgx_eigs' iteration deflated by the pairs found (mgx_eig_many.hpp) ----
+int mgx_eigs_many(mgx_handle s, int nev, void* x, double* lambda, double tol, int max_iters, mgx_stats* stats, double* history, int history_cap)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (nev < 1 || nev > MGX_EIGS_MAX) return s->fail(MGX_ERR_INVALID, "mgx_eigs_many: 1 <= nev <= MGX_EIGS_MAX required");
+    if (!x || !lambda) return s->fail(MGX_ERR_INVALID, "mgx_eigs_many: x and lambda must not be NULL");
+    if (!(tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_eigs_many: tol >= 0 required");
+    if (max_iters < 0) return s->fail(MGX_ERR_INVALID, "mgx_eigs_many: max_iters >= 0 required");
+    if (int rc = multi_guard(s, "mgx_eigs_many")) return rc;
+    return s->work_f64 ? eigs_many_t<double>(s, nev, x, lambda, tol, max_iters, stats, history, history_cap)
+                       : eigs_many_t<float>(s, nev, x, lambda, tol, max_iters, stats, history, history_cap);
+}
+
+int mgx_time_eig_project(mgx_handle s, int pass, int m, int k, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (pass < MGX_EIG_PROJECT_DOTS || pass > MGX_EIG_PROJECT_SUB || repeats < 1 || m < 1 || m > MGX_EIGS_MAX - 1 || k < 1 || k > MGX_MAX_RHS || !ms)
+        return s->fail(MGX_ERR_INVALID, "mgx_time_eig_project: a pass of MGX_EIG_PROJECT_*, repeats >= 1, 1 <= m <= MGX_EIGS_MAX - 1, 1 <= k <= MGX_MAX_RHS "
+                                        "and ms required");
+    if (int rc = multi_guard(s, "mgx_time_eig_project")) return rc;
+    if (s->eigm.slots < m + k || s->multi.cols < k)
+        return s->fail(MGX_ERR_STATE, "mgx_time_eig_project: call mgx_eigs_many with nev >= m + k first (it allocates the locked vectors and the columns)");
+    return s->work_f64 ? eig_time_project<double>(s, pass, m, k, repeats, ms) : eig_time_project<float>(s, pass, m, k, repeats, ms);
 }
 
 int mgx_time_eig_pass(mgx_handle s, int pass, int nev, int repeats, double* ms)

@@ -157,14 +157,27 @@ inline bool eig_theta_ok(const double* theta, int nev, int* which)
     return true;
 }
 
-template <typename T>
-int eigs_t(mgx_solver* s, int nev, void* x, double* lambda, double tol, int max_iters, mgx_stats* stats, double* history, int history_cap)
+// what one block of LOBPCG leaves on the host (its Ritz vectors are the workspace's X[0 .. nev), on the device)
+struct EigBlockResult {
+    std::vector<double> hist[MGX_MAX_RHS];
+    double fu[MGX_MAX_RHS] = {};
+    int cycles[MGX_MAX_RHS] = {};
+    double theta[MGX_MAX_RHS] = {};
+    bool failed = false;
+    std::string reason;
+    bool converged(int j, double tol) const { return !failed && hist[j].back() <= tol * theta[j]; }
+};
+
+// THE ITERATION of mgx_eig.hpp on the nev <= MGX_MAX_RHS host guesses x, in the workspace columns [0, nev) (which exist).
+// `who` opens every message.  project(k, columns) constrains k device columns to the space the caller iterates in: the
+// guesses twice before the first Rayleigh-Ritz step, W_act once per iteration after the cycle (mgx_eigs: nothing;
+// mgx_eigs_many: against the locked vectors, mgx_eig_many.hpp).  The stream is idle on return
+template <typename T, typename Project>
+int eig_block(EigRun<T>& run, const void* x, double tol, int max_iters, const std::string& who, Project&& project, EigBlockResult& out)
 {
     namespace de = mgx_eig_dense;
-    const auto t0 = std::chrono::steady_clock::now();
-    EigRun<T> run{s, nev, eig_geom<T>(s)};
-    if (int rc = multi_ensure(s, nev)) return rc;
-    if (int rc = eig_ensure(s, nev, run.e.g.blocks)) return rc;
+    mgx_solver* s = run.s;
+    const int nev = run.nev;
     const int L = s->cfg.finest_level;
     Level& l = s->lv[L];
     auto& ew = s->eig;
@@ -172,13 +185,15 @@ int eigs_t(mgx_solver* s, int nev, void* x, double* lambda, double tol, int max_
     const size_t nn = (size_t)(l.N - 1) * (size_t)(l.N - 1);
     for (int j = 0; j < nev; ++j)
         if (int rc = copy_in(s, l, ew.X[j], (const T*)x + (size_t)j * nn, nn)) return rc;
+    project(nev, ew.X);
+    project(nev, ew.X);
 
-    std::vector<double> hist[MGX_MAX_RHS];
-    double fu[MGX_MAX_RHS] = {};
-    int cycles[MGX_MAX_RHS] = {};
+    auto& hist = out.hist;
+    auto& fu = out.fu;
+    auto& cycles = out.cycles;
     double G[de::kMax * de::kMax], H[de::kMax * de::kMax], C[de::kMax * MGX_MAX_RHS], theta[MGX_MAX_RHS];
-    std::string reason;
-    bool failed = false;
+    std::string& reason = out.reason;
+    bool& failed = out.failed;
 
     // the initial Rayleigh-Ritz step on the guesses
     EigBlock bx{nev, {}, {}};
@@ -187,7 +202,7 @@ int eigs_t(mgx_solver* s, int nev, void* x, double* lambda, double tol, int max_
     if (int rc = run.gram_all(&bx, 1, G, H, nev)) return rc;
     de::Result rr = de::rayleigh_ritz(nev, nev, G, H, theta, C);
     if (!rr.ok)
-        return s->fail(MGX_ERR_INVALID, "mgx_eigs: the guesses are linearly dependent (or not finite): Cholesky pivot " + std::to_string(rr.pivot) +
+        return s->fail(MGX_ERR_INVALID, who + ": the guesses are linearly dependent (or not finite): Cholesky pivot " + std::to_string(rr.pivot) +
                                             " at column " + std::to_string(rr.index));
     for (int j = 0; j < nev; ++j) run.theta[j] = theta[j];
     run.combine(nev, ew.X, nev, ew.X, C);
@@ -195,7 +210,7 @@ int eigs_t(mgx_solver* s, int nev, void* x, double* lambda, double tol, int max_
     int which = 0;
     if (!eig_theta_ok(theta, nev, &which)) {
         failed = true;
-        reason = "mgx_eigs: Ritz value " + std::to_string(which) + " of the guesses is " + std::to_string(theta[which]) +
+        reason = who + ": Ritz value " + std::to_string(which) + " of the guesses is " + std::to_string(theta[which]) +
                  ", not a positive finite number: the operator is not symmetric positive definite";
     }
 
@@ -220,6 +235,7 @@ int eigs_t(mgx_solver* s, int nev, void* x, double* lambda, double tol, int max_
             bw.v[i] = w.u[c];
             bw.av[i] = ew.AW[c];
         }
+        project(act.m, bw.v);
         for (int j = 0; j < nev; ++j) { bp.v[j] = ew.P[j]; bp.av[j] = ew.AP[j]; }
         run.apply(act.m, bw.v, bw.av);
         const EigBlock blk[3] = {bx, bw, bp};
@@ -244,13 +260,13 @@ int eigs_t(mgx_solver* s, int nev, void* x, double* lambda, double tol, int max_
                          first_try.index);
         if (!rr.ok) {
             failed = true;
-            reason = "mgx_eigs: iteration " + std::to_string(k + 1) + ": the basis [X, W" + std::string(have_p ? ", P" : "") +
+            reason = who + ": iteration " + std::to_string(k + 1) + ": the basis [X, W" + std::string(have_p ? ", P" : "") +
                      "] is rank deficient with and without P (Cholesky pivot " + std::to_string(rr.pivot) + " at column " + std::to_string(rr.index) + ")";
             break;
         }
         if (!eig_theta_ok(theta, nev, &which)) {
             failed = true;
-            reason = "mgx_eigs: iteration " + std::to_string(k + 1) + ": Ritz value " + std::to_string(which) + " is " + std::to_string(theta[which]) +
+            reason = who + ": iteration " + std::to_string(k + 1) + ": Ritz value " + std::to_string(which) + " is " + std::to_string(theta[which]) +
                      ", not a positive finite number: the operator is not symmetric positive definite";
             break;
         }
@@ -274,18 +290,33 @@ int eigs_t(mgx_solver* s, int nev, void* x, double* lambda, double tol, int max_
     }
     HIPCHK(s, hipGetLastError());
     HIPCHK(s, hipStreamSynchronize(s->stream));
+    for (int j = 0; j < nev; ++j) out.theta[j] = run.theta[j];
+    return MGX_OK;
+}
+
+template <typename T>
+int eigs_t(mgx_solver* s, int nev, void* x, double* lambda, double tol, int max_iters, mgx_stats* stats, double* history, int history_cap)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    EigRun<T> run{s, nev, eig_geom<T>(s)};
+    if (int rc = multi_ensure(s, nev)) return rc;
+    if (int rc = eig_ensure(s, nev, run.e.g.blocks)) return rc;
+    EigBlockResult res;
+    if (int rc = eig_block<T>(run, x, tol, max_iters, "mgx_eigs", [](int, void* const*) {}, res)) return rc;
+    Level& l = s->lv[s->cfg.finest_level];
+    const size_t nn = (size_t)(l.N - 1) * (size_t)(l.N - 1);
     for (int j = 0; j < nev; ++j) {
-        if (int rc = copy_out(s, l, ew.X[j], (T*)x + (size_t)j * nn, nn)) return rc;
-        lambda[j] = run.theta[j];
+        if (int rc = copy_out(s, l, s->eig.X[j], (T*)x + (size_t)j * nn, nn)) return rc;
+        lambda[j] = res.theta[j];
     }
     for (int j = 0; j < nev; ++j)
-        finish_solve(stats ? stats + j : nullptr, history ? history + (size_t)j * (size_t)history_cap : nullptr, history_cap, hist[j], cycles[j],
-                     !failed && hist[j].back() <= tol * run.theta[j], t0, fu[j]);
+        finish_solve(stats ? stats + j : nullptr, history ? history + (size_t)j * (size_t)history_cap : nullptr, history_cap, res.hist[j],
+                     res.cycles[j], res.converged(j, tol), t0, res.fu[j]);
     if (stats) {
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int j = 0; j < nev; ++j) stats[j].seconds = seconds;
     }
-    if (!reason.empty()) s->err = reason;
+    if (!res.reason.empty()) s->err = res.reason;
     return MGX_OK;
 }
 

@@ -12,6 +12,8 @@
 //   -DMGX_INST_KIND=9  launch_gcr_direction_multi<T>  (mgx_multi.hpp: k_gcr_direction_multi<T, 5 | 9, 2..4>)
 //   -DMGX_INST_KIND=10 launch_refine_direction  (mgx_refine_gcr.hpp: k_refine_direction<5 | 9, 1..4>; T = double)
 //   -DMGX_INST_KIND=11 launch_eig_gram<T>, launch_eig_combine<T>, launch_eig_residual<T>, launch_eig_apply<T>  (mgx_eig.hpp)
+//   -DMGX_INST_KIND=12 launch_eig_project_dots<T>, launch_eig_project_sub<T>  (mgx_eig_many.hpp: k_eig_project_dots<T, 1..8, 1..4>,
+//                      k_eig_project_sub<T, 1..4>)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
@@ -30,6 +32,8 @@
 #include "mgx_refine_gcr.hpp"
 #elif MGX_INST_KIND == 11
 #include "mgx_eig.hpp"
+#elif MGX_INST_KIND == 12
+#include "mgx_eig_many.hpp"
 #endif
 
 namespace mgx {
@@ -75,7 +79,10 @@ template void launch_eig_combine<T_>(int, int, const T_* const*, T_* const*, con
 template void launch_eig_residual<T_>(int, const T_* const*, const T_* const*, T_* const*, double* const*, double* const*, const double*, const EigGeom&,
                                       hipStream_t);
 template void launch_eig_apply<T_>(int, bool, const T_* const*, T_* const*, const Op9<T_>&, const EigGeom&, hipStream_t);
+#elif MGX_INST_KIND == 12
+template void launch_eig_project_dots<T_>(int, int, const T_* const*, const T_* const*, double*, double*, const EigGeom&, hipStream_t);
+template void launch_eig_project_sub<T_>(int, int, const T_* const*, T_* const*, const double*, const EigGeom&, hipStream_t);
 #else
-#error "MGX_INST_KIND must be 1 .. 11"
+#error "MGX_INST_KIND must be 1 .. 12"
 #endif
 } // namespace mgx
