@@ -291,6 +291,29 @@ MGX_API int mgx_set_stencil9(mgx_handle h, int level, const void* c, const void*
  * State model, errors and ring-pointing coefficients as for mgx_set_stencil9; count != (N + 1)^2: MGX_ERR_INVALID. */
 MGX_API int mgx_set_tensor(mgx_handle h, const double* axx, const double* axy, const double* ayy, size_t count);
 
+/* ---- a zero-order term on the finest operator: handles with op = MGX_OPERATOR_GALERKIN (csrc/mgx_theta.hpp) ----------
+ * The finest operator becomes S = A0 + diag(d): A0 is what the last of mgx_set_stencil / mgx_set_coefficient /
+ * mgx_set_stencil9 / mgx_set_tensor gave, d an interior n x n grid (row-major, the handle's working type).  Like those
+ * operators d carries no h^-2: pass kappa h^2 for -div(a grad u) + kappa u, or rho h^2 / (theta dt) for a time step
+ * (mgx_theta_steps).  On the device c = c0 + d, one rounding in the working type, into slot 0 of the finest level
+ * (k_reaction_shift); the handle keeps the base centre c0 and d as two more finest-level grids, allocated by the first
+ * call before anything else is touched (MGX_ERR_ALLOC leaves operator and hierarchy usable) and freed by mgx_destroy.
+ * State model: a second call with d2 gives A0 + diag(d2), not an accumulation.  d = NULL while a term is set restores
+ * c0 bit for bit - the handle then computes the bits of one that never had a term; d = NULL with none set is MGX_OK and
+ * changes nothing (hierarchy and graphs kept; count is not looked at).  A later mgx_set_stencil / mgx_set_stencil9 /
+ * mgx_set_coefficient / mgx_set_tensor drops the term: the operator is what that call gave.  A call that changes the
+ * operator invalidates the hierarchy exactly as mgx_set_stencil does (schedules return MGX_ERR_STATE until
+ * mgx_build_galerkin[_transfer] has run; cached graphs are dropped; the float copy of the refine solvers is rebuilt by
+ * their next call).  Nothing else changes: R S P, the splittings, lambda bounds, line factors and the dense bottom inverse
+ * come from the build, mgx_get_stencil / mgx_get_stencil9 return the shifted centre in slot 0 (the operator as stored),
+ * and every solver, smoother, transfer and cycle runs on S.  Positivity of c0 + d is the caller's duty, as for
+ * mgx_set_stencil (the line smoothers report a zero pivot at the build).
+ * MGX_ERR_STATE with the reason on POISSON handles, STENCIL5 handles (their caller owns every level's stencil and adds the
+ * term there), multi-GPU and rank handles, and before the finest operator is set; MGX_ERR_INVALID for count != n * n or
+ * a NULL handle.  mgx_get_reaction reads d back; MGX_ERR_STATE when none is set. */
+MGX_API int mgx_set_reaction(mgx_handle h, const void* d, size_t count);
+MGX_API int mgx_get_reaction(mgx_handle h, void* dst, size_t count);
+
 /* ---- the prolongation of the Galerkin hierarchy (csrc/mgx_opdep.hpp) ------------------------------------------
  * BILINEAR: the weights 1, 1/2, 1/4 on every level.  OPERATOR: the operator-dependent ("black box", Alcouffe / Dendy)
  * prolongation, its weights read off the stencil (c, n, s, w, e, nw, ne, sw, se) of the fine point they belong to:
@@ -698,6 +721,39 @@ MGX_API int mgx_eigs(mgx_handle h, int nev, void* x, double* lambda, double tol,
 MGX_API int mgx_eigs_many(mgx_handle h, int nev, void* x, double* lambda, double tol, int max_iters,
                           mgx_stats* stats, double* history, int history_cap);
 
+/* ---- implicit time stepping: theta steps of  M u_t + A0 u = f  on the device (csrc/mgx_theta.hpp; absent in the
+ * reference) -----------------------------------------------------------------------------------------------------------
+ * The handle's operator is S = A0 + diag(d) with d = M / (theta dt) (mass over step, in stencil units: mgx_set_reaction).
+ * One step is
+ *     S u+ = (1 / theta) d.u - ((1 - theta) / theta) S u + g,        g = f / theta in stencil units,
+ * theta = 1 implicit Euler, theta = 1/2 Crank-Nicolson.  g: host, n * n, the working type, constant over the call's
+ * steps, may be NULL; it is uploaded once per call into a grid the handle keeps (MGX_ERR_ALLOC leaves the handle usable).
+ * Per step one launch of k_theta_rhs writes B of the finest level from U, d, g and the finest coefficients, then the
+ * chosen solver runs from the current U (the previous time level) with the caller's tol, max_iters and restart (ignored
+ * for MGX_STEP_SOLVE): mgx_solve, mgx_solve_gcr or mgx_solve_refine_gcr.  Nothing but that solver's own scalars crosses
+ * the bus between steps.  The pass, every product and sum rounded on its own in the working type T:
+ *     m = d_p * u_p
+ *     theta = 1:  b_p = m, then + g_p if g is given                       (reads no coefficient grid)
+ *     theta < 1:  q = (S u)_p, the sum of mgx_residual (CSR order, centre included, ring-pointing coefficients times the
+ *                 zero ring);  b_p = c1 * m - c0 * q, then + g_p;  c1 = (T)(1 / theta), c0 = (T)((1 - theta) / theta)
+ *                 formed in double and rounded once.
+ * Ring and padding of B stay zero.  What step k leaves in U, stats[k] and history slot k are bit for bit what the caller
+ * gets from  b = the pass on the host (S u = -mgx_residual with B = 0);  mgx_set_rhs(b);  the same solver call  on the
+ * same handle.  stats: NULL or nsteps entries; history: NULL or nsteps slots of history_cap doubles; *steps_done (may be
+ * NULL) counts the completed steps.  A step whose solve ends with converged = 0 (budget or breakdown) ends the call after
+ * that step: MGX_OK, *steps_done includes it, U is its iterate, the later stats and history slots are untouched and
+ * mgx_last_error names the step and the reason.  nsteps = 0 does nothing.  On return B holds the last step's right-hand
+ * side.  cfg.schedule is whatever the chosen solver makes of it: under MGX_STEP_SOLVE an FMG handle discards U in its
+ * first cycle - a V-schedule handle is what keeps the warm start there; the Krylov solvers ignore the schedule.
+ * MGX_ERR_INVALID, checked first and in this order: theta not in (0, 1] (NaN included), nsteps < 0, unknown solver, tol
+ * not >= 0, max_iters < 0, and for the GCR solvers restart outside 1 .. MGX_GCR_MAX_RESTART.  MGX_ERR_STATE where
+ * mgx_set_reaction returns it, when no term is set (there is no mass term to step with), before the hierarchy is built,
+ * and with MGX_STEP_REFINE_GCR wherever mgx_solve_refine_gcr returns it (F32 handles).  A time-dependent g: one call
+ * with nsteps = 1 per step. */
+enum { MGX_STEP_SOLVE = 0, MGX_STEP_GCR = 1, MGX_STEP_REFINE_GCR = 2 };
+MGX_API int mgx_theta_steps(mgx_handle h, double theta, int nsteps, const void* g, int solver, double tol, int max_iters,
+                            int restart, int* steps_done, mgx_stats* stats, double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -784,6 +840,13 @@ MGX_API int mgx_time_eig_pass(mgx_handle h, int pass, int nev, int repeats, doub
  * NULL ms. */
 enum { MGX_EIG_PROJECT_DOTS = 0, MGX_EIG_PROJECT_SUB = 1 };
 MGX_API int mgx_time_eig_project(mgx_handle h, int pass, int m, int k, int repeats, double* ms);
+/* ms per launch of mgx_theta_steps' right-hand-side pass on the handle's own buffers, `repeats` launches between two
+ * events (tools/theta_bench.py; the yardstick is k_residual_var<T, NQ, 0, 1>, one word per point fewer, through mgx_residual
+ * in the same run): k_theta_rhs<T, 5 | 9, false> for theta < 1 (NQ + 3 words in, 1 out), k_theta_rhs<T, 5, true> for
+ * theta = 1 (3 in, 1 out), with a source grid (zeros until a mgx_theta_steps call gave one).  The pass writes into the
+ * finest R: U and B keep their bits.  MGX_ERR_STATE where mgx_set_reaction returns it and when no term is set;
+ * MGX_ERR_INVALID for theta outside (0, 1], repeats < 1, NULL ms. */
+MGX_API int mgx_time_theta_rhs(mgx_handle h, double theta, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

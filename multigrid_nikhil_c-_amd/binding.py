@@ -59,7 +59,10 @@ EXPORTS = [
     "mgx_solve_refine_gcr", "mgx_time_refine_gcr_pass", "mgx_solve_multi", "mgx_time_multi_smoother",
     "mgx_solve_multi_gcr", "mgx_time_multi_gcr_direction", "mgx_solve_multi_refine_gcr", "mgx_time_multi_refine_direction",
     "mgx_eigs", "mgx_time_eig_pass", "mgx_eigs_many", "mgx_time_eig_project",
+    "mgx_set_reaction", "mgx_get_reaction", "mgx_theta_steps", "mgx_time_theta_rhs",
 ]
+STEP_SOLVE, STEP_GCR, STEP_REFINE_GCR = 0, 1, 2      # the solver of a theta step (theta_steps)
+STEP_SOLVERS = {"solve": STEP_SOLVE, "gcr": STEP_GCR, "refine_gcr": STEP_REFINE_GCR}
 EIG_PASS_GRAM, EIG_PASS_COMBINE, EIG_PASS_RESIDUAL, EIG_PASS_APPLY = 0, 1, 2, 3
 EIG_PROJECT_DOTS, EIG_PROJECT_SUB = 0, 1
 EIGS_MAX = 16
@@ -241,6 +244,10 @@ def lib() -> C.CDLL:
     L.mgx_get_line_chunks.argtypes = [vp, C.c_int, ip, ip]
     L.mgx_set_cycle.argtypes = [vp, C.c_int]
     L.mgx_get_cycle.argtypes = [vp, ip]
+    L.mgx_set_reaction.argtypes = [vp, vp, C.c_size_t]
+    L.mgx_get_reaction.argtypes = [vp, vp, C.c_size_t]
+    L.mgx_theta_steps.argtypes = [vp, C.c_double, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int, ip, C.POINTER(Stats), dp, C.c_int]
+    L.mgx_time_theta_rhs.argtypes = [vp, C.c_double, C.c_int, dp]
     _lib = L
     return L
 
@@ -463,6 +470,54 @@ class Multigrid:
         a = [np.ascontiguousarray(x, dtype=np.float64) for x in (axx, axy, ayy)]
         assert a[0].size == a[1].size == a[2].size, "axx, axy, ayy must have the same size"
         self._chk(lib().mgx_set_tensor(self._h, *[x.ctypes.data for x in a], a[0].size), "mgx_set_tensor")
+
+    def set_reaction(self, d):
+        """the zero-order term of a GALERKIN handle's finest operator: S = A0 + diag(d), d an interior n x n grid without
+        h^-2 (mgx_set_reaction); None removes it and restores A0 bit for bit.  build_galerkin() then builds the hierarchy of S"""
+        if d is None:
+            self._chk(lib().mgx_set_reaction(self._h, None, 0), "mgx_set_reaction")
+            return
+        a = np.ascontiguousarray(d, dtype=self.level_dtype(self.cfg.finest_level))
+        self._chk(lib().mgx_set_reaction(self._h, a.ctypes.data, a.size), "mgx_set_reaction")
+
+    def reaction(self):
+        """the zero-order term as set_reaction() stored it (mgx_get_reaction); raises when none is set"""
+        n = self.n()
+        a = np.empty((n, n), dtype=self.level_dtype(self.cfg.finest_level))
+        self._chk(lib().mgx_get_reaction(self._h, a.ctypes.data, a.size), "mgx_get_reaction")
+        return a
+
+    def theta_steps(self, nsteps, theta=1.0, g=None, solver="solve", tol=1e-8, max_iters=50, restart=4):
+        """nsteps theta steps of M u_t + A0 u = f on the device, from the current U (mgx_theta_steps): the handle's operator
+        is A0 + diag(d) with d = M / (theta dt) from set_reaction(), g = f / theta (n x n or None) is constant over the
+        steps, solver "solve" | "gcr" | "refine_gcr" (or a STEP_* value) solves every step warm-started with tol, max_iters
+        (and restart).  Returns (steps_done, list of stats, list of residual histories) of the completed steps; a step that
+        does not converge is the last one (mgx_last_error names it).  A V-schedule handle keeps the warm start under "solve"."""
+        dt = self.level_dtype(self.cfg.finest_level)
+        ga = None if g is None else np.ascontiguousarray(g, dtype=dt)
+        if ga is not None:
+            assert ga.size == self.n() ** 2, "g must hold n x n values"
+        k = max(int(nsteps), 1)
+        st = (Stats * k)()
+        cap = max(int(max_iters), 0) + 1
+        hist = np.zeros((k, cap), dtype=np.float64)
+        done = C.c_int(0)
+        code = STEP_SOLVERS[solver] if isinstance(solver, str) else int(solver)
+        self._chk(lib().mgx_theta_steps(self._h, theta, nsteps, None if ga is None else ga.ctypes.data, code, tol, max_iters, restart,
+                                        C.byref(done), st, hist.ctypes.data_as(C.POINTER(C.c_double)), cap), "mgx_theta_steps")
+        stats = []
+        for j in range(done.value):
+            one = Stats()
+            C.memmove(C.byref(one), C.byref(st[j]), C.sizeof(Stats))
+            stats.append(one)
+        return done.value, stats, [hist[j, : stats[j].history_len].copy() for j in range(done.value)]
+
+    def time_theta_rhs(self, theta, repeats=20):
+        """ms per launch of theta_steps' right-hand-side pass (k_theta_rhs) on the handle's own buffers, into the finest R: U
+        and B unchanged; after a set_reaction()"""
+        ms = C.c_double()
+        self._chk(lib().mgx_time_theta_rhs(self._h, theta, repeats, C.byref(ms)), "mgx_time_theta_rhs")
+        return ms.value
 
     def get_stencil(self, level, which):
         n = self.n(level)

@@ -40,6 +40,7 @@
 #include "mgx_multi.hpp"
 #include "mgx_eig.hpp"
 #include "mgx_eig_many.hpp"
+#include "mgx_theta.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -213,6 +214,14 @@ struct mgx_solver {
         double *coef = nullptr, *part = nullptr;
         int slots = 0;
     } eigm;
+    // mgx_set_reaction / mgx_theta_steps (mgx_theta_host.hpp), grids of the finest level with ring and padding zero: c0
+    // the centre of the finest operator as the last operator call gave it, d the zero-order term (A[0] = c0 + d while
+    // `set`), g the source of the theta steps.  c0 and d are allocated by the first mgx_set_reaction, g by the first
+    // mgx_theta_steps with a source; kept until mgx_destroy
+    struct ReactionWs {
+        void *c0 = nullptr, *d = nullptr, *g = nullptr;
+        bool set = false;
+    } rx;
 
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -617,9 +626,12 @@ int galerkin_build_t(mgx_solver* s, int transfer)
     return MGX_OK;
 }
 
-// a new finest operator of a GALERKIN handle: the coarse operators and every splitting are stale
+// a new finest operator of a GALERKIN handle: the coarse operators and every splitting are stale.  The operator is what
+// the call gave: a zero-order term of mgx_set_reaction is gone with the centre it was added to (mgx_set_reaction itself
+// raises the flag again after this)
 void galerkin_invalidate(mgx_solver* s)
 {
+    s->rx.set = false;
     for (int lv = s->cfg.coarsest_level; lv < s->cfg.finest_level; ++lv) s->lv[lv].stencil_set = false;
     s->lv[s->cfg.finest_level].stencil_set = true;
     s->gal_built = false;
@@ -1470,6 +1482,7 @@ static int create_solver(const mgx_config* cfg, const mgx_solver* like, mgx_hand
 #include "mgx_multi_refine_host.hpp"
 #include "mgx_eig_host.hpp"
 #include "mgx_eig_many_host.hpp"
+#include "mgx_theta_host.hpp"
 
 // =====================================================================================
 // C-ABI
@@ -1708,6 +1721,7 @@ int mgx_destroy(mgx_handle s)
     multi_free(s->multi);
     eig_free(s->eig);
     eig_many_free(s->eigm);
+    reaction_free(s->rx);
     drop_graphs(s);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2664,6 +2678,58 @@ int mgx_time_multi_refine_direction(mgx_handle s, int nrhs, int repeats, double*
         return s->fail(MGX_ERR_STATE, "mgx_time_multi_refine_direction: call mgx_solve_multi_refine_gcr with at least this nrhs first (it allocates "
                                       "the float columns and basis slot 0 of the columns)");
     return multi_refine_time_direction(s, nrhs, repeats, ms);
+}
+
+// ---- the zero-order term and implicit time stepping (mgx_theta_host.hpp) ---------------------------------------------
+int mgx_set_reaction(mgx_handle s, const void* d, size_t count)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (int rc = reaction_guard(s, "mgx_set_reaction")) return rc;
+    return set_reaction(s, d, count);
+}
+
+int mgx_get_reaction(mgx_handle s, void* dst, size_t count)
+{
+    if (!s || !dst) return MGX_ERR_INVALID;
+    if (int rc = reaction_guard(s, "mgx_get_reaction")) return rc;
+    if (!s->rx.set) return s->fail(MGX_ERR_STATE, "mgx_get_reaction: no zero-order term is set (mgx_set_reaction)");
+    return copy_out(s, s->lv[s->cfg.finest_level], s->rx.d, dst, count);
+}
+
+int mgx_theta_steps(mgx_handle s, double theta, int nsteps, const void* g, int solver, double tol, int max_iters, int restart, int* steps_done,
+                    mgx_stats* stats, double* history, int history_cap)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (steps_done) *steps_done = 0;
+    if (!(theta > 0.0 && theta <= 1.0)) return s->fail(MGX_ERR_INVALID, "mgx_theta_steps: 0 < theta <= 1 required");
+    if (nsteps < 0) return s->fail(MGX_ERR_INVALID, "mgx_theta_steps: nsteps >= 0 required");
+    if (solver < MGX_STEP_SOLVE || solver > MGX_STEP_REFINE_GCR)
+        return s->fail(MGX_ERR_INVALID, "mgx_theta_steps: solver must be MGX_STEP_SOLVE, MGX_STEP_GCR or MGX_STEP_REFINE_GCR");
+    if (!(tol >= 0.0) || max_iters < 0) return s->fail(MGX_ERR_INVALID, "mgx_theta_steps: tol >= 0 and max_iters >= 0 required");
+    if (solver != MGX_STEP_SOLVE && (restart < 1 || restart > MGX_GCR_MAX_RESTART))
+        return s->fail(MGX_ERR_INVALID, "mgx_theta_steps: 1 <= restart <= MGX_GCR_MAX_RESTART required");
+    if (int rc = reaction_guard(s, "mgx_theta_steps")) return rc;
+    if (!s->rx.set) return s->fail(MGX_ERR_STATE, "mgx_theta_steps: no zero-order term is set: there is no mass term to step with (mgx_set_reaction)");
+    if (solver == MGX_STEP_REFINE_GCR)
+        if (int rc = refine_guard(s, "mgx_theta_steps: MGX_STEP_REFINE_GCR")) return rc;
+    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
+    return theta_steps(s, theta, nsteps, g, solver, tol, max_iters, restart, steps_done, stats, history, history_cap);
+}
+
+int mgx_time_theta_rhs(mgx_handle s, double theta, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!ms || repeats < 1 || !(theta > 0.0 && theta <= 1.0))
+        return s->fail(MGX_ERR_INVALID, "mgx_time_theta_rhs: 0 < theta <= 1, repeats >= 1 and ms required");
+    if (int rc = reaction_guard(s, "mgx_time_theta_rhs")) return rc;
+    if (!s->rx.set) return s->fail(MGX_ERR_STATE, "mgx_time_theta_rhs: no zero-order term is set (mgx_set_reaction)");
+    Level& l = s->lv[s->cfg.finest_level];
+    if (int rc = ensure_r(s, l)) return rc;
+    // with a source, so that the pass reads what a step with a source reads (zeros until a mgx_theta_steps call gave one)
+    if (int rc = reaction_grid(s, &s->rx.g, "mgx_time_theta_rhs", "the source term")) return rc;
+    const int rc = time_on_stream(s, ms, [&] { for (int i = 0; i < repeats; ++i) theta_rhs(s, theta, l.u, s->rx.g, l.r); });
+    if (rc == MGX_OK) *ms /= repeats;
+    return rc;
 }
 
 // =====================================================================================

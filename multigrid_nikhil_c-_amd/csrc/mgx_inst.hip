@@ -14,6 +14,8 @@
 //   -DMGX_INST_KIND=11 launch_eig_gram<T>, launch_eig_combine<T>, launch_eig_residual<T>, launch_eig_apply<T>  (mgx_eig.hpp)
 //   -DMGX_INST_KIND=12 launch_eig_project_dots<T>, launch_eig_project_sub<T>  (mgx_eig_many.hpp: k_eig_project_dots<T, 1..8, 1..4>,
 //                      k_eig_project_sub<T, 1..4>)
+//   -DMGX_INST_KIND=13 launch_reaction_shift<T>, launch_theta_rhs<T>  (mgx_theta.hpp: k_reaction_shift, k_theta_rhs<T, 5 | 9, false>,
+//                      k_theta_rhs<T, 5, true>)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
@@ -34,6 +36,8 @@
 #include "mgx_eig.hpp"
 #elif MGX_INST_KIND == 12
 #include "mgx_eig_many.hpp"
+#elif MGX_INST_KIND == 13
+#include "mgx_theta.hpp"
 #endif
 
 namespace mgx {
@@ -82,7 +86,10 @@ template void launch_eig_apply<T_>(int, bool, const T_* const*, T_* const*, cons
 #elif MGX_INST_KIND == 12
 template void launch_eig_project_dots<T_>(int, int, const T_* const*, const T_* const*, double*, double*, const EigGeom&, hipStream_t);
 template void launch_eig_project_sub<T_>(int, int, const T_* const*, T_* const*, const double*, const EigGeom&, hipStream_t);
+#elif MGX_INST_KIND == 13
+template void launch_reaction_shift<T_>(const T_*, const T_*, T_*, int, long, hipStream_t);
+template void launch_theta_rhs<T_>(const VarLevel<T_>&, const T_*, const T_*, const T_*, T_*, double, hipStream_t);
 #else
-#error "MGX_INST_KIND must be 1 .. 12"
+#error "MGX_INST_KIND must be 1 .. 13"
 #endif
 } // namespace mgx
