@@ -754,6 +754,74 @@ enum { MGX_STEP_SOLVE = 0, MGX_STEP_GCR = 1, MGX_STEP_REFINE_GCR = 2 };
 MGX_API int mgx_theta_steps(mgx_handle h, double theta, int nsteps, const void* g, int solver, double tol, int max_iters,
                             int restart, int* steps_done, mgx_stats* stats, double* history, int history_cap);
 
+/* ---- Newton-multigrid for the semilinear problem  -div(a grad u) + kappa(x) phi(u) = f,  u = 0 on the boundary, on the
+ * device (csrc/mgx_newton.hpp; absent in the reference) -----------------------------------------------------------------
+ * Handles with op = MGX_OPERATOR_GALERKIN, on the finest level.  A0 is the finest operator without a zero-order term (what
+ * the last of mgx_set_stencil / mgx_set_coefficient / mgx_set_stencil9 / mgx_set_tensor gave), kappa an interior n x n
+ * grid in stencil units (host, row-major, the working type T: pass kappa h^2, as for mgx_set_reaction),
+ * phi(u) = p1 u + p2 u^2 + p3 u^3 with the three doubles rounded to T once, q2 = (T)(2 p2) and q3 = (T)(3 p3) formed in
+ * double and rounded once, f the finest B at entry, the guess the finest U at entry:  F(u) = A0 u + kappa phi(u) - f.
+ * The pass (k_newton_pass, one launch and one reduction; every product and sum rounded on its own in T):
+ *     v   = u                       the first evaluation
+ *     v   = u + lam * de            a trial: lam = 2^-j, de the linear solve's result
+ *     q   = (A0 v)_p                the sum of mgx_residual (CSR order, centre included, ring-pointing coefficients times
+ *                                   the zero ring)
+ *     ph  = ((p3 * v + p2) * v + p1) * v
+ *     dp  = (q3 * v + q2) * v + p1
+ *     b_p = f_p - (q + kap_p * ph)          d_p = kap_p * dp
+ * and ||F(v)||_2 = sqrt(sum b_p^2), the sum formed as mgx_residual_norm forms it: bit for bit its value for B = b, U = 0.
+ * The iteration, hist[0] = ||F(U)||, for k = 0 .. max_newton - 1 while !(hist[k] <= tol * hist[0]):
+ *     the operator becomes A0 + diag(d) (as mgx_set_reaction(d) does) and the hierarchy is rebuilt with the transfer it
+ *     was last built with;  B = b, U = 0, the chosen solver runs with lin_tol, lin_max_iters and restart (ignored for
+ *     MGX_STEP_SOLVE): lin_stats[k];  de = U;  trials lam = 1, 1/2, ... until
+ *         ||F(u + lam de)|| <= (1 - 1e-4 lam) hist[k]          (in double on the host; a NaN rejects)
+ *     at most max_backtracks halvings (0: plain Newton, every full step must pass the test);  u = u + lam de,
+ *     hist[k + 1] = its norm, step_lengths[k] = lam.
+ * A linear solve that ends with converged = 0 (budget or breakdown) does not end the call: it is an inexact Newton step
+ * that the line search guards, and lin_stats[k] reports it.  An error status of the solver ends the call with that
+ * status, mgx_last_error prefixed "mgx_newton: step k:".  A failed line search ends the call with MGX_OK and converged =
+ * 0, U the last accepted iterate; mgx_last_error names the step, the smallest lam tried and the two norms.
+ * After every accepted step the iterate, hist, lin_stats, step_lengths and the backtrack count are bit for bit what the
+ * caller gets on the same handle from: the pass on the host; mgx_set_reaction(d); mgx_build_galerkin_transfer(t);
+ * mgx_set_rhs(b), a zero guess, the same solver call, mgx_get_solution; u + lam de on the host and its norm through
+ * mgx_residual_norm with U = 0.
+ * On return U holds the iterate and B the caller's f bit for bit.  The handle's operator is A0 + diag(d_k) of the last
+ * linear solve with its hierarchy built: mgx_get_reaction returns d_k and mgx_set_reaction(h, NULL, 0) restores A0,
+ * exactly as after a caller's own mgx_set_reaction + build; a term set before the call is replaced, as a second
+ * mgx_set_reaction does.  When no iteration runs (max_newton = 0, or hist[0] <= tol * hist[0]) the operator, the
+ * hierarchy and the graphs are untouched.  Positivity of c0 + d is the caller's duty, as for mgx_set_reaction.
+ * nstats may be NULL; lin_stats and step_lengths: NULL or max_newton entries; history: NULL or history_cap doubles, the
+ * first min(history_len, history_cap) are written.
+ * Workspace: five finest-level grids (the iterate, the trial, f, kappa, the next d) and mgx_set_reaction's two, allocated
+ * before anything is touched (MGX_ERR_ALLOC leaves operator and hierarchy usable) and freed by mgx_destroy.
+ * MGX_ERR_INVALID, checked first and in this order: NULL handle or opt (outputs left alone), a p that is not finite,
+ * unknown solver, lin_tol not >= 0, lin_max_iters < 0, for the GCR solvers restart outside 1 .. MGX_GCR_MAX_RESTART, tol
+ * not >= 0, max_newton < 0, max_backtracks outside 0 .. 30, NULL kappa, count != n * n.  MGX_ERR_STATE with the reason
+ * where mgx_set_reaction returns it (POISSON, STENCIL5, multi-GPU and rank handles; finest operator not set), before the
+ * hierarchy has been built (that is how the transfer is known), and with MGX_STEP_REFINE_GCR wherever
+ * mgx_solve_refine_gcr returns it (F32 handles).  Every smoother, cycle kind, transfer, bottom and a five- or nine-point
+ * finest level are accepted: the call runs the public solvers. */
+typedef struct {
+    double p1, p2, p3;      /* phi(u) = p1 u + p2 u^2 + p3 u^3 */
+    int solver;             /* MGX_STEP_SOLVE / MGX_STEP_GCR / MGX_STEP_REFINE_GCR (the enum of mgx_theta_steps) */
+    double lin_tol;         /* the linear solver's tol, ... */
+    int lin_max_iters;      /* ... max_iters ... */
+    int restart;            /* ... and restart (GCR solvers) */
+    double tol;             /* stop when ||F|| <= tol * ||F(guess)|| */
+    int max_newton;         /* at most this many Newton steps */
+    int max_backtracks;     /* halvings per step; 0: plain Newton, every full step must pass the test */
+} mgx_newton_opts;
+typedef struct {
+    int iterations;         /* accepted Newton steps */
+    int converged;          /* hist[last] <= tol * hist[0] */
+    double initial_residual, final_residual, seconds;
+    int linear_iterations;  /* sum of lin_stats[k].cycles */
+    int backtracks;         /* rejected trials over all steps */
+    int history_len;        /* iterations + 1 */
+} mgx_newton_stats;
+MGX_API int mgx_newton(mgx_handle h, const mgx_newton_opts* opt, const void* kappa, size_t count, mgx_newton_stats* nstats,
+                       mgx_stats* lin_stats, double* step_lengths, double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -847,6 +915,14 @@ MGX_API int mgx_time_eig_project(mgx_handle h, int pass, int m, int k, int repea
  * finest R: U and B keep their bits.  MGX_ERR_STATE where mgx_set_reaction returns it and when no term is set;
  * MGX_ERR_INVALID for theta outside (0, 1], repeats < 1, NULL ms. */
 MGX_API int mgx_time_theta_rhs(mgx_handle h, double theta, int repeats, double* ms);
+/* ms per launch of mgx_newton's pass (with the reduction of its sums) on the handle's own buffers, `repeats` launches
+ * between two events (tools/newton_bench.py; the yardstick is k_residual_var<T, NQ, 0, 1> through mgx_residual in the same
+ * run): step = 0 times k_newton_pass<T, NQ, false> (NQ + 3 words in, 2 out), step = 1 <T, NQ, true> with lam = 1 (NQ + 4
+ * in, 3 out), on the iterate, f, kappa and polynomial the last mgx_newton call left and the current U as de.  The pass
+ * writes into the finest R, the trial iterate and the next d: U, B, the iterate and the operator keep their bits.
+ * MGX_ERR_STATE where mgx_set_reaction returns it and until a mgx_newton call has allocated the workspace;
+ * MGX_ERR_INVALID for another step, repeats < 1, NULL ms. */
+MGX_API int mgx_time_newton_pass(mgx_handle h, int step, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

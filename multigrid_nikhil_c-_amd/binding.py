@@ -60,6 +60,7 @@ EXPORTS = [
     "mgx_solve_multi_gcr", "mgx_time_multi_gcr_direction", "mgx_solve_multi_refine_gcr", "mgx_time_multi_refine_direction",
     "mgx_eigs", "mgx_time_eig_pass", "mgx_eigs_many", "mgx_time_eig_project",
     "mgx_set_reaction", "mgx_get_reaction", "mgx_theta_steps", "mgx_time_theta_rhs",
+    "mgx_newton", "mgx_time_newton_pass",
 ]
 STEP_SOLVE, STEP_GCR, STEP_REFINE_GCR = 0, 1, 2      # the solver of a theta step (theta_steps)
 STEP_SOLVERS = {"solve": STEP_SOLVE, "gcr": STEP_GCR, "refine_gcr": STEP_REFINE_GCR}
@@ -90,6 +91,24 @@ class Stats(C.Structure):
         ("cycles", C.c_int), ("converged", C.c_int),
         ("initial_residual", C.c_double), ("final_residual", C.c_double),
         ("seconds", C.c_double), ("fine_updates", C.c_double), ("history_len", C.c_int),
+    ]
+
+
+class NewtonOpts(C.Structure):
+    """mgx_newton_opts"""
+    _fields_ = [
+        ("p1", C.c_double), ("p2", C.c_double), ("p3", C.c_double),
+        ("solver", C.c_int), ("lin_tol", C.c_double), ("lin_max_iters", C.c_int), ("restart", C.c_int),
+        ("tol", C.c_double), ("max_newton", C.c_int), ("max_backtracks", C.c_int),
+    ]
+
+
+class NewtonStats(C.Structure):
+    """mgx_newton_stats"""
+    _fields_ = [
+        ("iterations", C.c_int), ("converged", C.c_int),
+        ("initial_residual", C.c_double), ("final_residual", C.c_double), ("seconds", C.c_double),
+        ("linear_iterations", C.c_int), ("backtracks", C.c_int), ("history_len", C.c_int),
     ]
 
 
@@ -248,6 +267,8 @@ def lib() -> C.CDLL:
     L.mgx_get_reaction.argtypes = [vp, vp, C.c_size_t]
     L.mgx_theta_steps.argtypes = [vp, C.c_double, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int, ip, C.POINTER(Stats), dp, C.c_int]
     L.mgx_time_theta_rhs.argtypes = [vp, C.c_double, C.c_int, dp]
+    L.mgx_newton.argtypes = [vp, C.POINTER(NewtonOpts), vp, C.c_size_t, C.POINTER(NewtonStats), C.POINTER(Stats), dp, dp, C.c_int]
+    L.mgx_time_newton_pass.argtypes = [vp, C.c_int, C.c_int, dp]
     _lib = L
     return L
 
@@ -517,6 +538,43 @@ class Multigrid:
         and B unchanged; after a set_reaction()"""
         ms = C.c_double()
         self._chk(lib().mgx_time_theta_rhs(self._h, theta, repeats, C.byref(ms)), "mgx_time_theta_rhs")
+        return ms.value
+
+    def newton(self, kappa, p=(0.0, 0.0, 1.0), solver="solve", lin_tol=1e-8, lin_max_iters=50, restart=4, tol=1e-10, max_newton=20,
+               max_backtracks=8):
+        """Newton-multigrid for -div(a grad u) + kappa phi(u) = f on the device (mgx_newton): phi(u) = p[0] u + p[1] u^2 +
+        p[2] u^3, kappa an interior n x n grid in stencil units (kappa h^2), f the current B, the guess the current U.  Every
+        step sets the zero-order term kappa phi'(u), rebuilds the hierarchy with its transfer, solves with solver "solve" |
+        "gcr" | "refine_gcr" (or a STEP_* value; lin_tol, lin_max_iters, restart) from a zero guess and backtracks on ||F||
+        (at most max_backtracks halvings).  Returns (NewtonStats, history of ||F||, list of the linear solves' Stats, step
+        lengths); U holds the iterate (get_solution()), B the caller's f.  A failed line search returns converged = 0
+        (mgx_last_error names it)."""
+        ka = np.ascontiguousarray(kappa, dtype=self.level_dtype(self.cfg.finest_level))
+        code = STEP_SOLVERS[solver] if isinstance(solver, str) else int(solver)
+        o = NewtonOpts(float(p[0]), float(p[1]), float(p[2]), code, lin_tol, lin_max_iters, restart, tol, max_newton, max_backtracks)
+        k = max(int(max_newton), 1)
+        st = (Stats * k)()
+        lam = np.zeros(k, dtype=np.float64)
+        hist = np.zeros(k + 1, dtype=np.float64)
+        ns = NewtonStats()
+        self._chk(lib().mgx_newton(self._h, C.byref(o), ka.ctypes.data, ka.size, C.byref(ns), st, lam.ctypes.data_as(C.POINTER(C.c_double)),
+                                   hist.ctypes.data_as(C.POINTER(C.c_double)), k + 1), "mgx_newton")
+        # one linear solve per accepted step, and one more when the call ended in a failed line search (not converged with
+        # steps left): that step's solve ran too
+        failed = not ns.converged and ns.iterations < int(max_newton)
+        stats = []
+        for j in range(ns.iterations + (1 if failed else 0)):
+            one = Stats()
+            C.memmove(C.byref(one), C.byref(st[j]), C.sizeof(Stats))
+            stats.append(one)
+        return ns, hist[: ns.history_len].copy(), stats, lam[: ns.iterations].copy()
+
+    def time_newton_pass(self, step, repeats=20):
+        """ms per launch of newton()'s pass (k_newton_pass and the reduction of its sums) on the handle's own buffers:
+        step 0 the first evaluation, 1 a trial with lam = 1; into the finest R, the trial iterate and the next d: U, B, the
+        iterate and the operator unchanged; after a newton()"""
+        ms = C.c_double()
+        self._chk(lib().mgx_time_newton_pass(self._h, int(step), repeats, C.byref(ms)), "mgx_time_newton_pass")
         return ms.value
 
     def get_stencil(self, level, which):

@@ -41,6 +41,7 @@
 #include "mgx_eig.hpp"
 #include "mgx_eig_many.hpp"
 #include "mgx_theta.hpp"
+#include "mgx_newton.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -222,6 +223,14 @@ struct mgx_solver {
         void *c0 = nullptr, *d = nullptr, *g = nullptr;
         bool set = false;
     } rx;
+    // mgx_newton (mgx_newton_host.hpp), grids of the finest level with ring and padding zero: the iterate un and the trial
+    // ut (swapped when a trial is accepted), the caller's f while B holds the step's right-hand side, kappa, and the
+    // Jacobian's diagonal term dn the pass writes (swapped with rx.d before a step's shift); p1..p3 of the last call for
+    // mgx_time_newton_pass.  Allocated by the first mgx_newton, kept until mgx_destroy
+    struct NewtonWs {
+        void *un = nullptr, *ut = nullptr, *f = nullptr, *kap = nullptr, *dn = nullptr;
+        double p1 = 0.0, p2 = 0.0, p3 = 0.0;
+    } nwt;
 
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -1483,6 +1492,7 @@ static int create_solver(const mgx_config* cfg, const mgx_solver* like, mgx_hand
 #include "mgx_eig_host.hpp"
 #include "mgx_eig_many_host.hpp"
 #include "mgx_theta_host.hpp"
+#include "mgx_newton_host.hpp"
 
 // =====================================================================================
 // C-ABI
@@ -1722,6 +1732,7 @@ int mgx_destroy(mgx_handle s)
     eig_free(s->eig);
     eig_many_free(s->eigm);
     reaction_free(s->rx);
+    newton_free(s->nwt);
     drop_graphs(s);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2728,6 +2739,44 @@ int mgx_time_theta_rhs(mgx_handle s, double theta, int repeats, double* ms)
     // with a source, so that the pass reads what a step with a source reads (zeros until a mgx_theta_steps call gave one)
     if (int rc = reaction_grid(s, &s->rx.g, "mgx_time_theta_rhs", "the source term")) return rc;
     const int rc = time_on_stream(s, ms, [&] { for (int i = 0; i < repeats; ++i) theta_rhs(s, theta, l.u, s->rx.g, l.r); });
+    if (rc == MGX_OK) *ms /= repeats;
+    return rc;
+}
+
+// ---- Newton-multigrid for -div(a grad u) + kappa phi(u) = f (mgx_newton_host.hpp) ----------------------------------------
+int mgx_newton(mgx_handle s, const mgx_newton_opts* o, const void* kappa, size_t count, mgx_newton_stats* nstats, mgx_stats* lin_stats,
+               double* step_lengths, double* history, int history_cap)
+{
+    if (!s || !o) return MGX_ERR_INVALID;
+    if (!std::isfinite(o->p1) || !std::isfinite(o->p2) || !std::isfinite(o->p3)) return s->fail(MGX_ERR_INVALID, "mgx_newton: p1, p2, p3 must be finite");
+    if (o->solver < MGX_STEP_SOLVE || o->solver > MGX_STEP_REFINE_GCR)
+        return s->fail(MGX_ERR_INVALID, "mgx_newton: solver must be MGX_STEP_SOLVE, MGX_STEP_GCR or MGX_STEP_REFINE_GCR");
+    if (!(o->lin_tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_newton: lin_tol >= 0 required");
+    if (o->lin_max_iters < 0) return s->fail(MGX_ERR_INVALID, "mgx_newton: lin_max_iters >= 0 required");
+    if (o->solver != MGX_STEP_SOLVE && (o->restart < 1 || o->restart > MGX_GCR_MAX_RESTART))
+        return s->fail(MGX_ERR_INVALID, "mgx_newton: 1 <= restart <= MGX_GCR_MAX_RESTART required");
+    if (!(o->tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_newton: tol >= 0 required");
+    if (o->max_newton < 0) return s->fail(MGX_ERR_INVALID, "mgx_newton: max_newton >= 0 required");
+    if (o->max_backtracks < 0 || o->max_backtracks > 30) return s->fail(MGX_ERR_INVALID, "mgx_newton: 0 <= max_backtracks <= 30 required");
+    if (!kappa) return s->fail(MGX_ERR_INVALID, "mgx_newton: kappa required");
+    const size_t n = ((size_t)1 << s->cfg.finest_level) - 1;
+    if (count != n * n) return s->fail(MGX_ERR_INVALID, "mgx_newton: vector length must be n*n with n = 2^finest_level - 1");
+    if (int rc = newton_guard(s, "mgx_newton")) return rc;
+    if (o->solver == MGX_STEP_REFINE_GCR)
+        if (int rc = refine_guard(s, "mgx_newton: MGX_STEP_REFINE_GCR")) return rc;
+    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
+    return newton(s, *o, kappa, count, nstats, lin_stats, step_lengths, history, history_cap);
+}
+
+int mgx_time_newton_pass(mgx_handle s, int step, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!ms || repeats < 1 || step < 0 || step > 1) return s->fail(MGX_ERR_INVALID, "mgx_time_newton_pass: step 0 or 1, repeats >= 1 and ms required");
+    if (int rc = reaction_guard(s, "mgx_time_newton_pass")) return rc;
+    if (!s->nwt.un) return s->fail(MGX_ERR_STATE, "mgx_time_newton_pass: call mgx_newton first (it allocates the workspace)");
+    Level& l = s->lv[s->cfg.finest_level];
+    if (int rc = ensure_r(s, l)) return rc;
+    const int rc = time_on_stream(s, ms, [&] { for (int i = 0; i < repeats; ++i) (void)newton_pass(s, step != 0, 1.0, l.r, nullptr); });
     if (rc == MGX_OK) *ms /= repeats;
     return rc;
 }

@@ -35,6 +35,31 @@ int reaction_grid(mgx_solver* s, void** p, const char* fn, const char* what)
     return MGX_OK;
 }
 
+// the device half of mgx_set_reaction, in two steps (c0 and d exist).  reaction_base: c0 holds the centre of A0 - copied
+// from slot 0 unless a term is set (then slot 0 is shifted and c0 already holds it).  reaction_shift: slot 0 = c0 + d from
+// the d on the device (mgx_set_reaction uploads it; mgx_newton's pass wrote it there), the hierarchy invalidated
+int reaction_base(mgx_solver* s)
+{
+    Level& l = s->lv[s->cfg.finest_level];
+    if (!s->rx.set) HIPCHK(s, hipMemcpyAsync(s->rx.c0, l.A[0], l.bytes, hipMemcpyDeviceToDevice, s->stream));
+    return MGX_OK;
+}
+
+int reaction_shift(mgx_solver* s)
+{
+    Level& l = s->lv[s->cfg.finest_level];
+    auto& w = s->rx;
+    with_float_type(l.f64, [&](auto tag) {
+        using T = decltype(tag);
+        launch_reaction_shift<T>((const T*)w.c0, (const T*)w.d, (T*)l.A[0], l.N, l.pitch, s->stream);
+    });
+    HIPCHK(s, hipGetLastError());
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    galerkin_invalidate(s);
+    w.set = true;
+    return MGX_OK;
+}
+
 int set_reaction(mgx_solver* s, const void* d, size_t count)
 {
     Level& l = s->lv[s->cfg.finest_level];
@@ -51,17 +76,9 @@ int set_reaction(mgx_solver* s, const void* d, size_t count)
     // both grids before anything is touched: a failure leaves the operator and the hierarchy as they were
     if (int rc = reaction_grid(s, &w.c0, "mgx_set_reaction", "the base centre")) return rc;
     if (int rc = reaction_grid(s, &w.d, "mgx_set_reaction", "the zero-order term")) return rc;
-    if (!w.set) HIPCHK(s, hipMemcpyAsync(w.c0, l.A[0], l.bytes, hipMemcpyDeviceToDevice, s->stream));
+    if (int rc = reaction_base(s)) return rc;
     if (int rc = copy_in(s, l, w.d, d, count)) return rc;
-    with_float_type(l.f64, [&](auto tag) {
-        using T = decltype(tag);
-        launch_reaction_shift<T>((const T*)w.c0, (const T*)w.d, (T*)l.A[0], l.N, l.pitch, s->stream);
-    });
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    galerkin_invalidate(s);
-    w.set = true;
-    return MGX_OK;
+    return reaction_shift(s);
 }
 
 // one launch of k_theta_rhs on the finest level: out <- the right-hand side of a theta step from u
