@@ -822,6 +822,49 @@ typedef struct {
 MGX_API int mgx_newton(mgx_handle h, const mgx_newton_opts* opt, const void* kappa, size_t count, mgx_newton_stats* nstats,
                        mgx_stats* lin_stats, double* step_lengths, double* history, int history_cap);
 
+/* ---- implicit time stepping of the semilinear problem  rho u_t = div(a grad u) - kappa(x) phi(u) + f,  u = 0 on the
+ * boundary, on the device (csrc/mgx_newton.hpp, csrc/mgx_newton_steps_host.hpp; absent in the reference) ---------------
+ * Handles with op = MGX_OPERATOR_GALERKIN, on the finest level; A0, kappa, phi, p1 .. p3, q2, q3 as for mgx_newton,
+ * everything in stencil units.  mass = dm = rho h^2 / (theta dt) and kappa are interior n x n grids (host, row-major, the
+ * working type T); g = f / theta in stencil units, constant over the call's steps, may be NULL.  All three are uploaded once
+ * per call into grids the handle keeps.  One theta step from the time level u (the finest U at entry) to u+ solves
+ *     G(v) = A0 v + dm.v + kappa.phi(v) - r = 0,      r = dm.u - c0 (A0 u + kappa.phi(u)) + g,
+ * c0 = (T)((1 - theta) / theta) formed in double and rounded once; theta = 1 implicit Euler, theta = 1/2 Crank-Nicolson.
+ * Per step one launch of k_newton_step_rhs writes r, every product and sum rounded on its own in T:
+ *     m = dm_p * u_p
+ *     theta = 1:  r_p = m, then + g_p if g is given                      (reads no neighbour and no coefficient grid)
+ *     theta < 1:  q = (A0 u)_p as in mgx_newton's pass;  ph = ((p3 * u + p2) * u + p1) * u;
+ *                 r_p = m - c0 * (q + kap_p * ph), then + g_p
+ * then Newton's method runs on G from u as the guess (warm start) exactly as mgx_newton runs it on F, with opt's tol,
+ * max_newton, max_backtracks, solver, lin_tol, lin_max_iters and restart; its pass is mgx_newton's with a mass term
+ * (k_newton_pass, MASS instances; v, q, ph, dp as there):
+ *     b_p = r_p - ((q + dm_p * v) + kap_p * ph)          d_p = dm_p + kap_p * dp
+ * so the Jacobian is A0 + diag(dm + kappa phi'(v)), and ||G(v)||_2 is bit for bit mgx_residual_norm of (B = b, U = 0).
+ * Between steps nothing but the solvers' own scalars and the pass norms crosses the bus.
+ * step_stats: NULL or nsteps entries, step_stats[k] what mgx_newton reports for the iteration of step k (seconds = the
+ * step's); history: NULL or nsteps slots of history_cap doubles, slot k the norms ||G|| of step k; *steps_done (may be
+ * NULL) counts the completed steps.  After every step U, step_stats[k] (all fields but seconds) and history slot k are
+ * bit for bit what the caller gets on the same handle from the host composition: the right-hand-side pass on the host;
+ * then per Newton iteration the MASS pass on the host, mgx_set_reaction(d), mgx_build_galerkin_transfer(t),
+ * mgx_set_rhs(b), a zero guess, the same solver call, mgx_get_solution; the trial u + lam de on the host and its norm
+ * through mgx_residual_norm with U = 0.
+ * A step whose Newton iteration ends with converged = 0 (budget or failed line search) ends the call after that step:
+ * MGX_OK, *steps_done includes it, U holds its last accepted iterate, the later slots are untouched and mgx_last_error
+ * names the step and the reason.  An error status of a solver ends the call with that status, mgx_last_error prefixed
+ * "mgx_newton_steps: step k:".  nsteps = 0 touches nothing: operator, hierarchy, graphs, U and B stay as they are.
+ * On return U is the last time level and B holds the last step's r.  The handle's operator is A0 + diag(d) of the last
+ * linear solve with its hierarchy built: mgx_get_reaction returns that d and mgx_set_reaction(h, NULL, 0) restores A0; a
+ * term set before the call is replaced.  (When no step ran a Newton iteration the operator is untouched, as for
+ * mgx_newton.)  Positivity of c0 + d is the caller's duty.  A time-dependent g: one call with nsteps = 1 per step.
+ * Workspace: mgx_newton's grids, the mass term and, with the first g, the source, allocated before anything is touched
+ * (MGX_ERR_ALLOC leaves operator and hierarchy usable) and freed by mgx_destroy.
+ * MGX_ERR_INVALID, checked first and in this order: NULL handle or opt (outputs left alone), mgx_newton's checks on opt in
+ * its order, theta not in (0, 1] (NaN included), nsteps < 0, NULL mass, NULL kappa, count != n * n.  MGX_ERR_STATE exactly
+ * where mgx_newton returns it.  A refused call leaves the handle usable with its bits. */
+MGX_API int mgx_newton_steps(mgx_handle h, const mgx_newton_opts* opt, double theta, int nsteps, const void* mass,
+                             const void* kappa, const void* g, size_t count, int* steps_done, mgx_newton_stats* step_stats,
+                             double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -917,12 +960,22 @@ MGX_API int mgx_time_eig_project(mgx_handle h, int pass, int m, int k, int repea
 MGX_API int mgx_time_theta_rhs(mgx_handle h, double theta, int repeats, double* ms);
 /* ms per launch of mgx_newton's pass (with the reduction of its sums) on the handle's own buffers, `repeats` launches
  * between two events (tools/newton_bench.py; the yardstick is k_residual_var<T, NQ, 0, 1> through mgx_residual in the same
- * run): step = 0 times k_newton_pass<T, NQ, false> (NQ + 3 words in, 2 out), step = 1 <T, NQ, true> with lam = 1 (NQ + 4
- * in, 3 out), on the iterate, f, kappa and polynomial the last mgx_newton call left and the current U as de.  The pass
+ * run): step = 0 times k_newton_pass<T, NQ, false, false> (NQ + 3 words in, 2 out), step = 1 <T, NQ, true, false> with lam = 1
+ * (NQ + 4 in, 3 out), on the iterate, f, kappa and polynomial the last mgx_newton call left and the current U as de.  The pass
  * writes into the finest R, the trial iterate and the next d: U, B, the iterate and the operator keep their bits.
  * MGX_ERR_STATE where mgx_set_reaction returns it and until a mgx_newton call has allocated the workspace;
  * MGX_ERR_INVALID for another step, repeats < 1, NULL ms. */
 MGX_API int mgx_time_newton_pass(mgx_handle h, int step, int repeats, double* ms);
+/* ms per launch of mgx_newton_steps' passes on the handle's own buffers, `repeats` launches between two events
+ * (tools/newton_steps_bench.py; the yardstick is k_residual_var<T, NQ, 0, 1> through mgx_residual in the same run):
+ * pass = 0 times k_newton_step_rhs (theta < 1: <T, NQ, false>, NQ + 4 words in, 1 out; theta = 1: <T, 5, true>, 3 in, 1
+ * out) with a source grid (zeros until a mgx_newton_steps call gave one); pass = 1 k_newton_pass<T, NQ, false, true> with
+ * its reduction (NQ + 4 in, 2 out); pass = 2 <T, NQ, true, true> with lam = 1 (NQ + 5 in, 3 out); theta is read by pass 0
+ * only.  They run on the time level, r, mass, kappa and polynomial the last mgx_newton_steps call left and the current U
+ * as de, and write into the finest R, the trial iterate and the next d: U, B, the time level and the operator are
+ * unchanged.  MGX_ERR_STATE where mgx_set_reaction returns it and until a mgx_newton_steps call has allocated the
+ * workspace; MGX_ERR_INVALID for pass outside 0 .. 2, theta outside (0, 1], repeats < 1, NULL ms. */
+MGX_API int mgx_time_newton_step_pass(mgx_handle h, int pass, double theta, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

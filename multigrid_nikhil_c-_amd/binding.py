@@ -60,7 +60,7 @@ EXPORTS = [
     "mgx_solve_multi_gcr", "mgx_time_multi_gcr_direction", "mgx_solve_multi_refine_gcr", "mgx_time_multi_refine_direction",
     "mgx_eigs", "mgx_time_eig_pass", "mgx_eigs_many", "mgx_time_eig_project",
     "mgx_set_reaction", "mgx_get_reaction", "mgx_theta_steps", "mgx_time_theta_rhs",
-    "mgx_newton", "mgx_time_newton_pass",
+    "mgx_newton", "mgx_time_newton_pass", "mgx_newton_steps", "mgx_time_newton_step_pass",
 ]
 STEP_SOLVE, STEP_GCR, STEP_REFINE_GCR = 0, 1, 2      # the solver of a theta step (theta_steps)
 STEP_SOLVERS = {"solve": STEP_SOLVE, "gcr": STEP_GCR, "refine_gcr": STEP_REFINE_GCR}
@@ -269,6 +269,8 @@ def lib() -> C.CDLL:
     L.mgx_time_theta_rhs.argtypes = [vp, C.c_double, C.c_int, dp]
     L.mgx_newton.argtypes = [vp, C.POINTER(NewtonOpts), vp, C.c_size_t, C.POINTER(NewtonStats), C.POINTER(Stats), dp, dp, C.c_int]
     L.mgx_time_newton_pass.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.mgx_newton_steps.argtypes = [vp, C.POINTER(NewtonOpts), C.c_double, C.c_int, vp, vp, vp, C.c_size_t, ip, C.POINTER(NewtonStats), dp, C.c_int]
+    L.mgx_time_newton_step_pass.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp]
     _lib = L
     return L
 
@@ -575,6 +577,43 @@ class Multigrid:
         iterate and the operator unchanged; after a newton()"""
         ms = C.c_double()
         self._chk(lib().mgx_time_newton_pass(self._h, int(step), repeats, C.byref(ms)), "mgx_time_newton_pass")
+        return ms.value
+
+    def newton_steps(self, nsteps, mass, kappa, p=(0.0, 0.0, 1.0), theta=1.0, g=None, solver="solve", lin_tol=1e-8, lin_max_iters=50, restart=4,
+                     tol=1e-8, max_newton=20, max_backtracks=8):
+        """nsteps theta steps of rho u_t = div(a grad u) - kappa phi(u) + f on the device, from the current U
+        (mgx_newton_steps): mass = rho h^2 / (theta dt) and kappa interior n x n grids in stencil units, phi as for newton(),
+        g = f / theta (n x n or None) constant over the steps.  Every step forms its explicit part in one pass and runs
+        Newton's method from the previous time level with newton()'s options.  Returns (steps_done, list of NewtonStats,
+        list of histories of ||G||) of the completed steps; a step whose iteration does not converge is the last one
+        (mgx_last_error names it).  U holds the last time level, B the last step's right-hand side."""
+        dt = self.level_dtype(self.cfg.finest_level)
+        ma, ka = np.ascontiguousarray(mass, dtype=dt), np.ascontiguousarray(kappa, dtype=dt)
+        ga = None if g is None else np.ascontiguousarray(g, dtype=dt)
+        assert ma.size == ka.size and (ga is None or ga.size == ka.size), "mass, kappa and g must hold n x n values each"
+        code = STEP_SOLVERS[solver] if isinstance(solver, str) else int(solver)
+        o = NewtonOpts(float(p[0]), float(p[1]), float(p[2]), code, lin_tol, lin_max_iters, restart, tol, max_newton, max_backtracks)
+        k = max(int(nsteps), 1)
+        cap = max(int(max_newton), 0) + 1
+        st = (NewtonStats * k)()
+        hist = np.zeros((k, cap), dtype=np.float64)
+        done = C.c_int(0)
+        self._chk(lib().mgx_newton_steps(self._h, C.byref(o), theta, nsteps, ma.ctypes.data, ka.ctypes.data, None if ga is None else ga.ctypes.data,
+                                         ka.size, C.byref(done), st, hist.ctypes.data_as(C.POINTER(C.c_double)), cap), "mgx_newton_steps")
+        stats = []
+        for j in range(done.value):
+            one = NewtonStats()
+            C.memmove(C.byref(one), C.byref(st[j]), C.sizeof(NewtonStats))
+            stats.append(one)
+        return done.value, stats, [hist[j, : stats[j].history_len].copy() for j in range(done.value)]
+
+    def time_newton_step_pass(self, which, theta=0.5, repeats=20):
+        """ms per launch of newton_steps()' passes on the handle's own buffers: which = 0 the right-hand-side pass
+        (k_newton_step_rhs, theta = 1 its Euler instance), 1 the first evaluation with the mass term, 2 a trial with lam = 1
+        (k_newton_pass and the reduction of its sums); into the finest R, the trial iterate and the next d: U, B, the time
+        level and the operator unchanged; after a newton_steps()"""
+        ms = C.c_double()
+        self._chk(lib().mgx_time_newton_step_pass(self._h, int(which), theta, repeats, C.byref(ms)), "mgx_time_newton_step_pass")
         return ms.value
 
     def get_stencil(self, level, which):

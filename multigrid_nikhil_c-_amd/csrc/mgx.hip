@@ -226,9 +226,11 @@ struct mgx_solver {
     // mgx_newton (mgx_newton_host.hpp), grids of the finest level with ring and padding zero: the iterate un and the trial
     // ut (swapped when a trial is accepted), the caller's f while B holds the step's right-hand side, kappa, and the
     // Jacobian's diagonal term dn the pass writes (swapped with rx.d before a step's shift); p1..p3 of the last call for
-    // mgx_time_newton_pass.  Allocated by the first mgx_newton, kept until mgx_destroy
+    // mgx_time_newton_pass.  Allocated by the first mgx_newton, kept until mgx_destroy.  mgx_newton_steps
+    // (mgx_newton_steps_host.hpp) runs on the same grids - un the time level, f the step's r - and adds the mass term dm
+    // and, with its first source, g
     struct NewtonWs {
-        void *un = nullptr, *ut = nullptr, *f = nullptr, *kap = nullptr, *dn = nullptr;
+        void *un = nullptr, *ut = nullptr, *f = nullptr, *kap = nullptr, *dn = nullptr, *dm = nullptr, *g = nullptr;
         double p1 = 0.0, p2 = 0.0, p3 = 0.0;
     } nwt;
 
@@ -1493,6 +1495,7 @@ static int create_solver(const mgx_config* cfg, const mgx_solver* like, mgx_hand
 #include "mgx_eig_many_host.hpp"
 #include "mgx_theta_host.hpp"
 #include "mgx_newton_host.hpp"
+#include "mgx_newton_steps_host.hpp"
 
 // =====================================================================================
 // C-ABI
@@ -2748,16 +2751,7 @@ int mgx_newton(mgx_handle s, const mgx_newton_opts* o, const void* kappa, size_t
                double* step_lengths, double* history, int history_cap)
 {
     if (!s || !o) return MGX_ERR_INVALID;
-    if (!std::isfinite(o->p1) || !std::isfinite(o->p2) || !std::isfinite(o->p3)) return s->fail(MGX_ERR_INVALID, "mgx_newton: p1, p2, p3 must be finite");
-    if (o->solver < MGX_STEP_SOLVE || o->solver > MGX_STEP_REFINE_GCR)
-        return s->fail(MGX_ERR_INVALID, "mgx_newton: solver must be MGX_STEP_SOLVE, MGX_STEP_GCR or MGX_STEP_REFINE_GCR");
-    if (!(o->lin_tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_newton: lin_tol >= 0 required");
-    if (o->lin_max_iters < 0) return s->fail(MGX_ERR_INVALID, "mgx_newton: lin_max_iters >= 0 required");
-    if (o->solver != MGX_STEP_SOLVE && (o->restart < 1 || o->restart > MGX_GCR_MAX_RESTART))
-        return s->fail(MGX_ERR_INVALID, "mgx_newton: 1 <= restart <= MGX_GCR_MAX_RESTART required");
-    if (!(o->tol >= 0.0)) return s->fail(MGX_ERR_INVALID, "mgx_newton: tol >= 0 required");
-    if (o->max_newton < 0) return s->fail(MGX_ERR_INVALID, "mgx_newton: max_newton >= 0 required");
-    if (o->max_backtracks < 0 || o->max_backtracks > 30) return s->fail(MGX_ERR_INVALID, "mgx_newton: 0 <= max_backtracks <= 30 required");
+    if (int rc = newton_opts_check(s, o, "mgx_newton")) return rc;
     if (!kappa) return s->fail(MGX_ERR_INVALID, "mgx_newton: kappa required");
     const size_t n = ((size_t)1 << s->cfg.finest_level) - 1;
     if (count != n * n) return s->fail(MGX_ERR_INVALID, "mgx_newton: vector length must be n*n with n = 2^finest_level - 1");
@@ -2776,7 +2770,49 @@ int mgx_time_newton_pass(mgx_handle s, int step, int repeats, double* ms)
     if (!s->nwt.un) return s->fail(MGX_ERR_STATE, "mgx_time_newton_pass: call mgx_newton first (it allocates the workspace)");
     Level& l = s->lv[s->cfg.finest_level];
     if (int rc = ensure_r(s, l)) return rc;
-    const int rc = time_on_stream(s, ms, [&] { for (int i = 0; i < repeats; ++i) (void)newton_pass(s, step != 0, 1.0, l.r, nullptr); });
+    const int rc = time_on_stream(s, ms, [&] { for (int i = 0; i < repeats; ++i) (void)newton_pass(s, step != 0, 1.0, nullptr, l.r, nullptr); });
+    if (rc == MGX_OK) *ms /= repeats;
+    return rc;
+}
+
+// ---- implicit time stepping of rho u_t = div(a grad u) - kappa phi(u) + f (mgx_newton_steps_host.hpp) ------------------
+int mgx_newton_steps(mgx_handle s, const mgx_newton_opts* o, double theta, int nsteps, const void* mass, const void* kappa, const void* g,
+                     size_t count, int* steps_done, mgx_newton_stats* step_stats, double* history, int history_cap)
+{
+    if (!s || !o) return MGX_ERR_INVALID;
+    if (steps_done) *steps_done = 0;
+    if (int rc = newton_opts_check(s, o, "mgx_newton_steps")) return rc;
+    if (!(theta > 0.0 && theta <= 1.0)) return s->fail(MGX_ERR_INVALID, "mgx_newton_steps: 0 < theta <= 1 required");
+    if (nsteps < 0) return s->fail(MGX_ERR_INVALID, "mgx_newton_steps: nsteps >= 0 required");
+    if (!mass) return s->fail(MGX_ERR_INVALID, "mgx_newton_steps: mass required");
+    if (!kappa) return s->fail(MGX_ERR_INVALID, "mgx_newton_steps: kappa required");
+    const size_t n = ((size_t)1 << s->cfg.finest_level) - 1;
+    if (count != n * n) return s->fail(MGX_ERR_INVALID, "mgx_newton_steps: vector length must be n*n with n = 2^finest_level - 1");
+    if (int rc = newton_guard(s, "mgx_newton_steps")) return rc;
+    if (o->solver == MGX_STEP_REFINE_GCR)
+        if (int rc = refine_guard(s, "mgx_newton_steps: MGX_STEP_REFINE_GCR")) return rc;
+    if (int vr = var_ready(s, s->cfg.coarsest_level, s->cfg.finest_level)) return vr;
+    if (nsteps == 0) return MGX_OK;                           // nothing is touched, the workspace included
+    return newton_steps(s, *o, theta, nsteps, mass, kappa, g, count, steps_done, step_stats, history, history_cap);
+}
+
+int mgx_time_newton_step_pass(mgx_handle s, int pass, double theta, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!ms || repeats < 1 || pass < 0 || pass > 2 || !(theta > 0.0 && theta <= 1.0))
+        return s->fail(MGX_ERR_INVALID, "mgx_time_newton_step_pass: pass 0, 1 or 2, 0 < theta <= 1, repeats >= 1 and ms required");
+    if (int rc = reaction_guard(s, "mgx_time_newton_step_pass")) return rc;
+    if (!s->nwt.dm) return s->fail(MGX_ERR_STATE, "mgx_time_newton_step_pass: call mgx_newton_steps first (it allocates the workspace)");
+    Level& l = s->lv[s->cfg.finest_level];
+    if (int rc = ensure_r(s, l)) return rc;
+    // with a source, so that pass 0 reads what a step with a source reads (zeros until a mgx_newton_steps call gave one)
+    if (int rc = reaction_grid(s, &s->nwt.g, "mgx_time_newton_step_pass", "the source term")) return rc;
+    const int rc = time_on_stream(s, ms, [&] {
+        for (int i = 0; i < repeats; ++i) {
+            if (pass == 0) newton_step_rhs(s, theta, s->nwt.un, s->nwt.g, l.r);
+            else (void)newton_pass(s, pass == 2, 1.0, s->nwt.dm, l.r, nullptr);
+        }
+    });
     if (rc == MGX_OK) *ms /= repeats;
     return rc;
 }

@@ -16,7 +16,8 @@
 //                      k_eig_project_sub<T, 1..4>)
 //   -DMGX_INST_KIND=13 launch_reaction_shift<T>, launch_theta_rhs<T>  (mgx_theta.hpp: k_reaction_shift, k_theta_rhs<T, 5 | 9, false>,
 //                      k_theta_rhs<T, 5, true>)
-//   -DMGX_INST_KIND=14 launch_newton_pass<T>  (mgx_newton.hpp: k_newton_pass<T, 5 | 9, false | true>)
+//   -DMGX_INST_KIND=14 launch_newton_pass<T>, launch_newton_step_rhs<T>  (mgx_newton.hpp: k_newton_pass<T, 5 | 9, STEP, MASS> with both
+//                      flags false | true, k_newton_step_rhs<T, 5 | 9, false>, k_newton_step_rhs<T, 5, true>)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
@@ -93,8 +94,10 @@ template void launch_eig_project_sub<T_>(int, int, const T_* const*, T_* const*,
 template void launch_reaction_shift<T_>(const T_*, const T_*, T_*, int, long, hipStream_t);
 template void launch_theta_rhs<T_>(const VarLevel<T_>&, const T_*, const T_*, const T_*, T_*, double, hipStream_t);
 #elif MGX_INST_KIND == 14
-template void launch_newton_pass<T_>(const VarLevel<T_>&, bool, const T_*, const T_*, const T_*, const T_*, const T_*, T_*, T_*, T_*,
+template void launch_newton_pass<T_>(const VarLevel<T_>&, bool, const T_*, const T_*, const T_*, const T_*, const T_*, const T_*, T_*, T_*, T_*,
                                      const NewtonPoly<T_>&, double*, double*, hipStream_t);
+template void launch_newton_step_rhs<T_>(const VarLevel<T_>&, const T_*, const T_*, const T_*, const T_*, const T_*, T_*, const NewtonPoly<T_>&,
+                                         double, hipStream_t);
 #else
 #error "MGX_INST_KIND must be 1 .. 14"
 #endif
