@@ -42,7 +42,33 @@ solve_refine_gcr (mgx_solve_refine_gcr) is tests/refine_gcr_ref.py's loop around
 cycle of THE SAME float model: a solve_refine and a solve_refine_gcr share it, either one rebuilds it.  The loop's residual
 lives in vectors of its own, so B stays the caller's and the coarse levels stay untouched, as for solve_refine; U of the
 finest level is x, also after a breakdown.  time_refine_gcr_pass moves nothing and refuses where the device's guard does:
-until a float model (solve_refine or solve_refine_gcr) AND a GCR basis (solve_gcr or solve_refine_gcr) exist."""
+until a float model (solve_refine or solve_refine_gcr) AND a GCR basis (solve_gcr or solve_refine_gcr) exist.
+
+set_reaction / get_reaction (mgx_set_reaction, mgx_get_reaction; GALERKIN handles) keep the base centre c0 and the term d beside
+the finest operator, whose slot 0 is tests/theta_ref.py's shift: c0 + d, one rounding in the working type.  A second call
+replaces the term; None with a term set restores c0 bit for bit, None with none set changes nothing - the hierarchy stays
+valid; set_stencil, set_stencil9, set_coefficient and set_tensor drop the term, so a later None brings no old centre back.
+Every call that changes the operator leaves the hierarchy invalid until build_galerkin, as set_stencil does.  The float model
+of solve_refine is handed the float32 of the STORED centre - c0 + d rounded in double, then to float - because it copies
+slot 0 as it stands.  Refused where the device returns MGX_ERR_STATE (RuntimeError): POISSON, STENCIL5, operator not set,
+get_reaction with no term.  The line smoothers are not modelled here (ValueError).
+
+theta_steps (mgx_theta_steps) forms theta_ref.rhs_pass from the model's own S u (minus its residual against a zero right-hand
+side) into B of the finest level and runs the model's solve, solve_gcr or solve_refine_gcr from the current U, step by step:
+per-step statistics and histories and steps_done; a step with converged = 0 ends the call after that step, nsteps = 0 moves
+nothing.  time_theta_rhs moves nothing and is refused while no term is set.
+
+newton and newton_steps (mgx_newton, mgx_newton_steps) run the loops of tests/newton_ref.py and tests/newton_steps_ref.py with
+A0 = base_operator() - a caller's term is no part of F - around the model's own linear solve: set_reaction(d), build_galerkin
+with the transfer in use, set_rhs(b), a zero U and the chosen solver; the norm is the model's residual norm of (B = b,
+U = 0).  On return U is the last accepted iterate and B the caller's f (newton) or the last step's r (newton_steps); the
+operator is A0 + diag(d_k) of the last linear solve with its hierarchy built, and the coarse levels hold what that solve
+left.  When no iteration runs (max_newton = 0, nsteps = 0, or the first norm passes the tolerance) operator, hierarchy and
+every level stay as they were (newton_steps with steps but no iteration leaves r in B).  A failed line search: failed,
+converged = 0, U the last accepted iterate.  norms and lin keep every norm and every linear solve's record of the last call:
+tests/test_handle_model_newton.py replays the Armijo and stop decisions from them.  time_newton_pass and time_newton_step_pass
+move nothing and are refused until a newton (any newton_steps with nsteps > 0) or a newton_steps call has allocated their
+workspace, as the guards of csrc/mgx.hip read."""
 import numpy as np
 
 import cheby_ref
@@ -50,11 +76,14 @@ import colour_ref as cf
 import galerkin_ref as gr
 import gcr_ref
 import line_ref as lr
+import newton_ref as nf
+import newton_steps_ref as nsr
 import nine_ref as nr
 import opdep_ref as od
 import pcg_ref
 import refine_gcr_ref
 import refine_ref
+import theta_ref as tr
 
 JACOBI, RBGS, CHEBYSHEV = 0, 1, 2
 LINE_X, LINE_Y, LINE_ALT = lr.LINE_X, lr.LINE_Y, lr.LINE_ALT
@@ -69,6 +98,7 @@ EXACT, SMOOTH = 0, 1
 SEPARATE, FMA = 0, 1
 POISSON, STENCIL5, GALERKIN = 0, 1, 3
 BILINEAR, OPERATOR = 0, 1
+STEP_SOLVE, STEP_GCR, STEP_REFINE_GCR = 0, 1, 2    # the solver of mgx_theta_steps / mgx_newton / mgx_newton_steps
 
 DEFAULTS = dict(finest_level=10, coarsest_level=7, mu0=30, mu1=10, mu2=10, omega=2.0 / 3.0, smoother=JACOBI, dtype=F64,
                 schedule=FMG, restrict_mode=CONSISTENT, bottom=EXACT, arith=SEPARATE, op=POISSON)      # mgx_config_default
@@ -205,6 +235,12 @@ class HandleModel:
         self.f32 = None                        # solve_refine: the float model, created by the first call ...
         self.f32_of = None                     # ... and the hierarchy (self.h at the time) whose float copy it holds
         self.basis = False                     # slot 0 of the GCR basis exists: after a solve_gcr or a solve_refine_gcr
+        self.c0 = None                         # set_reaction: the base centre (slot 0 of A0) while a term is set ...
+        self.d = None                          # ... and the term; None: no term is set (the device's rx.set is lowered)
+        self.nwt = False                       # mgx_newton's workspace exists: after a newton or a newton_steps with nsteps > 0
+        self.nwt_mass = False                  # ... and its mass grid: after a newton_steps with nsteps > 0
+        self.norms = []                        # every norm of the last newton / newton_steps call, in the order formed ...
+        self.lin = []                          # ... and (stats, history) of every linear solve it ran
         if self.op == POISSON:
             self.h = PoissonOps(self.po, self.L, self.Lc, self.dt, c["restrict_mode"], c["omega"], c["smoother"], c["arith"])
 
@@ -269,6 +305,7 @@ class HandleModel:
             self.st5, self.st9 = self._w(self.oracle.stencil_from_nodes(a, self.L, self.L)), None
             self.h = None
             self.transfer = None
+            self.c0 = self.d = None             # the term is gone with the centre it was added to
         else:
             raise RuntimeError("op = POISSON: MGX_ERR_STATE")
 
@@ -284,6 +321,7 @@ class HandleModel:
             self.st5, self.st9 = self._w(st5), None
             self.h = None
             self.transfer = None
+            self.c0 = self.d = None
         else:
             raise RuntimeError("MGX_ERR_STATE")
 
@@ -297,6 +335,7 @@ class HandleModel:
         self.st5, self.st9 = None, self._w(st9)
         self.h = None
         self.transfer = None
+        self.c0 = self.d = None
 
     def set_stencil9(self, level, st9):
         """mgx_set_stencil9: the finest level of a GALERKIN handle becomes nine-point; invalid until build_galerkin"""
@@ -627,3 +666,211 @@ class HandleModel:
         self._refine_guard()
         if self.f32 is None or not self.basis:
             raise ValueError("mgx_time_refine_gcr_pass: call mgx_solve_refine_gcr first")
+
+    # -- mgx_set_reaction / mgx_get_reaction -------------------------------------------------------------------
+    def _reaction_guard(self):
+        """the handles that carry no zero-order term (the device: MGX_ERR_STATE), and the line smoothers, which stay out
+        of the model here as under a nine-point finest level"""
+        if self.op != GALERKIN:
+            raise RuntimeError("zero-order terms: GALERKIN handles only (POISSON, STENCIL5: MGX_ERR_STATE)")
+        if self.line:
+            raise ValueError("a zero-order term under a line smoother is not modelled")
+        if self.st5 is None and self.st9 is None:
+            raise RuntimeError("finest operator not set: MGX_ERR_STATE")
+
+    def _finest(self):
+        """the finest operator as stored: five or nine arrays, slot 0 the (shifted) centre"""
+        return self.st9 if self.st9 is not None else self.st5
+
+    def base_operator(self):
+        """A0 as nine arrays: the finest operator without the term (slot 0 is c0 while one is set)"""
+        st9 = list(self.st9) if self.st9 is not None else gr.nine(self.st5[:5])
+        return st9 if self.d is None else [self.c0] + st9[1:]
+
+    def set_reaction(self, d):
+        """mgx_set_reaction: slot 0 of the finest operator becomes c0 + d (theta_ref.shift: one rounding in the working
+        type); a second call replaces the term.  None with a term set restores c0, None with none set changes nothing.
+        Every call that changes the operator leaves the hierarchy invalid until build_galerkin, as set_stencil does"""
+        self._reaction_guard()
+        st = self._finest()
+        if d is None:
+            if self.d is None:
+                return                          # nothing to remove: the hierarchy stays valid
+            st[0] = self.c0
+            self.c0 = self.d = None
+        else:
+            d = np.array(d, dtype=self.wdt, order="C")
+            if d.size != self.n(self.L) ** 2:
+                raise ValueError("MGX_ERR_INVALID")
+            if self.d is None:
+                self.c0 = st[0]
+            self.d = d.reshape((self.n(self.L),) * 2)
+            st[0] = tr.shift([self.c0], self.d)[0]
+        self.h = None
+        self.transfer = None
+
+    def get_reaction(self):
+        self._reaction_guard()
+        if self.d is None:
+            raise RuntimeError("mgx_get_reaction: no zero-order term is set: MGX_ERR_STATE")
+        return self.d
+
+    # -- mgx_theta_steps ---------------------------------------------------------------------------------------
+    def _step_solve(self, solver, tol, max_iters, restart, history=None, dot=None):
+        """the solver of a step from the current U: (stats, history)"""
+        dot = pcg_ref.dot if dot is None else dot
+        if solver == STEP_SOLVE:
+            return self.solve(tol=tol, max_cycles=max_iters)
+        if solver == STEP_GCR:
+            return self.solve_gcr(tol=tol, max_iters=max_iters, restart=restart, dot=dot)
+        return self.solve_refine_gcr(tol=tol, max_iters=max_iters, restart=restart, history=history, dot=dot)
+
+    @staticmethod
+    def _step_solver_check(solver, tol, max_iters, restart):
+        if solver not in (STEP_SOLVE, STEP_GCR, STEP_REFINE_GCR) or not tol >= 0.0 or max_iters < 0:
+            raise ValueError("MGX_ERR_INVALID")
+        if solver != STEP_SOLVE and not 1 <= restart <= 8:
+            raise ValueError("MGX_ERR_INVALID")
+
+    def _built_guard(self, solver):
+        if solver == STEP_REFINE_GCR:
+            self._refine_guard()
+        if self.h is None:
+            raise RuntimeError("Galerkin hierarchy not built: MGX_ERR_STATE")
+
+    def theta_steps(self, theta, nsteps, g=None, solver=STEP_SOLVE, tol=1e-8, max_iters=50, restart=4, histories=None, dot=None):
+        """mgx_theta_steps: (steps_done, [stats], [history]).  Per step theta_ref.rhs_pass from the model's own S u (minus
+        the residual of U against a zero right-hand side) into B of the finest level, then the model's solve, solve_gcr or
+        solve_refine_gcr from the current U; a step with converged = 0 is the last one; nsteps = 0 moves nothing.
+        histories: the per-step histories a device returned (the scales of solve_refine_gcr); dot: the Krylov solvers'
+        inner product"""
+        if not 0.0 < theta <= 1.0 or nsteps < 0:
+            raise ValueError("MGX_ERR_INVALID")
+        self._step_solver_check(solver, tol, max_iters, restart)
+        self._reaction_guard()
+        if self.d is None:
+            raise RuntimeError("mgx_theta_steps: no zero-order term is set: MGX_ERR_STATE")
+        self._built_guard(solver)
+        L = self.L
+        stats, hists = [], []
+        for k in range(nsteps):
+            u = self.U[L]
+            Su = None if float(theta) == 1.0 else -self.h.residual(L, u, np.zeros_like(u))
+            self.B[L] = np.ascontiguousarray(tr.rhs_pass(Su, u, self.d, g, theta), dtype=self.dt)
+            st, h = self._step_solve(solver, tol, max_iters, restart, None if histories is None or k >= len(histories) else histories[k], dot)
+            stats.append(st)
+            hists.append(h)
+            if not st["converged"]:
+                break
+        return len(stats), stats, hists
+
+    def time_theta_rhs(self, theta, repeats):
+        """mgx_time_theta_rhs: nothing moves (the pass writes the finest R); refused while no term is set"""
+        if repeats < 1 or not 0.0 < theta <= 1.0:
+            raise ValueError("MGX_ERR_INVALID")
+        self._reaction_guard()
+        if self.d is None:
+            raise RuntimeError("mgx_time_theta_rhs: no zero-order term is set: MGX_ERR_STATE")
+
+    # -- mgx_newton / mgx_newton_steps -------------------------------------------------------------------------
+    def _newton_check(self, p, solver, lin_tol, lin_max_iters, restart, tol, max_newton, max_backtracks):
+        if not all(np.isfinite(float(x)) for x in p):
+            raise ValueError("MGX_ERR_INVALID")
+        self._step_solver_check(solver, lin_tol, lin_max_iters, restart)
+        if not tol >= 0.0 or max_newton < 0 or not 0 <= max_backtracks <= 30:
+            raise ValueError("MGX_ERR_INVALID")
+
+    def _grid(self, a):
+        if a is None:
+            raise ValueError("MGX_ERR_INVALID")
+        a = np.array(a, dtype=self.wdt, order="C")
+        if a.size != self.n(self.L) ** 2:
+            raise ValueError("MGX_ERR_INVALID")
+        return a.reshape((self.n(self.L),) * 2)
+
+    def _newton_parts(self, solver, lin_tol, lin_max_iters, restart, dot):
+        """(solve, norm) for newton_ref.newton's loop on this handle: the linear solve is set_reaction(d), build_galerkin
+        with the transfer in use, set_rhs(b), a zero U and the chosen solver; the norm is residual_norm of (B = b, U = 0)"""
+        L, transfer = self.L, self.transfer
+        self.norms, self.lin = [], []
+
+        def solve(S9, b, d, k):
+            self.set_reaction(d)
+            self.build_galerkin(transfer)
+            self.set_rhs(b)
+            self.zero_level(L, 0)
+            rec = self._step_solve(solver, lin_tol, lin_max_iters, restart, None, dot)
+            self.lin.append(rec)
+            return self.U[L], rec
+
+        def norm(b):
+            b = np.ascontiguousarray(b, dtype=self.dt)
+            r = self.po.norm2(self._ops().residual(L, np.zeros_like(b), b))
+            self.norms.append(r)
+            return r
+
+        return solve, norm
+
+    @staticmethod
+    def _newton_stats(o):
+        return dict(iterations=len(o["hist"]) - 1, converged=int(o["converged"]), backtracks=o["backtracks"],
+                    linear_iterations=sum(rec[0]["cycles"] for rec in o["lin"]), failed=o["failed"])
+
+    def newton(self, kappa, p=(0.0, 0.0, 1.0), solver=STEP_SOLVE, lin_tol=1e-8, lin_max_iters=50, restart=4, tol=1e-10, max_newton=20,
+               max_backtracks=8, dot=None):
+        """mgx_newton: (stats, history, [(stats, history) of every linear solve], step lengths) - newton_ref.newton's
+        loop with A0 = base_operator() (a caller's term is not part of F), f = B and the guess = U of the finest level.
+        Afterwards U is the last accepted iterate and B the caller's f; when an iteration ran, the operator is A0 + diag(d_k)
+        of the last linear solve with its hierarchy built and the coarse levels hold what that solve left; when none
+        ran, nothing has moved.  A failed line search: stats["failed"], converged = 0"""
+        self._newton_check(p, solver, lin_tol, lin_max_iters, restart, tol, max_newton, max_backtracks)
+        kap = self._grid(kappa)
+        self._reaction_guard()
+        self._built_guard(solver)
+        self.nwt = True
+        L = self.L
+        f = self.B[L]
+        solve, norm = self._newton_parts(solver, lin_tol, lin_max_iters, restart, dot)
+        o = nf.newton(self.base_operator(), kap, f, p, self.U[L], solve, tol, max_newton, max_backtracks, norm)
+        self.U[L] = np.ascontiguousarray(o["u"], dtype=self.dt)
+        self.B[L] = f
+        return self._newton_stats(o), o["hist"], o["lin"], o["lam"]
+
+    def newton_steps(self, theta, nsteps, mass, kappa, g=None, p=(0.0, 0.0, 1.0), solver=STEP_SOLVE, lin_tol=1e-8, lin_max_iters=50,
+                     restart=4, tol=1e-8, max_newton=20, max_backtracks=8, dot=None):
+        """mgx_newton_steps: (steps_done, [stats], [history]) - newton_steps_ref.steps with newton()'s linear solve and
+        norm.  Afterwards U is the last time level and B the last step's r; the operator as after newton(); a step that does
+        not converge is the last one; nsteps = 0 touches nothing, the workspace included"""
+        self._newton_check(p, solver, lin_tol, lin_max_iters, restart, tol, max_newton, max_backtracks)
+        if not 0.0 < theta <= 1.0 or nsteps < 0:
+            raise ValueError("MGX_ERR_INVALID")
+        dm, kap = self._grid(mass), self._grid(kappa)
+        self._reaction_guard()
+        self._built_guard(solver)
+        if nsteps == 0:
+            return 0, [], []
+        self.nwt = self.nwt_mass = True
+        L = self.L
+        solve, norm = self._newton_parts(solver, lin_tol, lin_max_iters, restart, dot)
+        out = nsr.steps(self.base_operator(), kap, dm, None if g is None else self._grid(g), p, self.U[L], theta, nsteps, solve, tol,
+                        max_newton, max_backtracks, norm)
+        self.U[L] = np.ascontiguousarray(out[-1]["u"], dtype=self.dt)
+        self.B[L] = np.ascontiguousarray(out[-1]["r"], dtype=self.dt)
+        return len(out), [self._newton_stats(o) for o in out], [o["hist"] for o in out]
+
+    def time_newton_pass(self, step, repeats):
+        """mgx_time_newton_pass: nothing moves (the pass writes the finest R, the trial and the next d of the workspace);
+        refused until a newton or a newton_steps call has allocated the workspace"""
+        if step not in (0, 1) or repeats < 1:
+            raise ValueError("MGX_ERR_INVALID")
+        self._reaction_guard()
+        if not self.nwt:
+            raise RuntimeError("mgx_time_newton_pass: call mgx_newton first: MGX_ERR_STATE")
+
+    def time_newton_step_pass(self, which, theta, repeats):
+        """mgx_time_newton_step_pass: nothing moves; refused until a newton_steps call has allocated the mass grid"""
+        if which not in (0, 1, 2) or repeats < 1 or not 0.0 < theta <= 1.0:
+            raise ValueError("MGX_ERR_INVALID")
+        self._reaction_guard()
+        if not self.nwt_mass:
+            raise RuntimeError("mgx_time_newton_step_pass: call mgx_newton_steps first: MGX_ERR_STATE")

@@ -159,11 +159,16 @@ The other calls there: history of solve / solve_pcg / solve_gcr / solve_refine a
 state after solve_pcg / solve_gcr at most 3.3e-5 / 3.6e-4 of RTOL64.  The runs under MGX_SMALL_VISIT=0 and MGX_GRAPH=0 give the same
 figures to the digit.
 
+The zero-order term, the theta steps and Newton (mgx_set_reaction, mgx_theta_steps, mgx_newton, mgx_newton_steps and their timing
+entry points) are drawn, run and described in tests/test_gpu_handle_newton.py; apply_device, apply_model and step know their
+calls (apply_model_steps, step_checks), and the committed seeds of this file draw none of them.
+
 A failing sequence is reproduced from the seed, the step index and the calls so far, which the message carries."""
 import numpy as np
 import pytest
 
 import handle_model as hm
+import newton_ref as nf
 import nine_ref as nr
 from refine_gcr_ref import device_dot
 from test_gpu_colour import random5
@@ -623,8 +628,44 @@ def stencil9(L, kind, dt, device):
     return hm.operator9(L, kind, dt)
 
 
-def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
-    """transfer: what a GALERKIN set_operator rebuilds with (the model's transfer in use).
+# the zero-order term, the theta steps and Newton (tests/test_gpu_handle_newton.py draws them; reaction_stage there)
+STEP_CALLS = ("theta_steps", "newton", "newton_steps")            # the calls that run a solver per step inside
+STEP_TIMING = ("time_theta_rhs", "time_newton_pass", "time_newton_step_pass")
+STEP_MASS = 0.5                                # mass = rho h^2 / (theta dt) of every ("newton_steps", ...), a constant grid
+
+
+def reaction_term(c0, seed):
+    """d of ("set_reaction", seed) for the base centre c0: between 0.05 and 0.25 of c0, moved so that c0 + d (one rounding in
+    double: the centre as a double handle stores it) lies 2^-10 of a float32 spacing beside the middle of two neighbouring
+    float32 values, on a random side.  float32 of the stored centre falls to that side; float32(c0) + float32(d), summed in
+    float, falls where the float32 rounding of d - some 2^-4 of that spacing - puts it: a float copy of the hierarchy
+    assembled from the parts instead of the stored centre differs at about half of the points"""
+    rng = np.random.RandomState(seed)
+    c0 = np.asarray(c0, dtype=np.float64)
+    s = c0 * (1.05 + 0.2 * rng.uniform(0.0, 1.0, c0.shape))
+    lo = s.astype(np.float32)
+    hi = np.nextafter(lo, np.float32(np.inf))
+    gap = hi.astype(np.float64) - lo.astype(np.float64)
+    side = np.where(rng.uniform(0.0, 1.0, c0.shape) < 0.5, -1.0, 1.0)
+    target = 0.5 * (lo.astype(np.float64) + hi.astype(np.float64)) + side * gap * 2.0 ** -10
+    return target - c0
+
+
+def newton_problem(L, name, dt):
+    """(kappa, p) of ("newton", name, ...): "cubic" kappa = 50 / N^2, phi = u + u^3 (every Newton step from a random
+    guess passes the Armijo test with a margin above 0.9: tests/test_handle_model_newton.py asserts it on the committed
+    lists); "backtracking" newton_ref.backtracking_input, whose first full step overshoots"""
+    n, N = (1 << L) - 1, 1 << L
+    if name == "backtracking":
+        _, kap, _, p, _ = nf.backtracking_input(L, dt)
+        return kap, p
+    assert name == "cubic", name
+    return np.full((n, n), 50.0 / N ** 2, dtype=dt), (1.0, 0.0, 1.0)
+
+
+def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR, model=None):
+    """transfer: what a GALERKIN set_operator rebuilds with (the model's transfer in use).  model: the model BEFORE the call
+    (("set_reaction", seed) places its term beside the base centre, which the model knows).
     The binding (multigrid_nikhil_c-_amd/binding.py) wraps the bare mgx_fmg, mgx_bottom_solve, mgx_residual,
     mgx_restrict*, mgx_prolong* only together with set_level calls, so those go to the C entry points through the
     wrapper's own handle and status check: Multigrid._h and Multigrid._chk - a rename there has to be followed here"""
@@ -644,7 +685,35 @@ def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
         return mg.solve_refine(tol=a[0], max_cycles=a[1])
     if name == "solve_refine_gcr":
         return mg.solve_refine_gcr(tol=a[0], max_iters=a[1], restart=a[2])
-    if name == "time_refine_pass":
+    dt = mg.level_dtype(L)
+    if name == "get_reaction":
+        return mg.reaction()
+    if name == "residual_norm":
+        return mg.residual_norm()
+    if name == "theta_steps":                              # (theta, nsteps, seed of g or None, solver, tol, max_iters, restart)
+        g = None if a[2] is None else field(mg.n(L), a[2])
+        return mg.theta_steps(a[1], theta=a[0], g=g, solver=a[3], tol=a[4], max_iters=a[5], restart=a[6])
+    if name == "newton":                                   # (problem, solver, lin_max_iters, restart, tol, max_newton, max_backtracks)
+        kap, p = newton_problem(L, a[0], dt)
+        return mg.newton(kap, p=p, solver=a[1], lin_tol=0.0, lin_max_iters=a[2], restart=a[3], tol=a[4], max_newton=a[5], max_backtracks=a[6])
+    if name == "newton_steps":                             # (theta, nsteps, seed of g or None, solver, lin_max_iters, restart, tol, max_newton, max_backtracks)
+        kap, p = newton_problem(L, "cubic", dt)
+        g = None if a[2] is None else field(mg.n(L), a[2])
+        return mg.newton_steps(a[1], np.full_like(kap, STEP_MASS), kap, p=p, theta=a[0], g=g, solver=a[3], lin_tol=0.0, lin_max_iters=a[4],
+                               restart=a[5], tol=a[6], max_newton=a[7], max_backtracks=a[8])
+    if name == "set_reaction":
+        mg.set_reaction(None if a[0] is None else reaction_term(model.base_operator()[0], a[0]))
+    elif name == "set_newton_data":                        # U and B of newton_ref.backtracking_input
+        _, _, f, _, u0 = nf.backtracking_input(L, dt)
+        mg.set_guess(u0)
+        mg.set_rhs(f)
+    elif name == "time_theta_rhs":
+        assert mg.time_theta_rhs(a[0], 2) > 0.0
+    elif name == "time_newton_pass":
+        assert mg.time_newton_pass(a[0], 2) > 0.0
+    elif name == "time_newton_step_pass":
+        assert mg.time_newton_step_pass(a[0], a[1], 2) > 0.0
+    elif name == "time_refine_pass":
         assert mg.time_refine_pass(a[0]) > 0.0
     elif name == "time_refine_gcr_pass":
         assert mg.time_refine_gcr_pass(a[0], a[1]) > 0.0
@@ -703,6 +772,123 @@ def apply_device(pkg, mg, call, L, transfer=hm.BILINEAR):
     return None
 
 
+def inner_solver(call):
+    """the solver (hm.STEP_*) a theta_steps / newton / newton_steps call runs inside; None for every other call"""
+    return call[{"theta_steps": 4, "newton": 2, "newton_steps": 4}[call[0]]] if call[0] in STEP_CALLS else None
+
+
+def apply_model_steps(m, call, L, device=None, rows=0):
+    """mgx_set_reaction, mgx_theta_steps, mgx_newton, mgx_newton_steps and their timing entry points on the model.  Beside a
+    device a refining inner solver sums its dots in the device's order (device_dot), and theta_steps, which reports its
+    per-step histories, takes the scales from them, as apply_model does for solve_refine_gcr; mgx_newton and
+    mgx_newton_steps report no inner history: the model's own scales"""
+    name, a = call[0], call[1:]
+    refining = device is not None and inner_solver(call) == hm.STEP_REFINE_GCR
+    dot = (lambda p, q: device_dot(p, q, rows)) if refining else None
+    n = m.n(L)
+    if name == "set_reaction":
+        m.set_reaction(None if a[0] is None else reaction_term(m.base_operator()[0], a[0]))
+    elif name == "get_reaction":
+        return m.get_reaction()
+    elif name == "residual_norm":
+        return m.residual_norm()
+    elif name == "set_newton_data":
+        _, _, f, _, u0 = nf.backtracking_input(L, m.wdt)
+        m.set_guess(u0)
+        m.set_rhs(f)
+    elif name == "theta_steps":
+        g = None if a[2] is None else field(n, a[2])
+        return m.theta_steps(a[0], a[1], g, a[3], a[4], a[5], a[6], histories=device[2] if refining else None, dot=dot)
+    elif name == "newton":
+        kap, p = newton_problem(L, a[0], m.wdt)
+        return m.newton(kap, p=p, solver=a[1], lin_tol=0.0, lin_max_iters=a[2], restart=a[3], tol=a[4], max_newton=a[5], max_backtracks=a[6], dot=dot)
+    elif name == "newton_steps":
+        kap, p = newton_problem(L, "cubic", m.wdt)
+        g = None if a[2] is None else field(n, a[2])
+        return m.newton_steps(a[0], a[1], np.full_like(kap, STEP_MASS), kap, g, p=p, solver=a[3], lin_tol=0.0, lin_max_iters=a[4], restart=a[5],
+                              tol=a[6], max_newton=a[7], max_backtracks=a[8], dot=dot)
+    elif name == "time_theta_rhs":
+        m.time_theta_rhs(a[0], 2)
+    elif name == "time_newton_pass":
+        m.time_newton_pass(a[0], 2)
+    elif name == "time_newton_step_pass":
+        m.time_newton_step_pass(a[0], a[1], 2)
+    else:
+        raise AssertionError(name)
+    return None
+
+
+def step_checks(pkg, mg, m, cfg, call, got, want, tally, where, g_before, h_before):
+    """what step() holds after a call of the zero-order term, the theta steps and Newton, beside U and B of every level:
+    steps_done, every statistic, the step lengths and the backtracks equal; the histories as the solver inside is held
+    (history_check: mgx_solve's bound for MGX_STEP_SOLVE and for the Newton norms around it, the Krylov bound otherwise); the
+    operator as stored and the term bit for bit (mgx_get_stencil[9] slot 0, mgx_get_reaction) - after a Newton call with a
+    Krylov solver inside to the state bound, after which the model takes the device's term over and rebuilds; a call that
+    the model says moves nothing leaves graphs_cached() alone.  h_before: the model's hierarchy before the call"""
+    name, a = call[0], call[1:]
+    L = cfg["finest_level"]
+    f64 = cfg.get("dtype", hm.F64) == hm.F64
+    inner = inner_solver(call)
+    held_as = ("solve",) if inner in (None, hm.STEP_SOLVE) else ("solve_gcr",)
+    label = name if inner is None else f"{name}/{('solve', 'gcr', 'refine_gcr')[inner]}"
+
+    def hist(h, ref):
+        tally.histories.append(np.array(h))
+        ok, frac = history_check(cfg, held_as, h, ref)
+        tally.steps_hist[label] = max(tally.steps_hist.get(label, 0.0), frac if np.isfinite(frac) else 0.0)
+        assert ok, f"history {frac:.3g} x its bound: {h} vs {ref}; {where()}"
+
+    def same(st, st_m, fields):
+        have = tuple(getattr(st, k) for k in fields)
+        assert have == tuple(st_m[k] for k in fields), f"stats {have} vs {st_m}; {where()}"
+
+    if name == "get_reaction":
+        assert np.array_equal(got, want), where()
+    elif name == "residual_norm":
+        frac = abs(got - want) / ((HIST_TOL if f64 else NORM32) * want)
+        tally.steps_hist[name] = max(tally.steps_hist.get(name, 0.0), frac)
+        assert frac <= 1.0, f"residual norm {got!r} vs {want!r}: {frac:.3g} x its bound; {where()}"
+    elif name == "theta_steps":
+        (done, sts, hs), (done_m, sts_m, hs_m) = got, want
+        assert done == done_m, f"steps_done {done} vs {done_m}; {where()}"
+        for k in range(done):
+            hist(hs[k], hs_m[k])
+            same(sts[k], sts_m[k], ("cycles", "converged", "fine_updates"))
+    elif name == "newton":
+        (ns, h, lin, lam), (st_m, h_m, lin_m, lam_m) = got, want
+        same(ns, st_m, ("iterations", "converged", "backtracks", "linear_iterations"))
+        assert np.array_equal(lam, lam_m), f"step lengths {lam} vs {lam_m}; {where()}"
+        hist(h, h_m)
+        assert len(lin) == len(lin_m), where()
+        for st, (st_lin, _) in zip(lin, lin_m):
+            same(st, st_lin, ("cycles", "converged", "fine_updates"))
+    elif name == "newton_steps":
+        (done, sts, hs), (done_m, sts_m, hs_m) = got, want
+        assert done == done_m, f"steps_done {done} vs {done_m}; {where()}"
+        for k in range(done):
+            same(sts[k], sts_m[k], ("iterations", "converged", "backtracks", "linear_iterations"))
+            hist(hs[k], hs_m[k])
+    # the operator as stored (mgx_get_stencil9 waits for the build: a nine-point level is read after it), and the term
+    slot0 = mg.get_stencil(L, 0) if m.st9 is None else (mg.get_stencil9(L, 0) if m.h is not None else m.st9[0])
+    if m.d is None:
+        with pytest.raises(pkg.MgxError, match="no zero-order term"):
+            mg.reaction()
+    else:
+        d = mg.reaction()
+        if name in ("newton", "newton_steps") and inner != hm.STEP_SOLVE and m.h is not h_before:
+            rtol = state_tolerance(cfg, call)
+            dev = float(np.max(np.abs(d.astype(np.float64) - m.d.astype(np.float64)))) / float(np.max(np.abs(m.d)))
+            tally.steps_state[label] = max(tally.steps_state.get(label, 0.0), dev / rtol)
+            assert dev <= rtol, f"the term off by {dev:.3g} (bound {rtol:g}); {where()}"
+            transfer = m.transfer
+            m.set_reaction(d)
+            m.build_galerkin(transfer)
+        assert np.array_equal(d, m.d), f"the term differs at {int(np.sum(d != m.d))} points; {where()}"
+    assert np.array_equal(slot0, m._finest()[0]), f"slot 0 of the finest operator differs at {int(np.sum(slot0 != m._finest()[0]))} points; {where()}"
+    if m.h is h_before and name != "build_galerkin" and (name in STEP_TIMING or name in ("set_reaction", "get_reaction", "residual_norm", "newton", "newton_steps")):
+        assert mg.graphs_cached() == g_before, f"graphs {g_before} -> {mg.graphs_cached()} over a call that moves nothing; {where()}"
+
+
 def apply_model(m, call, L, device=None, rows=0):
     """device: what apply_device returned for this call.  solve_refine takes its scales s_k from the history the device
     reported (a norm is the one place where the device's order of summation reaches the iterate), as
@@ -717,6 +903,8 @@ def apply_model(m, call, L, device=None, rows=0):
         if device is None:
             return m.solve_refine_gcr(tol=a[0], max_iters=a[1], restart=a[2])
         return m.solve_refine_gcr(tol=a[0], max_iters=a[1], restart=a[2], history=device[1], dot=lambda p, q: device_dot(p, q, rows))
+    if name in STEP_CALLS or name in STEP_TIMING or name in ("set_reaction", "get_reaction", "set_newton_data", "residual_norm"):
+        return apply_model_steps(m, call, L, device, rows)
     if name == "solve":
         return m.solve(tol=a[0], max_cycles=a[1])
     if name == "solve_pcg":
@@ -754,6 +942,8 @@ def state_tolerance(cfg, call):
         return RTOL64 if f64 else PCG32_STATE
     if name == "solve_refine_gcr":                          # (F64 handles only; U of the finest level: touched)
         return RTOL64
+    if name in STEP_CALLS:                                  # the solver inside: mgx_solve bit for bit, the Krylov solvers as themselves
+        return 0.0 if inner_solver(call) == hm.STEP_SOLVE else (RTOL64 if f64 else PCG32_STATE)
     sine_bottom = cfg.get("op", hm.POISSON) == hm.POISSON and cfg.get("bottom", hm.EXACT) == hm.EXACT
     if not sine_bottom:
         return 0.0
@@ -771,6 +961,13 @@ def touched(cfg, call):
         return {(call[1], "U")} if call[2] else set()
     if name == "solve_refine_gcr":                          # the iterate alone: B holds the residual during the solve and the caller's
         return {(L, "U")}                                   # b again after it, the cycle runs in the float copy - bit for bit
+    if name in STEP_CALLS:
+        # a Krylov solver inside: what it writes, and B of the finest level where a later step forms it from an iterate
+        # held to the bound (mgx_newton puts the caller's f back: bit for bit)
+        out = {(L, "U")} | (set() if name == "newton" else {(L, "B")})
+        if inner_solver(call) == hm.STEP_REFINE_GCR:
+            return out
+        return out | {(lv, x) for lv in range(Lc, L) for x in ("U", "B")}
     top =call[1] if name == "vcycle" else L                # vcycle_zero, fmg, solve, solve_pcg, solve_gcr: from the finest level
     return {(top, "U")} | {(lv, x) for lv in range(Lc, top) for x in ("U", "B")}
 
@@ -802,6 +999,8 @@ class Tally:
         self.graph_counts = []
         self.histories = []                                # of the device, in call order
         self.final = None                                  # U and B of every level after the last call
+        self.steps_hist = {}                               # theta_steps / newton / newton_steps by solver inside: largest history deviation / bound
+        self.steps_state = {}                              # ... largest deviation of a written array or the term / bound (Krylov solvers inside)
         self.bound = 0.0                                   # line cases: the largest bound of the tolerance rule used
         self.ratio = 0.0                                   # ... and the largest device deviation / its bound
 
@@ -810,8 +1009,8 @@ def step(pkg, mg, m, cfg, call, tally, where, rows=0):
     """one call on both sides, then every level's U and B, the history and the statistics.  rows: MGX_ROWS of the
     environment the handle was created under (apply_model)"""
     L, Lc = cfg["finest_level"], cfg["coarsest_level"]
-    g_before = mg.graphs_cached()
-    got = apply_device(pkg, mg, call, L, hm.BILINEAR if m.transfer is None else m.transfer)
+    g_before, h_before = mg.graphs_cached(), m.h
+    got = apply_device(pkg, mg, call, L, hm.BILINEAR if m.transfer is None else m.transfer, m)
     want = apply_model(m, call, L, got, rows)
     tally.executed += 1
     if call[0] == "set_cycle":                             # the graph key carries no kind: the setter has to drop the graphs
@@ -827,6 +1026,9 @@ def step(pkg, mg, m, cfg, call, tally, where, rows=0):
             f"stats {(st.cycles, st.converged, st.fine_updates)} vs {st_m}; {where()}"
     elif call[0] == "residual":
         assert np.array_equal(got, want), f"R of level {call[1]}; {where()}"
+    elif call[0] in STEP_CALLS or call[0] in STEP_TIMING or call[0] in ("set_reaction", "get_reaction", "residual_norm") or \
+            (call[0] == "build_galerkin" and m.d is not None):     # (a build under a term: the shifted centre went into the hierarchy)
+        step_checks(pkg, mg, m, cfg, call, got, want, tally, where, g_before, h_before)
     rtol = state_tolerance(cfg, call)
     loose = touched(cfg, call) if rtol else set()
     for lv in range(Lc, L + 1):
@@ -846,6 +1048,9 @@ def step(pkg, mg, m, cfg, call, tally, where, rows=0):
                     tally.state_gcr = max(tally.state_gcr, dev)
                 elif call[0] == "solve_refine_gcr":
                     tally.state_refine_gcr = max(tally.state_refine_gcr, dev)
+                elif call[0] in STEP_CALLS:
+                    label = f"{call[0]}/{('solve', 'gcr', 'refine_gcr')[inner_solver(call)]}"
+                    tally.steps_state[label] = max(tally.steps_state.get(label, 0.0), dev / rtol)
                 else:
                     tally.state = max(tally.state, dev)
                 assert dev <= rtol, f"{name} of level {lv} off by {dev:.3g} (bound {rtol:g}); {where()}"
@@ -880,6 +1085,9 @@ def run_sequence(pkg, po, cfg, calls, seed, env=None):
           f"state_dev_pcg={tally.state_pcg:.3g} ({tally.state_pcg / krylov_bound:.3g}xbound) state_dev_gcr={tally.state_gcr:.3g} "
           f"({tally.state_gcr / krylov_bound:.3g}xbound) state_dev_refine_gcr={tally.state_refine_gcr:.3g} "
           f"({tally.state_refine_gcr / RTOL64:.3g}xbound) graphs={tally.graph_counts}")
+    if tally.steps_hist or tally.steps_state:
+        print(f"[handle-state] steps: history / bound {({k: float(f'{v:.3g}') for k, v in sorted(tally.steps_hist.items())})} "
+              f"written state / bound {({k: float(f'{v:.3g}') for k, v in sorted(tally.steps_state.items())})}")
     return tally
 
 
