@@ -865,6 +865,78 @@ MGX_API int mgx_newton_steps(mgx_handle h, const mgx_newton_opts* opt, double th
                              const void* kappa, const void* g, size_t count, int* steps_done, mgx_newton_stats* step_stats,
                              double* history, int history_cap);
 
+/* ---- Picard and Newton multigrid for the quasilinear problem  -div(a(x) k(u) grad u) = f,  u = 0 on the boundary, on the
+ * device (csrc/mgx_quasi.hpp, csrc/mgx_quasi_host.hpp; absent in the reference) ---------------------------------------------
+ * Handles with op = MGX_OPERATOR_GALERKIN, on the finest level.  a_nodes is the nodal coefficient on the (N + 1)^2 nodes,
+ * N = 2^finest_level (host, double, row-major, boundary nodes included: the argument of mgx_set_coefficient);
+ * k(u) = k0 + k1 u + k2 u^2 with the three doubles as given; f the finest B at entry in stencil units, the guess the
+ * finest U at entry:  F(u) = A(u) u - f,  A(u) the five-point operator mgx_set_coefficient forms from the nodal a k(u).
+ * The pass (k_quasi_pass, one launch and one reduction).  All coefficient arithmetic is in double whatever T is, one
+ * rounding to T per coefficient; everything on u is in T; every product and sum rounded on its own.  At the interior
+ * point p and its neighbours x = N, S, W, E, the ring of v being zero:
+ *     v     = u                          the first evaluation
+ *     v     = u + lam * de               a trial: lam = 2^-j (rounded to T), de the linear solve's result
+ *     vd_x  = (double)v_x;   kap_x = a_x * ((k2 * vd_x + k1) * vd_x + k0)
+ *     fn    = 0.5 * (kap_p + kap_N), fs, fw, fe alike
+ *     cP    = (T)(((fn + fw) + fe) + fs);   nP = (T)(-fn), sP = (T)(-fs), wP = (T)(-fw), eP = (T)(-fe)
+ *     q     = cP, nP, sP, wP, eP applied to v in T: the sum of mgx_residual (CSR order N, W, C, E, S; ring-pointing
+ *             coefficients times the zero ring);   b_p = f_p - q
+ * and ||F(v)||_2 = sqrt(sum b_p^2), the sum formed as mgx_residual_norm forms it: bit for bit its value for B = b, U = 0.
+ * MGX_QUASI_PICARD: the operator of the next linear solve is (cP, nP, sP, wP, eP) = A(v).  MGX_QUASI_NEWTON: it is the
+ * Jacobian of F, five-point and not symmetric, with kk2 = 2.0 * k2 formed in double:
+ *     dk_x  = a_x * (kk2 * vd_x + k1);   gN = vd_p - vd_N, gS, gW, gE alike;   sg = ((gN + gW) + gE) + gS
+ *     cJ    = (T)((((fn + fw) + fe) + fs) + (0.5 * dk_p) * sg)
+ *     nJ    = (T)((0.5 * dk_N) * gN - fn), sJ, wJ, eJ alike
+ * (the residual uses the Picard coefficients either way).  Coefficients that point at the ring are stored as computed.
+ * The iteration, hist[0] = ||F(U)||, for k = 0 .. max_iters - 1 while !(hist[k] <= tol * hist[0]):
+ *     the finest operator becomes what the pass wrote for u_k (as mgx_set_stencil does) and the hierarchy is rebuilt with
+ *     opt.transfer;  B = b, U = 0, the chosen solver runs with lin_tol, lin_max_iters and restart (ignored for
+ *     MGX_STEP_SOLVE): lin_stats[k];  de = U;  trials lam = 1, 1/2, ... until
+ *         ||F(u + lam de)|| <= (1 - 1e-4 lam) hist[k]          (in double on the host; a NaN rejects)
+ *     at most max_backtracks halvings (0: every full step must pass the test);  u = u + lam de, hist[k + 1] = its norm,
+ *     step_lengths[k] = lam.  The accepted trial's pass output is the next iteration's operator and right-hand side.
+ * A linear solve that ends with converged = 0 (budget or breakdown) does not end the call: it is an inexact step that the
+ * line search guards, and lin_stats[k] reports it.  An error status of the solver ends the call with that status,
+ * mgx_last_error prefixed "mgx_quasi: step k:".  A failed line search ends the call with MGX_OK and converged = 0, U the
+ * last accepted iterate; mgx_last_error names the step, the smallest lam tried and the two norms.
+ * After every accepted step the iterate, hist, lin_stats (all but seconds), step_lengths and the backtrack count are bit
+ * for bit what the caller gets on the same handle from: the pass on the host; mgx_set_stencil(finest, the five grids);
+ * mgx_build_galerkin_transfer(transfer); mgx_set_rhs(b), a zero guess, the same solver call, mgx_get_solution; u + lam de
+ * on the host and its norm through mgx_residual_norm with B = the trial's b and U = 0.
+ * On return U holds the iterate and B the caller's f bit for bit.  The handle is in the state those mgx_set_stencil +
+ * build calls leave: the finest level is five-point whatever it was before, a zero-order term set earlier is dropped,
+ * and mgx_get_stencil / mgx_get_stencil9 return the operator of the last linear solve on every level (a rejected or a
+ * last accepted trial writes a second set of grids, never the operator).  When no iteration runs (max_iters = 0, or
+ * hist[0] <= tol * hist[0]) the operator, the hierarchy and the graphs are untouched.  The call needs no operator or
+ * hierarchy beforehand.  Positivity of a k(u) at every iterate, and for MGX_QUASI_NEWTON solvability of the Jacobian, are
+ * the caller's duty, as positivity of c0 + d is for mgx_newton.
+ * nstats may be NULL; lin_stats and step_lengths: NULL or max_iters entries; history: NULL or history_cap doubles, the
+ * first min(history_len, history_cap) are written.
+ * Workspace: eight finest-level grids (the iterate, the trial, f, the five coefficient grids of the next operator; b is
+ * the level's B) and the nodal a as doubles in the level's rows and pitch, allocated before anything is touched
+ * (MGX_ERR_ALLOC leaves the handle usable) and freed by mgx_destroy.
+ * MGX_ERR_INVALID, checked first and in this order: NULL handle or opt (outputs left alone), a k that is not finite,
+ * unknown method, unknown transfer, unknown solver, lin_tol not >= 0, lin_max_iters < 0, for the GCR solvers restart
+ * outside 1 .. MGX_GCR_MAX_RESTART, tol not >= 0, max_iters < 0, max_backtracks outside 0 .. 30, NULL a_nodes,
+ * count != (N + 1)^2.  MGX_ERR_STATE with the reason on POISSON, STENCIL5, multi-GPU and rank handles, and with
+ * MGX_STEP_REFINE_GCR wherever mgx_solve_refine_gcr returns it (F32 handles).  A refused call leaves the handle's bits
+ * alone.  Every smoother, cycle kind and bottom are accepted: the call runs the public solvers. */
+enum { MGX_QUASI_PICARD = 0, MGX_QUASI_NEWTON = 1 };
+typedef struct {
+    double k0, k1, k2;      /* k(u) = k0 + k1 u + k2 u^2 */
+    int method;             /* MGX_QUASI_PICARD = 0, MGX_QUASI_NEWTON = 1 */
+    int transfer;           /* MGX_TRANSFER_BILINEAR / MGX_TRANSFER_OPERATOR */
+    int solver;             /* MGX_STEP_SOLVE / MGX_STEP_GCR / MGX_STEP_REFINE_GCR (the enum of mgx_theta_steps) */
+    double lin_tol;         /* the linear solver's tol, ... */
+    int lin_max_iters;      /* ... max_iters ... */
+    int restart;            /* ... and restart (GCR solvers) */
+    double tol;             /* stop when ||F|| <= tol * ||F(guess)|| */
+    int max_iters;          /* at most this many nonlinear steps */
+    int max_backtracks;     /* halvings per step; 0: every full step must pass the test */
+} mgx_quasi_opts;
+MGX_API int mgx_quasi(mgx_handle h, const mgx_quasi_opts* opt, const double* a_nodes, size_t count, mgx_newton_stats* stats,
+                      mgx_stats* lin_stats, double* step_lengths, double* history, int history_cap);
+
 /* ---- measurement ------------------------------------------------------------ */
 enum {
     MGX_PROF_SMOOTH_FINE = 0,   /* finest-level smoother launches */
@@ -976,6 +1048,15 @@ MGX_API int mgx_time_newton_pass(mgx_handle h, int step, int repeats, double* ms
  * unchanged.  MGX_ERR_STATE where mgx_set_reaction returns it and until a mgx_newton_steps call has allocated the
  * workspace; MGX_ERR_INVALID for pass outside 0 .. 2, theta outside (0, 1], repeats < 1, NULL ms. */
 MGX_API int mgx_time_newton_step_pass(mgx_handle h, int pass, double theta, int repeats, double* ms);
+/* ms per launch of mgx_quasi's pass (with the reduction of its sums) on the handle's own buffers, `repeats` launches
+ * between two events (tools/quasi_bench.py; the yardstick is k_residual_var<T, 5, 0, 1> through mgx_residual in the same
+ * run): step = 0 times k_quasi_pass<T, false, NEWTON> (u, f and the nodal a in - a counts two words in float - five
+ * coefficients and b out), step = 1 <T, true, NEWTON> with lam = 1 (de in and the trial out as well); method selects NEWTON.
+ * It runs on the iterate, f, nodal a and k the last mgx_quasi call left and the current U as de, and writes b into the
+ * finest R, the trial iterate and the second set of coefficient grids: U, B, the iterate and the operator are unchanged.
+ * MGX_ERR_STATE where mgx_quasi returns it and until a mgx_quasi call has allocated the workspace; MGX_ERR_INVALID for
+ * step outside 0 .. 1, an unknown method, repeats < 1, NULL ms. */
+MGX_API int mgx_time_quasi_pass(mgx_handle h, int step, int method, int repeats, double* ms);
 MGX_API int mgx_synchronize(mgx_handle h);
 /* Number of hipGraphs mgx_solve has captured for its loop body ("one V-cycle +
  * residual norm", PS:727 run to a tolerance): 0 until the first graph cycle,

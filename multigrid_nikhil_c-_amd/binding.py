@@ -61,7 +61,10 @@ EXPORTS = [
     "mgx_eigs", "mgx_time_eig_pass", "mgx_eigs_many", "mgx_time_eig_project",
     "mgx_set_reaction", "mgx_get_reaction", "mgx_theta_steps", "mgx_time_theta_rhs",
     "mgx_newton", "mgx_time_newton_pass", "mgx_newton_steps", "mgx_time_newton_step_pass",
+    "mgx_quasi", "mgx_time_quasi_pass",
 ]
+QUASI_PICARD, QUASI_NEWTON = 0, 1                    # what the pass of quasi() writes: A(u) or the Jacobian of A(u) u - f
+QUASI_METHODS = {"picard": QUASI_PICARD, "newton": QUASI_NEWTON}
 STEP_SOLVE, STEP_GCR, STEP_REFINE_GCR = 0, 1, 2      # the solver of a theta step (theta_steps)
 STEP_SOLVERS = {"solve": STEP_SOLVE, "gcr": STEP_GCR, "refine_gcr": STEP_REFINE_GCR}
 EIG_PASS_GRAM, EIG_PASS_COMBINE, EIG_PASS_RESIDUAL, EIG_PASS_APPLY = 0, 1, 2, 3
@@ -100,6 +103,16 @@ class NewtonOpts(C.Structure):
         ("p1", C.c_double), ("p2", C.c_double), ("p3", C.c_double),
         ("solver", C.c_int), ("lin_tol", C.c_double), ("lin_max_iters", C.c_int), ("restart", C.c_int),
         ("tol", C.c_double), ("max_newton", C.c_int), ("max_backtracks", C.c_int),
+    ]
+
+
+class QuasiOpts(C.Structure):
+    """mgx_quasi_opts"""
+    _fields_ = [
+        ("k0", C.c_double), ("k1", C.c_double), ("k2", C.c_double),
+        ("method", C.c_int), ("transfer", C.c_int),
+        ("solver", C.c_int), ("lin_tol", C.c_double), ("lin_max_iters", C.c_int), ("restart", C.c_int),
+        ("tol", C.c_double), ("max_iters", C.c_int), ("max_backtracks", C.c_int),
     ]
 
 
@@ -271,6 +284,8 @@ def lib() -> C.CDLL:
     L.mgx_time_newton_pass.argtypes = [vp, C.c_int, C.c_int, dp]
     L.mgx_newton_steps.argtypes = [vp, C.POINTER(NewtonOpts), C.c_double, C.c_int, vp, vp, vp, C.c_size_t, ip, C.POINTER(NewtonStats), dp, C.c_int]
     L.mgx_time_newton_step_pass.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp]
+    L.mgx_quasi.argtypes = [vp, C.POINTER(QuasiOpts), vp, C.c_size_t, C.POINTER(NewtonStats), C.POINTER(Stats), dp, dp, C.c_int]
+    L.mgx_time_quasi_pass.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     _lib = L
     return L
 
@@ -577,6 +592,46 @@ class Multigrid:
         iterate and the operator unchanged; after a newton()"""
         ms = C.c_double()
         self._chk(lib().mgx_time_newton_pass(self._h, int(step), repeats, C.byref(ms)), "mgx_time_newton_pass")
+        return ms.value
+
+    def quasi(self, a_nodes, k, method="picard", solver="solve", transfer=TRANSFER_BILINEAR, lin_tol=1e-8, lin_max_iters=50, restart=4,
+              tol=1e-10, max_iters=20, max_backtracks=8):
+        """Picard or Newton multigrid for -div(a k(u) grad u) = f on the device (mgx_quasi): a_nodes the (N + 1)^2 nodal
+        values of a (set_coefficient's argument), k(u) = k[0] + k[1] u + k[2] u^2, f the current B, the guess the current U.
+        Every step makes the pass's five grids the finest operator - A(u) for method "picard", the Jacobian of A(u) u - f
+        for "newton" (or a QUASI_* value) - rebuilds the hierarchy with `transfer`, solves with solver "solve" | "gcr" |
+        "refine_gcr" (or a STEP_* value; lin_tol, lin_max_iters, restart) from a zero guess and backtracks on ||F|| (at
+        most max_backtracks halvings).  Returns (NewtonStats, history of ||F||, list of the linear solves' Stats, step
+        lengths); U holds the iterate (get_solution()), B the caller's f.  A failed line search returns converged = 0
+        (mgx_last_error names it)."""
+        a = np.ascontiguousarray(a_nodes, dtype=np.float64)
+        code = STEP_SOLVERS[solver] if isinstance(solver, str) else int(solver)
+        meth = QUASI_METHODS[method] if isinstance(method, str) else int(method)
+        o = QuasiOpts(float(k[0]), float(k[1]), float(k[2]), meth, int(transfer), code, lin_tol, lin_max_iters, restart, tol, max_iters,
+                      max_backtracks)
+        m = max(int(max_iters), 1)
+        st = (Stats * m)()
+        lam = np.zeros(m, dtype=np.float64)
+        hist = np.zeros(m + 1, dtype=np.float64)
+        ns = NewtonStats()
+        self._chk(lib().mgx_quasi(self._h, C.byref(o), a.ctypes.data, a.size, C.byref(ns), st, lam.ctypes.data_as(C.POINTER(C.c_double)),
+                                  hist.ctypes.data_as(C.POINTER(C.c_double)), m + 1), "mgx_quasi")
+        # one linear solve per accepted step, and one more when the call ended in a failed line search
+        failed = not ns.converged and ns.iterations < int(max_iters)
+        stats = []
+        for j in range(ns.iterations + (1 if failed else 0)):
+            one = Stats()
+            C.memmove(C.byref(one), C.byref(st[j]), C.sizeof(Stats))
+            stats.append(one)
+        return ns, hist[: ns.history_len].copy(), stats, lam[: ns.iterations].copy()
+
+    def time_quasi_pass(self, step, method="picard", repeats=20):
+        """ms per launch of quasi()'s pass (k_quasi_pass and the reduction of its sums) on the handle's own buffers: step 0
+        the first evaluation, 1 a trial with lam = 1 and the current U as de; b goes into the finest R, the coefficients
+        into the second set of grids: U, B, the iterate and the operator unchanged; after a quasi()"""
+        meth = QUASI_METHODS[method] if isinstance(method, str) else int(method)
+        ms = C.c_double()
+        self._chk(lib().mgx_time_quasi_pass(self._h, int(step), meth, repeats, C.byref(ms)), "mgx_time_quasi_pass")
         return ms.value
 
     def newton_steps(self, nsteps, mass, kappa, p=(0.0, 0.0, 1.0), theta=1.0, g=None, solver="solve", lin_tol=1e-8, lin_max_iters=50, restart=4,

@@ -42,6 +42,7 @@
 #include "mgx_eig_many.hpp"
 #include "mgx_theta.hpp"
 #include "mgx_newton.hpp"
+#include "mgx_quasi.hpp"
 #include "mgx_dist_plan.hpp"
 
 #include <chrono>
@@ -233,6 +234,16 @@ struct mgx_solver {
         void *un = nullptr, *ut = nullptr, *f = nullptr, *kap = nullptr, *dn = nullptr, *dm = nullptr, *g = nullptr;
         double p1 = 0.0, p2 = 0.0, p3 = 0.0;
     } nwt;
+    // mgx_quasi (mgx_quasi_host.hpp), grids of the finest level with ring and padding zero: the iterate un and the trial ut
+    // (swapped when a trial is accepted), the caller's f while B holds the step's right-hand side, the five coefficient
+    // grids A2 the pass writes (swapped with the level's A[0 .. 4] when an iteration makes them the operator), and the
+    // nodal coefficient an, doubles in the level's rows and pitch with the boundary nodes; k0 .. k2 of the last call for
+    // mgx_time_quasi_pass.  Allocated by the first mgx_quasi, kept until mgx_destroy
+    struct QuasiWs {
+        void *un = nullptr, *ut = nullptr, *f = nullptr, *A2[5] = {};
+        double* an = nullptr;
+        double k0 = 0.0, k1 = 0.0, k2 = 0.0;
+    } qsi;
 
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -1496,6 +1507,7 @@ static int create_solver(const mgx_config* cfg, const mgx_solver* like, mgx_hand
 #include "mgx_theta_host.hpp"
 #include "mgx_newton_host.hpp"
 #include "mgx_newton_steps_host.hpp"
+#include "mgx_quasi_host.hpp"
 
 // =====================================================================================
 // C-ABI
@@ -1736,6 +1748,7 @@ int mgx_destroy(mgx_handle s)
     eig_many_free(s->eigm);
     reaction_free(s->rx);
     newton_free(s->nwt);
+    quasi_free(s->qsi);
     drop_graphs(s);
     for (auto& p : s->ev_used) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : s->ev_free) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2820,6 +2833,35 @@ int mgx_time_newton_step_pass(mgx_handle s, int pass, double theta, int repeats,
 // =====================================================================================
 // slab-level operators on caller-owned device memory
 // =====================================================================================
+// ---- Picard and Newton multigrid for -div(a k(u) grad u) = f (mgx_quasi_host.hpp) --------------------------------------
+int mgx_quasi(mgx_handle s, const mgx_quasi_opts* o, const double* a_nodes, size_t count, mgx_newton_stats* nstats, mgx_stats* lin_stats,
+              double* step_lengths, double* history, int history_cap)
+{
+    if (!s || !o) return MGX_ERR_INVALID;
+    if (int rc = quasi_opts_check(s, o, "mgx_quasi")) return rc;
+    if (!a_nodes) return s->fail(MGX_ERR_INVALID, "mgx_quasi: a_nodes required");
+    const size_t nodes = ((size_t)1 << s->cfg.finest_level) + 1;
+    if (count != nodes * nodes) return s->fail(MGX_ERR_INVALID, "mgx_quasi: coefficient must hold (N + 1)^2 nodal values, N = 2^finest_level");
+    if (int rc = quasi_guard(s, "mgx_quasi")) return rc;
+    if (o->solver == MGX_STEP_REFINE_GCR)
+        if (int rc = refine_guard(s, "mgx_quasi: MGX_STEP_REFINE_GCR")) return rc;
+    return quasi(s, *o, a_nodes, nstats, lin_stats, step_lengths, history, history_cap);
+}
+
+int mgx_time_quasi_pass(mgx_handle s, int step, int method, int repeats, double* ms)
+{
+    if (!s) return MGX_ERR_INVALID;
+    if (!ms || repeats < 1 || step < 0 || step > 1 || (method != MGX_QUASI_PICARD && method != MGX_QUASI_NEWTON))
+        return s->fail(MGX_ERR_INVALID, "mgx_time_quasi_pass: step 0 or 1, method MGX_QUASI_PICARD or MGX_QUASI_NEWTON, repeats >= 1 and ms required");
+    if (int rc = quasi_guard(s, "mgx_time_quasi_pass")) return rc;
+    if (!s->qsi.an) return s->fail(MGX_ERR_STATE, "mgx_time_quasi_pass: call mgx_quasi first (it allocates the workspace)");
+    Level& l = s->lv[s->cfg.finest_level];
+    if (int rc = ensure_r(s, l)) return rc;
+    const int rc = time_on_stream(s, ms, [&] { for (int i = 0; i < repeats; ++i) (void)quasi_pass(s, step != 0, method == MGX_QUASI_NEWTON, 1.0, l.r, nullptr); });
+    if (rc == MGX_OK) *ms /= repeats;
+    return rc;
+}
+
 static int slab_check(const mgx_slab* s)
 {
     if (!s || s->level < 2 || s->level > 15 || s->rows < 1) return MGX_ERR_INVALID;

@@ -18,6 +18,7 @@
 //                      k_theta_rhs<T, 5, true>)
 //   -DMGX_INST_KIND=14 launch_newton_pass<T>, launch_newton_step_rhs<T>  (mgx_newton.hpp: k_newton_pass<T, 5 | 9, STEP, MASS> with both
 //                      flags false | true, k_newton_step_rhs<T, 5 | 9, false>, k_newton_step_rhs<T, 5, true>)
+//   -DMGX_INST_KIND=15 launch_quasi_pass<T>  (mgx_quasi.hpp: k_quasi_pass<T, STEP, NEWTON> with both flags false | true)
 //   -DMGX_INST_T=double|float   -DMGX_INST_SM=0|1   -DMGX_INST_AR=0|1
 #include "mgx_launch.hpp"
 #if MGX_INST_KIND == 4
@@ -42,6 +43,8 @@
 #include "mgx_theta.hpp"
 #elif MGX_INST_KIND == 14
 #include "mgx_newton.hpp"
+#elif MGX_INST_KIND == 15
+#include "mgx_quasi.hpp"
 #endif
 
 namespace mgx {
@@ -98,7 +101,10 @@ template void launch_newton_pass<T_>(const VarLevel<T_>&, bool, const T_*, const
                                      const NewtonPoly<T_>&, double*, double*, hipStream_t);
 template void launch_newton_step_rhs<T_>(const VarLevel<T_>&, const T_*, const T_*, const T_*, const T_*, const T_*, T_*, const NewtonPoly<T_>&,
                                          double, hipStream_t);
+#elif MGX_INST_KIND == 15
+template void launch_quasi_pass<T_>(int, int, long, bool, bool, const T_*, const T_*, const T_*, const double*, const Quasi5Out<T_>&, T_*, T_*,
+                                    const QuasiPoly<T_>&, double*, double*, hipStream_t);
 #else
-#error "MGX_INST_KIND must be 1 .. 14"
+#error "MGX_INST_KIND must be 1 .. 15"
 #endif
 } // namespace mgx
